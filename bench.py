@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the hot path (mask stack -> field -> marching cubes -> final mesh).
 
-    python bench.py --gpus N --steps K --warmup W [--workload default|cfg3|cfg4|cfg5]
+    python bench.py --gpus N --steps K --warmup W [--workload default|cfg3|cfg4|cfg5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts N rank processes itself (a fresh
@@ -14,14 +14,22 @@ One "step" = one pass of the whole hot path over one synthetic ellipsoid mask st
 
 Workloads (BASELINE.json configs; sizes are width x height x slices there, (nz, ny, nx) here):
   default  N = 1: cfg3 = the 1024^3 ellipsoid.  N > 1: Z-slabs of 1024 slices of 1024^2 per rank (WEAK scaling:
-           the N = 1 point is the BENCH line), halos over RCCL (tomography_3d_reconstructor_amd/slab.py) -- followed by a SECOND
-           timed block on BASELINE configs[4] (2048x2048x4096, STRONG: the stack north_star quotes "near-linear to 8 GPUs" on),
+           the N = 1 point is the BENCH line), halos over RCCL (tomography_3d_reconstructor_amd/slab.py) -- with --full followed
+           by a SECOND timed block on BASELINE configs[4] (2048x2048x4096, STRONG: the stack north_star quotes "near-linear to 8 GPUs" on),
            reported as `north_star_scaling` with the single-GPU time of the same stack measured on rank 0 in the same run
            (`per_rank_efficiency_vs_n1`); at N = 1 that block is the single-GPU time itself (`cfg5_single_ms_per_step`).
   cfg3     (1024, 1024, 1024) total      cfg4  (2048, 1024, 1024) total      cfg5  (4096, 2048, 2048) total
            -- a FIXED total volume cut into N Z-slabs (STRONG scaling; N = 1 runs the whole stack on one GPU).
 
-Every run checks its own result (`parity_in_run`): SHA-256 of the WHOLE vertex and face arrays -- a Z-slab job forms them rank
+A plain run sets up, warms up, times exactly K steps and prints its line: `value`, `ms_per_step` (one timed step), the roofline
+and pass floor of those steps and, for N > 1, `comm`.  `--full` adds everything else below -- the second (north-star) block, the
+side measurements (`cold_pass_ms`, `read_every_pass_ms_per_step`, `one_stream_ms_per_step`, `two_in_flight_ms_per_pass`,
+host to host), `cpu_baseline` and the parity check; a plain line says `parity_in_run: "not checked ..."`.
+`--dump-outputs DIR` writes the mesh the last timed step returned, DIR/vertices.npy (float32) and DIR/faces.npy (float64; a Z-slab
+job: vertices.rank<r>.npy / faces.rank<r>.npy per rank), each cut to a fixed seeded sample of its rows when the whole would pass
+64 MB in all (dump_outputs).  The input stack is the same synthetic ellipsoid in every run.
+
+A --full run checks its own result (`parity_in_run`): SHA-256 of the WHOLE vertex and face arrays -- a Z-slab job forms them rank
 after rank, nothing is gathered (SlabJob.mesh_sha256) -- against the committed fixture of the stack (tests/golden/
 ellipsoid_hashes.json: the REFERENCE's own output up to 1024^3; ellipsoid_hashes_oracle.json: the pinned oracle's for configs[3]
 and [4]); a distributed run on a stack without fixture is compared with a single-GPU pass of the same stack on rank 0.  A
@@ -33,12 +41,13 @@ Prints ONE JSON line (rank 0) with metric/value/unit..., plus
                  volume read) / measured kernel time (HIP events on the launch stream, inside the timed region) vs the 8 TB/s
                  HBM3E peak; `frac_survey` = the same with SURVEY 8(d)'s 5 B per padded voxel;
   pass_floor:    the whole pass against its own HBM floor (1 B mask in + 4 B field out per voxel);
+  comm (N > 1):  ranks / distinct devices seen by the process group, halo bytes and time per pass;
+and, with --full,
   cold_pass_ms, host_to_host_cold_ms / host_to_host_ms: one pass without the size hints of earlier passes; the three
                  drop-in class methods host list in -> host arrays out (PCIe inclusive), FIRST call of the process and warm
                  -- reported beside `value`, never as `value`;
   cpu_baseline:  the CPU oracle (a C/NumPy restatement of the reference) on the SAME 1024^3 stack, one thread, and
-                 (`all_cores`) on up to 16 host cores; timed before this process touches the GPU;
-  comm (N > 1):  ranks / distinct devices seen by the process group, halo bytes and time per pass.
+                 (`all_cores`) on up to 16 host cores; timed before this process touches the GPU.
 """
 import argparse
 import json
@@ -96,7 +105,17 @@ def parse(argv=None):
     ap.add_argument("--north-star-size", type=int, nargs=3, default=None, metavar=("NZ", "NY", "NX"),
                     help="total volume of that block instead of 4096 2048 2048 (rehearsals)")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port of a self-launched run (0: pick a free one)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements and checks: CPU baseline, cold pass / one-stream / two-in-flight / host-to-host "
+                         "extras, the in-run parity check and the north-star block (the --no-* options above switch them off again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the mesh of the last one as DIR/<name>.npy (float32 / float64, at most 64 MB: "
+                         "a fixed seeded sample of the rows of a larger array)")
+    args = ap.parse_args(argv)
+    if not args.full:
+        # a plain run measures the headline figure and nothing else
+        args.no_cpu_baseline = args.no_extras = args.no_parity = args.no_north_star = True
+    return args
 
 
 # ----------------------------------------------------------------------------- launch decision (no GPU, no torch)
@@ -498,6 +517,30 @@ def sha_mesh(v, f):
     return hv.hexdigest(), hf.hexdigest(), int(v.shape[0]), int(f.shape[0])
 
 
+DUMP_BYTES = 60 * 1000 * 1000        # --dump-outputs: array bytes in all (the .npy headers stay well inside 64 MB)
+
+
+def dump_outputs(outdir, arrays, budget=DUMP_BYTES, seed=0):
+    """--dump-outputs: {name: host array} -> outdir/<name>.npy, float32 as it is, anything else as float64 (exact for the
+    int64 face indices).  An array larger than its equal share of `budget` is cut to a fixed sample of its rows: `seed`ed,
+    in row order, the same rows for the same row count -- so two builds of the project can be compared output for output.
+    -> {name: rows written}."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    share = budget // max(len(arrays), 1)
+    written = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        dt = np.float32 if a.dtype == np.float32 else np.float64
+        row = np.dtype(dt).itemsize * int(np.prod(a.shape[1:], dtype=np.int64))
+        if a.ndim and a.shape[0] * row > share:
+            keep = np.sort(np.random.default_rng(seed).choice(a.shape[0], max(share // row, 1), replace=False))
+            a = a[keep]
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, dtype=dt))
+        written[name] = int(a.shape[0]) if a.ndim else 1
+    return written
+
+
 def field_pmc_for_this_build():
     """The committed counter bytes of the field kernel (separate rocprofv3 --pmc passes) -- usable only for the kernel they were
     measured on: the file names the SHA-256 of csrc/field.hip it was made with (a kernel change must not leave a
@@ -824,6 +867,12 @@ def run(args, world, cpu=None):
     # ------------------------------------------------------------------ the headline block
     blk = timed_block((gz, ny, nx), args.steps, args.warmup, True)
     workload, parallelism, job, res = blk["workload"], blk["parallelism"], blk["job"], blk["res"]
+    if args.dump_outputs and res is not None:
+        # the (vertices, faces) the last timed step handed back; a Z-slab job: this rank's part, one file pair per rank
+        sfx = ".rank%d" % rank if dist else ""
+        dump_outputs(args.dump_outputs, {"vertices" + sfx: res[0].cpu().numpy(), "faces" + sfx: res[1].cpu().numpy()},
+                     DUMP_BYTES // (world if dist else 1))
+        beat[0] = time.monotonic()
     if wname in CONFIG_INDEX and (gz, ny, nx) == WORKLOADS[wname]:
         workload += " (BASELINE configs[%d])" % CONFIG_INDEX[wname]
     total_voxels = gz * ny * nx
@@ -886,7 +935,7 @@ def run(args, world, cpu=None):
     # ------------------------------------------------------------------ is it the reference's mesh?  (every run says so itself)
     job = None                                        # (verify may have to free this rank's share of the job: no second reference to it)
     if args.no_parity:
-        parity = {"parity_in_run": "not checked (--no-parity)"}
+        parity = {"parity_in_run": "not checked (--no-parity)" if args.full else "not checked (plain run: --full checks it)"}
         nverts = nfaces = 0
         if res is not None:
             cnt = torch.tensor([int(res[0].shape[0]), int(res[1].shape[0])], dtype=torch.int64, device=rdev)

@@ -132,3 +132,39 @@ def test_cpu_baseline_all_core_leg_counts_like_the_one_thread_run():
     assert r["cores"] == 1 and r["kind"] == "port" and r["all_cores"]["cores"] == 3
     assert (r["all_cores"]["n_vertices"], r["all_cores"]["n_faces"]) == (r["n_vertices"], r["n_faces"]) and r["n_vertices"] > 0
     assert "counts equal to the one-thread run: True" in r["all_cores"]["sample"]
+
+
+def test_plain_run_measures_the_headline_only_and_full_keeps_the_rest():
+    """A plain run: no CPU baseline child, no side measurements, no parity check, no north-star block.  --full: all of them,
+    each still switched off by its own --no-* option."""
+    legs = ("no_cpu_baseline", "no_extras", "no_parity", "no_north_star")
+    plain = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not plain.full and all(getattr(plain, k) for k in legs) and (plain.steps, plain.warmup) == (7, 2)
+    assert plain.dump_outputs is None
+    full = bench.parse(["--full"])
+    assert full.full and not any(getattr(full, k) for k in legs)
+    part = bench.parse(["--full", "--no-cpu-baseline", "--dump-outputs", "out"])
+    assert part.no_cpu_baseline and not part.no_extras and not part.no_parity and part.dump_outputs == "out"
+
+
+def test_dump_outputs_dtypes_sample_and_size(tmp_path):
+    """bench.dump_outputs: float32 stays float32, integer arrays become float64 with their values; an array over its share of
+    the budget becomes a fixed sample of its rows (in row order, the same every time), so that the files stay inside it."""
+    import numpy as np
+    rng = np.random.default_rng(5)
+    v = rng.random((1000, 3), dtype=np.float32)
+    f = rng.integers(0, 1000, (2000, 3), dtype=np.int64)
+    assert bench.dump_outputs(str(tmp_path / "a"), {"vertices": v, "faces": f}) == {"vertices": 1000, "faces": 2000}
+    v2, f2 = np.load(tmp_path / "a" / "vertices.npy"), np.load(tmp_path / "a" / "faces.npy")
+    assert v2.dtype == np.float32 and np.array_equal(v2, v) and f2.dtype == np.float64 and np.array_equal(f2, f)
+    budget = 24000                                       # 12 000 bytes a name: 1 000 vertex rows, 500 face rows
+    for d in ("b", "c"):
+        assert bench.dump_outputs(str(tmp_path / d), {"vertices": v, "faces": f}, budget) == {"vertices": 1000, "faces": 500}
+    fb, fc = np.load(tmp_path / "b" / "faces.npy"), np.load(tmp_path / "c" / "faces.npy")
+    assert np.array_equal(fb, fc) and fb.shape == (500, 3)
+    rows = {tuple(r) for r in f.astype(np.float64)}
+    assert all(tuple(r) in rows for r in fb)
+    idx = [int(np.flatnonzero((f == r).all(axis=1))[0]) for r in fb.astype(np.int64)]
+    assert idx == sorted(idx)
+    assert sum(os.path.getsize(tmp_path / "b" / n) for n in os.listdir(tmp_path / "b")) < budget + 512
+    assert bench.DUMP_BYTES + 4 * 1024 <= 64 * 1000 * 1000

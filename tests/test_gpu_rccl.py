@@ -91,7 +91,7 @@ def _sha(t):
 
 @pytest.mark.parametrize("world,supervised,size,ns_size", [(2, True, (128, 256, 256), (64, 128, 128)), (3, False, (160, 96, 128), (96, 80, 112))])
 def test_rank_processes_over_gloo_give_the_single_gpu_mesh(world, supervised, size, ns_size):
-    """bench.py --gpus N --backend gloo: N rank PROCESSES sharing this GPU (three: a rank with BOTH neighbours), halos staged
+    """bench.py --full --gpus N --backend gloo: N rank PROCESSES sharing this GPU (three: a rank with BOTH neighbours), halos staged
     through the host -- the whole multi-rank code path of the bench (self-launch, process group, TorchDistComm, preflight,
     one-exchange front, deferred numbering, the SHA-256 chain over the ranks, the second block on the strong-scaling stack)
     except the transport.  The run checks ITSELF (`parity_in_run`): against the reference-derived fixture where the total stack
@@ -104,7 +104,7 @@ def test_rank_processes_over_gloo_give_the_single_gpu_mesh(world, supervised, si
     from tomography_3d_reconstructor_amd import pipeline
     nzr, ny, nx = size
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--backend", "gloo", "--size", str(nzr), str(ny), str(nx),
-           "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--north-star-size"] + [str(x) for x in ns_size]
+           "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--north-star-size"] + [str(x) for x in ns_size]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "TOMO_BENCH_WORKER")}
     # TOMO_BENCH_SUPERVISE=1: every rank process is a supervisor around a worker child, as under an `nccl` launch -- the real
     # process tree (self-launch -> torch.distributed.run -> rank supervisors -> workers), environment and output relayed
@@ -144,7 +144,7 @@ def test_rank_processes_over_gloo_give_the_single_gpu_mesh(world, supervised, si
 
 
 def test_a_run_whose_mesh_is_wrong_says_so_and_fails():
-    """parity_in_run is a CHECK: with a fixture that does not describe the stack (TOMO_BENCH_GOLDEN_OVERRIDE: a copy whose
+    """parity_in_run (--full) is a CHECK: with a fixture that does not describe the stack (TOMO_BENCH_GOLDEN_OVERRIDE: a copy whose
     face digest is wrong) the run prints parity_in_run false and leaves with a non-zero code."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
@@ -156,7 +156,7 @@ def test_a_run_whose_mesh_is_wrong_says_so_and_fails():
         json.dump(bad, fh)
     try:
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--size", "96", "80", "112", "--steps", "2", "--warmup", "1",
-               "--no-cpu-baseline", "--no-extras"]
+               "--full", "--no-cpu-baseline", "--no-extras"]
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=dict(os.environ, TOMO_BENCH_GOLDEN_OVERRIDE=fh.name))
         d = json.loads([x for x in p.stdout.splitlines() if x.startswith("{")][-1])
         assert p.returncode == 5 and d["parity_in_run"] is False and "PARITY FAILED" in p.stderr

@@ -15,5 +15,5 @@ rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o x -- $CMD > 
 # the same passes with every kernel on ONE stream: kernel durations without a neighbour on the second stream
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace1 -o x -- $CMD --one-stream > $OUT/bench_trace1.log 2>&1
 cd $ROOT
-python3 bench.py > $OUT/bench_plain.log 2>&1
+python3 bench.py --full > $OUT/bench_plain.log 2>&1
 python3 tools/profile_summary.py $OUT $TAG

@@ -64,7 +64,7 @@ json.dump(pmcj, open(os.path.join(out, "%s_field_pmc.json" % tag), "w"), indent=
 md = ["# Round profile `%s` -- `rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras`\n" % tag,
       "MI355X (gfx950), 1024^3 ellipsoid, 9 passes of the hot path (2 priming + 2 warm-up + 5 timed).  Full CSV: `%s_bench_kernel_stats.csv`.\n" % tag,
       "Bench line of the profiled run: `%s`\n" % last_json(os.path.join(out, "bench_trace.log")),
-      "Bench line, un-profiled (`python bench.py`): `%s`\n" % last_json(os.path.join(out, "bench_plain.log")),
+      "Bench line, un-profiled (`python bench.py --full`): `%s`\n" % last_json(os.path.join(out, "bench_plain.log")),
       "\n| kernel | calls | avg us | ms per pass | % |\n|---|---|---|---|---|"]
 for n, v in sorted(acc.items(), key=lambda kv: -sum(kv[1])):
     md.append("| `%s` | %d | %.2f | %.3f | %.2f |" % (n[:70], len(v), sum(v) / len(v), sum(v) / PASSES / 1e3, 100 * sum(v) / tot))

@@ -17,8 +17,8 @@ rocprofv3 --kernel-trace --output-format csv -d $R/$O/tr_cfg5 -o x -- python3 $R
 cd $R
 python tools/timeline.py $O/tr_1024 field_tile_kernel 6 > $O/timeline_1024.txt
 python tools/timeline.py $O/tr_cfg5 field_tile_kernel 5 > $O/timeline_cfg5.txt
-python bench.py --workload cfg4 --steps 10 --warmup 2 --no-cpu-baseline --no-extras > $O/bench_cfg4.json 2>/dev/null
-python bench.py --workload cfg5 --steps 5 --warmup 2 --no-cpu-baseline --no-extras > $O/bench_cfg5.json 2>/dev/null
-python bench.py --rehearse-dist --no-cpu-baseline --no-extras > $O/bench_rehearse.json 2>/dev/null || true
+python bench.py --workload cfg4 --steps 10 --warmup 2 --full --no-cpu-baseline --no-extras > $O/bench_cfg4.json 2>/dev/null
+python bench.py --workload cfg5 --steps 5 --warmup 2 --full --no-cpu-baseline --no-extras > $O/bench_cfg5.json 2>/dev/null
+python bench.py --rehearse-dist --full --no-cpu-baseline --no-extras > $O/bench_rehearse.json 2>/dev/null || true
 grep -h "ms per pass" $O/self*.log | cut -c1-420
 tail -1 gpurun_out/prof_r03/bench_plain.log | cut -c1-900
