@@ -115,6 +115,14 @@ SIGNATURES = {
     "tomo_mesh_faces": (_c_i, [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p]),
     "tomo_mesh_faces_direct": (_c_i, [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_p]),
     "tomo_mesh_volume_area": (_c_i, [_c_p, _c_p, _c_i64, _c_p, _c_p]),
+    "tomo_layer_colors": (_c_i, [_c_p, _c_i, _c_i64, _c_i64, _c_d, _c_d, _c_i, _c_d, _c_d, _c_i, _c_p, _c_p]),
+    "tomo_mesh_edge_table_bytes": (_c_i64, [_c_i64]),
+    "tomo_mesh_edges": (_c_i, [_c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_p]),
+    "tomo_mesh_orient_workspace_bytes": (_c_i64, [_c_i64]),
+    "tomo_mesh_orient": (_c_i, [_c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p]),
+    "tomo_mesh_signed_volume": (_c_i, [_c_p, _c_p, _c_i64, _c_p, _c_p, _c_p]),
+    "tomo_glb_pack_faces": (_c_i, [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_i, _c_p]),
+    "tomo_glb_pack_positions": (_c_i, [_c_p, _c_i, _c_i64, _c_p, _c_p, _c_p]),
 }
 
 _LIB = None

@@ -1,0 +1,409 @@
+// glb.hip -- the device half of the GLB export (glb_exporter.py of the reference, 52-91 and the trimesh calls of 26-49):
+// layer colours, the undirected edge table of a triangle mesh, face orientation (consistency check, then a union-find with
+// parity when the winding is not consistent), the signed volume after the per-face flips, and the packing of positions and
+// indices straight into the GLB binary chunk.  The orientation contract is written out in include/tomo_hip.h.
+#include "tomo_common.h"
+
+namespace {
+
+constexpr u64 EMPTY_KEY = ~0ULL;
+constexpr int BLOCK = 256;
+
+static inline unsigned grid_for(int64_t n, int64_t cap = 4096)
+{
+    int64_t b = ceil_div64(n > 0 ? n : 1, BLOCK);
+    return (unsigned)(b > cap ? cap : b);
+}
+
+// Table layout inside the caller's buffer: keys u64[cap] | count u32[cap] | entries u32[2 cap] (face << 1 | direction).
+// cap = the power of two >= max(1024, 2 * 3 nf): at most a quarter of the slots are ever taken on a closed mesh (every
+// undirected edge of a closed mesh is inserted twice).
+static inline int64_t table_cap(int64_t nf)
+{
+    int64_t want = 6 * nf, cap = 1024;
+    while (cap < want) cap <<= 1;
+    return cap;
+}
+static inline int64_t table_bytes(int64_t nf) { return table_cap(nf) * (8 + 4 + 8); }
+
+struct Table {
+    u64 *keys;
+    u32 *cnt;
+    u32 *ent;
+    int64_t cap;
+};
+
+static inline Table table_view(void *base, int64_t cap)
+{
+    char *p = (char *)base;
+    return Table{(u64 *)p, (u32 *)(p + 8 * cap), (u32 *)(p + 12 * cap), cap};
+}
+
+__device__ static inline u64 mix64(u64 k)
+{
+    k ^= k >> 33;
+    k *= 0xff51afd7ed558ccdULL;
+    k ^= k >> 33;
+    k *= 0xc4ceb9fe1a85ec53ULL;
+    k ^= k >> 33;
+    return k;
+}
+
+// one atomicAdd per wave of a per-lane count
+__device__ static inline void wave_add(unsigned long long *dst, u32 v)
+{
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+    if ((threadIdx.x & 63) == 0 && v) atomicAdd(dst, (unsigned long long)v);
+}
+
+// ---- layer colours (glb_exporter.py:52-91) ------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void layer_colors_kernel(const T *__restrict__ v, int64_t nv, int64_t stride, double s1,
+                                                              double e1, int en1, double s2, double e2, int en2,
+                                                              u32 *__restrict__ rgba)
+{
+    for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < nv; i += (int64_t)gridDim.x * BLOCK) {
+        const double z = (double)v[i * stride];
+        u32 c = 0xffc8c8c8u;                                       // 200, 200, 200, 255 (little endian RGBA)
+        if (en1 && z >= s1 && z <= e1) c = 0xff0000ffu;           // 255, 0, 0, 255
+        if (en2 && z >= s2 && z <= e2) c = 0xffff0000u;           // 0, 0, 255, 255: blue is applied after red
+        rgba[i] = c;
+    }
+}
+
+// ---- edge table ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(BLOCK) void edge_insert_kernel(const int64_t *__restrict__ faces, int64_t nf, int64_t nv, Table t,
+                                                             unsigned long long *__restrict__ counters)
+{
+    u32 bad = 0, degenerate = 0;
+    for (int64_t f = (int64_t)blockIdx.x * BLOCK + threadIdx.x; f < nf; f += (int64_t)gridDim.x * BLOCK) {
+        const int64_t a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
+        if (a < 0 || b < 0 || c < 0 || a >= nv || b >= nv || c >= nv) { bad++; continue; }
+        if (a == b || b == c || a == c) { degenerate++; continue; }
+        const int64_t from[3] = {a, b, c}, to[3] = {b, c, a};
+#pragma unroll
+        for (int e = 0; e < 3; e++) {
+            const u64 lo = (u64)(from[e] < to[e] ? from[e] : to[e]), hi = (u64)(from[e] < to[e] ? to[e] : from[e]);
+            const u64 key = (lo << 32) | hi;
+            const u32 dir = from[e] < to[e] ? 0u : 1u;
+            u64 s = mix64(key) & (u64)(t.cap - 1);
+            for (int64_t probe = 0; probe < t.cap; probe++) {
+                const u64 old = atomicCAS(&t.keys[s], EMPTY_KEY, key);
+                if (old == EMPTY_KEY || old == key) {
+                    const u32 k = atomicAdd(&t.cnt[s], 1u);
+                    if (k < 2) t.ent[2 * s + k] = ((u32)f << 1) | dir;
+                    break;
+                }
+                s = (s + 1) & (u64)(t.cap - 1);
+            }
+        }
+    }
+    wave_add(&counters[4], bad);
+    wave_add(&counters[5], degenerate);
+}
+
+__global__ __launch_bounds__(BLOCK) void edge_classify_kernel(Table t, unsigned long long *__restrict__ counters)
+{
+    u32 boundary = 0, manifold = 0, nonmanifold = 0, inconsistent = 0;
+    for (int64_t s = (int64_t)blockIdx.x * BLOCK + threadIdx.x; s < t.cap; s += (int64_t)gridDim.x * BLOCK) {
+        if (t.keys[s] == EMPTY_KEY) continue;
+        const u32 n = t.cnt[s];
+        if (n == 1) boundary++;
+        else if (n == 2) {
+            manifold++;
+            if (((t.ent[2 * s] ^ t.ent[2 * s + 1]) & 1u) == 0) inconsistent++;    // both faces run the edge the same way
+        } else nonmanifold++;
+    }
+    wave_add(&counters[0], boundary);
+    wave_add(&counters[1], manifold);
+    wave_add(&counters[2], nonmanifold);
+    wave_add(&counters[3], inconsistent);
+}
+
+// ---- union-find with parity ---------------------------------------------------------------------------------------------
+// uf[f] = parent << 1 | parity of f relative to its parent.  A root holds (f << 1 | 0).  Every link points from a larger
+// face index to a smaller one (hooking puts the larger root under the smaller; compression only moves a link further up
+// the same chain), so there are no cycles and each component's root is its lowest-index face.
+__device__ static inline u64 uf_load(const u64 *p)
+{
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// (root << 1 | parity of x relative to root); links x straight to the root it found (one 64-bit store: root and parity)
+__device__ static inline u64 uf_find(u64 *uf, u32 x)
+{
+    const u64 w = uf_load(uf + x);
+    const u32 p = (u32)(w >> 1);
+    if (p == x) return w;
+    u32 cur = p, par = (u32)(w & 1);
+    for (;;) {
+        const u64 wc = uf_load(uf + cur);
+        const u32 pc = (u32)(wc >> 1);
+        if (pc == cur) break;
+        par ^= (u32)(wc & 1);
+        cur = pc;
+    }
+    const u64 res = ((u64)cur << 1) | par;
+    if (cur != p) __hip_atomic_store(uf + x, res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // x is not a root: nobody hooks it
+    return res;
+}
+
+__global__ __launch_bounds__(BLOCK) void uf_init_kernel(u64 *__restrict__ uf, u32 *__restrict__ conflict, int64_t nf)
+{
+    for (int64_t f = (int64_t)blockIdx.x * BLOCK + threadIdx.x; f < nf; f += (int64_t)gridDim.x * BLOCK) {
+        uf[f] = (u64)f << 1;
+        conflict[f] = 0;
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void uf_union_kernel(Table t, u64 *uf)
+{
+    for (int64_t s = (int64_t)blockIdx.x * BLOCK + threadIdx.x; s < t.cap; s += (int64_t)gridDim.x * BLOCK) {
+        if (t.keys[s] == EMPTY_KEY || t.cnt[s] != 2) continue;
+        const u32 e0 = t.ent[2 * s], e1 = t.ent[2 * s + 1];
+        const u32 f = e0 >> 1, g = e1 >> 1;
+        if (f == g) continue;
+        const u32 r = ((e0 ^ e1) & 1u) ^ 1u;          // 1: the two faces must end up with opposite flips
+        for (;;) {
+            const u64 a = uf_find(uf, f), b = uf_find(uf, g);
+            const u32 ra = (u32)(a >> 1), rb = (u32)(b >> 1);
+            if (ra == rb) break;                       // same component: the verification pass judges this edge
+            const u32 p = (u32)((a ^ b) & 1) ^ r;
+            const u32 hi = ra > rb ? ra : rb, lo = ra > rb ? rb : ra;
+            const u64 expect = (u64)hi << 1;
+            if (atomicCAS((unsigned long long *)&uf[hi], (unsigned long long)expect, (unsigned long long)(((u64)lo << 1) | p)) == expect)
+                break;
+        }
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void uf_resolve_kernel(u64 *uf, int64_t nf, u32 *__restrict__ root, uint8_t *__restrict__ flip,
+                                                            unsigned long long *__restrict__ counts)
+{
+    u32 comps = 0;
+    for (int64_t f = (int64_t)blockIdx.x * BLOCK + threadIdx.x; f < nf; f += (int64_t)gridDim.x * BLOCK) {
+        const u64 w = uf_find(uf, (u32)f);
+        root[f] = (u32)(w >> 1);
+        flip[f] = (uint8_t)(w & 1);
+        comps += (u32)(w >> 1) == (u32)f;
+    }
+    wave_add(&counts[0], comps);
+}
+
+// every manifold edge whose two faces do not end up opposite marks its component (the pass that decides conflicts)
+__global__ __launch_bounds__(BLOCK) void uf_verify_kernel(Table t, const u32 *__restrict__ root, const uint8_t *__restrict__ flip,
+                                                           u32 *__restrict__ conflict)
+{
+    for (int64_t s = (int64_t)blockIdx.x * BLOCK + threadIdx.x; s < t.cap; s += (int64_t)gridDim.x * BLOCK) {
+        if (t.keys[s] == EMPTY_KEY || t.cnt[s] != 2) continue;
+        const u32 e0 = t.ent[2 * s], e1 = t.ent[2 * s + 1];
+        const u32 f = e0 >> 1, g = e1 >> 1;
+        const u32 r = ((e0 ^ e1) & 1u) ^ 1u;
+        if (((u32)(flip[f] ^ flip[g])) != r) conflict[root[f]] = 1;
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void uf_conflict_kernel(int64_t nf, const u32 *__restrict__ root, const u32 *__restrict__ conflict,
+                                                             uint8_t *__restrict__ flip, unsigned long long *__restrict__ counts)
+{
+    u32 bad = 0;
+    for (int64_t f = (int64_t)blockIdx.x * BLOCK + threadIdx.x; f < nf; f += (int64_t)gridDim.x * BLOCK) {
+        const u32 r = root[f];
+        if (conflict[r]) {
+            flip[f] = 0;                               // a conflicting component is left as given
+            bad += r == (u32)f;
+        }
+    }
+    wave_add(&counts[1], bad);
+}
+
+// ---- signed volume after the flips, packing -----------------------------------------------------------------------------
+__global__ __launch_bounds__(BLOCK) void signed_volume_kernel(const float *__restrict__ v, const int64_t *__restrict__ faces, int64_t nf,
+                                                               const uint8_t *__restrict__ flip, double *__restrict__ out)
+{
+    double vol = 0.0;
+    for (int64_t f = (int64_t)blockIdx.x * BLOCK + threadIdx.x; f < nf; f += (int64_t)gridDim.x * BLOCK) {
+        const float *a = v + 3 * faces[3 * f], *b = v + 3 * faces[3 * f + 1], *c = v + 3 * faces[3 * f + 2];
+        // the arithmetic of tomo_mesh_volume_area; a reversed face contributes the negated term
+        float cx = b[1] * c[2] - b[2] * c[1], cy = b[2] * c[0] - b[0] * c[2], cz = b[0] * c[1] - b[1] * c[0];
+        float d = a[0] * cx + a[1] * cy + a[2] * cz;
+        const double t = (double)d / 6.0;
+        vol += (flip && flip[f]) ? -t : t;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) vol += __shfl_xor(vol, d, 64);
+    if ((threadIdx.x & 63) == 0) atomicAdd(out, vol);
+}
+
+template <typename O>
+__global__ __launch_bounds__(BLOCK) void pack_faces_kernel(const int64_t *__restrict__ faces, int64_t nf, const uint8_t *__restrict__ flip,
+                                                            const double *__restrict__ volume, O *__restrict__ out)
+{
+    const u32 all = (volume && *volume < 0.0) ? 1u : 0u;
+    for (int64_t f = (int64_t)blockIdx.x * BLOCK + threadIdx.x; f < nf; f += (int64_t)gridDim.x * BLOCK) {
+        const int64_t a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
+        const bool rev = ((flip ? (u32)flip[f] : 0u) ^ all) != 0;
+        out[3 * f] = (O)(rev ? c : a);
+        out[3 * f + 1] = (O)b;
+        out[3 * f + 2] = (O)(rev ? a : c);
+    }
+}
+
+// float -> u32 whose unsigned order is the float order (for atomicMin / atomicMax)
+__device__ static inline u32 f2key(float x)
+{
+    const u32 u = __float_as_uint(x);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ static inline float key2f(u32 k)
+{
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+__global__ void minmax_init_kernel(u32 *keys)
+{
+    if (threadIdx.x < 6) keys[threadIdx.x] = threadIdx.x < 3 ? 0xffffffffu : 0u;
+}
+
+__global__ void minmax_decode_kernel(u32 *keys)
+{
+    if (threadIdx.x < 6) {
+        const float f = key2f(keys[threadIdx.x]);
+        ((float *)keys)[threadIdx.x] = f;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void pack_positions_kernel(const T *__restrict__ v, int64_t nv, float *__restrict__ pos, u32 *keys)
+{
+    u32 mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
+    for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < nv; i += (int64_t)gridDim.x * BLOCK) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const float x = (float)v[3 * i + c];
+            pos[3 * i + c] = x;
+            const u32 k = f2key(x);
+            mn[c] = k < mn[c] ? k : mn[c];
+            mx[c] = k > mx[c] ? k : mx[c];
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) {
+            const u32 a = __shfl_xor(mn[c], d, 64), b = __shfl_xor(mx[c], d, 64);
+            mn[c] = a < mn[c] ? a : mn[c];
+            mx[c] = b > mx[c] ? b : mx[c];
+        }
+        if ((threadIdx.x & 63) == 0) {
+            atomicMin(&keys[c], mn[c]);
+            atomicMax(&keys[3 + c], mx[c]);
+        }
+    }
+}
+
+}  // namespace
+
+TOMO_API int tomo_layer_colors(const void *verts, int is_f64, int64_t nv, int64_t stride, double start1, double end1, int enable1,
+                               double start2, double end2, int enable2, uint8_t *rgba, void *stream)
+{
+    if (nv < 0 || stride < 1) return TOMO_E_ARG;
+    if (nv == 0) return TOMO_OK;
+    if (!verts || !rgba || ((uintptr_t)rgba & 3)) return TOMO_E_ARG;
+    const unsigned g = grid_for(nv);
+    if (is_f64)
+        hipLaunchKernelGGL(layer_colors_kernel<double>, dim3(g), dim3(BLOCK), 0, (hipStream_t)stream, (const double *)verts, nv, stride,
+                           start1, end1, enable1, start2, end2, enable2, (u32 *)rgba);
+    else
+        hipLaunchKernelGGL(layer_colors_kernel<float>, dim3(g), dim3(BLOCK), 0, (hipStream_t)stream, (const float *)verts, nv, stride,
+                           start1, end1, enable1, start2, end2, enable2, (u32 *)rgba);
+    return tomo_status();
+}
+
+TOMO_API int64_t tomo_mesh_edge_table_bytes(int64_t nf)
+{
+    if (nf < 0 || nf >= (int64_t)1 << 31) return TOMO_E_SIZE;
+    return table_bytes(nf);
+}
+
+TOMO_API int tomo_mesh_edges(const int64_t *faces, int64_t nf, int64_t nv, void *table, int64_t bytes, unsigned long long *counters,
+                             void *stream)
+{
+    if (!faces || !table || !counters || nf <= 0 || nv <= 0) return TOMO_E_ARG;
+    if (nf >= (int64_t)1 << 31 || nv > (int64_t)0xffffffffLL) return TOMO_E_SIZE;
+    const int64_t cap = table_cap(nf);
+    if (bytes < table_bytes(nf)) return TOMO_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const Table t = table_view(table, cap);
+    if (hipMemsetAsync(t.keys, 0xff, 8 * cap, st) != hipSuccess || hipMemsetAsync(t.cnt, 0, 4 * cap, st) != hipSuccess ||
+        hipMemsetAsync(counters, 0, 6 * sizeof(unsigned long long), st) != hipSuccess)
+        return TOMO_E_LAUNCH;
+    hipLaunchKernelGGL(edge_insert_kernel, dim3(grid_for(nf)), dim3(BLOCK), 0, st, faces, nf, nv, t, counters);
+    hipLaunchKernelGGL(edge_classify_kernel, dim3(grid_for(cap)), dim3(BLOCK), 0, st, t, counters);
+    return tomo_status();
+}
+
+TOMO_API int64_t tomo_mesh_orient_workspace_bytes(int64_t nf)
+{
+    if (nf < 0 || nf >= (int64_t)1 << 31) return TOMO_E_SIZE;
+    return nf * (8 + 4 + 4);
+}
+
+TOMO_API int tomo_mesh_orient(const void *table, int64_t bytes, int64_t nf, void *workspace, int64_t workspace_bytes, uint8_t *flip,
+                              unsigned long long *counts, void *stream)
+{
+    if (!table || !workspace || !flip || !counts || nf <= 0) return TOMO_E_ARG;
+    if (nf >= (int64_t)1 << 31) return TOMO_E_SIZE;
+    const int64_t cap = table_cap(nf);
+    if (bytes < table_bytes(nf) || workspace_bytes < tomo_mesh_orient_workspace_bytes(nf)) return TOMO_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const Table t = table_view((void *)table, cap);
+    u64 *uf = (u64 *)workspace;
+    u32 *root = (u32 *)((char *)workspace + 8 * nf);
+    u32 *conflict = root + nf;
+    if (hipMemsetAsync(counts, 0, 2 * sizeof(unsigned long long), st) != hipSuccess) return TOMO_E_LAUNCH;
+    hipLaunchKernelGGL(uf_init_kernel, dim3(grid_for(nf)), dim3(BLOCK), 0, st, uf, conflict, nf);
+    hipLaunchKernelGGL(uf_union_kernel, dim3(grid_for(cap)), dim3(BLOCK), 0, st, t, uf);
+    hipLaunchKernelGGL(uf_resolve_kernel, dim3(grid_for(nf)), dim3(BLOCK), 0, st, uf, nf, root, flip, counts);
+    hipLaunchKernelGGL(uf_verify_kernel, dim3(grid_for(cap)), dim3(BLOCK), 0, st, t, root, flip, conflict);
+    hipLaunchKernelGGL(uf_conflict_kernel, dim3(grid_for(nf)), dim3(BLOCK), 0, st, nf, root, conflict, flip, counts);
+    return tomo_status();
+}
+
+TOMO_API int tomo_mesh_signed_volume(const float *verts, const int64_t *faces, int64_t nf, const uint8_t *flip, double *out, void *stream)
+{
+    if (!verts || !faces || !out || nf < 0) return TOMO_E_ARG;
+    if (nf == 0) return TOMO_OK;
+    hipLaunchKernelGGL(signed_volume_kernel, dim3(grid_for(nf, 1024)), dim3(BLOCK), 0, (hipStream_t)stream, verts, faces, nf, flip, out);
+    return tomo_status();
+}
+
+TOMO_API int tomo_glb_pack_faces(const int64_t *faces, int64_t nf, const uint8_t *flip, const double *volume, void *out, int out_i64,
+                                 void *stream)
+{
+    if (!faces || !out || nf < 0) return TOMO_E_ARG;
+    if (nf == 0) return TOMO_OK;
+    if ((uintptr_t)out & (out_i64 ? 7 : 3)) return TOMO_E_ARG;
+    const unsigned g = grid_for(nf);
+    if (out_i64)
+        hipLaunchKernelGGL(pack_faces_kernel<int64_t>, dim3(g), dim3(BLOCK), 0, (hipStream_t)stream, faces, nf, flip, volume, (int64_t *)out);
+    else
+        hipLaunchKernelGGL(pack_faces_kernel<uint32_t>, dim3(g), dim3(BLOCK), 0, (hipStream_t)stream, faces, nf, flip, volume, (uint32_t *)out);
+    return tomo_status();
+}
+
+TOMO_API int tomo_glb_pack_positions(const void *verts, int is_f64, int64_t nv, float *pos, float *minmax, void *stream)
+{
+    if (!verts || !pos || !minmax || nv <= 0 || ((uintptr_t)pos & 3) || ((uintptr_t)minmax & 3)) return TOMO_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    u32 *keys = (u32 *)minmax;
+    hipLaunchKernelGGL(minmax_init_kernel, dim3(1), dim3(64), 0, st, keys);
+    const unsigned g = grid_for(nv, 1024);
+    if (is_f64)
+        hipLaunchKernelGGL(pack_positions_kernel<double>, dim3(g), dim3(BLOCK), 0, st, (const double *)verts, nv, pos, keys);
+    else
+        hipLaunchKernelGGL(pack_positions_kernel<float>, dim3(g), dim3(BLOCK), 0, st, (const float *)verts, nv, pos, keys);
+    hipLaunchKernelGGL(minmax_decode_kernel, dim3(1), dim3(64), 0, st, keys);
+    return tomo_status();
+}
