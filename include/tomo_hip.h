@@ -18,6 +18,8 @@
  *    (Nz, Ny, Nx) = (nz + 2p, ny + 2p, nx + 2p) with p = pad in {0, 1};
  *  - "bits" = bit-packed volume: uint64 words, (nz, ny, wx) with wx = tomo_words_per_row(nx);
  *    bit b of word w of a row is voxel x = 64 w + b; bits at x >= nx are zero.
+ *
+ * Removed in ABI 7 (none had a caller left): tomo_mesh_unique_presorted, tomo_mesh_faces, tomo_mesh_faces_direct, tomo_mesh_faces_workspace_bytes, tomo_mc3_sort_rank, tomo_close_stencil, tomo_pack_close_slab.
  */
 #ifndef TOMO_HIP_H
 #define TOMO_HIP_H
@@ -97,32 +99,27 @@ int tomo_fill_holes_ends(uint64_t *bits, int nz, int ny, int nx, uint64_t *scrat
  * c'[z] = c[z] | (c[z-1] & c[z+1]).  Needs nz >= 3, nx % 16 == 0 and a 16-byte aligned mask (TOMO_E_ARG otherwise: use
  * tomo_pack_bits + tomo_fill_holes_ends + tomo_close_ends_scan).  scratch: ny * wx + 8 words. */
 int tomo_pack_close_ends(const uint8_t *mask, uint64_t *bits, int nz, int ny, int nx, uint64_t *scratch, void *stream);
-/* The fused pass for ONE Z-slab of a sharded stack: lo_fixed / hi_fixed say that the slab's first / last slice is a GLOBAL
- * end slice, already packed and filled in `bits`; otherwise `below` / `above` (bit-packed (ny, wx) slices with the ORIGINAL
- * content of the neighbour rank's adjacent slice) close the stencil and every slice of the slab is computed.  nz >= 2. */
-int tomo_pack_close_slab(const uint8_t *mask, uint64_t *bits, int nz, int ny, int nx, const uint64_t *below,
-                         const uint64_t *above, int lo_fixed, int hi_fixed, void *stream);
-/* tomo_pack_close_slab for the output slices [z_from, z_to) only (the middle of a slab depends on the mask alone: a Z-slab
- * rank enqueues it before it talks to its neighbours, the end ranges afterwards; `below` / `above` are needed only if the
- * range reaches an end that is not fixed).  Any split of [0, nz) into ranges gives the same bits. */
+/* The fused pass for ONE Z-slab of a sharded stack, output slices [z_from, z_to) only: lo_fixed / hi_fixed say that the slab's
+ * first / last slice is a GLOBAL end slice, already packed and filled in `bits`; otherwise `below` / `above` (bit-packed
+ * (ny, wx) slices with the ORIGINAL content of the neighbour rank's adjacent slice) close the stencil there.  The middle of a
+ * slab depends on the mask alone: a Z-slab rank enqueues it before it talks to its neighbours, the end ranges afterwards;
+ * `below` / `above` are needed only if the range reaches an end that is not fixed.  Any split of [0, nz) into ranges gives
+ * the same bits.  nz >= 2. */
 int tomo_pack_close_range(const uint8_t *mask, uint64_t *bits, int nz, int ny, int nx, int z_from, int z_to,
                           const uint64_t *below, const uint64_t *above, int lo_fixed, int hi_fixed, void *stream);
-/* The stencil on n bit-packed slices whose neighbours are given separately: out[i] = mid[i] | (prev & next), prev = i ?
- * mid[i-1] : before, next = i < n-1 ? mid[i+1] : after ((ny, wx) words per slice; out must not overlap mid).  A Z-slab
- * rank closes the ORIGINAL halo slices of its neighbours with it. */
 /* Launch-count savers of the Z-slab front (slab.py; scale-out of voxel_processor.py:46, :56-77, no counterpart in the
  * single-process reference): tomo_pack_bits_pair = two tomo_pack_bits in one launch (the original edge slices for the two
  * neighbours; needs nx % 16 == 0 and 16-byte aligned masks); tomo_slab_edges = tomo_pack_close_range(0, edge) +
- * tomo_pack_close_range(nz - edge, nz) + the two tomo_close_stencil calls on the neighbours' halo slices (lo_n / hi_n = 0:
- * no such neighbour) in ONE launch. */
+ * tomo_pack_close_range(nz - edge, nz) + the stencil on the lo_n / hi_n ORIGINAL halo slices of the two neighbours (0: no
+ * such neighbour) in ONE launch.  The stencil on n bit-packed slices whose neighbours are given separately:
+ * out[i] = mid[i] | (prev & next), prev = i ? mid[i-1] : before, next = i < n-1 ? mid[i+1] : after ((ny, wx) words per slice;
+ * out must not overlap mid). */
 int tomo_pack_bits_pair(const uint8_t *maskA, uint64_t *bitsA, int nzA, const uint8_t *maskB, uint64_t *bitsB, int nzB,
                         int ny, int nx, void *stream);
 int tomo_slab_edges(const uint8_t *mask, uint64_t *bits, int nz, int ny, int nx, int edge, const uint64_t *below,
                     const uint64_t *above, int lo_fixed, int hi_fixed, const uint64_t *lo_before, const uint64_t *lo_mid,
                     const uint64_t *lo_after, int lo_n, uint64_t *lo_out, const uint64_t *hi_before, const uint64_t *hi_mid,
                     const uint64_t *hi_after, int hi_n, uint64_t *hi_out, void *stream);
-int tomo_close_stencil(const uint64_t *before, const uint64_t *mid, const uint64_t *after, int n, int ny, int nx,
-                       uint64_t *out, void *stream);
 /* The z recurrence of _close_volume_ends (voxel_processor.py:72-75), in place.
  * workspace: tomo_close_ends_workspace_words() uint64 words. */
 int64_t tomo_close_ends_workspace_words(int nz, int ny, int nx);
@@ -264,7 +261,7 @@ int tomo_mc_first_touch(const float *field, int Nz, int Ny, int Nx, int64_t pitc
  *   tomo_mc3_vertices  FINAL vertex rows (-1 shift, slice-depth map, y / x scale: surface_extractor.py:57-65, :82-113) as
  *                      16-byte records {z', y', x', id}, partitioned per slice into in-plane / between-plane buckets,
  *                      with their 32-bit sort keys; vertex id = 4 * (list position of the owner voxel) + slot
- *   tomo_mc3_sort_rank segmented sort inside the buckets + gather: uniq rows in np.unique's order, table[id] = index;
+ *   tomo_mc3_sort_rank_top / _fused  sort inside the buckets + gather: uniq rows in np.unique's order, table[id] = index;
  *                      tot[4] counts the places where the rows do not ascend strictly (0 <=> the result is exact)
  *   tomo_mc3_faces     final int64 triangles (reference order and winding) through table; tot[5] degenerate triangles
  *                      (the caller drops them), tot[6] corners without vertex (must stay 0)
@@ -291,10 +288,8 @@ int tomo_mc3_vertices(int Nz, int Ny, int Nx, int xorg, const unsigned long long
                       const double *cum, int64_t ncum, const double *adj, int64_t nadj, float mm_y, float mm_x, float *vrec,
                       uint32_t *keys, uint32_t *idx, void *stream);
 int64_t tomo_mc3_sort_workspace_bytes(int64_t cap_v, int64_t nseg);    /* nseg = tomo_mc3_sort_segments(Nz, Ny) */
-int tomo_mc3_sort_rank(const float *vrec, uint32_t *keys, uint32_t *idx, int64_t cap_v, int Nz, int Ny, const uint32_t *slice_tab,
-                       unsigned long long *tot, float *uniq, int32_t *table, void *workspace, int64_t workspace_bytes,
-                       void *stream);
-/* The same, and tot[7] = number of rows with z' == z_top (the plane a Z-slab rank shares with the rank above; NaN: none). */
+/* The unique stage through rocPRIM's segmented sort (workspace: tomo_mc3_sort_workspace_bytes), and tot[7] = number of rows
+ * with z' == z_top (the plane a Z-slab rank shares with the rank above; NaN: none). */
 int tomo_mc3_sort_rank_top(const float *vrec, uint32_t *keys, uint32_t *idx, int64_t cap_v, int Nz, int Ny, const uint32_t *slice_tab,
                            unsigned long long *tot, float *uniq, int32_t *table, void *workspace, int64_t workspace_bytes,
                            float z_top, void *stream);
@@ -302,7 +297,7 @@ int tomo_mc3_sort_rank_top(const float *vrec, uint32_t *keys, uint32_t *idx, int
  * places that do not ascend strictly (tot[4]), the rows on z' == z_top (tot[7]) -- in ONE hand-written kernel (a workgroup per
  * segment: wave bitonic + merge rounds in LDS, rows gathered in sorted order), no library primitive, no workspace; `idx` of
  * tomo_mc3_vertices may be NULL for it.  A segment longer than 4 096 entries (1 024 for the clamped run of a padded stack's
- * first slices) sets bit 8 of tot[3]: repeat the stage with tomo_mc3_sort_rank_top (after zeroing tot[3], tot[4], tot[7]). */
+ * first slices) sets the value 8 (bit 3) in tot[3]: repeat the stage with tomo_mc3_sort_rank_top (after zeroing tot[3], tot[4], tot[7]). */
 int tomo_mc3_sort_rank_fused(const float *vrec, const uint32_t *keys, int64_t cap_v, int Nz, int Ny, uint32_t *slice_tab,
                              unsigned long long *tot, float *uniq, int32_t *table, float z_top, void *stream);
 int tomo_mc3_faces(int Nz, int Ny, int Nx, int xorg, const unsigned long long *vox_key, int64_t cap, unsigned long long *tot,
@@ -316,26 +311,12 @@ int tomo_mc3_faces(int Nz, int Ny, int Nx, int xorg, const unsigned long long *v
  * skips it), y *= mm_y, x *= mm_x (float32). */
 int tomo_vertex_finalize(float *vpos, int64_t nv, int shift, const double *cum, int64_t ncum,
                          const double *adj, int64_t nadj, float mm_y, float mm_x, void *stream);
-/* surface_extractor.py:115-126 (np.unique(axis=0, return_inverse) + drop faces with < 3 distinct
- * indices), on the device:
- *   tomo_mesh_unique: lexicographic (z,y,x) sort of the vertex rows, dedupe -> uniq (U,3),
- *                     rank[V] = final index of every provisional vertex; totals[0] = U;
- *   tomo_mesh_faces:  faces32 -> rank -> degenerate triangles dropped (order kept) -> int64;
- *                     totals[1] = number of kept faces.
- * Workspace sizes from the *_bytes helpers. */
+/* The vertex half of surface_extractor.py:115-126 (np.unique(axis=0, return_inverse)) for arbitrary rows, on the device:
+ * lexicographic (z,y,x) sort of the vertex rows, dedupe -> uniq (U,3), rank[V] = final index of every provisional vertex;
+ * totals[0] = U.  Workspace size from tomo_mesh_unique_workspace_bytes. */
 int64_t tomo_mesh_unique_workspace_bytes(int64_t nv);
 int tomo_mesh_unique(const float *vpos, int64_t nv, float *uniq, int32_t *rank, unsigned long long *totals,
                      void *workspace, int64_t workspace_bytes, void *stream);
-/* The same through the one-sort path, for rows in marching-cubes order together with the vertex keys tomo_mc_emit wrote
- * (vkey) and the field's Ny / Nz: the order is that of ONE stable sort on a 48-bit key (slice bucket, then y in a plane or
- * z between planes), carried out as a stable two-way partition inside every slab plus a segmented 32-bit sort inside
- * the 2 Nz buckets.  Exact if and only if totals[2] (which the caller zeroes) is still 0 afterwards -- it counts the places
- * where the result descends in (z, y, x) (float32 rounding coincidences, zero slice depths); if it is not 0, call
- * tomo_mesh_unique instead.  Same workspace. */
-int tomo_mesh_unique_presorted(const float *vpos, const unsigned long long *vkey, int64_t nv, int Ny, int Nz, float *uniq,
-                               int32_t *rank, unsigned long long *totals, void *workspace, int64_t workspace_bytes,
-                               void *stream);
-int64_t tomo_mesh_faces_workspace_bytes(int64_t nf);
 /* out[i] = index of query row i in the sorted duplicate-free row list uniq (nu x 3), -1 (and *missing += 1, a device
  * counter the caller zeroes) if it is not there.  Used by the Z-slab job for the shared-plane vertices. */
 int tomo_mesh_lookup(const float *uniq, int64_t nu, const float *query, int64_t nq, int32_t *out,
@@ -368,13 +349,6 @@ int tomo_mc3_faces_slab(int Nz, int Ny, int Nx, int xorg, const unsigned long lo
                         const uint16_t *vox_used, const uint32_t *blk3, const int32_t *table, int64_t *faces, int64_t cap_f,
                         const int64_t *gathered, int rank, int world, const int32_t *ids_next, int64_t cap_top, int64_t cap_v,
                         void *stream);
-int tomo_mesh_faces(const int32_t *faces32, int64_t nf, const int32_t *rank, int64_t *faces_out,
-                    unsigned long long *totals, void *workspace, int64_t workspace_bytes, void *stream);
-/* Speculative one-pass variant: faces_out[f] = rank[faces32[f]] for every face (int64), totals[1] = nf, and totals[3]
- * (zeroed by the caller) += number of degenerate faces.  The result is final if and only if totals[3] stays 0; otherwise
- * call tomo_mesh_faces. */
-int tomo_mesh_faces_direct(const int32_t *faces32, int64_t nf, const int32_t *rank, int64_t *faces_out,
-                           unsigned long long *totals, void *stream);
 /* surface_extractor.py:128-149: out[0] = sum over faces of dot(v0, cross(v1,v2))/6 (float64
  * accumulation of float32 terms), out[1] = sum of 0.5*|cross(v1-v0, v2-v0)|.  out is zeroed by the
  * caller; tree reduction => parity with the reference's sequential sums is to 1e-6 rel, not bitwise. */

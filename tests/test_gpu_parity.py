@@ -501,7 +501,7 @@ def test_device_failures_return_none_like_the_reference(dev, monkeypatch, capsys
 
         def boom(*a, **k):
             raise _lib.TomoError("internal error: 3 triangle corners reference a missing vertex")
-        m.setattr(pipeline, "mc3_vertices" if pipeline.MC3 else "ensure_manifold_mesh", boom)
+        m.setattr(pipeline, "mc3_vertices", boom)
         assert se.extract_manifold_surface(v, depths, 1.0, 1.0) is None
     with monkeypatch.context() as m:                     # (4) a failing launch (status from the C ABI)
         m.setattr(pipeline._lib, "check", lambda code, what: (_ for _ in ()).throw(_lib.TomoError(what + " failed")))
@@ -672,40 +672,23 @@ def test_missing_library_fails_loudly(monkeypatch):
         _lib.lib()
 
 
-def test_unique_one_sort_path_detects_disorder_and_falls_back(dev):
-    """tomo_mesh_unique_presorted is exact only for rows in marching-cubes order; it must count every place where its
-    result descends, and pipeline.ensure_manifold_mesh must then fall back to the two-sort path: np.unique either way."""
+def test_unique_rows_equal_np_unique_for_ordered_and_disordered_rows(dev):
+    """pipeline.unique_rows (tomo_mesh_unique, the general two-sort path) is np.unique(axis=0, return_inverse=True) whatever
+    order the rows arrive in, and rank[faces] without the degenerate triangles is the oracle's manifold mesh."""
     rng = np.random.default_rng(9)
-    L = _lib.lib()
     for ordered in (True, False):
         v = rng.integers(0, 6, (5000, 3)).astype(np.float32) * np.float32(0.37)
-        if ordered:     # marching-cubes-like: plane vertices of slice Z = index of the z value, rows sorted, duplicates kept
+        if ordered:     # marching-cubes-like: rows sorted, duplicates kept
             v = v[np.lexsort((v[:, 2], v[:, 1], v[:, 0]))]
-            zidx = np.searchsorted(np.unique(v[:, 0]), v[:, 0]).astype(np.int64)
-            key = (zidx << 22)                                   # Ny = 1, slot 0: bucket 2 Z, sub-key y
-        else:
-            key = np.zeros(len(v), np.int64)                     # everything in one bucket, sorted by y only
         f = rng.integers(0, len(v), (7000, 3)).astype(np.int32)
-        vt, ft, kt = torch.from_numpy(v).to(dev), torch.from_numpy(f).to(dev), torch.from_numpy(key).to(dev)
-        totals = torch.zeros(4, dtype=torch.int64, device=dev)
-        uniq = torch.empty_like(vt)
-        rank = torch.empty(len(v), dtype=torch.int32, device=dev)
-        wsb = L.tomo_mesh_unique_workspace_bytes(len(v))
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        _lib.check(L.tomo_mesh_unique_presorted(vt.data_ptr(), kt.data_ptr(), len(v), 1, 6 if ordered else 1, uniq.data_ptr(), rank.data_ptr(),
-                                                totals.data_ptr(), ws.data_ptr(), wsb, torch.cuda.current_stream().cuda_stream),
-                   "presorted")
-        nviol = int(totals[2].item())
-        assert (nviol == 0) == ordered
+        uniq, rank = pipeline.unique_rows(torch.from_numpy(v).to(dev))
         eu, einv = np.unique(v, axis=0, return_inverse=True)
-        if ordered:
-            assert np.array_equal(uniq[: int(totals[0].item())].cpu().numpy(), eu)
-            assert np.array_equal(rank.cpu().numpy(), einv.reshape(-1))
-        mesh = pipeline.RawMesh(kt, vt, ft)
-        mesh._ny, mesh._nz = 1, (6 if ordered else 1)
-        gv, gf = pipeline.ensure_manifold_mesh(mesh)
+        assert np.array_equal(uniq.cpu().numpy(), eu)
+        assert np.array_equal(rank.cpu().numpy(), einv.reshape(-1))
+        gf = rank.cpu().numpy().astype(np.int64)[f]
+        gf = gf[(gf[:, 0] != gf[:, 1]) & (gf[:, 1] != gf[:, 2]) & (gf[:, 0] != gf[:, 2])]
         ev, ef = O.ensure_manifold_mesh(v, f)
-        assert np.array_equal(gv.cpu().numpy(), ev) and np.array_equal(gf.cpu().numpy(), ef)
+        assert np.array_equal(uniq.cpu().numpy(), ev) and np.array_equal(gf, ef)
 
 
 @pytest.mark.parametrize("shape,pad", [((5, 7, 9), 1), ((5, 7, 9), 0), ((9, 33, 64), 1), ((4, 20, 1), 0), ((3, 3, 27), 1),
@@ -872,8 +855,6 @@ def test_mc3_chain_size_hints(dev):
     ref = {k: O.SurfaceExtractor().extract_manifold_surface(v, depths, 0.8, 1.1) for k, v in
            (("small", small), ("big", big), ("mid", mid), ("empty", empty))}
     vols = {"small": small, "big": big, "mid": mid, "empty": empty}
-    if not pipeline.MC3:
-        pytest.skip("TOMO_MC_PATH=old: the round-1 kernels are selected")
     assert pipeline.NA_HINTS
     pipeline._MC3_HINT.clear()
     c0 = dict(pipeline.COUNTERS)
@@ -909,7 +890,7 @@ def test_mc3_chain_size_hints(dev):
 @pytest.mark.parametrize("kind", ["first", "both", "noise_first"])
 def test_one_sort_unique_with_clamped_first_slice(dev, kind):
     """A mask in the first slice puts vertices on the z edges below it; the slice-depth map clamps their z to 0 -- the z of
-    the in-plane vertices of that slice -- so np.unique interleaves two runs of the one-sort path.  The merge of those runs
+    the in-plane vertices of that slice -- so np.unique interleaves two runs of the bucketed sort.  The merge of those runs
     keeps the fast path exact: same mesh as the oracle WITHOUT falling back to the general sort."""
     rng = np.random.default_rng(3)
     shape = (12, 40, 90)
@@ -928,13 +909,9 @@ def test_one_sort_unique_with_clamped_first_slice(dev, kind):
     gv, gf = got[0].cpu().numpy(), got[1].cpu().numpy()
     assert gv.shape == ref[0].shape and np.array_equal(gv.view(np.int32), np.ascontiguousarray(ref[0]).view(np.int32))
     assert np.array_equal(gf, ref[1])
-    if kind != "noise_first":                     # (noise may break the one-sort order elsewhere: float32 ties between buckets)
-        if pipeline.MC3:
-            assert pipeline.COUNTERS.get("mc3_exact", 0) - c0.get("mc3_exact", 0) == 1
-            assert pipeline.COUNTERS.get("mc3_general_unique", 0) - c0.get("mc3_general_unique", 0) == 0
-        else:
-            assert pipeline.COUNTERS["unique_one_sort"] - c0["unique_one_sort"] == 1
-            assert pipeline.COUNTERS["unique_fallback"] - c0["unique_fallback"] == 0
+    if kind != "noise_first":                     # (noise may break the bucketed order elsewhere: float32 ties between buckets)
+        assert pipeline.COUNTERS.get("mc3_exact", 0) - c0.get("mc3_exact", 0) == 1
+        assert pipeline.COUNTERS.get("mc3_general_unique", 0) - c0.get("mc3_general_unique", 0) == 0
 
 
 @pytest.mark.parametrize("ny,kind", [(638, "body"), (639, "body"), (1400, "body"), (1400, "wide"), (1400, "first"), (660, "first_thin"), (1560, "noise")])

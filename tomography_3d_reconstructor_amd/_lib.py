@@ -55,11 +55,9 @@ SIGNATURES = {
     "tomo_fill_holes_slice": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_i, _c_p, _c_p]),
     "tomo_fill_holes_ends": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_p]),
     "tomo_pack_close_ends": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_p, _c_p]),
-    "tomo_pack_close_slab": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_i, _c_i, _c_p]),
     "tomo_pack_bits_pair": (_c_i, [_c_p, _c_p, _c_i, _c_p, _c_p, _c_i, _c_i, _c_i, _c_p]),
     "tomo_slab_edges": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_p, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_i, _c_p, _c_p, _c_p, _c_p,
                                _c_i, _c_p, _c_p]),
-    "tomo_close_stencil": (_c_i, [_c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_p, _c_p]),
     "tomo_pack_close_range": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_i, _c_p, _c_p, _c_i, _c_i, _c_p]),
     "tomo_close_ends_workspace_words": (_c_i64, [_c_i, _c_i, _c_i]),
     "tomo_close_ends_scan": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_p]),
@@ -96,15 +94,12 @@ SIGNATURES = {
     "tomo_mc3_vertices": (_c_i, [_c_i, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i, _c_i,
                                  _c_p, _c_i64, _c_p, _c_i64, _c_f, _c_f, _c_p, _c_p, _c_p, _c_p]),
     "tomo_mc3_sort_workspace_bytes": (_c_i64, [_c_i64, _c_i64]),
-    "tomo_mc3_sort_rank": (_c_i, [_c_p, _c_p, _c_p, _c_i64, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p]),
     "tomo_mc3_sort_rank_top": (_c_i, [_c_p, _c_p, _c_p, _c_i64, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_f, _c_p]),
     "tomo_mc3_sort_rank_fused": (_c_i, [_c_p, _c_p, _c_i64, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_f, _c_p]),
     "tomo_mc3_faces": (_c_i, [_c_i, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p]),
     "tomo_vertex_finalize": (_c_i, [_c_p, _c_i64, _c_i, _c_p, _c_i64, _c_p, _c_i64, _c_f, _c_f, _c_p]),
     "tomo_mesh_unique_workspace_bytes": (_c_i64, [_c_i64]),
     "tomo_mesh_unique": (_c_i, [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p]),
-    "tomo_mesh_unique_presorted": (_c_i, [_c_p, _c_p, _c_i64, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p]),
-    "tomo_mesh_faces_workspace_bytes": (_c_i64, [_c_i64]),
     "tomo_mesh_lookup": (_c_i, [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p]),
     "tomo_slab_top_rows": (_c_i, [_c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
     "tomo_slab_lookup": (_c_i, [_c_p, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p]),
@@ -112,8 +107,6 @@ SIGNATURES = {
     "tomo_slab_lookup_summary": (_c_i, [_c_p, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
     "tomo_mc3_faces_slab": (_c_i, [_c_i, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64,
                                    _c_p, _c_i, _c_i, _c_p, _c_i64, _c_i64, _c_p]),
-    "tomo_mesh_faces": (_c_i, [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p]),
-    "tomo_mesh_faces_direct": (_c_i, [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_p]),
     "tomo_mesh_volume_area": (_c_i, [_c_p, _c_p, _c_i64, _c_p, _c_p]),
     "tomo_layer_colors": (_c_i, [_c_p, _c_i, _c_i64, _c_i64, _c_d, _c_d, _c_i, _c_d, _c_d, _c_i, _c_p, _c_p]),
     "tomo_mesh_edge_table_bytes": (_c_i64, [_c_i64]),

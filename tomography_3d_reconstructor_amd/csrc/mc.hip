@@ -1092,7 +1092,7 @@ __global__ __launch_bounds__(256) void mc3_bands_kernel(const McGrid g, const u3
         merge3[0] = ov ? 0u : sliceA[1] + sliceB[0];
         merge3[1] = ov ? 0u : sliceA[1] + sliceB[1];
         merge3[2] = ov ? 0u : sliceA[Nz >= 2 ? 2 : 1] + sliceB[1];
-        merge3[3] = 0u;                                           // the ticket word of uq3_sortrank_kernel (mesh.hip)
+        merge3[3] = 0u;                                           // spare word of the table: no kernel reads it
         return;
     }
     if (i > nseg) return;

@@ -1,7 +1,7 @@
-// mesh.hip -- vertex finalisation and the np.unique / face-remap stage on the device.
+// mesh.hip -- vertex finalisation and the np.unique stage on the device.
 //
 // Replaces surface_extractor.py:57-65 (-1 shift, y/x scale), :82-113 (_apply_variable_slice_depths),
-// :115-126 (_ensure_manifold_mesh = np.unique(axis=0, return_inverse) + per-face degenerate filter)
+// :115-126 (np.unique(axis=0, return_inverse); the per-face degenerate filter follows in mc.hip / on the host)
 // and :128-149 (mesh volume / surface area).  The final vertex index of the reference is the rank of
 // the vertex row in the lexicographic (z,y,x) order of the float32 rows, so this is a sort problem:
 // an LSD radix sort (rocPRIM device primitive) of order-preserving uint keys, x first, then (z,y).
@@ -71,28 +71,9 @@ __global__ __launch_bounds__(256) void uq_gather_kernel(const float *__restrict_
     kzy[i] = ((u64)fkey32(p[0]) << 32) | (u64)fkey32(p[1]);
 }
 
-// 48-bit keys of the one-sort path: (bucket, sub).  bucket = 2 Z for a vertex in slice plane Z of its owner voxel
-// (x- / y-edge: sub = y), 2 Z + 1 for a vertex between planes Z and Z + 1 (z-edge or cell centre: sub = z).
-__global__ __launch_bounds__(256) void uq_keys_bucket_kernel(const float *__restrict__ vpos, const u64 *__restrict__ vkey,
-                                                             int64_t nv, int key_row_shift, int Ny, u64 *__restrict__ keys,
-                                                             u32 *__restrict__ idx)
-{
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nv) return;
-    const u64 k = vkey[i];
-    const int slot = (int)(k & 3ull);
-    const u64 Z = (k >> key_row_shift) / (u64)Ny;
-    const float *p = vpos + 3 * i;
-    const u64 bucket = 2ull * Z + (slot >= 2 ? 1ull : 0ull);
-    keys[i] = (bucket << 32) | (u64)fkey32(slot >= 2 ? p[0] : p[1]);
-    idx[i] = (u32)i;
-}
-
-// head[i] = row idx[i] differs from row idx[i-1]; with `violations` also counts the places where two consecutive
-// rows DEscend in the lexicographic (z, y, x) order (the one-sort path is only valid when there are none)
+// head[i] = row idx[i] differs from row idx[i-1]
 __global__ __launch_bounds__(256) void uq_heads_kernel(const float *__restrict__ vpos, int64_t nv,
-                                                       const u32 *__restrict__ idx, u32 *__restrict__ head,
-                                                       u64 *__restrict__ violations)
+                                                       const u32 *__restrict__ idx, u32 *__restrict__ head)
 {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nv) return;
@@ -100,91 +81,8 @@ __global__ __launch_bounds__(256) void uq_heads_kernel(const float *__restrict__
     if (i > 0) {
         const float *a = vpos + 3 * (int64_t)idx[i], *b = vpos + 3 * (int64_t)idx[i - 1];
         h = (a[0] != b[0] || a[1] != b[1] || a[2] != b[2]) ? 1u : 0u;
-        if (violations && (a[0] < b[0] || (a[0] == b[0] && (a[1] < b[1] || (a[1] == b[1] && a[2] < b[2])))))
-            atomicAdd(violations, 1ull);
     }
     head[i] = h;
-}
-
-// head flag of sorted position i as a function object: lets the scan read the flags through a transform iterator
-// instead of an array (one kernel and 14 MB of traffic less per 3.5 M vertices)
-// Sorted order of the one-sort path: idx, except for positions [off[1], off[3]) -- the between-planes part of slab 0 and
-// the in-plane part of slab 1 -- which are read from `alt`, where uq_merge_kernel has merged those two runs (off == null:
-// plain idx).
-struct UqOrder {
-    const u32 *idx, *alt, *off;
-    __device__ u32 at(u32 i) const
-    {
-        if (off != nullptr && i >= off[1] && i < off[3]) return alt[i];
-        return idx[i];
-    }
-};
-
-struct UqHead {
-    const float *vpos;
-    UqOrder ord;
-    __device__ u32 operator()(u32 i) const
-    {
-        if (i == 0) return 1u;
-        const float *a = vpos + 3 * (int64_t)ord.at(i), *b = vpos + 3 * (int64_t)ord.at(i - 1);
-        return (a[0] != b[0] || a[1] != b[1] || a[2] != b[2]) ? 1u : 0u;
-    }
-};
-
-// With padding, the vertices on the z edges between padded slices 0 and 1 (a mask that touches the first slice) all get
-// z' = 0 from the slice-depth map (surface_extractor.py:100-101 clamps z < 0), the same z' as the in-plane vertices of
-// slice 1: two runs, each sorted by (z', y, x), that np.unique interleaves.  One thread per element of either run finds
-// its rank in the other by binary search (ties: the first run first) -- a merge that is the identity whenever the first
-// run's z' lie below the second's, i.e. for every other pair of neighbouring buckets and without the clamp.
-__global__ __launch_bounds__(256) void uq_merge_kernel(const float *__restrict__ vpos, const u32 *__restrict__ off,
-                                                       const u32 *__restrict__ idx, u32 *__restrict__ alt)
-{
-    const u32 o1 = off[1], o2 = off[2], o3 = off[3];
-    const u32 na = o2 - o1, nb = o3 - o2;
-    for (u32 t = blockIdx.x * blockDim.x + threadIdx.x; t < na + nb; t += gridDim.x * blockDim.x) {
-        const bool inA = t < na;
-        const u32 src = idx[inA ? o1 + t : o2 + (t - na)];
-        const float *k = vpos + 3 * (int64_t)src;
-        const float k0 = k[0], k1 = k[1], k2 = k[2];
-        const u32 base = inA ? o2 : o1;
-        u32 lo = 0, hi = inA ? nb : na;
-        while (lo < hi) {
-            const u32 mid = lo + ((hi - lo) >> 1);
-            const float *m = vpos + 3 * (int64_t)idx[base + mid];
-            const bool less = m[0] < k0 || (m[0] == k0 && (m[1] < k1 || (m[1] == k1 && m[2] < k2)));
-            const bool equal = m[0] == k0 && m[1] == k1 && m[2] == k2;
-            if (less || (!inA && equal)) lo = mid + 1; else hi = mid;      // B counts the A elements <= itself
-        }
-        alt[o1 + (inA ? t : t - na) + lo] = src;
-    }
-}
-
-// scatter of the one-sort path: recomputes the head flag (same two rows the order check needs anyway), counts the places
-// where the sorted result descends lexicographically, writes uniq / rank
-__global__ __launch_bounds__(256) void uq_scatter_check_kernel(const float *__restrict__ vpos, int64_t nv,
-                                                               const UqOrder ord, const u32 *__restrict__ hscan,
-                                                               float *__restrict__ uniq, int32_t *__restrict__ rank,
-                                                               u64 *__restrict__ totals)
-{
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nv) return;
-    const u32 src = ord.at((u32)i);
-    const float *a = vpos + 3 * (int64_t)src;
-    const float a0 = a[0], a1 = a[1], a2 = a[2];
-    bool head = true;
-    if (i > 0) {
-        const float *b = vpos + 3 * (int64_t)ord.at((u32)i - 1u);
-        const float b0 = b[0], b1 = b[1], b2 = b[2];
-        head = (a0 != b0 || a1 != b1 || a2 != b2);
-        if (a0 < b0 || (a0 == b0 && (a1 < b1 || (a1 == b1 && a2 < b2)))) atomicAdd(&totals[2], 1ull);
-    }
-    const u32 u = hscan[i] - 1u;
-    rank[src] = (int32_t)u;
-    if (head) {
-        float *q = uniq + 3 * (int64_t)u;
-        q[0] = a0; q[1] = a1; q[2] = a2;
-    }
-    if (i == nv - 1) totals[0] = (u64)hscan[i];
 }
 
 __global__ __launch_bounds__(256) void uq_scatter_kernel(const float *__restrict__ vpos, int64_t nv,
@@ -205,80 +103,11 @@ __global__ __launch_bounds__(256) void uq_scatter_kernel(const float *__restrict
     if (i == nv - 1) totals[0] = (u64)hscan[i];
 }
 
-// ---- one-sort path, bucket partition + segmented sort
-// class of a vertex from its key: 1 = between two slice planes (z-edge / cell centre), 0 = in a plane
-struct UqBetween {
-    __host__ __device__ u32 operator()(u64 key) const { return (key & 3ull) >= 2ull ? 1u : 0u; }
-};
-
-// slab_start[Z] = index of the first vertex whose owner voxel is in slice >= Z (vertices arrive ordered by slice);
-// slab_start[0 .. Nz] inclusive, slab_start[Nz] = nv
-__global__ __launch_bounds__(256) void uq_slabs_kernel(const u64 *__restrict__ vkey, int64_t nv, int Ny, int Nz,
-                                                       u32 *__restrict__ slab_start)
-{
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nv) return;
-    int64_t Z = (int64_t)((vkey[i] >> TOMO_KEY_ROW_SHIFT) / (u64)Ny);
-    if (Z > Nz - 1) Z = Nz - 1;
-    int64_t Zp = i == 0 ? -1 : (int64_t)((vkey[i - 1] >> TOMO_KEY_ROW_SHIFT) / (u64)Ny);
-    if (Zp > Nz - 1) Zp = Nz - 1;
-    for (int64_t z = Zp + 1; z <= Z; z++) slab_start[z] = (u32)i;
-    if (i == nv - 1) for (int64_t z = Z + 1; z <= Nz; z++) slab_start[z] = (u32)nv;
-}
-
-// stable partition of every slab into [in-plane vertices][between-plane vertices]: B[i] = number of between-plane
-// vertices before i.  Writes the 32-bit sub key (y in a plane, z between planes) and the source index at the
-// destination, and the segment offsets (2 Z -> plane part of slab Z, 2 Z + 1 -> between part; offsets[2 Nz] = nv).
-__global__ __launch_bounds__(256) void uq_partition_kernel(const float *__restrict__ vpos, const u64 *__restrict__ vkey,
-                                                           int64_t nv, int Ny, int Nz, const u32 *__restrict__ B,
-                                                           const u32 *__restrict__ slab_start, u32 *__restrict__ keys,
-                                                           u32 *__restrict__ idx, u32 *__restrict__ offsets)
-{
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < (int64_t)Nz) {                                   // the first Nz threads also publish the segment offsets
-        const u32 s0 = slab_start[i], s1 = slab_start[i + 1];
-        const u32 nb = B[s1] - B[s0];
-        offsets[2 * i] = s0;
-        offsets[2 * i + 1] = s1 - nb;
-        if (i == Nz - 1) offsets[2 * (int64_t)Nz] = (u32)nv;
-    }
-    if (i >= nv) return;
-    const u64 k = vkey[i];
-    int64_t Z = (int64_t)((k >> TOMO_KEY_ROW_SHIFT) / (u64)Ny);
-    if (Z > Nz - 1) Z = Nz - 1;
-    const bool between = (k & 3ull) >= 2ull;
-    const u32 s0 = slab_start[Z], s1 = slab_start[Z + 1];
-    const u32 b0 = B[s0], bi = B[i];
-    const u32 nplane = (s1 - s0) - (B[s1] - b0);
-    const u32 dest = between ? s0 + nplane + (bi - b0) : s0 + ((u32)i - s0) - (bi - b0);
-    const float *p = vpos + 3 * i;
-    keys[dest] = fkey32(between ? p[0] : p[1]);
-    idx[dest] = (u32)i;
-}
-
-__global__ void uq_total_kernel(const u64 *__restrict__ vkey, int64_t nv, u32 *__restrict__ B)
-{   // closes the exclusive scan: B[nv] = number of between-plane vertices
-    if (threadIdx.x == 0 && blockIdx.x == 0) B[nv] = B[nv - 1] + (((vkey[nv - 1] & 3ull) >= 2ull) ? 1u : 0u);
-}
-
-#define UQ_MAX_SLABS 65536          // slices the bucket tables of the one-sort path are sized for
-
 struct UqLayout {
-    size_t kx_a, kx_b, idx_a, idx_b, idx_c, kzy_a, kzy_b, head, hscan, seg, temp, temp_bytes, total;
+    size_t kx_a, kx_b, idx_a, idx_b, idx_c, kzy_a, kzy_b, head, hscan, temp, temp_bytes, total;
 };
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-// The segments (one per slice plane / between-planes bucket) hold ~1 000 - 6 000 vertices at 1024^2 slices.  rocPRIM's default
-// (128 threads x 17 items) sorts at most 2 176 of them in one go and sends longer segments through several global-memory
-// passes of one small block: 512 x 8 keeps every segment up to 4 096 in registers / LDS (measured, unique stage at 1024^3:
-// default 0.43 ms, 256x16 0.32, 512x8 0.315, 1024x4 0.36, 512x6 0.35, 512x10 0.36, 256x24 0.39).
-// The partitioning threshold (4th WarpSortConfig parameter: the number of SEGMENTS from which rocPRIM first partitions them by
-// size) is set out of reach: that path copies its segment counts to the host and waits for them (device_segmented_radix_sort.hpp,
-// memcpy_and_sync) -- one hidden host round trip per pass of a chain that is built to have none until its single download.
-typedef rocprim::segmented_radix_sort_config<8, rocprim::kernel_config<512, 8>, rocprim::WarpSortConfig<32, 4, 256, 0x7fffffff, 32, 4, 256>, true>
-    UqSegCfg;
-
 
 static UqLayout uq_layout(int64_t nv)
 {
@@ -289,34 +118,14 @@ static UqLayout uq_layout(int64_t nv)
     L.idx_a = take(n * 4); L.idx_b = take(n * 4); L.idx_c = take(n * 4);
     L.kzy_a = take(n * 8); L.kzy_b = take(n * 8);
     L.head = take(n * 4); L.hscan = take(n * 4);
-    L.seg = take((size_t)(3 * UQ_MAX_SLABS + 16) * 4);              // slab_start[Nz + 1] | offsets[2 Nz + 1]
     size_t t1 = 0, t2 = 0, t3 = 0;
     (void)rocprim::radix_sort_pairs(nullptr, t1, (u32 *)nullptr, (u32 *)nullptr, (u32 *)nullptr, (u32 *)nullptr, n, 0, 32,
                               (hipStream_t)0);
     (void)rocprim::radix_sort_pairs(nullptr, t2, (u64 *)nullptr, (u64 *)nullptr, (u32 *)nullptr, (u32 *)nullptr, n, 0, 64,
                               (hipStream_t)0);
     (void)rocprim::inclusive_scan(nullptr, t3, (u32 *)nullptr, (u32 *)nullptr, n, rocprim::plus<u32>(), (hipStream_t)0);
-    size_t t4 = 0;
-    auto heads = rocprim::make_transform_iterator(rocprim::make_counting_iterator<u32>(0u), UqHead{nullptr, nullptr});
-    (void)rocprim::inclusive_scan(nullptr, t4, heads, (u32 *)nullptr, n, rocprim::plus<u32>(), (hipStream_t)0);
     L.temp_bytes = t1 > t2 ? t1 : t2;
     if (t3 > L.temp_bytes) L.temp_bytes = t3;
-    if (t4 > L.temp_bytes) L.temp_bytes = t4;
-    size_t t5 = 0, t6 = 0;
-    (void)rocprim::segmented_radix_sort_pairs(nullptr, t5, (u32 *)nullptr, (u32 *)nullptr, (u32 *)nullptr, (u32 *)nullptr,
-                                              (unsigned)n, (unsigned)(2 * UQ_MAX_SLABS), (const u32 *)nullptr, (const u32 *)nullptr,
-                                              0, 32, (hipStream_t)0);
-    {
-        size_t ta = 0;
-        (void)rocprim::segmented_radix_sort_pairs<UqSegCfg>(nullptr, ta, (u32 *)nullptr, (u32 *)nullptr, (u32 *)nullptr, (u32 *)nullptr,
-                                                            (unsigned)n, (unsigned)(2 * UQ_MAX_SLABS), (const u32 *)nullptr,
-                                                            (const u32 *)nullptr, 0, 32, (hipStream_t)0);
-        if (ta > t5) t5 = ta;
-    }
-    auto cls = rocprim::make_transform_iterator((const u64 *)nullptr, UqBetween());
-    (void)rocprim::exclusive_scan(nullptr, t6, cls, (u32 *)nullptr, 0u, n + 1, rocprim::plus<u32>(), (hipStream_t)0);
-    if (t5 > L.temp_bytes) L.temp_bytes = t5;
-    if (t6 > L.temp_bytes) L.temp_bytes = t6;
     L.temp = take(L.temp_bytes + 256);
     L.total = off;
     return L;
@@ -345,7 +154,7 @@ TOMO_API int tomo_mesh_unique(const float *vpos, int64_t nv, float *uniq, int32_
     hipLaunchKernelGGL(uq_gather_kernel, dim3(blocks), dim3(256), 0, s, vpos, nv, (const u32 *)idx_b, kzy_a);
     tb = L.temp_bytes;
     if (rocprim::radix_sort_pairs(temp, tb, kzy_a, kzy_b, idx_b, idx_c, (size_t)nv, 0, 64, s) != hipSuccess) return TOMO_E_LAUNCH;
-    hipLaunchKernelGGL(uq_heads_kernel, dim3(blocks), dim3(256), 0, s, vpos, nv, (const u32 *)idx_c, head, (u64 *)nullptr);
+    hipLaunchKernelGGL(uq_heads_kernel, dim3(blocks), dim3(256), 0, s, vpos, nv, (const u32 *)idx_c, head);
     tb = L.temp_bytes;
     if (rocprim::inclusive_scan(temp, tb, head, hscan, (size_t)nv, rocprim::plus<u32>(), s) != hipSuccess) return TOMO_E_LAUNCH;
     hipLaunchKernelGGL(uq_scatter_kernel, dim3(blocks), dim3(256), 0, s, vpos, nv, (const u32 *)idx_c, (const u32 *)head,
@@ -353,80 +162,48 @@ TOMO_API int tomo_mesh_unique(const float *vpos, int64_t nv, float *uniq, int32_
     return tomo_status();
 }
 
-// One-sort variant for rows that arrive in marching-cubes order (owner voxel z, y, x, then slot) together with their
-// vertex keys.  In that order the vertices of a slice plane Z come before the vertices between planes Z and Z + 1, inside
-// a plane the rows ascend, inside a row the x-edge vertices (y = the row) ascend in x and precede the y-edge vertices, and
-// vertices that share their fractional coordinate ascend in the other two.  So ONE stable radix sort on a 48-bit key
-// (bucket 2 Z / 2 Z + 1, then y inside a plane or z between planes) yields the lexicographic order -- 6 digit passes
-// instead of the 12 of the general two-sort path.  "Almost": float32 rounding (a fractional coordinate landing exactly
-// on a plane / row value) or a zero slice depth can break it; every place where the result descends is counted in
-// totals[2] and the caller must then redo the call with tomo_mesh_unique (exact if and only if totals[2] == 0).
-// vkey: the keys tomo_mc_emit wrote (row << key_row_shift | x << 2 | slot, row = Z * Ny + Y).  Same workspace size.
-TOMO_API int tomo_mesh_unique_presorted(const float *vpos, const unsigned long long *vkey, int64_t nv, int Ny, int Nz,
-                                        float *uniq, int32_t *rank, unsigned long long *totals, void *workspace,
-                                        int64_t workspace_bytes, void *stream)
-{
-    if (!vpos || !vkey || !uniq || !rank || !totals || !workspace || nv <= 0 || Ny <= 0) return TOMO_E_ARG;
-    if (nv >= 0x7fffffffll) return TOMO_E_SIZE;
-    UqLayout L = uq_layout(nv);
-    if ((size_t)workspace_bytes < L.total) return TOMO_E_WORKSPACE;
-    char *ws = (char *)workspace;
-    u32 *idx_b = (u32 *)(ws + L.idx_b), *idx_c = (u32 *)(ws + L.idx_c);
-    u64 *kzy_a = (u64 *)(ws + L.kzy_a), *kzy_b = (u64 *)(ws + L.kzy_b);
-    u32 *hscan = (u32 *)(ws + L.hscan);
-    void *temp = ws + L.temp;
-    size_t tb = L.temp_bytes;
-    hipStream_t s = (hipStream_t)stream;
-    unsigned blocks = (unsigned)ceil_div64(nv, 256);
-    UqOrder order{(const u32 *)idx_c, nullptr, nullptr};
-    if (Nz <= 0 || Nz > UQ_MAX_SLABS) {
-        hipLaunchKernelGGL(uq_keys_bucket_kernel, dim3(blocks), dim3(256), 0, s, vpos, (const u64 *)vkey, nv, TOMO_KEY_ROW_SHIFT, Ny,
-                           kzy_a, idx_b);
-        if (rocprim::radix_sort_pairs(temp, tb, kzy_a, kzy_b, idx_b, idx_c, (size_t)nv, 0, 48, s) != hipSuccess) return TOMO_E_LAUNCH;
-    } else {
-        // The bucket (slice, in-plane / between planes) part of that key needs no device-wide sort: vertices arrive grouped
-        // by slice, so it is a stable two-way partition inside every slab (one scan + one scatter); what remains is a
-        // 32-bit sort INSIDE each of the 2 Nz buckets -- a segmented sort, one pass over the data, no look-back chain.
-        u32 *kx_a = (u32 *)(ws + L.kx_a), *kx_b = (u32 *)(ws + L.kx_b);
-        u32 *Bscan = (u32 *)kzy_a;                                   // nv + 1 entries (the 64-bit key area is free here)
-        u32 *slab_start = (u32 *)(ws + L.seg), *offsets = slab_start + UQ_MAX_SLABS + 8;
-        unsigned blocks2 = (unsigned)ceil_div64(nv > Nz ? nv : Nz, 256);
-        hipLaunchKernelGGL(uq_slabs_kernel, dim3(blocks), dim3(256), 0, s, (const u64 *)vkey, nv, Ny, Nz, slab_start);
-        auto cls = rocprim::make_transform_iterator((const u64 *)vkey, UqBetween());
-        if (rocprim::exclusive_scan(temp, tb, cls, Bscan, 0u, (size_t)nv, rocprim::plus<u32>(), s) != hipSuccess) return TOMO_E_LAUNCH;
-        hipLaunchKernelGGL(uq_total_kernel, dim3(1), dim3(64), 0, s, (const u64 *)vkey, nv, Bscan);
-        hipLaunchKernelGGL(uq_partition_kernel, dim3(blocks2), dim3(256), 0, s, vpos, (const u64 *)vkey, nv, Ny, Nz,
-                           (const u32 *)Bscan, (const u32 *)slab_start, kx_a, idx_b, offsets);
-        tb = L.temp_bytes;
-        if (rocprim::segmented_radix_sort_pairs<UqSegCfg>(temp, tb, kx_a, kx_b, idx_b, idx_c, (unsigned)nv, (unsigned)(2 * Nz),
-                                                          (const u32 *)offsets, (const u32 *)offsets + 1, 0, 32, s) != hipSuccess)
-            return TOMO_E_LAUNCH;
-        if (Nz >= 2) {                              // the clamped run of slab 0 and the plane of slab 1 (see uq_merge_kernel)
-            hipLaunchKernelGGL(uq_merge_kernel, dim3(256), dim3(256), 0, s, vpos, (const u32 *)offsets, (const u32 *)idx_c, idx_b);
-            order.alt = idx_b;
-            order.off = offsets;
-        }
-    }
-    tb = L.temp_bytes;
-    auto heads = rocprim::make_transform_iterator(rocprim::make_counting_iterator<u32>(0u), UqHead{vpos, order});
-    if (rocprim::inclusive_scan(temp, tb, heads, hscan, (size_t)nv, rocprim::plus<u32>(), s) != hipSuccess) return TOMO_E_LAUNCH;
-    hipLaunchKernelGGL(uq_scatter_check_kernel, dim3(blocks), dim3(256), 0, s, vpos, nv, order, (const u32 *)hscan,
-                       uniq, rank, (u64 *)totals);
-    return tomo_status();
-}
-
 // ------------------------------------------------------------------------------------------ mc3: sort + rank
 // The unique stage of the mc3 chain (mc.hip): vertices arrive FINALISED as 16-byte records {z', y', x', id}, already
 // partitioned into the 2 Nz buckets with their 32-bit sort keys; the offsets (mc3_bands_kernel) cut every plane's bucket
-// further into bands of owner rows -- the order inside a plane is local to a row.  One segmented sort inside the segments, the clamped-run merge of the first two buckets (see uq_merge_kernel), and one gather that writes
+// further into bands of owner rows -- the order inside a plane is local to a row.  One segmented sort inside the segments,
+// the clamped-run merge of the first two buckets (uq3_merge_kernel), and one gather that writes
 // the rows in order, table[id] = position, and counts every place where the result does not ascend STRICTLY: with a
 // count of zero the sorted position is np.unique's index (no duplicate rows, no rounding coincidence) -- otherwise the
 // caller redoes the stage with tomo_mesh_unique on the rows.
+#define UQ_MAX_SLABS 65536          // most slices the mc3 sort entry points take
+
+// The segments (one per slice plane / between-planes bucket) hold ~1 000 - 6 000 vertices at 1024^2 slices.  rocPRIM's default
+// (128 threads x 17 items) sorts at most 2 176 of them in one go and sends longer segments through several global-memory
+// passes of one small block: 512 x 8 keeps every segment up to 4 096 in registers / LDS (measured, unique stage at 1024^3:
+// default 0.43 ms, 256x16 0.32, 512x8 0.315, 1024x4 0.36, 512x6 0.35, 512x10 0.36, 256x24 0.39).
+// The partitioning threshold (4th WarpSortConfig parameter: the number of SEGMENTS from which rocPRIM first partitions them by
+// size) is set out of reach: that path copies its segment counts to the host and waits for them (device_segmented_radix_sort.hpp,
+// memcpy_and_sync) -- one hidden host round trip per pass of a chain that is built to have none until its single download.
+typedef rocprim::segmented_radix_sort_config<8, rocprim::kernel_config<512, 8>, rocprim::WarpSortConfig<32, 4, 256, 0x7fffffff, 32, 4, 256>, true>
+    UqSegCfg;
+
+// Sorted order of the mc3 library sort: idx, except for positions [off[1], off[3]) -- the between-planes bucket of slice 0
+// and the plane of slice 1 -- which are read from `alt`, where uq3_merge_kernel has merged those two runs (off == null:
+// plain idx).
+struct UqOrder {
+    const u32 *idx, *alt, *off;
+    __device__ u32 at(u32 i) const
+    {
+        if (off != nullptr && i >= off[1] && i < off[3]) return alt[i];
+        return idx[i];
+    }
+};
+
 __device__ static inline bool rec_less(const float4 &a, const float4 &b)
 {
     return a.x < b.x || (a.x == b.x && (a.y < b.y || (a.y == b.y && a.z < b.z)));
 }
 
+// With padding, the vertices on the z edges between padded slices 0 and 1 (a mask that touches the first slice) all get
+// z' = 0 from the slice-depth map (surface_extractor.py:100-101 clamps z < 0), the same z' as the in-plane vertices of
+// slice 1: two runs, each sorted by (z', y, x), that np.unique interleaves.  One thread per element of either run finds
+// its rank in the other by binary search (ties: the first run first) -- a merge that is the identity whenever the first
+// run's z' lie below the second's, i.e. for every other pair of neighbouring buckets and without the clamp.
 __global__ __launch_bounds__(256) void uq3_merge_kernel(const float4 *__restrict__ vrec, const u32 *__restrict__ off,
                                                         const u32 *__restrict__ idx, u32 *__restrict__ alt)
 {
@@ -538,14 +315,6 @@ TOMO_API int tomo_mc3_sort_rank_top(const float *vrec, uint32_t *keys, uint32_t 
     return tomo_status();
 }
 
-TOMO_API int tomo_mc3_sort_rank(const float *vrec, uint32_t *keys, uint32_t *idx, int64_t cap_v, int Nz, int Ny, const uint32_t *slice_tab,
-                                unsigned long long *tot, float *uniq, int32_t *table, void *workspace, int64_t workspace_bytes,
-                                void *stream)
-{
-    return tomo_mc3_sort_rank_top(vrec, keys, idx, cap_v, Nz, Ny, slice_tab, tot, uniq, table, workspace, workspace_bytes,
-                                  __builtin_nanf(""), stream);
-}
-
 // ------------------------------------------------------------------------------------------ mc3: sort + rank in ONE kernel (round 4)
 // The default path of the unique stage since round 4: 97 + 5 us at 1024^3 against 83 + 5 + 45 for rocPRIM's segmented sort +
 // uq3_merge_kernel + uq3_rank_kernel, which stay as the path for segments too long for LDS (pipeline.FUSED_SORT /
@@ -575,8 +344,8 @@ TOMO_API int tomo_mc3_sort_rank(const float *vrec, uint32_t *keys, uint32_t *idx
 // L2 back, 3 000 times): hence the separate seam kernel.
 // The clamped run of a padded stack -- the between-plane bucket of slice 0 and the plane of slice 1 have the SAME z' when the
 // depth map clamps z < 0 to 0 (uq3_merge_kernel merges them in the rocPRIM path) -- is ONE segment here, ordered by (y', x')
-// through two stable passes (x', then y').  Segments beyond SR_CAP entries (1 024 for the clamped run) set bit 8 of
-// tot[3]: the host repeats the stage on the rocPRIM path and remembers it for this geometry (pipeline._MC3_LARGE).
+// through two stable passes (x', then y').  Segments beyond SR_CAP entries (1 024 for the clamped run) set the value 8
+// (bit 3) in tot[3]: the host repeats the stage on the rocPRIM path and remembers it for this geometry (pipeline._MC3_LARGE).
 #define SR_THREADS 256
 #define SR_E 8                       // words per thread and round
 #define SR_CAP 4096                  // longest segment the kernel takes (two halves)
@@ -902,7 +671,7 @@ __global__ __launch_bounds__(256) void uq3_seams_kernel(const float *__restrict_
 }
 
 // keys: the 32-bit sort keys mc3_vertices wrote (its idx array is not needed: the sort carries positions); slice_tab: as for
-// tomo_mc3_sort_rank_top.  No workspace.  Segments too long for the kernel's LDS are reported in tot[3] (bit 8).
+// tomo_mc3_sort_rank_top.  No workspace.  Segments too long for the kernel's LDS are reported in tot[3] (value 8, bit 3).
 TOMO_API int tomo_mc3_sort_rank_fused(const float *vrec, const uint32_t *keys, int64_t cap_v, int Nz, int Ny, uint32_t *slice_tab,
                                       unsigned long long *tot, float *uniq, int32_t *table, float z_top, void *stream)
 {
@@ -1123,103 +892,6 @@ TOMO_API int tomo_slab_summary(const unsigned long long *tot, int64_t cap_v, con
     if (!tot || !out || cap_v < 1 || cap_top < 0) return TOMO_E_ARG;
     hipLaunchKernelGGL(slab_summary_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const u64 *)tot, cap_v, msg_in,
                        (u64 *)missing, cap_top, caller_flags, out);
-    return tomo_status();
-}
-
-// ------------------------------------------------------------------------------------------ faces
-// provisional vertex ids (int32, from mc_emit) -> final ids through `rank`, drop triangles with fewer than
-// three distinct indices (order kept), widen to int64 like np.unique's inverse.
-__global__ __launch_bounds__(256) void faces_rank_kernel(const int32_t *__restrict__ faces32, int64_t nf,
-                                                         const int32_t *__restrict__ rank, int32_t *__restrict__ ids,
-                                                         u32 *__restrict__ keep)
-{
-    int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= nf) return;
-    int32_t a = rank[faces32[3 * f + 0]], b = rank[faces32[3 * f + 1]], c = rank[faces32[3 * f + 2]];
-    ids[3 * f + 0] = a; ids[3 * f + 1] = b; ids[3 * f + 2] = c;
-    keep[f] = (a != b && b != c && a != c) ? 1u : 0u;
-}
-
-__global__ __launch_bounds__(256) void faces_compact_kernel(const int32_t *__restrict__ ids, const u32 *__restrict__ keep,
-                                                            const u32 *__restrict__ kscan, int64_t nf,
-                                                            int64_t *__restrict__ faces_out, u64 *__restrict__ totals)
-{
-    int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= nf) return;
-    if (keep[f]) {
-        int64_t o = (int64_t)kscan[f] - 1;
-        faces_out[3 * o + 0] = ids[3 * f + 0];
-        faces_out[3 * o + 1] = ids[3 * f + 1];
-        faces_out[3 * o + 2] = ids[3 * f + 2];
-    }
-    if (f == nf - 1) totals[1] = (u64)kscan[f];
-}
-
-// Speculative single pass: final ids straight to int64 at the face's own position, counting the degenerate faces.  If the
-// count is 0 -- no two vertices of a triangle merged, the usual case -- this IS the result (totals[1] = nf) and the
-// rank / scan / compact passes of tomo_mesh_faces are not needed; otherwise the caller runs tomo_mesh_faces.
-__global__ __launch_bounds__(256) void faces_direct_kernel(const int32_t *__restrict__ faces32, int64_t nf,
-                                                           const int32_t *__restrict__ rank, int64_t *__restrict__ faces_out,
-                                                           u64 *__restrict__ totals)
-{
-    int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    bool bad = false;
-    if (f < nf) {
-        const int32_t a = rank[faces32[3 * f + 0]], b = rank[faces32[3 * f + 1]], c = rank[faces32[3 * f + 2]];
-        faces_out[3 * f + 0] = a; faces_out[3 * f + 1] = b; faces_out[3 * f + 2] = c;
-        bad = (a == b || b == c || a == c);
-    }
-    const u64 nbad = (u64)__popcll(__ballot(bad));
-    if ((threadIdx.x & 63) == 0 && nbad) atomicAdd(&totals[3], (unsigned long long)nbad);
-    if (f == 0) totals[1] = (u64)nf;
-}
-
-TOMO_API int tomo_mesh_faces_direct(const int32_t *faces32, int64_t nf, const int32_t *rank, int64_t *faces_out,
-                                    unsigned long long *totals, void *stream)
-{
-    if (!faces32 || !rank || !faces_out || !totals || nf <= 0) return TOMO_E_ARG;
-    if (nf >= 0x7fffffffll) return TOMO_E_SIZE;
-    hipLaunchKernelGGL(faces_direct_kernel, dim3((unsigned)ceil_div64(nf, 256)), dim3(256), 0, (hipStream_t)stream, faces32, nf,
-                       rank, faces_out, (u64 *)totals);
-    return tomo_status();
-}
-
-struct FcLayout { size_t ids, keep, kscan, temp, temp_bytes, total; };
-
-static FcLayout fc_layout(int64_t nf)
-{
-    FcLayout L;
-    size_t n = (size_t)(nf > 0 ? nf : 1), off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    L.ids = take(n * 12); L.keep = take(n * 4); L.kscan = take(n * 4);
-    size_t t = 0;
-    (void)rocprim::inclusive_scan(nullptr, t, (u32 *)nullptr, (u32 *)nullptr, n, rocprim::plus<u32>(), (hipStream_t)0);
-    L.temp_bytes = t;
-    L.temp = take(t + 256);
-    L.total = off;
-    return L;
-}
-
-TOMO_API int64_t tomo_mesh_faces_workspace_bytes(int64_t nf) { return (int64_t)fc_layout(nf).total; }
-
-TOMO_API int tomo_mesh_faces(const int32_t *faces32, int64_t nf, const int32_t *rank, int64_t *faces_out,
-                             unsigned long long *totals, void *workspace, int64_t workspace_bytes, void *stream)
-{
-    if (!faces32 || !rank || !faces_out || !totals || !workspace || nf <= 0) return TOMO_E_ARG;
-    if (nf >= 0x7fffffffll) return TOMO_E_SIZE;
-    FcLayout L = fc_layout(nf);
-    if ((size_t)workspace_bytes < L.total) return TOMO_E_WORKSPACE;
-    char *ws = (char *)workspace;
-    int32_t *ids = (int32_t *)(ws + L.ids);
-    u32 *keep = (u32 *)(ws + L.keep), *kscan = (u32 *)(ws + L.kscan);
-    hipStream_t s = (hipStream_t)stream;
-    unsigned blocks = (unsigned)ceil_div64(nf, 256);
-    hipLaunchKernelGGL(faces_rank_kernel, dim3(blocks), dim3(256), 0, s, faces32, nf, rank, ids, keep);
-    size_t tb = L.temp_bytes;
-    if (rocprim::inclusive_scan(ws + L.temp, tb, keep, kscan, (size_t)nf, rocprim::plus<u32>(), s) != hipSuccess)
-        return TOMO_E_LAUNCH;
-    hipLaunchKernelGGL(faces_compact_kernel, dim3(blocks), dim3(256), 0, s, (const int32_t *)ids, (const u32 *)keep,
-                       (const u32 *)kscan, nf, faces_out, (u64 *)totals);
     return tomo_status();
 }
 

@@ -18,9 +18,9 @@ import torch
 from . import _lib
 
 
-# how often the speculative kernels of ensure_manifold_mesh held / had to be redone; a path that fails more often than
-# it holds in this process is no longer tried first
-COUNTERS = {"unique_one_sort": 0, "unique_fallback": 0, "faces_direct": 0, "faces_fallback": 0}
+# which way the size hints and the unique stage of the surfaces of this process went (tests and tools read the deltas)
+COUNTERS = dict.fromkeys(("na_hint_hit", "na_hint_miss", "mc3_hint_hit", "mc3_hint_miss", "mc3_sort_fused", "mc3_sort_library",
+                          "mc3_exact", "mc3_general_unique", "mc3_degenerate"), 0)
 NA_HINTS = os.environ.get("TOMO_NA_HINTS", "1") not in ("", "0")   # marching_cubes: launch ahead of the first count download
 _NA_HINT = {}
 LIST_LIMIT = 2 ** 31        # active-voxel list entries / vertices / triangles one pass can index (int32 offsets in mc.hip, mesh.hip);
@@ -299,8 +299,7 @@ def marching_cubes(f: Field, level: float = 0.5, z_offset: int = 0):
     seg_cnt = torch.empty(nseg, dtype=torch.int32, device=dev)       # active voxels of every segment
     _lib.check(L.tomo_mc_classify(_p(f.signs), _p(f.gcls), f.Nz, f.Ny, f.Nx, f.xorg, _p(seg_act), _p(seg_cnt), st), "tomo_mc_classify")
     seg_aoff = torch.empty(nseg + 1, dtype=torch.int32, device=dev)
-    stats = torch.zeros(16, dtype=torch.int64, device=dev)   # [0:4] segment scan, [4:8] voxel scan + emit errors, [8:12] unique
-    totals = stats[:8]
+    totals = torch.zeros(8, dtype=torch.int64, device=dev)   # [0:4] segment scan, [4:8] voxel scan + emit errors
     wsb = L.tomo_mc_scan_workspace_bytes(nseg)
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
     _lib.check(L.tomo_mc_scan_segments(_p(seg_cnt), nseg, _p(seg_aoff), _p(totals), _p(ws), wsb, st), "tomo_mc_scan_segments")
@@ -328,13 +327,13 @@ def marching_cubes(f: Field, level: float = 0.5, z_offset: int = 0):
                        "tomo_mc_eval_capped")
             _lib.check(L.tomo_mc_scan(_p(vox_counts), cap, _p(vox_voff), _p(vox_foff), None, _p(tot2), _p(ws2), wsb2, st),
                        "tomo_mc_scan")
-            host = stats[:8].cpu()
+            host = totals.cpu()
             na, nv, nf = int(host[0]), int(host[4]), int(host[5])
             if na > cap:
-                COUNTERS["na_hint_miss"] = COUNTERS.get("na_hint_miss", 0) + 1
+                COUNTERS["na_hint_miss"] += 1
                 na = None                                   # too short: the plain path below redoes list, eval and scan
             else:
-                COUNTERS["na_hint_hit"] = COUNTERS.get("na_hint_hit", 0) + 1
+                COUNTERS["na_hint_hit"] += 1
     if na is None:
         na = int(totals[0].item())
         if na == 0:
@@ -369,10 +368,7 @@ def marching_cubes(f: Field, level: float = 0.5, z_offset: int = 0):
                               int(z_offset), _p(vkey), _p(vpos), _p(faces32), _p(tot2), st), "tomo_mc_emit")
     mesh = RawMesh(vkey, vpos, faces32[:nf])
     mesh._mc = (f, geo, vox_key, na, seg_act, seg_aoff, vox_voff, vox_flags)   # for first_touch_order (manifold=False)
-    mesh._ny = f.Ny       # rows / slices of the field: the one-sort unique path derives the slice of a vertex from its key
-    mesh._nz = f.Nz
-    mesh._stats_fresh = True
-    mesh._stats = stats   # stats[7] != 0 would mean a triangle corner without vertex (read with the unique totals)
+    mesh._stats = totals  # [7] != 0 would mean a triangle corner without vertex (no download here: the tests read it)
     return mesh
 
 
@@ -412,86 +408,8 @@ def finalize_vertices(vpos: torch.Tensor, slice_depths, mm_per_pixel_y, mm_per_p
     return vpos
 
 
-def ensure_manifold_mesh(mesh: RawMesh, presorted: bool = True):
-    """_ensure_manifold_mesh (surface_extractor.py:115-126): unique vertex rows (lexicographic order) and
-    remapped int64 faces without degenerate triangles.  mesh.vpos must already be finalised.
-    presorted: the rows are in marching-cubes order with their keys (a RawMesh from marching_cubes), so try the
-    one-sort path first (tomo_mesh_unique_presorted) and fall back to the two-sort path if it reports a violation."""
-    L = _lib.lib()
-    dev = mesh.vpos.device
-    nv, nf = mesh.vpos.shape[0], mesh.faces32.shape[0]
-    uniq = torch.empty((nv, 3), dtype=torch.float32, device=dev)
-    rank = torch.empty(nv, dtype=torch.int32, device=dev)
-    wsb = L.tomo_mesh_unique_workspace_bytes(nv)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    faces = torch.empty((nf, 3), dtype=torch.int64, device=dev) if nf > 0 else None
-    ws2 = None
-    if nf > 0:
-        wsb2 = L.tomo_mesh_faces_workspace_bytes(nf)
-        ws2 = torch.empty(wsb2, dtype=torch.uint8, device=dev)
-    # counters: marching_cubes' own tensor when the mesh comes from there (its [8:12] part is still zero the first
-    # time), so that ONE download at the end brings the emit error count and the unique totals
-    stats = getattr(mesh, "_stats", None)
-    fresh = stats is not None and getattr(mesh, "_stats_fresh", False)
-    if stats is None:
-        stats, fresh = torch.zeros(16, dtype=torch.int64, device=dev), True
-    mesh._stats_fresh = False
-    ny = getattr(mesh, "_ny", None)
-    one_sort = presorted and mesh.vkey is not None and ny is not None
-    # Speculative fast paths first -- one-sort unique, one-pass face remap.  Each reports through a counter whether its
-    # result is exact; where it is not, the general kernel runs and the counters are downloaded again (ONE download per
-    # round, normally one round).
-    if COUNTERS["unique_fallback"] > COUNTERS["unique_one_sort"] + 2:
-        one_sort = False
-    do_unique = "one_sort" if one_sort else "general"          # None: uniq / rank are final
-    do_faces = "direct" if COUNTERS["faces_fallback"] <= COUNTERS["faces_direct"] + 2 else "compact"
-    nu = nkeep = nbad = 0
-    first = True
-    while True:
-        if not (first and fresh):
-            stats[8:12].zero_()
-        first = False
-        totals = stats[8:12]
-        if do_unique == "one_sort":
-            _lib.check(L.tomo_mesh_unique_presorted(_p(mesh.vpos), _p(mesh.vkey), nv, int(ny), int(getattr(mesh, "_nz", 0) or 0),
-                                                    _p(uniq), _p(rank), _p(totals), _p(ws), wsb, _stream()),
-                       "tomo_mesh_unique_presorted")
-        elif do_unique == "general":
-            _lib.check(L.tomo_mesh_unique(_p(mesh.vpos), nv, _p(uniq), _p(rank), _p(totals), _p(ws), wsb, _stream()),
-                       "tomo_mesh_unique")
-        if nf > 0 and do_faces == "direct":
-            _lib.check(L.tomo_mesh_faces_direct(_p(mesh.faces32), nf, _p(rank), _p(faces), _p(totals), _stream()),
-                       "tomo_mesh_faces_direct")
-        elif nf > 0:
-            _lib.check(L.tomo_mesh_faces(_p(mesh.faces32), nf, _p(rank), _p(faces), _p(totals), _p(ws2), wsb2, _stream()),
-                       "tomo_mesh_faces")
-        host = stats.cpu()
-        nbad = int(host[7])
-        if do_unique is not None:
-            nu = int(host[8])
-        nkeep, nviol, ndegen = int(host[9]), int(host[10]), int(host[11])
-        if do_unique == "one_sort":
-            COUNTERS["unique_one_sort" if nviol == 0 else "unique_fallback"] += 1
-            if nviol:
-                do_unique = "general"                            # the order check failed: sort properly, remap again
-                continue
-        do_unique = None
-        if nf > 0 and do_faces == "direct":
-            COUNTERS["faces_fallback" if ndegen else "faces_direct"] += 1
-            if ndegen:
-                do_faces = "compact"                             # some triangles collapsed: drop them, keep the order
-                continue
-        break
-    if nbad:
-        raise _lib.TomoError("internal error: %d triangle corners reference a missing vertex" % nbad)
-    verts = uniq[:nu]
-    faces = faces[:nkeep] if faces is not None else torch.empty((0, 3), dtype=torch.int64, device=dev)
-    return verts, faces
-
-
-def unique_rows(vpos: torch.Tensor, vkey: torch.Tensor = None, ny: int = None, nz: int = 0):
-    """np.unique(rows, axis=0, return_inverse=True) of finalised vertex rows -> (uniq (U,3), rank (V,) int32).  With the
-    marching-cubes keys of the rows (and the field's row count) the one-sort path is tried first."""
+def unique_rows(vpos: torch.Tensor):
+    """np.unique(rows, axis=0, return_inverse=True) of finalised vertex rows -> (uniq (U,3), rank (V,) int32)."""
     L = _lib.lib()
     dev = vpos.device
     nv = vpos.shape[0]
@@ -502,21 +420,9 @@ def unique_rows(vpos: torch.Tensor, vkey: torch.Tensor = None, ny: int = None, n
         return uniq, rank
     wsb = L.tomo_mesh_unique_workspace_bytes(nv)
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    fast = vkey is not None and ny is not None and COUNTERS["unique_fallback"] <= COUNTERS["unique_one_sort"] + 2
-    while True:
-        totals = torch.zeros(4, dtype=torch.int64, device=dev)
-        if fast:
-            _lib.check(L.tomo_mesh_unique_presorted(_p(vpos), _p(vkey.contiguous()), nv, int(ny), int(nz or 0), _p(uniq), _p(rank),
-                                                    _p(totals), _p(ws), wsb, _stream()), "tomo_mesh_unique_presorted")
-        else:
-            _lib.check(L.tomo_mesh_unique(_p(vpos), nv, _p(uniq), _p(rank), _p(totals), _p(ws), wsb, _stream()), "tomo_mesh_unique")
-        host = totals.cpu()
-        if fast:
-            COUNTERS["unique_one_sort" if int(host[2]) == 0 else "unique_fallback"] += 1
-            if int(host[2]):
-                fast = False
-                continue
-        return uniq[: int(host[0])], rank
+    totals = torch.zeros(4, dtype=torch.int64, device=dev)
+    _lib.check(L.tomo_mesh_unique(_p(vpos), nv, _p(uniq), _p(rank), _p(totals), _p(ws), wsb, _stream()), "tomo_mesh_unique")
+    return uniq[: int(totals[0].item())], rank
 
 
 def lookup_rows(uniq: torch.Tensor, query: torch.Tensor, sync: bool = True):
@@ -531,31 +437,6 @@ def lookup_rows(uniq: torch.Tensor, query: torch.Tensor, sync: bool = True):
     _lib.check(_lib.lib().tomo_mesh_lookup(_p(uniq.contiguous()), uniq.shape[0], _p(query.contiguous()), nq, _p(out), _p(miss),
                                            _stream()), "tomo_mesh_lookup")
     return out, (int(miss.item()) if sync else miss)
-
-
-def remap_faces(faces32: torch.Tensor, gid32: torch.Tensor):
-    """faces (F,3) int64 = gid32[faces32] without the degenerate triangles, order kept (the face half of
-    _ensure_manifold_mesh for an arbitrary provisional -> final index map)."""
-    L = _lib.lib()
-    dev = faces32.device
-    nf = faces32.shape[0]
-    if nf == 0:
-        return torch.zeros((0, 3), dtype=torch.int64, device=dev)
-    faces = torch.empty((nf, 3), dtype=torch.int64, device=dev)
-    totals = torch.zeros(4, dtype=torch.int64, device=dev)
-    faces32, gid32 = faces32.contiguous(), gid32.contiguous()
-    direct = COUNTERS["faces_fallback"] <= COUNTERS["faces_direct"] + 2
-    if direct:
-        _lib.check(L.tomo_mesh_faces_direct(_p(faces32), nf, _p(gid32), _p(faces), _p(totals), _stream()), "tomo_mesh_faces_direct")
-        host = totals.cpu()
-        COUNTERS["faces_fallback" if int(host[3]) else "faces_direct"] += 1
-        if int(host[3]) == 0:
-            return faces
-        totals.zero_()
-    wsb = L.tomo_mesh_faces_workspace_bytes(nf)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    _lib.check(L.tomo_mesh_faces(_p(faces32), nf, _p(gid32), _p(faces), _p(totals), _p(ws), wsb, _stream()), "tomo_mesh_faces")
-    return faces[: int(totals[1].item())]
 
 
 def first_touch_order(mesh: RawMesh):
@@ -593,21 +474,16 @@ def extract_surface(vol: BitVolume, slice_depths, mm_per_pixel_y, mm_per_pixel_x
     device tensors, or None where the reference returns None.
     """
     f = make_field(vol, manifold, add_padding, sparse=FIELD_SPARSE)
-    if manifold and MC3:
+    if manifold:
         m = mc3_vertices(f, slice_depths, mm_per_pixel_y, mm_per_pixel_x, add_padding)
         return None if m is None else (m.uniq, m.faces_final)
+    # surface_extractor.py:55-72 without the manifold branches: skimage's own numbering, int32 faces
     mesh = marching_cubes(f, 0.5)
     if mesh is None:
         return None
-    if not manifold:
-        # surface_extractor.py:55-72 without the manifold branches: skimage's own numbering, int32 faces
-        vpos, faces = first_touch_order(mesh)
-        finalize_vertices(vpos, slice_depths, mm_per_pixel_y, mm_per_pixel_x, False, add_padding)
-        return vpos, faces
-    mesh._mc = None
-    del f
-    finalize_vertices(mesh.vpos, slice_depths, mm_per_pixel_y, mm_per_pixel_x, manifold, add_padding)
-    return ensure_manifold_mesh(mesh)
+    vpos, faces = first_touch_order(mesh)
+    finalize_vertices(vpos, slice_depths, mm_per_pixel_y, mm_per_pixel_x, False, add_padding)
+    return vpos, faces
 
 
 class PendingSurface:
@@ -629,14 +505,14 @@ def extract_surface_submit(vol: BitVolume, slice_depths, mm_per_pixel_y, mm_per_
     """extract_surface in two halves, for a caller that processes one stack after the other: everything is enqueued here
     (from the size hints of the last surface of this geometry) and the ONE download of the pass is started; .result() waits
     for it.  Enqueueing the next stack before reading this one keeps the GPU busy through the host's read (bench.py)."""
-    if manifold and MC3:
+    if manifold:
         f = make_field(vol, manifold, add_padding, sparse=FIELD_SPARSE)
         return PendingSurface(surface=mc3_vertices(f, slice_depths, mm_per_pixel_y, mm_per_pixel_x, add_padding, defer=True))
     return PendingSurface(value=extract_surface(vol, slice_depths, mm_per_pixel_y, mm_per_pixel_x, manifold, add_padding))
 
 
 # ----------------------------------------------------------------------------- mc3: marching cubes + finalise + unique, one chain
-MC3 = os.environ.get("TOMO_MC_PATH", "mc3") != "old"     # manifold=True surfaces through the mc3 chain (csrc/mc.hip, "mc3")
+MC3 = True              # manifold=True surfaces go through the mc3 chain (csrc/mc.hip, "mc3"); the name is read by bench.py
 _MC3_HINT = {}          # field geometry -> (active voxels, vertices, triangles) of the last surface of that geometry
 # The unique stage: ONE hand-written kernel (tomo_mc3_sort_rank_fused; a workgroup per sort segment, everything in LDS) unless
 # the last surface of the geometry had a segment too long for it (a flat cap of > 4 096 vertices between two planes, a noise
@@ -755,7 +631,7 @@ class Mc3Surface:
             raise _lib.TomoError("internal error: %d triangle corners reference a missing vertex" % host[6])
         faces = faces[:host[2]]
         if host[5]:
-            COUNTERS["mc3_degenerate"] = COUNTERS.get("mc3_degenerate", 0) + 1
+            COUNTERS["mc3_degenerate"] += 1
             keep = (faces[:, 0] != faces[:, 1]) & (faces[:, 1] != faces[:, 2]) & (faces[:, 0] != faces[:, 2])
             faces = faces[keep]
         return faces
@@ -852,11 +728,11 @@ def mc3_vertices(f: Field, slice_depths, mm_per_pixel_y, mm_per_pixel_x, add_pad
                                        _p(adj_t), nadj, mmy, mmx, _p(m._vrec), _p(keys), _p(idx), st), "tomo_mc3_vertices")
         m._cap_v = cap_v
         if fused:
-            COUNTERS["mc3_sort_fused"] = COUNTERS.get("mc3_sort_fused", 0) + 1
+            COUNTERS["mc3_sort_fused"] += 1
             _lib.check(L.tomo_mc3_sort_rank_fused(_p(m._vrec), _p(keys), cap_v, f.Nz, f.Ny, _p(m._slice_tab), _p(tot), _p(m._uniq),
                                                   _p(m.table), z_top, st), "tomo_mc3_sort_rank_fused")
             return
-        COUNTERS["mc3_sort_library"] = COUNTERS.get("mc3_sort_library", 0) + 1
+        COUNTERS["mc3_sort_library"] += 1
         wsb = L.tomo_mc3_sort_workspace_bytes(cap_v, L.tomo_mc3_sort_segments(f.Nz, f.Ny))
         ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
         _lib.check(L.tomo_mc3_sort_rank_top(_p(m._vrec), _p(keys), _p(idx), cap_v, f.Nz, f.Ny, _p(m._slice_tab), _p(tot), _p(m._uniq),
@@ -866,12 +742,12 @@ def mc3_vertices(f: Field, slice_depths, mm_per_pixel_y, mm_per_pixel_x, add_pad
         """Everything after the counters of a hinted chain have arrived (host = None: no hinted chain ran)."""
         if host is not None:
             if host[3]:
-                COUNTERS["mc3_hint_miss"] = COUNTERS.get("mc3_hint_miss", 0) + 1
+                COUNTERS["mc3_hint_miss"] += 1
                 if host[3] & 8:
                     _MC3_LARGE[hint_key] = True                  # a sort segment too long for the fused kernel: the library path from now on
                 host = faces = None                              # something did not fit: redo with exact sizes
             else:
-                COUNTERS["mc3_hint_hit"] = COUNTERS.get("mc3_hint_hit", 0) + 1
+                COUNTERS["mc3_hint_hit"] += 1
         if host is None:
             build_list(1 << 16)                                   # a token buffer: tot[0] comes out exact, nothing is written past it
             na = _download_tot(tot)[0]
@@ -891,7 +767,7 @@ def mc3_vertices(f: Field, slice_depths, mm_per_pixel_y, mm_per_pixel_x, add_pad
             vertices_sort(na, nv)
             m._cap_f = max(nf, 1)
             if FUSED_SORT and not _MC3_LARGE.get(hint_key):
-                # the fused kernel reports a segment it cannot hold in LDS (bit 8 of tot[3]): the stage is repeated on the library
+                # the fused kernel reports a segment it cannot hold in LDS (value 8, bit 3, of tot[3]): the stage is repeated on the library
                 # path, and stays there for this geometry
                 host = _download_tot(tot)
                 if host[3] & 8:
@@ -913,7 +789,7 @@ def mc3_vertices(f: Field, slice_depths, mm_per_pixel_y, mm_per_pixel_x, add_pad
         m.uniq = m._uniq[:m.nv]
         if host[4]:
             # duplicate rows or a rounding coincidence: the general sort decides (np.unique semantics), the triangles follow
-            COUNTERS["mc3_general_unique"] = COUNTERS.get("mc3_general_unique", 0) + 1
+            COUNTERS["mc3_general_unique"] += 1
             rows = m._vrec[:m.nv, :3].contiguous()
             uniq, rank = unique_rows(rows)
             ids = m._vrec[:m.nv, 3].contiguous().view(torch.int32).to(torch.int64)
@@ -923,13 +799,13 @@ def mc3_vertices(f: Field, slice_depths, mm_per_pixel_y, mm_per_pixel_x, add_pad
                 faces = m.faces(again=True)
                 host = _download_tot(tot)
         else:
-            COUNTERS["mc3_exact"] = COUNTERS.get("mc3_exact", 0) + 1
+            COUNTERS["mc3_exact"] += 1
         if with_faces:
             if host[6]:
                 raise _lib.TomoError("internal error: %d triangle corners reference a missing vertex" % host[6])
             faces = faces[:m.nf]
             if host[5]:                                              # triangles with fewer than three distinct vertices are dropped, order kept
-                COUNTERS["mc3_degenerate"] = COUNTERS.get("mc3_degenerate", 0) + 1
+                COUNTERS["mc3_degenerate"] += 1
                 keep = (faces[:, 0] != faces[:, 1]) & (faces[:, 1] != faces[:, 2]) & (faces[:, 0] != faces[:, 2])
                 faces = faces[keep]
             m.faces_final = faces

@@ -416,33 +416,15 @@ class HipEngine:
                               f.signs[a:b] if f.signs is not None else None, f.signs_level,
                               f.gcls[a:b] if f.gcls is not None else None)
 
-    def marching_cubes(self, f, z_offset):
-        return pipeline.marching_cubes(f, 0.5, z_offset)
-
     def finalize_vertices(self, vpos, depths, mm_y, mm_x):
+        """The vertex finalisation on its own (SlabJob._z_top maps the shared plane through it)."""
         return pipeline.finalize_vertices(vpos, depths, mm_y, mm_x, True, True)
 
     def unique(self, vpos):
         """-> (uniq (U,3), rank (V,) int32 final index of every input row)."""
-        from . import _lib
-        L = _lib.lib()
-        dev = vpos.device
-        nv = vpos.shape[0]
-        totals = torch.zeros(4, dtype=torch.int64, device=dev)
-        uniq = torch.empty((nv, 3), dtype=torch.float32, device=dev)
-        rank = torch.empty(nv, dtype=torch.int32, device=dev)
-        wsb = L.tomo_mesh_unique_workspace_bytes(nv)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        _lib.check(L.tomo_mesh_unique(vpos.contiguous().data_ptr(), nv, uniq.data_ptr(), rank.data_ptr(), totals.data_ptr(),
-                                      ws.data_ptr(), wsb, torch.cuda.current_stream().cuda_stream), "tomo_mesh_unique")
-        return uniq[: int(totals[0].item())], rank
-
+        return pipeline.unique_rows(vpos)
 
     # optional fast paths (engines without them -- the CPU oracle engine of the tests -- use unique() and torch ops)
-    def unique_mc(self, vpos, vkey, ny, nz=0):
-        """unique() for rows in marching-cubes order with their keys: one-sort path with automatic fallback."""
-        return pipeline.unique_rows(vpos, vkey, ny, nz)
-
     def lookup(self, uniq, query):
         return pipeline.lookup_rows(uniq, query)
 
@@ -450,16 +432,11 @@ class HipEngine:
         """lookup() without the host round trip: the miss count stays on the device (a 1-element int64 tensor)."""
         return pipeline.lookup_rows(uniq, query, sync=False)
 
-    def remap_faces(self, faces32, gid32):
-        return pipeline.remap_faces(faces32, gid32)
-
     def mc3_vertices(self, f, z_offset, depths, mm_y, mm_x, z_top=None, defer=False, tot=None):
         """The production chain (pipeline.mc3_vertices): finalised, sorted, duplicate-free vertex rows of this slab plus
         the table vertex id -> row index; the triangles are written later, through a table of GLOBAL indices.
         z_top: the mapped z of the plane shared with the rank above (its rows are counted on the device); defer: return
         without reading any count when size hints exist (SlabJob._numbering_deferred reads them, once, at the end)."""
-        if not pipeline.MC3:
-            return NotImplemented
         return pipeline.mc3_vertices(f, depths, mm_y, mm_x, True, z_offset=z_offset, with_faces=False, z_top=z_top, defer=defer, tot=tot)
 
     def mc3_ready(self, f, z_offset):
@@ -705,25 +682,22 @@ class SlabJob:
             counters = torch.empty(8 + 8 * self.world, dtype=torch.int64, device=dev) if deferred else None
             m = (e.mc3_vertices(f, Za, slice_depths, mm_y, mm_x, z_top=z_top, defer=True, tot=counters[:8]) if deferred else
                  e.mc3_vertices(f, Za, slice_depths, mm_y, mm_x, z_top=z_top, defer=False))
-            if m is not NotImplemented:
-                ready = m is not None and hasattr(e, "mc3_ready") and bool(e.mc3_ready(f, Za))
-                if deferred:
-                    ticket["pending"] = self._numbering_deferred(m, f, Za, slice_depths, mm_y, mm_x, z_top, dev, counters)
-                else:
-                    ticket["mesh"] = self._global_numbering_mc3(m, slice_depths, dev, ready)
-                    ticket["numbering"] = (self.vertex_offset, self.n_vertices_global)
-                return ticket
+            ready = m is not None and hasattr(e, "mc3_ready") and bool(e.mc3_ready(f, Za))
+            if deferred:
+                ticket["pending"] = self._numbering_deferred(m, f, Za, slice_depths, mm_y, mm_x, z_top, dev, counters)
+            else:
+                ticket["mesh"] = self._global_numbering_mc3(m, slice_depths, dev, ready)
+                ticket["numbering"] = (self.vertex_offset, self.n_vertices_global)
+            return ticket
+        # an engine without the mc3 chain (the CPU oracle engine of the tests): plain marching cubes, generic numbering
         mesh = e.marching_cubes(f, Za)
-        vkey = ny = None
         if mesh is None:
             vpos = torch.zeros((0, 3), dtype=torch.float32, device=dev)
             faces32 = torch.zeros((0, 3), dtype=torch.int32, device=dev)
         else:
             vpos, faces32 = mesh.vpos, mesh.faces32
-            vkey, ny = getattr(mesh, "vkey", None), getattr(mesh, "_ny", None)
-            self._mesh_nz = getattr(mesh, "_nz", 0)
             e.finalize_vertices(vpos, slice_depths, mm_y, mm_x)
-        ticket["mesh"] = self._global_numbering(vpos, faces32, slice_depths, dev, vkey, ny)
+        ticket["mesh"] = self._global_numbering(vpos, faces32, slice_depths, dev)
         ticket["numbering"] = (self.vertex_offset, self.n_vertices_global)
         return ticket
 
@@ -820,13 +794,10 @@ class SlabJob:
         self._numbering = {"counts": counts, "n_top": n_top, "ids_next": ids_next if n_top else None, "merged": remap is not None}
         return uniq[:k], gid
 
-    def _global_numbering(self, vpos, faces32, slice_depths, dev, vkey=None, ny=None):
-        e = self.eng
-        nv = vpos.shape[0]
-        fast = vkey is not None and ny is not None and hasattr(e, "unique_mc")     # rows in marching-cubes order, with keys
+    def _global_numbering(self, vpos, faces32, slice_depths, dev):
         # ALL vertices of this rank: sorted unique rows + the index of every provisional vertex in them
-        if nv:
-            uniq, rank = e.unique_mc(vpos, vkey, ny, getattr(self, "_mesh_nz", 0)) if fast else e.unique(vpos.contiguous())
+        if vpos.shape[0]:
+            uniq, rank = self.eng.unique(vpos.contiguous())
         else:
             uniq, rank = vpos, torch.zeros(0, dtype=torch.int32, device=dev)
         kept, gid_rows = self._number_rows(uniq, slice_depths, dev)
@@ -937,8 +908,6 @@ class SlabJob:
     def _faces(self, faces32, gid):
         if faces32.shape[0] == 0:
             return torch.zeros((0, 3), dtype=torch.int64, device=faces32.device)
-        if hasattr(self.eng, "remap_faces") and self.n_vertices_global < 2 ** 31:
-            return self.eng.remap_faces(faces32, gid.to(torch.int32))
         f = gid[faces32.to(torch.int64)]
         keep = (f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 0] != f[:, 2])
         return f[keep]

@@ -19,8 +19,7 @@ if os.environ.get("TOMO_EXT"):            # debugging switches
 if os.environ.get("TOMO_SLAB_NOPACKINTO"):
     delattr(slab.HipEngine, "pack_into")
 if os.environ.get("TOMO_SLAB_NOFAST"):
-    for m in ("unique_mc", "lookup", "remap_faces"):
-        delattr(slab.HipEngine, m)
+    delattr(slab.HipEngine, "lookup")
 gz = nzr * world
 depths = np.full(gz, 1.0)
 steps = 12
