@@ -131,8 +131,13 @@ int tomo_close_ends_gp(const uint64_t *bits, int nz, int ny, int nx, uint64_t *w
  * op 0 = erosion with border_value 1, op 1 = dilation with border value 0.  in != out. */
 int tomo_morph_pass(const uint64_t *in, uint64_t *out, int nz, int ny, int nx, int op, void *stream);
 /* nops (2, 4, 6 or 8) such passes fused into one kernel: bit j of `ops` is the op of pass j (0 erosion, 1 dilation).
- * smooth_voxel_data(iterations=3, create_manifold=True) is E D | D E | D E | D E = ops 0b01010110. */
+ * smooth_voxel_data(iterations=3, create_manifold=True) spelled out is E D | D E | D E | D E = ops 0b01010110;
+ * tomo_smooth runs it as E D | D E = ops 0b0110. */
 int tomo_morph_fused(const uint64_t *in, uint64_t *out, int nz, int ny, int nx, uint32_t ops, int nops, void *stream);
+/* smooth_voxel_data (voxel_processor.py:79-97) whole, in ONE launch into `out` (in != out): the opening if
+ * create_manifold, then ONE closing if iterations >= 1 -- with the reference's border values (dilation pads with 0,
+ * erosion with 1) a closing is idempotent, so `iterations` closings leave the bits of one.  No pass at all copies. */
+int tomo_smooth(const uint64_t *in, uint64_t *out, int nz, int ny, int nx, int iterations, int create_manifold, void *stream);
 
 /* ---------------------------------------------------------------- callers either side of the path */
 /* volume_calculator.py:23-35: counts[z] (device uint64[nz]) = np.sum(voxel_data[z]); the call zeroes counts first. */

@@ -185,26 +185,13 @@ def close_ends(vol: BitVolume, inplace: bool = False) -> BitVolume:
 
 
 def smooth(vol: BitVolume, iterations: int = 3, create_manifold: bool = True) -> BitVolume:
-    """smooth_voxel_data (voxel_processor.py:79-97): opening, then `iterations` closings (3-D cross)."""
+    """smooth_voxel_data (voxel_processor.py:79-97): opening, then `iterations` closings (3-D cross).  The pass list is
+    planned in tomo_smooth (csrc/bits.hip): repeated closings are one closing, so every request is ONE launch."""
     nz, ny, nx = vol.shape
-    L = _lib.lib()
-    a = vol.bits
-    ops = ([0, 1] if create_manifold else []) + [1, 0] * int(iterations)      # 0 = erosion (border 1), 1 = dilation
-    if not ops:
-        return BitVolume(a.clone(), vol.shape)
-    bufs = [torch.empty_like(a), torch.empty_like(a)]
-    k = 0
-    cur = a
-    i = 0
-    while i < len(ops):
-        n = min(4, len(ops) - i)                   # 4 passes per launch: the barrier-free one-wave-per-tile kernel (n is even)
-        mask = sum(op << j for j, op in enumerate(ops[i:i + n]))
-        dst = bufs[k]
-        k ^= 1
-        _lib.check(L.tomo_morph_fused(_p(cur), _p(dst), nz, ny, nx, mask, n, _stream()), "tomo_morph_fused")
-        cur = dst
-        i += n
-    return BitVolume(cur, vol.shape)
+    out = torch.empty_like(vol.bits)
+    _lib.check(_lib.lib().tomo_smooth(_p(vol.bits), _p(out), nz, ny, nx, int(iterations), int(bool(create_manifold)), _stream()),
+               "tomo_smooth")
+    return BitVolume(out, vol.shape)
 
 
 # ----------------------------------------------------------------------------- field

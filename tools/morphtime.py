@@ -1,4 +1,4 @@
-"""Times smooth_voxel_data's two 4-pass launches on the 1024^3 ellipsoid (env switches: TOMO_MORPH_GENERIC, TOMO_MORPH_W)."""
+"""Times smooth_voxel_data's one 4-pass launch on the 1024^3 ellipsoid (env switch: TOMO_MORPH_PATH)."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tomography_3d_reconstructor_amd import _lib, pipeline
