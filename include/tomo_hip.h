@@ -364,7 +364,20 @@ int tomo_mesh_volume_area(const float *verts, const int64_t *faces, int64_t nf, 
  *  1. two faces are neighbours when they share an undirected edge that has exactly two faces;
  *  2. in each connected component the lowest-index face keeps its winding; every other face is reversed exactly when its
  *     parity to that face is odd; a component whose constraints contradict each other is left as given;
- *  3. if the signed volume of the result is < 0, every face is reversed.  Reversing is (a,b,c) -> (c,b,a). */
+ *  3. if the signed volume of the result is < 0, every face is reversed.  Reversing is (a,b,c) -> (c,b,a).
+ *
+ * Normals contract (NORMAL is optional and has no counterpart in the reference's file; area-weighted vertex normals).
+ * Inputs: the float32 POSITION rows exactly as the file stores them (float64 vertices are rounded first) and the faces
+ * AFTER the orientation contract, i.e. the index buffer the file stores.  Columns keep the order given, like POSITION.
+ *  1. face vector, in float64 from the float32 positions, no fused multiply-add: u = p1 - p0, w = p2 - p0,
+ *     g = (u.y w.z - u.z w.y, u.z w.x - u.x w.z, u.x w.y - u.y w.x).  Not normalised (the sum is area-weighted); a face
+ *     with a repeated index gives g = 0 by itself;
+ *  2. vertex sum s_v = sum of g_f over the corners that name v (a face that names v twice counts twice -- with g = 0), in
+ *     float64, ADDED IN ASCENDING FACE INDEX starting from +0.0: the result is a function of the input alone, the same
+ *     bytes on every run and every schedule;
+ *  3. q = s.x s.x + s.y s.y + s.z s.z (left to right).  If q is finite and > 0: n = s / sqrt(q) component by component in
+ *     float64, then rounded to float32.  Otherwise (a vertex no face names, faces that cancel, overflow) n = (0, 0, 1) and
+ *     a counter goes up by one: glTF forbids a zero-length normal. */
 /* glb_exporter.py:52-91 on the device.  z = verts[i * stride] (float32, or float64 when is_f64).  rgba: uint8 (nv, 4),
  * 4-byte aligned; 200,200,200,255 by default, 255,0,0,255 where enable1 && start1 <= z <= end1, then 0,0,255,255 where
  * enable2 && start2 <= z <= end2 (blue wins).  Comparisons in float64: the caller passes bounds already rounded the way
@@ -399,6 +412,17 @@ int tomo_glb_pack_faces(const int64_t *faces, int64_t nf, const uint8_t *flip, c
 /* POSITION: verts (nv x 3, float32 or float64) -> float32 pos (4-byte aligned), and minmax[6] = per-column min then max of
  * pos, reduced exactly in float32 (glTF requires min / max on POSITION). */
 int tomo_glb_pack_positions(const void *verts, int is_f64, int64_t nv, float *pos, float *minmax, void *stream);
+/* The normals contract.  pos: float32 (nv, 3); idx: the oriented faces (nf, 3), uint32 or (idx_i64) int64; normals: float32
+ * (nv, 3), 4-byte aligned (the NORMAL block of the chunk).  counters[2] (zeroed by the call): [0] vertices that got the
+ * default (0, 0, 1), [1] faces with an index outside [0, nv) -- they enter no sum and nothing is read through them; the mesh
+ * is invalid when this is not 0.  No float atomics: an inverted index (per vertex the faces that name it: integer atomics
+ * count and fill it, tomo_mc_scan places the lists), and one lane per vertex brings its list into ascending order -- in
+ * registers up to 16 entries, by repeated selection across the wave beyond -- and sums.  workspace: 256-byte aligned,
+ * tomo_mesh_vertex_normals_workspace_bytes(nv, nf) bytes (about 8 nv + 12 nf); nv < 2^32 - 1 and 3 nf < 2^32
+ * (TOMO_E_SIZE otherwise). */
+int64_t tomo_mesh_vertex_normals_workspace_bytes(int64_t nv, int64_t nf);
+int tomo_mesh_vertex_normals(const float *pos, int64_t nv, const void *idx, int idx_i64, int64_t nf, void *workspace,
+                             int64_t workspace_bytes, float *normals, unsigned long long *counters, void *stream);
 
 #ifdef __cplusplus
 }

@@ -117,6 +117,8 @@ SIGNATURES = {
     "tomo_mesh_signed_volume": (_c_i, [_c_p, _c_p, _c_i64, _c_p, _c_p, _c_p]),
     "tomo_glb_pack_faces": (_c_i, [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_i, _c_p]),
     "tomo_glb_pack_positions": (_c_i, [_c_p, _c_i, _c_i64, _c_p, _c_p, _c_p]),
+    "tomo_mesh_vertex_normals_workspace_bytes": (_c_i64, [_c_i64, _c_i64]),
+    "tomo_mesh_vertex_normals": (_c_i, [_c_p, _c_i64, _c_p, _c_i, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p]),
 }
 
 _LIB = None

@@ -303,7 +303,224 @@ __global__ __launch_bounds__(BLOCK) void pack_positions_kernel(const T *__restri
     }
 }
 
+// ---- vertex normals (the normals contract in include/tomo_hip.h) ----------------------------------------------------------
+// An inverted index instead of float atomics: per vertex the list of the faces that name it (one entry per corner), built
+// with integer atomics in whatever order the corners arrive, then put into ascending order by the kernel that sums -- so
+// the float64 sums do not depend on the schedule.  A face with an index outside [0, nv) enters no list and is counted.
+constexpr int NRM_REG = 16;            // lists up to this length are sorted in registers (a marching-cubes vertex has 4-9 faces)
+
+template <typename I>
+__device__ static inline bool face_corners(const I *__restrict__ idx, int64_t f, int64_t nv, u64 c[3])
+{
+    c[0] = (u64)idx[3 * f];
+    c[1] = (u64)idx[3 * f + 1];
+    c[2] = (u64)idx[3 * f + 2];
+    return c[0] < (u64)nv && c[1] < (u64)nv && c[2] < (u64)nv;          // a negative int64 is a huge u64
+}
+
+template <typename I>
+__global__ __launch_bounds__(BLOCK) void normals_count_kernel(const I *__restrict__ idx, int64_t nf, int64_t nv, u32 *__restrict__ deg,
+                                                               unsigned long long *__restrict__ counters)
+{
+    u32 bad = 0;
+    for (int64_t f = (int64_t)blockIdx.x * BLOCK + threadIdx.x; f < nf; f += (int64_t)gridDim.x * BLOCK) {
+        u64 c[3];
+        if (!face_corners(idx, f, nv, c)) { bad++; continue; }
+#pragma unroll
+        for (int k = 0; k < 3; k++) atomicAdd(&deg[c[k]], 1u);
+    }
+    wave_add(&counters[1], bad);
+}
+
+// deg counts down to zero: the slot of a corner is off[v] + (what is left of deg[v]) - 1
+template <typename I>
+__global__ __launch_bounds__(BLOCK) void normals_fill_kernel(const I *__restrict__ idx, int64_t nf, int64_t nv, u32 *__restrict__ deg,
+                                                              const u32 *__restrict__ off, u32 *__restrict__ list)
+{
+    for (int64_t f = (int64_t)blockIdx.x * BLOCK + threadIdx.x; f < nf; f += (int64_t)gridDim.x * BLOCK) {
+        u64 c[3];
+        if (!face_corners(idx, f, nv, c)) continue;
+#pragma unroll
+        for (int k = 0; k < 3; k++) list[off[c[k]] + (atomicSub(&deg[c[k]], 1u) - 1u)] = (u32)f;
+    }
+}
+
+// rule 1 of the contract: float64 from the float32 positions, no fused multiply-add (the build passes -ffp-contract=off)
+template <typename I>
+__device__ static inline void face_vector(const float *__restrict__ pos, const I *__restrict__ idx, u32 f, double g[3])
+{
+    const float *p0 = pos + 3 * (int64_t)idx[3 * (int64_t)f], *p1 = pos + 3 * (int64_t)idx[3 * (int64_t)f + 1],
+                *p2 = pos + 3 * (int64_t)idx[3 * (int64_t)f + 2];
+    const double ux = (double)p1[0] - (double)p0[0], uy = (double)p1[1] - (double)p0[1], uz = (double)p1[2] - (double)p0[2];
+    const double wx = (double)p2[0] - (double)p0[0], wy = (double)p2[1] - (double)p0[1], wz = (double)p2[2] - (double)p0[2];
+    g[0] = uy * wz - uz * wy;
+    g[1] = uz * wx - ux * wz;
+    g[2] = ux * wy - uy * wx;
+}
+
+// One lane per vertex.  A list of at most NRM_REG entries is sorted in registers (odd-even transposition, padded with
+// 0xffffffff: a face number is below 2^32 / 3) and summed by its lane.  Longer lists are taken one at a time by the whole
+// wave: each step finds the smallest face number above the last one summed and how often it occurs (a face that names the
+// vertex twice has two entries), so the order is exact for any length without memory for a sorted copy.
+template <typename I>
+__global__ __launch_bounds__(BLOCK) void vertex_normals_kernel(const float *__restrict__ pos, int64_t nv, const I *__restrict__ idx,
+                                                                const u32 *__restrict__ off, const u32 *__restrict__ list,
+                                                                float *__restrict__ normals, unsigned long long *__restrict__ counters)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6, nwaves = (int64_t)gridDim.x * (BLOCK / 64);
+    u32 defaulted = 0;
+    for (int64_t base = wave * 64; base < nv; base += nwaves * 64) {
+        const int64_t v = base + lane;
+        u32 o = 0, d = 0;
+        if (v < nv) {
+            o = off[v];
+            d = off[v + 1] - o;
+        }
+        double s[3] = {0.0, 0.0, 0.0};
+        if (d <= NRM_REG) {
+            u32 key[NRM_REG];
+#pragma unroll
+            for (int k = 0; k < NRM_REG; k++) key[k] = (u32)k < d ? list[o + k] : 0xffffffffu;
+#pragma unroll
+            for (int r = 0; r < NRM_REG; r++) {
+#pragma unroll
+                for (int i = r & 1; i + 1 < NRM_REG; i += 2) {
+                    const u32 a = key[i], b = key[i + 1];
+                    key[i] = a < b ? a : b;
+                    key[i + 1] = a < b ? b : a;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < NRM_REG; k++) {
+                if ((u32)k < d) {
+                    double g[3];
+                    face_vector(pos, idx, key[k], g);
+                    s[0] += g[0];
+                    s[1] += g[1];
+                    s[2] += g[2];
+                }
+            }
+        }
+        u64 longer = __ballot(d > NRM_REG);
+        while (longer) {
+            const int src = __ffsll((long long)longer) - 1;
+            longer &= longer - 1;
+            const u32 lo = __shfl(o, src, 64), ld = __shfl(d, src, 64);
+            double t[3] = {0.0, 0.0, 0.0};
+            int64_t last = -1;
+            for (u32 done = 0; done < ld;) {
+                u32 m = 0xffffffffu, c = 0;
+                for (u32 k = lane; k < ld; k += 64) {
+                    const u32 f = list[lo + k];
+                    if ((int64_t)f <= last) continue;
+                    if (f < m) { m = f; c = 1; }
+                    else if (f == m) c++;
+                }
+                u32 best = m;
+#pragma unroll
+                for (int w = 32; w > 0; w >>= 1) {
+                    const u32 x = __shfl_xor(best, w, 64);
+                    best = x < best ? x : best;
+                }
+                const u32 times = wave_sum(m == best ? c : 0u);
+                if (best == 0xffffffffu || times == 0) break;          // cannot happen with the lists the fill kernel wrote
+                double g[3];
+                face_vector(pos, idx, best, g);
+                for (u32 j = 0; j < times; j++) {
+                    t[0] += g[0];
+                    t[1] += g[1];
+                    t[2] += g[2];
+                }
+                last = (int64_t)best;
+                done += times;
+            }
+            if (lane == src) {
+                s[0] = t[0];
+                s[1] = t[1];
+                s[2] = t[2];
+            }
+        }
+        if (v < nv) {
+            const double q = s[0] * s[0] + s[1] * s[1] + s[2] * s[2];
+            float n[3] = {0.0f, 0.0f, 1.0f};
+            if (q > 0.0 && q < (double)INFINITY) {                      // finite and positive (a NaN fails both)
+                const double r = sqrt(q);
+                n[0] = (float)(s[0] / r);
+                n[1] = (float)(s[1] / r);
+                n[2] = (float)(s[2] / r);
+            } else {
+                defaulted++;
+            }
+            normals[3 * v] = n[0];
+            normals[3 * v + 1] = n[1];
+            normals[3 * v + 2] = n[2];
+        }
+    }
+    wave_add(&counters[0], defaulted);
+}
+
+// Workspace of the normals: deg u32[nv] | off u32[nv + 1] | list u32[3 nf] | totals u64[4] | scan workspace, each part on
+// a 256-byte boundary.
+struct NormalsWs {
+    int64_t off, list, totals, scan, scan_bytes, total;
+};
+static inline int64_t up256(int64_t x) { return (x + 255) & ~(int64_t)255; }
+static inline NormalsWs normals_ws(int64_t nv, int64_t nf)
+{
+    NormalsWs w;
+    w.off = up256(4 * nv);
+    w.list = w.off + up256(4 * (nv + 1));
+    w.totals = w.list + up256(12 * nf);
+    w.scan = w.totals + 256;
+    w.scan_bytes = tomo_mc_scan_workspace_bytes(nv);
+    w.total = w.scan + up256(w.scan_bytes);
+    return w;
+}
+static inline bool normals_sizes_ok(int64_t nv, int64_t nf) { return nv < (int64_t)0xffffffffLL && 3 * nf < ((int64_t)1 << 32); }
+
 }  // namespace
+
+TOMO_API int64_t tomo_mesh_vertex_normals_workspace_bytes(int64_t nv, int64_t nf)
+{
+    if (nv <= 0 || nf <= 0) return TOMO_E_ARG;
+    if (!normals_sizes_ok(nv, nf)) return TOMO_E_SIZE;
+    return normals_ws(nv, nf).total;
+}
+
+TOMO_API int tomo_mesh_vertex_normals(const float *pos, int64_t nv, const void *idx, int idx_i64, int64_t nf, void *workspace,
+                                      int64_t workspace_bytes, float *normals, unsigned long long *counters, void *stream)
+{
+    if (!pos || !idx || !workspace || !normals || !counters || nv <= 0 || nf <= 0) return TOMO_E_ARG;
+    if (((uintptr_t)pos & 3) || ((uintptr_t)normals & 3) || ((uintptr_t)idx & (idx_i64 ? 7 : 3)) || ((uintptr_t)workspace & 255) ||
+        ((uintptr_t)counters & 7))
+        return TOMO_E_ARG;
+    if (!normals_sizes_ok(nv, nf)) return TOMO_E_SIZE;
+    const NormalsWs w = normals_ws(nv, nf);
+    if (workspace_bytes < w.total) return TOMO_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    char *base = (char *)workspace;
+    u32 *deg = (u32 *)base, *off = (u32 *)(base + w.off), *list = (u32 *)(base + w.list);
+    if (hipMemsetAsync(deg, 0, 4 * nv, st) != hipSuccess || hipMemsetAsync(counters, 0, 2 * sizeof(unsigned long long), st) != hipSuccess)
+        return TOMO_E_LAUNCH;
+    const unsigned gf = grid_for(nf), gv = grid_for(nv);
+    if (idx_i64)
+        hipLaunchKernelGGL(normals_count_kernel<int64_t>, dim3(gf), dim3(BLOCK), 0, st, (const int64_t *)idx, nf, nv, deg, counters);
+    else
+        hipLaunchKernelGGL(normals_count_kernel<uint32_t>, dim3(gf), dim3(BLOCK), 0, st, (const uint32_t *)idx, nf, nv, deg, counters);
+    const int rc = tomo_mc_scan(deg, nv, off, nullptr, nullptr, (unsigned long long *)(base + w.totals), base + w.scan, w.scan_bytes, st);
+    if (rc != TOMO_OK) return rc;
+    if (idx_i64) {
+        hipLaunchKernelGGL(normals_fill_kernel<int64_t>, dim3(gf), dim3(BLOCK), 0, st, (const int64_t *)idx, nf, nv, deg, off, list);
+        hipLaunchKernelGGL(vertex_normals_kernel<int64_t>, dim3(gv), dim3(BLOCK), 0, st, pos, nv, (const int64_t *)idx, off, list, normals,
+                           counters);
+    } else {
+        hipLaunchKernelGGL(normals_fill_kernel<uint32_t>, dim3(gf), dim3(BLOCK), 0, st, (const uint32_t *)idx, nf, nv, deg, off, list);
+        hipLaunchKernelGGL(vertex_normals_kernel<uint32_t>, dim3(gv), dim3(BLOCK), 0, st, pos, nv, (const uint32_t *)idx, off, list, normals,
+                           counters);
+    }
+    return tomo_status();
+}
 
 TOMO_API int tomo_layer_colors(const void *verts, int is_f64, int64_t nv, int64_t stride, double start1, double end1, int enable1,
                                double start2, double end2, int enable2, uint8_t *rgba, void *stream)

@@ -3,7 +3,13 @@ lines, with the work of trimesh (fix_normals, export as GLB) and of create_layer
 (csrc/glb.hip; pipeline.layer_colors / glb_pack underneath).  The file is a valid glTF 2.0 binary with the orientation of
 the contract in include/tomo_hip.h; it is not byte-identical to a trimesh-written file.  trimesh is not
 needed.  No CPU fallback.
+
+Optional, beyond the reference: with `include_normals` set (an instance attribute; TOMO_GLB_NORMALS=1 in the environment
+turns it on for every new exporter, so the reference's unchanged orchestrator gets it too) the file also carries NORMAL,
+the area-weighted vertex normals of the normals contract in include/tomo_hip.h.  Off by default: the file is then byte for
+byte what it was.
 """
+import os
 from typing import Optional
 
 import numpy as np
@@ -28,7 +34,7 @@ class GLBExporter:
     """Handles exporting 3D models to GLB file format (reference: glb_exporter.py:20)."""
 
     def __init__(self):
-        pass
+        self.include_normals = os.environ.get("TOMO_GLB_NORMALS", "0") not in ("", "0")
 
     def export_to_glb(self, vertices: np.ndarray, faces: np.ndarray,
                       filename: str = "tomography_model.glb",
@@ -48,12 +54,13 @@ class GLBExporter:
                 if c.dtype != np.uint8 or c.ndim != 2 or c.shape[0] != len(v) or c.shape[1] not in (3, 4):
                     raise ValueError("vertex colours must be uint8 (V, 3) or (V, 4), got %s %s" % (c.dtype, c.shape))
                 cc = c.shape[1]
-            pipeline.glb_check_sizes(len(v), len(f), cc)             # from the shapes, before anything is copied
+            normals = bool(self.include_normals)
+            pipeline.glb_check_sizes(len(v), len(f), cc, normals)    # from the shapes, before anything is copied
             if v.dtype not in (np.float32, np.float64):
                 v = v.astype(np.float64)
             vt, ft = _upload(v), _upload(f.astype(np.int64, copy=False))
             ct = _upload(c) if cc else None
-            pipeline.export_glb(filename, vt, ft, ct)
+            pipeline.export_glb(filename, vt, ft, ct, normals)
             print(f"Model exported: {filename}")
             return True
         except pipeline._lib.TomoUnavailable:

@@ -858,7 +858,8 @@ def ellipsoid_mask(nz, ny, nx, device, z0=0, z1=None):
 
 
 # ---- GLB export (glb_exporter.py of the reference) ----------------------------------------------------
-# The orientation contract is written out in include/tomo_hip.h (trimesh's fix_normals(multibody=False) restated).
+# The orientation contract is written out in include/tomo_hip.h (trimesh's fix_normals(multibody=False) restated), and below
+# it the normals contract of the optional NORMAL attribute.
 GLB_MAX_BYTES = (1 << 32) - 1          # the GLB header's length field
 
 
@@ -963,9 +964,44 @@ def orient_faces(verts: torch.Tensor, faces: torch.Tensor):
     return out, stats
 
 
+def _vertex_normals_launch(pos_ptr, nv, idx_ptr, idx_i64, nf, normals_ptr, counters_ptr, dev):
+    """tomo_mesh_vertex_normals with its workspace (enqueue only; the workspace is handed back to the caching allocator,
+    which keeps it for this stream until the kernels are through)."""
+    L = _lib.lib()
+    wsb = L.tomo_mesh_vertex_normals_workspace_bytes(nv, nf)
+    if wsb < 0:
+        raise ValueError("the mesh is too large for the vertex-normal lists: %d vertices, %d faces" % (nv, nf))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    _lib.check(L.tomo_mesh_vertex_normals(pos_ptr, nv, idx_ptr, idx_i64, nf, _p(ws), wsb, normals_ptr, counters_ptr, _stream()),
+               "tomo_mesh_vertex_normals")
+
+
+def vertex_normals(verts: torch.Tensor, faces: torch.Tensor, oriented: bool = False, counts: torch.Tensor = None) -> torch.Tensor:
+    """Area-weighted vertex normals on the device (the normals contract in include/tomo_hip.h): float32 (V, 3), the same
+    bytes on every run.  faces: as given (orient_faces runs first) or, with oriented=True, already oriented -- then an index
+    outside [0, V) is not an error here: the face enters no sum and is counted.  counts: an optional int64 (2,) device
+    tensor that receives [vertices that got the default (0, 0, 1), faces skipped]; nothing here waits for the device, the
+    caller reads it when it wants to."""
+    verts, faces = _glb_mesh(verts, faces)
+    if not oriented:
+        faces, _ = orient_faces(verts, faces)
+    nv, nf = verts.shape[0], faces.shape[0]
+    if nv == 0:
+        raise ValueError("no vertices")
+    pos = verts if verts.dtype == torch.float32 else verts.to(torch.float32)      # POSITION as the file stores it
+    if counts is None:
+        counts = torch.empty(2, dtype=torch.int64, device=verts.device)
+    elif counts.dtype != torch.int64 or counts.numel() != 2 or not counts.is_contiguous() or counts.device != verts.device:
+        raise ValueError("counts must be a contiguous int64 (2,) tensor on the mesh's device")
+    normals = torch.empty((nv, 3), dtype=torch.float32, device=verts.device)
+    _vertex_normals_launch(_p(pos), nv, _p(faces), 1, nf, _p(normals), _p(counts), verts.device)
+    return normals
+
+
 @dataclass
 class GlbPacked:
-    """The binary chunk of a GLB on the device (`buf[:bin_len]`), with min / max of POSITION and the signed volume in a tail."""
+    """The binary chunk of a GLB on the device (`buf[:bin_len]`), with min / max of POSITION, the signed volume and (with
+    normals) the normals' two counters in a tail."""
     buf: torch.Tensor
     nv: int
     nf: int
@@ -973,14 +1009,16 @@ class GlbPacked:
     bin_len: int
     tail: int
     stats: dict
+    normals: bool = False
 
 
-def glb_layout_bytes(nv: int, nf: int, color_cols: int = 0) -> int:
-    """Bytes of the binary chunk: POSITION (12 V) | indices (12 F) | COLOR_0 (4 V, one 4-byte element per vertex)."""
-    return 12 * nv + 12 * nf + (4 * nv if color_cols else 0)
+def glb_layout_bytes(nv: int, nf: int, color_cols: int = 0, normals: bool = False) -> int:
+    """Bytes of the binary chunk: POSITION (12 V) | indices (12 F) | COLOR_0 (4 V, one 4-byte element per vertex) | NORMAL
+    (12 V, last: the blocks before it sit where they sit without it)."""
+    return 12 * nv + 12 * nf + (4 * nv if color_cols else 0) + (12 * nv if normals else 0)
 
 
-def glb_check_sizes(nv: int, nf: int, color_cols: int = 0):
+def glb_check_sizes(nv: int, nf: int, color_cols: int = 0, normals: bool = False):
     """The limits a GLB of this mesh must fit, checked from the shapes alone (before anything is copied)."""
     if nf == 0:
         raise ValueError("no faces")
@@ -988,13 +1026,14 @@ def glb_check_sizes(nv: int, nf: int, color_cols: int = 0):
         raise ValueError("%d vertices do not fit 32-bit GLB indices" % nv)
     if color_cols not in (0, 3, 4):
         raise ValueError("vertex colours must be uint8 (V, 3) or (V, 4)")
-    if 12 + 8 + 8 + 1024 + glb_layout_bytes(nv, nf, color_cols) > GLB_MAX_BYTES:
+    if 12 + 8 + 8 + 1024 + glb_layout_bytes(nv, nf, color_cols, normals) > GLB_MAX_BYTES:
         raise ValueError("the GLB would exceed the 4 GiB length field (%d vertices, %d faces)" % (nv, nf))
 
 
-def glb_pack(verts: torch.Tensor, faces: torch.Tensor, colors: torch.Tensor = None) -> GlbPacked:
+def glb_pack(verts: torch.Tensor, faces: torch.Tensor, colors: torch.Tensor = None, normals: bool = False) -> GlbPacked:
     """Steps 2-3 of the export on the device: edge table, orientation (fast path or union-find), inversion decision, and the
-    binary chunk -- positions, oriented uint32 indices and colours -- packed in one device buffer."""
+    binary chunk -- positions, oriented uint32 indices, colours and (normals=True) the vertex normals of the normals
+    contract, computed from the chunk's own POSITION and index blocks -- packed in one device buffer."""
     verts, faces = _glb_mesh(verts, faces)
     nv, nf = verts.shape[0], faces.shape[0]
     cc = 0
@@ -1002,12 +1041,13 @@ def glb_pack(verts: torch.Tensor, faces: torch.Tensor, colors: torch.Tensor = No
         if colors.dtype != torch.uint8 or colors.dim() != 2 or colors.shape[0] != nv or colors.shape[1] not in (3, 4):
             raise ValueError("vertex colours must be uint8 (V, 3) or (V, 4)")
         cc = colors.shape[1]
-    glb_check_sizes(nv, nf, cc)
+    normals = bool(normals)
+    glb_check_sizes(nv, nf, cc, normals)
     L = _lib.lib()
     flip, stats = _edge_stats(faces, nv)
-    bin_len = glb_layout_bytes(nv, nf, cc)
+    bin_len = glb_layout_bytes(nv, nf, cc, normals)
     tail = (bin_len + 7) & ~7
-    buf = torch.empty(tail + 32, dtype=torch.uint8, device=verts.device)
+    buf = torch.empty(tail + (48 if normals else 32), dtype=torch.uint8, device=verts.device)
     buf[tail + 24:].zero_()
     base, st = buf.data_ptr(), _stream()
     _lib.check(L.tomo_glb_pack_positions(_p(verts), 1 if verts.dtype == torch.float64 else 0, nv, base, base + tail, st),
@@ -1015,11 +1055,13 @@ def glb_pack(verts: torch.Tensor, faces: torch.Tensor, colors: torch.Tensor = No
     _lib.check(L.tomo_mesh_signed_volume(base, _p(faces), nf, _p(flip), base + tail + 24, st), "tomo_mesh_signed_volume")
     _lib.check(L.tomo_glb_pack_faces(_p(faces), nf, _p(flip), base + tail + 24, base + 12 * nv, 0, st), "tomo_glb_pack_faces")
     if cc:
-        cv = buf[12 * nv + 12 * nf: bin_len].view(nv, 4)
+        cv = buf[12 * nv + 12 * nf: 16 * nv + 12 * nf].view(nv, 4)
         cv[:, :cc].copy_(colors)
         if cc == 3:
             cv[:, 3].zero_()
-    return GlbPacked(buf, nv, nf, cc, bin_len, tail, stats)
+    if normals:
+        _vertex_normals_launch(base, nv, base + 12 * nv, 0, nf, base + bin_len - 12 * nv, base + tail + 32, verts.device)
+    return GlbPacked(buf, nv, nf, cc, bin_len, tail, stats, normals)
 
 
 def glb_download(p: GlbPacked) -> np.ndarray:
@@ -1042,6 +1084,10 @@ def glb_json(p: GlbPacked, minmax) -> dict:
         views.append({"buffer": 0, "byteOffset": 12 * p.nv + 12 * p.nf, "byteLength": 4 * p.nv, "byteStride": 4, "target": 34962})
         accessors.append({"bufferView": 2, "componentType": 5121, "normalized": True, "count": p.nv,
                           "type": "VEC4" if p.color_cols == 4 else "VEC3"})
+    if p.normals:
+        attrs["NORMAL"] = len(accessors)
+        views.append({"buffer": 0, "byteOffset": p.bin_len - 12 * p.nv, "byteLength": 12 * p.nv, "target": 34962})
+        accessors.append({"bufferView": len(views) - 1, "componentType": 5126, "count": p.nv, "type": "VEC3"})
     return {"asset": {"version": "2.0", "generator": "tomography_3d_reconstructor_amd"},
             "scene": 0, "scenes": [{"nodes": [0]}], "nodes": [{"mesh": 0}],
             "meshes": [{"primitives": [{"attributes": attrs, "indices": 1, "mode": 4}]}],
@@ -1069,11 +1115,14 @@ def glb_write(path, p: GlbPacked, host: np.ndarray) -> dict:
     stats = dict(p.stats)
     stats["inverted"] = vol < 0
     stats["signed_volume"] = -vol if vol < 0 else vol
+    if p.normals:
+        stats["normals_defaulted"] = int(host[p.tail + 32: p.tail + 40].view(np.uint64)[0])
     return stats
 
 
-def export_glb(path, verts: torch.Tensor, faces: torch.Tensor, colors: torch.Tensor = None) -> dict:
+def export_glb(path, verts: torch.Tensor, faces: torch.Tensor, colors: torch.Tensor = None, normals: bool = False) -> dict:
     """GLBExporter.export_to_glb for device tensors: orient (the contract in include/tomo_hip.h), pack, download once, write.
-    Returns the orientation stats (see orient_faces)."""
-    p = glb_pack(verts, faces, colors)
+    Returns the orientation stats (see orient_faces); with normals=True the file carries NORMAL (the normals contract) and
+    the stats `normals_defaulted`, the number of vertices that got the default (0, 0, 1)."""
+    p = glb_pack(verts, faces, colors, normals)
     return glb_write(path, p, glb_download(p))

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """GLB export at n^3 (default 1024): GLBExporter.export_to_glb host to host, split into upload, device work (edge table,
 orientation check, pack), download and write; the device work alone on the fast path and on the same mesh with 30 % of
-its faces reversed (the union-find path); create_layer_colors on the device next to the reference's NumPy passes.
+its faces reversed (the union-find path); the same with the optional NORMAL attribute (vertex normals, the normals contract
+of include/tomo_hip.h); create_layer_colors on the device next to the reference's NumPy passes.
 
     python tools/glbtime.py [--n 1024] [--reps 5] [--out glbtime.json]
 """
@@ -93,9 +94,19 @@ def main():
         del p, host, vt, ft, ct
     res["split_ms_median"] = {k: round(float(np.median(x)), 3) for k, x in split.items()}
     res["file_bytes"] = os.path.getsize(path)
+    g.include_normals = True                                                    # the same call with NORMAL in the file
+    with contextlib.redirect_stdout(io.StringIO()):
+        g.export_to_glb(vn, fn, path, colors)
+        res["export_to_glb_normals"] = ms(lambda: g.export_to_glb(vn, fn, path, colors), a.reps)
+    res["file_bytes_normals"] = os.path.getsize(path)
+    g.include_normals = False
 
     # device work alone: fast path, and the same mesh with 30 % of the faces reversed (union-find)
     res["device_fast"] = ms(lambda: pipeline.glb_pack(v, f, None), a.reps)
+    res["device_fast_normals"] = ms(lambda: pipeline.glb_pack(v, f, None, True), a.reps)
+    oriented = f.flip(1).contiguous()
+    res["vertex_normals_alone"] = ms(lambda: pipeline.vertex_normals(v, oriented, oriented=True), a.reps)
+    del oriented
     fs = fn.copy()
     sel = np.random.default_rng(30).random(nf) < 0.30
     fs[sel] = fs[sel][:, ::-1]
