@@ -78,16 +78,21 @@ class RawMesh:
 
 
 # ----------------------------------------------------------------------------- binary stages
-def pack(mask: torch.Tensor, out: torch.Tensor = None) -> BitVolume:
-    """np.stack(mask_images) (voxel_processor.py:46) as a device uint8/bool tensor -> BitVolume (into `out`, a contiguous
-    int64 (nz, ny, words) tensor -- e.g. the middle of a halo-extended buffer -- when given)."""
+def _mask_u8(mask: torch.Tensor) -> torch.Tensor:
+    """A (nz, ny, nx) bool / uint8 mask stack as the contiguous uint8 tensor the pack kernels read."""
     if mask.dim() != 3:
         raise ValueError("mask must be (nz, ny, nx)")
     if mask.dtype == torch.bool:
         mask = mask.view(torch.uint8)
     if mask.dtype != torch.uint8:
         raise TypeError("mask must be bool or uint8")
-    mask = mask.contiguous()
+    return mask.contiguous()
+
+
+def pack(mask: torch.Tensor, out: torch.Tensor = None) -> BitVolume:
+    """np.stack(mask_images) (voxel_processor.py:46) as a device uint8/bool tensor -> BitVolume (into `out`, a contiguous
+    int64 (nz, ny, words) tensor -- e.g. the middle of a halo-extended buffer -- when given)."""
+    mask = _mask_u8(mask)
     nz, ny, nx = mask.shape
     L = _lib.lib()
     wx = L.tomo_words_per_row(nx)
@@ -151,13 +156,7 @@ def pack_closed(mask: torch.Tensor) -> BitVolume:
     """np.stack + _close_volume_ends (voxel_processor.py:46, :56-77) from a device uint8 / bool (nz, ny, nx) mask stack in ONE
     pass over the mask where the layout allows it (nz >= 3, nx % 16 == 0): pack + fill the end slices, then the fused
     pack + stencil kernel; otherwise pack, then close_ends in place."""
-    if mask.dim() != 3:
-        raise ValueError("mask must be (nz, ny, nx)")
-    if mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
-    if mask.dtype != torch.uint8:
-        raise TypeError("mask must be bool or uint8")
-    mask = mask.contiguous()
+    mask = _mask_u8(mask)
     nz, ny, nx = mask.shape
     if nz < 3 or nx % 16 != 0 or mask.data_ptr() % 16 != 0 or not PACK_CLOSE_FUSED:
         return close_ends(pack(mask), inplace=True)
@@ -217,12 +216,11 @@ def make_field(vol: BitVolume, manifold: bool = True, add_padding: bool = True, 
         sbuf = torch.empty(L.tomo_sign_buffer_words(Nz, Ny, Nx, xorg), dtype=torch.int64, device=vol.device)
         signs = sbuf[: Nz * S * NyP * 4].view(Nz, S, NyP, 4)
         gcls = torch.empty((Nz, NyP // 16, S), dtype=torch.uint8, device=vol.device)
-    is_sparse = False
-    if manifold and FIELD_FROM_BITS and sparse and fused:
+    is_sparse = bool(manifold and FIELD_FROM_BITS and sparse and fused)
+    if is_sparse:
         span = torch.empty(L.tomo_field_span_bytes(nz, ny, nx, pad), dtype=torch.uint8, device=vol.device)
         _lib.check(L.tomo_field_fill_bits_sparse(_p(vol.bits), _p(data), nz, ny, nx, pad, _p(sbuf), _p(gcls), _p(span), _stream()),
                    "tomo_field_fill_bits_sparse")
-        is_sparse = True
     elif manifold and FIELD_FROM_BITS:
         # the Gaussian field straight from the bit volume: border rules applied while the kernel stages its input
         _lib.check(L.tomo_field_fill_bits(_p(vol.bits), _p(data), nz, ny, nx, pad, _p(sbuf), _p(gcls), _stream()),
@@ -233,9 +231,7 @@ def make_field(vol: BitVolume, manifold: bool = True, add_padding: bool = True, 
         _lib.check(L.tomo_extend_bits(_p(vol.bits), _p(ext), nz, ny, nx, pad, _stream()), "tomo_extend_bits")
         _lib.check(L.tomo_field_fill(_p(ext), _p(data), nz, ny, nx, pad, 1 if manifold else 0, _p(sbuf), _p(gcls), _stream()),
                    "tomo_field_fill")
-    f = Field(data, Nz, Ny, Nx, pitch, xorg, signs, 0.5, gcls)
-    f.sparse = is_sparse
-    return f
+    return Field(data, Nz, Ny, Nx, pitch, xorg, signs, 0.5, gcls, sparse=is_sparse)
 
 
 def field_signs(f: Field, level: float, z_begin: int = 0, z_end: int = None):
@@ -262,6 +258,20 @@ def field_from_dense(dense: torch.Tensor) -> Field:
 
 
 # ----------------------------------------------------------------------------- marching cubes
+def _check_limits(na, nv=0, nf=0, ids=1):
+    """TomoError when a pass leaves the 32-bit index range: na list entries (LIST_LIMIT; `ids` int32 table entries per list
+    position -- 4 in the mc3 chain), nv vertices / nf triangles (MESH_LIMIT)."""
+    if na >= LIST_LIMIT or na * ids >= 2 ** 31:
+        raise _lib.TomoError("surface too large for 32-bit indices")
+    if nv >= MESH_LIMIT or nf >= MESH_LIMIT:
+        raise _lib.TomoError("mesh too large for 32-bit indices")
+
+
+def drop_degenerate(faces: torch.Tensor) -> torch.Tensor:
+    """Triangles with three distinct vertex indices, order kept (surface_extractor.py:122-125)."""
+    return faces[(faces[:, 0] != faces[:, 1]) & (faces[:, 1] != faces[:, 2]) & (faces[:, 0] != faces[:, 2])]
+
+
 def marching_cubes(f: Field, level: float = 0.5, z_offset: int = 0):
     """skimage.measure.marching_cubes(volume, level) (surface_extractor.py:55) -> RawMesh or None.
 
@@ -279,7 +289,7 @@ def marching_cubes(f: Field, level: float = 0.5, z_offset: int = 0):
     nseg = f.Nz * f.Ny * spr
     # pass 1: active voxels per segment, scan, list of active segments
     if f.signs is None or f.signs_level != lvl:
-        if getattr(f, "sparse", False):
+        if f.sparse:
             raise _lib.TomoError("a sparse field holds floats only near the 0.5 surface: other levels need make_field(sparse=False)")
         field_signs(f, lvl)
     seg_act = torch.empty(nseg * 4, dtype=torch.int64, device=dev)   # 32-byte record per NON-EMPTY segment
@@ -325,8 +335,7 @@ def marching_cubes(f: Field, level: float = 0.5, z_offset: int = 0):
         na = int(totals[0].item())
         if na == 0:
             return None
-        if na >= LIST_LIMIT:
-            raise _lib.TomoError("surface too large for 32-bit indices")
+        _check_limits(na)
         vox_key = torch.empty(na, dtype=torch.int64, device=dev)
         _lib.check(L.tomo_mc_list(f.Nz, f.Ny, f.Nx, f.xorg, _p(seg_aoff), _p(seg_act), _p(vox_key), st), "tomo_mc_list")
         vox_counts = torch.empty(na, dtype=torch.int32, device=dev)
@@ -345,8 +354,7 @@ def marching_cubes(f: Field, level: float = 0.5, z_offset: int = 0):
     _NA_HINT[hint_key] = na
     if nv == 0:
         return None
-    if nv >= MESH_LIMIT or nf >= MESH_LIMIT:
-        raise _lib.TomoError("mesh too large for 32-bit indices")
+    _check_limits(na, nv, nf)
     # pass 4: vertices and triangles
     vkey = torch.empty(nv, dtype=torch.int64, device=dev)
     vpos = torch.empty((nv, 3), dtype=torch.float32, device=dev)
@@ -379,16 +387,18 @@ def _depth_tables_on_device(d, add_padding, dev):
     return hit
 
 
+def _depth_args(slice_depths, add_padding, dev):
+    """The depth table as the vertex kernels take it: (cum tensor, its length, adj tensor, its length); no table: (None, 0, None, 0)."""
+    d = np.ascontiguousarray(slice_depths, dtype=np.float64)
+    if not len(d):
+        return None, 0, None, 0
+    cum_t, adj_t = _depth_tables_on_device(d, add_padding, dev)
+    return cum_t, cum_t.shape[0], adj_t, adj_t.shape[0]
+
+
 def finalize_vertices(vpos: torch.Tensor, slice_depths, mm_per_pixel_y, mm_per_pixel_x, manifold=True, add_padding=True):
     """surface_extractor.py:57-65 and :82-113, in place on the (V,3) float32 device tensor."""
-    d = np.ascontiguousarray(slice_depths, dtype=np.float64)
-    dev = vpos.device
-    if len(d):
-        cum_t, adj_t = _depth_tables_on_device(d, add_padding, dev)
-        nadj, ncum = adj_t.shape[0], cum_t.shape[0]
-    else:
-        adj_t = cum_t = None
-        nadj = ncum = 0
+    cum_t, ncum, adj_t, nadj = _depth_args(slice_depths, add_padding, vpos.device)
     _lib.check(_lib.lib().tomo_vertex_finalize(_p(vpos), vpos.shape[0], 1 if manifold else 0, _p(cum_t), ncum, _p(adj_t),
                                                nadj, float(np.float32(mm_per_pixel_y)), float(np.float32(mm_per_pixel_x)),
                                                _stream()), "tomo_vertex_finalize")
@@ -506,27 +516,17 @@ _MC3_HINT = {}          # field geometry -> (active voxels, vertices, triangles)
 # slice): then rocPRIM's segmented sort + merge + rank kernels (tomo_mc3_sort_rank_top), as in rounds 2-3.
 FUSED_SORT = os.environ.get("TOMO_FUSED_SORT", "1") not in ("", "0")     # A/B switch
 _MC3_LARGE = {}         # field geometry -> True: use the rocPRIM path
-_PINNED_TOT = {}
+_PINNED = {}
 
 
-def _download_tot(tot):
-    """The 8 counters of a chain in ONE transfer into page-locked memory (no pageable bounce buffer, no extra blit)."""
-    key = (str(tot.device), threading.get_ident())         # rank threads of a slab job share the process: one buffer each
-    host = _PINNED_TOT.get(key)
+def _download(t):
+    """A small int64 device vector (the 8 counters of a chain) in ONE transfer into page-locked memory -> list of ints (no
+    pageable bounce buffer, no extra blit).  One buffer per device, thread and length: rank threads of a slab job share the process."""
+    key = (str(t.device), threading.get_ident(), t.numel())
+    host = _PINNED.get(key)
     if host is None:
-        host = _PINNED_TOT[key] = torch.empty(8, dtype=torch.int64, pin_memory=True)
-    host.copy_(tot, non_blocking=True)
-    torch.cuda.current_stream(tot.device).synchronize()
-    return [int(x) for x in host]
-
-
-def _download_vec(t):
-    """Any small int64 device vector in ONE transfer into page-locked memory -> list of ints."""
-    key = (str(t.device), threading.get_ident(), int(t.numel()))
-    host = _PINNED_TOT.get(key)
-    if host is None:
-        host = _PINNED_TOT[key] = torch.empty(t.numel(), dtype=torch.int64, pin_memory=True)
-    host.copy_(t.reshape(-1), non_blocking=True)
+        host = _PINNED[key] = torch.empty(t.numel(), dtype=torch.int64, pin_memory=True)
+    host.copy_(t if t.dim() == 1 else t.reshape(-1), non_blocking=True)
     torch.cuda.current_stream(t.device).synchronize()
     return host.tolist()
 
@@ -575,53 +575,219 @@ class PendingDownload:
 
 
 class Mc3Surface:
-    """Vertices of a surface through the mc3 chain, ready for its triangles: `uniq` (U,3) float32 final rows in np.unique's
-    order, `table` int32 (vertex id -> row index; id = 4 * list position of the owner voxel + slot).  faces(table) writes the
-    final int64 triangles through any such table (a Z-slab rank passes GLOBAL indices)."""
+    """One pass of the mc3 chain over a manifold=True field at level 0.5, and the surface it leaves behind.  Built from the field,
+    the depth table and pixel sizes, `z_offset` (a Z-slab rank's first padded slice), `z_top` (also count the rows with
+    z' == z_top into tot[7]: the plane shared with the rank above) and optionally `tot`, the int64[8] its kernels count in (a
+    caller may place it inside a larger buffer it downloads itself).  States, as mc3_vertices drives them:
+      classified  classify(): sign records -> seg_act / seg_cnt
+      enqueued    enqueue(cap, cap_v, cap_f) = build_list + eval_scan + vertices_sort into buffers of those capacities, faces()
+                  adds the triangles; no count is read.  Capacities from a size hint are guesses: only the counters say
+                  whether everything fitted
+      deferred    `deferred` is set: enqueued from hints, counters unread.  With triangles start_counters() has begun their
+                  download and finish() completes the pass; without, the caller reads `tot` itself and calls adopt()
+      resolved    resolve() / adopt() have published uniq, table, faces_final, na / nv / nf and stored the size hint
+    tot: [0] active voxels (na)  [1] vertices (nv)  [2] triangles (nf)  [3] overflow flags (bit 3: a sort segment too long for
+    the fused kernel)  [4] rows that do not ascend strictly  [5] degenerate triangles  [6] corners without vertex  [7] rows on z_top.
+    Buffers: field; seg_act, seg_cnt, seg_blk, seg_aoff (per segment); vox_key, vox_loc, vox_til, vox_flags, vox_used, vox_f3,
+    vox_c3, blk3 (`cap` list positions); slice_tab (sort segments); vrec (rows + id, unsorted) and rows (sorted, duplicate-free),
+    both of capacity cap_v; table int32 (vertex id -> row index; id = 4 * list position of the owner voxel + slot: 4 * cap
+    entries); cap_f, the triangle capacity.  Results: `uniq` (U,3) float32 final rows in np.unique's order (rows[:nv] unless
+    the general unique re-sorted them), `table`, and `faces_final` (F,3) int64 when the triangles were asked for."""
 
-    def __init__(self):
-        self.uniq = self.table = None
+    def __init__(self, f, slice_depths, mm_per_pixel_y, mm_per_pixel_x, add_padding=True, z_offset=0, z_top=None, tot=None):
+        self.field, self.z_offset = f, int(z_offset)
+        self.z_top = float("nan") if z_top is None else float(z_top)
+        self.hint_key = (f.Nz, f.Ny, f.Nx, self.z_offset)
+        self._depth = _depth_args(slice_depths, add_padding, f.data.device)
+        self._mm = (float(np.float32(mm_per_pixel_y)), float(np.float32(mm_per_pixel_x)))
+        self.tot = torch.empty(8, dtype=torch.int64, device=f.data.device) if tot is None else tot
+        self.uniq = self.table = self.faces_final = None
         self.nv = self.nf = self.na = 0
-        self.deferred = False       # True: enqueued into hint-sized buffers, no count has been read yet (see mc3_vertices)
-        self.finish = None          # deferred WITH faces: finish() reads the counters (one pass late, if the caller likes) -> self | None
+        self.deferred = False
+        self._pending = None        # (PendingDownload of tot, triangles) between start_counters() and finish()
+
+    def classify(self):
+        L, f, dev = _lib.lib(), self.field, self.field.data.device
+        if f.signs is None or f.signs_level != 0.5:
+            if f.sparse:
+                raise _lib.TomoError("a sparse field holds floats only near the 0.5 surface")
+            field_signs(f, 0.5)
+        nseg = f.Nz * f.Ny * L.tomo_mc_segments_per_row(f.Nx, f.xorg)
+        self.seg_act = torch.empty(nseg * 4, dtype=torch.int64, device=dev)
+        self.seg_cnt = torch.empty(nseg, dtype=torch.int32, device=dev)
+        _lib.check(L.tomo_mc_classify(_p(f.signs), _p(f.gcls), f.Nz, f.Ny, f.Nx, f.xorg, _p(self.seg_act), _p(self.seg_cnt), _stream()),
+                   "tomo_mc_classify")
+        self.seg_blk = torch.empty((nseg + 255) // 256, dtype=torch.int32, device=dev)
+        self.seg_aoff = torch.empty(nseg + 1, dtype=torch.int32, device=dev)
+
+    def build_list(self, cap):
+        f, self.cap = self.field, cap
+        self.vox_key = torch.empty(cap, dtype=torch.int64, device=f.data.device)
+        _lib.check(_lib.lib().tomo_mc3_list(f.Nz, f.Ny, f.Nx, f.xorg, _p(self.seg_cnt), _p(self.seg_act), _p(self.seg_blk), _p(self.seg_aoff),
+                                            _p(self.vox_key), cap, _p(self.tot), _stream()), "tomo_mc3_list")
+
+    def eval_scan(self, cap_v, cap_f):
+        L, f, cap, st, dev = _lib.lib(), self.field, self.cap, _stream(), self.field.data.device
+        self.vox_loc = torch.empty(cap, dtype=torch.int32, device=dev)
+        self.vox_til = torch.empty(cap, dtype=torch.int32, device=dev)
+        self.vox_flags = torch.empty(cap, dtype=torch.uint8, device=dev)
+        self.vox_used = torch.empty(cap, dtype=torch.int16, device=dev)
+        self.vox_f3 = torch.empty(3 * cap, dtype=torch.float32, device=dev)
+        self.vox_c3 = torch.empty(3 * cap, dtype=torch.float32, device=dev)
+        self.blk3 = torch.empty(3 * ((cap + 255) // 256), dtype=torch.int32, device=dev)
+        self.slice_tab = torch.empty(L.tomo_mc3_slice_table_words(f.Nz, f.Ny), dtype=torch.int32, device=dev)
+        _lib.check(L.tomo_mc3_eval(_p(f.data), f.Nz, f.Ny, f.Nx, f.pitch, f.xorg, 0.5, _p(self.vox_key), cap, _p(self.tot), self.z_offset,
+                                   _p(self.vox_loc), _p(self.vox_til), _p(self.vox_flags), _p(self.vox_used), _p(self.vox_f3),
+                                   _p(self.vox_c3), _p(self.blk3), st), "tomo_mc3_eval")
+        _lib.check(L.tomo_mc3_scan(f.Nz, f.Ny, f.Nx, f.xorg, _p(self.seg_aoff), _p(self.vox_loc), cap, _p(self.blk3), _p(self.slice_tab),
+                                   _p(self.tot), cap_v, cap_f, st), "tomo_mc3_scan")
+
+    def vertices_sort(self, cap_v):
+        """Finalised rows, then the unique stage: the fused kernel, or the library path once _MC3_LARGE names this geometry."""
+        L, f, cap, tot, st, dev = _lib.lib(), self.field, self.cap, self.tot, _stream(), self.field.data.device
+        cum_t, ncum, adj_t, nadj = self._depth
+        self.cap_v = cap_v
+        self.vrec = torch.empty((cap_v, 4), dtype=torch.float32, device=dev)
+        keys = torch.empty(cap_v, dtype=torch.int32, device=dev)
+        self.rows = torch.empty((cap_v, 3), dtype=torch.float32, device=dev)
+        self.table = torch.empty(4 * cap, dtype=torch.int32, device=dev)
+        fused = FUSED_SORT and not _MC3_LARGE.get(self.hint_key)
+        idx = None if fused else torch.empty(cap_v, dtype=torch.int32, device=dev)
+        _lib.check(L.tomo_mc3_vertices(f.Nz, f.Ny, f.Nx, f.xorg, _p(self.vox_key), cap, _p(tot), _p(self.vox_loc), _p(self.vox_flags),
+                                       _p(self.vox_f3), _p(self.vox_c3), _p(self.blk3), _p(self.slice_tab), self.z_offset, 1, _p(cum_t), ncum,
+                                       _p(adj_t), nadj, *self._mm, _p(self.vrec), _p(keys), _p(idx), st), "tomo_mc3_vertices")
+        if fused:
+            COUNTERS["mc3_sort_fused"] += 1
+            _lib.check(L.tomo_mc3_sort_rank_fused(_p(self.vrec), _p(keys), cap_v, f.Nz, f.Ny, _p(self.slice_tab), _p(tot), _p(self.rows),
+                                                  _p(self.table), self.z_top, st), "tomo_mc3_sort_rank_fused")
+            return
+        COUNTERS["mc3_sort_library"] += 1
+        wsb = L.tomo_mc3_sort_workspace_bytes(cap_v, L.tomo_mc3_sort_segments(f.Nz, f.Ny))
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        _lib.check(L.tomo_mc3_sort_rank_top(_p(self.vrec), _p(keys), _p(idx), cap_v, f.Nz, f.Ny, _p(self.slice_tab), _p(tot), _p(self.rows),
+                                            _p(self.table), _p(ws), wsb, self.z_top, st), "tomo_mc3_sort_rank_top")
+
+    def enqueue(self, cap, cap_v, cap_f):
+        """List, eval + scan, vertices + sort into buffers of the given capacities; no count is read."""
+        self.build_list(cap)
+        self.eval_scan(cap_v, cap_f)
+        self.vertices_sort(cap_v)
+        self.cap_f = cap_f
 
     def faces(self, table=None, again=False, slab_map=None):
-        """slab_map = (gathered int64 (world, 8), rank, world, ids_next int32 or None, cap_top, cap_v): the triangles leave with
+        """The final int64 triangles through `table` (default: the chain's own; a Z-slab rank passes GLOBAL indices).
+        slab_map = (gathered int64 (world, 8), rank, world, ids_next int32 or None, cap_top, cap_v): the triangles leave with
         GLOBAL indices of a Z-slab job, every count taken from device memory (tomo_mc3_faces_slab)."""
         L = _lib.lib()
-        f, st = self._f, _stream()
+        f, st = self.field, _stream()
         tab = self.table if table is None else table
-        if tab.dtype != torch.int32 or tab.numel() < 4 * self._cap:
+        if tab.dtype != torch.int32 or tab.numel() < 4 * self.cap:
             raise ValueError("table must be int32 with 4 entries per list position")
         if again:
-            self._tot[5:7].zero_()                               # the counters of an earlier faces pass
-        faces = torch.empty((max(self._cap_f, 1), 3), dtype=torch.int64, device=tab.device)
+            self.tot[5:7].zero_()                               # the counters of an earlier faces pass
+        faces = torch.empty((max(self.cap_f, 1), 3), dtype=torch.int64, device=tab.device)
+        args = (f.Nz, f.Ny, f.Nx, f.xorg, _p(self.vox_key), self.cap, _p(self.tot), _p(self.seg_act), _p(self.seg_aoff), _p(self.vox_loc),
+                _p(self.vox_til), _p(self.vox_used), _p(self.blk3), _p(tab), _p(faces), self.cap_f)
         if slab_map is not None:
             gathered, rank, world, ids_next, cap_top, cap_v = slab_map
-            _lib.check(L.tomo_mc3_faces_slab(f.Nz, f.Ny, f.Nx, f.xorg, _p(self._vox_key), self._cap, _p(self._tot), _p(self._seg_act),
-                                             _p(self._seg_aoff), _p(self._vox_loc), _p(self._vox_til), _p(self._vox_used), _p(self._blk3),
-                                             _p(tab), _p(faces), self._cap_f, _p(gathered), rank, world, _p(ids_next), cap_top, cap_v, st),
-                       "tomo_mc3_faces_slab")
-            return faces
-        _lib.check(L.tomo_mc3_faces(f.Nz, f.Ny, f.Nx, f.xorg, _p(self._vox_key), self._cap, _p(self._tot), _p(self._seg_act),
-                                    _p(self._seg_aoff), _p(self._vox_loc), _p(self._vox_til), _p(self._vox_used), _p(self._blk3), _p(tab), _p(faces),
-                                    self._cap_f, st), "tomo_mc3_faces")
+            _lib.check(L.tomo_mc3_faces_slab(*args, _p(gathered), rank, world, _p(ids_next), cap_top, cap_v, st), "tomo_mc3_faces_slab")
+        else:
+            _lib.check(L.tomo_mc3_faces(*args, st), "tomo_mc3_faces")
         return faces
 
-    def faces_checked(self, table=None, again=False, faces=None):
-        """faces(table) + the download of the counters: raises on an internal inconsistency, drops the triangles with fewer
-        than three distinct vertices (order kept, surface_extractor.py:122-125) -> (F', 3) int64."""
-        if faces is None:
-            faces = self.faces(table, again)
-        host = _download_tot(self._tot)
+    def trim(self, host, faces, count=True):
+        """The triangles a faces() pass really wrote, given its counters: raises on an internal inconsistency, drops the
+        triangles with fewer than three distinct vertices (count: note that in COUNTERS) -> (F', 3) int64."""
         if host[6]:
             raise _lib.TomoError("internal error: %d triangle corners reference a missing vertex" % host[6])
         faces = faces[:host[2]]
         if host[5]:
-            COUNTERS["mc3_degenerate"] += 1
-            keep = (faces[:, 0] != faces[:, 1]) & (faces[:, 1] != faces[:, 2]) & (faces[:, 0] != faces[:, 2])
-            faces = faces[keep]
+            if count:
+                COUNTERS["mc3_degenerate"] += 1
+            faces = drop_degenerate(faces)
         return faces
+
+    def faces_checked(self, table=None, again=False, faces=None):
+        """faces(table) + the download of the counters + trim()."""
+        if faces is None:
+            faces = self.faces(table, again)
+        return self.trim(_download(self.tot), faces)
+
+    def start_counters(self, faces):
+        """Deferred with triangles: the ONE download of the pass starts now, finish() waits for it."""
+        self._pending, self.deferred = (PendingDownload(self.tot), faces), True
+
+    def finish(self):
+        """Second half of a deferred pass with triangles (one pass late, if the caller likes) -> self, or None as resolve()."""
+        (pend, faces), self._pending = self._pending, None
+        return self.resolve(pend.wait(), faces, True)
+
+    def resolve(self, host, faces, with_faces):
+        """Everything after the counters of a hinted chain have arrived (host = None: no hinted chain ran): a chain that did not
+        fit is redone with exact sizes, one host read per stage.  -> self, or None where the reference returns None."""
+        key, tot = self.hint_key, self.tot
+        if host is not None:
+            if host[3]:
+                COUNTERS["mc3_hint_miss"] += 1
+                if host[3] & 8:
+                    _MC3_LARGE[key] = True                       # a sort segment too long for the fused kernel: the library path from now on
+                host = None                                      # something did not fit: redo with exact sizes
+            else:
+                COUNTERS["mc3_hint_hit"] += 1
+        if host is None:
+            self.build_list(1 << 16)                             # a token buffer: tot[0] comes out exact, nothing is written past it
+            na = _download(tot)[0]
+            if na == 0:
+                return None
+            _check_limits(na, ids=4)
+            self.build_list(na)
+            self.eval_scan(2 ** 31 - 2, 2 ** 31 - 2)
+            host = _download(tot)
+            nv, nf = host[1], host[2]
+            if nv == 0:
+                _MC3_HINT[key] = (na, 1, 1)
+                return None
+            _check_limits(na, nv, nf, ids=4)
+            self.vertices_sort(nv)
+            self.cap_f = max(nf, 1)
+            if FUSED_SORT and not _MC3_LARGE.get(key):
+                # value 8 (bit 3) of tot[3]: a segment the fused kernel cannot hold in LDS -- the library path repeats the stage and stays
+                if _download(tot)[3] & 8:
+                    _MC3_LARGE[key] = True
+                    tot[3:5].zero_()
+                    tot[7].zero_()
+                    self.vertices_sort(nv)
+            faces = self.faces() if with_faces else None
+            host = _download(tot)
+        return self.adopt(host, faces)
+
+    def adopt(self, host, faces=None, slab=False):
+        """The eight counters of a chain that fitted are on the host: check the limits, publish na / nv / nf, uniq and the size
+        hint, let the general unique decide where the rows do not ascend strictly, and (faces: what faces() returned) trim the
+        triangles into faces_final.  -> self, or None for an empty surface.
+        slab=True -- a Z-slab rank whose deferred pass all ranks found exact, so host[4] is 0: an empty slab stays a surface (the
+        rank keeps its place in the numbering), the hint is floored at 1 so that the next pass runs from hints too, and COUNTERS
+        is left alone (the slab pass has never counted its exact or degenerate outcomes)."""
+        na, nv, nf = self.na, self.nv, self.nf = host[0], host[1], host[2]
+        if not slab and (na == 0 or nv == 0):
+            return None
+        _check_limits(na, nv, nf, ids=4)
+        _MC3_HINT[self.hint_key] = (max(na, 1), max(nv, 1), max(nf, 1)) if slab else (na, nv, nf)
+        self.uniq, self.deferred = self.rows[:nv], False
+        if host[4] and not slab:
+            # duplicate rows or a rounding coincidence: the general sort decides (np.unique semantics), the triangles follow
+            COUNTERS["mc3_general_unique"] += 1
+            self.uniq, rank = unique_rows(self.vrec[:nv, :3].contiguous())
+            ids = self.vrec[:nv, 3].contiguous().view(torch.int32).to(torch.int64)
+            self.table[ids] = rank
+            if faces is not None:
+                faces = self.faces(again=True)
+                host = _download(self.tot)
+        elif not slab:
+            COUNTERS["mc3_exact"] += 1
+        if faces is not None:
+            self.faces_final = self.trim(host, faces, count=not slab)
+        return self
 
 
 def _mc3_caps(hint):
@@ -641,189 +807,32 @@ def mc3_hint_ready(f: Field, z_offset=0):
 
 def mc3_vertices(f: Field, slice_depths, mm_per_pixel_y, mm_per_pixel_x, add_padding=True, z_offset=0, with_faces=True,
                  z_top=None, defer=False, tot=None):
-    """surface_extractor.py:55-65 + :82-113 + the vertex half of :115-126 for a manifold=True field at level 0.5.
-    -> Mc3Surface (its .faces_final holds the triangles when with_faces), or None where the reference returns None.
-    z_top: also count the rows with z' == z_top into tot[7] (a Z-slab rank's plane shared with the rank above).
-    defer: when size hints exist, return right after enqueueing -- `.deferred` is set, no count has been read.
-    with_faces=False: `_uniq` / `table` have the hinted capacities `_cap_v` / 4 `_cap` and the caller reads `_tot` itself
-    (slab.SlabJob._numbering_deferred; `tot`: where the chain keeps its counters, int64[8]).  with_faces=True: the triangles are enqueued too and the download of the counters has
-    been STARTED; `.finish()` waits for it and completes the call (-> the surface, or None where the reference returns None),
-    so a caller with several stacks to process can enqueue the next pass before it reads this one's counters (bench.py,
-    extract_surface_submit).  Without hints the call behaves as usual (`.deferred` stays False)."""
-    L = _lib.lib()
+    """surface_extractor.py:55-65 + :82-113 + the vertex half of :115-126 for a manifold=True field at level 0.5: one Mc3Surface
+    (see there for z_offset, z_top, tot and the states) driven as far as the caller asks -> it, or None where the reference
+    returns None.  With a size hint for the geometry the whole chain -- and with_faces: the triangles -- is enqueued before any
+    count is known, and ONE download follows:
+      defer=False                    the counters are read here: the surface comes back resolved.
+      defer=True, with_faces=True    their download has been started: the surface is `deferred` and .finish() resolves it, so a
+                                     caller with several stacks can enqueue the next pass first (bench.py, extract_surface_submit).
+      defer=True, with_faces=False   nothing is read: the surface is `deferred`, the caller downloads `tot` itself and calls
+                                     .adopt() (slab.SlabJob; rows / table have the capacities cap_v / 4 cap).
+    Without a hint the chain runs with exact sizes, one host read per stage, and comes back resolved (`deferred` stays False)."""
     if min(f.Nz, f.Ny, f.Nx) < 2:
         return None
-    if f.signs is None or f.signs_level != 0.5:
-        if getattr(f, "sparse", False):
-            raise _lib.TomoError("a sparse field holds floats only near the 0.5 surface")
-        field_signs(f, 0.5)
-    dev, st = f.data.device, _stream()
-    geo = (f.Nz, f.Ny, f.Nx, f.pitch, f.xorg, 0.5)
-    spr = L.tomo_mc_segments_per_row(f.Nx, f.xorg)
-    nseg = f.Nz * f.Ny * spr
-    seg_act = torch.empty(nseg * 4, dtype=torch.int64, device=dev)
-    seg_cnt = torch.empty(nseg, dtype=torch.int32, device=dev)
-    _lib.check(L.tomo_mc_classify(_p(f.signs), _p(f.gcls), f.Nz, f.Ny, f.Nx, f.xorg, _p(seg_act), _p(seg_cnt), st), "tomo_mc_classify")
-    seg_blk = torch.empty((nseg + 255) // 256, dtype=torch.int32, device=dev)
-    seg_aoff = torch.empty(nseg + 1, dtype=torch.int32, device=dev)
-    if tot is None:                 # the chain's eight counters (a caller may place them inside a larger buffer it downloads)
-        tot = torch.empty(8, dtype=torch.int64, device=dev)
-    d = np.ascontiguousarray(slice_depths, dtype=np.float64)
-    if len(d):
-        cum_t, adj_t = _depth_tables_on_device(d, add_padding, dev)
-        nadj, ncum = adj_t.shape[0], cum_t.shape[0]
-    else:
-        adj_t = cum_t = None
-        nadj = ncum = 0
-    mmy, mmx = float(np.float32(mm_per_pixel_y)), float(np.float32(mm_per_pixel_x))
-    hint_key = (f.Nz, f.Ny, f.Nx, int(z_offset))
-    hint = _MC3_HINT.get(hint_key) if NA_HINTS else None
-    z_top = float("nan") if z_top is None else float(z_top)
-    m = Mc3Surface()
-    m._f, m._seg_act, m._seg_aoff, m._tot, m._hint_key = f, seg_act, seg_aoff, tot, hint_key
-
-    def build_list(cap):
-        m._cap = cap
-        m._vox_key = torch.empty(cap, dtype=torch.int64, device=dev)
-        _lib.check(L.tomo_mc3_list(f.Nz, f.Ny, f.Nx, f.xorg, _p(seg_cnt), _p(seg_act), _p(seg_blk), _p(seg_aoff), _p(m._vox_key), cap,
-                                   _p(tot), st), "tomo_mc3_list")
-
-    def eval_scan(cap, cap_v, cap_f):
-        nblk = (cap + 255) // 256
-        m._vox_loc = torch.empty(cap, dtype=torch.int32, device=dev)
-        m._vox_til = torch.empty(cap, dtype=torch.int32, device=dev)
-        m._vox_flags = torch.empty(cap, dtype=torch.uint8, device=dev)
-        m._vox_used = torch.empty(cap, dtype=torch.int16, device=dev)
-        m._vox_f3 = torch.empty(3 * cap, dtype=torch.float32, device=dev)
-        m._vox_c3 = torch.empty(3 * cap, dtype=torch.float32, device=dev)
-        m._blk3 = torch.empty(3 * nblk, dtype=torch.int32, device=dev)
-        m._slice_tab = torch.empty(L.tomo_mc3_slice_table_words(f.Nz, f.Ny), dtype=torch.int32, device=dev)
-        _lib.check(L.tomo_mc3_eval(_p(f.data), *geo, _p(m._vox_key), cap, _p(tot), int(z_offset), _p(m._vox_loc), _p(m._vox_til),
-                                   _p(m._vox_flags), _p(m._vox_used), _p(m._vox_f3), _p(m._vox_c3), _p(m._blk3), st), "tomo_mc3_eval")
-        _lib.check(L.tomo_mc3_scan(f.Nz, f.Ny, f.Nx, f.xorg, _p(seg_aoff), _p(m._vox_loc), cap, _p(m._blk3), _p(m._slice_tab), _p(tot),
-                                   cap_v, cap_f, st), "tomo_mc3_scan")
-
-    def vertices_sort(cap, cap_v):
-        m._vrec = torch.empty((cap_v, 4), dtype=torch.float32, device=dev)
-        keys = torch.empty(cap_v, dtype=torch.int32, device=dev)
-        m._uniq = torch.empty((cap_v, 3), dtype=torch.float32, device=dev)
-        m.table = torch.empty(4 * cap, dtype=torch.int32, device=dev)
-        fused = FUSED_SORT and not _MC3_LARGE.get(hint_key)
-        idx = None if fused else torch.empty(cap_v, dtype=torch.int32, device=dev)
-        _lib.check(L.tomo_mc3_vertices(f.Nz, f.Ny, f.Nx, f.xorg, _p(m._vox_key), cap, _p(tot), _p(m._vox_loc), _p(m._vox_flags),
-                                       _p(m._vox_f3), _p(m._vox_c3), _p(m._blk3), _p(m._slice_tab), int(z_offset), 1, _p(cum_t), ncum,
-                                       _p(adj_t), nadj, mmy, mmx, _p(m._vrec), _p(keys), _p(idx), st), "tomo_mc3_vertices")
-        m._cap_v = cap_v
-        if fused:
-            COUNTERS["mc3_sort_fused"] += 1
-            _lib.check(L.tomo_mc3_sort_rank_fused(_p(m._vrec), _p(keys), cap_v, f.Nz, f.Ny, _p(m._slice_tab), _p(tot), _p(m._uniq),
-                                                  _p(m.table), z_top, st), "tomo_mc3_sort_rank_fused")
-            return
-        COUNTERS["mc3_sort_library"] += 1
-        wsb = L.tomo_mc3_sort_workspace_bytes(cap_v, L.tomo_mc3_sort_segments(f.Nz, f.Ny))
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        _lib.check(L.tomo_mc3_sort_rank_top(_p(m._vrec), _p(keys), _p(idx), cap_v, f.Nz, f.Ny, _p(m._slice_tab), _p(tot), _p(m._uniq),
-                                            _p(m.table), _p(ws), wsb, z_top, st), "tomo_mc3_sort_rank_top")
-
-    def complete(host, faces):
-        """Everything after the counters of a hinted chain have arrived (host = None: no hinted chain ran)."""
-        if host is not None:
-            if host[3]:
-                COUNTERS["mc3_hint_miss"] += 1
-                if host[3] & 8:
-                    _MC3_LARGE[hint_key] = True                  # a sort segment too long for the fused kernel: the library path from now on
-                host = faces = None                              # something did not fit: redo with exact sizes
-            else:
-                COUNTERS["mc3_hint_hit"] += 1
-        if host is None:
-            build_list(1 << 16)                                   # a token buffer: tot[0] comes out exact, nothing is written past it
-            na = _download_tot(tot)[0]
-            if na == 0:
-                return None
-            if na >= LIST_LIMIT or na >= 2 ** 29:
-                raise _lib.TomoError("surface too large for 32-bit indices")
-            build_list(na)
-            eval_scan(na, 2 ** 31 - 2, 2 ** 31 - 2)
-            host = _download_tot(tot)
-            nv, nf = host[1], host[2]
-            if nv == 0:
-                _MC3_HINT[hint_key] = (na, 1, 1)
-                return None
-            if nv >= MESH_LIMIT or nf >= MESH_LIMIT:
-                raise _lib.TomoError("mesh too large for 32-bit indices")
-            vertices_sort(na, nv)
-            m._cap_f = max(nf, 1)
-            if FUSED_SORT and not _MC3_LARGE.get(hint_key):
-                # the fused kernel reports a segment it cannot hold in LDS (value 8, bit 3, of tot[3]): the stage is repeated on the library
-                # path, and stays there for this geometry
-                host = _download_tot(tot)
-                if host[3] & 8:
-                    _MC3_LARGE[hint_key] = True
-                    tot[3:5].zero_()
-                    tot[7].zero_()
-                    vertices_sort(na, nv)
-            if with_faces:
-                faces = m.faces()
-            host = _download_tot(tot)
-        m.na, m.nv, m.nf = host[0], host[1], host[2]
-        if m.na == 0 or m.nv == 0:
-            return None
-        if m.na >= LIST_LIMIT:
-            raise _lib.TomoError("surface too large for 32-bit indices")
-        if m.nv >= MESH_LIMIT or m.nf >= MESH_LIMIT:
-            raise _lib.TomoError("mesh too large for 32-bit indices")
-        _MC3_HINT[hint_key] = (m.na, m.nv, m.nf)
-        m.uniq = m._uniq[:m.nv]
-        if host[4]:
-            # duplicate rows or a rounding coincidence: the general sort decides (np.unique semantics), the triangles follow
-            COUNTERS["mc3_general_unique"] += 1
-            rows = m._vrec[:m.nv, :3].contiguous()
-            uniq, rank = unique_rows(rows)
-            ids = m._vrec[:m.nv, 3].contiguous().view(torch.int32).to(torch.int64)
-            m.table[ids] = rank
-            m.uniq = uniq
-            if with_faces:
-                faces = m.faces(again=True)
-                host = _download_tot(tot)
-        else:
-            COUNTERS["mc3_exact"] += 1
-        if with_faces:
-            if host[6]:
-                raise _lib.TomoError("internal error: %d triangle corners reference a missing vertex" % host[6])
-            faces = faces[:m.nf]
-            if host[5]:                                              # triangles with fewer than three distinct vertices are dropped, order kept
-                COUNTERS["mc3_degenerate"] += 1
-                keep = (faces[:, 0] != faces[:, 1]) & (faces[:, 1] != faces[:, 2]) & (faces[:, 0] != faces[:, 2])
-                faces = faces[keep]
-            m.faces_final = faces
+    m = Mc3Surface(f, slice_depths, mm_per_pixel_y, mm_per_pixel_x, add_padding, z_offset, z_top, tot)
+    m.classify()
+    caps = _mc3_caps(_MC3_HINT.get(m.hint_key)) if NA_HINTS else None
+    if not caps:
+        return m.resolve(None, None, with_faces)
+    m.enqueue(*caps)
+    if defer and not with_faces:
+        m.deferred = True
         return m
-
-    host = None
-    faces = None
-    if hint:
-        # everything is enqueued into buffers of hint + 25 % before any count is known; ONE download at the end
-        caps = _mc3_caps(hint)
-        if caps:
-            cap, cap_v, cap_f = caps
-            build_list(cap)
-            eval_scan(cap, cap_v, cap_f)
-            vertices_sort(cap, cap_v)
-            m._cap_f = cap_f
-            if defer and not with_faces:
-                m.deferred = True
-                return m
-            if with_faces:
-                faces = m.faces()
-            if defer:
-                pend = PendingDownload(tot)
-
-                def finish(pend=pend, faces=faces):
-                    m.deferred, m.finish = False, None
-                    return complete(pend.wait(), faces)
-                m.deferred, m.finish = True, finish
-                return m
-            host = _download_tot(tot)
-    return complete(host, faces)
+    faces = m.faces() if with_faces else None
+    if defer:
+        m.start_counters(faces)
+        return m
+    return m.resolve(_download(m.tot), faces, with_faces)
 
 
 def mesh_volume_area(verts: torch.Tensor, faces: torch.Tensor):

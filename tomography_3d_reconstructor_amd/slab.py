@@ -485,7 +485,7 @@ class HipEngine:
         return out
 
     def download(self, t):
-        return pipeline._download_vec(t)
+        return pipeline._download(t)
 
     def download_start(self, t):
         """-> an object whose wait() returns the list of ints (the copy runs on the current stream, into its own page-locked buffer)."""
@@ -815,7 +815,7 @@ class SlabJob:
         if self.n_vertices_global >= 2 ** 31:
             raise pipeline._lib.TomoError("more than 2^31 vertices: the triangle table holds 32-bit indices")
         info = getattr(self, "_numbering", None)
-        if self.world > 1 and info is not None and not info["merged"] and nu == m.nv and getattr(m, "_cap_v", 0) >= m.nv:
+        if self.world > 1 and info is not None and not info["merged"] and nu == m.nv and m.cap_v >= m.nv:
             # the triangle kernel maps this rank's rows to GLOBAL indices itself (own rows by position + the lower ranks' kept
             # counts, shared-plane rows through the upper rank's answer), as in the pass without round trips; the counts it
             # takes from `gathered` are the ones the host has just read (was: a table of global indices built with five
@@ -823,7 +823,7 @@ class SlabJob:
             g = np.zeros((self.world, 8), dtype=np.int64)
             g[:, 0] = info["counts"]
             gathered = torch.from_numpy(g).to(dev)
-            faces = m.faces(again=True, slab_map=(gathered, self.rank, self.world, info["ids_next"], info["n_top"], m._cap_v))
+            faces = m.faces(again=True, slab_map=(gathered, self.rank, self.world, info["ids_next"], info["n_top"], m.cap_v))
             return kept, m.faces_checked(faces=faces)
         # rows merged with the lower rank's (a row from below that was new here) or re-sorted by the general unique: through a
         # table of global indices; entries that belong to no vertex hold whatever was in memory: clamp before they index anything
@@ -842,11 +842,11 @@ class SlabJob:
         e, c = self.eng, self.comm
         r, w = self.rank, self.world
         first, last = r == 0, r == w - 1
-        live = m is not None and getattr(m, "deferred", False)
+        live = m is not None and m.deferred
         tot, gathered = counters[:8], counters[8:].view(w, 8)
         if live:
-            assert m._tot.data_ptr() == tot.data_ptr()
-            uniq, cap_v = m._uniq, m._cap_v
+            assert m.tot.data_ptr() == tot.data_ptr()
+            uniq, cap_v = m.rows, m.cap_v
         else:                                                     # stand-ins: no rows, "overflow" set so that no count is trusted
             tot.copy_(torch.tensor([0, 0, 0, 1, 0, 0, 0, 0], dtype=torch.int64), non_blocking=True)
             uniq, cap_v = torch.zeros((1, 3), dtype=torch.float32, device=dev), 1
@@ -881,8 +881,8 @@ class SlabJob:
             # rare: a hint or a message capacity was too small, rows that do not ascend strictly (the general sort decides),
             # a row from below that is new here -- everybody takes the exact pass
             self.deferred_redone += 1
-            self.deferred_why = {"summaries": g, "tot": own, "hint": pipeline._MC3_HINT.get(getattr(m, "_hint_key", None)) if m is not None else None,
-                                 "caps": (getattr(m, "_cap", None), getattr(m, "_cap_v", None), getattr(m, "_cap_f", None)) if m is not None else None}
+            self.deferred_why = {"summaries": g, "tot": own, "hint": pipeline._MC3_HINT.get(m.hint_key) if m is not None else None,
+                                 "caps": (m.cap, m.cap_v, m.cap_f) if m is not None else None}
             self._deferred_ok = False
             m2 = e.mc3_vertices(f, Za, slice_depths, mm_y, mm_x, z_top=z_top, defer=False)
             ready = m2 is not None and bool(e.mc3_ready(f, Za))
@@ -893,24 +893,14 @@ class SlabJob:
         self.vertex_offset, self.n_vertices_global = int(offs[r]), int(offs[-1])
         if self.n_vertices_global >= 2 ** 31:
             raise pipeline._lib.TomoError("more than 2^31 vertices: the triangle table holds 32-bit indices")
-        if own[6]:
-            raise pipeline._lib.TomoError("internal error: %d triangle corners reference a missing vertex" % own[6])
-        m.na, m.nv, m.nf = own[0], own[1], own[2]
-        m.uniq = m._uniq[:m.nv]
-        pipeline._MC3_HINT[m._hint_key] = (max(m.na, 1), max(m.nv, 1), max(m.nf, 1))
+        m.adopt(own, faces, slab=True)
         self._cap_top, self._cap_prev = self._msg_cap(g[r][4]), self._msg_cap(g[r][5])
-        faces = faces[:m.nf]
-        if own[5]:
-            keep = (faces[:, 0] != faces[:, 1]) & (faces[:, 1] != faces[:, 2]) & (faces[:, 0] != faces[:, 2])
-            faces = faces[keep]
-        return m._uniq[:counts[r]], faces
+        return m.rows[:counts[r]], m.faces_final
 
     def _faces(self, faces32, gid):
         if faces32.shape[0] == 0:
             return torch.zeros((0, 3), dtype=torch.int64, device=faces32.device)
-        f = gid[faces32.to(torch.int64)]
-        keep = (f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 0] != f[:, 2])
-        return f[keep]
+        return pipeline.drop_degenerate(gid[faces32.to(torch.int64)])
 
     # ------------------------------------------------------------------------- consumers of a finished run()
     # BASELINE configs[3] asks for a "seam-free OBJ export" of the Z-slab job and configs[4] for a cross-check against

@@ -171,14 +171,14 @@ def main():
             return orig(t)
         job._numbering_deferred_finish = spy
         job.run(mask, depths, 1.0, 1.0)
-        m = keep["m"]; f = m._f
+        m = keep["m"]; f = m.field
         nseg = int(_lib.lib().tomo_mc3_sort_segments(f.Nz, f.Ny))
-        tab = m._slice_tab.cpu().numpy().view(np.uint32)
+        tab = m.slice_tab.cpu().numpy().view(np.uint32)
         off = tab[2 * (f.Nz + 1): 2 * (f.Nz + 1) + nseg + 1].astype(np.int64)
         sz = np.diff(off)
         per = sz.reshape(f.Nz, nseg // f.Nz)
         print("segments: Nz %d Ny %d, %d segments, sizes max %d mean %.0f, > 4096: %d; monotone: %s; cap_v %d nv %d; per-slice max per column %s; slice 0 %s, slice -1 %s"
-              % (f.Nz, f.Ny, nseg, sz.max(), sz.mean(), (sz > 4096).sum(), bool((sz >= 0).all()), m._cap_v, m.nv, per.max(axis=0).tolist(),
+              % (f.Nz, f.Ny, nseg, sz.max(), sz.mean(), (sz > 4096).sum(), bool((sz >= 0).all()), m.cap_v, m.nv, per.max(axis=0).tolist(),
                  per[0].tolist(), per[-1].tolist()), flush=True)
     del res
     # host time of submit() alone: enqueue 4 passes back to back without reading any, then collect them

@@ -15,7 +15,7 @@ for it in range(3):
     m = pipeline.mc3_vertices(f, depths, 1.0, 1.0, True, with_faces=False)
 torch.cuda.synchronize()
 nseg = int(L.tomo_mc3_sort_segments(f.Nz, f.Ny))
-tab = m._slice_tab.cpu().numpy().view(np.uint32)
+tab = m.slice_tab.cpu().numpy().view(np.uint32)
 off = tab[2 * (f.Nz + 1): 2 * (f.Nz + 1) + nseg + 1].astype(np.int64)
 sz = np.diff(off)
 nb1 = nseg // f.Nz
