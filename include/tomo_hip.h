@@ -377,7 +377,21 @@ int tomo_mesh_volume_area(const float *verts, const int64_t *faces, int64_t nf, 
  *     bytes on every run and every schedule;
  *  3. q = s.x s.x + s.y s.y + s.z s.z (left to right).  If q is finite and > 0: n = s / sqrt(q) component by component in
  *     float64, then rounded to float32.  Otherwise (a vertex no face names, faces that cancel, overflow) n = (0, 0, 1) and
- *     a counter goes up by one: glTF forbids a zero-length normal. */
+ *     a counter goes up by one: glTF forbids a zero-length normal.
+ *
+ * Multi-rank (the Z-slab job's export; every rank holds its own vertex rows and its own faces, faces in rank order, and a
+ * face of rank r names rows of rank r or a prefix of rank r + 1's rows -- the GHOST rows of rank r, all on the plane the two
+ * ranks share).  A SEAM EDGE is an undirected edge both of whose endpoints are ghost rows of the lower rank: the only kind
+ * of edge that can have faces on two ranks.  The lower rank sends one record per seam edge of its table (key in the upper
+ * rank's row numbers, face count, direction bits of its first two faces); the upper rank looks each one up in its own table
+ * and corrects the four edge counters so that, summed over the ranks, they are tomo_mesh_edges' counters of the gathered
+ * mesh: an edge with c_lo faces below and c_hi above counts once, in the class of c_lo + c_hi, and a pair with one face on
+ * either side is inconsistent exactly when both run the edge the same way (row order is the same in local and in global
+ * numbers).  With zero inconsistent pairs no face flips by rules 1-2, and rule 3 reads a sum of per-rank volumes.
+ * Normals: rule 2 adds in ascending GLOBAL face index, and every face of a lower rank precedes every face of an upper one.
+ * So the lower rank adds its faces' vectors to +0.0 for each ghost row, in ascending order, and hands the RAW float64 sums
+ * up; the owner starts from them instead of +0.0 and goes on with its own faces: ((0 + g1) + g2) + g3 ... is the same
+ * sequence of additions as on one GPU, hence the same bytes. */
 /* glb_exporter.py:52-91 on the device.  z = verts[i * stride] (float32, or float64 when is_f64).  rgba: uint8 (nv, 4),
  * 4-byte aligned; 200,200,200,255 by default, 255,0,0,255 where enable1 && start1 <= z <= end1, then 0,0,255,255 where
  * enable2 && start2 <= z <= end2 (blue wins).  Comparisons in float64: the caller passes bounds already rounded the way
@@ -394,6 +408,19 @@ int64_t tomo_mesh_edge_table_bytes(int64_t nf);
  * holds the face count and the first two (face << 1 | direction) entries. */
 int tomo_mesh_edges(const int64_t *faces, int64_t nf, int64_t nv, void *table, int64_t table_bytes, unsigned long long *counters,
                     void *stream);
+/* Multi-rank, the lower rank's half: every entry of a table built by tomo_mesh_edges (nf faces, LOCAL indices: own rows, then
+ * ghost rows from first_ghost on) whose two endpoints are >= first_ghost becomes one record of two uint64 in msg:
+ * [0] = (lo - first_ghost) << 32 | (hi - first_ghost), the key in the upper rank's local indices; [1] = bits << 32 | face
+ * count, bit 0 / 1 of bits = the direction of the first / second stored face.  *count (zeroed by the call) ends as the
+ * number of such entries whatever cap is; at most cap records are written (cap = 0, msg = NULL: count only).  The order
+ * of the records depends on the schedule; what tomo_mesh_seam_merge makes of them does not. */
+int tomo_mesh_seam_edges(const void *table, int64_t table_bytes, int64_t nf, int64_t first_ghost, unsigned long long *msg,
+                         int64_t cap, unsigned long long *count, void *stream);
+/* Multi-rank, the upper rank's half: looks n records up in this rank's table (read only) and writes corr[4] (int64, zeroed
+ * by the call): signed corrections to boundary / manifold / non-manifold edges and inconsistent pairs such that the sum
+ * over the ranks of (tomo_mesh_edges' counters + corr) equals the counters of the gathered mesh. */
+int tomo_mesh_seam_merge(const void *table, int64_t table_bytes, int64_t nf, const unsigned long long *msg, int64_t n,
+                         int64_t *corr, void *stream);
 int64_t tomo_mesh_orient_workspace_bytes(int64_t nf);
 /* Rules 1-2 of the contract over a table built by tomo_mesh_edges (only needed when counters[3] > 0: otherwise no face
  * flips).  Union-find with parity: parent and parity in one 64-bit word, the larger root hooked under the smaller with
@@ -423,6 +450,17 @@ int tomo_glb_pack_positions(const void *verts, int is_f64, int64_t nv, float *po
 int64_t tomo_mesh_vertex_normals_workspace_bytes(int64_t nv, int64_t nf);
 int tomo_mesh_vertex_normals(const float *pos, int64_t nv, const void *idx, int idx_i64, int64_t nf, void *workspace,
                              int64_t workspace_bytes, float *normals, unsigned long long *counters, void *stream);
+
+/* tomo_mesh_vertex_normals for one rank of a multi-rank mesh: nv = own rows followed by n_raw ghost rows, idx in these local
+ * numbers, nf >= 0.  The first n_seed vertices start their sums from seed (float64 (n_seed, 3)) instead of +0.0; the last
+ * n_raw vertices get no normal: their raw float64 sums go to raw ((n_raw, 3)) and they are not counted.  Both the register
+ * path and the long-list path honour the seed.  normals: float32 (nv - n_raw, 3).  phase 1: build the lists in the
+ * workspace, zero the counters, write raw; phase 2: the normals, from the lists phase 1 left in the same workspace (same nv,
+ * nf); 3: both.  Between the two a rank sends raw up and receives its seed.  Workspace as for tomo_mesh_vertex_normals
+ * (sized with max(nf, 1)).  With n_seed = n_raw = 0 and phase 3 it is tomo_mesh_vertex_normals. */
+int tomo_mesh_vertex_normals_seeded(const float *pos, int64_t nv, const void *idx, int idx_i64, int64_t nf, void *workspace,
+                                    int64_t workspace_bytes, float *normals, unsigned long long *counters, const double *seed,
+                                    int64_t n_seed, double *raw, int64_t n_raw, int phase, void *stream);
 
 #ifdef __cplusplus
 }

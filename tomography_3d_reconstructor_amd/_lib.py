@@ -112,6 +112,8 @@ SIGNATURES = {
     "tomo_layer_colors": (_c_i, [_c_p, _c_i, _c_i64, _c_i64, _c_d, _c_d, _c_i, _c_d, _c_d, _c_i, _c_p, _c_p]),
     "tomo_mesh_edge_table_bytes": (_c_i64, [_c_i64]),
     "tomo_mesh_edges": (_c_i, [_c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_p]),
+    "tomo_mesh_seam_edges": (_c_i, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_p]),
+    "tomo_mesh_seam_merge": (_c_i, [_c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_p]),
     "tomo_mesh_orient_workspace_bytes": (_c_i64, [_c_i64]),
     "tomo_mesh_orient": (_c_i, [_c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p]),
     "tomo_mesh_signed_volume": (_c_i, [_c_p, _c_p, _c_i64, _c_p, _c_p, _c_p]),
@@ -119,6 +121,8 @@ SIGNATURES = {
     "tomo_glb_pack_positions": (_c_i, [_c_p, _c_i, _c_i64, _c_p, _c_p, _c_p]),
     "tomo_mesh_vertex_normals_workspace_bytes": (_c_i64, [_c_i64, _c_i64]),
     "tomo_mesh_vertex_normals": (_c_i, [_c_p, _c_i64, _c_p, _c_i, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p]),
+    "tomo_mesh_vertex_normals_seeded": (_c_i, [_c_p, _c_i64, _c_p, _c_i, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64,
+                                              _c_i, _c_p]),
 }
 
 _LIB = None

@@ -121,6 +121,90 @@ __global__ __launch_bounds__(BLOCK) void edge_classify_kernel(Table t, unsigned 
     wave_add(&counters[3], inconsistent);
 }
 
+// ---- seam edges of a mesh that is cut into ranks (the multi-rank paragraph of the orientation contract) --------------------
+// one atomicAdd per wave of a per-lane SIGNED count (two's complement: the counters are read as int64)
+__device__ static inline void wave_add_signed(unsigned long long *dst, int v)
+{
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+    if ((threadIdx.x & 63) == 0 && v) atomicAdd(dst, (unsigned long long)(long long)v);
+}
+
+// Every table entry whose two endpoints are ghost rows (local index >= first_ghost: lo < hi, so lo decides) becomes one
+// record {key in the UPPER rank's local indices, direction bits << 32 | face count}.  *count ends as the number of such
+// entries whatever cap is; records beyond cap are not written.  The loop bound is wave-uniform (cap and the stride are
+// multiples of 64), so the ballot sees whole waves.
+__global__ __launch_bounds__(BLOCK) void seam_collect_kernel(Table t, u64 first_ghost, int64_t cap, u64 *__restrict__ msg,
+                                                              unsigned long long *__restrict__ count)
+{
+    const int lane = threadIdx.x & 63;
+    for (int64_t s = (int64_t)blockIdx.x * BLOCK + threadIdx.x; s < t.cap; s += (int64_t)gridDim.x * BLOCK) {
+        const u64 key = t.keys[s];
+        const bool hit = key != EMPTY_KEY && (key >> 32) >= first_ghost;
+        const u64 mask = __ballot(hit);
+        if (!mask) continue;
+        unsigned long long base = 0;
+        const int leader = __ffsll((long long)mask) - 1;
+        if (lane == leader) base = atomicAdd(count, (unsigned long long)__popcll(mask));
+        base = __shfl(base, leader, 64);
+        if (!hit) continue;
+        const int64_t at = (int64_t)base + __popcll(mask & ((1ULL << lane) - 1ULL));
+        if (at >= cap) continue;
+        const u32 n = t.cnt[s];
+        const u32 bits = (t.ent[2 * s] & 1u) | (n >= 2 ? (t.ent[2 * s + 1] & 1u) << 1 : 0u);
+        msg[2 * at] = (((key >> 32) - first_ghost) << 32) | ((key & 0xffffffffULL) - first_ghost);
+        msg[2 * at + 1] = ((u64)bits << 32) | (u64)n;
+    }
+}
+
+__device__ static inline void seam_class(u32 n, int sign, int &boundary, int &manifold, int &nonmanifold)
+{
+    if (n == 1) boundary += sign;
+    else if (n == 2) manifold += sign;
+    else if (n >= 3) nonmanifold += sign;
+}
+
+// The upper rank's half: each record is looked up in this rank's table (read only).  corr[0..3] receive what has to be
+// ADDED to (the lower rank's counters + this rank's counters) so that the edge counts once, in the class of c_lo + c_hi.
+__global__ __launch_bounds__(BLOCK) void seam_merge_kernel(Table t, const u64 *__restrict__ msg, int64_t n,
+                                                            unsigned long long *__restrict__ corr)
+{
+    int boundary = 0, manifold = 0, nonmanifold = 0, inconsistent = 0;
+    for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
+        const u64 key = msg[2 * i], w = msg[2 * i + 1];
+        const u32 c_lo = (u32)w, bits = (u32)(w >> 32);
+        if (c_lo == 0) continue;
+        u32 c_hi = 0, e0 = 0, e1 = 0;
+        u64 s = mix64(key) & (u64)(t.cap - 1);
+        for (int64_t probe = 0; probe < t.cap; probe++) {
+            const u64 k = t.keys[s];
+            if (k == key) {
+                c_hi = t.cnt[s];
+                e0 = t.ent[2 * s];
+                e1 = c_hi >= 2 ? t.ent[2 * s + 1] : 0u;
+                break;
+            }
+            if (k == EMPTY_KEY) break;
+            s = (s + 1) & (u64)(t.cap - 1);
+        }
+        if (c_hi == 0) continue;                       // the lower rank's own count stands
+        const u32 sum = c_lo + c_hi;
+        seam_class(sum, 1, boundary, manifold, nonmanifold);
+        seam_class(c_lo, -1, boundary, manifold, nonmanifold);
+        seam_class(c_hi, -1, boundary, manifold, nonmanifold);
+        if (sum == 2) {                                // one face on either side: they run the edge the same way or not
+            if (((bits ^ e0) & 1u) == 0) inconsistent++;
+        } else {                                       // three or more faces: no pair; take back what either side counted
+            if (c_lo == 2 && ((bits ^ (bits >> 1)) & 1u) == 0) inconsistent--;
+            if (c_hi == 2 && ((e0 ^ e1) & 1u) == 0) inconsistent--;
+        }
+    }
+    wave_add_signed(&corr[0], boundary);
+    wave_add_signed(&corr[1], manifold);
+    wave_add_signed(&corr[2], nonmanifold);
+    wave_add_signed(&corr[3], inconsistent);
+}
+
 // ---- union-find with parity ---------------------------------------------------------------------------------------------
 // uf[f] = parent << 1 | parity of f relative to its parent.  A root holds (f << 1 | 0).  Every link points from a larger
 // face index to a smaller one (hooking puts the larger root under the smaller; compression only moves a link further up
@@ -307,6 +391,8 @@ __global__ __launch_bounds__(BLOCK) void pack_positions_kernel(const T *__restri
 // An inverted index instead of float atomics: per vertex the list of the faces that name it (one entry per corner), built
 // with integer atomics in whatever order the corners arrive, then put into ascending order by the kernel that sums -- so
 // the float64 sums do not depend on the schedule.  A face with an index outside [0, nv) enters no list and is counted.
+// Multi-rank form: the kernel that sums takes a vertex range [vb, nv), starts the first n_seed vertices from given sums
+// instead of +0.0 and leaves the vertices from raw_base on as raw float64 sums (not normalised, not counted).
 constexpr int NRM_REG = 16;            // lists up to this length are sorted in registers (a marching-cubes vertex has 4-9 faces)
 
 template <typename I>
@@ -363,21 +449,29 @@ __device__ static inline void face_vector(const float *__restrict__ pos, const I
 // wave: each step finds the smallest face number above the last one summed and how often it occurs (a face that names the
 // vertex twice has two entries), so the order is exact for any length without memory for a sorted copy.
 template <typename I>
-__global__ __launch_bounds__(BLOCK) void vertex_normals_kernel(const float *__restrict__ pos, int64_t nv, const I *__restrict__ idx,
-                                                                const u32 *__restrict__ off, const u32 *__restrict__ list,
-                                                                float *__restrict__ normals, unsigned long long *__restrict__ counters)
+__global__ __launch_bounds__(BLOCK) void vertex_normals_kernel(const float *__restrict__ pos, int64_t vb, int64_t nv,
+                                                                const I *__restrict__ idx, const u32 *__restrict__ off,
+                                                                const u32 *__restrict__ list, float *__restrict__ normals,
+                                                                unsigned long long *__restrict__ counters,
+                                                                const double *__restrict__ seed, int64_t n_seed,
+                                                                double *__restrict__ raw, int64_t raw_base)
 {
     const int lane = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6, nwaves = (int64_t)gridDim.x * (BLOCK / 64);
     u32 defaulted = 0;
-    for (int64_t base = wave * 64; base < nv; base += nwaves * 64) {
+    for (int64_t base = vb + wave * 64; base < nv; base += nwaves * 64) {
         const int64_t v = base + lane;
         u32 o = 0, d = 0;
+        double s[3] = {0.0, 0.0, 0.0};
         if (v < nv) {
             o = off[v];
             d = off[v + 1] - o;
+            if (v < n_seed) {                                           // the sums of the faces a lower rank holds come first
+                s[0] = seed[3 * v];
+                s[1] = seed[3 * v + 1];
+                s[2] = seed[3 * v + 2];
+            }
         }
-        double s[3] = {0.0, 0.0, 0.0};
         if (d <= NRM_REG) {
             u32 key[NRM_REG];
 #pragma unroll
@@ -407,7 +501,7 @@ __global__ __launch_bounds__(BLOCK) void vertex_normals_kernel(const float *__re
             const int src = __ffsll((long long)longer) - 1;
             longer &= longer - 1;
             const u32 lo = __shfl(o, src, 64), ld = __shfl(d, src, 64);
-            double t[3] = {0.0, 0.0, 0.0};
+            double t[3] = {__shfl(s[0], src, 64), __shfl(s[1], src, 64), __shfl(s[2], src, 64)};     // +0.0 or the seed
             int64_t last = -1;
             for (u32 done = 0; done < ld;) {
                 u32 m = 0xffffffffu, c = 0;
@@ -441,7 +535,11 @@ __global__ __launch_bounds__(BLOCK) void vertex_normals_kernel(const float *__re
                 s[2] = t[2];
             }
         }
-        if (v < nv) {
+        if (v < nv && v >= raw_base) {                                  // a ghost row: its owner continues the sum
+            raw[3 * (v - raw_base)] = s[0];
+            raw[3 * (v - raw_base) + 1] = s[1];
+            raw[3 * (v - raw_base) + 2] = s[2];
+        } else if (v < nv) {
             const double q = s[0] * s[0] + s[1] * s[1] + s[2] * s[2];
             float n[3] = {0.0f, 0.0f, 1.0f};
             if (q > 0.0 && q < (double)INFINITY) {                      // finite and positive (a NaN fails both)
@@ -488,6 +586,50 @@ TOMO_API int64_t tomo_mesh_vertex_normals_workspace_bytes(int64_t nv, int64_t nf
     return normals_ws(nv, nf).total;
 }
 
+// phase bit 0: build the lists (and zero the counters), then the raw sums of the last n_raw vertices; bit 1: the normals of
+// the first nv - n_raw vertices, the first n_seed of them continued from `seed`.
+static int normals_run(const float *pos, int64_t nv, const void *idx, int idx_i64, int64_t nf, void *workspace, float *normals,
+                       unsigned long long *counters, const double *seed, int64_t n_seed, double *raw, int64_t n_raw, int phase,
+                       hipStream_t st)
+{
+    const NormalsWs w = normals_ws(nv, nf);
+    char *base = (char *)workspace;
+    u32 *deg = (u32 *)base, *off = (u32 *)(base + w.off), *list = (u32 *)(base + w.list);
+    const unsigned gf = grid_for(nf);
+    const int64_t own = nv - n_raw;
+    if (phase & 1) {
+        if (hipMemsetAsync(deg, 0, 4 * nv, st) != hipSuccess || hipMemsetAsync(counters, 0, 2 * sizeof(unsigned long long), st) != hipSuccess)
+            return TOMO_E_LAUNCH;
+        if (nf > 0) {
+            if (idx_i64)
+                hipLaunchKernelGGL(normals_count_kernel<int64_t>, dim3(gf), dim3(BLOCK), 0, st, (const int64_t *)idx, nf, nv, deg, counters);
+            else
+                hipLaunchKernelGGL(normals_count_kernel<uint32_t>, dim3(gf), dim3(BLOCK), 0, st, (const uint32_t *)idx, nf, nv, deg, counters);
+        }
+        const int rc = tomo_mc_scan(deg, nv, off, nullptr, nullptr, (unsigned long long *)(base + w.totals), base + w.scan, w.scan_bytes, st);
+        if (rc != TOMO_OK) return rc;
+        if (nf > 0) {
+            if (idx_i64)
+                hipLaunchKernelGGL(normals_fill_kernel<int64_t>, dim3(gf), dim3(BLOCK), 0, st, (const int64_t *)idx, nf, nv, deg, off, list);
+            else
+                hipLaunchKernelGGL(normals_fill_kernel<uint32_t>, dim3(gf), dim3(BLOCK), 0, st, (const uint32_t *)idx, nf, nv, deg, off, list);
+        }
+    }
+    for (int part = 0; part < 2; part++) {                 // 0: the raw suffix [own, nv), 1: the normals of [0, own)
+        if (!(phase & (1 << part))) continue;
+        const int64_t vb = part == 0 ? own : 0, ve = part == 0 ? nv : own;
+        if (ve <= vb) continue;
+        const unsigned gv = grid_for(ve - vb);
+        if (idx_i64)
+            hipLaunchKernelGGL(vertex_normals_kernel<int64_t>, dim3(gv), dim3(BLOCK), 0, st, pos, vb, ve, (const int64_t *)idx, off, list,
+                               normals, counters, seed, part == 1 ? n_seed : (int64_t)0, raw, part == 0 ? own : ve);
+        else
+            hipLaunchKernelGGL(vertex_normals_kernel<uint32_t>, dim3(gv), dim3(BLOCK), 0, st, pos, vb, ve, (const uint32_t *)idx, off, list,
+                               normals, counters, seed, part == 1 ? n_seed : (int64_t)0, raw, part == 0 ? own : ve);
+    }
+    return tomo_status();
+}
+
 TOMO_API int tomo_mesh_vertex_normals(const float *pos, int64_t nv, const void *idx, int idx_i64, int64_t nf, void *workspace,
                                       int64_t workspace_bytes, float *normals, unsigned long long *counters, void *stream)
 {
@@ -496,30 +638,23 @@ TOMO_API int tomo_mesh_vertex_normals(const float *pos, int64_t nv, const void *
         ((uintptr_t)counters & 7))
         return TOMO_E_ARG;
     if (!normals_sizes_ok(nv, nf)) return TOMO_E_SIZE;
-    const NormalsWs w = normals_ws(nv, nf);
-    if (workspace_bytes < w.total) return TOMO_E_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    char *base = (char *)workspace;
-    u32 *deg = (u32 *)base, *off = (u32 *)(base + w.off), *list = (u32 *)(base + w.list);
-    if (hipMemsetAsync(deg, 0, 4 * nv, st) != hipSuccess || hipMemsetAsync(counters, 0, 2 * sizeof(unsigned long long), st) != hipSuccess)
-        return TOMO_E_LAUNCH;
-    const unsigned gf = grid_for(nf), gv = grid_for(nv);
-    if (idx_i64)
-        hipLaunchKernelGGL(normals_count_kernel<int64_t>, dim3(gf), dim3(BLOCK), 0, st, (const int64_t *)idx, nf, nv, deg, counters);
-    else
-        hipLaunchKernelGGL(normals_count_kernel<uint32_t>, dim3(gf), dim3(BLOCK), 0, st, (const uint32_t *)idx, nf, nv, deg, counters);
-    const int rc = tomo_mc_scan(deg, nv, off, nullptr, nullptr, (unsigned long long *)(base + w.totals), base + w.scan, w.scan_bytes, st);
-    if (rc != TOMO_OK) return rc;
-    if (idx_i64) {
-        hipLaunchKernelGGL(normals_fill_kernel<int64_t>, dim3(gf), dim3(BLOCK), 0, st, (const int64_t *)idx, nf, nv, deg, off, list);
-        hipLaunchKernelGGL(vertex_normals_kernel<int64_t>, dim3(gv), dim3(BLOCK), 0, st, pos, nv, (const int64_t *)idx, off, list, normals,
-                           counters);
-    } else {
-        hipLaunchKernelGGL(normals_fill_kernel<uint32_t>, dim3(gf), dim3(BLOCK), 0, st, (const uint32_t *)idx, nf, nv, deg, off, list);
-        hipLaunchKernelGGL(vertex_normals_kernel<uint32_t>, dim3(gv), dim3(BLOCK), 0, st, pos, nv, (const uint32_t *)idx, off, list, normals,
-                           counters);
-    }
-    return tomo_status();
+    if (workspace_bytes < normals_ws(nv, nf).total) return TOMO_E_WORKSPACE;
+    return normals_run(pos, nv, idx, idx_i64, nf, workspace, normals, counters, nullptr, 0, nullptr, 0, 3, (hipStream_t)stream);
+}
+
+TOMO_API int tomo_mesh_vertex_normals_seeded(const float *pos, int64_t nv, const void *idx, int idx_i64, int64_t nf, void *workspace,
+                                             int64_t workspace_bytes, float *normals, unsigned long long *counters, const double *seed,
+                                             int64_t n_seed, double *raw, int64_t n_raw, int phase, void *stream)
+{
+    if (!pos || !workspace || !counters || nv <= 0 || nf < 0 || n_seed < 0 || n_raw < 0 || phase < 1 || phase > 3) return TOMO_E_ARG;
+    if (n_raw > nv || n_seed > nv - n_raw || (nf > 0 && !idx) || (n_seed > 0 && !seed) || (n_raw > 0 && !raw)) return TOMO_E_ARG;
+    if ((phase & 2) && nv - n_raw > 0 && !normals) return TOMO_E_ARG;
+    if (((uintptr_t)pos & 3) || ((uintptr_t)normals & 3) || ((uintptr_t)idx & (idx_i64 ? 7 : 3)) || ((uintptr_t)workspace & 255) ||
+        ((uintptr_t)counters & 7) || ((uintptr_t)seed & 7) || ((uintptr_t)raw & 7))
+        return TOMO_E_ARG;
+    if (!normals_sizes_ok(nv, nf)) return TOMO_E_SIZE;
+    if (workspace_bytes < normals_ws(nv, nf).total) return TOMO_E_WORKSPACE;
+    return normals_run(pos, nv, idx, idx_i64, nf, workspace, normals, counters, seed, n_seed, raw, n_raw, phase, (hipStream_t)stream);
 }
 
 TOMO_API int tomo_layer_colors(const void *verts, int is_f64, int64_t nv, int64_t stride, double start1, double end1, int enable1,
@@ -558,6 +693,36 @@ TOMO_API int tomo_mesh_edges(const int64_t *faces, int64_t nf, int64_t nv, void 
         return TOMO_E_LAUNCH;
     hipLaunchKernelGGL(edge_insert_kernel, dim3(grid_for(nf)), dim3(BLOCK), 0, st, faces, nf, nv, t, counters);
     hipLaunchKernelGGL(edge_classify_kernel, dim3(grid_for(cap)), dim3(BLOCK), 0, st, t, counters);
+    return tomo_status();
+}
+
+TOMO_API int tomo_mesh_seam_edges(const void *table, int64_t bytes, int64_t nf, int64_t first_ghost, unsigned long long *msg, int64_t cap,
+                                  unsigned long long *count, void *stream)
+{
+    if (!table || !count || nf <= 0 || first_ghost < 0 || cap < 0 || (cap > 0 && !msg)) return TOMO_E_ARG;
+    if (((uintptr_t)msg & 7) || ((uintptr_t)count & 7)) return TOMO_E_ARG;
+    if (nf >= (int64_t)1 << 31 || first_ghost > (int64_t)0xffffffffLL) return TOMO_E_SIZE;
+    if (bytes < table_bytes(nf)) return TOMO_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t cap_t = table_cap(nf);
+    if (hipMemsetAsync(count, 0, sizeof(unsigned long long), st) != hipSuccess) return TOMO_E_LAUNCH;
+    hipLaunchKernelGGL(seam_collect_kernel, dim3(grid_for(cap_t)), dim3(BLOCK), 0, st, table_view((void *)table, cap_t), (u64)first_ghost, cap,
+                       (u64 *)msg, count);
+    return tomo_status();
+}
+
+TOMO_API int tomo_mesh_seam_merge(const void *table, int64_t bytes, int64_t nf, const unsigned long long *msg, int64_t n, int64_t *corr,
+                                  void *stream)
+{
+    if (!table || !corr || nf <= 0 || n < 0 || (n > 0 && !msg)) return TOMO_E_ARG;
+    if (((uintptr_t)msg & 7) || ((uintptr_t)corr & 7)) return TOMO_E_ARG;
+    if (nf >= (int64_t)1 << 31) return TOMO_E_SIZE;
+    if (bytes < table_bytes(nf)) return TOMO_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(corr, 0, 4 * sizeof(int64_t), st) != hipSuccess) return TOMO_E_LAUNCH;
+    if (n == 0) return TOMO_OK;
+    hipLaunchKernelGGL(seam_merge_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, st, table_view((void *)table, table_cap(nf)), (const u64 *)msg, n,
+                       (unsigned long long *)corr);
     return tomo_status();
 }
 

@@ -905,18 +905,26 @@ def layer_colors(verts: torch.Tensor, slice_depths, first_section1_slice, last_s
     return out
 
 
+def edge_table(faces: torch.Tensor, nv: int):
+    """tomo_mesh_edges, enqueued: (table bytes on the device, their number, counters int64 (6,) on the device)."""
+    L = _lib.lib()
+    nf = faces.shape[0]
+    tb = L.tomo_mesh_edge_table_bytes(nf)
+    if tb < 0:
+        raise ValueError("too many faces for the edge table: %d" % nf)
+    table = torch.empty(tb, dtype=torch.uint8, device=faces.device)
+    counters = torch.empty(6, dtype=torch.int64, device=faces.device)
+    _lib.check(L.tomo_mesh_edges(_p(faces), nf, nv, _p(table), tb, _p(counters), _stream()), "tomo_mesh_edges")
+    return table, tb, counters
+
+
 def _edge_stats(faces: torch.Tensor, nv: int):
     """Rules 1-2 of the orientation contract: (flip uint8 (F,) or None, stats).  The edge table decides; the union-find runs
     only when some manifold edge has both faces running it the same way."""
     L = _lib.lib()
     nf = faces.shape[0]
     dev = faces.device
-    tb = L.tomo_mesh_edge_table_bytes(nf)
-    if tb < 0:
-        raise ValueError("too many faces for the edge table: %d" % nf)
-    table = torch.empty(tb, dtype=torch.uint8, device=dev)
-    counters = torch.empty(6, dtype=torch.int64, device=dev)
-    _lib.check(L.tomo_mesh_edges(_p(faces), nf, nv, _p(table), tb, _p(counters), _stream()), "tomo_mesh_edges")
+    table, tb, counters = edge_table(faces, nv)
     c = counters.cpu().tolist()
     if c[4]:
         raise IndexError("%d faces have an index outside [0, %d)" % (c[4], nv))
@@ -1082,44 +1090,59 @@ def glb_download(p: GlbPacked) -> np.ndarray:
 
 
 def glb_json(p: GlbPacked, minmax) -> dict:
+    return glb_json_counts(p.nv, p.nf, p.color_cols, p.normals, minmax)
+
+
+def glb_json_counts(nv: int, nf: int, color_cols: int, normals: bool, minmax) -> dict:
+    """The JSON chunk's content from the counts and POSITION's min / max alone (the Z-slab job forms it on every rank from
+    the global counts)."""
+    bin_len = glb_layout_bytes(nv, nf, color_cols, normals)
     attrs = {"POSITION": 0}
-    views = [{"buffer": 0, "byteOffset": 0, "byteLength": 12 * p.nv, "target": 34962},
-             {"buffer": 0, "byteOffset": 12 * p.nv, "byteLength": 12 * p.nf, "target": 34963}]
-    accessors = [{"bufferView": 0, "componentType": 5126, "count": p.nv, "type": "VEC3",
+    views = [{"buffer": 0, "byteOffset": 0, "byteLength": 12 * nv, "target": 34962},
+             {"buffer": 0, "byteOffset": 12 * nv, "byteLength": 12 * nf, "target": 34963}]
+    accessors = [{"bufferView": 0, "componentType": 5126, "count": nv, "type": "VEC3",
                   "min": [float(x) for x in minmax[:3]], "max": [float(x) for x in minmax[3:]]},
-                 {"bufferView": 1, "componentType": 5125, "count": 3 * p.nf, "type": "SCALAR"}]
-    if p.color_cols:
+                 {"bufferView": 1, "componentType": 5125, "count": 3 * nf, "type": "SCALAR"}]
+    if color_cols:
         attrs["COLOR_0"] = 2
-        views.append({"buffer": 0, "byteOffset": 12 * p.nv + 12 * p.nf, "byteLength": 4 * p.nv, "byteStride": 4, "target": 34962})
-        accessors.append({"bufferView": 2, "componentType": 5121, "normalized": True, "count": p.nv,
-                          "type": "VEC4" if p.color_cols == 4 else "VEC3"})
-    if p.normals:
+        views.append({"buffer": 0, "byteOffset": 12 * nv + 12 * nf, "byteLength": 4 * nv, "byteStride": 4, "target": 34962})
+        accessors.append({"bufferView": 2, "componentType": 5121, "normalized": True, "count": nv,
+                          "type": "VEC4" if color_cols == 4 else "VEC3"})
+    if normals:
         attrs["NORMAL"] = len(accessors)
-        views.append({"buffer": 0, "byteOffset": p.bin_len - 12 * p.nv, "byteLength": 12 * p.nv, "target": 34962})
-        accessors.append({"bufferView": len(views) - 1, "componentType": 5126, "count": p.nv, "type": "VEC3"})
+        views.append({"buffer": 0, "byteOffset": bin_len - 12 * nv, "byteLength": 12 * nv, "target": 34962})
+        accessors.append({"bufferView": len(views) - 1, "componentType": 5126, "count": nv, "type": "VEC3"})
     return {"asset": {"version": "2.0", "generator": "tomography_3d_reconstructor_amd"},
             "scene": 0, "scenes": [{"nodes": [0]}], "nodes": [{"mesh": 0}],
             "meshes": [{"primitives": [{"attributes": attrs, "indices": 1, "mode": 4}]}],
-            "buffers": [{"byteLength": p.bin_len}], "bufferViews": views, "accessors": accessors}
+            "buffers": [{"byteLength": bin_len}], "bufferViews": views, "accessors": accessors}
+
+
+def glb_head(nv: int, nf: int, color_cols: int, normals: bool, minmax):
+    """Everything in front of the binary chunk's data -- the 12-byte header, the JSON chunk (padded with spaces) and the
+    binary chunk's 8-byte header -- and the file's total length: (bytes, total).  Raises like glb_write."""
+    import json
+    import struct
+    if not np.isfinite(np.asarray(minmax, dtype=np.float32)).all():
+        raise ValueError("vertex positions are not finite")
+    bin_len = glb_layout_bytes(nv, nf, color_cols, normals)
+    js = json.dumps(glb_json_counts(nv, nf, color_cols, normals, minmax), separators=(",", ":")).encode()
+    js += b" " * (-len(js) % 4)
+    total = 12 + 8 + len(js) + 8 + bin_len
+    if total > GLB_MAX_BYTES:
+        raise ValueError("the GLB would exceed the 4 GiB length field (%d bytes)" % total)
+    return (struct.pack("<4sII", b"glTF", 2, total) + struct.pack("<II", len(js), 0x4E4F534A) + js
+            + struct.pack("<II", bin_len, 0x004E4942)), total
 
 
 def glb_write(path, p: GlbPacked, host: np.ndarray) -> dict:
     """Step 5: the JSON chunk (padded with spaces) and the binary chunk (padded with zeros -- its length is already a
     multiple of 4) behind the 12-byte header.  Returns the stats, `inverted` and `signed_volume` filled in."""
-    import json
-    import struct
     minmax = host[p.tail: p.tail + 24].view(np.float32)
     vol = float(host[p.tail + 24: p.tail + 32].view(np.float64)[0])
-    if not np.isfinite(minmax).all():
-        raise ValueError("vertex positions are not finite")
-    js = json.dumps(glb_json(p, minmax), separators=(",", ":")).encode()
-    js += b" " * (-len(js) % 4)
-    total = 12 + 8 + len(js) + 8 + p.bin_len
-    if total > GLB_MAX_BYTES:
-        raise ValueError("the GLB would exceed the 4 GiB length field (%d bytes)" % total)
+    head, _ = glb_head(p.nv, p.nf, p.color_cols, p.normals, minmax)
     with open(path, "wb") as fh:
-        fh.write(struct.pack("<4sII", b"glTF", 2, total) + struct.pack("<II", len(js), 0x4E4F534A) + js
-                 + struct.pack("<II", p.bin_len, 0x004E4942))
+        fh.write(head)
         fh.write(memoryview(host)[: p.bin_len])
     stats = dict(p.stats)
     stats["inverted"] = vol < 0

@@ -528,6 +528,38 @@ def balanced_cuts(weights, world, min_slices=1):
     return cuts
 
 
+def glb_rank_layout(counts_v, counts_f, color_cols=0, normals=False):
+    """Where every rank's blocks lie in the binary chunk of the ONE GLB the ranks write together (pure arithmetic; layout as
+    pipeline.glb_layout_bytes: POSITION 12 V | indices 12 F | COLOR_0 4 V | NORMAL 12 V, each block the ranks' runs in rank
+    order).  counts_v / counts_f: vertices / faces per rank.  -> (bytes of the chunk, per rank a list of (block name, offset
+    in the chunk, bytes))."""
+    V, F = int(sum(counts_v)), int(sum(counts_f))
+    col_at = 12 * V + 12 * F
+    nrm_at = col_at + (4 * V if color_cols else 0)
+    per, ov, of = [], 0, 0
+    for kv, kf in zip(counts_v, counts_f):
+        kv, kf = int(kv), int(kf)
+        blocks = [("POSITION", 12 * ov, 12 * kv), ("indices", 12 * V + 12 * of, 12 * kf)]
+        if color_cols:
+            blocks.append(("COLOR_0", col_at + 4 * ov, 4 * kv))
+        if normals:
+            blocks.append(("NORMAL", nrm_at + 12 * ov, 12 * kv))
+        per.append(blocks)
+        ov, of = ov + kv, of + kf
+    return pipeline.glb_layout_bytes(V, F, color_cols, bool(normals)), per
+
+
+# what a failure on one rank becomes on every rank (the code travels in the all-gathers of export_glb)
+_GLB_ERRORS = (None, ValueError, OSError, IndexError, TypeError, RuntimeError)
+
+
+def _glb_error_code(e):
+    for code in range(1, len(_GLB_ERRORS) - 1):
+        if isinstance(e, _GLB_ERRORS[code]):
+            return code
+    return len(_GLB_ERRORS) - 1
+
+
 class SlabJob:
     """One rank's share of: close ends -> smooth -> field -> marching cubes -> global mesh numbering."""
 
@@ -1033,6 +1065,332 @@ class SlabJob:
         nv, nf = (int(x) for x in out[64:].view(np.int64))
         return out[:32].tobytes().hex(), out[32:64].tobytes().hex(), nv, nf
 
+    def _agree(self, row, what, path, err, dev, who="export_obj", deadline=False):
+        """All-gather one int64 row per rank whose LAST entry is this rank's error flag; a failure on ANY rank becomes the
+        same exception on EVERY rank (nobody is left waiting in the next collective step) and rank 0 removes the file.
+        export_obj raises OSError; export_glb's flag is a code into _GLB_ERRORS (the lowest failing rank's kind is raised)
+        and its waits have the job's deadline."""
+        import os
+        row = row if torch.is_tensor(row) else torch.tensor(row, dtype=torch.int64, device=dev)
+        table = torch.stack(self.comm.all_gather(row))
+        if deadline:
+            self._await(dev)
+        table = table.cpu().numpy()
+        bad = [r for r in range(self.world) if table[r, -1]]
+        if bad:
+            if self.rank == 0:
+                try:
+                    os.unlink(path)
+                except OSError:
+                    pass
+            kind = OSError if who == "export_obj" else _GLB_ERRORS[min(max(int(table[bad[0], -1]), 1), len(_GLB_ERRORS) - 1)]
+            raise kind("%s: %s failed on rank(s) %s%s" % (who, what, bad, (": %r" % (err[0],)) if err else ""))
+        return table
+
+    def layer_colors(self, slice_depths, first_section1_slice, last_section1_slice, highlight_thickness_mm=1.0):
+        """create_layer_colors (glb_exporter.py:52-91) for THIS rank's own vertex rows: uint8 (k, 4) on the device, what
+        pipeline.layer_colors gives for these rows of the gathered mesh.  slice_depths: the depths of the WHOLE stack (a
+        vertex's colour depends on its own depth and the global table only), so export_glb(colors=job.layer_colors(...))
+        is the orchestrator's export (tomography_3d_reconstruction.py:253-268)."""
+        if self.mesh is None:
+            raise RuntimeError("run() first")
+        return pipeline.layer_colors(self.mesh[0], slice_depths, first_section1_slice, last_section1_slice, highlight_thickness_mm)
+
+    def export_glb(self, path, colors=None, normals=False, mesh=None):
+        """ONE GLB of the whole mesh, byte for byte what pipeline.export_glb(path, V, F, C, normals) writes from the gathered
+        mesh (the ranks' vertex runs, face runs and colour rows concatenated in rank order) -- without gathering it.  A
+        collective call: every rank passes the same path, the same `normals` and colours or none, after run() / result().
+        colors: this rank's uint8 (k, 3) or (k, 4) device tensor for its k own rows; mesh: this rank's (vertices, faces) with
+        the job's current numbering (default: self.mesh).  Returns pipeline.export_glb's stats dict, the same on every rank
+        (signed_volume is the per-rank partial sums added in rank order: equal to the single-GPU tree sum to ~1e-6 relative).
+
+        Every mesh the job makes is closed and consistently wound, so the single-GPU export takes its fast path on it: no
+        face flips by rules 1-2 of the orientation contract (include/tomo_hip.h), every face or none by the sign of the
+        volume.  That path is distributed here.  A face of rank r names own rows or a prefix of rank r + 1's rows (its GHOST
+        rows, on the shared plane); the rank works on local indices (faces - offset: own rows, then ghost rows), so the
+        single-GPU kernels run unchanged.  Collective steps: counts + index range (all-gather) | ghost rows down | seam-edge
+        counts (all-gather) | seam records up | corrected edge counters (all-gather, the joint decision) | partial volumes and
+        POSITION min / max (all-gather) | raw normal sums of the ghost rows up | ONE download per rank | "the file exists" |
+        every rank writes its slices of the blocks (glb_rank_layout) | "written".  A rank holds its own rows, its own faces
+        and messages the size of one shared plane.
+
+        Fallback -- input the job never makes (inconsistent pairs, e.g. faces edited through `mesh`, or a face that names a
+        row outside its own and the next rank's run, e.g. planes merged by zero slice depths): rows, faces and colours travel
+        down the ranks in world - 1 neighbour steps and rank 0 runs the single-GPU export.  THIS PATH NEEDS THE WHOLE MESH ON
+        ONE CARD (rank 0's); a cross-rank union-find is not built.
+
+        A failure on any rank -- a colour tensor of the wrong shape, the size limits, non-finite positions, an unwritable path,
+        a failed launch -- is the same exception type on every rank at the same collective step; rank 0 removes the file."""
+        import os
+        from . import _lib
+        mesh = self.mesh if mesh is None else mesh
+        if mesh is None:
+            raise RuntimeError("run() first")
+        verts, faces = mesh
+        normals = bool(normals)
+        if self.world == 1:
+            return pipeline.export_glb(path, verts, faces, colors, normals)
+        L = _lib.lib()
+        r, w = self.rank, self.world
+        dev = verts.device
+        err = []
+
+        def i64(*x):
+            return torch.tensor(x, dtype=torch.int64, device=dev)
+
+        def agree(row, what):
+            row = row if torch.is_tensor(row) else i64(*row)
+            return self._agree(torch.cat([row, i64(_glb_error_code(err[0]) if err else 0)]), what, path, err, dev, "export_glb", True)
+
+        # -- counts, index range, local argument checks
+        k = nf = cc = 0
+        frange = i64(0, -1)
+        try:
+            if verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype not in (torch.float32, torch.float64):
+                raise ValueError("vertices must be (V, 3) float32 or float64")
+            if faces.dim() != 2 or faces.shape[1] != 3:
+                raise ValueError("faces must be (F, 3)")
+            if faces.dtype != torch.int64:
+                if faces.dtype.is_floating_point or faces.dtype == torch.bool:
+                    raise TypeError("faces must be integer")
+                faces = faces.to(torch.int64)
+            verts, faces = verts.to(torch.float32).contiguous(), faces.contiguous()     # POSITION as the file stores it
+            if colors is not None:
+                if colors.dtype != torch.uint8 or colors.dim() != 2 or colors.shape[0] != verts.shape[0] or colors.shape[1] not in (3, 4):
+                    raise ValueError("vertex colours must be uint8 (V, 3) or (V, 4)")
+                cc = int(colors.shape[1])
+            k, nf = int(verts.shape[0]), int(faces.shape[0])
+            if nf:
+                frange = torch.stack(torch.aminmax(faces.reshape(-1)))
+        except Exception as e:                                       # noqa: BLE001  (raised on every rank below)
+            err.append(e)
+            k = nf = 0
+        t = agree(torch.cat([i64(k, nf, cc, int(normals), int(getattr(self, "vertex_offset", 0) or 0)), frange]), "checking the arguments")
+        ks, nfs = [int(x) for x in t[:, 0]], [int(x) for x in t[:, 1]]
+        offs = [0]
+        for x in ks:
+            offs.append(offs[-1] + x)
+        V, F = offs[-1], sum(nfs)
+        # everything decided from the table is decided alike on every rank
+        if len(set(int(x) for x in t[:, 2])) > 1 or len(set(int(x) for x in t[:, 3])) > 1:
+            raise ValueError("export_glb: every rank must pass the same `normals` and colours of one width, or none")
+        if any(int(t[i, 4]) != offs[i] for i in range(w)):
+            raise ValueError("export_glb: the mesh does not have the job's current numbering")
+        pipeline.glb_check_sizes(V, F, cc, normals)
+        top = [offs[i + 1] + (ks[i + 1] if i + 1 < w else 0) for i in range(w)]
+        pre_ok = all(nfs[i] == 0 or (int(t[i, 5]) >= offs[i] and int(t[i, 6]) < top[i]) for i in range(w))
+        if not pre_ok:
+            return self._export_glb_gathered(path, verts, faces, colors, cc, normals, ks, nfs, err, agree)
+        ghosts = [max(0, int(t[i, 6]) - offs[i + 1] + 1) if nfs[i] else 0 for i in range(w)]
+        g, gp = ghosts[r], (ghosts[r - 1] if r else 0)                # ghost rows of this rank / of the rank below (a prefix of mine)
+
+        # -- this rank's ONE buffer: POSITION own | ghost rows | indices | COLOR_0 | NORMAL | tail (min / max, volume, counters)
+        o_idx = 12 * (k + g)
+        o_col = o_idx + 12 * nf
+        o_nrm = o_col + (4 * k if cc else 0)
+        tail = (o_nrm + (12 * k if normals else 0) + 7) & ~7
+        buf = base = st = down = None
+        if not err:
+            try:
+                buf = torch.empty(tail + 48, dtype=torch.uint8, device=dev)
+                buf[tail:].zero_()
+                base, st = buf.data_ptr(), pipeline._stream()
+                if k:
+                    _lib.check(L.tomo_glb_pack_positions(verts.data_ptr(), 0, k, base, base + tail, st), "tomo_glb_pack_positions")
+                down = buf[:12 * gp].view(torch.float32).view(gp, 3)
+            except Exception as e:                                   # noqa: BLE001
+                err.append(e)
+        if down is None:
+            down = torch.zeros((gp, 3), dtype=torch.float32, device=dev)
+        _, ghost = self.comm.exchange(down, None, torch.float32, recv_shape_next=(g, 3))
+
+        # -- local edge table, number of seam edges
+        nseam = torch.zeros(1, dtype=torch.int64, device=dev)
+        counters = torch.zeros(6, dtype=torch.int64, device=dev)
+        table = tb = faces_l = None
+        if not err:
+            try:
+                if g:
+                    buf[12 * k:12 * (k + g)].view(torch.float32).copy_(ghost.reshape(-1))
+                if nf:
+                    faces_l = faces - offs[r]                         # own rows 0 .. k - 1, ghost rows k .. k + g - 1
+                    table, tb, counters = pipeline.edge_table(faces_l, k + g)
+                    if g:
+                        _lib.check(L.tomo_mesh_seam_edges(table.data_ptr(), tb, nf, k, None, 0, nseam.data_ptr(), st), "tomo_mesh_seam_edges")
+            except Exception as e:                                   # noqa: BLE001
+                err.append(e)
+        seams = [int(x) for x in agree(nseam, "building the edge table")[:, 0]]
+        ns, nsp = seams[r], (seams[r - 1] if r else 0)
+
+        # -- seam records up, corrections, the joint decision
+        msg = torch.zeros((ns, 2), dtype=torch.int64, device=dev)
+        if ns and not err:
+            try:
+                _lib.check(L.tomo_mesh_seam_edges(table.data_ptr(), tb, nf, k, msg.data_ptr(), ns, nseam.data_ptr(), st), "tomo_mesh_seam_edges")
+            except Exception as e:                                   # noqa: BLE001
+                err.append(e)
+        below, _ = self.comm.exchange(None, msg, torch.int64, recv_shape_prev=(nsp, 2))
+        corr = torch.zeros(4, dtype=torch.int64, device=dev)
+        if nsp and nf and not err:                                    # (no faces here: nothing to pair with, the lower rank's counts stand)
+            try:
+                below = below.contiguous()
+                _lib.check(L.tomo_mesh_seam_merge(table.data_ptr(), tb, nf, below.data_ptr(), nsp, corr.data_ptr(), st), "tomo_mesh_seam_merge")
+            except Exception as e:                                   # noqa: BLE001
+                err.append(e)
+        t = agree(torch.cat([counters[:4] + corr, counters[4:6]]), "classifying the edges")
+        del table, below, msg
+        c = [int(x) for x in t[:, :6].sum(0)]
+        if c[4]:
+            raise IndexError("%d faces have an index outside [0, %d)" % (c[4], V))
+        if c[3]:
+            return self._export_glb_gathered(path, verts, faces, colors, cc, normals, ks, nfs, err, agree)
+        stats = {"boundary_edges": c[0], "manifold_edges": c[1], "non_manifold_edges": c[2], "inconsistent_pairs": 0,
+                 "degenerate_faces": c[5], "components": None, "conflicts": 0, "fast_path": True}
+
+        # -- rule 3: partial volumes in rank order, POSITION min / max of the ranks that have rows
+        row = torch.zeros(7, dtype=torch.int64, device=dev)
+        if not err:
+            try:
+                if nf:
+                    _lib.check(L.tomo_mesh_signed_volume(base, faces_l.data_ptr(), nf, None, base + tail + 24, st), "tomo_mesh_signed_volume")
+                row = torch.cat([buf[tail + 24:tail + 32].view(torch.int64), buf[tail:tail + 24].view(torch.float32).to(torch.float64).view(torch.int64)])
+            except Exception as e:                                   # noqa: BLE001
+                err.append(e)
+        vals = np.ascontiguousarray(agree(row, "the signed volume")[:, :7]).view(np.float64)
+        vol = 0.0
+        for i in range(w):
+            vol += float(vals[i, 0])
+        have = [i for i in range(w) if ks[i]]
+        minmax = np.concatenate([vals[have, 1:4].astype(np.float32).min(0), vals[have, 4:7].astype(np.float32).max(0)])
+        head, total = pipeline.glb_head(V, F, cc, normals, minmax)    # raises alike on every rank (non-finite positions, 4 GiB)
+        stats["inverted"] = vol < 0
+        stats["signed_volume"] = -vol if vol < 0 else vol
+        sent = {"ghost_rows_down": 12 * gp, "seam_records_up": 16 * ns if r + 1 < w else 0, "normal_sums_up": 0}
+
+        # -- pack: global indices, colours, normals (ghost rows' raw sums go up, the owner continues them)
+        host = None
+        if not err:
+            try:
+                gvol = torch.tensor([vol], dtype=torch.float64, device=dev)
+                if nf:
+                    _lib.check(L.tomo_glb_pack_faces(faces.data_ptr(), nf, None, gvol.data_ptr(), base + o_idx, 0, st), "tomo_glb_pack_faces")
+                if cc:
+                    cv = buf[o_col:o_col + 4 * k].view(k, 4)
+                    cv[:, :cc].copy_(colors)
+                    if cc == 3:
+                        cv[:, 3].zero_()
+            except Exception as e:                                   # noqa: BLE001
+                err.append(e)
+        if normals:
+            raw = torch.zeros((g, 3), dtype=torch.float64, device=dev)
+            ws = wsb = idx_l = None
+
+            def sums(seed, phase):
+                _lib.check(L.tomo_mesh_vertex_normals_seeded(base, k + g, pipeline._p(idx_l), 0, nf, ws.data_ptr(), wsb, base + o_nrm,
+                                                             base + tail + 32, pipeline._p(seed), gp if seed is not None else 0,
+                                                             pipeline._p(raw) if g else None, g, phase, st), "tomo_mesh_vertex_normals_seeded")
+            if k + g and not err:
+                try:
+                    if nf:
+                        idx_l = torch.empty((nf, 3), dtype=torch.int32, device=dev)       # the oriented faces in local numbers
+                        _lib.check(L.tomo_glb_pack_faces(faces_l.data_ptr(), nf, None, gvol.data_ptr(), idx_l.data_ptr(), 0, st), "tomo_glb_pack_faces")
+                    wsb = L.tomo_mesh_vertex_normals_workspace_bytes(k + g, max(nf, 1))
+                    if wsb < 0:
+                        raise ValueError("the mesh is too large for the vertex-normal lists: %d vertices, %d faces" % (k + g, nf))
+                    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+                    sums(None, 1)
+                except Exception as e:                               # noqa: BLE001
+                    err.append(e)
+            seed, _ = self.comm.exchange(None, raw, torch.float64, recv_shape_prev=(gp, 3))
+            sent["normal_sums_up"] = 24 * g
+            if k and not err:
+                try:
+                    sums(seed.contiguous() if gp else None, 2)
+                except Exception as e:                               # noqa: BLE001
+                    err.append(e)
+            del ws, idx_l
+        del faces_l
+        ndef = 0
+        if not err:
+            try:                                                      # ONE download per rank, as on one GPU
+                host = torch.empty(buf.numel(), dtype=torch.uint8, pin_memory=True)
+                host.copy_(buf, non_blocking=True)
+                self._await(dev)
+                torch.cuda.current_stream(dev).synchronize()
+                host = host.numpy()
+                ndef = int(host[tail + 32:tail + 40].view(np.uint64)[0])
+            except Exception as e:                                   # noqa: BLE001
+                err.append(e)
+
+        # -- the file: rank 0 lays it out, every rank writes its slices of the blocks
+        if r == 0 and not err:
+            try:
+                with open(path, "wb") as fh:
+                    fh.write(head)
+                    fh.truncate(total)
+            except OSError as e:                                      # an unwritable path, a full disk
+                err.append(e)
+        t = agree([ndef], "creating the file")                        # the file exists before anyone writes into it
+        if normals:
+            stats["normals_defaulted"] = int(t[:, 0].sum())
+        src = {"POSITION": 0, "indices": o_idx, "COLOR_0": o_col, "NORMAL": o_nrm}
+        try:
+            fd = os.open(path, os.O_WRONLY)
+            try:
+                for name, at, nb in glb_rank_layout(ks, nfs, cc, normals)[1][r]:
+                    view, done = memoryview(host)[src[name]:src[name] + nb], 0
+                    while done < nb:
+                        done += os.pwrite(fd, view[done:], len(head) + at + done)
+            finally:
+                os.close(fd)
+        except OSError as e:
+            err.append(e)
+        agree([0], "writing")                                         # complete on return, on every rank
+        self.glb_last = {"bytes_sent": sent, "ghost_rows": g, "seam_edges": ns, "file_bytes": total}
+        return stats
+
+    def _export_glb_gathered(self, path, verts, faces, colors, cc, normals, ks, nfs, err, agree):
+        """export_glb's fallback: the ranks' rows, faces and colours travel down to rank 0 in world - 1 neighbour steps (in step
+        s a rank passes on what it received in step s - 1, so rank 0 receives rank s + 1's share; a rank in between holds one
+        other rank's share at a time) and rank 0 runs pipeline.glb_pack / glb_write on the WHOLE mesh.  Every rank takes part
+        in every step and receives the stats."""
+        r, w = self.rank, self.world
+        dev = verts.device
+        kinds = [(torch.float32, 3), (torch.int64, 3)] + ([(torch.uint8, cc)] if cc else [])
+        held = [verts, faces] + ([colors.contiguous()] if cc else [])
+        parts = [[x] for x in held]
+        for step in range(w - 1):
+            src = r + step + 1                                        # whose share arrives here in this step
+            rows = (ks[src], nfs[src], ks[src]) if src < w else (0, 0, 0)
+            got = []
+            for i, (dt, cols) in enumerate(kinds):
+                _, x = self.comm.exchange(held[i], None, dt, recv_shape_next=(rows[i], cols))
+                got.append(x if x is not None else torch.zeros((0, cols), dtype=dt, device=dev))
+            held = got
+            if r == 0:
+                for i, x in enumerate(held):
+                    parts[i].append(x)
+        row = [0] * 11
+        if r == 0 and not err:
+            try:
+                self._await(dev)
+                p = pipeline.glb_pack(torch.cat(parts[0]), torch.cat(parts[1]), torch.cat(parts[2]) if cc else None, normals)
+                s = pipeline.glb_write(path, p, pipeline.glb_download(p))
+                row = [s["boundary_edges"], s["manifold_edges"], s["non_manifold_edges"], s["inconsistent_pairs"], s["degenerate_faces"],
+                       -1 if s["components"] is None else s["components"], s["conflicts"], int(s["fast_path"]), int(s["inverted"]),
+                       int(np.float64(s["signed_volume"]).view(np.int64)), s.get("normals_defaulted", 0)]
+            except Exception as e:                                   # noqa: BLE001
+                err.append(e)
+        del parts, held
+        t = [int(x) for x in agree(row, "the single-GPU export on rank 0")[0]]
+        stats = {"boundary_edges": t[0], "manifold_edges": t[1], "non_manifold_edges": t[2], "inconsistent_pairs": t[3],
+                 "degenerate_faces": t[4], "components": None if t[5] < 0 else t[5], "conflicts": t[6], "fast_path": bool(t[7]),
+                 "inverted": bool(t[8]), "signed_volume": float(np.int64(t[9]).view(np.float64))}
+        if normals:
+            stats["normals_defaulted"] = t[10]
+        self.glb_last = {"bytes_sent": None, "gathered": True}
+        return stats
+
     def export_obj(self, path, nthreads=None):
         """ONE OBJ file of the whole mesh, byte for byte what OBJExporter.export_to_obj writes from the gathered
         (vertices, faces) (obj_exporter.py:17-37) -- without gathering it: every rank formats its run of the vertex list
@@ -1052,18 +1410,7 @@ class SlabJob:
         blocks = []
 
         def agree(row, what):
-            """All-gather one int64 row per rank whose LAST entry is this rank's error flag; a failure on ANY rank becomes the
-            same exception on EVERY rank (nobody is left waiting in the next collective step) and rank 0 removes the file."""
-            table = torch.stack(self.comm.all_gather(torch.tensor(row, dtype=torch.int64, device=dev))).cpu().numpy()
-            bad = [r for r in range(self.world) if table[r, -1]]
-            if bad:
-                if self.rank == 0:
-                    try:
-                        os.unlink(path)
-                    except OSError:
-                        pass
-                raise OSError("export_obj: %s failed on rank(s) %s%s" % (what, bad, (": %r" % (err[0],)) if err else ""))
-            return table
+            return self._agree(row, what, path, err, dev)
 
         err = []
         try:
