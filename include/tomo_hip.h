@@ -145,6 +145,21 @@ int tomo_slice_popcounts(const uint64_t *bits, int nz, int ny, int nx, unsigned 
 /* volume_calculator.py:40,62 (np.where(voxel_data) + min/max): box (device int32[6]) = {zmin, zmax, ymin, ymax, xmin,
  * xmax} of the set voxels; an empty volume gives {INT32_MAX, -1, INT32_MAX, -1, INT32_MAX, -1}. */
 int tomo_bbox(const uint64_t *bits, int nz, int ny, int nx, int32_t *box, void *stream);
+/* voxel_processor.py:99-127 (np.where(voxel_data), every k-th entry, one float64 row per kept entry) on the resident bits.
+ * The RANK g of a set voxel is the number of set voxels in front of it in C order (z, y, x) = word order, then ascending
+ * bit; it is kept iff g % k == 0 and becomes row g / k = (z_mm[z], (double)y * mm_y, (double)x * mm_x).
+ *   tomo_point_cloud_blocks  number of fixed-size tiles of words the two passes work in
+ *   tomo_point_cloud_count   blk_off[i] = rank_base + the set voxels of the tiles before tile i, i <= blocks (a popcount per
+ *                            tile, then one single-workgroup 64-bit scan): blk_off[blocks] - rank_base set voxels in all
+ *   tomo_point_cloud_rows    row g / k of every kept voxel goes to out + 3 * (g / k - row_first) iff row_first <= g / k <
+ *                            row_first + cap_rows; nothing else of `out` is written.  A caller fetches a large cloud in windows
+ *                            this way; a Z-slab rank passes rank_base = the set voxels of the ranks below it and row_first =
+ *                            ceil(rank_base / k), and its rows are its run of the whole stack's array.  k >= 1; cap_rows = 0
+ *                            writes nothing (out may be NULL then).  TOMO_E_SIZE from 2^31 words on. */
+int64_t tomo_point_cloud_blocks(int nz, int ny, int nx);
+int tomo_point_cloud_count(const uint64_t *bits, int nz, int ny, int nx, uint64_t rank_base, uint64_t *blk_off, void *stream);
+int tomo_point_cloud_rows(const uint64_t *bits, int nz, int ny, int nx, const uint64_t *blk_off, int64_t k, const double *z_mm,
+                          double mm_y, double mm_x, int64_t row_first, int64_t cap_rows, double *out, void *stream);
 /* image_loader.py:108 (`img >= threshold`) fused with the packing: grey = uint8 (nz, ny, nx) on the device. */
 int tomo_pack_threshold(const uint8_t *grey, uint64_t *bits, int nz, int ny, int nx, int threshold, void *stream);
 /* obj_exporter.py:17-38, byte for byte ("v %.6f %.6f %.6f" per vertex, "f a+1 b+1 c+1" per face), HOST arrays:

@@ -163,3 +163,230 @@ TOMO_API int tomo_pack_threshold(const uint8_t *grey, uint64_t *bits, int nz, in
                            (u64 *)bits, rows, nx, wx, groups, threshold);
     return tomo_status();
 }
+
+// ------------------------------------------------------------------------------------------ point cloud (rank / select)
+// voxel_processor.py:99-127: np.where(voxel_data) -- three int64 index arrays, 24 B per set voxel -- then every k-th entry and
+// one float64 row (z_mm[z], y * mm_y, x * mm_x) per kept entry.  Here the rank of a set voxel (np.where's C order = word
+// order, then ascending bit) comes from popcounts: a count per TILE of PC_TILE words, one 64-bit scan of the tile counts,
+// and a second pass in which every tile ranks its own words and writes the rows whose rank is a multiple of k.
+#define PC_THREADS 256
+#define PC_ROUNDS 8
+#define PC_TILE (PC_THREADS * PC_ROUNDS)        // words per tile; word r * PC_THREADS + t of a tile belongs to thread t, round r
+#define PC_CHUNK 4096                            // selected voxels compacted in LDS at a time
+
+TOMO_API int64_t tomo_point_cloud_blocks(int nz, int ny, int nx)
+{
+    if (nz <= 0 || ny <= 0 || nx <= 0) return TOMO_E_ARG;
+    return ceil_div64((int64_t)nz * ny * tomo_words_per_row(nx), PC_TILE);
+}
+
+__global__ __launch_bounds__(PC_THREADS) void pc_count_kernel(const u64 *__restrict__ bits, u32 nwords, u64 *__restrict__ blk_off)
+{
+    __shared__ u32 wsum[PC_THREADS / 64];
+    const u32 base = blockIdx.x * (u32)PC_TILE;
+    u32 acc = 0;
+#pragma unroll
+    for (int r = 0; r < PC_ROUNDS; r++) {
+        const u32 i = base + r * PC_THREADS + threadIdx.x;
+        acc += i < nwords ? (u32)__popcll(bits[i]) : 0u;
+    }
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) blk_off[blockIdx.x] = (u64)wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// one workgroup: off[i] = base + sum of off[0 .. i) for i <= n, in place, 1024 entries per step with a running carry
+__global__ __launch_bounds__(1024) void pc_scan_kernel(u64 *__restrict__ off, int64_t n, u64 base)
+{
+    __shared__ u64 wsum[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    u64 carry = base;
+    for (int64_t i0 = 0; i0 < n; i0 += 1024) {
+        const int64_t i = i0 + threadIdx.x;
+        const u64 v = i < n ? off[i] : 0;
+        u64 inc = v;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const u64 o = __shfl_up(inc, d, 64);
+            if (lane >= d) inc += o;
+        }
+        if (lane == 63) wsum[wave] = inc;
+        __syncthreads();
+        u64 before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < 16; w++) {
+            const u64 x = wsum[w];
+            before += w < wave ? x : 0;
+            total += x;
+        }
+        if (i < n) off[i] = carry + before + inc - v;
+        carry += total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) off[n] = carry;
+}
+
+TOMO_API int tomo_point_cloud_count(const uint64_t *bits, int nz, int ny, int nx, uint64_t rank_base, uint64_t *blk_off,
+                                    void *stream)
+{
+    if (!bits || !blk_off || nz <= 0 || ny <= 0 || nx <= 0) return TOMO_E_ARG;
+    const int64_t nwords = (int64_t)nz * ny * tomo_words_per_row(nx);
+    if (nwords >= ((int64_t)1 << 31)) return TOMO_E_SIZE;            // word indices are 32-bit in the kernels
+    const int64_t blocks = ceil_div64(nwords, PC_TILE);
+    hipLaunchKernelGGL(pc_count_kernel, dim3((unsigned)blocks), dim3(PC_THREADS), 0, (hipStream_t)stream, (const u64 *)bits,
+                       (u32)nwords, (u64 *)blk_off);
+    hipLaunchKernelGGL(pc_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (u64 *)blk_off, blocks, (u64)rank_base);
+    return tomo_status();
+}
+
+// t = q k + r for t < 2^32 or t < 2 k (the only cases the rows kernel forms): one 32-bit division or one subtraction
+__device__ static inline void pc_divmod(u64 t, u64 k, u64 *q, u64 *r)
+{
+    if (((t | k) >> 32) == 0) {
+        const u32 qq = (u32)t / (u32)k;
+        *q = qq;
+        *r = (u32)t - qq * (u32)k;
+    } else {
+        u64 qq = 0;
+        while (t >= k) { t -= k; qq++; }
+        *q = qq;
+        *r = t;
+    }
+}
+__device__ static inline u64 pc_ceil_div(u64 a, u64 k) { const u64 q = a / k; return q + (a != q * k ? 1 : 0); }
+
+// position of the j-th (0-based) set bit of w; j < popcount(w)
+__device__ static inline u32 pc_select(u64 w, u32 j)
+{
+    u32 pos = 0;
+#pragma unroll
+    for (int width = 32; width > 0; width >>= 1) {
+        const u32 c = (u32)__popcll(w & ((1ull << width) - 1));
+        if (j >= c) { j -= c; w >>= width; pos += width; }
+    }
+    return pos;
+}
+
+__global__ __launch_bounds__(PC_THREADS) void pc_rows_kernel(const u64 *__restrict__ bits, u32 nwords, int ny, int wx,
+                                                             const u64 *__restrict__ blk_off, u64 k,
+                                                             const double *__restrict__ z_mm, double mm_y, double mm_x,
+                                                             int64_t row_first, int64_t cap_rows, double *__restrict__ out)
+{
+    __shared__ double zt[PC_TILE];            // per word of the tile: z_mm[z], y, 64 * (word in row)
+    __shared__ u32 yt[PC_TILE];
+    __shared__ u32 xt[PC_TILE];
+    __shared__ u32 sel[PC_CHUNK];             // (word in tile) << 6 | bit of the selected voxels of the chunk, in row order
+    __shared__ u32 wtot[PC_ROUNDS][PC_THREADS / 64];
+
+    const u64 lo = blk_off[blockIdx.x], hi = blk_off[blockIdx.x + 1];
+    // rows of this tile: [R0, R1) of the whole run; of those, local rows [ls, le) fall into the caller's window
+    const u64 R0 = pc_ceil_div(lo, k), R1 = pc_ceil_div(hi, k);
+    const u64 W0 = (u64)row_first, W1 = (u64)row_first + (u64)cap_rows;
+    const u64 a = R0 > W0 ? R0 : W0, b = R1 < W1 ? R1 : W1;
+    if (a >= b) return;
+    const u32 ls = (u32)(a - R0), le = (u32)(b - R0);
+    const u64 m = lo % k;
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const u32 base = blockIdx.x * (u32)PC_TILE;
+    u64 w[PC_ROUNDS];
+    u32 pre[PC_ROUNDS];                       // inclusive wave prefix of the popcounts, then the word's exclusive rank in the tile
+#pragma unroll
+    for (int r = 0; r < PC_ROUNDS; r++) {
+        const u32 wi = r * PC_THREADS + threadIdx.x, i = base + wi;
+        w[r] = i < nwords ? bits[i] : 0ull;
+        pre[r] = wave_inclusive_scan((u32)__popcll(w[r]));
+        if (lane == 63) wtot[r][wave] = pre[r];
+        if (i < nwords) {
+            const u32 row = i / (u32)wx, z = row / (u32)ny;
+            zt[wi] = z_mm[z];
+            yt[wi] = row - z * (u32)ny;
+            xt[wi] = (i - row * (u32)wx) * 64u;
+        }
+    }
+    __syncthreads();
+    u32 first[PC_ROUNDS], skip[PC_ROUNDS], nsel[PC_ROUNDS];   // local row of the word's first selected bit, set bits in front of it
+    {
+        u32 run = 0;
+#pragma unroll
+        for (int r = 0; r < PC_ROUNDS; r++) {
+            u32 before = run;
+#pragma unroll
+            for (int v = 0; v < PC_THREADS / 64; v++) {
+                const u32 x = wtot[r][v];
+                before += v < wave ? x : 0u;
+                run += x;
+            }
+            const u32 c = (u32)__popcll(w[r]);
+            const u32 p = before + pre[r] - c;                 // set voxels of the tile in front of this word
+            u64 q, rem;
+            pc_divmod(m + p, k, &q, &rem);
+            first[r] = (u32)q + (rem ? 1u : 0u) - (m ? 1u : 0u);   // multiples of k among the ranks [lo, lo + p)
+            const u64 j0 = rem ? k - rem : 0;                  // set bits of the word in front of its first selected one
+            if (j0 < c) {
+                skip[r] = (u32)j0;
+                nsel[r] = (c - (u32)j0 - 1) / (u32)(k < 64 ? k : 64) + 1;
+            } else {
+                skip[r] = 0;
+                nsel[r] = 0;
+            }
+        }
+    }
+
+    for (u32 cb = ls - ls % PC_CHUNK; cb < le; cb += PC_CHUNK) {
+        const u32 ce = cb + PC_CHUNK;
+#pragma unroll
+        for (int r = 0; r < PC_ROUNDS; r++) {
+            if (!nsel[r] || first[r] >= ce || first[r] + nsel[r] <= cb) continue;
+            const u32 tag = (u32)(r * PC_THREADS + threadIdx.x) << 6;
+            if (k >= 64) {                                     // one selected bit at most: jump to it
+                sel[first[r] - cb] = tag | pc_select(w[r], skip[r]);
+            } else {
+                u64 ww = w[r];
+                u32 j = 0, next = skip[r], row = first[r];
+                while (ww) {
+                    const u32 bit = (u32)__ffsll((long long)ww) - 1;
+                    ww &= ww - 1;
+                    if (j == next) {
+                        if (row >= cb && row < ce) sel[row - cb] = tag | bit;
+                        row++;
+                        next += (u32)k;
+                    }
+                    j++;
+                }
+            }
+        }
+        __syncthreads();
+        // the rows of the chunk are one run of doubles: lane j stores double j (row j / 3, column j % 3)
+        const u32 r_lo = cb > ls ? cb : ls, r_hi = ce < le ? ce : le;
+        double *dst = out + 3 * ((int64_t)(R0 - W0) + (int64_t)r_lo);   // >= out: R0 + r_lo >= W0 by the choice of ls
+        const u32 nd = 3 * (r_hi - r_lo);
+        for (u32 j = threadIdx.x; j < nd; j += PC_THREADS) {
+            const u32 row = j / 3, col = j - 3 * row;
+            const u32 v = sel[r_lo - cb + row], wi = v >> 6;
+            double val;
+            if (col == 0) val = zt[wi];
+            else if (col == 1) val = (double)yt[wi] * mm_y;
+            else val = (double)(xt[wi] + (v & 63u)) * mm_x;
+            dst[j] = val;
+        }
+        __syncthreads();
+    }
+}
+
+TOMO_API int tomo_point_cloud_rows(const uint64_t *bits, int nz, int ny, int nx, const uint64_t *blk_off, int64_t k,
+                                   const double *z_mm, double mm_y, double mm_x, int64_t row_first, int64_t cap_rows,
+                                   double *out, void *stream)
+{
+    if (!bits || !blk_off || !z_mm || nz <= 0 || ny <= 0 || nx <= 0 || k < 1 || row_first < 0 || cap_rows < 0) return TOMO_E_ARG;
+    if (cap_rows == 0) return TOMO_OK;
+    if (!out) return TOMO_E_ARG;
+    const int wx = (int)tomo_words_per_row(nx);
+    const int64_t nwords = (int64_t)nz * ny * wx;
+    if (nwords >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
+    const int64_t blocks = ceil_div64(nwords, PC_TILE);
+    hipLaunchKernelGGL(pc_rows_kernel, dim3((unsigned)blocks), dim3(PC_THREADS), 0, (hipStream_t)stream, (const u64 *)bits,
+                       (u32)nwords, ny, wx, (const u64 *)blk_off, (u64)k, z_mm, mm_y, mm_x, row_first, cap_rows, out);
+    return tomo_status();
+}

@@ -152,6 +152,85 @@ def bounding_box(vol: BitVolume):
     return None if b[1] < 0 else tuple(b)
 
 
+# ----------------------------------------------------------------------------- point cloud
+def point_cloud_z_table(slice_depths, nz, z0=0) -> np.ndarray:
+    """The z column of generate_point_cloud (voxel_processor.py:110-119) for slices z0 .. z0 + nz - 1 -> float64 (nz,), on the
+    host: the centre of slice z while z < len(slice_depths), the total depth beyond.  The kernel only looks it up."""
+    d = np.asarray(slice_depths, dtype=np.float64)
+    cum = np.cumsum(np.concatenate([[0], d]))
+    z = np.arange(int(z0), int(z0) + int(nz))
+    if len(d):
+        zc = np.minimum(z, len(d) - 1)
+        return np.where(z < len(d), cum[zc] + d[zc] / 2, cum[-1])
+    return np.full(len(z), cum[-1])
+
+
+def point_cloud_step(subsample_factor) -> int:
+    """k of the rank rule: voxel_processor.py:104-105 subsamples only when the factor is > 1."""
+    return int(subsample_factor) if subsample_factor > 1 else 1
+
+
+def point_cloud_rows(n, k, rank_base=0):
+    """The rows of n set voxels whose ranks start at rank_base, every k-th rank kept: (row_first, rows) -- this run is rows
+    [row_first, row_first + rows) of the array of the whole stack.  Python ints."""
+    n, k, rank_base = int(n), int(k), int(rank_base)
+    row_first = -(-rank_base // k)
+    return row_first, -(-(rank_base + n) // k) - row_first
+
+
+class PointCloudPlan:
+    """The counting half of the point cloud of one BitVolume: tile offsets on the device and, after ONE host read, the
+    number of set voxels.  rows(a, b) then writes any window of the run, so a cloud larger than device memory can be
+    fetched piece by piece.  z_mm: point_cloud_z_table of the volume's slices."""
+
+    def __init__(self, vol: BitVolume, z_mm, mm_per_pixel_y, mm_per_pixel_x, k=1, rank_base=0):
+        nz, ny, nx = vol.shape
+        L = _lib.lib()
+        self.k, self.rank_base = int(k), int(rank_base)
+        if self.k < 1 or self.rank_base < 0:
+            raise ValueError("k must be >= 1 and rank_base >= 0")
+        z_mm = np.ascontiguousarray(z_mm, dtype=np.float64)
+        if z_mm.shape != (nz,):
+            raise ValueError("z_mm must hold one float64 per slice")
+        self.vol, self.bits = vol, vol.bits.contiguous()
+        self.z_mm = torch.from_numpy(z_mm).to(vol.device)
+        self.mm_y, self.mm_x = float(mm_per_pixel_y), float(mm_per_pixel_x)
+        blocks = int(L.tomo_point_cloud_blocks(nz, ny, nx))
+        self.blk_off = torch.empty(blocks + 1, dtype=torch.int64, device=vol.device)
+        _lib.check(L.tomo_point_cloud_count(_p(self.bits), nz, ny, nx, self.rank_base, _p(self.blk_off), _stream()),
+                   "tomo_point_cloud_count")
+        self.n = int(self.blk_off[-1].item()) - self.rank_base           # the one host read: it sizes the output
+        self.row_first, self.n_rows = point_cloud_rows(self.n, self.k, self.rank_base)
+
+    def rows(self, a=0, b=None, out=None) -> torch.Tensor:
+        """Rows [a, b) of this run (clipped to it) -> (b - a, 3) float64 device tensor."""
+        a = max(0, int(a))
+        b = self.n_rows if b is None else min(self.n_rows, int(b))
+        cap = max(0, b - a)
+        if out is None:
+            out = torch.empty((cap, 3), dtype=torch.float64, device=self.vol.device)
+        elif tuple(out.shape) != (cap, 3) or out.dtype != torch.float64 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float64 (rows, 3) tensor")
+        if cap:
+            nz, ny, nx = self.vol.shape
+            _lib.check(_lib.lib().tomo_point_cloud_rows(_p(self.bits), nz, ny, nx, _p(self.blk_off), self.k, _p(self.z_mm),
+                                                        self.mm_y, self.mm_x, self.row_first + a, cap, _p(out), _stream()),
+                       "tomo_point_cloud_rows")
+        return out
+
+
+def point_cloud(vol: BitVolume, slice_depths, mm_per_pixel_x, mm_per_pixel_y, subsample_factor=1, rank_base=0, z0=0,
+                window=None) -> torch.Tensor:
+    """generate_point_cloud (voxel_processor.py:99-127) of a resident volume -> (rows, 3) float64 device tensor, byte for byte
+    the reference's rows (z_mm, y * mm_per_pixel_y, x * mm_per_pixel_x).  rank_base / z0: the set voxels and the slices in
+    front of this volume when it is one Z-slab of a stack -- the result is then this slab's run of the stack's array.
+    window = (a, b): rows [a, b) of the run only."""
+    nz = vol.shape[0]
+    plan = PointCloudPlan(vol, point_cloud_z_table(slice_depths, nz, z0), mm_per_pixel_y, mm_per_pixel_x,
+                          point_cloud_step(subsample_factor), rank_base)
+    return plan.rows() if window is None else plan.rows(window[0], window[1])
+
+
 def pack_closed(mask: torch.Tensor) -> BitVolume:
     """np.stack + _close_volume_ends (voxel_processor.py:46, :56-77) from a device uint8 / bool (nz, ny, nx) mask stack in ONE
     pass over the mask where the layout allows it (nz >= 3, nx % 16 == 0): pack + fill the end slices, then the fused

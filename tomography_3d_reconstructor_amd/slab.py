@@ -498,6 +498,11 @@ class HipEngine:
     def bbox(self, vol):
         return pipeline.bounding_box(vol)
 
+    def point_cloud(self, vol, z_mm, mm_y, mm_x, k, rank_base):
+        """The rows of this volume's set voxels whose ranks, counted from rank_base, are multiples of k (voxel_processor.py:99-127;
+        z_mm: the z column per owned slice) -> (rows, 3) float64 on the device."""
+        return pipeline.PointCloudPlan(vol, z_mm, mm_y, mm_x, k, rank_base).rows()
+
 
 # ----------------------------------------------------------------------------- the job
 def slab_range(gz, rank, world):
@@ -952,6 +957,19 @@ class SlabJob:
         if not torch.is_tensor(c):
             c = torch.as_tensor(np.asarray(c, dtype=np.int64))
         return self._gather_per_slice(c)
+
+    def point_cloud(self, slice_depths, mm_per_pixel_x, mm_per_pixel_y, subsample_factor=1, which="smoothed"):
+        """== VoxelProcessor.generate_point_cloud(whole volume, ...) (voxel_processor.py:99-127), rank by rank: (rows, row_first,
+        total_rows), rows = this rank's (r, 3) float64 run on the engine's device, rows [row_first, row_first + r) of the
+        total_rows of the whole stack -- concatenated in rank order the runs are that array, byte for byte.  Collective: one
+        slice_counts(which) tells every rank how many set voxels lie below its slab; no voxel and no row travels."""
+        vol = self._volume(which)
+        counts = self.slice_counts(which)
+        k = pipeline.point_cloud_step(subsample_factor)
+        rank_base = int(counts[: self.z0].sum())
+        z_mm = pipeline.point_cloud_z_table(slice_depths, self.z1 - self.z0, self.z0)
+        rows = self.eng.point_cloud(vol, z_mm, float(mm_per_pixel_y), float(mm_per_pixel_x), k, rank_base)
+        return rows, pipeline.point_cloud_rows(0, k, rank_base)[0], pipeline.point_cloud_rows(int(counts.sum()), k)[1]
 
     def _gather_per_slice(self, mine):
         """One int64 per owned slice on every rank -> the (gz,) array of the whole stack on every rank (one all-gather)."""

@@ -55,7 +55,8 @@ def upload_volume(voxel_data):
     return pipeline.pack(t)
 
 
-_NP_OF = {torch.bool: np.bool_, torch.uint8: np.uint8, torch.float32: np.float32, torch.int64: np.int64, torch.int32: np.int32}
+_NP_OF = {torch.bool: np.bool_, torch.uint8: np.uint8, torch.float32: np.float32, torch.float64: np.float64, torch.int64: np.int64,
+          torch.int32: np.int32}
 
 
 BIG = 1 << 28        # bytes from which a transfer goes straight from / into ordinary (pageable) memory: ROCm page-locks a large
@@ -244,6 +245,59 @@ def _common_base(mask_images):
     return base
 
 
+POINT_CLOUD_WINDOW_BYTES = 1 << 30      # device memory one download window of generate_point_cloud holds at most
+
+
+def _point_cloud_host(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, subsample_factor=1):
+    """voxel_processor.py:99-127 in NumPy."""
+    z, y, x = np.where(voxel_data)
+    if subsample_factor > 1:
+        idx = np.arange(0, len(z), subsample_factor)
+        z, y, x = z[idx], y[idx], x[idx]
+    d = np.asarray(slice_depths, dtype=np.float64)
+    cum = np.cumsum(np.concatenate([[0], d]))
+    if len(d):
+        zc = np.minimum(z, len(d) - 1)
+        z_mm = np.where(z < len(d), cum[zc] + d[zc] / 2, cum[-1])
+    else:
+        z_mm = np.full(len(z), cum[-1])
+    return np.column_stack([z_mm, y * mm_per_pixel_y, x * mm_per_pixel_x])
+
+
+def _plain_scale(v, extent):
+    """A scale the kernel's `(double)index * (double)scale` reproduces for indices below `extent`: NumPy multiplies the int64
+    indices by a float scale in float64, and by an int scale in int64 -- the same value while the product stays below 2^53."""
+    if isinstance(v, (float, np.float64, np.float32)):
+        return True
+    return isinstance(v, (int, np.integer)) and abs(int(v)) * extent < 2 ** 53
+
+
+def _point_cloud_on_device(voxel_data, mm_per_pixel_x, mm_per_pixel_y, subsample_factor):
+    if not (isinstance(voxel_data, np.ndarray) and voxel_data.ndim == 3 and voxel_data.dtype == np.bool_ and voxel_data.size > 0):
+        return False
+    nz, ny, nx = voxel_data.shape
+    return (isinstance(subsample_factor, (int, np.integer)) and _plain_scale(mm_per_pixel_x, nx) and _plain_scale(mm_per_pixel_y, ny)
+            and nz * ny * ((nx + 63) // 64) < 2 ** 31                       # the kernels index words with 32 bits (TOMO_E_SIZE beyond)
+            and torch.cuda.is_available() and os.path.exists(pipeline._lib.SO_PATH))
+
+
+def _point_cloud_device(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, subsample_factor):
+    vol = to_device_volume(voxel_data)
+    plan = pipeline.PointCloudPlan(vol, pipeline.point_cloud_z_table(slice_depths, vol.shape[0]), mm_per_pixel_y, mm_per_pixel_x,
+                                   pipeline.point_cloud_step(subsample_factor))
+    rows = plan.n_rows
+    step = max(1, POINT_CLOUD_WINDOW_BYTES // 24)
+    if rows == 0:
+        return np.empty((0, 3), dtype=np.float64)
+    if rows <= step:
+        return to_host_array(plan.rows())
+    out = _hostbuf.take((rows, 3), np.float64)
+    for a in range(0, rows, step):
+        b = min(rows, a + step)
+        torch.from_numpy(out[a:b]).copy_(plan.rows(a, b))        # returns when the bytes are there: one window resident at a time
+    return out
+
+
 class VoxelProcessor:
     """Handles voxel data creation and processing operations (reference: voxel_processor.py:27)."""
 
@@ -319,19 +373,17 @@ class VoxelProcessor:
 
     def generate_point_cloud(self, voxel_data: np.ndarray, mm_per_pixel_x: float, mm_per_pixel_y: float,
                              slice_depths: np.ndarray, subsample_factor: int = 1) -> np.ndarray:
-        """voxel_processor.py:99-127 (fallback path of the orchestrator; host NumPy, not on the hot path)."""
-        z, y, x = np.where(voxel_data)
-        if subsample_factor > 1:
-            idx = np.arange(0, len(z), subsample_factor)
-            z, y, x = z[idx], y[idx], x[idx]
-        d = np.asarray(slice_depths, dtype=np.float64)
-        cum = np.cumsum(np.concatenate([[0], d]))
-        if len(d):
-            zc = np.minimum(z, len(d) - 1)
-            z_mm = np.where(z < len(d), cum[zc] + d[zc] / 2, cum[-1])
-        else:
-            z_mm = np.full(len(z), cum[-1])
-        return np.column_stack([z_mm, y * mm_per_pixel_y, x * mm_per_pixel_x])
+        """voxel_processor.py:99-127 (the orchestrator's fallback when there is no surface -- on the largest stacks).  A 3-D
+        bool array with a GPU in sight is ranked and selected on the device, from the bit-packed copy (the cached one if this
+        package handed the array out), and the float64 rows come down in windows of POINT_CLOUD_WINDOW_BYTES at most; anything
+        else -- no GPU, another dtype, a non-integer factor, 2^31 words or more, no device memory -- is the reference's NumPy,
+        unchanged.  Any other failure of the device path (a failed launch, a TomoError) raises: it is never hidden behind NumPy."""
+        if _point_cloud_on_device(voxel_data, mm_per_pixel_x, mm_per_pixel_y, subsample_factor):
+            try:
+                return _point_cloud_device(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, subsample_factor)
+            except torch.cuda.OutOfMemoryError:
+                pass
+        return _point_cloud_host(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, subsample_factor)
 
     def calculate_slice_depths(self, total_depth_mm: float) -> np.ndarray:
         """voxel_processor.py:129-164."""
