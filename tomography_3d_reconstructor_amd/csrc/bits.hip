@@ -967,9 +967,12 @@ TOMO_API int tomo_pack_close_ends(const uint8_t *mask, uint64_t *bits, int nz, i
     const int wx = (int)tomo_words_per_row(nx);
     if (wx > FH_THREADS) return TOMO_E_SIZE;
     const int groups = (wx + 15) / 16;
+    // the pack kernel clears the band kernel's 16 control words on its way -- unless scratch (ny * wx + 8 words) is shorter than
+    // that: such a slice never takes the band kernel (fill_holes_launch), and the words behind scratch are not ours
+    u64 *ctrl = (int64_t)ny * wx + 8 >= 16 ? (u64 *)scratch : nullptr;
     hipLaunchKernelGGL(pack16_ends_kernel, dim3((unsigned)ceil_div64(ceil_div64((int64_t)ny * groups, PACK_U), 4), 2), dim3(256), 0,
                        (hipStream_t)stream, mask, (u64 *)bits, (int64_t)ny, nx, wx, groups, (int64_t)(nz - 1) * ny * nx,
-                       (int64_t)(nz - 1) * ny * wx, (u64 *)scratch);
+                       (int64_t)(nz - 1) * ny * wx, ctrl);
     int rc = fill_holes_launch((u64 *)bits, (u64 *)bits + (int64_t)(nz - 1) * ny * wx, ny, nx, wx, (u64 *)scratch, (hipStream_t)stream,
                                true);
     if (rc) return rc;
