@@ -160,6 +160,35 @@ int64_t tomo_point_cloud_blocks(int nz, int ny, int nx);
 int tomo_point_cloud_count(const uint64_t *bits, int nz, int ny, int nx, uint64_t rank_base, uint64_t *blk_off, void *stream);
 int tomo_point_cloud_rows(const uint64_t *bits, int nz, int ny, int nx, const uint64_t *blk_off, int64_t k, const double *z_mm,
                           double mm_y, double mm_x, int64_t row_first, int64_t cap_rows, double *out, void *stream);
+/* Connected components of the resident bits (no counterpart in the reference; the semantics are scipy.ndimage.label's with
+ * generate_binary_structure(3, 1) -- connectivity 6, the 3-D cross of voxel_processor.py:88,91 -- or (3, 3) -- connectivity 26;
+ * anything else is TOMO_E_ARG).  The unit is the X-RUN, a maximal run of set bits in a row; run ids ascend in raster order,
+ * the root of a component is its smallest run id, and components are numbered 1..n in the raster order of their first voxel:
+ * the output is unique, whatever the schedule.  Working memory scales with the rows and the runs, never with the voxels.
+ *   tomo_cc_scan_blocks  uint64 words of the scratch `blk` for a table of n entries
+ *   tomo_cc_count_runs   row_off uint32[nz * ny + 1] = runs in front of every row (exclusive scan; the last entry = all runs);
+ *                        zeroes tot (device uint64[8]) and sets tot[0] = runs, bit 0 of tot[2] from 2^31 runs on.
+ *                        blk: tomo_cc_scan_blocks(nz * ny + 1) words
+ *   tomo_cc_label_runs   parent uint32[cap_runs] = the root of every run, rank uint32[cap_runs] = at a root, the number of roots
+ *                        in front of it: the label of run r is rank[parent[r]] + 1; tot[1] = n; sizes int64[cap_runs], of which
+ *                        the first n = voxels of component 1..n (integer atomics: the same on every run).
+ *                        blk: tomo_cc_scan_blocks(cap_runs) words.  The caller reads tot[0] once and passes cap_runs >= it; the
+ *                        kernels take the count from tot and touch nothing (bit 1 of tot[2]) if it exceeds cap_runs; a run id
+ *                        outside the tables (the bits changed since tomo_cc_count_runs) sets bit 2 and is skipped
+ *   tomo_cc_expand       labels int32 (nz, ny, nx): scipy's array
+ *   tomo_cc_filter       out (!= bits) = the bits of the components with sizes >= min_voxels; largest: of those only the largest
+ *                        one, the lowest label among equals (its label goes to tot[3], 0: none).  Tail bits of out are zero.
+ * TOMO_E_SIZE from 2^31 words or cap_runs on. */
+int64_t tomo_cc_scan_blocks(int64_t n);
+int tomo_cc_count_runs(const uint64_t *bits, int nz, int ny, int nx, uint32_t *row_off, uint64_t *blk, unsigned long long *tot,
+                       void *stream);
+int tomo_cc_label_runs(const uint64_t *bits, int nz, int ny, int nx, int connectivity, const uint32_t *row_off, int64_t cap_runs,
+                       uint32_t *parent, uint32_t *rank, int64_t *sizes, uint64_t *blk, unsigned long long *tot, void *stream);
+int tomo_cc_expand(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
+                   const uint32_t *rank, unsigned long long *tot, int32_t *labels, void *stream);
+int tomo_cc_filter(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
+                   const uint32_t *rank, const int64_t *sizes, unsigned long long *tot, int64_t min_voxels, int largest,
+                   uint64_t *out, void *stream);
 /* image_loader.py:108 (`img >= threshold`) fused with the packing: grey = uint8 (nz, ny, nx) on the device. */
 int tomo_pack_threshold(const uint8_t *grey, uint64_t *bits, int nz, int ny, int nx, int threshold, void *stream);
 /* obj_exporter.py:17-38, byte for byte ("v %.6f %.6f %.6f" per vertex, "f a+1 b+1 c+1" per face), HOST arrays:

@@ -50,6 +50,11 @@ SIGNATURES = {
     "tomo_point_cloud_blocks": (_c_i64, [_c_i, _c_i, _c_i]),
     "tomo_point_cloud_count": (_c_i, [_c_p, _c_i, _c_i, _c_i, ctypes.c_uint64, _c_p, _c_p]),
     "tomo_point_cloud_rows": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_d, _c_d, _c_i64, _c_i64, _c_p, _c_p]),
+    "tomo_cc_scan_blocks": (_c_i64, [_c_i64]),
+    "tomo_cc_count_runs": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p]),
+    "tomo_cc_label_runs": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
+    "tomo_cc_expand": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p]),
+    "tomo_cc_filter": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i, _c_p, _c_p]),
     "tomo_pack_threshold": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_p]),
     "tomo_obj_write": (_c_i, [ctypes.c_char_p, _c_p, _c_i, _c_i64, _c_p, _c_i64, _c_i]),
     "tomo_obj_block_format": (_c_i, [_c_i, _c_p, _c_i64, _c_i, ctypes.POINTER(_c_p), ctypes.POINTER(_c_i64)]),

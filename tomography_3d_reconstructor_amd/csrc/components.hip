@@ -1,0 +1,587 @@
+// components.hip -- connected-component labelling, component sizes and island removal on the resident bit volume
+// (scipy.ndimage.label with generate_binary_structure(3, 1) or (3, 3); no counterpart in the reference, whose only defence
+// against debris is the opening of voxel_processor.py:88).
+//
+// The unit of work is the X-RUN, a maximal run of set bits in a row, never the voxel.  Run ids are handed out in raster order
+// (exclusive scan of the runs per row), every run starts as its own tree (linked to its first neighbour in the row above, which
+// needs no atomic), overlapping runs of neighbouring rows are united by hooking the larger root under the smaller one with
+// atomicMin, and the trees are flattened in a launch of their own.  A root is the smallest run id of its component = the
+// component's first run in raster order, so numbering the roots with a scan IS scipy's numbering, whatever the schedule did.
+// Sizes are integer atomics per component.  Nothing here holds a per-voxel array except tomo_cc_expand's output.
+//
+// Termination: parent[r] <= r always and a parent only ever decreases (atomicMin, or a store of a smaller ancestor); cc_find
+// follows strictly decreasing ids; every turn of cc_union's loop that does not end it lowers a + b.  No kernel waits for
+// another workgroup: the phases are separate launches.
+//
+// tot (device uint64[8]): [0] runs  [1] components  [2] flags (1: 2^31 runs or more, 2: more runs than the caller's buffers
+// hold, 4: a run id outside the tables -- the bits changed between the calls)  [3] label tomo_cc_filter(largest) kept (0: none).
+#include "tomo_common.h"
+
+#define CC_THREADS 256
+#define CC_SCAN_TILE 1024            // entries per workgroup of the scan kernels (4 per thread)
+#define CC_F_MANY 1ull
+#define CC_F_CAP 2ull
+#define CC_F_RANGE 4ull
+
+TOMO_API int64_t tomo_cc_scan_blocks(int64_t n)
+{
+    if (n <= 0) return TOMO_E_ARG;
+    return ceil_div64(n, CC_SCAN_TILE) + 1;
+}
+
+// ---------------------------------------------------------------------------------------------- rows and runs
+__device__ static inline u64 cc_tail_mask(int nx, int wx, int w)
+{
+    const int r = nx - 64 * (wx - 1);                      // bits of the last word, 1 .. 64
+    return (w == wx - 1 && r < 64) ? ((1ull << r) - 1) : ~0ull;
+}
+
+// word w of a row, bits at x >= nx cleared whatever the buffer holds there
+__device__ static inline u64 cc_word(const u64 *__restrict__ row, int nx, int wx, int w)
+{
+    return row[w] & cc_tail_mask(nx, wx, w);
+}
+
+// bits of word w at which a run starts
+__device__ static inline u64 cc_starts(const u64 *__restrict__ row, int nx, int wx, int w, u64 cur)
+{
+    const u64 carry = w > 0 ? row[w - 1] >> 63 : 0ull;    // bit 63 of a word before the last is never a tail bit
+    return cur & ~((cur << 1) | carry);
+}
+
+// the runs of one row, in ascending x: [s, e)
+struct CcRuns {
+    const u64 *row;
+    int nx, wx, pos;
+    int s, e;
+    bool valid;
+};
+
+__device__ static inline void cc_runs_next(CcRuns &it)
+{
+    const int end = 64 * it.wx;
+    it.valid = false;
+    if (it.pos >= end) return;
+    int w = it.pos >> 6;
+    u64 m = cc_word(it.row, it.nx, it.wx, w) & (~0ull << (it.pos & 63));
+    while (m == 0) {                                        // w only grows: at most wx turns
+        if (++w >= it.wx) { it.pos = end; return; }
+        m = cc_word(it.row, it.nx, it.wx, w);
+    }
+    it.s = 64 * w + __ffsll((long long)m) - 1;
+    w = it.s >> 6;
+    m = ~cc_word(it.row, it.nx, it.wx, w) & (~0ull << (it.s & 63));
+    int e = end;
+    while (true) {
+        if (m != 0) { e = 64 * w + __ffsll((long long)m) - 1; break; }
+        if (++w >= it.wx) break;
+        m = ~cc_word(it.row, it.nx, it.wx, w);
+    }
+    it.e = e;
+    it.pos = e;
+    it.valid = true;
+}
+
+__device__ static inline CcRuns cc_runs_begin(const u64 *__restrict__ bits, int64_t row, int nx, int wx)
+{
+    CcRuns it;
+    it.row = bits + row * wx;
+    it.nx = nx;
+    it.wx = wx;
+    it.pos = 0;
+    it.s = it.e = 0;
+    cc_runs_next(it);
+    return it;
+}
+
+// row_off[row] = runs of the row (row_off[nrows] = 0): the input of the scan
+__global__ __launch_bounds__(CC_THREADS) void cc_row_count_kernel(const u64 *__restrict__ bits, int64_t nrows, int nx, int wx,
+                                                                  u32 *__restrict__ row_off)
+{
+    const int64_t row = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    if (row > nrows) return;
+    u32 c = 0;
+    if (row < nrows) {
+        const u64 *r = bits + row * wx;
+        for (int w = 0; w < wx; w++) c += (u32)__popcll(cc_starts(r, nx, wx, w, cc_word(r, nx, wx, w)));
+    }
+    row_off[row] = c;
+}
+
+// ---------------------------------------------------------------------------------------------- exclusive scan of u32, in place
+// n comes from the host (n_dev == NULL) or from device memory, clipped to the capacity the grid was sized for
+__device__ static inline int64_t cc_count(const u64 *n_dev, int64_t cap)
+{
+    if (!n_dev) return cap;
+    const u64 n = *n_dev;
+    return n > (u64)cap ? 0 : (int64_t)n;                  // too many for the buffers: nothing is touched (flag CC_F_CAP)
+}
+
+__global__ __launch_bounds__(CC_THREADS) void cc_blocksum_kernel(const u32 *__restrict__ v, const u64 *n_dev, int64_t cap,
+                                                                 u64 *__restrict__ blk)
+{
+    __shared__ u32 wsum[CC_THREADS / 64];
+    const int64_t n = cc_count(n_dev, cap);
+    const int64_t i0 = (int64_t)blockIdx.x * CC_SCAN_TILE + 4 * threadIdx.x;
+    u32 acc = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) acc += i0 + j < n ? v[i0 + j] : 0u;
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) blk[blockIdx.x] = (u64)wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// one workgroup: blk[i] = sum of blk[0 .. i) for i < nblk, *total = the sum of all; 1024 entries per step with a running carry
+__global__ __launch_bounds__(1024) void cc_scan1_kernel(u64 *__restrict__ blk, int64_t nblk, u64 *__restrict__ total, u64 *flags)
+{
+    __shared__ u64 wsum[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    u64 carry = 0;
+    for (int64_t i0 = 0; i0 < nblk; i0 += 1024) {
+        const int64_t i = i0 + threadIdx.x;
+        const u64 v = i < nblk ? blk[i] : 0;
+        u64 inc = v;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const u64 o = __shfl_up(inc, d, 64);
+            if (lane >= d) inc += o;
+        }
+        if (lane == 63) wsum[wave] = inc;
+        __syncthreads();
+        u64 before = 0, sum = 0;
+#pragma unroll
+        for (int w = 0; w < 16; w++) {
+            const u64 x = wsum[w];
+            before += w < wave ? x : 0;
+            sum += x;
+        }
+        if (i < nblk) blk[i] = carry + before + inc - v;
+        carry += sum;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        *total = carry;
+        if (flags && carry >= (1ull << 31)) *flags |= CC_F_MANY;
+    }
+}
+
+__global__ __launch_bounds__(CC_THREADS) void cc_apply_kernel(u32 *__restrict__ v, const u64 *n_dev, int64_t cap,
+                                                              const u64 *__restrict__ blk)
+{
+    __shared__ u32 wsum[CC_THREADS / 64];
+    const int64_t n = cc_count(n_dev, cap);
+    const int64_t i0 = (int64_t)blockIdx.x * CC_SCAN_TILE + 4 * threadIdx.x;
+    u32 x[4];
+    u32 acc = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        x[j] = i0 + j < n ? v[i0 + j] : 0u;
+        acc += x[j];
+    }
+    const u32 inc = wave_inclusive_scan(acc);
+    if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = inc;
+    __syncthreads();
+    u32 before = 0;
+    for (int w = 0; w < (int)(threadIdx.x >> 6); w++) before += wsum[w];
+    u32 run = (u32)blk[blockIdx.x] + before + inc - acc;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        if (i0 + j < n) v[i0 + j] = run;
+        run += x[j];
+    }
+}
+
+static void cc_scan(u32 *v, const u64 *n_dev, int64_t cap, u64 *blk, u64 *total, u64 *flags, hipStream_t st)
+{
+    const int64_t nblk = ceil_div64(cap, CC_SCAN_TILE);
+    hipLaunchKernelGGL(cc_blocksum_kernel, dim3((unsigned)nblk), dim3(CC_THREADS), 0, st, (const u32 *)v, n_dev, cap, blk);
+    hipLaunchKernelGGL(cc_scan1_kernel, dim3(1), dim3(1024), 0, st, blk, nblk, total, flags);
+    hipLaunchKernelGGL(cc_apply_kernel, dim3((unsigned)nblk), dim3(CC_THREADS), 0, st, v, n_dev, cap, (const u64 *)blk);
+}
+
+static int cc_geometry(const void *bits, int nz, int ny, int nx, int64_t *nrows, int *wx)
+{
+    if (!bits || nz <= 0 || ny <= 0 || nx <= 0) return TOMO_E_ARG;
+    *wx = (int)tomo_words_per_row(nx);
+    *nrows = (int64_t)nz * ny;
+    if (*nrows * *wx >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
+    return TOMO_OK;
+}
+
+TOMO_API int tomo_cc_count_runs(const uint64_t *bits, int nz, int ny, int nx, uint32_t *row_off, uint64_t *blk,
+                                unsigned long long *tot, void *stream)
+{
+    int64_t nrows;
+    int wx;
+    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
+    if (g != TOMO_OK) return g;
+    if (!row_off || !blk || !tot) return TOMO_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(tot, 0, 8 * sizeof(u64), st) != hipSuccess) return TOMO_E_LAUNCH;
+    hipLaunchKernelGGL(cc_row_count_kernel, dim3((unsigned)ceil_div64(nrows + 1, CC_THREADS)), dim3(CC_THREADS), 0, st,
+                       (const u64 *)bits, nrows, nx, wx, (u32 *)row_off);
+    cc_scan((u32 *)row_off, NULL, nrows + 1, (u64 *)blk, (u64 *)tot, (u64 *)tot + 2, st);
+    return tomo_status();
+}
+
+// ---------------------------------------------------------------------------------------------- union-find over runs
+__device__ static inline u32 cc_load(const u32 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// the root above x as far as this thread can see it (ids strictly decrease along the way: at most x steps)
+__device__ static inline u32 cc_find(const u32 *parent, u32 x)
+{
+    u32 p = cc_load(parent + x);
+    while (p < x) {
+        x = p;
+        p = cc_load(parent + x);
+    }
+    return x;
+}
+
+// ... and every run on the way is pointed at it (atomicMin: a parent never rises)
+__device__ static inline u32 cc_find_compress(u32 *parent, u32 x)
+{
+    const u32 r = cc_find(parent, x);
+    while (x > r) {
+        const u32 old = atomicMin(parent + x, r);
+        if (old >= x) break;
+        x = old;
+    }
+    return r;
+}
+
+__device__ static inline void cc_union(u32 *parent, u32 a, u32 b)
+{
+    while (true) {
+        a = cc_find_compress(parent, a);
+        b = cc_find_compress(parent, b);
+        if (a == b) return;
+        if (a < b) { const u32 t = a; a = b; b = t; }       // a > b: hook a under b
+        const u32 old = atomicMin(parent + a, b);
+        if (old >= a) return;                               // a was a root: hooked (old == a; > a cannot be)
+        a = old;                                            // somebody hooked a first, under old < a: unite old and b
+    }
+}
+
+// 0-based component of a run once the trees are flat and the roots are numbered (a parent above its run cannot be: the run
+// stands for itself then, and nothing is read outside the tables)
+__device__ static inline u32 cc_component(const u32 *__restrict__ parent, const u32 *__restrict__ rank, u32 run)
+{
+    const u32 p = parent[run];
+    return rank[p < run ? p : run];
+}
+
+// The runs of `row` against the runs of the neighbour row `nb` (widen = 1: diagonal neighbours count, connectivity 26).
+// mode 0: parent[a] = the FIRST run of nb that touches a (or a itself) -- plain stores, every run is written exactly once, by
+//         this thread; only for the row above in the same slice;  mode 1: unite with every touching run but the first (what
+//         mode 0 left to do);  mode 2: unite with every touching run.
+template <int MODE>
+__device__ static inline void cc_pair_rows(const u64 *__restrict__ bits, int nx, int wx, int64_t row, int64_t nb,
+                                           const u32 *__restrict__ row_off, u32 nruns, int widen, u32 *parent, u64 *flags)
+{
+    CcRuns a = cc_runs_begin(bits, row, nx, wx);
+    u32 ia = row_off[row], ib = 0;
+    CcRuns b;
+    b.valid = false;
+    if (nb >= 0) {
+        b = cc_runs_begin(bits, nb, nx, wx);
+        ib = row_off[nb];
+    }
+    bool linked = false;
+    while (a.valid) {                                       // every turn moves a or b on: at most runs(a) + runs(b) turns
+        if (ia >= nruns || (b.valid && ib >= nruns)) {
+            atomicOr((unsigned long long *)flags, CC_F_RANGE);
+            return;
+        }
+        bool next_a = true;
+        if (b.valid) {
+            if (a.s < b.e + widen && b.s < a.e + widen) {
+                if (MODE == 0) {
+                    if (!linked) parent[ia] = ib;
+                } else if (MODE == 2 || linked) {
+                    cc_union(parent, ia, ib);
+                }
+                linked = true;
+            }
+            next_a = a.e <= b.e;
+        }
+        if (next_a) {
+            if (MODE == 0 && !linked) parent[ia] = ia;
+            cc_runs_next(a);
+            ia++;
+            linked = false;
+        } else {
+            cc_runs_next(b);
+            ib++;
+        }
+    }
+}
+
+__global__ __launch_bounds__(CC_THREADS) void cc_init_kernel(const u64 *__restrict__ bits, int64_t nrows, int ny, int nx, int wx,
+                                                             const u32 *__restrict__ row_off, const u64 *__restrict__ tot, int64_t cap,
+                                                             int widen, u32 *__restrict__ parent, u64 *flags)
+{
+    const int64_t row = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    if (row >= nrows) return;
+    const u32 nruns = (u32)cc_count(tot, cap);
+    if (row == 0 && tot[0] > (u64)cap) atomicOr((unsigned long long *)flags, CC_F_CAP);
+    const int y = (int)(row % ny);
+    cc_pair_rows<0>(bits, nx, wx, row, y > 0 ? row - 1 : -1, row_off, nruns, widen, parent, flags);
+}
+
+__global__ __launch_bounds__(CC_THREADS) void cc_union_kernel(const u64 *__restrict__ bits, int64_t nrows, int ny, int nx, int wx,
+                                                              const u32 *__restrict__ row_off, const u64 *__restrict__ tot, int64_t cap,
+                                                              int widen, u32 *parent, u64 *flags)
+{
+    const int64_t row = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    if (row >= nrows) return;
+    const u32 nruns = (u32)cc_count(tot, cap);
+    const int y = (int)(row % ny);
+    const bool below = row >= ny;                           // there is a slice z - 1
+    if (y > 0) cc_pair_rows<1>(bits, nx, wx, row, row - 1, row_off, nruns, widen, parent, flags);
+    if (below) {
+        cc_pair_rows<2>(bits, nx, wx, row, row - ny, row_off, nruns, widen, parent, flags);
+        if (widen) {
+            if (y > 0) cc_pair_rows<2>(bits, nx, wx, row, row - ny - 1, row_off, nruns, widen, parent, flags);
+            if (y + 1 < ny) cc_pair_rows<2>(bits, nx, wx, row, row - ny + 1, row_off, nruns, widen, parent, flags);
+        }
+    }
+}
+
+// parent[r] = its root.  mark: rank[r] = 1 for a root, 0 otherwise (the input of the numbering scan)
+__global__ __launch_bounds__(CC_THREADS) void cc_flatten_kernel(u32 *parent, const u64 *__restrict__ tot, int64_t cap, u32 *__restrict__ rank)
+{
+    const int64_t r = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    if (r >= cc_count(tot, cap)) return;
+    const u32 root = cc_find(parent, (u32)r);
+    if (root != (u32)r) __hip_atomic_store(parent + r, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // smaller than what was there
+    if (rank) rank[r] = root == (u32)r ? 1u : 0u;
+}
+
+// sizes[c] += voxels of the runs of component c = rank[parent[run]]; a thread adds up neighbouring runs of one component
+// first, a wave whose lanes all hold the same component adds once (one solid body: one atomic per 64 rows)
+__global__ __launch_bounds__(CC_THREADS) void cc_sizes_kernel(const u64 *__restrict__ bits, int64_t nrows, int nx, int wx,
+                                                              const u32 *__restrict__ row_off, const u64 *__restrict__ tot, int64_t cap,
+                                                              const u32 *__restrict__ parent, const u32 *__restrict__ rank,
+                                                              unsigned long long *__restrict__ sizes, u64 *flags)
+{
+    const int64_t row = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    const u32 nruns = (u32)cc_count(tot, cap);
+    u32 comp = 0;                                           // component + 1 the thread is adding up, 0: none
+    u64 acc = 0;
+    if (row < nrows) {
+        CcRuns a = cc_runs_begin(bits, row, nx, wx);
+        u32 ia = row_off[row];
+        while (a.valid) {
+            if (ia >= nruns) {
+                atomicOr((unsigned long long *)flags, CC_F_RANGE);
+                break;
+            }
+            const u32 c = cc_component(parent, rank, ia) + 1;
+            if (c != comp) {
+                if (acc && comp - 1 < nruns) atomicAdd(sizes + (comp - 1), (unsigned long long)acc);
+                comp = c;
+                acc = 0;
+            }
+            acc += (u64)(a.e - a.s);
+            cc_runs_next(a);
+            ia++;
+        }
+    }
+    if (!acc) comp = 0;
+    u32 top = comp;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const u32 o = __shfl_xor(top, d, 64);
+        top = o > top ? o : top;
+    }
+    if (top == 0) return;                                   // wave-uniform
+    if (__all(comp == 0 || comp == top)) {
+        const u64 sum = wave_sum64(acc);
+        if ((threadIdx.x & 63) == 0 && top - 1 < nruns) atomicAdd(sizes + (top - 1), (unsigned long long)sum);
+    } else if (acc && comp - 1 < nruns) {
+        atomicAdd(sizes + (comp - 1), (unsigned long long)acc);
+    }
+}
+
+TOMO_API int tomo_cc_label_runs(const uint64_t *bits, int nz, int ny, int nx, int connectivity, const uint32_t *row_off,
+                                int64_t cap_runs, uint32_t *parent, uint32_t *rank, int64_t *sizes, uint64_t *blk,
+                                unsigned long long *tot, void *stream)
+{
+    int64_t nrows;
+    int wx;
+    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
+    if (g != TOMO_OK) return g;
+    if (!row_off || !parent || !rank || !sizes || !blk || !tot || cap_runs <= 0 || (connectivity != 6 && connectivity != 26))
+        return TOMO_E_ARG;
+    if (cap_runs >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
+    hipStream_t st = (hipStream_t)stream;
+    const int widen = connectivity == 26 ? 1 : 0;
+    const unsigned row_blocks = (unsigned)ceil_div64(nrows, CC_THREADS), run_blocks = (unsigned)ceil_div64(cap_runs, CC_THREADS);
+    const u64 *t = (const u64 *)tot;
+    u64 *flags = (u64 *)tot + 2;
+    if (hipMemsetAsync(sizes, 0, (size_t)cap_runs * sizeof(int64_t), st) != hipSuccess) return TOMO_E_LAUNCH;
+    hipLaunchKernelGGL(cc_init_kernel, dim3(row_blocks), dim3(CC_THREADS), 0, st, (const u64 *)bits, nrows, ny, nx, wx,
+                       (const u32 *)row_off, t, cap_runs, widen, (u32 *)parent, flags);
+    hipLaunchKernelGGL(cc_flatten_kernel, dim3(run_blocks), dim3(CC_THREADS), 0, st, (u32 *)parent, t, cap_runs, (u32 *)nullptr);
+    hipLaunchKernelGGL(cc_union_kernel, dim3(row_blocks), dim3(CC_THREADS), 0, st, (const u64 *)bits, nrows, ny, nx, wx,
+                       (const u32 *)row_off, t, cap_runs, widen, (u32 *)parent, flags);
+    hipLaunchKernelGGL(cc_flatten_kernel, dim3(run_blocks), dim3(CC_THREADS), 0, st, (u32 *)parent, t, cap_runs, (u32 *)rank);
+    cc_scan((u32 *)rank, t, cap_runs, (u64 *)blk, (u64 *)tot + 1, nullptr, st);
+    hipLaunchKernelGGL(cc_sizes_kernel, dim3(row_blocks), dim3(CC_THREADS), 0, st, (const u64 *)bits, nrows, nx, wx,
+                       (const u32 *)row_off, t, cap_runs, (const u32 *)parent, (const u32 *)rank, (unsigned long long *)sizes, flags);
+    return tomo_status();
+}
+
+// ---------------------------------------------------------------------------------------------- per word: which run is bit b in?
+// runs that start in the words of the row in front of word wj, + the row's first run id: bit b of the word belongs to run
+// cc_before + popcount(starts & bits 0 .. b) - 1 (a run that came in from the word before has no start bit here)
+__device__ static inline u32 cc_before(const u64 *__restrict__ row, int nx, int wx, int wj, u32 first)
+{
+    for (int w = 0; w < wj; w++) first += (u32)__popcll(cc_starts(row, nx, wx, w, cc_word(row, nx, wx, w)));
+    return first;
+}
+
+__global__ __launch_bounds__(CC_THREADS) void cc_expand_kernel(const u64 *__restrict__ bits, int64_t nwords, int nx, int wx,
+                                                               const u32 *__restrict__ row_off, const u64 *__restrict__ tot, int64_t cap,
+                                                               const u32 *__restrict__ parent, const u32 *__restrict__ rank,
+                                                               int32_t *__restrict__ labels, u64 *flags)
+{
+    const int64_t i = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;       // the word of this lane
+    const int lane = threadIdx.x & 63;
+    const u32 nruns = (u32)cc_count(tot, cap);
+    u64 cur = 0, starts = 0;
+    u32 before = 0;
+    int64_t row = 0;
+    int wj = 0;
+    if (i < nwords) {
+        row = i / wx;
+        wj = (int)(i - row * wx);
+        const u64 *r = bits + row * wx;
+        cur = cc_word(r, nx, wx, wj);
+        starts = cc_starts(r, nx, wx, wj, cur);
+        before = cc_before(r, nx, wx, wj, row_off[row]);
+    }
+    // the 64 words of the wave one after the other: lane b writes voxel b of the word (256 contiguous bytes per store)
+    const int64_t wave0 = i - lane;
+    for (int j = 0; j < 64; j++) {
+        if (wave0 + j >= nwords) break;                     // wave-uniform
+        const u64 c = __shfl(cur, j, 64), s = __shfl(starts, j, 64);
+        const u32 bf = __shfl(before, j, 64);
+        const int64_t rj = __shfl(row, j, 64);
+        const int x = 64 * __shfl(wj, j, 64) + lane;
+        if (x < nx) {                                       // no lane leaves the loop early: the shuffles need all 64
+            int32_t lab = 0;
+            if ((c >> lane) & 1) {
+                const u32 run = bf + (u32)__popcll(s & (~0ull >> (63 - lane))) - 1;
+                if (run < nruns) lab = (int32_t)(cc_component(parent, rank, run) + 1);
+                else atomicOr((unsigned long long *)flags, CC_F_RANGE);
+            }
+            labels[rj * nx + x] = lab;
+        }
+    }
+}
+
+TOMO_API int tomo_cc_expand(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                            const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, int32_t *labels, void *stream)
+{
+    int64_t nrows;
+    int wx;
+    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
+    if (g != TOMO_OK) return g;
+    if (!row_off || !parent || !rank || !tot || !labels || cap_runs <= 0) return TOMO_E_ARG;
+    if (cap_runs >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
+    const int64_t nwords = nrows * wx;
+    hipLaunchKernelGGL(cc_expand_kernel, dim3((unsigned)ceil_div64(nwords, CC_THREADS)), dim3(CC_THREADS), 0, (hipStream_t)stream,
+                       (const u64 *)bits, nwords, nx, wx, (const u32 *)row_off, (const u64 *)tot, cap_runs, (const u32 *)parent,
+                       (const u32 *)rank, labels, (u64 *)tot + 2);
+    return tomo_status();
+}
+
+// ---------------------------------------------------------------------------------------------- the keep rule
+// one workgroup: tot[3] = label of the largest component with at least min_voxels voxels, the lowest label among equals; 0: none
+__global__ __launch_bounds__(1024) void cc_largest_kernel(const unsigned long long *__restrict__ sizes, u64 *tot, int64_t cap,
+                                                          u64 min_voxels)
+{
+    __shared__ u64 bs[16];
+    __shared__ u64 bl[16];
+    u64 n = tot[1];
+    if (n > (u64)cap || tot[0] > (u64)cap) n = 0;
+    u64 best = 0, lab = 0;                                  // lab 0: nothing yet
+    for (u64 c = threadIdx.x; c < n; c += 1024) {           // ascending labels: a later equal size never replaces
+        const u64 s = sizes[c];
+        if (s >= min_voxels && s > 0 && (lab == 0 || s > best)) { best = s; lab = c + 1; }
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const u64 os = __shfl_xor(best, d, 64), ol = __shfl_xor(lab, d, 64);
+        if (ol != 0 && (lab == 0 || os > best || (os == best && ol < lab))) { best = os; lab = ol; }
+    }
+    if ((threadIdx.x & 63) == 0) { bs[threadIdx.x >> 6] = best; bl[threadIdx.x >> 6] = lab; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 16; w++)
+            if (bl[w] != 0 && (lab == 0 || bs[w] > best || (bs[w] == best && bl[w] < lab))) { best = bs[w]; lab = bl[w]; }
+        tot[3] = lab;
+    }
+}
+
+// out word = the bits of the word's runs whose component is kept
+__global__ __launch_bounds__(CC_THREADS) void cc_filter_kernel(const u64 *__restrict__ bits, int64_t nwords, int nx, int wx,
+                                                               const u32 *__restrict__ row_off, const u64 *__restrict__ tot, int64_t cap,
+                                                               const u32 *__restrict__ parent, const u32 *__restrict__ rank,
+                                                               const unsigned long long *__restrict__ sizes, u64 min_voxels, int largest,
+                                                               u64 *__restrict__ out, u64 *flags)
+{
+    const int64_t i = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    if (i >= nwords) return;
+    const u32 nruns = (u32)cc_count(tot, cap);
+    const u64 only = largest ? tot[3] : 0;
+    const int64_t row = i / wx;
+    const int wj = (int)(i - row * wx);
+    const u64 *r = bits + row * wx;
+    u64 m = cc_word(r, nx, wx, wj);
+    u64 res = 0;
+    if (m) {
+        const bool carry = wj > 0 && (r[wj - 1] >> 63);
+        u32 next = cc_before(r, nx, wx, wj, row_off[row]);   // id of the next run that STARTS in this word
+        while (m) {                                         // every turn clears at least one bit of m
+            const int s = __ffsll((long long)m) - 1;
+            const u64 z = ~(m >> s);                        // bit k: position s + k is clear (the shift brings zeros in from the top)
+            const int len = z ? __ffsll((long long)z) - 1 : 64;
+            const u64 mask = len >= 64 ? ~0ull : ((1ull << len) - 1) << s;
+            const u32 run = (s == 0 && carry) ? next - 1 : next++;
+            if (run < nruns) {
+                const u32 c = cc_component(parent, rank, run);
+                const bool keep = largest ? (u64)c + 1 == only : (c < nruns && sizes[c] >= min_voxels);
+                if (keep) res |= mask;
+            } else {
+                atomicOr((unsigned long long *)flags, CC_F_RANGE);
+            }
+            m &= ~mask;
+        }
+    }
+    out[i] = res;
+}
+
+TOMO_API int tomo_cc_filter(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                            const uint32_t *parent, const uint32_t *rank, const int64_t *sizes, unsigned long long *tot,
+                            int64_t min_voxels, int largest, uint64_t *out, void *stream)
+{
+    int64_t nrows;
+    int wx;
+    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
+    if (g != TOMO_OK) return g;
+    if (!row_off || !parent || !rank || !sizes || !tot || !out || out == bits || cap_runs <= 0 || min_voxels < 0) return TOMO_E_ARG;
+    if (cap_runs >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t nwords = nrows * wx;
+    if (largest)
+        hipLaunchKernelGGL(cc_largest_kernel, dim3(1), dim3(1024), 0, st, (const unsigned long long *)sizes, (u64 *)tot, cap_runs,
+                           (u64)min_voxels);
+    hipLaunchKernelGGL(cc_filter_kernel, dim3((unsigned)ceil_div64(nwords, CC_THREADS)), dim3(CC_THREADS), 0, st, (const u64 *)bits,
+                       nwords, nx, wx, (const u32 *)row_off, (const u64 *)tot, cap_runs, (const u32 *)parent, (const u32 *)rank,
+                       (const unsigned long long *)sizes, (u64)min_voxels, largest ? 1 : 0, (u64 *)out, (u64 *)tot + 2);
+    return tomo_status();
+}

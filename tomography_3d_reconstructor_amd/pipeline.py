@@ -20,7 +20,8 @@ from . import _lib
 
 # which way the size hints and the unique stage of the surfaces of this process went (tests and tools read the deltas)
 COUNTERS = dict.fromkeys(("na_hint_hit", "na_hint_miss", "mc3_hint_hit", "mc3_hint_miss", "mc3_sort_fused", "mc3_sort_library",
-                          "mc3_exact", "mc3_general_unique", "mc3_degenerate"), 0)
+                          "mc3_exact", "mc3_general_unique", "mc3_degenerate", "components_label", "components_expand",
+                          "components_filter"), 0)
 NA_HINTS = os.environ.get("TOMO_NA_HINTS", "1") not in ("", "0")   # marching_cubes: launch ahead of the first count download
 _NA_HINT = {}
 LIST_LIMIT = 2 ** 31        # active-voxel list entries / vertices / triangles one pass can index (int32 offsets in mc.hip, mesh.hip);
@@ -229,6 +230,103 @@ def point_cloud(vol: BitVolume, slice_depths, mm_per_pixel_x, mm_per_pixel_y, su
     plan = PointCloudPlan(vol, point_cloud_z_table(slice_depths, nz, z0), mm_per_pixel_y, mm_per_pixel_x,
                           point_cloud_step(subsample_factor), rank_base)
     return plan.rows() if window is None else plan.rows(window[0], window[1])
+
+
+# ----------------------------------------------------------------------------- connected components
+CONNECTIVITIES = (6, 26)     # generate_binary_structure(3, 1) -- the cross of voxel_processor.py:88,91 -- and (3, 3)
+RUN_LIMIT = 2 ** 31          # run ids are 32-bit in csrc/components.hip
+
+
+class ComponentRuns:
+    """The run tables of one BitVolume under one connectivity: scipy.ndimage.label's components, held per X-RUN (a maximal
+    run of set bits in a row) and never per voxel.  Two host reads: the number of runs (it sizes the tables) and the
+    counters after the labelling.  n = components; labels() / sizes() / keep() read the tables."""
+
+    def __init__(self, vol: BitVolume, connectivity=6):
+        if connectivity not in CONNECTIVITIES:
+            raise ValueError("connectivity must be 6 or 26")
+        nz, ny, nx = vol.shape
+        L, dev, st = _lib.lib(), vol.device, _stream()
+        self.vol, self.bits, self.connectivity = vol, vol.bits.contiguous(), int(connectivity)
+        nrows = nz * ny
+        self.tot = torch.empty(8, dtype=torch.int64, device=dev)
+        self.row_off = torch.empty(nrows + 1, dtype=torch.int32, device=dev)
+        blk = torch.empty(L.tomo_cc_scan_blocks(nrows + 1), dtype=torch.int64, device=dev)
+        geo = (_p(self.bits), nz, ny, nx)
+        _lib.check(L.tomo_cc_count_runs(*geo, _p(self.row_off), _p(blk), _p(self.tot), st), "tomo_cc_count_runs")
+        self.runs = _download(self.tot)[0]                       # the one read that sizes the tables
+        self.n = 0
+        COUNTERS["components_label"] += 1
+        if self.runs == 0:
+            return
+        if self.runs >= RUN_LIMIT:
+            raise _lib.TomoError("too many runs for 32-bit run ids")
+        cap = self.runs
+        self.parent = torch.empty(cap, dtype=torch.int32, device=dev)
+        self.rank = torch.empty(cap, dtype=torch.int32, device=dev)
+        self._sizes = torch.empty(cap, dtype=torch.int64, device=dev)
+        blk = torch.empty(L.tomo_cc_scan_blocks(cap), dtype=torch.int64, device=dev)
+        _lib.check(L.tomo_cc_label_runs(*geo, self.connectivity, _p(self.row_off), cap, _p(self.parent), _p(self.rank), _p(self._sizes),
+                                        _p(blk), _p(self.tot), st), "tomo_cc_label_runs")
+
+    def _tables(self):
+        return _p(self.row_off), self.runs, _p(self.parent), _p(self.rank)
+
+    def _checked(self):
+        """The counters after the work enqueued so far -> n; raises when a guard of the kernels fired."""
+        host = _download(self.tot)
+        if host[2] or host[0] != self.runs:
+            raise _lib.TomoError("component labelling: the run tables do not fit the volume (flags %d)" % host[2])
+        self.n = host[1]
+        return self.n
+
+    def sizes(self) -> torch.Tensor:
+        """Voxels of component 1..n -> int64 (n,) device tensor (a view of the table)."""
+        if self.runs == 0:
+            return torch.zeros(0, dtype=torch.int64, device=self.vol.device)
+        return self._sizes[:self._checked()]
+
+    def labels(self):
+        """-> (int32 (nz, ny, nx) device tensor as scipy.ndimage.label returns it, n)."""
+        nz, ny, nx = self.vol.shape
+        COUNTERS["components_expand"] += 1
+        if self.runs == 0:
+            return torch.zeros((nz, ny, nx), dtype=torch.int32, device=self.vol.device), 0
+        out = torch.empty((nz, ny, nx), dtype=torch.int32, device=self.vol.device)
+        _lib.check(_lib.lib().tomo_cc_expand(_p(self.bits), nz, ny, nx, *self._tables(), _p(self.tot), _p(out), _stream()),
+                   "tomo_cc_expand")
+        return out, self._checked()
+
+    def keep(self, min_voxels=0, largest=False) -> BitVolume:
+        """A NEW volume with the components of at least min_voxels voxels; largest: only the largest of those."""
+        nz, ny, nx = self.vol.shape
+        min_voxels = max(0, int(min_voxels))
+        COUNTERS["components_filter"] += 1
+        if self.runs == 0:
+            return BitVolume(torch.zeros_like(self.bits), self.vol.shape)
+        out = torch.empty_like(self.bits)
+        _lib.check(_lib.lib().tomo_cc_filter(_p(self.bits), nz, ny, nx, *self._tables(), _p(self._sizes), _p(self.tot), min_voxels,
+                                             int(bool(largest)), _p(out), _stream()), "tomo_cc_filter")
+        self._checked()
+        return BitVolume(out, self.vol.shape)
+
+
+def label_components(vol: BitVolume, connectivity=6):
+    """scipy.ndimage.label(volume, generate_binary_structure(3, 1 if connectivity == 6 else 3)) of a resident volume ->
+    (labels int32 (nz, ny, nx) device tensor, n): components numbered 1..n in the raster order of their first voxel."""
+    return ComponentRuns(vol, connectivity).labels()
+
+
+def component_sizes(vol: BitVolume, connectivity=6) -> torch.Tensor:
+    """np.bincount(labels.ravel())[1:] without the label array -> int64 (n,) device tensor."""
+    return ComponentRuns(vol, connectivity).sizes()
+
+
+def keep_components(vol: BitVolume, min_voxels=0, largest=False, connectivity=6) -> BitVolume:
+    """Island removal: a new BitVolume holding the components of `vol` with at least min_voxels voxels -- with largest=True
+    only the single largest of those, the first in raster order among equals.  `vol` is left untouched; an empty volume
+    comes back empty.  Working memory scales with the rows and the runs: no per-voxel label array is made."""
+    return ComponentRuns(vol, connectivity).keep(min_voxels, largest)
 
 
 def pack_closed(mask: torch.Tensor) -> BitVolume:

@@ -298,14 +298,48 @@ def _point_cloud_device(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths
     return out
 
 
+def _env_count(name):
+    """A non-negative integer from the environment (unset / empty: 0); anything else is an error, not a silent default."""
+    text = os.environ.get(name, "").strip()
+    if not text:
+        return 0
+    value = int(text)
+    if value < 0:
+        raise ValueError("%s must be a non-negative integer" % name)
+    return value
+
+
 class VoxelProcessor:
-    """Handles voxel data creation and processing operations (reference: voxel_processor.py:27)."""
+    """Handles voxel data creation and processing operations (reference: voxel_processor.py:27).
+
+    Optional, beyond the reference: island removal.  Three instance attributes (TOMO_MIN_COMPONENT_VOXELS=N and
+    TOMO_KEEP_LARGEST=1 in the environment set the first two for every new object, which is how the unchanged orchestrator
+    gets them): with min_component_voxels > 0 or keep_largest_component set, every volume create_voxel_data and
+    smooth_voxel_data hand out holds only the connected components (component_connectivity 6 or 26, scipy.ndimage.label's
+    meaning) of at least that many voxels, respectively only the largest of those.  Off by default: nothing is launched then."""
 
     def __init__(self):
         self.voxel_data = None
         self.side_0_count = 0
         self.side_1_count = 0
         self.side_2_count = 0
+        self.min_component_voxels = _env_count("TOMO_MIN_COMPONENT_VOXELS")
+        self.keep_largest_component = os.environ.get("TOMO_KEEP_LARGEST", "0") not in ("", "0")
+        self.component_connectivity = 6
+
+    def _component_options(self):
+        """(min voxels, largest, connectivity) when island removal is on, else None."""
+        n, largest = int(self.min_component_voxels), bool(self.keep_largest_component)
+        if n <= 0 and not largest:
+            return None
+        if self.component_connectivity not in pipeline.CONNECTIVITIES:
+            raise ValueError("component_connectivity must be 6 or 26")
+        return max(n, 0), largest, int(self.component_connectivity)
+
+    def _keep_components(self, vol):
+        """`vol` without its islands (a new volume), or `vol` itself when the option is off."""
+        opts = self._component_options()
+        return vol if opts is None else pipeline.keep_components(vol, *opts)
 
     def create_voxel_data(self, mask_images: list, close_ends: bool = True,
                           side_0_count: int = 0, side_1_count: int = 0, side_2_count: int = 0) -> np.ndarray:
@@ -339,14 +373,20 @@ class VoxelProcessor:
                 vol = pipeline.close_ends(upload_volume(base), inplace=True)           # a fresh upload, never a cached volume: ours to overwrite
             else:
                 vol = pipeline.pack_closed(_stage_masks(mask_images))
+            vol = self._keep_components(vol)                 # after the ends are closed; the count below is the filtered one
             active = int(pipeline.popcount_async(vol).item())
             self.voxel_data = to_host_volume(vol)
         else:
             stacked = np.stack(mask_images, axis=0)          # the reference returns a new array here
             vol = cached if cached is not None else upload_volume(stacked)
-            active = int(pipeline.popcount_async(vol).item())
-            self.voxel_data = stacked
-            _devcache.put(stacked, vol)
+            if self._component_options() is not None:
+                vol = self._keep_components(vol)             # the array handed out is the download of the filtered volume
+                active = int(pipeline.popcount_async(vol).item())
+                self.voxel_data = to_host_volume(vol)
+            else:
+                active = int(pipeline.popcount_async(vol).item())
+                self.voxel_data = stacked
+                _devcache.put(stacked, vol)
         print(f"Voxels: {self.voxel_data.shape}, active: {active:,}")
         return self.voxel_data
 
@@ -358,17 +398,18 @@ class VoxelProcessor:
             try:
                 # the orchestrator repeats this very call several times: the device result is remembered (see _memo), the
                 # host array is a fresh download every time
-                key = (int(iterations), bool(create_manifold))
+                key = (int(iterations), bool(create_manifold), opts)
                 sm = _memo.smoothed.get(vol, key)
                 if sm is None:
-                    sm = pipeline.smooth(vol, iterations, create_manifold)
+                    sm = self._keep_components(pipeline.smooth(vol, iterations, create_manifold))   # opening can detach a piece
                     _memo.smoothed.put(vol, key, sm)
                 return to_host_volume(sm)
             except pipeline._lib.TomoUnavailable:
                 raise
             except Exception as e:                                       # noqa: BLE001 -- the reference catches Exception here
                 print(f"tomography_3d_reconstructor_amd: smoothing failed ({e}); closings only", file=sys.stderr)
-                return to_host_volume(pipeline.smooth(vol, iterations, False))
+                return to_host_volume(self._keep_components(pipeline.smooth(vol, iterations, False)))
+        opts = self._component_options()
         return with_device_volume(voxel_data, work)
 
     def generate_point_cloud(self, voxel_data: np.ndarray, mm_per_pixel_x: float, mm_per_pixel_y: float,
