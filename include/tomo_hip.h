@@ -189,6 +189,45 @@ int tomo_cc_expand(const uint64_t *bits, int nz, int ny, int nx, const uint32_t 
 int tomo_cc_filter(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
                    const uint32_t *rank, const int64_t *sizes, unsigned long long *tot, int64_t min_voxels, int largest,
                    uint64_t *out, void *stream);
+/* The same across Z-slabs (slab_components.py): rank r labels its slab with the functions above (n_r components); local
+ * component c has the global id base_r + c, base_r = n_0 + .. + n_(r-1).  Pieces that touch across a cut are united, the roots
+ * (smallest id = the piece with the component's first voxel) numbered in ascending id: scipy's numbering of the whole stack.
+ * Run and component ids that arrive in a message are range-checked before they index anything (bit 2 of the flags).
+ *   tomo_cc_slice_components  out int32[cap_out] = the local component (0-based) of every run of slice z, 0 behind them; bit 1 of
+ *                             tot[2] if the slice has more than cap_out runs
+ *   tomo_cc_seam_union        the seam below this slab: bits = the slab (its first slice is read), nb_bits = the lower
+ *                             neighbour's last slice (ny rows), nb_row_off uint32[ny + 1] = tomo_cc_count_runs(nb_bits, 1, ny, nx),
+ *                             nb_comp int32[nb_runs] = that slice's tomo_cc_slice_components.  win uint32[n_prev + n_own] = the
+ *                             window of the id table, relative to base_(r-1): identity, then every pair of touching runs united.
+ *                             seam_tot (device uint64[8]) is zeroed; [2] = flags
+ *   tomo_cc_merge_tables      msg = the ranks' rows of `stride` int64: [0] flags, [1 .. 1 + n_r) the sizes of the rank's
+ *                             components, from word off_win on its window as int32; bases = device int64[world + 1] (base_r,
+ *                             the last = n_total); max_n / max_win = the largest n_r / window.  table uint32[n_total] = the root
+ *                             of every id, num uint32[n_total] = at a root its 0-based number, sizes int64[n_total] of which the
+ *                             first n = voxels of component 1..n; tot is zeroed, [0] = n_total, [1] = n, [2] = flags OR the
+ *                             messages' flags.  blk: tomo_cc_scan_blocks(n_total) words
+ *   tomo_cc_local_maps        per local component c of the slab at `base`: keep uint8[n_local] = the keep rule of tomo_cc_filter
+ *                             on the global sizes (largest: the label goes to tot[3]) and / or label int32[n_local] = the global
+ *                             label; either may be NULL, not both
+ *   tomo_cc_filter_map        tomo_cc_filter with `keep` in place of the sizes      (tot: the slab's own counters)
+ *   tomo_cc_expand_map        tomo_cc_expand with `label` in place of the numbering */
+int tomo_cc_slice_components(int nz, int ny, int z, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
+                             const uint32_t *rank, unsigned long long *tot, int32_t *out, int64_t cap_out, void *stream);
+int tomo_cc_seam_union(const uint64_t *bits, int ny, int nx, int connectivity, const uint32_t *row_off, int64_t cap_runs,
+                       const uint32_t *parent, const uint32_t *rank, const unsigned long long *tot, const uint64_t *nb_bits,
+                       const uint32_t *nb_row_off, const int32_t *nb_comp, int64_t nb_runs, int64_t n_prev, int64_t n_own,
+                       uint32_t *win, unsigned long long *seam_tot, void *stream);
+int tomo_cc_merge_tables(const int64_t *msg, int world, int64_t stride, int64_t off_win, const int64_t *bases, int64_t n_total,
+                         int64_t max_n, int64_t max_win, uint32_t *table, uint32_t *num, int64_t *sizes, uint64_t *blk,
+                         unsigned long long *tot, void *stream);
+int tomo_cc_local_maps(const uint32_t *table, const uint32_t *num, const int64_t *sizes, unsigned long long *tot, int64_t n_total,
+                       int64_t base, int64_t n_local, int64_t min_voxels, int largest, uint8_t *keep, int32_t *label, void *stream);
+int tomo_cc_filter_map(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
+                       const uint32_t *rank, unsigned long long *tot, const uint8_t *keep, int64_t n_local, uint64_t *out,
+                       void *stream);
+int tomo_cc_expand_map(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
+                       const uint32_t *rank, unsigned long long *tot, const int32_t *label, int64_t n_local, int32_t *labels,
+                       void *stream);
 /* image_loader.py:108 (`img >= threshold`) fused with the packing: grey = uint8 (nz, ny, nx) on the device. */
 int tomo_pack_threshold(const uint8_t *grey, uint64_t *bits, int nz, int ny, int nx, int threshold, void *stream);
 /* obj_exporter.py:17-38, byte for byte ("v %.6f %.6f %.6f" per vertex, "f a+1 b+1 c+1" per face), HOST arrays:

@@ -21,7 +21,8 @@ from . import _lib
 # which way the size hints and the unique stage of the surfaces of this process went (tests and tools read the deltas)
 COUNTERS = dict.fromkeys(("na_hint_hit", "na_hint_miss", "mc3_hint_hit", "mc3_hint_miss", "mc3_sort_fused", "mc3_sort_library",
                           "mc3_exact", "mc3_general_unique", "mc3_degenerate", "components_label", "components_expand",
-                          "components_filter"), 0)
+                          "components_filter", "slab_components_label", "slab_components_seam", "slab_components_merge",
+                          "slab_components_expand", "slab_components_filter"), 0)
 NA_HINTS = os.environ.get("TOMO_NA_HINTS", "1") not in ("", "0")   # marching_cubes: launch ahead of the first count download
 _NA_HINT = {}
 LIST_LIMIT = 2 ** 31        # active-voxel list entries / vertices / triangles one pass can index (int32 offsets in mc.hip, mesh.hip);

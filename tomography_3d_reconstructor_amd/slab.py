@@ -588,6 +588,7 @@ class SlabJob:
             raise ValueError("slab thinner than the halo (%d slices): use fewer ranks" % self.halo)
         self.active = None
         self.created = self.smoothed = self.mesh = None     # this rank's share of the last run(), for the consumers below
+        self.kept = None                                    # this rank's share of the last keep_components()
         # the pass without host round trips (_numbering_deferred): agreed by ALL ranks in the last pass's all-gather, with the
         # message capacities both neighbours derive from that pass's exact shared-plane counts
         self._deferred_ok = False
@@ -944,10 +945,36 @@ class SlabJob:
     # volume_calculator.py: both work on what every rank already holds, exchange a few numbers, and give exactly what
     # the single-GPU classes (OBJExporter, VolumeCalculator) give on the whole volume / the gathered mesh.
     def _volume(self, which):
+        if which == "kept":
+            if self.kept is None:
+                raise RuntimeError("keep_components() first")
+            return self.kept
         vol = {"smoothed": self.smoothed, "created": self.created}[which]
         if vol is None:
             raise RuntimeError("run() first")
         return vol
+
+    # Connected components of the WHOLE stack (slab_components.py: three small collective steps, nothing wider than bits
+    # travels).  Filtering inside the pass is not built: the job's mesh is made from the unfiltered volume.
+    def _components(self, which, connectivity):
+        from .slab_components import SlabComponents
+        return SlabComponents(self._volume(which), self.comm, connectivity)
+
+    def component_sizes(self, which="smoothed", connectivity=6):
+        """== pipeline.component_sizes(whole volume): int64 (n,) device tensor, the same on every rank.  Collective."""
+        return self._components(which, connectivity).sizes()
+
+    def label_components(self, which="smoothed", connectivity=6):
+        """-> (labels, n): this rank's slices of pipeline.label_components(whole volume) -- concatenated in rank order the
+        ranks' arrays are scipy.ndimage.label's array -- and the number of components of the whole stack.  Collective."""
+        return self._components(which, connectivity).labels()
+
+    def keep_components(self, min_voxels=0, largest=False, connectivity=6, which="smoothed"):
+        """== pipeline.keep_components(whole volume, ...), slab by slab: this rank's slices of it as a new BitVolume, remembered
+        as self.kept -- which="kept" then selects it in slice_counts / index_box / voxel_volume / bounding_box / point_cloud.
+        Collective.  self.mesh and the numbering of the last run() are untouched."""
+        self.kept = self._components(which, connectivity).keep(min_voxels, largest)
+        return self.kept
 
     def slice_counts(self, which="smoothed"):
         """np.sum(volume[z]) for every slice of the WHOLE stack (volume_calculator.py:33) -> int64 (gz,) on every rank:
