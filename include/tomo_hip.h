@@ -228,6 +228,32 @@ int tomo_cc_filter_map(const uint64_t *bits, int nz, int ny, int nx, const uint3
 int tomo_cc_expand_map(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
                        const uint32_t *rank, unsigned long long *tot, const int32_t *label, int64_t n_local, int32_t *labels,
                        void *stream);
+/* Exact Euclidean distance transform of the resident bits in millimetres (no counterpart in the reference;
+ * scipy.ndimage.distance_transform_edt with a coordinate table per axis instead of one sampling per axis, so slice depths may
+ * change from slice to slice).  zt / yt / xt: device float64[n + 2], strictly ascending: entry i + 1 = the centre of index i,
+ * entries 0 and n + 1 = the VIRTUAL sites outside the volume.  inside != 0: the sites are the unset voxels and every virtual
+ * position, the value at a set voxel is the distance to the nearest site and 0 at an unset one.  inside == 0: the sites are
+ * the set voxels (virtual positions never are), the value at a set voxel is 0 and +inf everywhere if nothing is set.
+ * d2 = ((dx^2 + dy^2) + dz^2) in float64, every d a difference of two table entries, no contraction; three separable passes
+ * that each take the minimum over their line.  The volume is worked through in chunks of whole 64-column words of x:
+ *   tomo_edt_workspace_bytes  bytes of the workspace for the widest chunk that fits budget_bytes (at least one word: the
+ *                             result may exceed a smaller budget); linear in nz * ny * columns, never in the whole volume
+ *   tomo_edt_chunk_columns    columns per chunk a workspace of that many bytes gives (TOMO_E_WORKSPACE below one word)
+ *   tomo_edt_distance         out float32 (nz, ny, nx) = (float)sqrt(d2)
+ *   tomo_edt_threshold        out uint64 (nz, ny, words) (!= bits): bit = d2 > r2 (keep_greater) or d2 <= r2, compared in
+ *                             float64; tail bits zero; no float volume is made.  r2 >= 0
+ *   tomo_edt_argmax           result device int64[2]: [0] = the bits of the largest float32 output value, [1] = the smallest
+ *                             flat index (z * ny + y) * nx + x that attains it.  Per-thread partials folded by one workgroup
+ *                             in a fixed order: no float atomics, the same on every run
+ * The workspace is scratch: nothing is read from it that the call did not write.  bits is only read. */
+int64_t tomo_edt_workspace_bytes(int nz, int ny, int nx, int64_t budget_bytes);
+int64_t tomo_edt_chunk_columns(int nz, int ny, int nx, int64_t workspace_bytes);
+int tomo_edt_distance(const uint64_t *bits, int nz, int ny, int nx, const double *zt, const double *yt, const double *xt, int inside,
+                      float *out, void *workspace, int64_t workspace_bytes, void *stream);
+int tomo_edt_threshold(const uint64_t *bits, int nz, int ny, int nx, const double *zt, const double *yt, const double *xt, int inside,
+                       double r2, int keep_greater, uint64_t *out, void *workspace, int64_t workspace_bytes, void *stream);
+int tomo_edt_argmax(const uint64_t *bits, int nz, int ny, int nx, const double *zt, const double *yt, const double *xt, int inside,
+                    int64_t *result, void *workspace, int64_t workspace_bytes, void *stream);
 /* image_loader.py:108 (`img >= threshold`) fused with the packing: grey = uint8 (nz, ny, nx) on the device. */
 int tomo_pack_threshold(const uint8_t *grey, uint64_t *bits, int nz, int ny, int nx, int threshold, void *stream);
 /* obj_exporter.py:17-38, byte for byte ("v %.6f %.6f %.6f" per vertex, "f a+1 b+1 c+1" per face), HOST arrays:

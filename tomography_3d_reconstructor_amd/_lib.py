@@ -62,6 +62,11 @@ SIGNATURES = {
     "tomo_cc_local_maps": (_c_i, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i, _c_p, _c_p, _c_p]),
     "tomo_cc_filter_map": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p]),
     "tomo_cc_expand_map": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p]),
+    "tomo_edt_workspace_bytes": (_c_i64, [_c_i, _c_i, _c_i, _c_i64]),
+    "tomo_edt_chunk_columns": (_c_i64, [_c_i, _c_i, _c_i, _c_i64]),
+    "tomo_edt_distance": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_i, _c_p, _c_p, _c_i64, _c_p]),
+    "tomo_edt_threshold": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_i, _c_d, _c_i, _c_p, _c_p, _c_i64, _c_p]),
+    "tomo_edt_argmax": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_i, _c_p, _c_p, _c_i64, _c_p]),
     "tomo_pack_threshold": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_p]),
     "tomo_obj_write": (_c_i, [ctypes.c_char_p, _c_p, _c_i, _c_i64, _c_p, _c_i64, _c_i]),
     "tomo_obj_block_format": (_c_i, [_c_i, _c_p, _c_i64, _c_i, ctypes.POINTER(_c_p), ctypes.POINTER(_c_i64)]),

@@ -22,7 +22,7 @@ from . import _lib
 COUNTERS = dict.fromkeys(("na_hint_hit", "na_hint_miss", "mc3_hint_hit", "mc3_hint_miss", "mc3_sort_fused", "mc3_sort_library",
                           "mc3_exact", "mc3_general_unique", "mc3_degenerate", "components_label", "components_expand",
                           "components_filter", "slab_components_label", "slab_components_seam", "slab_components_merge",
-                          "slab_components_expand", "slab_components_filter"), 0)
+                          "slab_components_expand", "slab_components_filter", "distance_transform", "distance_offset"), 0)
 NA_HINTS = os.environ.get("TOMO_NA_HINTS", "1") not in ("", "0")   # marching_cubes: launch ahead of the first count download
 _NA_HINT = {}
 LIST_LIMIT = 2 ** 31        # active-voxel list entries / vertices / triangles one pass can index (int32 offsets in mc.hip, mesh.hip);
@@ -328,6 +328,116 @@ def keep_components(vol: BitVolume, min_voxels=0, largest=False, connectivity=6)
     only the single largest of those, the first in raster order among equals.  `vol` is left untouched; an empty volume
     comes back empty.  Working memory scales with the rows and the runs: no per-voxel label array is made."""
     return ComponentRuns(vol, connectivity).keep(min_voxels, largest)
+
+
+# ----------------------------------------------------------------------------- Euclidean distance in millimetres
+EDT_WORKSPACE_BUDGET = 1 << 30      # bytes of scratch a distance call may take; at least one 64-column chunk is always granted
+
+
+def _positive(x, what):
+    x = float(x)
+    if not (math.isfinite(x) and x > 0):
+        raise ValueError("%s must be positive and finite" % what)
+    return x
+
+
+def distance_positions(slice_depths, nz, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, ny=None, nx=None):
+    """The coordinate tables of the distance transform, on the host -> (zt, yt, xt) float64 with n + 2 entries each: entry
+    i + 1 is the centre of index i -- point_cloud_z_table's slice centres along z, j * mm_per_pixel_y, i * mm_per_pixel_x --
+    and entries 0 / n + 1 are the virtual background sites one step outside the volume (along z one end-slice depth, the
+    end-slice repetition of SurfaceExtractor._apply_variable_slice_depths).  slice_depths=None: depth 1.0 per slice.
+    yt / xt are None when ny / nx is not given."""
+    nz = int(nz)
+    d = np.ones(nz) if slice_depths is None else np.asarray(slice_depths, dtype=np.float64).reshape(-1)
+    if nz < 1 or len(d) != nz:
+        raise ValueError("slice_depths must hold one depth per slice (%d for nz = %d)" % (len(d), nz))
+    if not (np.isfinite(d).all() and (d > 0).all()):
+        raise ValueError("slice depths must be positive and finite")
+    zc = point_cloud_z_table(d, nz)
+    zt = np.concatenate([[zc[0] - d[0]], zc, [zc[-1] + d[-1]]])
+    mm_y, mm_x = _positive(mm_per_pixel_y, "mm_per_pixel_y"), _positive(mm_per_pixel_x, "mm_per_pixel_x")
+    yt = None if ny is None else np.arange(-1, int(ny) + 1, dtype=np.float64) * mm_y
+    xt = None if nx is None else np.arange(-1, int(nx) + 1, dtype=np.float64) * mm_x
+    return zt, yt, xt
+
+
+class _DistancePlan:
+    """What the three distance calls share: the bits, the tables on the device (one upload) and the chunked workspace."""
+
+    def __init__(self, vol: BitVolume, slice_depths, mm_per_pixel_y, mm_per_pixel_x):
+        nz, ny, nx = vol.shape
+        tables = distance_positions(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x, ny, nx)
+        for t in tables:
+            if not (np.diff(t) > 0).all():
+                raise ValueError("the spacing is too small against the extent: two positions coincide in float64")
+        L = _lib.lib()
+        self.vol, self.bits = vol, vol.bits.contiguous()
+        self.host_tables = tables
+        tab = torch.from_numpy(np.concatenate(tables)).to(vol.device)
+        self.tab = tab
+        self.zt, self.yt, self.xt = tab[:nz + 2], tab[nz + 2:nz + ny + 4], tab[nz + ny + 4:]
+        self.ws_bytes = int(L.tomo_edt_workspace_bytes(nz, ny, nx, EDT_WORKSPACE_BUDGET))
+        if self.ws_bytes <= 0:
+            raise _lib.TomoError("tomo_edt_workspace_bytes failed (%d)" % self.ws_bytes)
+        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=vol.device)
+
+    def head(self):
+        nz, ny, nx = self.vol.shape
+        return _p(self.bits), nz, ny, nx, _p(self.zt), _p(self.yt), _p(self.xt)
+
+    def tail(self):
+        return _p(self.ws), self.ws_bytes, _stream()
+
+
+def distance_transform(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, inside=True) -> torch.Tensor:
+    """Exact Euclidean distance transform of a resident volume in millimetres -> float32 (nz, ny, nx) device tensor.
+    Voxel (k, j, i) sits at (zc[k], j * mm_per_pixel_y, i * mm_per_pixel_x), zc = point_cloud_z_table(slice_depths, nz);
+    everything outside the volume is background (distance_positions: one layer of virtual sites).  inside=True: at a set
+    voxel the distance to the nearest unset site, 0.0 at an unset one.  inside=False: at an unset voxel the distance to the
+    nearest set voxel, 0 at a set one, +inf everywhere in an empty volume.  With uniform depths and inside=True this is
+    distance_transform_edt(np.pad(v, 1), sampling=(d, mm_y, mm_x))[1:-1, 1:-1, 1:-1].  Scratch: tomo_edt_workspace_bytes,
+    at most EDT_WORKSPACE_BUDGET unless one 64-column chunk needs more."""
+    plan = _DistancePlan(vol, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    out = torch.empty(vol.shape, dtype=torch.float32, device=vol.device)
+    COUNTERS["distance_transform"] += 1
+    _lib.check(_lib.lib().tomo_edt_distance(*plan.head(), int(bool(inside)), _p(out), *plan.tail()), "tomo_edt_distance")
+    return out
+
+
+def offset_volume(vol: BitVolume, radius_mm, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0) -> BitVolume:
+    """Erosion / dilation by a ball of radius_mm millimetres -> a NEW BitVolume; `vol` is left untouched.
+    radius_mm < 0: the set voxels whose inside distance is > |radius_mm|.  radius_mm > 0: `vol` plus the unset voxels whose
+    outside distance is <= radius_mm; the shape stays, so nothing grows past the volume.  radius_mm == 0: a copy.
+    The squared distance is compared with radius_mm ** 2 in float64 inside the last pass and balloted into bit words: the
+    call allocates the output words, the three small coordinate tables and the chunked scratch of distance_transform
+    (bounded by EDT_WORKSPACE_BUDGET; it scales with nz * ny * the chunk's columns) -- never a float per voxel."""
+    r = float(radius_mm)
+    if not math.isfinite(r):
+        raise ValueError("radius_mm must be finite")
+    plan = _DistancePlan(vol, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    COUNTERS["distance_offset"] += 1
+    if r == 0:
+        return BitVolume(plan.bits.clone(), vol.shape)
+    out = torch.empty_like(plan.bits)
+    _lib.check(_lib.lib().tomo_edt_threshold(*plan.head(), int(r < 0), r * r, int(r < 0), _p(out), *plan.tail()),
+               "tomo_edt_threshold")
+    return BitVolume(out, vol.shape)
+
+
+def inscribed_sphere(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0):
+    """The largest sphere that fits inside the object: the maximum of distance_transform(inside=True) and the first voxel in
+    raster order that attains it -> (radius_mm, (k, j, i)) in Python numbers, None for an empty volume.  No float volume is
+    made (a per-thread maximum folded in a fixed order); one host read."""
+    nz, ny, nx = vol.shape
+    plan = _DistancePlan(vol, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    res = torch.empty(2, dtype=torch.int64, device=vol.device)
+    COUNTERS["distance_transform"] += 1
+    _lib.check(_lib.lib().tomo_edt_argmax(*plan.head(), 1, _p(res), *plan.tail()), "tomo_edt_argmax")
+    bits32, flat = _download(res)
+    radius = float(np.array([bits32], dtype=np.int64).astype(np.uint32).view(np.float32)[0])
+    if flat < 0 or not radius > 0:
+        return None
+    return radius, (flat // (ny * nx), flat // nx % ny, flat % nx)
 
 
 def pack_closed(mask: torch.Tensor) -> BitVolume:

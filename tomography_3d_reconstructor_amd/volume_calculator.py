@@ -82,6 +82,24 @@ def index_box(voxel_data):
     return tuple(f(axis) for axis in idx for f in (np.min, np.max))
 
 
+def largest_inscribed_sphere(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths):
+    """The largest sphere that fits inside the object, in millimetres (no counterpart in the reference): the maximum of the
+    exact Euclidean distance to the background (pipeline.inscribed_sphere: per-slice depths honoured, everything outside the
+    stack is background) -> {'radius_mm', 'diameter_mm', 'center_index': (z, y, x), 'center_mm': (z_mm, y_mm, x_mm)}.
+    An empty volume has radius 0.0 and no centre (None).  voxel_data: the bool (nz, ny, nx) array the other calculations
+    take; anything else is a TypeError -- there is no host path for this one."""
+    if not _on_device(voxel_data):
+        raise TypeError("largest_inscribed_sphere needs a bool (nz, ny, nx) array")
+    found = pipeline.inscribed_sphere(to_device_volume(voxel_data), slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    if found is None:
+        return {'radius_mm': 0.0, 'diameter_mm': 0.0, 'center_index': None, 'center_mm': None}
+    radius, (z, y, x) = found
+    nz, ny, nx = voxel_data.shape
+    zt, yt, xt = pipeline.distance_positions(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x, ny, nx)
+    return {'radius_mm': radius, 'diameter_mm': 2 * radius, 'center_index': (z, y, x),
+            'center_mm': (float(zt[z + 1]), float(yt[y + 1]), float(xt[x + 1]))}
+
+
 class VolumeCalculator:
     """Handles volume calculations and object property analysis (reference: volume_calculator.py:10)."""
 
