@@ -20,6 +20,7 @@
  *    bit b of word w of a row is voxel x = 64 w + b; bits at x >= nx are zero.
  *
  * Removed in ABI 7 (none had a caller left): tomo_mesh_unique_presorted, tomo_mesh_faces, tomo_mesh_faces_direct, tomo_mesh_faces_workspace_bytes, tomo_mc3_sort_rank, tomo_close_stencil, tomo_pack_close_slab.
+ * Removed in ABI 8 (none had a caller left): tomo_morph_pass, tomo_field_signs_fused; tomo_morph_fused accepts nops 2 and 4 only.
  */
 #ifndef TOMO_HIP_H
 #define TOMO_HIP_H
@@ -127,12 +128,11 @@ int tomo_close_ends_scan(uint64_t *bits, int nz, int ny, int nx, uint64_t *works
 /* The same chain reduced to a pair of bit planes gp_out = [G | P] (2 * ny * wx words) over slices 1 .. nz-2:
  * c'[nz-2] = G | (P & c'[0]).  What a Z-slab rank publishes in the multi-GPU path (same workspace size). */
 int tomo_close_ends_gp(const uint64_t *bits, int nz, int ny, int nx, uint64_t *workspace, uint64_t *gp_out, void *stream);
-/* One 6-neighbour pass (skimage binary_erosion/binary_dilation, voxel_processor.py:88,91):
- * op 0 = erosion with border_value 1, op 1 = dilation with border value 0.  in != out. */
-int tomo_morph_pass(const uint64_t *in, uint64_t *out, int nz, int ny, int nx, int op, void *stream);
-/* nops (2, 4, 6 or 8) such passes fused into one kernel: bit j of `ops` is the op of pass j (0 erosion, 1 dilation).
- * smooth_voxel_data(iterations=3, create_manifold=True) spelled out is E D | D E | D E | D E = ops 0b01010110;
- * tomo_smooth runs it as E D | D E = ops 0b0110. */
+/* nops (2 or 4; anything else is TOMO_E_ARG) 6-neighbour passes (skimage binary_erosion / binary_dilation,
+ * voxel_processor.py:88,91) fused into one kernel, in != out: bit j of `ops` is the op of pass j, 0 = erosion with
+ * border_value 1, 1 = dilation with border value 0.  The masks tomo_smooth plans (E D | D E = ops 0b0110 with nops 4,
+ * D E = 0b01 and E D = 0b10 with nops 2) run in kernels compiled for them; a mask tomo_smooth does not plan takes
+ * the run-time-mask kernel. */
 int tomo_morph_fused(const uint64_t *in, uint64_t *out, int nz, int ny, int nx, uint32_t ops, int nops, void *stream);
 /* smooth_voxel_data (voxel_processor.py:79-97) whole, in ONE launch into `out` (in != out): the opening if
  * create_manifold, then ONE closing if iterations >= 1 -- with the reference's border values (dilation pads with 0,
@@ -298,7 +298,6 @@ int tomo_field_fill_bits_sparse(const uint64_t *bits, float *field, int nz, int 
  * and the 16 records are NOT stored (70 % of the groups of an ellipsoid volume), 2 = the records are stored.
  * tomo_field_signs derives records from any float field for slices [z_begin, z_end) (all groups of class 2). */
 int64_t tomo_sign_rows(int Ny);
-int tomo_field_signs_fused(int nx);                      /* 1: tomo_field_fill writes the records itself (always, ABI 2) */
 /* Size (uint64 words) of the buffer passed as `signs` to tomo_field_fill. */
 int64_t tomo_sign_buffer_words(int Nz, int Ny, int Nx, int xorg);
 int tomo_field_signs(const float *field, int Nz, int Ny, int Nx, int64_t pitch, int xorg, double iso, int z_begin,

@@ -28,7 +28,7 @@ def test_library_builds_and_exports_every_declared_symbol():
 
 def test_abi_version_and_error_strings():
     L = _lib.lib()
-    assert L.tomo_abi_version() == 7
+    assert L.tomo_abi_version() == 8
     assert L.tomo_error_string(0) == b"ok"
     assert b"argument" in L.tomo_error_string(-1)
 
@@ -48,7 +48,12 @@ def test_geometry_helpers():
 def test_argument_checks_do_not_need_a_gpu():
     L = _lib.lib()
     assert L.tomo_pack_bits(None, None, 1, 1, 1, None) == -1
-    assert L.tomo_morph_pass(None, None, 4, 4, 4, 0, None) == -1
+    assert L.tomo_morph_fused(None, None, 4, 4, 4, 6, 4, None) == -1
+    # a pass count other than 2 or 4 is refused before anything is launched.  The function checks its pointers first, so
+    # they must be non-null here: two distinct host buffers, never dereferenced
+    a, b = (ctypes.c_uint64 * 64)(), (ctypes.c_uint64 * 64)()
+    for nops in (0, 1, 3, 6, 8):
+        assert L.tomo_morph_fused(ctypes.addressof(a), ctypes.addressof(b), 4, 4, 4, 6, nops, None) == -1
     assert L.tomo_mc_classify(None, None, 4, 4, 4, 0, None, None, None) == -1
 
 

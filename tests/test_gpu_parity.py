@@ -100,7 +100,7 @@ def test_binary_stages_vs_oracle(dev, shape, p):
 @pytest.mark.parametrize("it,cm", [(3, True), (1, True), (2, False), (3, False), (0, True)])
 def test_smooth_tile_edges_vs_oracle(dev, shape, it, cm):
     """The one-wave-per-tile smoothing kernel: rows wider than a 4-word strip with the tail in every position relative
-    to the strip and its 8-bit halo, several 56-row tiles, slices across z chunks, 2 / 4 / 6 / 8 passes."""
+    to the strip and its 8-bit halo, several 56-row tiles, slices across z chunks, 2 / 4 passes."""
     rng = np.random.default_rng(shape[2] + it)
     v = rng.random(shape) < 0.82
     v[:, : shape[1] // 3, -(shape[2] // 5 + 1):] = True          # solid block against the right border and the tail word

@@ -5,12 +5,18 @@ closing (see the comment at tomo_smooth in csrc/bits.hip and tests/test_smooth_c
 Shapes are the tile-edge ones of test_gpu_parity.test_smooth_tile_edges_vs_oracle: rows beyond one 56-row tile, odd and
 even word counts with the tail word in different places, nz across z chunks.
 """
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
 from oracle import oracle as O
 from tomography_3d_reconstructor_amd import _lib, pipeline
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from morph_reference import apply_mask, volume  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -23,15 +29,6 @@ def dev():
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     return torch.device("cuda:0")
-
-
-def volume(shape, seed):
-    rng = np.random.default_rng(seed)
-    v = rng.random(shape) < 0.82
-    v[:, : shape[1] // 3, -(shape[2] // 5 + 1):] = True          # solid block against the right border and the tail word
-    v[shape[0] // 2:, shape[1] // 2:, : shape[2] // 7 + 1] = rng.random((shape[0] - shape[0] // 2, shape[1] - shape[1] // 2,
-                                                                       shape[2] // 7 + 1)) < 0.5
-    return v
 
 
 def to_vol(arr, dev):
@@ -95,3 +92,32 @@ def test_explicit_two_closings_mask_still_served(dev):
                                            torch.cuda.current_stream().cuda_stream), "tomo_morph_fused")
     assert np.array_equal(to_np(pipeline.BitVolume(out, shape)), O.smooth(v, 2, False))
     assert np.array_equal(O.smooth(v, 2, False), O.smooth(v, 1, False))
+
+
+def words(v):
+    """Bit-packed (nz, ny, wx) int64 words of a boolean volume as the library lays them out: bits beyond nx are zero."""
+    nz, ny, nx = v.shape
+    wx = (nx + 63) // 64
+    padded = np.zeros((nz, ny, wx * 64), np.uint8)
+    padded[:, :, :nx] = v
+    return np.packbits(padded, axis=2, bitorder="little").view("<u8").view(np.int64).reshape(nz, ny, wx)
+
+
+# each the smallest that crosses one edge: two row tiles for both pass counts (60 and 56 own rows), five words and a
+# 6-bit tail; z chunks of 16 with a remainder, whole words; one row and fewer slices than the z halo
+@pytest.mark.parametrize("shape", [(9, 70, 262), (37, 57, 320), (3, 1, 700)])
+def test_every_pass_mask_vs_numpy_reference(dev, shape):
+    """tomo_morph_fused is the only way to a mask the planner does not emit: all 4 masks of 2 passes and all 16 of 4
+    passes, into a garbage-filled `out`, word for word (tail bits zero) against tests/morph_reference.py."""
+    v = volume(shape, shape[2] + 17)
+    vol = to_vol(v, dev)
+    assert np.array_equal(vol.bits.cpu().numpy(), words(v))
+    L = _lib.lib()
+    stream = torch.cuda.current_stream().cuda_stream
+    gen = torch.Generator(device=dev).manual_seed(7)
+    for nops in (2, 4):
+        for ops in range(1 << nops):
+            out = torch.randint(-2 ** 62, 2 ** 62, vol.bits.shape, dtype=torch.int64, device=dev, generator=gen)
+            _lib.check(L.tomo_morph_fused(vol.bits.data_ptr(), out.data_ptr(), *shape, ops, nops, stream), "tomo_morph_fused")
+            assert np.array_equal(out.cpu().numpy(), words(apply_mask(v, ops, nops))), (nops, ops)
+    assert np.array_equal(to_np(vol), v)

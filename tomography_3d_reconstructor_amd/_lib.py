@@ -82,7 +82,6 @@ SIGNATURES = {
     "tomo_close_ends_workspace_words": (_c_i64, [_c_i, _c_i, _c_i]),
     "tomo_close_ends_scan": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_p]),
     "tomo_close_ends_gp": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p]),
-    "tomo_morph_pass": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_p]),
     "tomo_morph_fused": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, ctypes.c_uint32, _c_i, _c_p]),
     "tomo_smooth": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_i, _c_p]),
     "tomo_extend_bits": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_p]),
@@ -91,7 +90,6 @@ SIGNATURES = {
     "tomo_field_span_bytes": (_c_i64, [_c_i, _c_i, _c_i, _c_i]),
     "tomo_field_fill_bits_sparse": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p]),
     "tomo_sign_rows": (_c_i64, [_c_i]),
-    "tomo_field_signs_fused": (_c_i, [_c_i]),
     "tomo_sign_buffer_words": (_c_i64, [_c_i, _c_i, _c_i, _c_i]),
     "tomo_field_signs": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_i64, _c_i, _c_d, _c_i, _c_i, _c_p, _c_p, _c_p]),
     "tomo_mc_classify": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p]),

@@ -935,10 +935,9 @@ TOMO_API int tomo_fill_holes_ends(uint64_t *bits, int nz, int ny, int nx, uint64
 static int pack_close_launch(const uint8_t *mask, u64 *bits, int nz, int ny, int nx, int wx, int groups, int za, int zb, int lo_fixed,
                              int hi_fixed, const u64 *below, const u64 *above, hipStream_t st)
 {
-    static const bool handover = !(getenv("TOMO_PACK_HANDOVER") && atoi(getenv("TOMO_PACK_HANDOVER")) == 0);
     const int G = (zb - za) / PC_U;
     const int nwg = (G + 4 * (PC_ZR / PC_U) - 1) / (4 * (PC_ZR / PC_U));         // ~PC_ZR slices per wave
-    if (handover && zb - za >= 4 * PC_ZR && G >= 4 * nwg) {
+    if (zb - za >= 4 * PC_ZR && G >= 4 * nwg) {
         const int head = (zb - za) % PC_U;
         const int64_t blocks = (int64_t)ny * groups * nwg;
         if (blocks > 0x7fffffff) return TOMO_E_SIZE;
@@ -1202,143 +1201,15 @@ TOMO_API int tomo_close_ends_gp(const uint64_t *bits, int nz, int ny, int nx, ui
 }
 
 // ------------------------------------------------------------------------------------------
-// 6-neighbour erosion (outside = 1) / dilation (outside = 0), one thread per word.
-template <int OP>
-__global__ __launch_bounds__(256) void morph_kernel(const u64 *__restrict__ in, u64 *__restrict__ out, int nz, int ny,
-                                                    int nx, int wx)
-{
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int64_t total = (int64_t)nz * ny * wx;
-    if (i >= total) return;
-    int w = (int)(i % wx);
-    int64_t r = i / wx;
-    int y = (int)(r % ny);
-    int z = (int)(r / ny);
-    const int64_t sw = (int64_t)ny * wx;
-    const u64 tailmask = (nx & 63) ? ((1ull << (nx & 63)) - 1ull) : ~0ull;
-    const u64 valid = (w == wx - 1) ? tailmask : ~0ull;
-    const u64 B = OP == 0 ? ~0ull : 0ull;   // value of voxels outside the volume
-    u64 c = in[i];
-    if (OP == 0) c |= ~valid;               // tail bits beyond nx count as outside (=1) for erosion
-    u64 zl = z > 0 ? in[i - sw] : B, zh = z < nz - 1 ? in[i + sw] : B;
-    u64 yl = y > 0 ? in[i - wx] : B, yh = y < ny - 1 ? in[i + wx] : B;
-    u64 pl = w > 0 ? in[i - 1] : B;         // word holding x-1 of bit 0
-    u64 ph = w < wx - 1 ? in[i + 1] : B;    // word holding x+1 of bit 63
-    u64 xl = (c << 1) | (pl >> 63);         // neighbour x-1 of every bit
-    u64 xh = (c >> 1) | (ph << 63);         // neighbour x+1 of every bit
-    u64 res = OP == 0 ? (c & zl & zh & yl & yh & xl & xh) : (c | zl | zh | yl | yh | xl | xh);
-    out[i] = res & valid;
-}
-
-TOMO_API int tomo_morph_pass(const uint64_t *in, uint64_t *out, int nz, int ny, int nx, int op, void *stream)
-{
-    if (!in || !out || in == out || nz <= 0 || ny <= 0 || nx <= 0 || (op != 0 && op != 1)) return TOMO_E_ARG;
-    int wx = (int)tomo_words_per_row(nx);
-    int64_t total = (int64_t)nz * ny * wx;
-    int64_t blocks = ceil_div64(total, 256);
-    if (blocks > 0x7fffffff) return TOMO_E_SIZE;
-    if (op == 0)
-        hipLaunchKernelGGL(morph_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const u64 *)in,
-                           (u64 *)out, nz, ny, nx, wx);
-    else
-        hipLaunchKernelGGL(morph_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const u64 *)in,
-                           (u64 *)out, nz, ny, nx, wx);
-    return tomo_status();
-}
-
-// ------------------------------------------------------------------------------------------
-// Fused smoothing: all H erosion/dilation passes of smooth_voxel_data (voxel_processor.py:79-97) in ONE kernel.
-// A block owns a tile of rows x words (plus an H-row / 1-word halo that it recomputes) and marches along z as a
-// software pipeline: stage j turns level j-1 into level j,
+// Fused smoothing: all H (<= 4) erosion/dilation passes of smooth_voxel_data (voxel_processor.py:79-97) in ONE kernel,
+// marching along z as a software pipeline: stage j turns level j-1 into level j,
 //     L_j[s] = inplane_j(L_{j-1}[s])  o  L_{j-1}[s-1]  o  L_{j-1}[s+1]          (o = AND for erosion, OR for dilation)
-// where the in-plane part (y+-1 rows, x+-1 bits) needs the neighbours' words: one LDS exchange per stage and
-// slice, two alternating tiles, one barrier per stage.  Per level a thread keeps three words in registers.
-// HBM traffic: ~1.6 x 1 read + 1 write of the bit volume instead of H reads + H writes.
-#define FM_TW 16      // words of a row per tile (a 1024-voxel row is one tile)
-
-__device__ static inline u64 fm_inplane(int op, u64 c, u64 yl, u64 yh, u64 pl, u64 ph, u64 valid)
-{
-    if (op == 0) c |= ~valid;                // bits beyond nx count as outside (=1) for erosion
-    u64 xl = (c << 1) | (pl >> 63), xh = (c >> 1) | (ph << 63);
-    return op == 0 ? (c & yl & yh & xl & xh) : (c | yl | yh | xl | xh);
-}
-
-template <int H, bool ROW16>
-__global__ __launch_bounds__(1024) void morph_fused_kernel(const u64 *__restrict__ in, u64 *__restrict__ out, int nz, int ny,
-                                                           int nx, int wx, u32 ops, int rows_own, int zchunk)
-{
-    extern __shared__ u64 fm_tile[];                     // 2 x (TYH x TWH) words
-    const int TWH = blockDim.x, TYH = blockDim.y;        // tile incl. halo
-    const int tw = threadIdx.x, ty = threadIdx.y;
-    const int xh = (wx > FM_TW) ? 1 : 0;                 // x halo only when the row is wider than one tile
-    const int w0 = (int)blockIdx.x * (TWH - 2 * xh);     // first owned word
-    const int w = w0 - xh + tw;
-    const int y0 = (int)blockIdx.y * rows_own;
-    const int y = y0 - H + ty;
-    const int za = (int)blockIdx.z * zchunk, zb = za + zchunk < nz ? za + zchunk : nz;
-    const bool inv = (w >= 0 && w < wx && y >= 0 && y < ny);             // this thread's column exists
-    const bool own = inv && tw >= xh && tw < TWH - xh && ty >= H && ty < TYH - H && y < y0 + rows_own;
-    const u64 tailmask = (nx & 63) ? ((1ull << (nx & 63)) - 1ull) : ~0ull;
-    const u64 valid = (w == wx - 1) ? tailmask : ~0ull;
-    const int64_t sw = (int64_t)ny * wx;
-    const int64_t col = inv ? (int64_t)y * wx + w : 0;
-    const int tidx = ty * TWH + tw;
-    u64 P[H], L1[H], L2[H];
-#pragma unroll
-    for (int j = 0; j < H; j++) { P[j] = 0; L1[j] = 0; L2[j] = 0; }
-    for (int t = za - H; t < zb + H; t++) {
-        u64 X = (inv && t >= 0 && t < nz) ? in[(int64_t)t * sw + col] : 0ull;   // level 0, slice t
-#pragma unroll
-        for (int j = 0; j < H; j++) {
-            // stage j+1 consumes X = L_j[t - j] and produces L_{j+1}[t - j - 1]
-            const int op = (ops >> j) & 1;
-            const u64 B = op == 0 ? ~0ull : 0ull;
-            const int sX = t - j;
-            const u64 Xe = (sX >= 0 && sX < nz) ? X : B;
-            u64 o = op == 0 ? (P[j] & L2[j] & Xe) : (P[j] | L2[j] | Xe);
-            o &= valid;
-            // in-plane part of slice sX for the next iteration: exchange X with the neighbours
-            u64 *tile = fm_tile + (j & 1) * (TYH * TWH);
-            tile[tidx] = X;
-            __syncthreads();
-            u64 yl = (ty > 0) ? tile[tidx - TWH] : B;
-            u64 yh = (ty < TYH - 1) ? tile[tidx + TWH] : B;
-            u64 pl, ph;
-            if (ROW16) {   // a tile row is exactly one 16-lane DPP row: x neighbours without LDS
-                int lo = (int)(u32)X, hi = (int)(u32)(X >> 32);
-                u32 pll = (u32)__builtin_amdgcn_update_dpp(0, lo, 0x111 /* row_shr:1 */, 0xf, 0xf, false);
-                u32 plh = (u32)__builtin_amdgcn_update_dpp(0, hi, 0x111, 0xf, 0xf, false);
-                u32 phl = (u32)__builtin_amdgcn_update_dpp(0, lo, 0x101 /* row_shl:1 */, 0xf, 0xf, false);
-                u32 phh = (u32)__builtin_amdgcn_update_dpp(0, hi, 0x101, 0xf, 0xf, false);
-                pl = ((u64)plh << 32) | pll;
-                ph = ((u64)phh << 32) | phl;
-            } else {
-                pl = (tw > 0) ? tile[tidx - 1] : B;
-                ph = (tw < TWH - 1) ? tile[tidx + 1] : B;
-            }
-            if (y <= 0) yl = B;
-            if (y >= ny - 1) yh = B;
-            if (w <= 0) pl = B;
-            if (w >= wx - 1) ph = B;
-            L2[j] = L1[j];
-            L1[j] = Xe;
-            P[j] = fm_inplane(op, X, yl, yh, pl, ph, valid);
-            X = o;
-        }
-        const int so = t - H;                               // slice of the final level that just completed
-        if (own && so >= za && so < zb) out[(int64_t)so * sw + col] = X;
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// Barrier-free variant for H <= 4 passes: ONE WAVE owns a whole (x, y) tile cross-section, so no stage needs LDS or a
-// barrier.  Lane = row (64 rows, 64 - 2H owned), registers = a strip of FW_W owned words of that row plus ONE "halo
-// word" whose top 8 bits are the 8 voxels left of the strip and whose low 8 bits the 8 voxels right of it.  The five
-// words form a ring (halo word between the last and the first owned word), which makes every word's x-neighbours the
-// previous / next word of the ring -- uniform code, no edge cases; the unused middle bits of the halo word decay by one
-// bit per pass, exactly like the outer rows of the tile.  y-neighbours are the adjacent lanes (DPP wave shifts),
-// z-neighbours the previous values in registers (same software pipeline along z as above).
-// The block version spends its time in barriers (8 per slice, 16 waves each); this one is pure VALU.
+// ONE WAVE owns a whole (x, y) tile cross-section, so no stage needs LDS or a barrier.  Lane = row (64 rows, 64 - 2H
+// owned), registers = a strip of FW_W owned words of that row plus ONE "halo word" whose top 8 bits are the 8 voxels left
+// of the strip and whose low 8 bits the 8 voxels right of it.  The five words form a ring (halo word between the last and
+// the first owned word), which makes every word's x-neighbours the previous / next word of the ring -- uniform code, no
+// edge cases; the unused middle bits of the halo word decay by one bit per pass, exactly like the outer rows of the tile.
+// y-neighbours are the adjacent lanes (DPP wave shifts), z-neighbours the previous values in registers: pure VALU.
 #define FW_W 4
 
 __device__ static inline u64 dpp_prev_u64(u64 v)
@@ -1732,40 +1603,10 @@ TOMO_API int tomo_morph_fused(const uint64_t *in, uint64_t *out, int nz, int ny,
                               void *stream)
 {
     if (!in || !out || in == out || nz <= 0 || ny <= 0 || nx <= 0) return TOMO_E_ARG;
-    if (nops != 2 && nops != 4 && nops != 6 && nops != 8) return TOMO_E_ARG;
     int wx = (int)tomo_words_per_row(nx);
     if (nops == 2) return morph_wave_launch<2>((const u64 *)in, (u64 *)out, nz, ny, nx, wx, ops, (hipStream_t)stream);
     if (nops == 4) return morph_wave_launch<4>((const u64 *)in, (u64 *)out, nz, ny, nx, wx, ops, (hipStream_t)stream);
-    int xh = wx > FM_TW ? 1 : 0;
-    int TWH = (wx > FM_TW ? FM_TW : wx) + 2 * xh;
-    int TYH = 1024 / TWH;
-    if (TYH > 64) TYH = 64;
-    int rows_own = TYH - 2 * nops;
-    if (rows_own < 4) return TOMO_E_SIZE;
-    if (rows_own > ny) { rows_own = ny; TYH = rows_own + 2 * nops; }
-    int zchunk = nz;
-    // enough blocks to fill the chip: split z
-    int64_t tiles = ceil_div64(wx, TWH - 2 * xh) * ceil_div64(ny, rows_own);
-    while (zchunk > 32 && tiles * ceil_div64(nz, zchunk) < 512) zchunk = (zchunk + 1) / 2;
-    dim3 grid((unsigned)ceil_div64(wx, TWH - 2 * xh), (unsigned)ceil_div64(ny, rows_own), (unsigned)ceil_div64(nz, zchunk));
-    dim3 block((unsigned)TWH, (unsigned)TYH);
-    size_t lds = (size_t)2 * TYH * TWH * sizeof(u64);
-    hipStream_t s = (hipStream_t)stream;
-    switch (nops) {
-    case 2: if (TWH == 16) hipLaunchKernelGGL((morph_fused_kernel<2, true>), grid, block, lds, s, (const u64 *)in, (u64 *)out, nz, ny, nx, wx, ops, rows_own, zchunk);
-        else hipLaunchKernelGGL((morph_fused_kernel<2, false>), grid, block, lds, s, (const u64 *)in, (u64 *)out, nz, ny, nx, wx, ops, rows_own, zchunk);
-        break;
-    case 4: if (TWH == 16) hipLaunchKernelGGL((morph_fused_kernel<4, true>), grid, block, lds, s, (const u64 *)in, (u64 *)out, nz, ny, nx, wx, ops, rows_own, zchunk);
-        else hipLaunchKernelGGL((morph_fused_kernel<4, false>), grid, block, lds, s, (const u64 *)in, (u64 *)out, nz, ny, nx, wx, ops, rows_own, zchunk);
-        break;
-    case 6: if (TWH == 16) hipLaunchKernelGGL((morph_fused_kernel<6, true>), grid, block, lds, s, (const u64 *)in, (u64 *)out, nz, ny, nx, wx, ops, rows_own, zchunk);
-        else hipLaunchKernelGGL((morph_fused_kernel<6, false>), grid, block, lds, s, (const u64 *)in, (u64 *)out, nz, ny, nx, wx, ops, rows_own, zchunk);
-        break;
-    default: if (TWH == 16) hipLaunchKernelGGL((morph_fused_kernel<8, true>), grid, block, lds, s, (const u64 *)in, (u64 *)out, nz, ny, nx, wx, ops, rows_own, zchunk);
-        else hipLaunchKernelGGL((morph_fused_kernel<8, false>), grid, block, lds, s, (const u64 *)in, (u64 *)out, nz, ny, nx, wx, ops, rows_own, zchunk);
-        break;
-    }
-    return tomo_status();
+    return TOMO_E_ARG;
 }
 
 // smooth_voxel_data (voxel_processor.py:79-97) planned here: the request is reduced to its canonical pass list and

@@ -602,12 +602,8 @@ __global__ __launch_bounds__(256) void field_worklist_kernel(const unsigned char
     }
 }
 
-static int ft_sparse_tp()
-{   // tile positions per block of the sparse grid (a multiple of 8 = whole marching-cubes segments)
-    static const int v = getenv("TOMO_SPARSE_TP") ? atoi(getenv("TOMO_SPARSE_TP")) : 16;
-    return v >= 8 && v <= FT_MAXT && v % 8 == 0 ? v : 16;
-}
-#define FT_SPARSE_TP ft_sparse_tp()
+// tile positions per block of the sparse grid (a multiple of 8 = whole marching-cubes segments, at most FT_MAXT)
+static constexpr int FT_SPARSE_TP = 16;
 TOMO_API int64_t tomo_field_span_bytes(int nz, int ny, int nx, int pad)
 {   // span + comb maps, the work list and its counter
     FieldParams p;
@@ -640,15 +636,8 @@ TOMO_API int tomo_field_fill_bits_sparse(const uint64_t *bits, float *field, int
     hipLaunchKernelGGL(field_worklist_kernel, dim3((unsigned)ceil_div64(blocks, 256)), dim3(256), 0, s, (const unsigned char *)comb,
                        p, list, count);
     p.comb = comb; p.list = list; p.count = count;
-    if (getenv("TOMO_EXP_NEAR_DENSE")) p.comb = nullptr;      // experiment: the listed blocks write ALL their tiles
     hipLaunchKernelGGL(field_tile_kernel<true>, dim3((unsigned)blocks), dim3(FT_THREADS), lds, s, (const u32 *)bits, field, p);
     return tomo_status();
-}
-
-TOMO_API int tomo_field_signs_fused(int nx)
-{   // does tomo_field_fill(gaussian = 1) write the sign records itself for this row width?  (always, since ABI 2)
-    (void)nx;
-    return 1;
 }
 
 TOMO_API int64_t tomo_sign_buffer_words(int Nz, int Ny, int Nx, int xorg)

@@ -510,29 +510,6 @@ __device__ static inline u32 find_vertex(u64 okey, int slot, const McGrid &g, co
     return vox_voff[pos] + (u32)__popc(fl & ((1u << slot) - 1u));
 }
 
-// (vertex base << 4 | flags) of the active voxel `okey`, or 0xffffffff if it is not in the list
-__device__ static inline u32 find_owner(u64 okey, const McGrid &g, const u64 *__restrict__ seg_act,
-                                        const u32 *__restrict__ seg_aoff, const u32 *__restrict__ vox_voff,
-                                        const uint8_t *__restrict__ vox_flags, u32 *flags_out)
-{
-    const u64 row = okey >> (KEY_XBITS + 2);
-    const u32 c = ((u32)(okey >> 2) & ((1u << KEY_XBITS) - 1u)) + (u32)g.xorg + SEG_SHIFT;
-    const u64 seg = row * (u64)g.segs_per_row + (c >> 8);
-    const u32 a0 = seg_aoff[seg], a1 = seg_aoff[seg + 1];
-    if (a1 == a0) return 0xffffffffu;
-    const Rec4 r = load_rec(seg_act, (int64_t)seg);
-    const int L = (int)((c & 255u) >> 2), k = (int)(c & 3u);
-    const u64 bk = k == 0 ? r.b[0] : (k == 1 ? r.b[1] : (k == 2 ? r.b[2] : r.b[3]));
-    if (!((bk >> L) & 1ull)) return 0xffffffffu;
-    const u64 m = (1ull << L) - 1ull;
-    u32 rank = (u32)(__popcll(r.b[0] & m) + __popcll(r.b[1] & m) + __popcll(r.b[2] & m) + __popcll(r.b[3] & m));
-    rank += (k > 0 ? (u32)((r.b[0] >> L) & 1ull) : 0u) + (k > 1 ? (u32)((r.b[1] >> L) & 1ull) : 0u) +
-            (k > 2 ? (u32)((r.b[2] >> L) & 1ull) : 0u);
-    const u32 pos = a0 + rank;
-    *flags_out = vox_flags[pos];
-    return vox_voff[pos];
-}
-
 __device__ static inline u32 slot_vertex(u32 base, u32 flags, int slot)
 {   // index of the vertex in `slot` of a voxel whose first vertex is `base`, 0xffffffff if it has none there
     if (base == 0xffffffffu || !(flags & (1u << slot))) return 0xffffffffu;

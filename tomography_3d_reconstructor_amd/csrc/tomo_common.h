@@ -64,10 +64,6 @@ __device__ static inline double dpp_from_next_f64(double v)
     int lo = __double2loint(v), hi = __double2hiint(v);
     return __hiloint2double(dpp_from_next(hi, 0), dpp_from_next(lo, 0));
 }
-__device__ static inline float dpp_from_next_f32(float v)
-{
-    return __int_as_float(dpp_from_next(__float_as_int(v), 0));
-}
 
 // inclusive wave scan (sum) of a u32 across the 64 lanes
 __device__ static inline u32 wave_inclusive_scan(u32 v)

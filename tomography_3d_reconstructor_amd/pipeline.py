@@ -495,7 +495,7 @@ def make_field(vol: BitVolume, manifold: bool = True, add_padding: bool = True, 
     data = torch.empty((Nz, Ny, pitch), dtype=torch.float32, device=vol.device)
     xorg = L.tomo_field_xorg(pad)
     # the field kernel leaves the sign records (marching-cubes pass 1 input) behind as a by-product
-    fused = bool(manifold) and bool(L.tomo_field_signs_fused(nx))
+    fused = bool(manifold)
     signs = None
     sbuf = None
     gcls = None
@@ -504,7 +504,7 @@ def make_field(vol: BitVolume, manifold: bool = True, add_padding: bool = True, 
         sbuf = torch.empty(L.tomo_sign_buffer_words(Nz, Ny, Nx, xorg), dtype=torch.int64, device=vol.device)
         signs = sbuf[: Nz * S * NyP * 4].view(Nz, S, NyP, 4)
         gcls = torch.empty((Nz, NyP // 16, S), dtype=torch.uint8, device=vol.device)
-    is_sparse = bool(manifold and FIELD_FROM_BITS and sparse and fused)
+    is_sparse = bool(manifold and FIELD_FROM_BITS and sparse)
     if is_sparse:
         span = torch.empty(L.tomo_field_span_bytes(nz, ny, nx, pad), dtype=torch.uint8, device=vol.device)
         _lib.check(L.tomo_field_fill_bits_sparse(_p(vol.bits), _p(data), nz, ny, nx, pad, _p(sbuf), _p(gcls), _p(span), _stream()),

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Where does a workgroup of field_tile_kernel spend its time?  Builds a PROFILING copy of the library (-DFT_PROFILE: s_memtime
 stamps per block and phase, tools/scratch/libtomo_prof.so), runs the dense / tile-sparse field fill on the 1024^3 ellipsoid and
-prints per-phase statistics.  usage: fieldprof.py build | run [dense|sparse|near]"""
+prints per-phase statistics.  usage: fieldprof.py build | run [dense|sparse]"""
 import ctypes, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SO = os.path.join(ROOT, "tools", "scratch", "libtomo_prof.so")
@@ -23,8 +23,6 @@ if sys.argv[1] == "build":
     sys.exit(0)
 os.environ["TOMO_LIB"] = SO
 mode = sys.argv[2] if len(sys.argv) > 2 else "dense"
-if mode == "near":
-    os.environ["TOMO_EXP_NEAR_DENSE"] = "1"
 import numpy as np, torch
 sys.path.insert(0, ROOT)
 from tomography_3d_reconstructor_amd import _lib, pipeline
