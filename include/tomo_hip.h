@@ -189,6 +189,40 @@ int tomo_cc_expand(const uint64_t *bits, int nz, int ny, int nx, const uint32_t 
 int tomo_cc_filter(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
                    const uint32_t *rank, const int64_t *sizes, unsigned long long *tot, int64_t min_voxels, int largest,
                    uint64_t *out, void *stream);
+/* Measurements per component of a labelled volume (the run tables of tomo_cc_label_runs; no counterpart in the reference,
+ * whose calculate_voxel_volume_variable_depth / calculate_bounding_box_variable_depth would have to be called on the mask
+ * `labels == c` once per component).  One more pass over the runs, integer atomics only: the same on every run.
+ *   tomo_cc_measure        table int64[cap][10], row c = component c + 1 for c < n = tot[1]: [0] voxels, [1, 2] zmin, zmax,
+ *                          [3, 4] ymin, ymax, [5, 6] xmin, xmax (inclusive indices), [7] sum of z over the voxels, [8] sum of y,
+ *                          [9] sum of x (a run [s, e) adds (e - s) * (s + e - 1) / 2, exact).  An init launch writes every
+ *                          row first (minima: the largest int64, everything else 0), so rows n .. cap - 1 hold that.  n > cap:
+ *                          bit 1 of tot[2] and nothing is measured; a run id outside the tables: bit 2, as above
+ *   tomo_cc_zhist_offsets  the keep rule of tomo_cc_filter on column 0 (largest: the label goes to tot[3]): sel uint8[cap], the
+ *                          first n = 1 for a selected component; off uint64[cap + 1], the first n + 1 = the exclusive scan
+ *                          (64-bit) of zmax - zmin + 1 over the selected ones, 0 for the others; off[n] = tot[4] = the sum,
+ *                          which sizes `hist`; slot uint32[cap], the first n = selected components in front of c; tot[5] =
+ *                          selected components.  cap = rows of the table >= n (else bit 1 of tot[2], nothing is written);
+ *                          blk: 2 * tomo_cc_scan_blocks(cap) words
+ *   tomo_cc_zhist          hist uint64[hist_cap], zeroed here: hist[off[c] + z - zmin[c]] = voxels of selected component c + 1
+ *                          in slice z.  tot[4] > hist_cap: bit 1 of tot[2] and nothing is added; a slice outside the
+ *                          component's box (the bits changed): bit 2
+ *   tomo_cc_zsums          one thread per selected component, its slices in ascending z, w / zc = device float64[nz]:
+ *                          vol += (double)count * w[z], mz += ((double)count * w[z]) * zc[z], sequential, never contracted;
+ *                          out float64[cap_sel][2] row slot[c] = (vol, mz), labels int64[cap_sel] entry slot[c] = c + 1.
+ *                          With w[z] = (mm_x * mm_y) * depth[z], vol is bit for bit volume_calculator.py:23-35 on the mask
+ *                          `labels == c`.  tot[4] > hist_cap or tot[5] > cap_sel: bit 1 of tot[2], nothing is written
+ * TOMO_E_ARG for a null pointer, a non-positive size or min_voxels < 0; TOMO_E_SIZE from 2^31 words, runs, components or
+ * selected components on (2^60 histogram entries). */
+int tomo_cc_measure(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
+                    const uint32_t *rank, unsigned long long *tot, int64_t *table, int64_t cap, void *stream);
+int tomo_cc_zhist_offsets(const int64_t *table, int64_t cap, unsigned long long *tot, int64_t min_voxels, int largest, uint8_t *sel,
+                          uint64_t *off, uint32_t *slot, uint64_t *blk, void *stream);
+int tomo_cc_zhist(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
+                  const uint32_t *rank, unsigned long long *tot, const int64_t *table, int64_t cap, const uint8_t *sel,
+                  const uint64_t *off, uint64_t *hist, int64_t hist_cap, void *stream);
+int tomo_cc_zsums(const int64_t *table, int64_t cap, unsigned long long *tot, const uint8_t *sel, const uint64_t *off,
+                  const uint32_t *slot, const uint64_t *hist, int64_t hist_cap, const double *w, const double *zc, int nz,
+                  double *out, int64_t *labels, int64_t cap_sel, void *stream);
 /* The same across Z-slabs (slab_components.py): rank r labels its slab with the functions above (n_r components); local
  * component c has the global id base_r + c, base_r = n_0 + .. + n_(r-1).  Pieces that touch across a cut are united, the roots
  * (smallest id = the piece with the component's first voxel) numbered in ascending id: scipy's numbering of the whole stack.

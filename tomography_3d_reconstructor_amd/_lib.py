@@ -55,6 +55,10 @@ SIGNATURES = {
     "tomo_cc_label_runs": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
     "tomo_cc_expand": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p]),
     "tomo_cc_filter": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i, _c_p, _c_p]),
+    "tomo_cc_measure": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p]),
+    "tomo_cc_zhist_offsets": (_c_i, [_c_p, _c_i64, _c_p, _c_i64, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p]),
+    "tomo_cc_zhist": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p]),
+    "tomo_cc_zsums": (_c_i, [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_i, _c_p, _c_p, _c_i64, _c_p]),
     "tomo_cc_slice_components": (_c_i, [_c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p]),
     "tomo_cc_seam_union": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p,
                                   _c_p, _c_p]),

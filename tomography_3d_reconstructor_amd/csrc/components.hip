@@ -14,7 +14,8 @@
 // another workgroup: the phases are separate launches.
 //
 // tot (device uint64[8]): [0] runs  [1] components  [2] flags (1: 2^31 runs or more, 2: more runs than the caller's buffers
-// hold, 4: a run id outside the tables -- the bits changed between the calls)  [3] label tomo_cc_filter(largest) kept (0: none).
+// hold, 4: a run id outside the tables -- the bits changed between the calls)  [3] label tomo_cc_filter(largest) kept (0: none)
+// [4] counters of the slice histogram  [5] components tomo_cc_zhist_offsets selected.
 #include "tomo_common.h"
 
 #define CC_THREADS 256
@@ -22,6 +23,7 @@
 #define CC_F_MANY 1ull
 #define CC_F_CAP 2ull
 #define CC_F_RANGE 4ull
+#define CC_COLS 10                   // columns of a row of the measurement table (tomo_cc_measure)
 
 TOMO_API int64_t tomo_cc_scan_blocks(int64_t n)
 {
@@ -505,16 +507,18 @@ TOMO_API int tomo_cc_expand(const uint64_t *bits, int nz, int ny, int nx, const 
 
 // ---------------------------------------------------------------------------------------------- the keep rule
 // one workgroup: tot[3] = label of the largest component with at least min_voxels voxels, the lowest label among equals; 0: none
+// (the size of component c is sizes[STRIDE * c]: 1 for the sizes table, CC_COLS for column 0 of the measurement table)
+template <int STRIDE>
 __global__ __launch_bounds__(1024) void cc_largest_kernel(const unsigned long long *__restrict__ sizes, u64 *tot, int64_t cap,
-                                                          u64 min_voxels)
+                                                          int64_t cap_runs, u64 min_voxels)
 {
     __shared__ u64 bs[16];
     __shared__ u64 bl[16];
     u64 n = tot[1];
-    if (n > (u64)cap || tot[0] > (u64)cap) n = 0;
+    if (n > (u64)cap || tot[0] > (u64)cap_runs) n = 0;
     u64 best = 0, lab = 0;                                  // lab 0: nothing yet
     for (u64 c = threadIdx.x; c < n; c += 1024) {           // ascending labels: a later equal size never replaces
-        const u64 s = sizes[c];
+        const u64 s = sizes[STRIDE * c];
         if (s >= min_voxels && s > 0 && (lab == 0 || s > best)) { best = s; lab = c + 1; }
     }
 #pragma unroll
@@ -589,12 +593,422 @@ TOMO_API int tomo_cc_filter(const uint64_t *bits, int nz, int ny, int nx, const 
     hipStream_t st = (hipStream_t)stream;
     const int64_t nwords = nrows * wx;
     if (largest)
-        hipLaunchKernelGGL(cc_largest_kernel, dim3(1), dim3(1024), 0, st, (const unsigned long long *)sizes, (u64 *)tot, cap_runs,
-                           (u64)min_voxels);
+        hipLaunchKernelGGL(cc_largest_kernel<1>, dim3(1), dim3(1024), 0, st, (const unsigned long long *)sizes, (u64 *)tot, cap_runs,
+                           cap_runs, (u64)min_voxels);
     hipLaunchKernelGGL(cc_filter_kernel<false>, dim3((unsigned)ceil_div64(nwords, CC_THREADS)), dim3(CC_THREADS), 0, st, (const u64 *)bits,
                        nwords, nx, wx, (const u32 *)row_off, (const u64 *)tot, cap_runs, (const u32 *)parent, (const u32 *)rank,
                        (const unsigned long long *)sizes, (u64)min_voxels, largest ? 1 : 0, (const uint8_t *)nullptr, 0u, (u64 *)out,
                        (u64 *)tot + 2);
+    return tomo_status();
+}
+
+// ---------------------------------------------------------------------------------------------- measurements per component
+// table (device int64[cap][CC_COLS]), row c = component c + 1: [0] voxels  [1, 2] zmin, zmax  [3, 4] ymin, ymax  [5, 6] xmin,
+// xmax (inclusive indices)  [7] sum of z over the voxels  [8] sum of y  [9] sum of x.  Every entry is a non-negative integer
+// below 2^63, so the kernels work on it as u64 and the 64-bit unsigned min / max / add atomics keep it exact and the same on
+// every run.  The count of components comes from tot[1]; more than the table's rows: nothing is touched (CC_F_CAP).
+__device__ static inline int64_t cc_ncomp(const u64 *tot, int64_t cap)
+{
+    const u64 n = tot[1];
+    return n > (u64)cap ? 0 : (int64_t)n;
+}
+
+// the minima start at the largest int64 (a memset cannot give that), everything else at 0
+__global__ __launch_bounds__(CC_THREADS) void cc_table_init_kernel(u64 *__restrict__ table, int64_t cap)
+{
+    const int64_t i = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    if (i >= cap * CC_COLS) return;
+    const int col = (int)(i % CC_COLS);
+    table[i] = (col == 1 || col == 3 || col == 5) ? 0x7fffffffffffffffull : 0ull;
+}
+
+// what a thread, or a wave, has added up for ONE component
+struct CcMeasure {
+    u64 vox, sz, sy, sx;
+    u32 z0, z1, y0, y1, x0, x1;
+};
+
+__device__ static inline void cc_measure_flush(u64 *__restrict__ table, u32 c, const CcMeasure &m)
+{
+    u64 *t = table + (int64_t)c * CC_COLS;
+    atomicAdd(t + 0, m.vox);
+    atomicMin(t + 1, (u64)m.z0);
+    atomicMax(t + 2, (u64)m.z1);
+    atomicMin(t + 3, (u64)m.y0);
+    atomicMax(t + 4, (u64)m.y1);
+    atomicMin(t + 5, (u64)m.x0);
+    atomicMax(t + 6, (u64)m.x1);
+    atomicAdd(t + 7, m.sz);
+    atomicAdd(t + 8, m.sy);
+    atomicAdd(t + 9, m.sx);
+}
+
+__device__ static inline u32 wave_min32(u32 v)
+{
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const u32 o = __shfl_xor(v, d, 64);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
+__device__ static inline u32 wave_max32(u32 v)
+{
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const u32 o = __shfl_xor(v, d, 64);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+// One thread per row (z, y) over its runs, as cc_sizes_kernel: a run [s, e) adds len = e - s voxels, len * z, len * y and
+// len * (s + e - 1) / 2 = s + (s + 1) + .. + (e - 1) (len or s + e - 1 is even: exact) and widens the box.  A thread adds up
+// neighbouring runs of one component first; a wave whose lanes all hold the same component adds once (one solid body: ten
+// atomics per 64 rows, whatever slices the rows lie in -- every lane brings its own z and y).
+__global__ __launch_bounds__(CC_THREADS) void cc_measure_kernel(const u64 *__restrict__ bits, int64_t nrows, int ny, int nx, int wx,
+                                                                const u32 *__restrict__ row_off, const u64 *__restrict__ tot,
+                                                                int64_t cap_runs, const u32 *__restrict__ parent,
+                                                                const u32 *__restrict__ rank, u64 *__restrict__ table, int64_t cap,
+                                                                u64 *flags)
+{
+    const int64_t row = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    const u32 nruns = (u32)cc_count(tot, cap_runs);
+    const u32 ncomp = (u32)cc_ncomp(tot, cap);
+    if (row == 0 && tot[1] > (u64)cap) atomicOr((unsigned long long *)flags, CC_F_CAP);
+    u32 comp = 0;                                           // component + 1 the thread is adding up, 0: none
+    CcMeasure m = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (row < nrows) {
+        const u32 z = (u32)(row / ny), y = (u32)(row % ny);
+        m.z0 = m.z1 = z;
+        m.y0 = m.y1 = y;
+        CcRuns a = cc_runs_begin(bits, row, nx, wx);
+        u32 ia = row_off[row];
+        while (a.valid) {
+            if (ia >= nruns) {
+                atomicOr((unsigned long long *)flags, CC_F_RANGE);
+                break;
+            }
+            const u32 c = cc_component(parent, rank, ia) + 1;
+            if (c != comp) {
+                if (m.vox && comp - 1 < ncomp) {
+                    m.sz = m.vox * z;
+                    m.sy = m.vox * y;
+                    cc_measure_flush(table, comp - 1, m);
+                }
+                comp = c;
+                m.vox = m.sx = 0;
+                m.x0 = (u32)a.s;
+            }
+            const u64 len = (u64)(a.e - a.s);
+            m.vox += len;
+            m.sx += len * (u64)(a.s + a.e - 1) / 2;
+            m.x1 = (u32)(a.e - 1);                          // the runs ascend
+            cc_runs_next(a);
+            ia++;
+        }
+        m.sz = m.vox * z;
+        m.sy = m.vox * y;
+    }
+    if (!m.vox) comp = 0;
+    const u32 top = wave_max32(comp);
+    if (top == 0) return;                                   // wave-uniform
+    if (__all(comp == 0 || comp == top)) {
+        const bool has = comp != 0;
+        CcMeasure w;
+        w.vox = wave_sum64(m.vox);
+        w.sz = wave_sum64(has ? m.sz : 0);
+        w.sy = wave_sum64(has ? m.sy : 0);
+        w.sx = wave_sum64(m.sx);
+        w.z0 = wave_min32(has ? m.z0 : ~0u);
+        w.z1 = wave_max32(has ? m.z1 : 0u);
+        w.y0 = wave_min32(has ? m.y0 : ~0u);
+        w.y1 = wave_max32(has ? m.y1 : 0u);
+        w.x0 = wave_min32(has ? m.x0 : ~0u);
+        w.x1 = wave_max32(has ? m.x1 : 0u);
+        if ((threadIdx.x & 63) == 0 && top - 1 < ncomp) cc_measure_flush(table, top - 1, w);
+    } else if (comp != 0 && comp - 1 < ncomp) {
+        cc_measure_flush(table, comp - 1, m);
+    }
+}
+
+TOMO_API int tomo_cc_measure(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                             const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, int64_t *table, int64_t cap,
+                             void *stream)
+{
+    int64_t nrows;
+    int wx;
+    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
+    if (g != TOMO_OK) return g;
+    if (!row_off || !parent || !rank || !tot || !table || cap_runs <= 0 || cap <= 0) return TOMO_E_ARG;
+    if (cap_runs >= ((int64_t)1 << 31) || cap >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(cc_table_init_kernel, dim3((unsigned)ceil_div64(cap * CC_COLS, CC_THREADS)), dim3(CC_THREADS), 0, st,
+                       (u64 *)table, cap);
+    hipLaunchKernelGGL(cc_measure_kernel, dim3((unsigned)ceil_div64(nrows, CC_THREADS)), dim3(CC_THREADS), 0, st, (const u64 *)bits,
+                       nrows, ny, nx, wx, (const u32 *)row_off, (const u64 *)tot, cap_runs, (const u32 *)parent, (const u32 *)rank,
+                       (u64 *)table, cap, (u64 *)tot + 2);
+    return tomo_status();
+}
+
+// ---------------------------------------------------------------------------------------------- voxels per component and slice
+// The volume of a component under per-slice depths needs its voxels PER SLICE.  The selected components (the keep rule of
+// tomo_cc_filter on column 0 of the table) get a segment of zmax - zmin + 1 counters each in one histogram: off = the
+// exclusive scan of the segment lengths, 0-length for the others, in 64 bits (2^31 components of up to 2^31 slices), and
+// slot = the exclusive scan of the selection = the row of a selected component in the compacted results.
+// tot[4] = all counters, tot[5] = selected components.
+__device__ static inline bool cc_selected(const u64 *__restrict__ table, const u64 *__restrict__ tot, int64_t c, u64 min_voxels,
+                                          int largest)
+{
+    return largest ? (u64)c + 1 == tot[3] : table[c * CC_COLS] >= min_voxels;
+}
+
+// length of the segment of component c (0: not selected, or a box that is none)
+__device__ static inline u64 cc_zspan(const u64 *__restrict__ table, const u64 *__restrict__ tot, int64_t c, u64 min_voxels,
+                                      int largest, bool *sel)
+{
+    const u64 z0 = table[c * CC_COLS + 1], z1 = table[c * CC_COLS + 2];
+    *sel = cc_selected(table, tot, c, min_voxels, largest);
+    return *sel && z1 >= z0 ? z1 - z0 + 1 : 0;
+}
+
+__device__ static inline u64 wave_inclusive_scan64(u64 v)
+{
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const u64 o = __shfl_up(v, d, 64);
+        if (lane >= d) v += o;
+    }
+    return v;
+}
+
+// per tile of CC_SCAN_TILE components: blk[b] = its counters, blk[nblk + b] = its selected components; sel[c] on the way
+__global__ __launch_bounds__(CC_THREADS) void cc_zspan_blocksum_kernel(const u64 *__restrict__ table, const u64 *__restrict__ tot,
+                                                                       int64_t cap, u64 min_voxels, int largest,
+                                                                       uint8_t *__restrict__ sel, u64 *__restrict__ blk, int64_t nblk,
+                                                                       u64 *flags)
+{
+    __shared__ u64 wsum[2][CC_THREADS / 64];
+    const int64_t n = cc_ncomp(tot, cap);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && tot[1] > (u64)cap) atomicOr((unsigned long long *)flags, CC_F_CAP);
+    const int64_t i0 = (int64_t)blockIdx.x * CC_SCAN_TILE + 4 * threadIdx.x;
+    u64 span = 0, cnt = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        if (i0 + j < n) {
+            bool s;
+            span += cc_zspan(table, tot, i0 + j, min_voxels, largest, &s);
+            cnt += s ? 1 : 0;
+            sel[i0 + j] = s ? 1 : 0;
+        }
+    }
+    span = wave_sum64(span);
+    cnt = wave_sum64(cnt);
+    if ((threadIdx.x & 63) == 0) {
+        wsum[0][threadIdx.x >> 6] = span;
+        wsum[1][threadIdx.x >> 6] = cnt;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        blk[blockIdx.x] = wsum[0][0] + wsum[0][1] + wsum[0][2] + wsum[0][3];
+        blk[nblk + blockIdx.x] = wsum[1][0] + wsum[1][1] + wsum[1][2] + wsum[1][3];
+    }
+}
+
+// off[c], slot[c] for every c < n and off[n] = all counters (written by the thread that holds component n - 1)
+__global__ __launch_bounds__(CC_THREADS) void cc_zspan_apply_kernel(const u64 *__restrict__ table, const u64 *__restrict__ tot,
+                                                                    int64_t cap, u64 min_voxels, int largest,
+                                                                    const u64 *__restrict__ blk, int64_t nblk, u64 *__restrict__ off,
+                                                                    u32 *__restrict__ slot)
+{
+    __shared__ u64 wsum[2][CC_THREADS / 64];
+    const int64_t n = cc_ncomp(tot, cap);
+    const int64_t i0 = (int64_t)blockIdx.x * CC_SCAN_TILE + 4 * threadIdx.x;
+    u64 x[4], k[4];
+    u64 span = 0, cnt = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        bool s = false;
+        x[j] = i0 + j < n ? cc_zspan(table, tot, i0 + j, min_voxels, largest, &s) : 0;
+        k[j] = s ? 1 : 0;
+        span += x[j];
+        cnt += k[j];
+    }
+    const u64 ispan = wave_inclusive_scan64(span), icnt = wave_inclusive_scan64(cnt);
+    if ((threadIdx.x & 63) == 63) {
+        wsum[0][threadIdx.x >> 6] = ispan;
+        wsum[1][threadIdx.x >> 6] = icnt;
+    }
+    __syncthreads();
+    u64 bspan = 0, bcnt = 0;
+    for (int w = 0; w < (int)(threadIdx.x >> 6); w++) {
+        bspan += wsum[0][w];
+        bcnt += wsum[1][w];
+    }
+    u64 run = blk[blockIdx.x] + bspan + ispan - span, num = blk[nblk + blockIdx.x] + bcnt + icnt - cnt;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        if (i0 + j < n) {
+            off[i0 + j] = run;
+            slot[i0 + j] = (u32)num;
+            if (i0 + j == n - 1) off[n] = run + x[j];
+        }
+        run += x[j];
+        num += k[j];
+    }
+}
+
+TOMO_API int tomo_cc_zhist_offsets(const int64_t *table, int64_t cap, unsigned long long *tot, int64_t min_voxels, int largest,
+                                   uint8_t *sel, uint64_t *off, uint32_t *slot, uint64_t *blk, void *stream)
+{
+    if (!table || !tot || !sel || !off || !slot || !blk || cap <= 0 || min_voxels < 0) return TOMO_E_ARG;
+    if (cap >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
+    hipStream_t st = (hipStream_t)stream;
+    const u64 *t = (const u64 *)table;
+    u64 *tt = (u64 *)tot;
+    const int64_t nblk = ceil_div64(cap, CC_SCAN_TILE);
+    if (largest)                                            // no run table is read here: only the count of components is capped
+        hipLaunchKernelGGL(cc_largest_kernel<CC_COLS>, dim3(1), dim3(1024), 0, st, (const unsigned long long *)t, tt, cap,
+                           (int64_t)0x7fffffffffffffffll, (u64)min_voxels);
+    hipLaunchKernelGGL(cc_zspan_blocksum_kernel, dim3((unsigned)nblk), dim3(CC_THREADS), 0, st, t, (const u64 *)tt, cap,
+                       (u64)min_voxels, largest ? 1 : 0, sel, (u64 *)blk, nblk, tt + 2);
+    hipLaunchKernelGGL(cc_scan1_kernel, dim3(1), dim3(1024), 0, st, (u64 *)blk, nblk, tt + 4, (u64 *)nullptr);
+    hipLaunchKernelGGL(cc_scan1_kernel, dim3(1), dim3(1024), 0, st, (u64 *)blk + nblk, nblk, tt + 5, (u64 *)nullptr);
+    hipLaunchKernelGGL(cc_zspan_apply_kernel, dim3((unsigned)nblk), dim3(CC_THREADS), 0, st, t, (const u64 *)tt, cap, (u64)min_voxels,
+                       largest ? 1 : 0, (const u64 *)blk, nblk, (u64 *)off, (u32 *)slot);
+    return tomo_status();
+}
+
+// hist[off[c] + z - zmin[c]] += voxels: checked against the component's box and the histogram's length before the add
+__device__ static inline void cc_zhist_add(const u64 *__restrict__ table, const u64 *__restrict__ off, u64 *__restrict__ hist,
+                                           u64 total, u32 c, u32 z, u64 count, u64 *flags)
+{
+    const u64 z0 = table[(int64_t)c * CC_COLS + 1], z1 = table[(int64_t)c * CC_COLS + 2];
+    const u64 pos = off[c] + ((u64)z - z0);
+    if (z < z0 || z > z1 || pos >= total) {
+        atomicOr((unsigned long long *)flags, CC_F_RANGE);
+        return;
+    }
+    atomicAdd(hist + pos, count);
+}
+
+// One thread per row, as cc_measure_kernel; only the runs of selected components count.  A wave whose lanes all hold the
+// same component adds once PER SLICE the wave's rows lie in: mostly one, more where the wave straddles slices (ny < 64).
+__global__ __launch_bounds__(CC_THREADS) void cc_zhist_kernel(const u64 *__restrict__ bits, int64_t nrows, int ny, int nx, int wx,
+                                                              const u32 *__restrict__ row_off, const u64 *__restrict__ tot,
+                                                              int64_t cap_runs, const u32 *__restrict__ parent,
+                                                              const u32 *__restrict__ rank, const u64 *__restrict__ table, int64_t cap,
+                                                              const uint8_t *__restrict__ sel, const u64 *__restrict__ off,
+                                                              u64 *__restrict__ hist, int64_t hist_cap, u64 *flags)
+{
+    const int64_t row = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    const u32 nruns = (u32)cc_count(tot, cap_runs);
+    const u64 total = tot[4];
+    const bool fits = total <= (u64)hist_cap;
+    const u32 ncomp = fits ? (u32)cc_ncomp(tot, cap) : 0u;  // a histogram that is too short: nothing is touched
+    if (row == 0 && (!fits || tot[1] > (u64)cap)) atomicOr((unsigned long long *)flags, CC_F_CAP);
+    const u32 z = row < nrows ? (u32)(row / ny) : 0u;
+    u32 comp = 0;                                           // SELECTED component + 1 the thread is adding up, 0: none
+    u64 acc = 0;
+    if (row < nrows) {
+        CcRuns a = cc_runs_begin(bits, row, nx, wx);
+        u32 ia = row_off[row];
+        while (a.valid) {
+            if (ia >= nruns) {
+                atomicOr((unsigned long long *)flags, CC_F_RANGE);
+                break;
+            }
+            u32 c = cc_component(parent, rank, ia) + 1;
+            if (c - 1 >= ncomp || !sel[c - 1]) c = 0;
+            if (c != comp) {
+                if (acc) cc_zhist_add(table, off, hist, total, comp - 1, z, acc, flags);
+                comp = c;
+                acc = 0;
+            }
+            if (c) acc += (u64)(a.e - a.s);
+            cc_runs_next(a);
+            ia++;
+        }
+    }
+    if (!acc) comp = 0;
+    const u32 top = wave_max32(comp);
+    if (top == 0) return;                                   // wave-uniform
+    if (__all(comp == 0 || comp == top)) {
+        const u32 zlo = wave_min32(comp ? z : ~0u), zhi = wave_max32(comp ? z : 0u);
+        for (u32 zz = zlo; zz <= zhi; zz++) {               // wave-uniform bounds: at most 64 slices hold the wave's 64 rows
+            const u64 sum = wave_sum64(comp && z == zz ? acc : 0);
+            if ((threadIdx.x & 63) == 0 && sum) cc_zhist_add(table, off, hist, total, top - 1, zz, sum, flags);
+        }
+    } else if (comp != 0) {
+        cc_zhist_add(table, off, hist, total, comp - 1, z, acc, flags);
+    }
+}
+
+TOMO_API int tomo_cc_zhist(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                           const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const int64_t *table, int64_t cap,
+                           const uint8_t *sel, const uint64_t *off, uint64_t *hist, int64_t hist_cap, void *stream)
+{
+    int64_t nrows;
+    int wx;
+    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
+    if (g != TOMO_OK) return g;
+    if (!row_off || !parent || !rank || !tot || !table || !sel || !off || !hist || cap_runs <= 0 || cap <= 0 || hist_cap <= 0)
+        return TOMO_E_ARG;
+    if (cap_runs >= ((int64_t)1 << 31) || cap >= ((int64_t)1 << 31) || hist_cap >= ((int64_t)1 << 60)) return TOMO_E_SIZE;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(hist, 0, (size_t)hist_cap * sizeof(u64), st) != hipSuccess) return TOMO_E_LAUNCH;
+    hipLaunchKernelGGL(cc_zhist_kernel, dim3((unsigned)ceil_div64(nrows, CC_THREADS)), dim3(CC_THREADS), 0, st, (const u64 *)bits,
+                       nrows, ny, nx, wx, (const u32 *)row_off, (const u64 *)tot, cap_runs, (const u32 *)parent, (const u32 *)rank,
+                       (const u64 *)table, cap, sel, (const u64 *)off, (u64 *)hist, hist_cap, (u64 *)tot + 2);
+    return tomo_status();
+}
+
+// One thread per component; a selected one walks its slices in ascending z: vol += (double)count * w[z] and
+// mz += ((double)count * w[z]) * zc[z], plain sequential float64 (nothing is contracted in this file: -ffp-contract=off), so
+// vol is the float a host loop over the slices of the mask `labels == c` gives -- the slices outside the box add 0.0 there.
+// out[slot[c]] = (vol, mz), labels[slot[c]] = c + 1.
+__global__ __launch_bounds__(CC_THREADS) void cc_zsums_kernel(const u64 *__restrict__ table, const u64 *__restrict__ tot, int64_t cap,
+                                                              const uint8_t *__restrict__ sel, const u64 *__restrict__ off,
+                                                              const u32 *__restrict__ slot, const u64 *__restrict__ hist,
+                                                              int64_t hist_cap, const double *__restrict__ w,
+                                                              const double *__restrict__ zc, int nz, double *__restrict__ out,
+                                                              int64_t *__restrict__ labels, int64_t cap_sel, u64 *flags)
+{
+    const int64_t c = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    const u64 total = tot[4];
+    const bool fits = total <= (u64)hist_cap && tot[5] <= (u64)cap_sel && tot[1] <= (u64)cap;
+    if (c == 0 && !fits) atomicOr((unsigned long long *)flags, CC_F_CAP);
+    if (!fits || c >= cc_ncomp(tot, cap) || !sel[c]) return;
+    const u64 z0 = table[c * CC_COLS + 1], z1 = table[c * CC_COLS + 2], o = off[c];
+    const u32 k = slot[c];
+    if (z1 < z0 || z1 >= (u64)nz || o + (z1 - z0) >= total || (int64_t)k >= cap_sel) {
+        atomicOr((unsigned long long *)flags, CC_F_RANGE);
+        return;
+    }
+    double vol = 0.0, mz = 0.0;
+    for (u64 z = z0; z <= z1; z++) {
+        const double v = (double)hist[o + (z - z0)] * w[z];
+        vol += v;
+        mz += v * zc[z];
+    }
+    out[2 * (int64_t)k] = vol;
+    out[2 * (int64_t)k + 1] = mz;
+    labels[k] = c + 1;
+}
+
+TOMO_API int tomo_cc_zsums(const int64_t *table, int64_t cap, unsigned long long *tot, const uint8_t *sel, const uint64_t *off,
+                           const uint32_t *slot, const uint64_t *hist, int64_t hist_cap, const double *w, const double *zc, int nz,
+                           double *out, int64_t *labels, int64_t cap_sel, void *stream)
+{
+    if (!table || !tot || !sel || !off || !slot || !hist || !w || !zc || !out || !labels || cap <= 0 || hist_cap <= 0 || nz <= 0 ||
+        cap_sel <= 0)
+        return TOMO_E_ARG;
+    if (cap >= ((int64_t)1 << 31) || cap_sel >= ((int64_t)1 << 31) || hist_cap >= ((int64_t)1 << 60)) return TOMO_E_SIZE;
+    hipLaunchKernelGGL(cc_zsums_kernel, dim3((unsigned)ceil_div64(cap, CC_THREADS)), dim3(CC_THREADS), 0, (hipStream_t)stream,
+                       (const u64 *)table, (const u64 *)tot, cap, sel, (const u64 *)off, (const u32 *)slot, (const u64 *)hist, hist_cap,
+                       w, zc, nz, out, labels, cap_sel, (u64 *)tot + 2);
     return tomo_status();
 }
 
@@ -827,8 +1241,8 @@ TOMO_API int tomo_cc_local_maps(const uint32_t *table, const uint32_t *num, cons
     if (n_total >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
     hipStream_t st = (hipStream_t)stream;
     if (keep && largest)
-        hipLaunchKernelGGL(cc_largest_kernel, dim3(1), dim3(1024), 0, st, (const unsigned long long *)sizes, (u64 *)tot, n_total,
-                           (u64)min_voxels);
+        hipLaunchKernelGGL(cc_largest_kernel<1>, dim3(1), dim3(1024), 0, st, (const unsigned long long *)sizes, (u64 *)tot, n_total,
+                           n_total, (u64)min_voxels);
     hipLaunchKernelGGL(cc_local_maps_kernel, dim3((unsigned)ceil_div64(n_local, CC_THREADS)), dim3(CC_THREADS), 0, st,
                        (const u32 *)table, (const u32 *)num, (const unsigned long long *)sizes, (const u64 *)tot, n_total, base, n_local,
                        (u64)min_voxels, largest ? 1 : 0, keep, label, (u64 *)tot + 2);

@@ -22,7 +22,8 @@ from . import _lib
 COUNTERS = dict.fromkeys(("na_hint_hit", "na_hint_miss", "mc3_hint_hit", "mc3_hint_miss", "mc3_sort_fused", "mc3_sort_library",
                           "mc3_exact", "mc3_general_unique", "mc3_degenerate", "components_label", "components_expand",
                           "components_filter", "slab_components_label", "slab_components_seam", "slab_components_merge",
-                          "slab_components_expand", "slab_components_filter", "distance_transform", "distance_offset"), 0)
+                          "slab_components_expand", "slab_components_filter", "distance_transform", "distance_offset",
+                          "components_measure", "components_zhist"), 0)
 NA_HINTS = os.environ.get("TOMO_NA_HINTS", "1") not in ("", "0")   # marching_cubes: launch ahead of the first count download
 _NA_HINT = {}
 LIST_LIMIT = 2 ** 31        # active-voxel list entries / vertices / triangles one pass can index (int32 offsets in mc.hip, mesh.hip);
@@ -236,6 +237,10 @@ def point_cloud(vol: BitVolume, slice_depths, mm_per_pixel_x, mm_per_pixel_y, su
 # ----------------------------------------------------------------------------- connected components
 CONNECTIVITIES = (6, 26)     # generate_binary_structure(3, 1) -- the cross of voxel_processor.py:88,91 -- and (3, 3)
 RUN_LIMIT = 2 ** 31          # run ids are 32-bit in csrc/components.hip
+TABLE_COLUMNS = 10           # voxels, zmin, zmax, ymin, ymax, xmin, xmax, sum z, sum y, sum x (tomo_cc_measure)
+# bytes component_properties may take for the voxels per selected component and slice; one component (at most nz counters) is
+# always granted
+COMPONENT_HIST_BUDGET = 1 << 30
 
 
 class ComponentRuns:
@@ -257,6 +262,7 @@ class ComponentRuns:
         _lib.check(L.tomo_cc_count_runs(*geo, _p(self.row_off), _p(blk), _p(self.tot), st), "tomo_cc_count_runs")
         self.runs = _download(self.tot)[0]                       # the one read that sizes the tables
         self.n = 0
+        self._table = None
         COUNTERS["components_label"] += 1
         if self.runs == 0:
             return
@@ -275,7 +281,7 @@ class ComponentRuns:
 
     def _checked(self):
         """The counters after the work enqueued so far -> n; raises when a guard of the kernels fired."""
-        host = _download(self.tot)
+        host = self.host = _download(self.tot)
         if host[2] or host[0] != self.runs:
             raise _lib.TomoError("component labelling: the run tables do not fit the volume (flags %d)" % host[2])
         self.n = host[1]
@@ -286,6 +292,31 @@ class ComponentRuns:
         if self.runs == 0:
             return torch.zeros(0, dtype=torch.int64, device=self.vol.device)
         return self._sizes[:self._checked()]
+
+    def _measure(self) -> torch.Tensor:
+        """The measurement table, enqueued once per object; its guards are read with the next _checked()."""
+        if self._table is None:
+            dev = self.vol.device
+            n = self._checked() if self.runs else 0
+            if n == 0:
+                self._table = torch.zeros((0, TABLE_COLUMNS), dtype=torch.int64, device=dev)
+            else:
+                nz, ny, nx = self.vol.shape
+                table = torch.empty((n, TABLE_COLUMNS), dtype=torch.int64, device=dev)
+                COUNTERS["components_measure"] += 1
+                _lib.check(_lib.lib().tomo_cc_measure(_p(self.bits), nz, ny, nx, *self._tables(), _p(self.tot), _p(table), n,
+                                                      _stream()), "tomo_cc_measure")
+                self._table = table
+        return self._table
+
+    def table(self) -> torch.Tensor:
+        """Per component 1..n: voxels, zmin, zmax, ymin, ymax, xmin, xmax (inclusive indices), sum of z, of y, of x over its
+        voxels -> int64 (n, 10) device tensor, computed once and kept.  Column 0 is sizes()."""
+        fresh = self._table is None
+        table = self._measure()
+        if fresh and table.shape[0]:
+            self._checked()
+        return table
 
     def labels(self):
         """-> (int32 (nz, ny, nx) device tensor as scipy.ndimage.label returns it, n)."""
@@ -328,6 +359,96 @@ def keep_components(vol: BitVolume, min_voxels=0, largest=False, connectivity=6)
     only the single largest of those, the first in raster order among equals.  `vol` is left untouched; an empty volume
     comes back empty.  Working memory scales with the rows and the runs: no per-voxel label array is made."""
     return ComponentRuns(vol, connectivity).keep(min_voxels, largest)
+
+
+def component_table(vol: BitVolume, connectivity=6) -> torch.Tensor:
+    """scipy.ndimage.find_objects + the sums behind center_of_mass without the label array -> int64 (n, 10) device tensor,
+    row c - 1 for label c: voxels, zmin, zmax, ymin, ymax, xmin, xmax (inclusive), sum of z, sum of y, sum of x."""
+    return ComponentRuns(vol, connectivity).table()
+
+
+@dataclass
+class ComponentProperties:
+    """component_properties' answer: host arrays, one row per selected component in ascending label."""
+    labels: np.ndarray           # int64 (m,)
+    voxels: np.ndarray           # int64 (m,)
+    index_box: np.ndarray        # int64 (m, 6): zmin, zmax, ymin, ymax, xmin, xmax, inclusive
+    index_sums: np.ndarray       # int64 (m, 3): sum of z, y, x over the voxels
+    volume_mm3: np.ndarray       # float64 (m,)
+    centroid_index: np.ndarray   # float64 (m, 3): index_sums / voxels
+    centroid_mm: np.ndarray      # float64 (m, 3): z, y, x in the coordinates of distance_positions
+
+    def __len__(self):
+        return len(self.labels)
+
+
+def _component_properties_from(table, labels, sums, mm_per_pixel_y, mm_per_pixel_x) -> ComponentProperties:
+    """Host arithmetic on the downloaded rows: table int64 (m, 10), sums float64 (m, 2) = (volume, sum of volume * z_mm)."""
+    voxels, isums = table[:, 0], table[:, 7:10]
+    cidx = isums / voxels[:, None]
+    cmm = np.empty((len(labels), 3), dtype=np.float64)
+    cmm[:, 0] = sums[:, 1] / sums[:, 0]
+    cmm[:, 1] = cidx[:, 1] * mm_per_pixel_y
+    cmm[:, 2] = cidx[:, 2] * mm_per_pixel_x
+    return ComponentProperties(labels, voxels.copy(), table[:, 1:7].copy(), isums.copy(), sums[:, 0].copy(), cidx, cmm)
+
+
+def component_properties(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, connectivity=6,
+                         min_voxels=0, largest=False) -> ComponentProperties:
+    """Per component of a resident volume: voxels, index box, index sums, volume in mm^3 under the slice depths, centroid in
+    indices and in millimetres -> ComponentProperties, one row per component with at least min_voxels voxels (largest: only
+    the largest of those, the lowest label among equals -- keep_components' rule), in ascending label.
+    volume_mm3 is the float VolumeCalculator.calculate_voxel_volume_variable_depth returns for the mask `labels == c`: count *
+    ((mm_x * mm_y) * depth) added slice by slice in ascending z.  centroid_mm = (sum of slice volume * zc / volume, sum y /
+    voxels * mm_y, sum x / voxels * mm_x) with zc the slice centres of distance_positions: the coordinates of
+    distance_transform and inscribed_sphere.  slice_depths=None: depth 1.0 per slice.
+    Four host reads (the run count, the counters after the labelling, the histogram's length, the results); working memory
+    scales with the runs, the components and the voxels-per-slice counters of the SELECTED components (one per slice of a
+    component's box; beyond COMPONENT_HIST_BUDGET bytes for more than one component: TomoError) -- never with the voxels."""
+    if connectivity not in CONNECTIVITIES:
+        raise ValueError("connectivity must be 6 or 26")
+    nz, ny, nx = vol.shape
+    zt, _, _ = distance_positions(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x)
+    mm_y, mm_x = float(mm_per_pixel_y), float(mm_per_pixel_x)
+    depth = np.ones(nz) if slice_depths is None else np.asarray(slice_depths, dtype=np.float64).reshape(-1)
+    tables = np.concatenate([(mm_x * mm_y) * depth, zt[1:-1]])
+    min_voxels = max(0, int(min_voxels))
+    none = np.zeros((0, TABLE_COLUMNS), dtype=np.int64)
+    empty = _component_properties_from(none, none[:, 0].copy(), np.zeros((0, 2)), mm_y, mm_x)
+    cr = ComponentRuns(vol, connectivity)
+    table = cr._measure()
+    n = table.shape[0]
+    if n == 0:
+        return empty
+    L, dev, st = _lib.lib(), vol.device, _stream()
+    sel = torch.empty(n, dtype=torch.uint8, device=dev)
+    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    slot = torch.empty(n, dtype=torch.int32, device=dev)
+    blk = torch.empty(2 * L.tomo_cc_scan_blocks(n), dtype=torch.int64, device=dev)
+    _lib.check(L.tomo_cc_zhist_offsets(_p(table), n, _p(cr.tot), min_voxels, int(bool(largest)), _p(sel), _p(off), _p(slot), _p(blk),
+                                       st), "tomo_cc_zhist_offsets")
+    cr._checked()                                               # ... and the guards of the measuring pass
+    total, m = cr.host[4], cr.host[5]
+    if m == 0 or total == 0:
+        return empty
+    if 8 * total > COMPONENT_HIST_BUDGET and m > 1:
+        raise _lib.TomoError("component_properties: %d components selected, their voxels-per-slice counters take %d bytes, more "
+                             "than COMPONENT_HIST_BUDGET (%d): raise min_voxels" % (m, 8 * total, COMPONENT_HIST_BUDGET))
+    hist = torch.empty(total, dtype=torch.int64, device=dev)
+    COUNTERS["components_zhist"] += 1
+    _lib.check(L.tomo_cc_zhist(_p(cr.bits), nz, ny, nx, *cr._tables(), _p(cr.tot), _p(table), n, _p(sel), _p(off), _p(hist), total,
+                               st), "tomo_cc_zhist")
+    tab = torch.from_numpy(tables).to(dev)
+    sums = torch.empty((m, 2), dtype=torch.float64, device=dev)
+    labels = torch.ones(m, dtype=torch.int64, device=dev)       # a valid row for the gather below even where a guard fired
+    _lib.check(L.tomo_cc_zsums(_p(table), n, _p(cr.tot), _p(sel), _p(off), _p(slot), _p(hist), total, _p(tab[:nz]), _p(tab[nz:]), nz,
+                               _p(sums), _p(labels), m, st), "tomo_cc_zsums")
+    rows = table.index_select(0, labels - 1)
+    flags = cr.tot[2:3]
+    host = [t.cpu().numpy() for t in (rows, labels, sums, flags)]
+    if host[3][0]:
+        raise _lib.TomoError("component_properties: the tables do not fit the volume (flags %d)" % host[3][0])
+    return _component_properties_from(host[0], host[1], host[2], mm_y, mm_x)
 
 
 # ----------------------------------------------------------------------------- Euclidean distance in millimetres

@@ -100,6 +100,29 @@ def largest_inscribed_sphere(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_d
             'center_mm': (float(zt[z + 1]), float(yt[y + 1]), float(xt[x + 1]))}
 
 
+def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=6, min_voxels=0, largest=False):
+    """The calculations of the class per connected component (no counterpart in the reference, which would be handed the mask
+    `labels == c` once per component) -> a list of dicts, one per component with at least min_voxels voxels (largest: only the
+    largest of those), in label order: {'label', 'voxels', 'voxel_volume_mm3', 'bounding_box': {'x', 'y', 'z'}, 'dimensions',
+    'centroid_mm': (z, y, x), 'centroid_index': (z, y, x)}.  voxel_volume_mm3, bounding_box and dimensions are the numbers
+    calculate_voxel_volume_variable_depth / calculate_bounding_box_variable_depth return for that mask; centroid_mm is in the
+    coordinates of largest_inscribed_sphere.  voxel_data: the bool (nz, ny, nx) array the other calculations take; anything
+    else is a TypeError -- there is no host path for this one."""
+    if not _on_device(voxel_data):
+        raise TypeError("component_properties needs a bool (nz, ny, nx) array")
+    depths = np.asarray(slice_depths, dtype=np.float64).reshape(-1)
+    p = pipeline.component_properties(to_device_volume(voxel_data), depths, mm_per_pixel_y, mm_per_pixel_x, connectivity,
+                                      min_voxels, largest)
+    out = []
+    for i in range(len(p)):
+        box = box_variable_depth(tuple(p.index_box[i]), mm_per_pixel_x, mm_per_pixel_y, depths)
+        out.append({'label': int(p.labels[i]), 'voxels': int(p.voxels[i]), 'voxel_volume_mm3': float(p.volume_mm3[i]),
+                    'bounding_box': {axis: box[axis] for axis in ('x', 'y', 'z')}, 'dimensions': box['dimensions'],
+                    'centroid_mm': tuple(float(v) for v in p.centroid_mm[i]),
+                    'centroid_index': tuple(float(v) for v in p.centroid_index[i])})
+    return out
+
+
 class VolumeCalculator:
     """Handles volume calculations and object property analysis (reference: volume_calculator.py:10)."""
 
