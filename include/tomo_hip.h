@@ -223,6 +223,35 @@ int tomo_cc_zhist(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *
 int tomo_cc_zsums(const int64_t *table, int64_t cap, unsigned long long *tot, const uint8_t *sel, const uint64_t *off,
                   const uint32_t *slot, const uint64_t *hist, int64_t hist_cap, const double *w, const double *zc, int nz,
                   double *out, int64_t *labels, int64_t cap_sel, void *stream);
+/* Second moments and principal axes per component (no counterpart in the reference).  A set voxel (k, j, i) of component c is a
+ * point mass at p = (zc[k], j * mm_y, i * mm_x) -- the coordinates of the distance transform -- of weight w[k] = (mm_x * mm_y) *
+ * depth[k], the voxel's volume (the table tomo_cc_zsums gets).  W = sum w; centre = sum w p / W; covariance = sum w (p - centre)
+ * (p - centre)^T / W, symmetric 3 x 3 in (z, y, x) order.  Voxels are points: no d^2 / 12 for a voxel's own extent, a plate one
+ * voxel thick has variance 0 across itself.  Principal variances = the eigenvalues, descending; principal axes = the unit
+ * eigenvectors in that order, the component of largest magnitude positive (the first such on a tie); a zero matrix (one voxel)
+ * has variances 0 and the identity.  Tables and selection (sel, off, slot, tot[4], tot[5]) are tomo_cc_zhist_offsets'.
+ *   tomo_cc_moment_hist  mom uint64[6 * hist_cap], zeroed here: mom[6 * (off[c] + z - zmin[c]) + 0 .. 5] = over the voxels of
+ *                        selected component c + 1 in slice z: their number, sum j', sum i', sum j'^2, sum i'^2, sum j' i' with
+ *                        j' = j - ymin[c], i' = i - xmin[c] (the box of tomo_cc_measure).  One pass over the runs, closed forms
+ *                        in 64-bit integers, integer atomics only: the same on every run.  tot[4] > hist_cap: bit 1 of tot[2]
+ *                        and nothing is added; a slice outside the component's box or a voxel in front of its corner (the bits
+ *                        changed): bit 2.  TOMO_E_SIZE where ny * nx * max(ny, nx)^2 >= 2^63: a slice's sum could leave 63 bits
+ *   tomo_cc_moments      one thread per selected component, its slices in ascending z twice, w / zc = device float64[nz],
+ *                        sequential float64, never contracted.  First walk: W by tomo_cc_zsums' very additions (bit for bit its
+ *                        vol), the z moment likewise (centre z = mz / W as there), the first moments about the box corner.
+ *                        Second walk: the six central sums about that centre.  Then a cyclic Jacobi iteration (at most 32
+ *                        sweeps), the sort, the sign rule.  out float64[cap_sel][22] row slot[c] = W, centre z y x in mm,
+ *                        covariance zz zy zx yy yx xx in mm^2, variances (3, clamped at 0), axes (3 rows of 3); labels
+ *                        int64[cap_sel] entry slot[c] = c + 1.  tot[4] > hist_cap or tot[5] > cap_sel: bit 1 of tot[2], nothing
+ *                        is written; a component without a voxel in its segment: bit 2
+ * TOMO_E_ARG for a null pointer, a non-positive size or spacing; TOMO_E_SIZE from 2^31 words, runs, components or selected
+ * components on (2^60 / 6 histogram entries). */
+int tomo_cc_moment_hist(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                        const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const int64_t *table, int64_t cap,
+                        const uint8_t *sel, const uint64_t *off, uint64_t *mom, int64_t hist_cap, void *stream);
+int tomo_cc_moments(const int64_t *table, int64_t cap, unsigned long long *tot, const uint8_t *sel, const uint64_t *off,
+                    const uint32_t *slot, const uint64_t *mom, int64_t hist_cap, const double *w, const double *zc, int nz,
+                    double mm_y, double mm_x, double *out, int64_t *labels, int64_t cap_sel, void *stream);
 /* The same across Z-slabs (slab_components.py): rank r labels its slab with the functions above (n_r components); local
  * component c has the global id base_r + c, base_r = n_0 + .. + n_(r-1).  Pieces that touch across a cut are united, the roots
  * (smallest id = the piece with the component's first voxel) numbered in ascending id: scipy's numbering of the whole stack.

@@ -1,0 +1,229 @@
+"""CPU tier of the per-component second moments: the NumPy helper the GPU tests compare with (component_moments_reference)
+agrees with a literal loop over the voxels and with analysis (a voxelised ellipsoid, a tilted rod), the eigenvalue-gap
+condition that decides which axes the GPU tests compare one by one holds where they rely on it, and the two new entry points
+are declared, bound, exported and check their arguments without a GPU."""
+import ctypes
+import math
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import component_moments_reference as M  # noqa: E402
+import component_props_reference as P  # noqa: E402
+import components_reference as C  # noqa: E402
+from tomography_3d_reconstructor_amd import _lib, pipeline, volume_calculator  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = np.load(os.path.join(ROOT, "tests", "golden", "components.npz"))
+NAMES = [k[len("shape_"):] for k in GOLDEN.files if k.startswith("shape_")]
+# the cases of tests/test_gpu_component_props.py: connectivity 26 where tests/test_gpu_components.py uses it
+GOLDEN_CASES = [(n, 6) for n in NAMES] + [(n, 26) for n in NAMES if n != "noise_090"]
+NEW_SYMBOLS = ("tomo_cc_moment_hist", "tomo_cc_moments")
+MM_X, MM_Y = 0.7, 0.45
+
+
+def depths_for(nz):
+    """Non-uniform, one value repeated (tests/test_gpu_component_props.py)."""
+    d = np.linspace(0.3, 1.7, nz)
+    if nz > 2:
+        d[nz // 2] = d[nz // 2 - 1]
+    return d
+
+
+def literal(v, labels, c, depths, mm_y, mm_x):
+    """The definition, voxel by voxel in Python floats widened to long double: (W, centre, covariance)."""
+    ld = np.longdouble
+    zc = P.slice_centres(depths)
+    pts = []
+    for k in range(v.shape[0]):
+        for j in range(v.shape[1]):
+            for i in range(v.shape[2]):
+                if labels[k, j, i] == c:
+                    pts.append((ld((mm_x * mm_y) * depths[k]), (ld(zc[k]), ld(j) * ld(mm_y), ld(i) * ld(mm_x))))
+    total = sum(w for w, _ in pts)
+    centre = [sum(w * p[a] for w, p in pts) / total for a in range(3)]
+    cov = [[sum(w * (p[a] - centre[a]) * (p[b] - centre[b]) for w, p in pts) / total for b in range(3)] for a in range(3)]
+    return float(total), np.array(centre, dtype=np.float64), np.array(cov, dtype=np.float64)
+
+
+def _tiny():
+    rng = np.random.default_rng(21)
+    blob = rng.random((4, 5, 9)) < 0.6
+    ell = np.zeros((3, 4, 6), dtype=bool)
+    ell[0, 0, 0:5] = ell[0:3, 0, 0] = ell[2, 0:4, 0] = True
+    two = np.zeros((2, 3, 4), dtype=bool)
+    two[0, 0, 0] = two[1, 2, 3] = two[1, 2, 2] = True
+    return {"blob": blob, "ell": ell, "two": two}
+
+
+@pytest.mark.parametrize("name", sorted(_tiny()))
+@pytest.mark.parametrize("conn", C.CONNECTIVITIES)
+def test_helper_is_the_definition_voxel_by_voxel(name, conn):
+    v = _tiny()[name]
+    labels, n, tab = P.measure(v, conn)
+    d = depths_for(v.shape[0])
+    ref = M.moments(labels, tab, d, MM_Y, MM_X)
+    assert ref["labels"].tolist() == list(range(1, n + 1)) and np.array_equal(ref["voxels"], tab[:, 0])
+    # the helper's W is one long-double sum; the product's volume_mm3 is held to component_properties' sequential float64 with ==
+    assert np.allclose(ref["volume_mm3"], P.properties(labels, tab, d, MM_Y, MM_X)["volume_mm3"], rtol=1e-14, atol=0)
+    for c in range(n):
+        total, centre, cov = literal(v, labels, c + 1, d, MM_Y, MM_X)
+        scale = ref["scale2"][c]
+        assert abs(ref["volume_mm3"][c] - total) <= 1e-15 * total
+        assert np.abs(ref["center_of_mass_mm"][c] - centre).max() <= 1e-15 * math.sqrt(scale)
+        assert np.abs(ref["covariance_mm2"][c] - cov).max() <= 1e-15 * scale
+        lam, axes = ref["principal_variances_mm2"][c], ref["principal_axes"][c]
+        assert (np.diff(lam) <= 0).all() and (lam >= 0).all()
+        assert np.abs(axes @ axes.T - np.eye(3)).max() <= 1e-14
+        assert np.abs(axes @ cov @ axes.T - np.diag(lam)).max() <= 1e-14 * scale
+        for a in range(3):
+            assert axes[a, int(np.argmax(np.abs(axes[a])))] > 0
+        assert np.array_equal(ref["ellipsoid_axes_mm"][c], 2.0 * np.sqrt(5.0 * lam))
+    single = np.flatnonzero(tab[:, 0] == 1)
+    for c in single:                                             # one voxel: zeros and the identity
+        assert not ref["covariance_mm2"][c].any() and not ref["principal_variances_mm2"][c].any()
+        assert np.array_equal(ref["principal_axes"][c], np.eye(3))
+    assert name != "two" or conn != 6 or len(single) == 1
+
+
+def test_sign_rule_takes_the_first_of_equal_magnitudes():
+    v = np.array([[-0.6, 0.6, 0.52915], [0.0, -1.0, 0.0], [0.5, 0.5, -0.70711]])
+    assert M.sign_rule(v).tolist() == [[0.6, -0.6, -0.52915], [0.0, 1.0, 0.0], [-0.5, -0.5, 0.70711]]
+
+
+def test_helper_against_analysis_ellipsoid():
+    """A solid ellipsoid of semi-axes (a, b, c) has variances a^2 / 5, b^2 / 5, c^2 / 5: 2 sqrt(5 lambda) gives back its full
+    axes.  The voxelised one of semi-axes (12, 9, 20) gives 40.12, 24.00, 18.04."""
+    v = M.ellipsoid()
+    assert v.shape == (32, 24, 48)
+    labels, n, tab = P.measure(v, 6)
+    assert n == 1
+    ref = M.moments(labels, tab, np.ones(32), 1.0, 1.0)
+    print("ellipsoid axes", ref["ellipsoid_axes_mm"][0].tolist(), "centre", ref["center_of_mass_mm"][0].tolist())
+    assert np.abs(ref["ellipsoid_axes_mm"][0] / np.array([40.0, 24.0, 18.0]) - 1.0).max() <= 0.02
+    assert np.abs(ref["center_of_mass_mm"][0] - np.array([16.0, 11.5, 23.5])).max() <= 1e-12
+    # the longest axis lies along x, the middle one along z, the shortest along y
+    assert np.abs(np.abs(ref["principal_axes"][0]) - np.array([[0, 0, 1], [1, 0, 0], [0, 1, 0]])).max() <= 1e-12
+
+
+def test_helper_against_analysis_rod():
+    v = M.tilted_rod()
+    assert v.shape == (40, 40, 40)
+    labels, n, tab = P.measure(v, 26)
+    assert n == 1
+    ref = M.moments(labels, tab, np.ones(40), 1.0, 1.0)
+    first = ref["principal_axes"][0, 0]
+    print("rod first axis", first.tolist())
+    # along (-0.447, 0, -0.894) = -(1, 0, 2) / sqrt(5) to three digits; the sign rule turns the largest component, x, positive.
+    # Half a unit of the last digit given
+    assert np.abs(first - np.array([1.0, 0.0, 2.0]) / math.sqrt(5.0)).max() <= 5e-4
+    assert first[2] > 0 and ref["principal_variances_mm2"][0, 0] > 50 * ref["principal_variances_mm2"][0, 1]
+
+
+@pytest.mark.parametrize("name", sorted(M.BUILT))
+def test_gap_condition_on_the_built_shapes(name):
+    """Which axes the GPU tests compare one by one with the helper's.  Both gaps hold for every built shape with three
+    distinct variances; the thin ones (a rod along z, two voxels, a row with two voxels off it, one voxel) have two
+    eigenvalues that are 0 or far below GAP * D^2, and exactly their first axis -- none for one voxel -- is pinned."""
+    v = M.BUILT[name]()
+    for conn in C.CONNECTIVITIES:
+        labels, n, tab = P.measure(v, conn)
+        assert n == 1
+        for d in (np.ones(v.shape[0]), depths_for(v.shape[0])):
+            ref = M.moments(labels, tab, d, MM_Y, MM_X)
+            assert tuple(M.axis_pinned(ref)[0].tolist()) == M.PINNED[name], (name, conn, ref["principal_variances_mm2"], ref["scale2"])
+            assert bool(M.gaps_hold(ref)[0]) == all(M.PINNED[name])
+
+
+@pytest.mark.parametrize("name,conn", GOLDEN_CASES)
+def test_gap_condition_on_the_golden_volumes(name, conn):
+    """The cap on the exemption: under the selection min_voxels = AXES_MIN_VOXELS, which the GPU test runs on every golden
+    volume, at least half the selected components have both gaps and so every axis compared."""
+    shape = tuple(int(s) for s in GOLDEN["shape_" + name])
+    labels, n, tab = P.measure(C.unpack(GOLDEN["bits_" + name], shape), conn)
+    for d in (np.ones(shape[0]), depths_for(shape[0])):
+        ref = M.moments(labels, tab, d, MM_Y, MM_X, M.AXES_MIN_VOXELS)
+        m = len(ref["labels"])
+        assert 2 * int(M.gaps_hold(ref).sum()) >= m, (name, conn, m)
+        assert M.axis_pinned(ref)[M.gaps_hold(ref)].all()
+
+
+def test_new_symbols_are_declared_bound_and_exported():
+    text = open(os.path.join(ROOT, "include", "tomo_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    L = ctypes.CDLL(_lib.build())
+    for s in NEW_SYMBOLS:
+        assert re.search(r"\b%s\s*\(" % s, text), s
+        assert s in _lib.SIGNATURES and hasattr(L, s), s
+    assert _lib.lib().tomo_abi_version() == 8                      # additive
+    assert pipeline.COUNTERS["components_moments"] >= 0
+    assert pipeline.MOMENT_SUMS == 6 and pipeline.MOMENT_COLUMNS == 22
+
+
+def test_argument_checks_do_not_need_a_gpu():
+    L = _lib.lib()
+    one = ctypes.c_void_p(8)                                      # never dereferenced: every call below fails its checks first
+    hist = lambda *a: L.tomo_cc_moment_hist(*a)                   # noqa: E731
+    assert hist(None, 4, 4, 4, one, 8, one, one, one, one, 8, one, one, one, 8, None) == -1
+    assert hist(one, 4, 4, 4, one, 8, one, one, one, one, 8, one, one, None, 8, None) == -1
+    assert hist(one, 4, 4, 4, one, 8, one, one, one, one, 8, None, one, one, 8, None) == -1
+    assert hist(one, 4, 4, 4, one, 8, one, one, one, one, 8, one, one, one, 0, None) == -1
+    assert hist(one, 4, 4, -1, one, 8, one, one, one, one, 8, one, one, one, 8, None) == -1
+    assert hist(one, 4, 4, 4, one, 0, one, one, one, one, 8, one, one, one, 8, None) == -1
+    assert hist(one, 4, 4, 4, one, 8, one, one, one, one, 1 << 31, one, one, one, 8, None) == -3
+    assert hist(one, 4, 4, 4, one, 1 << 31, one, one, one, one, 8, one, one, one, 8, None) == -3
+    assert hist(one, 4, 4, 4, one, 8, one, one, one, one, 8, one, one, one, 1 << 60, None) == -3
+    assert hist(one, 1 << 15, 1 << 15, 128, one, 8, one, one, one, one, 8, one, one, one, 8, None) == -3      # 2^31 words
+    # ny * nx * max(ny, nx)^2 >= 2^63: a slice's sum of squares could leave 63 bits.  2^21 * 2^21 * 2^42 = 2^84; one row of
+    # 2^21 voxels is 2^63 exactly, one voxel less is allowed (and fails on the next check, a null pointer)
+    assert hist(one, 1, 1 << 21, 1 << 21, one, 8, one, one, one, one, 8, one, one, one, 8, None) == -3
+    assert hist(one, 1, 1, 1 << 21, one, 8, one, one, one, one, 8, one, one, one, 8, None) == -3
+    assert hist(one, 1, 1, (1 << 21) - 1, None, 8, one, one, one, one, 8, one, one, one, 8, None) == -1
+    mom = lambda *a: L.tomo_cc_moments(*a)                        # noqa: E731
+    assert mom(None, 8, one, one, one, one, one, 8, one, one, 4, 1.0, 1.0, one, one, 8, None) == -1
+    assert mom(one, 8, one, one, one, one, None, 8, one, one, 4, 1.0, 1.0, one, one, 8, None) == -1
+    assert mom(one, 8, one, one, one, one, one, 8, None, one, 4, 1.0, 1.0, one, one, 8, None) == -1
+    assert mom(one, 8, one, one, one, one, one, 8, one, one, 4, 1.0, 1.0, one, None, 8, None) == -1
+    assert mom(one, 0, one, one, one, one, one, 8, one, one, 4, 1.0, 1.0, one, one, 8, None) == -1
+    assert mom(one, 8, one, one, one, one, one, 0, one, one, 4, 1.0, 1.0, one, one, 8, None) == -1
+    assert mom(one, 8, one, one, one, one, one, 8, one, one, 0, 1.0, 1.0, one, one, 8, None) == -1
+    assert mom(one, 8, one, one, one, one, one, 8, one, one, 4, 1.0, 1.0, one, one, 0, None) == -1
+    for bad in (0.0, -1.0, float("nan"), float("inf")):
+        assert mom(one, 8, one, one, one, one, one, 8, one, one, 4, bad, 1.0, one, one, 8, None) == -1
+        assert mom(one, 8, one, one, one, one, one, 8, one, one, 4, 1.0, bad, one, one, 8, None) == -1
+    assert mom(one, 1 << 31, one, one, one, one, one, 8, one, one, 4, 1.0, 1.0, one, one, 8, None) == -3
+    assert mom(one, 8, one, one, one, one, one, 1 << 60, one, one, 4, 1.0, 1.0, one, one, 8, None) == -3
+    assert mom(one, 8, one, one, one, one, one, 8, one, one, 4, 1.0, 1.0, one, one, 1 << 31, None) == -3
+
+
+def test_pipeline_rejects_bad_arguments_before_it_touches_the_device():
+    vol = pipeline.BitVolume(None, (1, 1, 1))
+    with pytest.raises(ValueError):
+        pipeline.component_moments(vol, connectivity=18)
+    vol = pipeline.BitVolume(None, (3, 4, 5))
+    for bad in ([1.0, 1.0], [1.0] * 4, [1.0, 0.0, 1.0], [1.0, float("nan"), 1.0]):
+        with pytest.raises(ValueError):
+            pipeline.component_moments(vol, bad)
+    for kw in ({"mm_per_pixel_y": 0.0}, {"mm_per_pixel_x": -1.0}, {"mm_per_pixel_x": float("inf")}):
+        with pytest.raises(ValueError):
+            pipeline.component_moments(vol, [1.0] * 3, **kw)
+    with pytest.raises(TypeError):
+        volume_calculator.component_properties(np.ones((3, 4, 5), np.uint8), 1.0, 1.0, np.ones(3), shape=True)
+
+
+def test_host_side_of_the_rows():
+    """_component_moments_from: the 22 columns of tomo_cc_moments to the dataclass, the covariance filled symmetrically."""
+    rows = np.arange(44, dtype=np.float64).reshape(2, 22)
+    m = pipeline._component_moments_from(np.array([5, 6]), np.array([1, 3]), rows)
+    assert len(m) == 2 and m.labels.tolist() == [1, 3] and m.voxels.tolist() == [5, 6] and m.volume_mm3.tolist() == [0.0, 22.0]
+    assert m.center_of_mass_mm[0].tolist() == [1.0, 2.0, 3.0]
+    assert m.covariance_mm2[0].tolist() == [[4.0, 5.0, 6.0], [5.0, 7.0, 8.0], [6.0, 8.0, 9.0]]
+    assert m.principal_variances_mm2[1].tolist() == [32.0, 33.0, 34.0]
+    assert m.principal_axes[0].tolist() == [[13.0, 14.0, 15.0], [16.0, 17.0, 18.0], [19.0, 20.0, 21.0]]
+    assert np.array_equal(m.ellipsoid_axes_mm, 2.0 * np.sqrt(5.0 * m.principal_variances_mm2))
+    e = pipeline._component_moments_from(np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros((0, 22)))
+    assert len(e) == 0 and e.covariance_mm2.shape == (0, 3, 3) and e.principal_axes.shape == (0, 3, 3) and e.ellipsoid_axes_mm.shape == (0, 3)

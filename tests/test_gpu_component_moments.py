@@ -1,0 +1,263 @@
+"""GPU tier: per-component second moments and principal axes on the resident bit volume (csrc/components.hip:
+tomo_cc_moment_hist, tomo_cc_moments -> pipeline.component_moments -> volume_calculator.component_properties(shape=True)).
+
+Every result is compared with tests/component_moments_reference.py (NumPy in long double, held against a literal loop over the
+voxels and against analysis by tests/test_component_moments_cpu.py) -- never with a second run of the code under test.  The one
+cross-check against existing code is volume_mm3 == pipeline.component_properties' of the same arguments: the bit-for-bit
+promise.  The volumes: those of tests/golden/components.npz under the connectivities tests/test_gpu_component_props.py uses,
+that file's three built volumes, and the seven of component_moments_reference.BUILT.
+
+Tolerances.  D^2 = the squared diagonal of the component's box in mm, voxel extents included.  The device adds at most 70
+slices in sequential float64: an error of a few nz * 2^-53 of the raw sums, which are bounded by D^2 per unit mass with the
+box corner as the origin (a NumPy model of the device arithmetic stayed below 3.6e-16 D^2 against the helper).  The centre is
+held to 1e-11 D, covariance and variances to 1e-11 D^2: a margin of about 10^4 for the Jacobi iteration and deeper stacks.
+Axes: |V V^T - I| <= 1e-12 and |C v - lambda v| <= 1e-11 D^2 for every component; an axis whose eigenvalue is further than
+GAP * D^2 = 1e-6 D^2 from its neighbours moves by at most |dC| / gap <= 1e-5 and must have dot >= 1 - 1e-9 with the helper's
+(all three axes wherever both gaps hold; of a thin body -- two eigenvalues 0 -- still the first)."""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import component_moments_reference as M  # noqa: E402
+import component_props_reference as P  # noqa: E402
+import components_reference as C  # noqa: E402
+import test_gpu_component_props as T  # noqa: E402  (its volumes, depths_for, reference() and run_fenced)
+from tomography_3d_reconstructor_amd import _devcache, _lib, _memo, pipeline, volume_calculator  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+MM_X, MM_Y = T.MM_X, T.MM_Y
+BUILT = {k: f() for k, f in M.BUILT.items()}
+CASES = T.CASES + [(n, c) for n in BUILT for c in (6, 26)]
+KEYS = ("components_measure", "components_zhist", "components_moments")
+FIELDS = ("labels", "voxels", "volume_mm3", "center_of_mass_mm", "covariance_mm2", "principal_variances_mm2", "principal_axes",
+          "ellipsoid_axes_mm")
+OLD_KEYS = ("label", "voxels", "voxel_volume_mm3", "bounding_box", "dimensions", "centroid_mm", "centroid_index")
+NEW_KEYS = ("center_of_mass_mm", "covariance_mm2", "principal_variances_mm2", "principal_axes", "ellipsoid_axes_mm")
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    return torch.device("cuda:0")
+
+
+def volume(name):
+    if name in BUILT:
+        return BUILT[name], C.pack(BUILT[name])
+    return T.volume(name)
+
+
+def resident(name, dev):
+    v, bits = volume(name)
+    return v, pipeline.BitVolume(torch.from_numpy(bits).to(dev), v.shape)
+
+
+_ref = {}
+
+
+def reference(name, conn):
+    """(labels, n, table) of the helper, computed once per case."""
+    if name not in BUILT:
+        return T.reference(name, conn)
+    if (name, conn) not in _ref:
+        _ref[(name, conn)] = P.measure(BUILT[name], conn)
+    return _ref[(name, conn)]
+
+
+def held(got, ref, what):
+    """A ComponentMoments against the helper's dict; the figures are printed before anything is asserted."""
+    m = len(ref["labels"])
+    for k in FIELDS:
+        g = getattr(got, k)
+        assert g.dtype == ref[k].dtype and g.shape == ref[k].shape, (what, k, g.dtype, g.shape, ref[k].dtype, ref[k].shape)
+    assert np.array_equal(got.labels, ref["labels"]) and np.array_equal(got.voxels, ref["voxels"]), what
+    assert len(got) == m
+    if m == 0:
+        return
+    d2 = ref["scale2"]
+    d1 = np.sqrt(d2)
+    cov, lam, axes = got.covariance_mm2, got.principal_variances_mm2, got.principal_axes
+    centre = (np.abs(got.center_of_mass_mm - ref["center_of_mass_mm"]).max(axis=1) / d1).max()
+    dcov = (np.abs(cov - ref["covariance_mm2"]).max(axis=(1, 2)) / d2).max()
+    dlam = (np.abs(lam - ref["principal_variances_mm2"]).max(axis=1) / d2).max()
+    orth = np.abs(np.einsum("mab,mcb->mac", axes, axes) - np.eye(3)).max()
+    resid = (np.abs(np.einsum("mab,mkb->mka", cov, axes) - lam[:, :, None] * axes).max(axis=(1, 2)) / d2).max()
+    pinned = M.axis_pinned(ref)
+    dots = np.einsum("mkb,mkb->mk", axes, ref["principal_axes"])
+    worst_dot = float((1.0 - dots[pinned]).max()) if pinned.any() else 0.0
+    print("%s: m %d  centre %.2e D  cov %.2e D^2  var %.2e D^2  |VV^T-I| %.2e  |Cv-lv| %.2e D^2  1-dot %.2e over %d axes, "
+          "%d components with both gaps" % (what, m, centre, dcov, dlam, orth, resid, worst_dot, int(pinned.sum()),
+                                            int(M.gaps_hold(ref).sum())))
+    assert centre <= 1e-11 and dcov <= 1e-11 and dlam <= 1e-11, what
+    assert orth <= 1e-12 and resid <= 1e-11, what
+    assert (dots[pinned] >= 1.0 - 1e-9).all(), (what, np.argwhere(pinned & (dots < 1.0 - 1e-9))[:5].tolist())
+    assert np.array_equal(cov, np.transpose(cov, (0, 2, 1))), what
+    assert (lam >= 0).all() and (np.diff(lam, axis=1) <= 0).all(), what
+    lead = np.take_along_axis(axes, np.argmax(np.abs(axes), axis=2)[:, :, None], axis=2)
+    assert (lead > 0).all(), what                               # the sign rule
+    assert np.array_equal(got.ellipsoid_axes_mm, 2.0 * np.sqrt(5.0 * lam)), what
+    one = ref["voxels"] == 1                                    # one voxel: zeros and the identity
+    assert not cov[one].any() and not lam[one].any() and (axes[one] == np.eye(3)).all(), what
+
+
+@pytest.mark.parametrize("name,conn", CASES)
+def test_moments(dev, name, conn):
+    v, vol = resident(name, dev)
+    labels, n, tab = reference(name, conn)
+    nz = v.shape[0]
+    before = vol.bits.clone()
+    selections = [0] if name in BUILT or name in T.BUILT else [0, M.AXES_MIN_VOXELS]
+    for depths, d in ((None, np.ones(nz)), (T.depths_for(nz), T.depths_for(nz))):
+        for min_voxels in selections:
+            ref = M.moments(labels, tab, d, MM_Y, MM_X, min_voxels)
+            got = pipeline.component_moments(vol, depths, MM_Y, MM_X, conn, min_voxels)
+            held(got, ref, "%s/%d depths %s min_voxels %d" % (name, conn, "uniform" if depths is None else "varied", min_voxels))
+            props = pipeline.component_properties(vol, depths, MM_Y, MM_X, conn, min_voxels)
+            assert np.array_equal(got.labels, props.labels) and np.array_equal(got.voxels, props.voxels)
+            assert got.volume_mm3.tobytes() == props.volume_mm3.tobytes()      # bit for bit
+            if len(got):                                                        # the very division of the very operands
+                assert got.center_of_mass_mm[:, 0].tobytes() == props.centroid_mm[:, 0].tobytes()
+            if name in BUILT:
+                pin = M.axis_pinned(ref)
+                assert n == 1 and tuple(pin[0].tolist()) == M.PINNED[name]
+    again = pipeline.component_moments(vol, T.depths_for(nz), MM_Y, MM_X, conn, selections[-1])    # integer atomics: every run alike
+    assert all(getattr(got, k).tobytes() == getattr(again, k).tobytes() for k in FIELDS)
+    assert torch.equal(vol.bits, before), "the input volume was modified"
+
+
+def test_shapes_against_analysis(dev):
+    """The device's own numbers for the two shapes the CPU tier holds the helper to."""
+    _, vol = resident("ellipsoid", dev)
+    got = pipeline.component_moments(vol)
+    print("ellipsoid axes", got.ellipsoid_axes_mm[0].tolist(), "centre", got.center_of_mass_mm[0].tolist())
+    assert len(got) == 1 and np.abs(got.ellipsoid_axes_mm[0] / np.array([40.0, 24.0, 18.0]) - 1.0).max() <= 0.02
+    assert np.abs(got.center_of_mass_mm[0] - np.array([16.0, 11.5, 23.5])).max() <= 1e-11 * np.sqrt(32 ** 2 + 24 ** 2 + 48 ** 2)
+    _, vol = resident("tilted_rod", dev)
+    first = pipeline.component_moments(vol).principal_axes[0, 0]
+    print("rod first axis", first.tolist())
+    assert np.abs(first - np.array([1.0, 0.0, 2.0]) / np.sqrt(5.0)).max() <= 5e-4 and first[2] > 0
+    _, vol = resident("plane", dev)                             # one voxel thick: variance 0 across itself, exactly
+    got = pipeline.component_moments(vol, T.depths_for(5), MM_Y, MM_X)
+    assert got.principal_variances_mm2[0, 2] == 0.0 and got.covariance_mm2[0, 0].tolist() == [0.0, 0.0, 0.0]
+    assert got.principal_axes[0, 2].tolist() == [1.0, 0.0, 0.0]  # no rotation ever touches the normal
+    assert np.abs(got.principal_axes[0] - np.array([[0.0, 0.0, 1.0], [0.0, 1.0, 0.0], [1.0, 0.0, 0.0]])).max() <= 1e-12
+    _, vol = resident("single", dev)
+    got = pipeline.component_moments(vol, T.depths_for(3), MM_Y, MM_X)
+    assert not got.covariance_mm2.any() and not got.principal_variances_mm2.any() and not got.ellipsoid_axes_mm.any()
+    assert got.principal_axes[0].tolist() == np.eye(3).tolist()
+    assert got.center_of_mass_mm[0, 1:].tolist() == [2 * MM_Y, 65 * MM_X]
+
+
+def test_selection(dev):
+    name, conn = "noise_031", 6
+    v, vol = resident(name, dev)
+    labels, n, tab = reference(name, conn)
+    d = T.depths_for(v.shape[0])
+    sizes = tab[:, 0]
+    assert int(np.median(sizes)) == 1                           # most of the noise is specks: a threshold of 2 drops them
+    for min_voxels, largest in [(2, False), (int(sizes.max()), False), (0, True), (2, True)]:
+        ref = M.moments(labels, tab, d, MM_Y, MM_X, min_voxels, largest)
+        assert 0 < len(ref["labels"]) < n
+        held(pipeline.component_moments(vol, d, MM_Y, MM_X, conn, min_voxels, largest), ref, "selection %d %s" % (min_voxels, largest))
+
+
+def test_a_tie_selects_the_first_of_two_equal_cubes(dev):
+    v, vol = resident("tie", dev)
+    labels, n, tab = reference("tie", 6)
+    assert tab[:, 0].tolist() == [1, 27, 27]
+    d = T.depths_for(v.shape[0])
+    got = pipeline.component_moments(vol, d, MM_Y, MM_X, largest=True)
+    assert got.labels.tolist() == [2]
+    held(got, M.moments(labels, tab, d, MM_Y, MM_X, 0, True), "tie")
+    assert pipeline.component_moments(vol, min_voxels=27).labels.tolist() == [2, 3]
+    assert pipeline.component_moments(vol, min_voxels=27, largest=True).labels.tolist() == [2]
+    # a 3 x 3 x 3 cube at unit spacing: variance 2 / 3 along every axis, no covariance
+    unit = pipeline.component_moments(vol, min_voxels=27)
+    assert np.abs(unit.covariance_mm2 - np.eye(3) * (2.0 / 3.0)).max() <= 1e-11 * 27
+    assert np.abs(unit.center_of_mass_mm - np.array([[2.5, 2.0, 4.0], [5.5, 6.0, 61.0]])).max() <= 1e-11 * np.sqrt(27.0)
+
+
+@pytest.mark.parametrize("name,min_voxels", [("empty", 0), ("one_voxel_clear", 0), ("tie", 28), ("noise_031", 1 << 40)])
+def test_nothing_selected_launches_nothing(dev, name, min_voxels):
+    """An empty volume launches nothing beyond the count of the runs.  An empty selection of a volume that has components
+    needs the table the selection reads (one tomo_cc_measure, as in component_properties) and launches neither histogram."""
+    v, vol = resident(name, dev)
+    c0 = dict(pipeline.COUNTERS)
+    for largest in (False, True):
+        got = pipeline.component_moments(vol, T.depths_for(v.shape[0]), MM_Y, MM_X, min_voxels=min_voxels, largest=largest)
+        assert len(got) == 0 and got.labels.dtype == np.int64 and got.voxels.dtype == np.int64
+        assert got.volume_mm3.shape == (0,) and got.center_of_mass_mm.shape == (0, 3) and got.covariance_mm2.shape == (0, 3, 3)
+        assert got.principal_variances_mm2.shape == (0, 3) and got.principal_axes.shape == (0, 3, 3) and got.ellipsoid_axes_mm.shape == (0, 3)
+    changed = {k for k in pipeline.COUNTERS if pipeline.COUNTERS[k] != c0[k]}
+    assert changed == ({"components_label"} if not v.any() else {"components_label", "components_measure"})
+    assert pipeline.COUNTERS["components_label"] == c0["components_label"] + 2
+
+
+def test_the_histogram_budget(dev, monkeypatch):
+    v, vol = resident("noise_big", dev)
+    labels, n, tab = reference("noise_big", 6)
+    d = T.depths_for(v.shape[0])
+    sizes = tab[:, 0]
+    top, second = int(sizes.max()), int(np.sort(sizes)[-2])
+    assert int((sizes == top).sum()) == 1 and second < top
+    monkeypatch.setattr(pipeline, "COMPONENT_HIST_BUDGET", 48)
+    with pytest.raises(_lib.TomoError, match="min_voxels"):
+        pipeline.component_moments(vol, d, MM_Y, MM_X)
+    with pytest.raises(_lib.TomoError, match="min_voxels"):
+        pipeline.component_moments(vol, d, MM_Y, MM_X, min_voxels=second)
+    # one component is always granted, whatever slices it spans
+    held(pipeline.component_moments(vol, d, MM_Y, MM_X, largest=True), M.moments(labels, tab, d, MM_Y, MM_X, 0, True), "budget")
+    held(pipeline.component_moments(vol, d, MM_Y, MM_X, min_voxels=top), M.moments(labels, tab, d, MM_Y, MM_X, top), "budget")
+
+
+def test_volume_calculator_shape(dev):
+    v, _ = volume("stacked")
+    d = T.depths_for(v.shape[0])
+    c0 = dict(pipeline.COUNTERS)
+    plain = volume_calculator.component_properties(v, MM_X, MM_Y, d)
+    assert len(plain) == 2 and all(sorted(g) == sorted(OLD_KEYS) for g in plain)
+    assert pipeline.COUNTERS["components_moments"] == c0["components_moments"]
+    full = volume_calculator.component_properties(v, MM_X, MM_Y, d, shape=True)
+    assert pipeline.COUNTERS["components_moments"] == c0["components_moments"] + 1
+    arrays = pipeline.component_moments(pipeline.BitVolume(torch.from_numpy(C.pack(v)).to(dev), v.shape), d, MM_Y, MM_X)
+    held(arrays, M.moments(*reference("stacked", 6)[::2], d, MM_Y, MM_X), "calculator")
+    assert [g["label"] for g in full] == arrays.labels.tolist()
+    for i, g in enumerate(full):
+        assert sorted(g) == sorted(OLD_KEYS + NEW_KEYS) and {k: g[k] for k in OLD_KEYS} == plain[i]
+        assert g["center_of_mass_mm"] == tuple(arrays.center_of_mass_mm[i].tolist())
+        assert g["covariance_mm2"] == tuple(tuple(r) for r in arrays.covariance_mm2[i].tolist())
+        assert g["principal_variances_mm2"] == tuple(arrays.principal_variances_mm2[i].tolist())
+        assert g["principal_axes"] == tuple(tuple(r) for r in arrays.principal_axes[i].tolist())
+        assert g["ellipsoid_axes_mm"] == tuple(arrays.ellipsoid_axes_mm[i].tolist())
+        assert all(type(x) is float for x in g["ellipsoid_axes_mm"] + g["principal_axes"][0] + g["covariance_mm2"][2])
+    largest = volume_calculator.component_properties(v, MM_X, MM_Y, d, largest=True, shape=True)
+    assert len(largest) == 1 and largest[0] == full[[g["voxels"] for g in full].index(max(g["voxels"] for g in full))]
+    _devcache.clear()
+    _memo.clear()
+
+
+# ------------------------------------------------------------------ fenced, poisoned buffers
+@pytest.mark.parametrize("conn", [26, 6])
+@pytest.mark.parametrize("poison", ["ff", "rand"])
+def test_fenced(dev, poison, conn):
+    """noise_big with min_voxels = 2, as tests/test_gpu_component_props.py::test_fenced: sel, off, slot, the moment sums and the
+    result rows all end in the middle of a tile, where a read past the selection would bring the poison in."""
+    name = "noise_big"
+    v, vol = resident(name, dev)
+    labels, n, tab = reference(name, conn)
+    d = T.depths_for(v.shape[0])
+    exp = M.moments(labels, tab, d, MM_Y, MM_X, 2)
+    exp_largest = M.moments(labels, tab, d, MM_Y, MM_X, 2, True)
+    assert 0 < len(exp["labels"]) < n and n % 1024 != 0 and len(exp["labels"]) % 1024 != 0
+
+    def body(fz):
+        with fz.unchanged(vol.bits):
+            held(pipeline.component_moments(vol, d, MM_Y, MM_X, conn, 2), exp, "fenced")
+            held(pipeline.component_moments(vol, d, MM_Y, MM_X, conn, 2, True), exp_largest, "fenced largest")
+        assert fz.ran("_measure") == 2 and fz.ran("component_moments") >= 2 * 7
+    T.run_fenced(poison, body, "%s/%d" % (name, conn))

@@ -1012,6 +1012,311 @@ TOMO_API int tomo_cc_zsums(const int64_t *table, int64_t cap, unsigned long long
     return tomo_status();
 }
 
+// ---------------------------------------------------------------------------------------------- second moments per component
+// A set voxel (k, j, i) of component c is a point mass at (zc[k], j * mm_y, i * mm_x) of weight w[k] = (mm_x * mm_y) * depth[k].
+// Its second moments need, per slice of the component's box, six integer sums over the slice's voxels of the component, taken
+// about the box corner (j' = j - ymin, i' = i - xmin) to keep them small: N, sum j', sum i', sum j'^2, sum i'^2, sum j' i'.
+// They live in the segments of tomo_cc_zhist_offsets, six words per entry: mom[6 * (off[c] + z - zmin) + k].
+#define CC_MOMS 6                    // sums per component and slice
+#define CC_MOMENT_COLS 22            // doubles per row of tomo_cc_moments' output
+#define CC_JACOBI_SWEEPS 32          // limit of the cyclic Jacobi iteration (a 3 x 3 matrix is done in 5 or 6)
+
+// 0^2 + 1^2 + .. + (n - 1)^2 = (n - 1) n (2 n - 1) / 6; n <= nx, and tomo_cc_moment_hist refuses max(ny, nx)^3 >= 2^63
+__device__ static inline u64 cc_squares_below(u64 n)
+{
+    return (n - 1) * n * (2 * n - 1) / 6;                   // n = 0: the wrapped factor meets a 0
+}
+
+// the six sums of one row from what its runs gave (voxels, sum i', sum i'^2) and the row's j'
+__device__ static inline void cc_moment_row(u64 n, u64 si, u64 sii, u64 jp, u64 (&v)[CC_MOMS])
+{
+    v[0] = n;
+    v[1] = jp * n;
+    v[2] = si;
+    v[3] = jp * jp * n;
+    v[4] = sii;
+    v[5] = jp * si;
+}
+
+// mom[6 * (off[c] + z - zmin[c]) + k] += v[k]: checked against the component's box and the histogram's length before the adds
+__device__ static inline void cc_moment_add(const u64 *__restrict__ table, const u64 *__restrict__ off, u64 *__restrict__ mom,
+                                            u64 total, u32 c, u32 z, const u64 (&v)[CC_MOMS], u64 *flags)
+{
+    const u64 z0 = table[(int64_t)c * CC_COLS + 1], z1 = table[(int64_t)c * CC_COLS + 2];
+    const u64 pos = off[c] + ((u64)z - z0);
+    if (z < z0 || z > z1 || pos >= total) {
+        atomicOr((unsigned long long *)flags, CC_F_RANGE);
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < CC_MOMS; k++)
+        if (v[k]) atomicAdd(mom + CC_MOMS * pos + k, v[k]);
+}
+
+// One thread per row, as cc_zhist_kernel: a run [s, e) of a selected component adds its length and, in closed form, the sums
+// of i' and i'^2 over it; the row supplies the factors j'.  A thread adds up neighbouring runs of one component first; a wave
+// whose lanes all hold the same component adds once PER SLICE the wave's rows lie in.  A voxel in front of the box corner
+// (the bits changed since tomo_cc_measure) is CC_F_RANGE and adds nothing.
+__global__ __launch_bounds__(CC_THREADS) void cc_moment_hist_kernel(const u64 *__restrict__ bits, int64_t nrows, int ny, int nx, int wx,
+                                                                    const u32 *__restrict__ row_off, const u64 *__restrict__ tot,
+                                                                    int64_t cap_runs, const u32 *__restrict__ parent,
+                                                                    const u32 *__restrict__ rank, const u64 *__restrict__ table,
+                                                                    int64_t cap, const uint8_t *__restrict__ sel,
+                                                                    const u64 *__restrict__ off, u64 *__restrict__ mom,
+                                                                    int64_t hist_cap, u64 *flags)
+{
+    const int64_t row = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    const u32 nruns = (u32)cc_count(tot, cap_runs);
+    const u64 total = tot[4];
+    const bool fits = total <= (u64)hist_cap;
+    const u32 ncomp = fits ? (u32)cc_ncomp(tot, cap) : 0u;  // a histogram that is too short: nothing is touched
+    if (row == 0 && (!fits || tot[1] > (u64)cap)) atomicOr((unsigned long long *)flags, CC_F_CAP);
+    const u32 z = row < nrows ? (u32)(row / ny) : 0u, y = row < nrows ? (u32)(row % ny) : 0u;
+    u32 comp = 0;                                           // SELECTED component + 1 the thread is adding up, 0: none
+    u64 x0 = 0, jp = 0;                                     // its box corner in x, the row's j' in its box
+    u64 n = 0, si = 0, sii = 0;
+    u64 v[CC_MOMS];
+    if (row < nrows) {
+        CcRuns a = cc_runs_begin(bits, row, nx, wx);
+        u32 ia = row_off[row];
+        while (a.valid) {
+            if (ia >= nruns) {
+                atomicOr((unsigned long long *)flags, CC_F_RANGE);
+                break;
+            }
+            u32 c = cc_component(parent, rank, ia) + 1;
+            if (c - 1 >= ncomp || !sel[c - 1]) c = 0;
+            if (c != comp) {
+                if (n) {
+                    cc_moment_row(n, si, sii, jp, v);
+                    cc_moment_add(table, off, mom, total, comp - 1, z, v, flags);
+                }
+                comp = c;
+                n = si = sii = 0;
+                if (c) {
+                    const u64 y0 = table[(int64_t)(c - 1) * CC_COLS + 3];
+                    x0 = table[(int64_t)(c - 1) * CC_COLS + 5];
+                    jp = (u64)y - y0;
+                    if ((u64)y < y0) {
+                        atomicOr((unsigned long long *)flags, CC_F_RANGE);
+                        comp = c = 0;
+                    }
+                }
+            }
+            if (c) {
+                if ((u64)a.s < x0) {
+                    atomicOr((unsigned long long *)flags, CC_F_RANGE);
+                } else {
+                    const u64 s = (u64)a.s - x0, e = (u64)a.e - x0, len = e - s;
+                    n += len;
+                    si += len * (s + e - 1) / 2;            // len or s + e - 1 is even: exact
+                    sii += cc_squares_below(e) - cc_squares_below(s);
+                }
+            }
+            cc_runs_next(a);
+            ia++;
+        }
+    }
+    if (!n) comp = 0;
+    const u32 top = wave_max32(comp);
+    if (top == 0) return;                                   // wave-uniform
+    cc_moment_row(n, si, sii, jp, v);
+    if (__all(comp == 0 || comp == top)) {
+        const u32 zlo = wave_min32(comp ? z : ~0u), zhi = wave_max32(comp ? z : 0u);
+        for (u32 zz = zlo; zz <= zhi; zz++) {               // wave-uniform bounds: at most 64 slices hold the wave's 64 rows
+            const bool mine = comp && z == zz;
+            u64 sum[CC_MOMS];
+#pragma unroll
+            for (int k = 0; k < CC_MOMS; k++) sum[k] = wave_sum64(mine ? v[k] : 0);
+            if ((threadIdx.x & 63) == 0 && sum[0]) cc_moment_add(table, off, mom, total, top - 1, zz, sum, flags);
+        }
+    } else if (comp != 0) {
+        cc_moment_add(table, off, mom, total, comp - 1, z, v, flags);
+    }
+}
+
+TOMO_API int tomo_cc_moment_hist(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                                 const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const int64_t *table,
+                                 int64_t cap, const uint8_t *sel, const uint64_t *off, uint64_t *mom, int64_t hist_cap, void *stream)
+{
+    int64_t nrows;
+    int wx;
+    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
+    if (g != TOMO_OK) return g;
+    if (!row_off || !parent || !rank || !tot || !table || !sel || !off || !mom || cap_runs <= 0 || cap <= 0 || hist_cap <= 0)
+        return TOMO_E_ARG;
+    if (cap_runs >= ((int64_t)1 << 31) || cap >= ((int64_t)1 << 31) || hist_cap >= ((int64_t)1 << 60) / CC_MOMS) return TOMO_E_SIZE;
+    const unsigned __int128 side = (unsigned __int128)(ny > nx ? ny : nx);
+    if ((unsigned __int128)ny * (unsigned __int128)nx * side * side >= ((unsigned __int128)1 << 63))
+        return TOMO_E_SIZE;                                 // a slice's sum of j'^2, i'^2 or j' i' could leave 63 bits
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(mom, 0, (size_t)hist_cap * CC_MOMS * sizeof(u64), st) != hipSuccess) return TOMO_E_LAUNCH;
+    hipLaunchKernelGGL(cc_moment_hist_kernel, dim3((unsigned)ceil_div64(nrows, CC_THREADS)), dim3(CC_THREADS), 0, st,
+                       (const u64 *)bits, nrows, ny, nx, wx, (const u32 *)row_off, (const u64 *)tot, cap_runs, (const u32 *)parent,
+                       (const u32 *)rank, (const u64 *)table, cap, sel, (const u64 *)off, (u64 *)mom, hist_cap, (u64 *)tot + 2);
+    return tomo_status();
+}
+
+// One Jacobi rotation of a symmetric 3 x 3 matrix that annihilates a_pq (r = the third index): A <- J^T A J, the eigenvector
+// estimates ep, eq (columns p, q of the accumulated rotations) turn with it.  t is the smaller root, |t| <= 1.
+__device__ static inline void cc_jacobi_rotate(double &app, double &aqq, double &apq, double &arp, double &arq, double (&ep)[3],
+                                               double (&eq)[3])
+{
+    if (apq == 0.0) return;
+    const double theta = (aqq - app) / (2.0 * apq), at = fabs(theta);
+    double t = at > 1e150 ? 0.5 / at : 1.0 / (at + sqrt(at * at + 1.0));
+    if (theta < 0.0) t = -t;
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+    app = app - t * apq;
+    aqq = aqq + t * apq;
+    apq = 0.0;
+    const double rp = arp, rq = arq;
+    arp = c * rp - s * rq;
+    arq = s * rp + c * rq;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const double vp = ep[k], vq = eq[k];
+        ep[k] = c * vp - s * vq;
+        eq[k] = s * vp + c * vq;
+    }
+}
+
+// swap so that the larger eigenvalue comes first; equal ones keep their order
+__device__ static inline void cc_order_pair(double &la, double &lb, double (&ea)[3], double (&eb)[3])
+{
+    if (la < lb) {
+        const double l = la;
+        la = lb;
+        lb = l;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const double e = ea[k];
+            ea[k] = eb[k];
+            eb[k] = e;
+        }
+    }
+}
+
+// the component of largest magnitude positive, the first such on a tie
+__device__ static inline void cc_axis_sign(double (&e)[3])
+{
+    int k = 0;
+    if (fabs(e[1]) > fabs(e[k])) k = 1;
+    if (fabs(e[2]) > fabs(e[k])) k = 2;
+    if (e[k] < 0.0) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) e[j] = 0.0 - e[j];
+    }
+}
+
+// One thread per component, as cc_zsums_kernel; a selected one walks its slices in ascending z twice, plain sequential
+// float64 (nothing is contracted in this file).  First walk: W by cc_zsums_kernel's very additions, the z moment likewise, and
+// the first moments about the box corner (zc[zmin], ymin, xmin).  Second walk: the six central sums about the centre those
+// give.  Then cyclic Jacobi on the 3 x 3 covariance, the eigenvalues sorted descending (clamped at 0), the sign rule.
+// out[slot[c]] = W, centre (z, y, x) in mm, covariance zz zy zx yy yx xx, variances, axes (rows); labels[slot[c]] = c + 1.
+__global__ __launch_bounds__(CC_THREADS) void cc_moments_kernel(const u64 *__restrict__ table, const u64 *__restrict__ tot,
+                                                                int64_t cap, const uint8_t *__restrict__ sel,
+                                                                const u64 *__restrict__ off, const u32 *__restrict__ slot,
+                                                                const u64 *__restrict__ mom, int64_t hist_cap,
+                                                                const double *__restrict__ w, const double *__restrict__ zc, int nz,
+                                                                double mm_y, double mm_x, double *__restrict__ out,
+                                                                int64_t *__restrict__ labels, int64_t cap_sel, u64 *flags)
+{
+    const int64_t c = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    const u64 total = tot[4];
+    const bool fits = total <= (u64)hist_cap && tot[5] <= (u64)cap_sel && tot[1] <= (u64)cap;
+    if (c == 0 && !fits) atomicOr((unsigned long long *)flags, CC_F_CAP);
+    if (!fits || c >= cc_ncomp(tot, cap) || !sel[c]) return;
+    const u64 z0 = table[c * CC_COLS + 1], z1 = table[c * CC_COLS + 2], o = off[c];
+    const u32 k = slot[c];
+    if (z1 < z0 || z1 >= (u64)nz || o + (z1 - z0) >= total || (int64_t)k >= cap_sel) {
+        atomicOr((unsigned long long *)flags, CC_F_RANGE);
+        return;
+    }
+    const u64 *m = mom + CC_MOMS * o;
+    const double zo = zc[z0];
+    double vol = 0.0, mz = 0.0, sz = 0.0, sy = 0.0, sx = 0.0;
+    for (u64 z = z0; z <= z1; z++) {
+        const u64 *s = m + CC_MOMS * (z - z0);
+        const double v = (double)s[0] * w[z];
+        vol += v;
+        mz += v * zc[z];
+        sz += v * (zc[z] - zo);
+        sy += w[z] * (double)s[1];
+        sx += w[z] * (double)s[2];
+    }
+    if (!(vol > 0.0)) {                                     // no voxel arrived in the segment: the bits changed
+        atomicOr((unsigned long long *)flags, CC_F_RANGE);
+        return;
+    }
+    const double cz = sz / vol, cy = sy / vol, cx = sx / vol;    // about the box corner: mm along z, indices in the plane
+    double qzz = 0.0, qzy = 0.0, qzx = 0.0, qyy = 0.0, qyx = 0.0, qxx = 0.0;
+    for (u64 z = z0; z <= z1; z++) {
+        const u64 *s = m + CC_MOMS * (z - z0);
+        const double n = (double)s[0], sj = (double)s[1], si = (double)s[2], sjj = (double)s[3], sii = (double)s[4],
+                     sji = (double)s[5];
+        const double dz = (zc[z] - zo) - cz;
+        const double a = sj - n * cy, b = si - n * cx;      // sums of j' - cy and of i' - cx over the slice
+        qzz += w[z] * (n * dz * dz);
+        qzy += w[z] * (dz * a);
+        qzx += w[z] * (dz * b);
+        qyy += w[z] * ((sjj - cy * sj) - cy * a);
+        qyx += w[z] * ((sji - cy * si) - cx * a);
+        qxx += w[z] * ((sii - cx * si) - cx * b);
+    }
+    double a00 = qzz / vol, a01 = qzy * mm_y / vol, a02 = qzx * mm_x / vol, a11 = qyy * (mm_y * mm_y) / vol,
+           a12 = qyx * (mm_y * mm_x) / vol, a22 = qxx * (mm_x * mm_x) / vol;
+    double *r = out + CC_MOMENT_COLS * (int64_t)k;
+    r[0] = vol;
+    r[1] = mz / vol;
+    r[2] = ((double)table[c * CC_COLS + 3] + cy) * mm_y;
+    r[3] = ((double)table[c * CC_COLS + 5] + cx) * mm_x;
+    r[4] = a00;
+    r[5] = a01;
+    r[6] = a02;
+    r[7] = a11;
+    r[8] = a12;
+    r[9] = a22;
+    double e0[3] = {1.0, 0.0, 0.0}, e1[3] = {0.0, 1.0, 0.0}, e2[3] = {0.0, 0.0, 1.0};
+    for (int sweep = 0; sweep < CC_JACOBI_SWEEPS; sweep++) {
+        const double offd = fabs(a01) + fabs(a02) + fabs(a12);
+        if (offd <= 0x1p-60 * (fabs(a00) + fabs(a11) + fabs(a22))) break;      // also a zero matrix
+        cc_jacobi_rotate(a00, a11, a01, a02, a12, e0, e1);
+        cc_jacobi_rotate(a00, a22, a02, a01, a12, e0, e2);
+        cc_jacobi_rotate(a11, a22, a12, a01, a02, e1, e2);
+    }
+    cc_order_pair(a00, a11, e0, e1);
+    cc_order_pair(a11, a22, e1, e2);
+    cc_order_pair(a00, a11, e0, e1);
+    cc_axis_sign(e0);
+    cc_axis_sign(e1);
+    cc_axis_sign(e2);
+    r[10] = a00 > 0.0 ? a00 : 0.0;
+    r[11] = a11 > 0.0 ? a11 : 0.0;
+    r[12] = a22 > 0.0 ? a22 : 0.0;
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        r[13 + j] = e0[j];
+        r[16 + j] = e1[j];
+        r[19 + j] = e2[j];
+    }
+    labels[k] = c + 1;
+}
+
+TOMO_API int tomo_cc_moments(const int64_t *table, int64_t cap, unsigned long long *tot, const uint8_t *sel, const uint64_t *off,
+                             const uint32_t *slot, const uint64_t *mom, int64_t hist_cap, const double *w, const double *zc, int nz,
+                             double mm_y, double mm_x, double *out, int64_t *labels, int64_t cap_sel, void *stream)
+{
+    if (!table || !tot || !sel || !off || !slot || !mom || !w || !zc || !out || !labels || cap <= 0 || hist_cap <= 0 || nz <= 0 ||
+        cap_sel <= 0 || !(mm_y > 0.0 && mm_y < __builtin_inf()) || !(mm_x > 0.0 && mm_x < __builtin_inf()))
+        return TOMO_E_ARG;                                  // a NaN fails both comparisons
+    if (cap >= ((int64_t)1 << 31) || cap_sel >= ((int64_t)1 << 31) || hist_cap >= ((int64_t)1 << 60) / CC_MOMS) return TOMO_E_SIZE;
+    hipLaunchKernelGGL(cc_moments_kernel, dim3((unsigned)ceil_div64(cap, CC_THREADS)), dim3(CC_THREADS), 0, (hipStream_t)stream,
+                       (const u64 *)table, (const u64 *)tot, cap, sel, (const u64 *)off, (const u32 *)slot, (const u64 *)mom, hist_cap,
+                       w, zc, nz, mm_y, mm_x, out, labels, cap_sel, (u64 *)tot + 2);
+    return tomo_status();
+}
+
 // ---------------------------------------------------------------------------------------------- components across Z-slabs
 // A stack cut along z: rank r labels its slab with the kernels above (n_r components) and local component c gets the global
 // id base_r + c, base_r = n_0 + ... + n_(r-1).  Global ids ascend in (rank, local raster order of the first voxel) = the

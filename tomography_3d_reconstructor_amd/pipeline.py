@@ -23,7 +23,7 @@ COUNTERS = dict.fromkeys(("na_hint_hit", "na_hint_miss", "mc3_hint_hit", "mc3_hi
                           "mc3_exact", "mc3_general_unique", "mc3_degenerate", "components_label", "components_expand",
                           "components_filter", "slab_components_label", "slab_components_seam", "slab_components_merge",
                           "slab_components_expand", "slab_components_filter", "distance_transform", "distance_offset",
-                          "components_measure", "components_zhist"), 0)
+                          "components_measure", "components_zhist", "components_moments"), 0)
 NA_HINTS = os.environ.get("TOMO_NA_HINTS", "1") not in ("", "0")   # marching_cubes: launch ahead of the first count download
 _NA_HINT = {}
 LIST_LIMIT = 2 ** 31        # active-voxel list entries / vertices / triangles one pass can index (int32 offsets in mc.hip, mesh.hip);
@@ -238,9 +238,11 @@ def point_cloud(vol: BitVolume, slice_depths, mm_per_pixel_x, mm_per_pixel_y, su
 CONNECTIVITIES = (6, 26)     # generate_binary_structure(3, 1) -- the cross of voxel_processor.py:88,91 -- and (3, 3)
 RUN_LIMIT = 2 ** 31          # run ids are 32-bit in csrc/components.hip
 TABLE_COLUMNS = 10           # voxels, zmin, zmax, ymin, ymax, xmin, xmax, sum z, sum y, sum x (tomo_cc_measure)
-# bytes component_properties may take for the voxels per selected component and slice; one component (at most nz counters) is
-# always granted
+# bytes component_properties / component_moments may take for the per-slice entries of the selected components (8 bytes an entry
+# for the voxel counts, 48 for the six moment sums); one component (at most nz entries) is always granted
 COMPONENT_HIST_BUDGET = 1 << 30
+MOMENT_SUMS = 6              # uint64 per component and slice: N, sum j', sum i', sum j'^2, sum i'^2, sum j' i' (tomo_cc_moment_hist)
+MOMENT_COLUMNS = 22          # float64 per row of tomo_cc_moments: W, centre (3), covariance (6), variances (3), axes (9)
 
 
 class ComponentRuns:
@@ -449,6 +451,97 @@ def component_properties(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, 
     if host[3][0]:
         raise _lib.TomoError("component_properties: the tables do not fit the volume (flags %d)" % host[3][0])
     return _component_properties_from(host[0], host[1], host[2], mm_y, mm_x)
+
+
+@dataclass
+class ComponentMoments:
+    """component_moments' answer: host arrays, one row per selected component in ascending label; vectors in (z, y, x) order."""
+    labels: np.ndarray                    # int64 (m,)
+    voxels: np.ndarray                    # int64 (m,)
+    volume_mm3: np.ndarray                # float64 (m,): W, bit for bit component_properties' volume_mm3
+    center_of_mass_mm: np.ndarray         # float64 (m, 3)
+    covariance_mm2: np.ndarray            # float64 (m, 3, 3), symmetric
+    principal_variances_mm2: np.ndarray   # float64 (m, 3), descending
+    principal_axes: np.ndarray            # float64 (m, 3, 3): ROWS are the unit eigenvectors in that order
+    ellipsoid_axes_mm: np.ndarray         # float64 (m, 3): 2 sqrt(5 variance)
+
+    def __len__(self):
+        return len(self.labels)
+
+
+def _component_moments_from(voxels, labels, rows) -> ComponentMoments:
+    """Host side of the downloaded rows: rows float64 (m, 22) as tomo_cc_moments writes them."""
+    m = len(labels)
+    cov = np.empty((m, 3, 3), dtype=np.float64)
+    for k, (a, b) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))):
+        cov[:, a, b] = cov[:, b, a] = rows[:, 4 + k]
+    lam = rows[:, 10:13].copy()
+    return ComponentMoments(labels, voxels, rows[:, 0].copy(), rows[:, 1:4].copy(), cov, lam, rows[:, 13:22].reshape(m, 3, 3).copy(),
+                            2.0 * np.sqrt(5.0 * lam))
+
+
+def component_moments(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, connectivity=6,
+                      min_voxels=0, largest=False) -> ComponentMoments:
+    """Second moments and principal axes per component of a resident volume -> ComponentMoments, one row per component the
+    keep rule of component_properties selects (at least min_voxels voxels; largest: only the largest of those, the lowest
+    label among equals), in ascending label.
+    A set voxel (k, j, i) is a point mass at p = (zc[k], j * mm_per_pixel_y, i * mm_per_pixel_x) -- zc the slice centres of
+    distance_positions, the coordinates of distance_transform and inscribed_sphere -- of weight w[k] = (mm_x * mm_y) *
+    depth[k], its volume.  volume_mm3 = W = sum w, bit for bit component_properties' volume_mm3 (the same additions in
+    ascending z).  center_of_mass_mm = sum w p / W: in z it is component_properties' centroid_mm[:, 0]; in y and x it equals
+    centroid_mm only under uniform depths, because that centroid divides by the voxel count in the plane, whatever the
+    slices weigh.  covariance_mm2 = sum w (p - centre)(p - centre)^T / W, symmetric.  Voxels are points: the d^2 / 12 of a
+    voxel's own extent is NOT added, a plate one voxel thick has variance 0 across itself.  principal_variances_mm2: the
+    eigenvalues, descending; principal_axes: the unit eigenvectors as rows in that order, the component of largest magnitude
+    positive (the first such on a tie); one voxel, or any zero matrix, has zeros and the identity.  ellipsoid_axes_mm =
+    2 sqrt(5 variance): the full axes of the solid ellipsoid with the same second moments.  slice_depths=None: depth 1.0.
+    The same four host reads as component_properties; working memory scales with the runs, the components and six sums per
+    slice of the box of every SELECTED component (48 bytes an entry; beyond COMPONENT_HIST_BUDGET bytes for more than one
+    component: TomoError) -- never with the voxels."""
+    if connectivity not in CONNECTIVITIES:
+        raise ValueError("connectivity must be 6 or 26")
+    nz, ny, nx = vol.shape
+    zt, _, _ = distance_positions(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x)
+    mm_y, mm_x = float(mm_per_pixel_y), float(mm_per_pixel_x)
+    depth = np.ones(nz) if slice_depths is None else np.asarray(slice_depths, dtype=np.float64).reshape(-1)
+    tables = np.concatenate([(mm_x * mm_y) * depth, zt[1:-1]])
+    min_voxels = max(0, int(min_voxels))
+    none = np.zeros(0, dtype=np.int64)
+    empty = _component_moments_from(none, none.copy(), np.zeros((0, MOMENT_COLUMNS)))
+    cr = ComponentRuns(vol, connectivity)
+    table = cr._measure()
+    n = table.shape[0]
+    if n == 0:
+        return empty
+    L, dev, st = _lib.lib(), vol.device, _stream()
+    sel = torch.empty(n, dtype=torch.uint8, device=dev)
+    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    slot = torch.empty(n, dtype=torch.int32, device=dev)
+    blk = torch.empty(2 * L.tomo_cc_scan_blocks(n), dtype=torch.int64, device=dev)
+    _lib.check(L.tomo_cc_zhist_offsets(_p(table), n, _p(cr.tot), min_voxels, int(bool(largest)), _p(sel), _p(off), _p(slot), _p(blk),
+                                       st), "tomo_cc_zhist_offsets")
+    cr._checked()                                               # ... and the guards of the measuring pass
+    total, m = cr.host[4], cr.host[5]
+    if m == 0 or total == 0:
+        return empty
+    if 8 * MOMENT_SUMS * total > COMPONENT_HIST_BUDGET and m > 1:
+        raise _lib.TomoError("component_moments: %d components selected, their moment sums per slice take %d bytes, more than "
+                             "COMPONENT_HIST_BUDGET (%d): raise min_voxels" % (m, 8 * MOMENT_SUMS * total, COMPONENT_HIST_BUDGET))
+    mom = torch.empty(MOMENT_SUMS * total, dtype=torch.int64, device=dev)
+    COUNTERS["components_moments"] += 1
+    _lib.check(L.tomo_cc_moment_hist(_p(cr.bits), nz, ny, nx, *cr._tables(), _p(cr.tot), _p(table), n, _p(sel), _p(off), _p(mom),
+                                     total, st), "tomo_cc_moment_hist")
+    tab = torch.from_numpy(tables).to(dev)
+    rows = torch.empty((m, MOMENT_COLUMNS), dtype=torch.float64, device=dev)
+    labels = torch.ones(m, dtype=torch.int64, device=dev)       # a valid row for the gather below even where a guard fired
+    _lib.check(L.tomo_cc_moments(_p(table), n, _p(cr.tot), _p(sel), _p(off), _p(slot), _p(mom), total, _p(tab[:nz]), _p(tab[nz:]), nz,
+                                 mm_y, mm_x, _p(rows), _p(labels), m, st), "tomo_cc_moments")
+    voxels = table[:, 0].index_select(0, labels - 1)
+    flags = cr.tot[2:3]
+    host = [t.cpu().numpy() for t in (voxels, labels, rows, flags)]
+    if host[3][0]:
+        raise _lib.TomoError("component_moments: the tables do not fit the volume (flags %d)" % host[3][0])
+    return _component_moments_from(host[0], host[1], host[2])
 
 
 # ----------------------------------------------------------------------------- Euclidean distance in millimetres

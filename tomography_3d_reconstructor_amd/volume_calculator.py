@@ -100,14 +100,19 @@ def largest_inscribed_sphere(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_d
             'center_mm': (float(zt[z + 1]), float(yt[y + 1]), float(xt[x + 1]))}
 
 
-def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=6, min_voxels=0, largest=False):
+def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=6, min_voxels=0, largest=False,
+                         shape=False):
     """The calculations of the class per connected component (no counterpart in the reference, which would be handed the mask
     `labels == c` once per component) -> a list of dicts, one per component with at least min_voxels voxels (largest: only the
     largest of those), in label order: {'label', 'voxels', 'voxel_volume_mm3', 'bounding_box': {'x', 'y', 'z'}, 'dimensions',
     'centroid_mm': (z, y, x), 'centroid_index': (z, y, x)}.  voxel_volume_mm3, bounding_box and dimensions are the numbers
     calculate_voxel_volume_variable_depth / calculate_bounding_box_variable_depth return for that mask; centroid_mm is in the
-    coordinates of largest_inscribed_sphere.  voxel_data: the bool (nz, ny, nx) array the other calculations take; anything
-    else is a TypeError -- there is no host path for this one."""
+    coordinates of largest_inscribed_sphere.  shape=True: every dict also carries the second moments of the component as a
+    body of point masses, one per voxel, weighted with the voxel's volume (pipeline.component_moments; vectors in (z, y, x)
+    order): 'center_of_mass_mm', 'covariance_mm2' (3 x 3 nested tuples), 'principal_variances_mm2' (descending),
+    'principal_axes' (3 rows, unit vectors in that order) and 'ellipsoid_axes_mm' (the full axes of the solid ellipsoid with
+    the same second moments).  With the default nothing more is launched and the dicts are as before.  voxel_data: the bool
+    (nz, ny, nx) array the other calculations take; anything else is a TypeError -- there is no host path for this one."""
     if not _on_device(voxel_data):
         raise TypeError("component_properties needs a bool (nz, ny, nx) array")
     depths = np.asarray(slice_depths, dtype=np.float64).reshape(-1)
@@ -120,6 +125,15 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
                     'bounding_box': {axis: box[axis] for axis in ('x', 'y', 'z')}, 'dimensions': box['dimensions'],
                     'centroid_mm': tuple(float(v) for v in p.centroid_mm[i]),
                     'centroid_index': tuple(float(v) for v in p.centroid_index[i])})
+    if shape:
+        q = pipeline.component_moments(to_device_volume(voxel_data), depths, mm_per_pixel_y, mm_per_pixel_x, connectivity,
+                                       min_voxels, largest)
+        for i, d in enumerate(out):                              # the same rule on the same volume: the same rows
+            d['center_of_mass_mm'] = tuple(float(v) for v in q.center_of_mass_mm[i])
+            d['covariance_mm2'] = tuple(tuple(float(v) for v in row) for row in q.covariance_mm2[i])
+            d['principal_variances_mm2'] = tuple(float(v) for v in q.principal_variances_mm2[i])
+            d['principal_axes'] = tuple(tuple(float(v) for v in row) for row in q.principal_axes[i])
+            d['ellipsoid_axes_mm'] = tuple(float(v) for v in q.ellipsoid_axes_mm[i])
     return out
 
 

@@ -7,7 +7,12 @@ included: it ends with the results on the host), and the CPU route on the same v
 downloaded (its transfer timed apart), scipy.ndimage.label + find_objects + center_of_mass on it.  The CPU route stops short
 of the volume in mm^3, which would take one pass over the whole array per component.
 
-    python tools/componentpropstime.py [--n 512] [--warmup 2] [--reps 7] [--density 0.25] [--no-scipy] [--out props.json]
+--moments times the second-moment chain on the same volumes and the same labelled tables, in the same run: HIP events around
+tomo_cc_moment_hist (memset + the pass over the runs, six atomics where tomo_cc_zhist issues one) and tomo_cc_moments (one
+thread per component: two walks over its slices and the 3 x 3 Jacobi iteration), a host clock around
+pipeline.component_moments, and moment_hist / zhist as a ratio of the medians.
+
+    python tools/componentpropstime.py [--n 512] [--warmup 2] [--reps 7] [--density 0.25] [--no-scipy] [--moments] [--out props.json]
 """
 import argparse
 import json
@@ -27,8 +32,9 @@ def spread(ms):
     return {"median_ms": round(float(np.median(ms)), 3), "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3)}
 
 
-def device_steps(vol, depths, warmup, reps):
-    """Event times of the four steps for min_voxels = 0 (every component selected) on run tables labelled once."""
+def device_steps(vol, depths, warmup, reps, moments=False):
+    """Event times of the four steps for min_voxels = 0 (every component selected) on run tables labelled once; moments: of
+    the two steps of the second-moment chain as well, on the same tables."""
     nz, ny, nx = vol.shape
     L, dev, st = _lib.lib(), vol.device, _stream()
     cr = pipeline.ComponentRuns(vol)
@@ -55,6 +61,13 @@ def device_steps(vol, depths, warmup, reps):
     steps["zhist"] = lambda: L.tomo_cc_zhist(*geo, *cr._tables(), _p(cr.tot), _p(table), n, _p(sel), _p(off), _p(hist), total, st)
     steps["zsums"] = lambda: L.tomo_cc_zsums(_p(table), n, _p(cr.tot), _p(sel), _p(off), _p(slot), _p(hist), total, _p(tab[:nz]),
                                              _p(tab[nz:]), nz, _p(sums), _p(labels), m, st)
+    if moments:
+        mom = torch.empty(pipeline.MOMENT_SUMS * total, dtype=torch.int64, device=dev)
+        rows = torch.empty((m, pipeline.MOMENT_COLUMNS), dtype=torch.float64, device=dev)
+        steps["moment_hist"] = lambda: L.tomo_cc_moment_hist(*geo, *cr._tables(), _p(cr.tot), _p(table), n, _p(sel), _p(off), _p(mom),
+                                                             total, st)
+        steps["moments"] = lambda: L.tomo_cc_moments(_p(table), n, _p(cr.tot), _p(sel), _p(off), _p(slot), _p(mom), total, _p(tab[:nz]),
+                                                     _p(tab[nz:]), nz, 0.45, 0.7, _p(rows), _p(labels), m, st)
     out = {"runs": cr.runs, "components": n, "selected": m, "hist_entries": total}
     for name, fn in steps.items():
         for _ in range(warmup):
@@ -69,6 +82,8 @@ def device_steps(vol, depths, warmup, reps):
             b.synchronize()
             ms.append(a.elapsed_time(b))
         out[name] = spread(ms)
+    if moments:
+        out["moment_hist_over_zhist"] = round(out["moment_hist"]["median_ms"] / max(out["zhist"]["median_ms"], 1e-3), 2)
     flags = pipeline._download(cr.tot)[2]
     if flags:
         sys.exit("a guard of the kernels fired (flags %d)" % flags)
@@ -120,6 +135,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--density", type=float, default=0.25)
     ap.add_argument("--no-scipy", action="store_true", help="skip the CPU route (tens of seconds per volume at 512^3)")
+    ap.add_argument("--moments", action="store_true", help="time the second-moment chain (tomo_cc_moment_hist, tomo_cc_moments) too")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -135,12 +151,17 @@ def main():
         for name, make in volumes.items():
             vol = pipeline.pack(make())
             row = {"n": n, "volume": name, "set_voxels": int(pipeline.popcount_async(vol).item())}
-            row.update(device_steps(vol, depths, a.warmup, a.reps))
+            row.update(device_steps(vol, depths, a.warmup, a.reps, a.moments))
             torch.cuda.empty_cache()
             row["component_properties_host_to_host"] = host_to_host(
                 lambda: pipeline.component_properties(vol, depths, 0.45, 0.7), a.warmup, a.reps)
             row["component_properties_largest_host_to_host"] = host_to_host(
                 lambda: pipeline.component_properties(vol, depths, 0.45, 0.7, largest=True), a.warmup, a.reps)
+            if a.moments:
+                row["component_moments_host_to_host"] = host_to_host(
+                    lambda: pipeline.component_moments(vol, depths, 0.45, 0.7), a.warmup, a.reps)
+                row["component_moments_largest_host_to_host"] = host_to_host(
+                    lambda: pipeline.component_moments(vol, depths, 0.45, 0.7, largest=True), a.warmup, a.reps)
             if not a.no_scipy:
                 row["cpu_route"] = cpu_route(vol, row["components"])
             del vol
