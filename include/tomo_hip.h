@@ -252,6 +252,37 @@ int tomo_cc_moment_hist(const uint64_t *bits, int nz, int ny, int nx, const uint
 int tomo_cc_moments(const int64_t *table, int64_t cap, unsigned long long *tot, const uint8_t *sel, const uint64_t *off,
                     const uint32_t *slot, const uint64_t *mom, int64_t hist_cap, const double *w, const double *zc, int nz,
                     double mm_y, double mm_x, double *out, int64_t *labels, int64_t cap_sel, void *stream);
+/* Euler number, cavities and handles per component (no counterpart in the reference).  Foreground connectivity k = 6 or 26, the
+ * background has the complementary k' = 32 - k, everything outside the stack is background.  chi under 26: V - E + F - C of the
+ * union of the closed unit cubes of the set voxels; under 6: N0 - N1 + N2 - N3 of the dual complex (voxels, face-adjacent pairs,
+ * 2 x 2 blocks, 2 x 2 x 2 blocks, all set).  Every cell is counted by one voxel (6: its low corner; 26: the raster-first set voxel
+ * incident to it), so the voxels of a component add up to the chi of the mask `labels == c`.  cavities = the components of the
+ * mask's complement under k' that do not reach the outside; handles = 1 - chi + cavities.  Integer atomics only: the same on
+ * every run.
+ *   tomo_cc_euler          euler int64[cap], zeroed here: euler[c] = chi of component c + 1 for c < n = tot[1], one pass over the
+ *                          rows with word-wide ANDs / ORs and popcounts under the masks of the runs.  parent == NULL: no table is
+ *                          read (row_off, rank and tot may be NULL) and euler[0] = chi of the whole volume.  n > cap: bit 1 of
+ *                          tot[2] and nothing is added; a run id outside the tables: bit 2
+ *   tomo_cc_complement     out (!= bits) = ~bits inside the stack, the bits at x >= nx clear: the background as a bit volume
+ *   tomo_cc_cavities       bg_* = the run tables, counters and measurement table (tomo_cc_measure, bg_cap rows) of the complement
+ *                          labelled under k'; bg_cap_runs = 0: the volume is full, no bg_* is read.  A background component
+ *                          whose box touches no face of the stack is a cavity of the component that holds the voxel left of the
+ *                          cavity's first run.  topo int64[cap][3], every row written: (euler[c], cavities, handles) for c < n,
+ *                          zeros behind.  A table that does not fit its counters: bit 1 of tot[2]; a left neighbour that is clear
+ *                          or outside the tables: bit 2.  bg_tot is only read
+ *   tomo_cc_topology_rows  out int64[cap_sel][5] row slot[c] = (c + 1, voxels, euler, cavities, handles) for the components
+ *                          tomo_cc_zhist_offsets selected (sel, slot, tot[5]); tot[5] > cap_sel: bit 1 of tot[2], nothing is written
+ * TOMO_E_ARG for a null pointer, a non-positive size or a connectivity other than 6 / 26; TOMO_E_SIZE from 2^31 words, runs or
+ * components on. */
+int tomo_cc_euler(const uint64_t *bits, int nz, int ny, int nx, int connectivity, const uint32_t *row_off, int64_t cap_runs,
+                  const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, int64_t *euler, int64_t cap, void *stream);
+int tomo_cc_complement(const uint64_t *bits, int nz, int ny, int nx, uint64_t *out, void *stream);
+int tomo_cc_cavities(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
+                     const uint32_t *rank, unsigned long long *tot, int64_t cap, const uint64_t *bg_bits, const uint32_t *bg_row_off,
+                     int64_t bg_cap_runs, const uint32_t *bg_parent, const uint32_t *bg_rank, const unsigned long long *bg_tot,
+                     const int64_t *bg_table, int64_t bg_cap, const int64_t *euler, int64_t *topo, void *stream);
+int tomo_cc_topology_rows(const int64_t *table, const int64_t *topo, int64_t cap, unsigned long long *tot, const uint8_t *sel,
+                          const uint32_t *slot, int64_t *out, int64_t cap_sel, void *stream);
 /* The same across Z-slabs (slab_components.py): rank r labels its slab with the functions above (n_r components); local
  * component c has the global id base_r + c, base_r = n_0 + .. + n_(r-1).  Pieces that touch across a cut are united, the roots
  * (smallest id = the piece with the component's first voxel) numbered in ascending id: scipy's numbering of the whole stack.

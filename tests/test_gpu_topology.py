@@ -1,0 +1,262 @@
+"""GPU tier: Euler number, cavities and handles on the resident bit volume (csrc/components.hip: tomo_cc_euler,
+tomo_cc_complement, tomo_cc_cavities, tomo_cc_topology_rows -> pipeline.euler_number / ComponentRuns.topology /
+component_topology / volume_topology -> volume_calculator.component_properties(..., topology=True)).
+
+Every result is compared with tests/topology_reference.py -- the definitions in NumPy on SciPy's labelling (or the NumPy
+labelling where SciPy does not import), held to hand values and to tests/golden/topology.npz by tests/test_topology_cpu.py --
+never with a second run of the code under test.  Everything is an integer and compared with ==."""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import component_props_reference as P  # noqa: E402
+import components_reference as C  # noqa: E402
+import fenced as F  # noqa: E402
+import topology_reference as T  # noqa: E402
+from tomography_3d_reconstructor_amd import _devcache, _lib, _memo, pipeline, volume_calculator  # noqa: E402
+from tomography_3d_reconstructor_amd.pipeline import _p, _stream  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = np.load(os.path.join(ROOT, "tests", "golden", "topology.npz"))
+FIXTURES = T.fixtures()
+CASES = [(name, conn) for name in FIXTURES for conn in C.CONNECTIVITIES]
+KEYS = ("components_euler", "components_cavities")
+FIELDS = ("labels", "voxels", "euler", "cavities", "handles")
+MM_X, MM_Y = 0.7, 0.45
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    return torch.device("cuda:0")
+
+
+def resident(name, dev):
+    """The BitVolume of a case, uploaded as bits: the kernels under test are the only ones that run."""
+    v = FIXTURES[name]
+    return v, pipeline.BitVolume(torch.from_numpy(C.pack(v)).to(dev), v.shape)
+
+
+_ref = {}
+
+
+def reference(name, conn):
+    """(labels, n, topology table, sizes) of the helper, computed once per case and held against the golden file."""
+    if (name, conn) not in _ref:
+        labels, n, tab = T.components(FIXTURES[name], conn)
+        assert np.array_equal(tab, GOLDEN["topo%d_%s" % (conn, name)]) and int(GOLDEN["chi%d_%s" % (conn, name)]) == int(tab[:, 0].sum())
+        _ref[(name, conn)] = (labels, n, tab, C.sizes(labels, n))
+    return _ref[(name, conn)]
+
+
+def same(got, labels, sizes, tab, what):
+    """A ComponentTopology against the helper's rows for `labels` (1-based, ascending)."""
+    exp = {"labels": labels, "voxels": sizes[labels - 1], "euler": tab[labels - 1, 0], "cavities": tab[labels - 1, 1],
+           "handles": tab[labels - 1, 2]}
+    for k in FIELDS:
+        g, e = getattr(got, k), np.asarray(exp[k], dtype=np.int64)
+        assert g.dtype == np.int64 and g.shape == e.shape, (what, k, g.dtype, g.shape, e.shape)
+        assert np.array_equal(g, e), (what, k, g.tolist()[:8], e.tolist()[:8])
+
+
+@pytest.mark.parametrize("name,conn", CASES)
+def test_every_column_equals_the_reference(dev, name, conn):
+    """Every fixture under both connectivities: the table, the dataclass, the whole-volume Euler number from the unlabelled
+    pass and the volume's dict."""
+    v, vol = resident(name, dev)
+    _, n, tab, sizes = reference(name, conn)
+    before = vol.bits.clone()
+    got = pipeline.ComponentRuns(vol, conn).topology()
+    assert got.dtype == torch.int64 and tuple(got.shape) == (n, 3) and got.device == vol.device
+    assert np.array_equal(got.cpu().numpy(), tab), (got.cpu().numpy()[:8].tolist(), tab[:8].tolist())
+    a = pipeline.component_topology(vol, conn)
+    same(a, np.arange(1, n + 1, dtype=np.int64), sizes, tab, name)
+    b = pipeline.component_topology(vol, conn)                    # the integer atomics: every run alike
+    assert all(getattr(a, k).tobytes() == getattr(b, k).tobytes() for k in FIELDS)
+    chi = pipeline.euler_number(vol, conn)
+    assert isinstance(chi, int) and chi == int(tab[:, 0].sum()) == T.euler(v, conn)
+    whole = pipeline.volume_topology(vol, conn)
+    assert whole == T.volume(tab) and all(isinstance(x, int) for x in whole.values())
+    assert whole["euler"] == whole["components"] - whole["handles"] + whole["cavities"] == chi
+    assert torch.equal(vol.bits, before), "the input volume was modified"
+
+
+def test_the_hand_values(dev):
+    """The table of the textbook bodies, read off the device."""
+    def rows(name, conn):
+        return pipeline.ComponentRuns(resident(name, dev)[1], conn).topology().cpu().tolist()
+    for conn in (6, 26):
+        assert rows("ball", conn) == [[1, 0, 0]] and rows("shell", conn) == [[2, 1, 0]] and rows("torus", conn) == [[0, 0, 1]]
+        assert rows("nested", conn) == [[2, 1, 0]] * 2            # the shell and the island with its own void
+        assert rows("open_void", conn) == [[1, 0, 0]]            # a void open to a face of the stack is no cavity
+        assert rows("full", conn) == [[1, 0, 0]] and rows("one_voxel", conn) == [[1, 0, 0]] and rows("empty", conn) == []
+        assert rows("cavity_at_64", conn) == [[2, 1, 0]]
+    assert rows("corner_pair", 6) == [[1, 0, 0]] * 2 and rows("corner_pair", 26) == [[1, 0, 0]]
+    assert rows("diamond", 6) == [[1, 0, 0]] * 4 and rows("diamond", 26) == [[0, 0, 1]]
+    assert rows("pierced_cube", 6) == [[1, 0, 0]] and rows("pierced_cube", 26) == [[2, 1, 0]]
+    v, vol = resident("noise_080", dev)
+    assert pipeline.volume_topology(vol, 6)["handles"] == 232
+    w = pipeline.volume_topology(vol, 26)
+    assert (w["cavities"], w["handles"]) == (133, 11)
+
+
+def test_an_empty_volume_gives_empty_arrays(dev):
+    v, vol = resident("empty", dev)
+    c0 = dict(pipeline.COUNTERS)
+    t = pipeline.component_topology(vol, 26)
+    assert len(t) == 0 and all(getattr(t, k).shape == (0,) and getattr(t, k).dtype == np.int64 for k in FIELDS)
+    assert pipeline.volume_topology(vol) == {"components": 0, "cavities": 0, "handles": 0, "euler": 0}
+    assert tuple(pipeline.ComponentRuns(vol).topology().shape) == (0, 3)
+    assert all(pipeline.COUNTERS[k] == c0[k] for k in KEYS)      # nothing was launched beyond the count of the runs
+    assert pipeline.euler_number(vol) == 0 and pipeline.euler_number(vol, 26) == 0
+    assert volume_calculator.component_properties(v, MM_X, MM_Y, np.ones(v.shape[0]), topology=True) == []
+    _devcache.clear()
+
+
+def selections(sizes):
+    return [(0, False), (int(np.median(sizes)), False), (2, False), (int(sizes.max()) + 1, False), (0, True), (2, True)]
+
+
+@pytest.mark.parametrize("name,conn", [("noise_030", 6), ("noise_050", 6), ("noise_030", 26), ("straddle", 26), ("nested", 6)])
+def test_selected_rows_are_those_of_component_properties(dev, name, conn):
+    v, vol = resident(name, dev)
+    _, n, tab, sizes = reference(name, conn)
+    for min_voxels, largest in selections(sizes):
+        pick = P.selected(sizes, min_voxels, largest).astype(np.int64) + 1
+        props = pipeline.component_properties(vol, connectivity=conn, min_voxels=min_voxels, largest=largest)
+        got = pipeline.component_topology(vol, conn, min_voxels, largest)
+        assert np.array_equal(got.labels, props.labels) and np.array_equal(got.voxels, props.voxels)
+        same(got, pick, sizes, tab, (name, conn, min_voxels, largest))
+
+
+@pytest.mark.parametrize("name,conn", [("nested", 6), ("noise_080", 26), ("straddle", 26)])
+def test_volume_calculator_dicts(dev, name, conn):
+    v, _ = resident(name, dev)
+    _, n, tab, sizes = reference(name, conn)
+    d = np.linspace(0.3, 1.7, v.shape[0])
+    c0 = dict(pipeline.COUNTERS)
+    plain = volume_calculator.component_properties(v, MM_X, MM_Y, d, conn)
+    assert all(pipeline.COUNTERS[k] == c0[k] for k in KEYS), "topology=False launched the topology kernels"
+    assert all(not {"euler_number", "cavities", "handles"} & set(g) for g in plain)
+    got = volume_calculator.component_properties(v, MM_X, MM_Y, d, conn, topology=True)
+    assert all(pipeline.COUNTERS[k] == c0[k] + 1 for k in KEYS)
+    assert [g["label"] for g in got] == list(range(1, n + 1))
+    for g, p in zip(got, plain):
+        assert sorted(g) == sorted(list(p) + ["euler_number", "cavities", "handles"])
+        assert all(g[k] == p[k] for k in p)
+        assert all(type(g[k]) is int for k in ("euler_number", "cavities", "handles"))
+        assert [g["euler_number"], g["cavities"], g["handles"]] == tab[g["label"] - 1].tolist()
+    both = volume_calculator.component_properties(v, MM_X, MM_Y, d, conn, 2, True, shape=True, topology=True)
+    pick = P.selected(sizes, 2, True)
+    assert [g["label"] for g in both] == (pick + 1).tolist()
+    for g in both:
+        assert "principal_axes" in g and [g["euler_number"], g["cavities"], g["handles"]] == tab[g["label"] - 1].tolist()
+    _devcache.clear()
+    _memo.clear()
+
+
+def test_the_topology_is_computed_once(dev):
+    _, vol = resident("noise_050", dev)
+    runs = pipeline.ComponentRuns(vol, 6)
+    c0 = dict(pipeline.COUNTERS)
+    a = runs.topology()
+    assert runs.topology() is a and all(pipeline.COUNTERS[k] == c0[k] + 1 for k in KEYS)
+    assert pipeline.COUNTERS["components_label"] == c0["components_label"] + 1           # the complement, labelled once
+    assert np.array_equal(a.cpu().numpy(), reference("noise_050", 6)[2])
+    c1 = dict(pipeline.COUNTERS)
+    pipeline.euler_number(vol)
+    assert pipeline.COUNTERS["components_euler"] == c1["components_euler"] + 1
+    assert pipeline.COUNTERS["components_label"] == c1["components_label"], "euler_number labelled the volume"
+
+
+def test_the_guards_flag_instead_of_writing_outside_a_table(dev):
+    """A table one row short of its counter: bit 1 of the flags and nothing is added.  Bits that do not go with the tables (the
+    complement in place of the volume, so that the voxel left of a cavity is clear): bit 2 and nothing is attributed."""
+    L, st = _lib.lib(), _stream()
+    v, vol = resident("noise_030", dev)
+    cr = pipeline.ComponentRuns(vol, 6)
+    n = cr._checked()
+    assert n == 293
+    geo = (_p(cr.bits), *v.shape)
+    euler = torch.full((n,), 77, dtype=torch.int64, device=dev)
+    _lib.check(L.tomo_cc_euler(*geo, 6, *cr._tables(), _p(cr.tot), _p(euler), n - 1, st), "tomo_cc_euler")
+    assert pipeline._download(cr.tot)[2] == 2
+    assert euler[:n - 1].eq(0).all() and int(euler[n - 1]) == 77
+    with pytest.raises(_lib.TomoError):
+        cr._checked()
+
+    v, vol = resident("noise_080", dev)
+    tab = reference("noise_080", 26)[2]
+    for short, wrong_bits, flag in ((1, False, 2), (0, True, 4), (0, False, 0)):
+        cr = pipeline.ComponentRuns(vol, 26)
+        n = cr._checked()
+        geo = (_p(cr.bits), *v.shape)
+        euler = torch.empty(n, dtype=torch.int64, device=dev)
+        _lib.check(L.tomo_cc_euler(*geo, 26, *cr._tables(), _p(cr.tot), _p(euler), n, st), "tomo_cc_euler")
+        outside = torch.empty_like(cr.bits)
+        _lib.check(L.tomo_cc_complement(*geo, _p(outside), st), "tomo_cc_complement")
+        assert np.array_equal(C.unpack(outside.cpu().numpy(), v.shape), ~v) and np.array_equal(outside.cpu().numpy(), C.pack(~v))
+        bg = pipeline.ComponentRuns(pipeline.BitVolume(outside, v.shape), 6)
+        bg_table = bg.table()
+        m = bg_table.shape[0]
+        assert m > 133
+        topo = torch.full((n, 3), 77, dtype=torch.int64, device=dev)
+        bits = outside if wrong_bits else cr.bits
+        _lib.check(L.tomo_cc_cavities(_p(bits), *v.shape, *cr._tables(), _p(cr.tot), n, _p(outside), _p(bg.row_off), bg.runs,
+                                      _p(bg.parent), _p(bg.rank), _p(bg.tot), _p(bg_table), m - short, _p(euler), _p(topo), st),
+                   "tomo_cc_cavities")
+        assert pipeline._download(cr.tot)[2] == flag and pipeline._download(bg.tot)[2] == 0
+        got = topo.cpu().numpy()
+        assert np.array_equal(got[:, 0], tab[:, 0])
+        if flag:
+            assert got[:, 1].tolist() == [0] * n and np.array_equal(got[:, 2], 1 - tab[:, 0])
+        else:
+            assert np.array_equal(got, tab)
+
+
+# ------------------------------------------------------------------ fenced, poisoned buffers
+def run_fenced(poison, body, name):
+    def once(p):
+        _devcache.clear()
+        with F.fenced(p, F.package_modules(), seed=7) as fz:
+            body(fz)
+            fz.check()
+            assert fz.total > 0, "nothing was allocated through the harness"
+    try:
+        once(poison)
+    except AssertionError as e:
+        try:
+            once("zero")
+            control = "the zero control PASSES: the failure is a read of memory nobody wrote"
+        except AssertionError as z:
+            control = "the zero control fails too (%s): not a matter of the poison" % (str(z).splitlines() or [""])[0][:200]
+        raise AssertionError("%s\n[%s] %s (%s)" % (e, poison, control, name)) from e
+
+
+@pytest.mark.parametrize("conn", [26, 6])
+@pytest.mark.parametrize("poison", ["ff", "rand"])
+def test_fenced(dev, poison, conn):
+    """The noise volumes (hundreds of components under 6, 133 cavities under 26 -- every table ends in the middle of a tile)
+    and the sponge (more than one workgroup of rows) inside fenced, poisoned buffers."""
+    names = ("noise_030", "noise_080", "sponge")
+    vols = {name: resident(name, dev)[1] for name in names}
+    refs = {name: reference(name, conn) for name in names}
+
+    def body(fz):
+        for name in names:
+            vol = vols[name]
+            _, n, tab, sizes = refs[name]
+            with fz.unchanged(vol.bits):
+                assert np.array_equal(pipeline.ComponentRuns(vol, conn).topology().cpu().numpy(), tab)
+                same(pipeline.component_topology(vol, conn, 2), P.selected(sizes, 2).astype(np.int64) + 1, sizes, tab, "fenced")
+                same(pipeline.component_topology(vol, conn, 0, True), P.selected(sizes, 0, True).astype(np.int64) + 1, sizes, tab,
+                     "fenced largest")
+                assert pipeline.euler_number(vol, conn) == int(tab[:, 0].sum())
+        assert fz.ran("topology") >= 3 * 3 * 3 and fz.ran("component_topology") >= 3 * 2 * 5 and fz.ran("euler_number") == 3
+    run_fenced(poison, body, "noise/%d" % conn)

@@ -63,6 +63,11 @@ SIGNATURES = {
                                    _c_p]),
     "tomo_cc_moments": (_c_i, [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_i, _c_d, _c_d, _c_p, _c_p, _c_i64,
                                _c_p]),
+    "tomo_cc_euler": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p]),
+    "tomo_cc_complement": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_p]),
+    "tomo_cc_cavities": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p,
+                                _c_i64, _c_p, _c_p, _c_p]),
+    "tomo_cc_topology_rows": (_c_i, [_c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p]),
     "tomo_cc_slice_components": (_c_i, [_c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p]),
     "tomo_cc_seam_union": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p,
                                   _c_p, _c_p]),

@@ -1317,6 +1317,388 @@ TOMO_API int tomo_cc_moments(const int64_t *table, int64_t cap, unsigned long lo
     return tomo_status();
 }
 
+// ---------------------------------------------------------------------------------------------- Euler number, cavities, handles
+// chi of the set voxels as a sum over the voxels, every cell of the complex counted by exactly ONE of them, so that nothing is
+// divided and the voxels of a component add up to the component's chi (every cell touches voxels of one component only):
+//   connectivity 6:  the dual complex (a cell = 1, 2, 4 or 8 voxels that are ALL set) -- a cell belongs to its low-corner
+//                    voxel.  Voxel v adds 1 - [x] - [y] - [z] + [x y xy] + [x z xz] + [y z yz] - [all seven], the names
+//                    being the voxels of the 2 x 2 x 2 block above v that must be set.
+//   connectivity 26: the cubical complex (a lattice vertex / edge / face / cube is present if ANY voxel incident to it is
+//                    set) -- a cell belongs to the raster-first set voxel incident to it, i.e. v owns a cell iff every
+//                    raster-EARLIER voxel incident to the cell is clear.  Of the 27 cells of v's cube the ones no earlier voxel
+//                    touches cancel (1 vertex - 3 edges + 3 faces - 1 cube = 0), and so do all that hang on the voxel at
+//                    x - 1 or at y - 1 alone.  With Q, P, R the rows (z-1, y), (z-1, y-1), (z-1, y+1), S the row (z, y-1), T
+//                    the row itself, a suffix m / p for the voxel at x - 1 / x + 1 and [..] = 1 iff all the voxels named are
+//                    CLEAR, what is left is
+//                      [Q] - [Q R] - [S Q P] - [Q Qp] - [Tm Q Qm]
+//                      + [Q Qp R Rp] + [Q Qm R Rm Tm] + [Q Qp P Pp S Sp] + [Q Qm P Pm Tm S Sm]
+//                    (the face below; the two edges below along x and the two along y; the four vertices below).
+// Per word these are ANDs / ORs of the row's word with up to four neighbour rows and their shifts by one bit, carried across
+// the word boundaries; a run's share is the popcount of every term under the run's mask.  Rows outside the stack and bits at
+// x >= nx read as 0.
+struct CcWin {                                               // three neighbouring words of one row, slid along x
+    u64 prv, cur, nxt;
+};
+
+__device__ static inline u64 cc_word_or0(const u64 *__restrict__ row, int nx, int wx, int w)
+{
+    return (row && w < wx) ? cc_word(row, nx, wx, w) : 0ull;
+}
+
+__device__ static inline u64 cc_xp(const CcWin &r) { return (r.cur >> 1) | (r.nxt << 63); }      // bit x = voxel x + 1
+__device__ static inline u64 cc_xm(const CcWin &r) { return (r.cur << 1) | (r.prv >> 63); }      // bit x = voxel x - 1
+
+#define CC_EULER_POS 5
+#define CC_EULER_NEG 4
+
+// the terms of chi for the word win[0].cur of the row: pos[] count + 1 per bit, neg[] count - 1
+template <int K>
+__device__ static inline void cc_euler_terms(const CcWin *win, u64 *pos, u64 *neg)
+{
+    const u64 t = win[0].cur;
+    if constexpr (K == 6) {                                 // win: the row, (z, y+1), (z+1, y), (z+1, y+1)
+        const u64 b = win[1].cur, c = win[2].cur, d = win[3].cur;
+        const u64 ex = t & cc_xp(win[0]), ey = t & b, ez = t & c;
+        const u64 fxy = ex & b & cc_xp(win[1]), fxz = ex & c & cc_xp(win[2]), fyz = ey & c & d;
+        pos[0] = t;
+        pos[1] = fxy;
+        pos[2] = fxz;
+        pos[3] = fyz;
+        pos[4] = 0;
+        neg[0] = ex;
+        neg[1] = ey;
+        neg[2] = ez;
+        neg[3] = fxy & c & cc_xp(win[2]) & d & cc_xp(win[3]);
+    } else {                                                // win: the row T, S = (z, y-1), Q = (z-1, y), P = (z-1, y-1), R = (z-1, y+1)
+        const u64 tm = cc_xm(win[0]);
+        const u64 s = win[1].cur, q = win[2].cur, p = win[3].cur, r = win[4].cur;
+        const u64 qlo = q | cc_xm(win[2]) | tm, qhi = q | cc_xp(win[2]);       // below and behind / below and ahead
+        const u64 slo = s | cc_xm(win[1]), shi = s | cc_xp(win[1]);
+        const u64 plo = p | cc_xm(win[3]), phi = p | cc_xp(win[3]);
+        const u64 rlo = r | cc_xm(win[4]), rhi = r | cc_xp(win[4]);
+        pos[0] = t & ~q;
+        pos[1] = t & ~(qhi | rhi);
+        pos[2] = t & ~(qlo | rlo);
+        pos[3] = t & ~(qhi | phi | shi);
+        pos[4] = t & ~(qlo | plo | slo);
+        neg[0] = t & ~(q | r);
+        neg[1] = t & ~(s | q | p);
+        neg[2] = t & ~qhi;
+        neg[3] = t & ~qlo;
+    }
+}
+
+// chi of the bits under mask, as a two's complement u64
+__device__ static inline u64 cc_euler_under(const u64 *pos, const u64 *neg, u64 mask)
+{
+    int v = 0;
+#pragma unroll
+    for (int i = 0; i < CC_EULER_POS; i++) v += __popcll(pos[i] & mask);
+#pragma unroll
+    for (int i = 0; i < CC_EULER_NEG; i++) v -= __popcll(neg[i] & mask);
+    return (u64)(int64_t)v;
+}
+
+// One thread per row (z, y) over its words and, LABELLED, over the runs in every word (as cc_filter_kernel walks them): a
+// thread adds up neighbouring runs of one component, a wave whose lanes all hold the same component adds once, then one signed
+// 64-bit atomic add (two's complement on u64) into euler[rank[parent[run]]].  Not LABELLED: no table is read and everything
+// goes to euler[0] -- the Euler number of the whole volume.
+template <int K, bool LABELLED>
+__global__ __launch_bounds__(CC_THREADS) void cc_euler_kernel(const u64 *__restrict__ bits, int64_t nrows, int ny, int nx, int wx,
+                                                              const u32 *__restrict__ row_off, const u64 *__restrict__ tot,
+                                                              int64_t cap_runs, const u32 *__restrict__ parent,
+                                                              const u32 *__restrict__ rank, unsigned long long *__restrict__ euler,
+                                                              int64_t cap, u64 *flags)
+{
+    constexpr int NR = K == 6 ? 4 : 5;
+    const int64_t row = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    const u32 nruns = LABELLED ? (u32)cc_count(tot, cap_runs) : 0u;
+    const u32 ncomp = LABELLED ? (u32)cc_ncomp(tot, cap) : 1u;
+    if (LABELLED && row == 0 && tot[1] > (u64)cap) atomicOr((unsigned long long *)flags, CC_F_CAP);
+    u32 comp = 0;                                           // component + 1 the thread is adding up, 0: none
+    u64 acc = 0;
+    if (row < nrows) {
+        const int y = (int)(row % ny);
+        const bool up = y + 1 < ny, down = y > 0, front = row + ny < nrows, back = row >= ny;
+        const u64 *self = bits + row * wx;
+        const u64 *r[NR];
+        r[0] = self;
+        if constexpr (K == 6) {
+            r[1] = up ? self + wx : nullptr;
+            r[2] = front ? self + (int64_t)ny * wx : nullptr;
+            r[3] = up && front ? self + (int64_t)(ny + 1) * wx : nullptr;
+        } else {
+            r[1] = down ? self - wx : nullptr;
+            r[2] = back ? self - (int64_t)ny * wx : nullptr;
+            r[3] = back && down ? self - (int64_t)(ny + 1) * wx : nullptr;
+            r[4] = back && up ? self - (int64_t)(ny - 1) * wx : nullptr;
+        }
+        CcWin win[NR];
+#pragma unroll
+        for (int i = 0; i < NR; i++) {
+            win[i].prv = 0;
+            win[i].cur = cc_word_or0(r[i], nx, wx, 0);
+            win[i].nxt = cc_word_or0(r[i], nx, wx, 1);
+        }
+        u32 next = LABELLED ? row_off[row] : 0u;            // id of the next run that STARTS
+        bool carry = false;                                 // the word before ended inside a run
+        for (int w = 0; w < wx; w++) {
+            u64 m = win[0].cur;
+            if (m) {
+                u64 pos[CC_EULER_POS], neg[CC_EULER_NEG];
+                cc_euler_terms<K>(win, pos, neg);
+                if (!LABELLED) {
+                    comp = 1;
+                    acc += cc_euler_under(pos, neg, m);
+                }
+                while (LABELLED && m) {                     // every turn clears at least one bit of m
+                    const int s = __ffsll((long long)m) - 1;
+                    const u64 z = ~(m >> s);
+                    const int len = z ? __ffsll((long long)z) - 1 : 64;
+                    const u64 mask = len >= 64 ? ~0ull : ((1ull << len) - 1) << s;
+                    const u32 run = (s == 0 && carry) ? next - 1 : next++;
+                    if (run < nruns) {
+                        const u32 c = cc_component(parent, rank, run) + 1;
+                        if (c != comp) {
+                            if (acc && comp - 1 < ncomp) atomicAdd(euler + (comp - 1), (unsigned long long)acc);
+                            comp = c;
+                            acc = 0;
+                        }
+                        acc += cc_euler_under(pos, neg, mask);
+                    } else {
+                        atomicOr((unsigned long long *)flags, CC_F_RANGE);
+                    }
+                    m &= ~mask;
+                }
+            }
+            carry = (win[0].cur >> 63) != 0;
+#pragma unroll
+            for (int i = 0; i < NR; i++) {
+                win[i].prv = win[i].cur;
+                win[i].cur = win[i].nxt;
+                win[i].nxt = cc_word_or0(r[i], nx, wx, w + 2);
+            }
+        }
+    }
+    if (!acc) comp = 0;
+    const u32 top = wave_max32(comp);
+    if (top == 0) return;                                   // wave-uniform
+    if (__all(comp == 0 || comp == top)) {
+        const u64 sum = wave_sum64(acc);
+        if ((threadIdx.x & 63) == 0 && sum && top - 1 < ncomp) atomicAdd(euler + (top - 1), (unsigned long long)sum);
+    } else if (comp != 0 && comp - 1 < ncomp) {
+        atomicAdd(euler + (comp - 1), (unsigned long long)acc);
+    }
+}
+
+TOMO_API int tomo_cc_euler(const uint64_t *bits, int nz, int ny, int nx, int connectivity, const uint32_t *row_off, int64_t cap_runs,
+                           const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, int64_t *euler, int64_t cap,
+                           void *stream)
+{
+    int64_t nrows;
+    int wx;
+    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
+    if (g != TOMO_OK) return g;
+    if (!euler || cap <= 0 || (connectivity != 6 && connectivity != 26)) return TOMO_E_ARG;
+    if (parent && (!row_off || !rank || !tot || cap_runs <= 0)) return TOMO_E_ARG;
+    if (cap >= ((int64_t)1 << 31) || (parent && cap_runs >= ((int64_t)1 << 31))) return TOMO_E_SIZE;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(euler, 0, (size_t)cap * sizeof(int64_t), st) != hipSuccess) return TOMO_E_LAUNCH;
+    const dim3 grid((unsigned)ceil_div64(nrows, CC_THREADS)), block(CC_THREADS);
+    const u64 *b = (const u64 *)bits, *t = (const u64 *)tot;
+    const u32 *ro = (const u32 *)row_off, *pa = (const u32 *)parent, *ra = (const u32 *)rank;
+    unsigned long long *e = (unsigned long long *)euler;
+    u64 *flags = tot ? (u64 *)tot + 2 : nullptr;
+    if (parent) {
+        if (connectivity == 6)
+            hipLaunchKernelGGL((cc_euler_kernel<6, true>), grid, block, 0, st, b, nrows, ny, nx, wx, ro, t, cap_runs, pa, ra, e, cap, flags);
+        else
+            hipLaunchKernelGGL((cc_euler_kernel<26, true>), grid, block, 0, st, b, nrows, ny, nx, wx, ro, t, cap_runs, pa, ra, e, cap, flags);
+    } else {
+        if (connectivity == 6)
+            hipLaunchKernelGGL((cc_euler_kernel<6, false>), grid, block, 0, st, b, nrows, ny, nx, wx, ro, t, cap_runs, pa, ra, e, cap, flags);
+        else
+            hipLaunchKernelGGL((cc_euler_kernel<26, false>), grid, block, 0, st, b, nrows, ny, nx, wx, ro, t, cap_runs, pa, ra, e, cap, flags);
+    }
+    return tomo_status();
+}
+
+// out = the complement inside the stack: ~word, the bits at x >= nx clear
+__global__ __launch_bounds__(CC_THREADS) void cc_complement_kernel(const u64 *__restrict__ bits, int64_t nwords, int nx, int wx,
+                                                                   u64 *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    if (i >= nwords) return;
+    out[i] = ~bits[i] & cc_tail_mask(nx, wx, (int)(i % wx));
+}
+
+TOMO_API int tomo_cc_complement(const uint64_t *bits, int nz, int ny, int nx, uint64_t *out, void *stream)
+{
+    int64_t nrows;
+    int wx;
+    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
+    if (g != TOMO_OK) return g;
+    if (!out || out == bits) return TOMO_E_ARG;
+    const int64_t nwords = nrows * wx;
+    hipLaunchKernelGGL(cc_complement_kernel, dim3((unsigned)ceil_div64(nwords, CC_THREADS)), dim3(CC_THREADS), 0, (hipStream_t)stream,
+                       (const u64 *)bits, nwords, nx, wx, (u64 *)out);
+    return tomo_status();
+}
+
+// x of the k-th (0-based) run of a row, -1 if the row has no such run (at most wx + 64 turns)
+__device__ static inline int cc_run_start(const u64 *__restrict__ row, int nx, int wx, u32 k)
+{
+    for (int w = 0; w < wx; w++) {
+        u64 s = cc_starts(row, nx, wx, w, cc_word(row, nx, wx, w));
+        const u32 c = (u32)__popcll(s);
+        if (k < c) {
+            while (k--) s &= s - 1;
+            return 64 * w + __ffsll((long long)s) - 1;
+        }
+        k -= c;
+    }
+    return -1;
+}
+
+// topo (device int64[cap][3]): row c = (euler[c], 0, 0) for c < n, zeros behind
+__global__ __launch_bounds__(CC_THREADS) void cc_topology_init_kernel(const u64 *__restrict__ euler, const u64 *__restrict__ tot,
+                                                                      int64_t cap, u64 *__restrict__ topo)
+{
+    const int64_t c = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    if (c >= cap) return;
+    topo[3 * c] = c < cc_ncomp(tot, cap) ? euler[c] : 0ull;
+    topo[3 * c + 1] = 0;
+    topo[3 * c + 2] = 0;
+}
+
+// One thread per run of the BACKGROUND (the complement, labelled under the complementary connectivity; bg_table = its
+// measurement table).  A run that is its own root is the first run of its component in raster order; if the component's box
+// touches no face of the stack it is a cavity, the voxel left of the run's start is set and belongs to the foreground
+// component that encloses it: its run is found as cc_expand_kernel maps a bit to a run, and that component counts one more.
+__global__ __launch_bounds__(CC_THREADS) void cc_cavities_kernel(const u64 *__restrict__ bits, int64_t nrows, int ny, int nx, int wx,
+                                                                 const u32 *__restrict__ row_off, const u64 *__restrict__ tot,
+                                                                 int64_t cap_runs, const u32 *__restrict__ parent,
+                                                                 const u32 *__restrict__ rank, int64_t cap,
+                                                                 const u64 *__restrict__ bg_bits, const u32 *__restrict__ bg_row_off,
+                                                                 const u64 *__restrict__ bg_tot, int64_t bg_cap_runs,
+                                                                 const u32 *__restrict__ bg_parent, const u32 *__restrict__ bg_rank,
+                                                                 const u64 *__restrict__ bg_table, int64_t bg_cap,
+                                                                 unsigned long long *__restrict__ topo, u64 *flags)
+{
+    const int64_t i = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    if (i == 0 && (tot[0] > (u64)cap_runs || tot[1] > (u64)cap || bg_tot[0] > (u64)bg_cap_runs || bg_tot[1] > (u64)bg_cap))
+        atomicOr((unsigned long long *)flags, CC_F_CAP);
+    const u32 nruns = (u32)cc_count(tot, cap_runs), ncomp = (u32)cc_ncomp(tot, cap);
+    const u32 nbg_comp = (u32)cc_ncomp(bg_tot, bg_cap);
+    if (i >= cc_count(bg_tot, bg_cap_runs) || nruns == 0 || ncomp == 0 || nbg_comp == 0) return;
+    const u32 run = (u32)i;
+    if (bg_parent[run] != run) return;
+    const u32 c = bg_rank[run];
+    if (c >= nbg_comp) {
+        atomicOr((unsigned long long *)flags, CC_F_RANGE);
+        return;
+    }
+    const u64 *box = bg_table + (int64_t)c * CC_COLS;
+    const u64 nz = (u64)(nrows / ny);
+    if (box[1] == 0 || box[2] + 1 >= nz || box[3] == 0 || box[4] + 1 >= (u64)ny || box[5] == 0 || box[6] + 1 >= (u64)nx) return;
+    int64_t lo = 0, hi = nrows - 1;                         // the row of the run: the last one with bg_row_off[row] <= run
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (bg_row_off[mid] <= run) lo = mid;
+        else hi = mid - 1;
+    }
+    const u32 first = bg_row_off[lo];
+    const int s = first <= run ? cc_run_start(bg_bits + lo * wx, nx, wx, run - first) : -1;
+    bool ok = s > 0;
+    if (ok) {
+        const int x = s - 1, wj = x >> 6, b = x & 63;
+        const u64 *r = bits + lo * wx;
+        const u64 cur = cc_word(r, nx, wx, wj);
+        ok = ((cur >> b) & 1) != 0;
+        if (ok) {
+            const u64 starts = cc_starts(r, nx, wx, wj, cur);
+            const u32 fr = cc_before(r, nx, wx, wj, row_off[lo]) + (u32)__popcll(starts & (~0ull >> (63 - b))) - 1;
+            ok = fr < nruns;
+            if (ok) {
+                const u32 fc = cc_component(parent, rank, fr);
+                ok = fc < ncomp;
+                if (ok) atomicAdd(topo + 3 * (int64_t)fc + 1, 1ull);
+            }
+        }
+    }
+    if (!ok) atomicOr((unsigned long long *)flags, CC_F_RANGE);
+}
+
+// handles = 1 - euler + cavities
+__global__ __launch_bounds__(CC_THREADS) void cc_handles_kernel(const u64 *__restrict__ tot, int64_t cap, u64 *__restrict__ topo)
+{
+    const int64_t c = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    if (c >= cc_ncomp(tot, cap)) return;
+    topo[3 * c + 2] = 1ull - topo[3 * c] + topo[3 * c + 1];
+}
+
+TOMO_API int tomo_cc_cavities(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                              const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, int64_t cap,
+                              const uint64_t *bg_bits, const uint32_t *bg_row_off, int64_t bg_cap_runs, const uint32_t *bg_parent,
+                              const uint32_t *bg_rank, const unsigned long long *bg_tot, const int64_t *bg_table, int64_t bg_cap,
+                              const int64_t *euler, int64_t *topo, void *stream)
+{
+    int64_t nrows;
+    int wx;
+    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
+    if (g != TOMO_OK) return g;
+    if (!row_off || !parent || !rank || !tot || !euler || !topo || cap_runs <= 0 || cap <= 0 || bg_cap_runs < 0) return TOMO_E_ARG;
+    if (bg_cap_runs > 0 && (!bg_bits || !bg_row_off || !bg_parent || !bg_rank || !bg_tot || !bg_table || bg_cap <= 0)) return TOMO_E_ARG;
+    if (cap_runs >= ((int64_t)1 << 31) || cap >= ((int64_t)1 << 31) || bg_cap_runs >= ((int64_t)1 << 31) || bg_cap >= ((int64_t)1 << 31))
+        return TOMO_E_SIZE;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned comp_blocks = (unsigned)ceil_div64(cap, CC_THREADS);
+    hipLaunchKernelGGL(cc_topology_init_kernel, dim3(comp_blocks), dim3(CC_THREADS), 0, st, (const u64 *)euler, (const u64 *)tot, cap,
+                       (u64 *)topo);
+    if (bg_cap_runs > 0)                                    // a full volume has no background run: nothing to attribute
+        hipLaunchKernelGGL(cc_cavities_kernel, dim3((unsigned)ceil_div64(bg_cap_runs, CC_THREADS)), dim3(CC_THREADS), 0, st,
+                           (const u64 *)bits, nrows, ny, nx, wx, (const u32 *)row_off, (const u64 *)tot, cap_runs, (const u32 *)parent,
+                           (const u32 *)rank, cap, (const u64 *)bg_bits, (const u32 *)bg_row_off, (const u64 *)bg_tot, bg_cap_runs,
+                           (const u32 *)bg_parent, (const u32 *)bg_rank, (const u64 *)bg_table, bg_cap, (unsigned long long *)topo,
+                           (u64 *)tot + 2);
+    hipLaunchKernelGGL(cc_handles_kernel, dim3(comp_blocks), dim3(CC_THREADS), 0, st, (const u64 *)tot, cap, (u64 *)topo);
+    return tomo_status();
+}
+
+// out[slot[c]] = (c + 1, voxels, euler, cavities, handles) for every selected component c (sel, slot, tot[5]: tomo_cc_zhist_offsets)
+__global__ __launch_bounds__(CC_THREADS) void cc_topology_rows_kernel(const u64 *__restrict__ table, const u64 *__restrict__ topo,
+                                                                      const u64 *__restrict__ tot, int64_t cap,
+                                                                      const uint8_t *__restrict__ sel, const u32 *__restrict__ slot,
+                                                                      u64 *__restrict__ out, int64_t cap_sel, u64 *flags)
+{
+    const int64_t c = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    const bool fits = tot[5] <= (u64)cap_sel && tot[1] <= (u64)cap;
+    if (c == 0 && !fits) atomicOr((unsigned long long *)flags, CC_F_CAP);
+    if (!fits || c >= cc_ncomp(tot, cap) || !sel[c]) return;
+    const u32 k = slot[c];
+    if ((int64_t)k >= cap_sel) {
+        atomicOr((unsigned long long *)flags, CC_F_RANGE);
+        return;
+    }
+    u64 *o = out + 5 * (int64_t)k;
+    o[0] = (u64)c + 1;
+    o[1] = table[c * CC_COLS];
+    o[2] = topo[3 * c];
+    o[3] = topo[3 * c + 1];
+    o[4] = topo[3 * c + 2];
+}
+
+TOMO_API int tomo_cc_topology_rows(const int64_t *table, const int64_t *topo, int64_t cap, unsigned long long *tot, const uint8_t *sel,
+                                   const uint32_t *slot, int64_t *out, int64_t cap_sel, void *stream)
+{
+    if (!table || !topo || !tot || !sel || !slot || !out || cap <= 0 || cap_sel <= 0) return TOMO_E_ARG;
+    if (cap >= ((int64_t)1 << 31) || cap_sel >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
+    hipLaunchKernelGGL(cc_topology_rows_kernel, dim3((unsigned)ceil_div64(cap, CC_THREADS)), dim3(CC_THREADS), 0, (hipStream_t)stream,
+                       (const u64 *)table, (const u64 *)topo, (const u64 *)tot, cap, sel, (const u32 *)slot, (u64 *)out, cap_sel,
+                       (u64 *)tot + 2);
+    return tomo_status();
+}
+
 // ---------------------------------------------------------------------------------------------- components across Z-slabs
 // A stack cut along z: rank r labels its slab with the kernels above (n_r components) and local component c gets the global
 // id base_r + c, base_r = n_0 + ... + n_(r-1).  Global ids ascend in (rank, local raster order of the first voxel) = the

@@ -23,7 +23,8 @@ COUNTERS = dict.fromkeys(("na_hint_hit", "na_hint_miss", "mc3_hint_hit", "mc3_hi
                           "mc3_exact", "mc3_general_unique", "mc3_degenerate", "components_label", "components_expand",
                           "components_filter", "slab_components_label", "slab_components_seam", "slab_components_merge",
                           "slab_components_expand", "slab_components_filter", "distance_transform", "distance_offset",
-                          "components_measure", "components_zhist", "components_moments"), 0)
+                          "components_measure", "components_zhist", "components_moments", "components_euler",
+                          "components_cavities"), 0)
 NA_HINTS = os.environ.get("TOMO_NA_HINTS", "1") not in ("", "0")   # marching_cubes: launch ahead of the first count download
 _NA_HINT = {}
 LIST_LIMIT = 2 ** 31        # active-voxel list entries / vertices / triangles one pass can index (int32 offsets in mc.hip, mesh.hip);
@@ -243,6 +244,7 @@ TABLE_COLUMNS = 10           # voxels, zmin, zmax, ymin, ymax, xmin, xmax, sum z
 COMPONENT_HIST_BUDGET = 1 << 30
 MOMENT_SUMS = 6              # uint64 per component and slice: N, sum j', sum i', sum j'^2, sum i'^2, sum j' i' (tomo_cc_moment_hist)
 MOMENT_COLUMNS = 22          # float64 per row of tomo_cc_moments: W, centre (3), covariance (6), variances (3), axes (9)
+TOPOLOGY_COLUMNS = 3         # euler, cavities, handles (tomo_cc_cavities)
 
 
 class ComponentRuns:
@@ -265,6 +267,7 @@ class ComponentRuns:
         self.runs = _download(self.tot)[0]                       # the one read that sizes the tables
         self.n = 0
         self._table = None
+        self._topology = None
         COUNTERS["components_label"] += 1
         if self.runs == 0:
             return
@@ -319,6 +322,38 @@ class ComponentRuns:
         if fresh and table.shape[0]:
             self._checked()
         return table
+
+    def topology(self) -> torch.Tensor:
+        """Per component 1..n: Euler number, cavities (enclosed voids, b2) and handles (tunnels, b1 = 1 - euler + cavities) of
+        the mask `labels == c` -> int64 (n, 3) device tensor, computed once and kept.  The background has the complementary
+        connectivity (26 for 6, 6 for 26) and everything outside the stack is background: a void that reaches a face of the
+        stack is no cavity.  The Euler pass runs over the rows of this object; the cavities come from a second ComponentRuns
+        over the complement: every component of it whose box touches no face is a cavity of the component left of its first
+        voxel.  Working memory: one more bit volume and the run tables of the complement, never a label array."""
+        if self._topology is None:
+            dev = self.vol.device
+            n = self._checked() if self.runs else 0
+            if n == 0:
+                self._topology = torch.zeros((0, TOPOLOGY_COLUMNS), dtype=torch.int64, device=dev)
+                return self._topology
+            nz, ny, nx = self.vol.shape
+            L, st = _lib.lib(), _stream()
+            geo = (_p(self.bits), nz, ny, nx)
+            euler = torch.empty(n, dtype=torch.int64, device=dev)
+            COUNTERS["components_euler"] += 1
+            _lib.check(L.tomo_cc_euler(*geo, self.connectivity, *self._tables(), _p(self.tot), _p(euler), n, st), "tomo_cc_euler")
+            outside = torch.empty_like(self.bits)
+            _lib.check(L.tomo_cc_complement(*geo, _p(outside), st), "tomo_cc_complement")
+            bg = ComponentRuns(BitVolume(outside, self.vol.shape), 32 - self.connectivity)
+            bg_table = bg.table()
+            topo = torch.empty((n, TOPOLOGY_COLUMNS), dtype=torch.int64, device=dev)
+            bg_args = (_p(outside), _p(bg.row_off), bg.runs, _p(bg.parent), _p(bg.rank), _p(bg.tot), _p(bg_table),
+                       bg_table.shape[0]) if bg.runs else (None, None, 0, None, None, None, None, 0)
+            COUNTERS["components_cavities"] += 1
+            _lib.check(L.tomo_cc_cavities(*geo, *self._tables(), _p(self.tot), n, *bg_args, _p(euler), _p(topo), st), "tomo_cc_cavities")
+            self._checked()
+            self._topology = topo
+        return self._topology
 
     def labels(self):
         """-> (int32 (nz, ny, nx) device tensor as scipy.ndimage.label returns it, n)."""
@@ -542,6 +577,86 @@ def component_moments(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_
     if host[3][0]:
         raise _lib.TomoError("component_moments: the tables do not fit the volume (flags %d)" % host[3][0])
     return _component_moments_from(host[0], host[1], host[2])
+
+
+# ----------------------------------------------------------------------------- Euler number, cavities and handles
+@dataclass
+class ComponentTopology:
+    """component_topology's answer: host arrays, one row per selected component in ascending label."""
+    labels: np.ndarray           # int64 (m,)
+    voxels: np.ndarray           # int64 (m,)
+    euler: np.ndarray            # int64 (m,): Euler number of the mask `labels == c`
+    cavities: np.ndarray         # int64 (m,): enclosed voids (b2)
+    handles: np.ndarray          # int64 (m,): tunnels (b1) = 1 - euler + cavities
+
+    def __len__(self):
+        return len(self.labels)
+
+
+def _component_topology_from(rows) -> ComponentTopology:
+    """Host side of the downloaded rows: int64 (m, 5) as tomo_cc_topology_rows writes them."""
+    rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1, 2 + TOPOLOGY_COLUMNS)
+    return ComponentTopology(*(rows[:, k].copy() for k in range(2 + TOPOLOGY_COLUMNS)))
+
+
+def euler_number(vol: BitVolume, connectivity=6) -> int:
+    """The Euler number of a resident volume: under connectivity 26, vertices - edges + faces - cubes of the union of the
+    closed unit cubes of the set voxels; under 6, voxels - face-adjacent pairs + full 2 x 2 blocks - full 2 x 2 x 2 blocks
+    (the dual complex).  Everything outside the stack is background.  It equals components - handles + cavities
+    (volume_topology) without any labelling: one pass over the rows, one host read."""
+    if connectivity not in CONNECTIVITIES:
+        raise ValueError("connectivity must be 6 or 26")
+    nz, ny, nx = vol.shape
+    chi = torch.empty(1, dtype=torch.int64, device=vol.device)
+    COUNTERS["components_euler"] += 1
+    _lib.check(_lib.lib().tomo_cc_euler(_p(vol.bits.contiguous()), nz, ny, nx, int(connectivity), None, 0, None, None, None, _p(chi), 1,
+                                        _stream()), "tomo_cc_euler")
+    return int(chi.item())
+
+
+def component_topology(vol: BitVolume, connectivity=6, min_voxels=0, largest=False) -> ComponentTopology:
+    """Per component of a resident volume: Euler number, cavities and handles (ComponentRuns.topology) -> ComponentTopology,
+    one row per component the keep rule of component_properties selects (at least min_voxels voxels; largest: only the
+    largest of those, the lowest label among equals), in ascending label: the rows, in the same order, component_properties
+    returns for the same arguments.  A ball reads (1, 0, 0), a hollow shell (2, 1, 0), a ring (0, 0, 1).  A void that reaches
+    a face of the stack is no cavity; an island floating in a void does not split it, and the island's own voids are the
+    island's.  There are no slice depths here: topology does not depend on them.  Working memory scales with the rows, the
+    runs of the volume and of its complement, and the components -- never with the voxels."""
+    if connectivity not in CONNECTIVITIES:
+        raise ValueError("connectivity must be 6 or 26")
+    min_voxels = max(0, int(min_voxels))
+    empty = _component_topology_from(np.zeros((0, 2 + TOPOLOGY_COLUMNS), dtype=np.int64))
+    cr = ComponentRuns(vol, connectivity)
+    topo = cr.topology()
+    n = topo.shape[0]
+    if n == 0:
+        return empty
+    table = cr._measure()
+    L, dev, st = _lib.lib(), vol.device, _stream()
+    sel = torch.empty(n, dtype=torch.uint8, device=dev)
+    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    slot = torch.empty(n, dtype=torch.int32, device=dev)
+    blk = torch.empty(2 * L.tomo_cc_scan_blocks(n), dtype=torch.int64, device=dev)
+    _lib.check(L.tomo_cc_zhist_offsets(_p(table), n, _p(cr.tot), min_voxels, int(bool(largest)), _p(sel), _p(off), _p(slot), _p(blk),
+                                       st), "tomo_cc_zhist_offsets")
+    cr._checked()                                               # ... and the guards of the measuring pass
+    m = cr.host[5]
+    if m == 0:
+        return empty
+    rows = torch.empty((m, 2 + TOPOLOGY_COLUMNS), dtype=torch.int64, device=dev)
+    _lib.check(L.tomo_cc_topology_rows(_p(table), _p(topo), n, _p(cr.tot), _p(sel), _p(slot), _p(rows), m, st), "tomo_cc_topology_rows")
+    host = [t.cpu().numpy() for t in (rows, cr.tot[2:3])]
+    if host[1][0]:
+        raise _lib.TomoError("component_topology: the tables do not fit the volume (flags %d)" % host[1][0])
+    return _component_topology_from(host[0])
+
+
+def volume_topology(vol: BitVolume, connectivity=6) -> dict:
+    """The topology of the whole volume -> {'components', 'cavities', 'handles', 'euler'}: the number of components and the
+    sums of ComponentRuns.topology's columns; euler = components - handles + cavities = euler_number(vol, connectivity)."""
+    topo = ComponentRuns(vol, connectivity).topology()
+    euler, cavities, handles = (int(v) for v in topo.sum(dim=0).cpu()) if topo.shape[0] else (0, 0, 0)
+    return {"components": int(topo.shape[0]), "cavities": cavities, "handles": handles, "euler": euler}
 
 
 # ----------------------------------------------------------------------------- Euclidean distance in millimetres

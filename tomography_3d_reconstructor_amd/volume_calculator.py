@@ -101,7 +101,7 @@ def largest_inscribed_sphere(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_d
 
 
 def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=6, min_voxels=0, largest=False,
-                         shape=False):
+                         shape=False, topology=False):
     """The calculations of the class per connected component (no counterpart in the reference, which would be handed the mask
     `labels == c` once per component) -> a list of dicts, one per component with at least min_voxels voxels (largest: only the
     largest of those), in label order: {'label', 'voxels', 'voxel_volume_mm3', 'bounding_box': {'x', 'y', 'z'}, 'dimensions',
@@ -111,8 +111,11 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
     body of point masses, one per voxel, weighted with the voxel's volume (pipeline.component_moments; vectors in (z, y, x)
     order): 'center_of_mass_mm', 'covariance_mm2' (3 x 3 nested tuples), 'principal_variances_mm2' (descending),
     'principal_axes' (3 rows, unit vectors in that order) and 'ellipsoid_axes_mm' (the full axes of the solid ellipsoid with
-    the same second moments).  With the default nothing more is launched and the dicts are as before.  voxel_data: the bool
-    (nz, ny, nx) array the other calculations take; anything else is a TypeError -- there is no host path for this one."""
+    the same second moments).  topology=True: every dict also carries 'euler_number', 'cavities' (enclosed voids; one that
+    reaches a face of the stack is none) and 'handles' (tunnels) of the component as Python ints
+    (pipeline.component_topology: a ball reads 1, 0, 0, a hollow shell 2, 1, 0, a ring 0, 0, 1; the background has the
+    complementary connectivity).  With the defaults nothing more is launched and the dicts are as before.  voxel_data: the
+    bool (nz, ny, nx) array the other calculations take; anything else is a TypeError -- there is no host path for this one."""
     if not _on_device(voxel_data):
         raise TypeError("component_properties needs a bool (nz, ny, nx) array")
     depths = np.asarray(slice_depths, dtype=np.float64).reshape(-1)
@@ -134,6 +137,10 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
             d['principal_variances_mm2'] = tuple(float(v) for v in q.principal_variances_mm2[i])
             d['principal_axes'] = tuple(tuple(float(v) for v in row) for row in q.principal_axes[i])
             d['ellipsoid_axes_mm'] = tuple(float(v) for v in q.ellipsoid_axes_mm[i])
+    if topology:
+        t = pipeline.component_topology(to_device_volume(voxel_data), connectivity, min_voxels, largest)
+        for i, d in enumerate(out):                              # the same rule on the same volume: the same rows
+            d['euler_number'], d['cavities'], d['handles'] = int(t.euler[i]), int(t.cavities[i]), int(t.handles[i])
     return out
 
 
