@@ -1,4 +1,4 @@
-"""GPU tier: per-component second moments and principal axes on the resident bit volume (csrc/components.hip:
+"""GPU tier: per-component second moments and principal axes on the resident bit volume (csrc/component_measures.hip:
 tomo_cc_moment_hist, tomo_cc_moments -> pipeline.component_moments -> volume_calculator.component_properties(shape=True)).
 
 Every result is compared with tests/component_moments_reference.py (NumPy in long double, held against a literal loop over the
@@ -166,6 +166,44 @@ def test_selection(dev):
         held(pipeline.component_moments(vol, d, MM_Y, MM_X, conn, min_voxels, largest), ref, "selection %d %s" % (min_voxels, largest))
 
 
+@pytest.mark.parametrize("conn", [6, 26])
+@pytest.mark.parametrize("name", ["straddle", "stacked", "seams", "noise_031"])
+def test_the_voxel_counts_are_the_first_moment_sum(dev, name, conn):
+    """tomo_cc_zhist and tomo_cc_moment_hist are one kernel under two widths: on the same tables and the same selection,
+    sum 0 of every entry of the moment histogram is the entry of the voxel histogram, and no guard fires.  straddle: every
+    wave spans 32 slices (the combine per slice); stacked: two components in one wave, runs across the word seam (the mixed
+    path, the flush on change); seams: runs ending at x = 63, 64, 65, 129; noise_031: every lane diverges."""
+    v, vol = T.resident(name, dev)
+    nz, ny, nx = v.shape
+    L, st = _lib.lib(), pipeline._stream()
+    _p = pipeline._p
+    cr = pipeline.ComponentRuns(vol, conn)
+    n = cr._checked()
+    sizes = cr.sizes().cpu().numpy()
+    geo = (_p(cr.bits), nz, ny, nx)
+    table = torch.empty((n, pipeline.TABLE_COLUMNS), dtype=torch.int64, device=dev)
+    _lib.check(L.tomo_cc_measure(*geo, *cr._tables(), _p(cr.tot), _p(table), n, st), "tomo_cc_measure")
+    sel = torch.empty(n, dtype=torch.uint8, device=dev)
+    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    slot = torch.empty(n, dtype=torch.int32, device=dev)
+    blk = torch.empty(2 * L.tomo_cc_scan_blocks(n), dtype=torch.int64, device=dev)
+    for min_voxels, largest in [(0, False), (int(np.median(sizes)), False), (0, True)]:
+        what = (name, conn, min_voxels, largest)
+        _lib.check(L.tomo_cc_zhist_offsets(_p(table), n, _p(cr.tot), min_voxels, int(largest), _p(sel), _p(off), _p(slot), _p(blk), st),
+                   "tomo_cc_zhist_offsets")
+        host = pipeline._download(cr.tot)
+        total, m = int(host[4]), int(host[5])
+        assert host[2] == 0 and m > 0 and total >= m, (what, host)
+        hist = torch.empty(total, dtype=torch.int64, device=dev)
+        mom = torch.empty(pipeline.MOMENT_SUMS * total, dtype=torch.int64, device=dev)
+        _lib.check(L.tomo_cc_zhist(*geo, *cr._tables(), _p(cr.tot), _p(table), n, _p(sel), _p(off), _p(hist), total, st), "tomo_cc_zhist")
+        _lib.check(L.tomo_cc_moment_hist(*geo, *cr._tables(), _p(cr.tot), _p(table), n, _p(sel), _p(off), _p(mom), total, st),
+                   "tomo_cc_moment_hist")
+        assert torch.equal(mom.view(total, pipeline.MOMENT_SUMS)[:, 0], hist), what
+        assert int(hist.sum()) == int(sizes[sel.cpu().numpy() != 0].sum()), what       # ... and neither is empty
+        assert pipeline._download(cr.tot)[2] == 0, what
+
+
 def test_a_tie_selects_the_first_of_two_equal_cubes(dev):
     v, vol = resident("tie", dev)
     labels, n, tab = reference("tie", 6)
@@ -259,5 +297,5 @@ def test_fenced(dev, poison, conn):
         with fz.unchanged(vol.bits):
             held(pipeline.component_moments(vol, d, MM_Y, MM_X, conn, 2), exp, "fenced")
             held(pipeline.component_moments(vol, d, MM_Y, MM_X, conn, 2, True), exp_largest, "fenced largest")
-        assert fz.ran("_measure") == 2 and fz.ran("component_moments") >= 2 * 7
+        assert fz.ran("_measure") == 2 and fz.ran("select") >= 2 * 4 and fz.ran("component_moments") >= 2 * 3
     T.run_fenced(poison, body, "%s/%d" % (name, conn))

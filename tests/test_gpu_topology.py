@@ -1,4 +1,4 @@
-"""GPU tier: Euler number, cavities and handles on the resident bit volume (csrc/components.hip: tomo_cc_euler,
+"""GPU tier: Euler number, cavities and handles on the resident bit volume (csrc/component_measures.hip: tomo_cc_euler,
 tomo_cc_complement, tomo_cc_cavities, tomo_cc_topology_rows -> pipeline.euler_number / ComponentRuns.topology /
 component_topology / volume_topology -> volume_calculator.component_properties(..., topology=True)).
 
@@ -258,5 +258,5 @@ def test_fenced(dev, poison, conn):
                 same(pipeline.component_topology(vol, conn, 0, True), P.selected(sizes, 0, True).astype(np.int64) + 1, sizes, tab,
                      "fenced largest")
                 assert pipeline.euler_number(vol, conn) == int(tab[:, 0].sum())
-        assert fz.ran("topology") >= 3 * 3 * 3 and fz.ran("component_topology") >= 3 * 2 * 5 and fz.ran("euler_number") == 3
+        assert fz.ran("topology") >= 3 * 3 * 3 and fz.ran("select") >= 3 * 2 * 4 and fz.ran("component_topology") >= 3 * 2 * 1 and fz.ran("euler_number") == 3
     run_fenced(poison, body, "noise/%d" % conn)

@@ -1,0 +1,336 @@
+// cc_runs.h -- the device-side vocabulary of the run tables (components.hip labels them, component_measures.hip measures
+// what they hold): rows and their runs, the union-find over run ids, which run a bit lies in, and the ROW PASS -- one thread
+// per row adds up what its runs give per component, a wave combines -- that every per-component quantity goes through.
+//
+// tot (device uint64[8]): [0] runs  [1] components  [2] flags (1: 2^31 runs or more, 2: more runs than the caller's buffers
+// hold, 4: a run id outside the tables -- the bits changed between the calls)  [3] label tomo_cc_filter(largest) kept (0: none)
+// [4] counters of the slice histogram  [5] components tomo_cc_zhist_offsets selected.
+#pragma once
+#include "tomo_common.h"
+
+#define CC_THREADS 256
+#define CC_SCAN_TILE 1024            // entries per workgroup of the scan kernels (4 per thread)
+#define CC_F_MANY 1ull
+#define CC_F_CAP 2ull
+#define CC_F_RANGE 4ull
+#define CC_COLS 10                   // columns of a row of the measurement table (tomo_cc_measure)
+
+static int cc_geometry(const void *bits, int nz, int ny, int nx, int64_t *nrows, int *wx)
+{
+    if (!bits || nz <= 0 || ny <= 0 || nx <= 0) return TOMO_E_ARG;
+    *wx = (int)tomo_words_per_row(nx);
+    *nrows = (int64_t)nz * ny;
+    if (*nrows * *wx >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
+    return TOMO_OK;
+}
+
+__device__ static inline void cc_flag(u64 *flags, u64 f) { atomicOr((unsigned long long *)flags, f); }
+
+// ---------------------------------------------------------------------------------------------- rows and runs
+__device__ static inline u64 cc_tail_mask(int nx, int wx, int w)
+{
+    const int r = nx - 64 * (wx - 1);                      // bits of the last word, 1 .. 64
+    return (w == wx - 1 && r < 64) ? ((1ull << r) - 1) : ~0ull;
+}
+
+// word w of a row, bits at x >= nx cleared whatever the buffer holds there
+__device__ static inline u64 cc_word(const u64 *__restrict__ row, int nx, int wx, int w)
+{
+    return row[w] & cc_tail_mask(nx, wx, w);
+}
+
+// bits of word w at which a run starts
+__device__ static inline u64 cc_starts(const u64 *__restrict__ row, int nx, int wx, int w, u64 cur)
+{
+    const u64 carry = w > 0 ? row[w - 1] >> 63 : 0ull;    // bit 63 of a word before the last is never a tail bit
+    return cur & ~((cur << 1) | carry);
+}
+
+// the runs of one row, in ascending x: [s, e)
+struct CcRuns {
+    const u64 *row;
+    int nx, wx, pos;
+    int s, e;
+    bool valid;
+};
+
+__device__ static inline void cc_runs_next(CcRuns &it)
+{
+    const int end = 64 * it.wx;
+    it.valid = false;
+    if (it.pos >= end) return;
+    int w = it.pos >> 6;
+    u64 m = cc_word(it.row, it.nx, it.wx, w) & (~0ull << (it.pos & 63));
+    while (m == 0) {                                        // w only grows: at most wx turns
+        if (++w >= it.wx) { it.pos = end; return; }
+        m = cc_word(it.row, it.nx, it.wx, w);
+    }
+    it.s = 64 * w + __ffsll((long long)m) - 1;
+    w = it.s >> 6;
+    m = ~cc_word(it.row, it.nx, it.wx, w) & (~0ull << (it.s & 63));
+    int e = end;
+    while (true) {
+        if (m != 0) { e = 64 * w + __ffsll((long long)m) - 1; break; }
+        if (++w >= it.wx) break;
+        m = ~cc_word(it.row, it.nx, it.wx, w);
+    }
+    it.e = e;
+    it.pos = e;
+    it.valid = true;
+}
+
+__device__ static inline CcRuns cc_runs_begin(const u64 *__restrict__ bits, int64_t row, int nx, int wx)
+{
+    CcRuns it;
+    it.row = bits + row * wx;
+    it.nx = nx;
+    it.wx = wx;
+    it.pos = 0;
+    it.s = it.e = 0;
+    cc_runs_next(it);
+    return it;
+}
+
+// ---------------------------------------------------------------------------------------------- the counts of the tables
+// n comes from the host (n_dev == NULL) or from device memory, clipped to the capacity the grid was sized for
+__device__ static inline int64_t cc_count(const u64 *n_dev, int64_t cap)
+{
+    if (!n_dev) return cap;
+    const u64 n = *n_dev;
+    return n > (u64)cap ? 0 : (int64_t)n;                  // too many for the buffers: nothing is touched (flag CC_F_CAP)
+}
+
+// the count of components comes from tot[1]; more than a table's rows: nothing is touched (CC_F_CAP)
+__device__ static inline int64_t cc_ncomp(const u64 *tot, int64_t cap)
+{
+    const u64 n = tot[1];
+    return n > (u64)cap ? 0 : (int64_t)n;
+}
+
+// one workgroup: blk[i] = sum of blk[0 .. i) for i < nblk, *total = the sum of all; 1024 entries per step with a running carry
+static __global__ __launch_bounds__(1024) void cc_scan1_kernel(u64 *__restrict__ blk, int64_t nblk, u64 *__restrict__ total, u64 *flags)
+{
+    __shared__ u64 wsum[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    u64 carry = 0;
+    for (int64_t i0 = 0; i0 < nblk; i0 += 1024) {
+        const int64_t i = i0 + threadIdx.x;
+        const u64 v = i < nblk ? blk[i] : 0;
+        const u64 inc = wave_inclusive_scan64(v);
+        if (lane == 63) wsum[wave] = inc;
+        __syncthreads();
+        u64 before = 0, sum = 0;
+#pragma unroll
+        for (int w = 0; w < 16; w++) {
+            const u64 x = wsum[w];
+            before += w < wave ? x : 0;
+            sum += x;
+        }
+        if (i < nblk) blk[i] = carry + before + inc - v;
+        carry += sum;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        *total = carry;
+        if (flags && carry >= (1ull << 31)) *flags |= CC_F_MANY;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- union-find over runs
+__device__ static inline u32 cc_load(const u32 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// the root above x as far as this thread can see it (ids strictly decrease along the way: at most x steps)
+__device__ static inline u32 cc_find(const u32 *parent, u32 x)
+{
+    u32 p = cc_load(parent + x);
+    while (p < x) {
+        x = p;
+        p = cc_load(parent + x);
+    }
+    return x;
+}
+
+// ... and every run on the way is pointed at it (atomicMin: a parent never rises)
+__device__ static inline u32 cc_find_compress(u32 *parent, u32 x)
+{
+    const u32 r = cc_find(parent, x);
+    while (x > r) {
+        const u32 old = atomicMin(parent + x, r);
+        if (old >= x) break;
+        x = old;
+    }
+    return r;
+}
+
+__device__ static inline void cc_union(u32 *parent, u32 a, u32 b)
+{
+    while (true) {
+        a = cc_find_compress(parent, a);
+        b = cc_find_compress(parent, b);
+        if (a == b) return;
+        if (a < b) { const u32 t = a; a = b; b = t; }       // a > b: hook a under b
+        const u32 old = atomicMin(parent + a, b);
+        if (old >= a) return;                               // a was a root: hooked (old == a; > a cannot be)
+        a = old;                                            // somebody hooked a first, under old < a: unite old and b
+    }
+}
+
+// 0-based component of a run once the trees are flat and the roots are numbered (a parent above its run cannot be: the run
+// stands for itself then, and nothing is read outside the tables)
+__device__ static inline u32 cc_component(const u32 *__restrict__ parent, const u32 *__restrict__ rank, u32 run)
+{
+    const u32 p = parent[run];
+    return rank[p < run ? p : run];
+}
+
+// ---------------------------------------------------------------------------------------------- the keep rule
+// one workgroup: tot[3] = label of the largest component with at least min_voxels voxels, the lowest label among equals; 0: none
+// (the size of component c is sizes[STRIDE * c]: 1 for the sizes table, CC_COLS for column 0 of the measurement table)
+template <int STRIDE>
+__global__ __launch_bounds__(1024) void cc_largest_kernel(const unsigned long long *__restrict__ sizes, u64 *tot, int64_t cap,
+                                                          int64_t cap_runs, u64 min_voxels)
+{
+    __shared__ u64 bs[16];
+    __shared__ u64 bl[16];
+    u64 n = tot[1];
+    if (n > (u64)cap || tot[0] > (u64)cap_runs) n = 0;
+    u64 best = 0, lab = 0;                                  // lab 0: nothing yet
+    for (u64 c = threadIdx.x; c < n; c += 1024) {           // ascending labels: a later equal size never replaces
+        const u64 s = sizes[STRIDE * c];
+        if (s >= min_voxels && s > 0 && (lab == 0 || s > best)) { best = s; lab = c + 1; }
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const u64 os = __shfl_xor(best, d, 64), ol = __shfl_xor(lab, d, 64);
+        if (ol != 0 && (lab == 0 || os > best || (os == best && ol < lab))) { best = os; lab = ol; }
+    }
+    if ((threadIdx.x & 63) == 0) { bs[threadIdx.x >> 6] = best; bl[threadIdx.x >> 6] = lab; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 16; w++)
+            if (bl[w] != 0 && (lab == 0 || bs[w] > best || (bs[w] == best && bl[w] < lab))) { best = bs[w]; lab = bl[w]; }
+        tot[3] = lab;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- per word: which run is a bit in?
+// runs that start in the words of the row in front of word wj, + the row's first run id
+__device__ static inline u32 cc_before(const u64 *__restrict__ row, int nx, int wx, int wj, u32 first)
+{
+    for (int w = 0; w < wj; w++) first += (u32)__popcll(cc_starts(row, nx, wx, w, cc_word(row, nx, wx, w)));
+    return first;
+}
+
+// bit b of a word belongs to run before + popcount(starts & bits 0 .. b) - 1, before = cc_before and starts = cc_starts of the
+// word (a run that came in from the word before has no start bit here)
+__device__ static inline u32 cc_run_at(u32 before, u64 starts, int bit)
+{
+    return before + (u32)__popcll(starts & (~0ull >> (63 - bit))) - 1;
+}
+
+// the run of the SET bit `bit` of word wj of a row whose first run has the id `first`
+__device__ static inline u32 cc_run_of_bit(const u64 *__restrict__ row, int nx, int wx, int wj, int bit, u32 first)
+{
+    return cc_run_at(cc_before(row, nx, wx, wj, first), cc_starts(row, nx, wx, wj, cc_word(row, nx, wx, wj)), bit);
+}
+
+// The runs that touch ONE word, in ascending x.  Set m = the word, carry = the word before ended inside a run, next = the id of
+// the next run that STARTS (cc_before for a word on its own; it carries on from word to word of a row); every
+// cc_word_runs_next that returns true leaves the run's bits of this word in mask and its id in run.
+struct CcWordRuns {
+    u64 m;
+    u32 next;
+    bool carry;
+    u64 mask;
+    u32 run;
+};
+
+__device__ static inline bool cc_word_runs_next(CcWordRuns &it)
+{
+    if (!it.m) return false;                                // every turn clears at least one bit of m
+    const int s = __ffsll((long long)it.m) - 1;
+    const u64 z = ~(it.m >> s);                             // bit k: position s + k is clear (the shift brings zeros in from the top)
+    const int len = z ? __ffsll((long long)z) - 1 : 64;
+    it.mask = len >= 64 ? ~0ull : ((1ull << len) - 1) << s;
+    it.run = (s == 0 && it.carry) ? it.next - 1 : it.next++;
+    it.m &= ~it.mask;
+    return true;
+}
+
+// ---------------------------------------------------------------------------------------------- the row pass
+// One thread per row adds up what the row gives per component: neighbouring runs of one component first, flushed to the
+// tables when the component changes; then a wave whose lanes all hold the same component combines and flushes once (one solid
+// body: one set of atomics per 64 rows).  What is added up, how it combines and which atomics flush it, checked against which
+// bound, is the kernel's ACCUMULATOR:
+//   bool any() const              something has been added up since begin
+//   u32 begin(u32 c, ...)         start afresh for component c (1-based) -> c, or 0 to refuse it
+//   void add(...)                 (the arguments are the CcRuns at the run, in cc_row_walk)
+//   void flush(u32 c) const       one lane's own, into component c (0-based)
+//   W combine(bool mine, u32 zz) const    the sum over the lanes with `mine`, for slice zz: again has any() and flush(c)
+//   u32 filter(u32 c) const       FILTER only: c if the component is counted at all, else 0
+
+// the component changed: flush what was added up, then start afresh
+template <class Acc, class... At>
+__device__ static inline u32 cc_change(u32 &comp, u32 c, Acc &acc, const At &...at)
+{
+    if (c != comp) {
+        if (acc.any()) acc.flush(comp - 1);
+        comp = c = acc.begin(c, at...);
+    }
+    return c;
+}
+
+// the runs of one row -> the component + 1 the thread is left adding up.  A run id outside the tables stops the walk.
+template <bool FILTER, class Acc>
+__device__ static inline u32 cc_row_walk(const u64 *__restrict__ bits, int64_t row, int nx, int wx, const u32 *__restrict__ row_off,
+                                         u32 nruns, const u32 *__restrict__ parent, const u32 *__restrict__ rank, u64 *flags, Acc &acc)
+{
+    u32 comp = 0;
+    CcRuns a = cc_runs_begin(bits, row, nx, wx);
+    u32 ia = row_off[row];
+    while (a.valid) {
+        if (ia >= nruns) {
+            cc_flag(flags, CC_F_RANGE);
+            break;
+        }
+        u32 c = cc_component(parent, rank, ia) + 1;
+        if constexpr (FILTER) c = acc.filter(c);
+        c = cc_change(comp, c, acc, a);
+        if (!FILTER || c) acc.add(a);
+        cc_runs_next(a);
+        ia++;
+    }
+    return comp;
+}
+
+// The wave tail.  comp: the component + 1 the lane holds, z: the slice of its row.  SLICED: the lanes combine once per slice
+// the wave's rows lie in -- mostly one, more where the wave straddles slices (ny < 64) -- otherwise once, whatever the slices.
+template <bool SLICED, class Acc>
+__device__ static inline void cc_wave_tail(u32 comp, u32 z, const Acc &acc)
+{
+    if (!acc.any()) comp = 0;
+    const u32 top = wave_max32(comp);
+    if (top == 0) return;                                   // wave-uniform
+    if (__all(comp == 0 || comp == top)) {
+        const u32 zlo = SLICED ? wave_min32(comp ? z : ~0u) : 0u, zhi = SLICED ? wave_max32(comp ? z : 0u) : 0u;
+        for (u32 zz = zlo; zz <= zhi; zz++) {               // wave-uniform bounds: at most 64 slices hold the wave's 64 rows
+            const auto w = acc.combine(comp != 0 && (!SLICED || z == zz), zz);
+            if ((threadIdx.x & 63) == 0 && w.any()) w.flush(top - 1);
+        }
+    } else if (comp != 0) {
+        acc.flush(comp - 1);
+    }
+}
+
+// the simplest accumulator: one u64 per component, out[c] += sum while c < bound (a two's complement sum may cancel to 0)
+struct CcSumAcc {
+    unsigned long long *out;
+    u32 bound;
+    u64 sum;
+    __device__ bool any() const { return sum != 0; }
+    template <class... At>
+    __device__ u32 begin(u32 c, const At &...) { sum = 0; return c; }
+    __device__ void add(const CcRuns &a) { sum += (u64)(a.e - a.s); }
+    __device__ void flush(u32 c) const { if (c < bound) atomicAdd(out + c, (unsigned long long)sum); }
+    __device__ CcSumAcc combine(bool mine, u32) const { return {out, bound, wave_sum64(mine ? sum : 0)}; }
+};

@@ -1,0 +1,981 @@
+// component_measures.hip -- what is measured per component on the run tables of components.hip: the measurement table
+// (voxels, box, index sums), the selection and its slice histograms (voxels, or six moment sums, per component and slice),
+// volume and centroid in mm, second moments and principal axes, Euler number, cavities and handles.  Every pass over the
+// rows is an accumulator for the row pass of cc_runs.h; the integer tables are integer atomics only, the float results are
+// sequential sums over those integers (nothing is contracted in this file: -ffp-contract=off).
+#include "cc_runs.h"
+
+// ---------------------------------------------------------------------------------------------- measurements per component
+// table (device int64[cap][CC_COLS]), row c = component c + 1: [0] voxels  [1, 2] zmin, zmax  [3, 4] ymin, ymax  [5, 6] xmin,
+// xmax (inclusive indices)  [7] sum of z over the voxels  [8] sum of y  [9] sum of x.  Every entry is a non-negative integer
+// below 2^63, so the kernels work on it as u64 and the 64-bit unsigned min / max / add atomics keep it exact and the same on
+// every run.  The count of components comes from tot[1]; more than the table's rows: nothing is touched (CC_F_CAP).
+
+// the minima start at the largest int64 (a memset cannot give that), everything else at 0
+__global__ __launch_bounds__(CC_THREADS) void cc_table_init_kernel(u64 *__restrict__ table, int64_t cap)
+{
+    const int64_t i = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    if (i >= cap * CC_COLS) return;
+    const int col = (int)(i % CC_COLS);
+    table[i] = (col == 1 || col == 3 || col == 5) ? 0x7fffffffffffffffull : 0ull;
+}
+
+// what a thread, or a wave, flushes for ONE component
+struct CcMeasureSum {
+    u64 *table;
+    u32 ncomp;
+    u64 vox, sz, sy, sx;
+    u32 z0, z1, y0, y1, x0, x1;
+    __device__ bool any() const { return vox != 0; }
+    __device__ void flush(u32 c) const
+    {
+        if (c >= ncomp) return;
+        u64 *t = table + (int64_t)c * CC_COLS;
+        atomicAdd(t + 0, vox);
+        atomicMin(t + 1, (u64)z0);
+        atomicMax(t + 2, (u64)z1);
+        atomicMin(t + 3, (u64)y0);
+        atomicMax(t + 4, (u64)y1);
+        atomicMin(t + 5, (u64)x0);
+        atomicMax(t + 6, (u64)x1);
+        atomicAdd(t + 7, sz);
+        atomicAdd(t + 8, sy);
+        atomicAdd(t + 9, sx);
+    }
+};
+
+// The accumulator of row (z, y): a run [s, e) adds len = e - s voxels and len * (s + e - 1) / 2 = s + (s + 1) + .. + (e - 1)
+// (len or s + e - 1 is even: exact) and widens the box in x; the record multiplies the voxels by z and y.  A wave combines
+// once whatever slices its rows lie in -- every lane brings its own z and y: ten atomics per 64 rows of one solid body.
+struct CcMeasureAcc {
+    u64 *table;
+    u32 ncomp, z, y;
+    u64 vox, sx;
+    u32 x0, x1;
+    __device__ bool any() const { return vox != 0; }
+    __device__ u32 begin(u32 c, const CcRuns &a)
+    {
+        vox = sx = 0;
+        x0 = (u32)a.s;
+        return c;
+    }
+    __device__ void add(const CcRuns &a)
+    {
+        const u64 len = (u64)(a.e - a.s);
+        vox += len;
+        sx += len * (u64)(a.s + a.e - 1) / 2;
+        x1 = (u32)(a.e - 1);                                // the runs ascend
+    }
+    __device__ CcMeasureSum record() const { return {table, ncomp, vox, vox * z, vox * y, sx, z, z, y, y, x0, x1}; }
+    __device__ void flush(u32 c) const { record().flush(c); }
+    __device__ CcMeasureSum combine(bool has, u32) const
+    {
+        const CcMeasureSum m = record();
+        return {table, ncomp, wave_sum64(m.vox), wave_sum64(has ? m.sz : 0), wave_sum64(has ? m.sy : 0), wave_sum64(m.sx),
+                wave_min32(has ? m.z0 : ~0u), wave_max32(has ? m.z1 : 0u), wave_min32(has ? m.y0 : ~0u), wave_max32(has ? m.y1 : 0u),
+                wave_min32(has ? m.x0 : ~0u), wave_max32(has ? m.x1 : 0u)};       // vox and sx are 0 where nothing is held
+    }
+};
+
+__global__ __launch_bounds__(CC_THREADS) void cc_measure_kernel(const u64 *__restrict__ bits, int64_t nrows, int ny, int nx, int wx,
+                                                                const u32 *__restrict__ row_off, const u64 *__restrict__ tot,
+                                                                int64_t cap_runs, const u32 *__restrict__ parent,
+                                                                const u32 *__restrict__ rank, u64 *__restrict__ table, int64_t cap,
+                                                                u64 *flags)
+{
+    const int64_t row = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    const u32 nruns = (u32)cc_count(tot, cap_runs);
+    if (row == 0 && tot[1] > (u64)cap) cc_flag(flags, CC_F_CAP);
+    const bool live = row < nrows;
+    CcMeasureAcc acc = {table, (u32)cc_ncomp(tot, cap), live ? (u32)(row / ny) : 0u, live ? (u32)(row % ny) : 0u, 0, 0, 0, 0};
+    u32 comp = 0;
+    if (live) comp = cc_row_walk<false>(bits, row, nx, wx, row_off, nruns, parent, rank, flags, acc);
+    cc_wave_tail<false>(comp, acc.z, acc);
+}
+
+TOMO_API int tomo_cc_measure(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                             const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, int64_t *table, int64_t cap,
+                             void *stream)
+{
+    int64_t nrows;
+    int wx;
+    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
+    if (g != TOMO_OK) return g;
+    if (!row_off || !parent || !rank || !tot || !table || cap_runs <= 0 || cap <= 0) return TOMO_E_ARG;
+    if (cap_runs >= ((int64_t)1 << 31) || cap >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(cc_table_init_kernel, dim3((unsigned)ceil_div64(cap * CC_COLS, CC_THREADS)), dim3(CC_THREADS), 0, st,
+                       (u64 *)table, cap);
+    hipLaunchKernelGGL(cc_measure_kernel, dim3((unsigned)ceil_div64(nrows, CC_THREADS)), dim3(CC_THREADS), 0, st, (const u64 *)bits,
+                       nrows, ny, nx, wx, (const u32 *)row_off, (const u64 *)tot, cap_runs, (const u32 *)parent, (const u32 *)rank,
+                       (u64 *)table, cap, (u64 *)tot + 2);
+    return tomo_status();
+}
+
+// ---------------------------------------------------------------------------------------------- voxels per component and slice
+// The volume of a component under per-slice depths needs its voxels PER SLICE.  The selected components (the keep rule of
+// tomo_cc_filter on column 0 of the table) get a segment of zmax - zmin + 1 counters each in one histogram: off = the
+// exclusive scan of the segment lengths, 0-length for the others, in 64 bits (2^31 components of up to 2^31 slices), and
+// slot = the exclusive scan of the selection = the row of a selected component in the compacted results.
+// tot[4] = all counters, tot[5] = selected components.
+__device__ static inline bool cc_selected(const u64 *__restrict__ table, const u64 *__restrict__ tot, int64_t c, u64 min_voxels,
+                                          int largest)
+{
+    return largest ? (u64)c + 1 == tot[3] : table[c * CC_COLS] >= min_voxels;
+}
+
+// length of the segment of component c (0: not selected, or a box that is none)
+__device__ static inline u64 cc_zspan(const u64 *__restrict__ table, const u64 *__restrict__ tot, int64_t c, u64 min_voxels,
+                                      int largest, bool *sel)
+{
+    const u64 z0 = table[c * CC_COLS + 1], z1 = table[c * CC_COLS + 2];
+    *sel = cc_selected(table, tot, c, min_voxels, largest);
+    return *sel && z1 >= z0 ? z1 - z0 + 1 : 0;
+}
+
+
+// per tile of CC_SCAN_TILE components: blk[b] = its counters, blk[nblk + b] = its selected components; sel[c] on the way
+__global__ __launch_bounds__(CC_THREADS) void cc_zspan_blocksum_kernel(const u64 *__restrict__ table, const u64 *__restrict__ tot,
+                                                                       int64_t cap, u64 min_voxels, int largest,
+                                                                       uint8_t *__restrict__ sel, u64 *__restrict__ blk, int64_t nblk,
+                                                                       u64 *flags)
+{
+    __shared__ u64 wsum[2][CC_THREADS / 64];
+    const int64_t n = cc_ncomp(tot, cap);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && tot[1] > (u64)cap) cc_flag(flags, CC_F_CAP);
+    const int64_t i0 = (int64_t)blockIdx.x * CC_SCAN_TILE + 4 * threadIdx.x;
+    u64 span = 0, cnt = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        if (i0 + j < n) {
+            bool s;
+            span += cc_zspan(table, tot, i0 + j, min_voxels, largest, &s);
+            cnt += s ? 1 : 0;
+            sel[i0 + j] = s ? 1 : 0;
+        }
+    }
+    span = wave_sum64(span);
+    cnt = wave_sum64(cnt);
+    if ((threadIdx.x & 63) == 0) {
+        wsum[0][threadIdx.x >> 6] = span;
+        wsum[1][threadIdx.x >> 6] = cnt;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        blk[blockIdx.x] = wsum[0][0] + wsum[0][1] + wsum[0][2] + wsum[0][3];
+        blk[nblk + blockIdx.x] = wsum[1][0] + wsum[1][1] + wsum[1][2] + wsum[1][3];
+    }
+}
+
+// off[c], slot[c] for every c < n and off[n] = all counters (written by the thread that holds component n - 1)
+__global__ __launch_bounds__(CC_THREADS) void cc_zspan_apply_kernel(const u64 *__restrict__ table, const u64 *__restrict__ tot,
+                                                                    int64_t cap, u64 min_voxels, int largest,
+                                                                    const u64 *__restrict__ blk, int64_t nblk, u64 *__restrict__ off,
+                                                                    u32 *__restrict__ slot)
+{
+    __shared__ u64 wsum[2][CC_THREADS / 64];
+    const int64_t n = cc_ncomp(tot, cap);
+    const int64_t i0 = (int64_t)blockIdx.x * CC_SCAN_TILE + 4 * threadIdx.x;
+    u64 x[4], k[4];
+    u64 span = 0, cnt = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        bool s = false;
+        x[j] = i0 + j < n ? cc_zspan(table, tot, i0 + j, min_voxels, largest, &s) : 0;
+        k[j] = s ? 1 : 0;
+        span += x[j];
+        cnt += k[j];
+    }
+    const u64 ispan = wave_inclusive_scan64(span), icnt = wave_inclusive_scan64(cnt);
+    if ((threadIdx.x & 63) == 63) {
+        wsum[0][threadIdx.x >> 6] = ispan;
+        wsum[1][threadIdx.x >> 6] = icnt;
+    }
+    __syncthreads();
+    u64 bspan = 0, bcnt = 0;
+    for (int w = 0; w < (int)(threadIdx.x >> 6); w++) {
+        bspan += wsum[0][w];
+        bcnt += wsum[1][w];
+    }
+    u64 run = blk[blockIdx.x] + bspan + ispan - span, num = blk[nblk + blockIdx.x] + bcnt + icnt - cnt;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        if (i0 + j < n) {
+            off[i0 + j] = run;
+            slot[i0 + j] = (u32)num;
+            if (i0 + j == n - 1) off[n] = run + x[j];
+        }
+        run += x[j];
+        num += k[j];
+    }
+}
+
+TOMO_API int tomo_cc_zhist_offsets(const int64_t *table, int64_t cap, unsigned long long *tot, int64_t min_voxels, int largest,
+                                   uint8_t *sel, uint64_t *off, uint32_t *slot, uint64_t *blk, void *stream)
+{
+    if (!table || !tot || !sel || !off || !slot || !blk || cap <= 0 || min_voxels < 0) return TOMO_E_ARG;
+    if (cap >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
+    hipStream_t st = (hipStream_t)stream;
+    const u64 *t = (const u64 *)table;
+    u64 *tt = (u64 *)tot;
+    const int64_t nblk = ceil_div64(cap, CC_SCAN_TILE);
+    if (largest)                                            // no run table is read here: only the count of components is capped
+        hipLaunchKernelGGL(cc_largest_kernel<CC_COLS>, dim3(1), dim3(1024), 0, st, (const unsigned long long *)t, tt, cap,
+                           (int64_t)0x7fffffffffffffffll, (u64)min_voxels);
+    hipLaunchKernelGGL(cc_zspan_blocksum_kernel, dim3((unsigned)nblk), dim3(CC_THREADS), 0, st, t, (const u64 *)tt, cap,
+                       (u64)min_voxels, largest ? 1 : 0, sel, (u64 *)blk, nblk, tt + 2);
+    hipLaunchKernelGGL(cc_scan1_kernel, dim3(1), dim3(1024), 0, st, (u64 *)blk, nblk, tt + 4, (u64 *)nullptr);
+    hipLaunchKernelGGL(cc_scan1_kernel, dim3(1), dim3(1024), 0, st, (u64 *)blk + nblk, nblk, tt + 5, (u64 *)nullptr);
+    hipLaunchKernelGGL(cc_zspan_apply_kernel, dim3((unsigned)nblk), dim3(CC_THREADS), 0, st, t, (const u64 *)tt, cap, (u64)min_voxels,
+                       largest ? 1 : 0, (const u64 *)blk, nblk, (u64 *)off, (u32 *)slot);
+    return tomo_status();
+}
+
+// ---------------------------------------------------------------------------------------------- sums per component and slice
+// The segments of tomo_cc_zhist_offsets hold SUMS words per entry: hist[SUMS * (off[c] + z - zmin) + k].  One word is the
+// count of voxels (tomo_cc_zhist).  CC_MOMS words are what second moments need (tomo_cc_moment_hist): a set voxel (k, j, i) of
+// component c is a point mass at (zc[k], j * mm_y, i * mm_x) of weight w[k] = (mm_x * mm_y) * depth[k], and per slice of the
+// component's box six integer sums over the slice's voxels of the component do, taken about the box corner (j' = j - ymin,
+// i' = i - xmin) to keep them small: N, sum j', sum i', sum j'^2, sum i'^2, sum j' i'.
+#define CC_MOMS 6                    // sums per component and slice
+#define CC_MOMENT_COLS 22            // doubles per row of tomo_cc_moments' output
+#define CC_JACOBI_SWEEPS 32          // limit of the cyclic Jacobi iteration (a 3 x 3 matrix is done in 5 or 6)
+
+// 0^2 + 1^2 + .. + (n - 1)^2 = (n - 1) n (2 n - 1) / 6; n <= nx, and tomo_cc_moment_hist refuses max(ny, nx)^3 >= 2^63
+__device__ static inline u64 cc_squares_below(u64 n)
+{
+    return (n - 1) * n * (2 * n - 1) / 6;                   // n = 0: the wrapped factor meets a 0
+}
+
+struct CcHist {
+    const u64 *table, *off;
+    u64 *hist;
+    u64 total;                                              // entries of the histogram
+    u64 *flags;
+};
+
+// hist[SUMS * (off[c] + z - zmin[c]) + k] += v[k]: checked against the component's box and the histogram's length before the adds
+template <int SUMS>
+__device__ static inline void cc_hist_add(const CcHist &h, u32 c, u32 z, const u64 (&v)[SUMS])
+{
+    const u64 z0 = h.table[(int64_t)c * CC_COLS + 1], z1 = h.table[(int64_t)c * CC_COLS + 2];
+    const u64 pos = h.off[c] + ((u64)z - z0);
+    if (z < z0 || z > z1 || pos >= h.total) {
+        cc_flag(h.flags, CC_F_RANGE);
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < SUMS; k++)
+        if (SUMS == 1 || v[k]) atomicAdd(h.hist + SUMS * pos + k, v[k]);
+}
+
+template <int SUMS>
+struct CcSliceSum {
+    const CcHist &h;
+    u32 z;
+    u64 v[SUMS];
+    __device__ bool any() const { return v[0] != 0; }
+    __device__ void flush(u32 c) const { cc_hist_add<SUMS>(h, c, z, v); }
+};
+
+// The accumulator of row (z, y); only the runs of selected components count.  A run [s, e) adds its length and, SUMS > 1, in
+// closed form the sums of i' and i'^2 over it; the row supplies the factors j' when a record is made.  A voxel in front of the
+// box corner (the bits changed since tomo_cc_measure) is CC_F_RANGE and adds nothing; with one sum the corner is never read.
+template <int SUMS>
+struct CcSliceAcc {
+    CcHist h;
+    const uint8_t *sel;
+    u32 ncomp, z, y;
+    u64 n, si, sii;
+    u64 x0, jp;                                             // the component's box corner in x, the row's j' in its box
+    __device__ u32 filter(u32 c) const { return (c - 1 >= ncomp || !sel[c - 1]) ? 0u : c; }
+    __device__ bool any() const { return n != 0; }
+    __device__ u32 begin(u32 c, const CcRuns &)
+    {
+        n = si = sii = 0;
+        if constexpr (SUMS > 1) {
+            if (c) {
+                const u64 y0 = h.table[(int64_t)(c - 1) * CC_COLS + 3];
+                x0 = h.table[(int64_t)(c - 1) * CC_COLS + 5];
+                jp = (u64)y - y0;
+                if ((u64)y < y0) {
+                    cc_flag(h.flags, CC_F_RANGE);
+                    return 0;
+                }
+            }
+        }
+        return c;
+    }
+    __device__ void add(const CcRuns &a)
+    {
+        if constexpr (SUMS == 1) {
+            n += (u64)(a.e - a.s);
+        } else if ((u64)a.s < x0) {
+            cc_flag(h.flags, CC_F_RANGE);
+        } else {
+            const u64 s = (u64)a.s - x0, e = (u64)a.e - x0, len = e - s;
+            n += len;
+            si += len * (s + e - 1) / 2;                    // len or s + e - 1 is even: exact
+            sii += cc_squares_below(e) - cc_squares_below(s);
+        }
+    }
+    __device__ CcSliceSum<SUMS> record() const
+    {
+        if constexpr (SUMS == 1) return {h, z, {n}};
+        else return {h, z, {n, jp * n, si, jp * jp * n, sii, jp * si}};
+    }
+    __device__ void flush(u32 c) const { record().flush(c); }
+    __device__ CcSliceSum<SUMS> combine(bool mine, u32 zz) const
+    {
+        const CcSliceSum<SUMS> r = record();
+        CcSliceSum<SUMS> w = {h, zz};
+#pragma unroll
+        for (int k = 0; k < SUMS; k++) w.v[k] = wave_sum64(mine ? r.v[k] : 0);
+        return w;
+    }
+};
+
+template <int SUMS>
+__global__ __launch_bounds__(CC_THREADS) void cc_slice_hist_kernel(const u64 *__restrict__ bits, int64_t nrows, int ny, int nx, int wx,
+                                                                   const u32 *__restrict__ row_off, const u64 *__restrict__ tot,
+                                                                   int64_t cap_runs, const u32 *__restrict__ parent,
+                                                                   const u32 *__restrict__ rank, const u64 *__restrict__ table,
+                                                                   int64_t cap, const uint8_t *__restrict__ sel,
+                                                                   const u64 *__restrict__ off, u64 *__restrict__ hist,
+                                                                   int64_t hist_cap, u64 *flags)
+{
+    const int64_t row = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    const u32 nruns = (u32)cc_count(tot, cap_runs);
+    const u64 total = tot[4];
+    const bool fits = total <= (u64)hist_cap;
+    const u32 ncomp = fits ? (u32)cc_ncomp(tot, cap) : 0u;  // a histogram that is too short: nothing is touched
+    if (row == 0 && (!fits || tot[1] > (u64)cap)) cc_flag(flags, CC_F_CAP);
+    const bool live = row < nrows;
+    CcSliceAcc<SUMS> acc = {{table, off, hist, total, flags}, sel, ncomp, live ? (u32)(row / ny) : 0u, live ? (u32)(row % ny) : 0u,
+                            0, 0, 0, 0, 0};
+    u32 comp = 0;                                           // SELECTED component + 1 the thread is left with, 0: none
+    if (live) comp = cc_row_walk<true>(bits, row, nx, wx, row_off, nruns, parent, rank, flags, acc);
+    cc_wave_tail<true>(comp, acc.z, acc);
+}
+
+template <int SUMS>
+static int cc_slice_hist(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
+                         const uint32_t *rank, unsigned long long *tot, const int64_t *table, int64_t cap, const uint8_t *sel,
+                         const uint64_t *off, uint64_t *hist, int64_t hist_cap, void *stream)
+{
+    int64_t nrows;
+    int wx;
+    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
+    if (g != TOMO_OK) return g;
+    if (!row_off || !parent || !rank || !tot || !table || !sel || !off || !hist || cap_runs <= 0 || cap <= 0 || hist_cap <= 0)
+        return TOMO_E_ARG;
+    if (cap_runs >= ((int64_t)1 << 31) || cap >= ((int64_t)1 << 31) || hist_cap >= ((int64_t)1 << 60) / SUMS) return TOMO_E_SIZE;
+    const unsigned __int128 side = (unsigned __int128)(ny > nx ? ny : nx);
+    if (SUMS > 1 && (unsigned __int128)ny * (unsigned __int128)nx * side * side >= ((unsigned __int128)1 << 63))
+        return TOMO_E_SIZE;                                 // a slice's sum of j'^2, i'^2 or j' i' could leave 63 bits
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(hist, 0, (size_t)hist_cap * SUMS * sizeof(u64), st) != hipSuccess) return TOMO_E_LAUNCH;
+    hipLaunchKernelGGL(cc_slice_hist_kernel<SUMS>, dim3((unsigned)ceil_div64(nrows, CC_THREADS)), dim3(CC_THREADS), 0, st,
+                       (const u64 *)bits, nrows, ny, nx, wx, (const u32 *)row_off, (const u64 *)tot, cap_runs, (const u32 *)parent,
+                       (const u32 *)rank, (const u64 *)table, cap, sel, (const u64 *)off, (u64 *)hist, hist_cap, (u64 *)tot + 2);
+    return tomo_status();
+}
+
+TOMO_API int tomo_cc_zhist(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                           const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const int64_t *table, int64_t cap,
+                           const uint8_t *sel, const uint64_t *off, uint64_t *hist, int64_t hist_cap, void *stream)
+{
+    return cc_slice_hist<1>(bits, nz, ny, nx, row_off, cap_runs, parent, rank, tot, table, cap, sel, off, hist, hist_cap, stream);
+}
+
+TOMO_API int tomo_cc_moment_hist(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                                 const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const int64_t *table,
+                                 int64_t cap, const uint8_t *sel, const uint64_t *off, uint64_t *mom, int64_t hist_cap, void *stream)
+{
+    return cc_slice_hist<CC_MOMS>(bits, nz, ny, nx, row_off, cap_runs, parent, rank, tot, table, cap, sel, off, mom, hist_cap, stream);
+}
+
+// ---------------------------------------------------------------------------------------------- per selected component: its segment
+struct CcSegment {
+    u64 z0, z1, o;                                          // its slices and where their entries start
+    u32 k;                                                  // its row in the compacted results
+};
+
+// One thread per component c -> true and the segment if c is selected and everything fits; thread 0 flags what does not fit
+// (CC_F_CAP: nothing is written at all), a segment outside the stack or the histogram is CC_F_RANGE.
+__device__ static inline bool cc_segment(const u64 *__restrict__ table, const u64 *__restrict__ tot, int64_t cap,
+                                         const uint8_t *__restrict__ sel, const u64 *__restrict__ off, const u32 *__restrict__ slot,
+                                         int64_t hist_cap, int nz, int64_t cap_sel, int64_t c, u64 *flags, CcSegment &s)
+{
+    const u64 total = tot[4];
+    const bool fits = total <= (u64)hist_cap && tot[5] <= (u64)cap_sel && tot[1] <= (u64)cap;
+    if (c == 0 && !fits) cc_flag(flags, CC_F_CAP);
+    if (!fits || c >= cc_ncomp(tot, cap) || !sel[c]) return false;
+    s.z0 = table[c * CC_COLS + 1];
+    s.z1 = table[c * CC_COLS + 2];
+    s.o = off[c];
+    s.k = slot[c];
+    if (s.z1 < s.z0 || s.z1 >= (u64)nz || s.o + (s.z1 - s.z0) >= total || (int64_t)s.k >= cap_sel) {
+        cc_flag(flags, CC_F_RANGE);
+        return false;
+    }
+    return true;
+}
+
+// what `count` voxels of a slice of weight w, centred at zc, add to a component's volume and z moment -> the slice's volume.
+// Plain sequential float64: over the slices in ascending z, vol is the float a host loop over the slices of the mask
+// `labels == c` gives -- the slices outside the box add 0.0 there.
+__device__ static inline double cc_slice_volume(u64 count, double w, double zc, double &vol, double &mz)
+{
+    const double v = (double)count * w;
+    vol += v;
+    mz += v * zc;
+    return v;
+}
+
+// One thread per component; a selected one walks its slices in ascending z.  out[slot[c]] = (vol, mz), labels[slot[c]] = c + 1.
+__global__ __launch_bounds__(CC_THREADS) void cc_zsums_kernel(const u64 *__restrict__ table, const u64 *__restrict__ tot, int64_t cap,
+                                                              const uint8_t *__restrict__ sel, const u64 *__restrict__ off,
+                                                              const u32 *__restrict__ slot, const u64 *__restrict__ hist,
+                                                              int64_t hist_cap, const double *__restrict__ w,
+                                                              const double *__restrict__ zc, int nz, double *__restrict__ out,
+                                                              int64_t *__restrict__ labels, int64_t cap_sel, u64 *flags)
+{
+    const int64_t c = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    CcSegment s;
+    if (!cc_segment(table, tot, cap, sel, off, slot, hist_cap, nz, cap_sel, c, flags, s)) return;
+    double vol = 0.0, mz = 0.0;
+    for (u64 z = s.z0; z <= s.z1; z++) cc_slice_volume(hist[s.o + (z - s.z0)], w[z], zc[z], vol, mz);
+    out[2 * (int64_t)s.k] = vol;
+    out[2 * (int64_t)s.k + 1] = mz;
+    labels[s.k] = c + 1;
+}
+
+TOMO_API int tomo_cc_zsums(const int64_t *table, int64_t cap, unsigned long long *tot, const uint8_t *sel, const uint64_t *off,
+                           const uint32_t *slot, const uint64_t *hist, int64_t hist_cap, const double *w, const double *zc, int nz,
+                           double *out, int64_t *labels, int64_t cap_sel, void *stream)
+{
+    if (!table || !tot || !sel || !off || !slot || !hist || !w || !zc || !out || !labels || cap <= 0 || hist_cap <= 0 || nz <= 0 ||
+        cap_sel <= 0)
+        return TOMO_E_ARG;
+    if (cap >= ((int64_t)1 << 31) || cap_sel >= ((int64_t)1 << 31) || hist_cap >= ((int64_t)1 << 60)) return TOMO_E_SIZE;
+    hipLaunchKernelGGL(cc_zsums_kernel, dim3((unsigned)ceil_div64(cap, CC_THREADS)), dim3(CC_THREADS), 0, (hipStream_t)stream,
+                       (const u64 *)table, (const u64 *)tot, cap, sel, (const u64 *)off, (const u32 *)slot, (const u64 *)hist, hist_cap,
+                       w, zc, nz, out, labels, cap_sel, (u64 *)tot + 2);
+    return tomo_status();
+}
+
+// ---------------------------------------------------------------------------------------------- second moments per component
+// One Jacobi rotation of a symmetric 3 x 3 matrix that annihilates a_pq (r = the third index): A <- J^T A J, the eigenvector
+// estimates ep, eq (columns p, q of the accumulated rotations) turn with it.  t is the smaller root, |t| <= 1.
+__device__ static inline void cc_jacobi_rotate(double &app, double &aqq, double &apq, double &arp, double &arq, double (&ep)[3],
+                                               double (&eq)[3])
+{
+    if (apq == 0.0) return;
+    const double theta = (aqq - app) / (2.0 * apq), at = fabs(theta);
+    double t = at > 1e150 ? 0.5 / at : 1.0 / (at + sqrt(at * at + 1.0));
+    if (theta < 0.0) t = -t;
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+    app = app - t * apq;
+    aqq = aqq + t * apq;
+    apq = 0.0;
+    const double rp = arp, rq = arq;
+    arp = c * rp - s * rq;
+    arq = s * rp + c * rq;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const double vp = ep[k], vq = eq[k];
+        ep[k] = c * vp - s * vq;
+        eq[k] = s * vp + c * vq;
+    }
+}
+
+// swap so that the larger eigenvalue comes first; equal ones keep their order
+__device__ static inline void cc_order_pair(double &la, double &lb, double (&ea)[3], double (&eb)[3])
+{
+    if (la < lb) {
+        const double l = la;
+        la = lb;
+        lb = l;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const double e = ea[k];
+            ea[k] = eb[k];
+            eb[k] = e;
+        }
+    }
+}
+
+// the component of largest magnitude positive, the first such on a tie
+__device__ static inline void cc_axis_sign(double (&e)[3])
+{
+    int k = 0;
+    if (fabs(e[1]) > fabs(e[k])) k = 1;
+    if (fabs(e[2]) > fabs(e[k])) k = 2;
+    if (e[k] < 0.0) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) e[j] = 0.0 - e[j];
+    }
+}
+
+// One thread per component, as cc_zsums_kernel; a selected one walks its slices in ascending z twice, plain sequential
+// float64.  First walk: W and the z moment by cc_zsums_kernel's very additions (cc_slice_volume), and
+// the first moments about the box corner (zc[zmin], ymin, xmin).  Second walk: the six central sums about the centre those
+// give.  Then cyclic Jacobi on the 3 x 3 covariance, the eigenvalues sorted descending (clamped at 0), the sign rule.
+// out[slot[c]] = W, centre (z, y, x) in mm, covariance zz zy zx yy yx xx, variances, axes (rows); labels[slot[c]] = c + 1.
+__global__ __launch_bounds__(CC_THREADS) void cc_moments_kernel(const u64 *__restrict__ table, const u64 *__restrict__ tot,
+                                                                int64_t cap, const uint8_t *__restrict__ sel,
+                                                                const u64 *__restrict__ off, const u32 *__restrict__ slot,
+                                                                const u64 *__restrict__ mom, int64_t hist_cap,
+                                                                const double *__restrict__ w, const double *__restrict__ zc, int nz,
+                                                                double mm_y, double mm_x, double *__restrict__ out,
+                                                                int64_t *__restrict__ labels, int64_t cap_sel, u64 *flags)
+{
+    const int64_t c = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    CcSegment seg;
+    if (!cc_segment(table, tot, cap, sel, off, slot, hist_cap, nz, cap_sel, c, flags, seg)) return;
+    const u64 z0 = seg.z0, z1 = seg.z1;
+    const u32 k = seg.k;
+    const u64 *m = mom + CC_MOMS * seg.o;
+    const double zo = zc[z0];
+    double vol = 0.0, mz = 0.0, sz = 0.0, sy = 0.0, sx = 0.0;
+    for (u64 z = z0; z <= z1; z++) {
+        const u64 *s = m + CC_MOMS * (z - z0);
+        const double v = cc_slice_volume(s[0], w[z], zc[z], vol, mz);
+        sz += v * (zc[z] - zo);
+        sy += w[z] * (double)s[1];
+        sx += w[z] * (double)s[2];
+    }
+    if (!(vol > 0.0)) {                                     // no voxel arrived in the segment: the bits changed
+        cc_flag(flags, CC_F_RANGE);
+        return;
+    }
+    const double cz = sz / vol, cy = sy / vol, cx = sx / vol;    // about the box corner: mm along z, indices in the plane
+    double qzz = 0.0, qzy = 0.0, qzx = 0.0, qyy = 0.0, qyx = 0.0, qxx = 0.0;
+    for (u64 z = z0; z <= z1; z++) {
+        const u64 *s = m + CC_MOMS * (z - z0);
+        const double n = (double)s[0], sj = (double)s[1], si = (double)s[2], sjj = (double)s[3], sii = (double)s[4],
+                     sji = (double)s[5];
+        const double dz = (zc[z] - zo) - cz;
+        const double a = sj - n * cy, b = si - n * cx;      // sums of j' - cy and of i' - cx over the slice
+        qzz += w[z] * (n * dz * dz);
+        qzy += w[z] * (dz * a);
+        qzx += w[z] * (dz * b);
+        qyy += w[z] * ((sjj - cy * sj) - cy * a);
+        qyx += w[z] * ((sji - cy * si) - cx * a);
+        qxx += w[z] * ((sii - cx * si) - cx * b);
+    }
+    double a00 = qzz / vol, a01 = qzy * mm_y / vol, a02 = qzx * mm_x / vol, a11 = qyy * (mm_y * mm_y) / vol,
+           a12 = qyx * (mm_y * mm_x) / vol, a22 = qxx * (mm_x * mm_x) / vol;
+    double *r = out + CC_MOMENT_COLS * (int64_t)k;
+    r[0] = vol;
+    r[1] = mz / vol;
+    r[2] = ((double)table[c * CC_COLS + 3] + cy) * mm_y;
+    r[3] = ((double)table[c * CC_COLS + 5] + cx) * mm_x;
+    r[4] = a00;
+    r[5] = a01;
+    r[6] = a02;
+    r[7] = a11;
+    r[8] = a12;
+    r[9] = a22;
+    double e0[3] = {1.0, 0.0, 0.0}, e1[3] = {0.0, 1.0, 0.0}, e2[3] = {0.0, 0.0, 1.0};
+    for (int sweep = 0; sweep < CC_JACOBI_SWEEPS; sweep++) {
+        const double offd = fabs(a01) + fabs(a02) + fabs(a12);
+        if (offd <= 0x1p-60 * (fabs(a00) + fabs(a11) + fabs(a22))) break;      // also a zero matrix
+        cc_jacobi_rotate(a00, a11, a01, a02, a12, e0, e1);
+        cc_jacobi_rotate(a00, a22, a02, a01, a12, e0, e2);
+        cc_jacobi_rotate(a11, a22, a12, a01, a02, e1, e2);
+    }
+    cc_order_pair(a00, a11, e0, e1);
+    cc_order_pair(a11, a22, e1, e2);
+    cc_order_pair(a00, a11, e0, e1);
+    cc_axis_sign(e0);
+    cc_axis_sign(e1);
+    cc_axis_sign(e2);
+    r[10] = a00 > 0.0 ? a00 : 0.0;
+    r[11] = a11 > 0.0 ? a11 : 0.0;
+    r[12] = a22 > 0.0 ? a22 : 0.0;
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        r[13 + j] = e0[j];
+        r[16 + j] = e1[j];
+        r[19 + j] = e2[j];
+    }
+    labels[k] = c + 1;
+}
+
+TOMO_API int tomo_cc_moments(const int64_t *table, int64_t cap, unsigned long long *tot, const uint8_t *sel, const uint64_t *off,
+                             const uint32_t *slot, const uint64_t *mom, int64_t hist_cap, const double *w, const double *zc, int nz,
+                             double mm_y, double mm_x, double *out, int64_t *labels, int64_t cap_sel, void *stream)
+{
+    if (!table || !tot || !sel || !off || !slot || !mom || !w || !zc || !out || !labels || cap <= 0 || hist_cap <= 0 || nz <= 0 ||
+        cap_sel <= 0 || !(mm_y > 0.0 && mm_y < __builtin_inf()) || !(mm_x > 0.0 && mm_x < __builtin_inf()))
+        return TOMO_E_ARG;                                  // a NaN fails both comparisons
+    if (cap >= ((int64_t)1 << 31) || cap_sel >= ((int64_t)1 << 31) || hist_cap >= ((int64_t)1 << 60) / CC_MOMS) return TOMO_E_SIZE;
+    hipLaunchKernelGGL(cc_moments_kernel, dim3((unsigned)ceil_div64(cap, CC_THREADS)), dim3(CC_THREADS), 0, (hipStream_t)stream,
+                       (const u64 *)table, (const u64 *)tot, cap, sel, (const u64 *)off, (const u32 *)slot, (const u64 *)mom, hist_cap,
+                       w, zc, nz, mm_y, mm_x, out, labels, cap_sel, (u64 *)tot + 2);
+    return tomo_status();
+}
+
+// ---------------------------------------------------------------------------------------------- Euler number, cavities, handles
+// chi of the set voxels as a sum over the voxels, every cell of the complex counted by exactly ONE of them, so that nothing is
+// divided and the voxels of a component add up to the component's chi (every cell touches voxels of one component only):
+//   connectivity 6:  the dual complex (a cell = 1, 2, 4 or 8 voxels that are ALL set) -- a cell belongs to its low-corner
+//                    voxel.  Voxel v adds 1 - [x] - [y] - [z] + [x y xy] + [x z xz] + [y z yz] - [all seven], the names
+//                    being the voxels of the 2 x 2 x 2 block above v that must be set.
+//   connectivity 26: the cubical complex (a lattice vertex / edge / face / cube is present if ANY voxel incident to it is
+//                    set) -- a cell belongs to the raster-first set voxel incident to it, i.e. v owns a cell iff every
+//                    raster-EARLIER voxel incident to the cell is clear.  Of the 27 cells of v's cube the ones no earlier voxel
+//                    touches cancel (1 vertex - 3 edges + 3 faces - 1 cube = 0), and so do all that hang on the voxel at
+//                    x - 1 or at y - 1 alone.  With Q, P, R the rows (z-1, y), (z-1, y-1), (z-1, y+1), S the row (z, y-1), T
+//                    the row itself, a suffix m / p for the voxel at x - 1 / x + 1 and [..] = 1 iff all the voxels named are
+//                    CLEAR, what is left is
+//                      [Q] - [Q R] - [S Q P] - [Q Qp] - [Tm Q Qm]
+//                      + [Q Qp R Rp] + [Q Qm R Rm Tm] + [Q Qp P Pp S Sp] + [Q Qm P Pm Tm S Sm]
+//                    (the face below; the two edges below along x and the two along y; the four vertices below).
+// Per word these are ANDs / ORs of the row's word with up to four neighbour rows and their shifts by one bit, carried across
+// the word boundaries; a run's share is the popcount of every term under the run's mask.  Rows outside the stack and bits at
+// x >= nx read as 0.
+struct CcWin {                                               // three neighbouring words of one row, slid along x
+    u64 prv, cur, nxt;
+};
+
+__device__ static inline u64 cc_word_or0(const u64 *__restrict__ row, int nx, int wx, int w)
+{
+    return (row && w < wx) ? cc_word(row, nx, wx, w) : 0ull;
+}
+
+__device__ static inline u64 cc_xp(const CcWin &r) { return (r.cur >> 1) | (r.nxt << 63); }      // bit x = voxel x + 1
+__device__ static inline u64 cc_xm(const CcWin &r) { return (r.cur << 1) | (r.prv >> 63); }      // bit x = voxel x - 1
+
+#define CC_EULER_POS 5
+#define CC_EULER_NEG 4
+
+// the terms of chi for the word win[0].cur of the row: pos[] count + 1 per bit, neg[] count - 1
+template <int K>
+__device__ static inline void cc_euler_terms(const CcWin *win, u64 *pos, u64 *neg)
+{
+    const u64 t = win[0].cur;
+    if constexpr (K == 6) {                                 // win: the row, (z, y+1), (z+1, y), (z+1, y+1)
+        const u64 b = win[1].cur, c = win[2].cur, d = win[3].cur;
+        const u64 ex = t & cc_xp(win[0]), ey = t & b, ez = t & c;
+        const u64 fxy = ex & b & cc_xp(win[1]), fxz = ex & c & cc_xp(win[2]), fyz = ey & c & d;
+        pos[0] = t;
+        pos[1] = fxy;
+        pos[2] = fxz;
+        pos[3] = fyz;
+        pos[4] = 0;
+        neg[0] = ex;
+        neg[1] = ey;
+        neg[2] = ez;
+        neg[3] = fxy & c & cc_xp(win[2]) & d & cc_xp(win[3]);
+    } else {                                                // win: the row T, S = (z, y-1), Q = (z-1, y), P = (z-1, y-1), R = (z-1, y+1)
+        const u64 tm = cc_xm(win[0]);
+        const u64 s = win[1].cur, q = win[2].cur, p = win[3].cur, r = win[4].cur;
+        const u64 qlo = q | cc_xm(win[2]) | tm, qhi = q | cc_xp(win[2]);       // below and behind / below and ahead
+        const u64 slo = s | cc_xm(win[1]), shi = s | cc_xp(win[1]);
+        const u64 plo = p | cc_xm(win[3]), phi = p | cc_xp(win[3]);
+        const u64 rlo = r | cc_xm(win[4]), rhi = r | cc_xp(win[4]);
+        pos[0] = t & ~q;
+        pos[1] = t & ~(qhi | rhi);
+        pos[2] = t & ~(qlo | rlo);
+        pos[3] = t & ~(qhi | phi | shi);
+        pos[4] = t & ~(qlo | plo | slo);
+        neg[0] = t & ~(q | r);
+        neg[1] = t & ~(s | q | p);
+        neg[2] = t & ~qhi;
+        neg[3] = t & ~qlo;
+    }
+}
+
+// chi of the bits under mask, as a two's complement u64
+__device__ static inline u64 cc_euler_under(const u64 *pos, const u64 *neg, u64 mask)
+{
+    int v = 0;
+#pragma unroll
+    for (int i = 0; i < CC_EULER_POS; i++) v += __popcll(pos[i] & mask);
+#pragma unroll
+    for (int i = 0; i < CC_EULER_NEG; i++) v -= __popcll(neg[i] & mask);
+    return (u64)(int64_t)v;
+}
+
+// One thread per row (z, y) over its words and, LABELLED, over the runs in every word (as cc_filter_kernel walks them): a
+// thread adds up neighbouring runs of one component, a wave whose lanes all hold the same component adds once, then one signed
+// 64-bit atomic add (two's complement on u64) into euler[rank[parent[run]]].  Not LABELLED: no table is read and everything
+// goes to euler[0] -- the Euler number of the whole volume.
+template <int K, bool LABELLED>
+__global__ __launch_bounds__(CC_THREADS) void cc_euler_kernel(const u64 *__restrict__ bits, int64_t nrows, int ny, int nx, int wx,
+                                                              const u32 *__restrict__ row_off, const u64 *__restrict__ tot,
+                                                              int64_t cap_runs, const u32 *__restrict__ parent,
+                                                              const u32 *__restrict__ rank, unsigned long long *__restrict__ euler,
+                                                              int64_t cap, u64 *flags)
+{
+    constexpr int NR = K == 6 ? 4 : 5;
+    const int64_t row = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    const u32 nruns = LABELLED ? (u32)cc_count(tot, cap_runs) : 0u;
+    const u32 ncomp = LABELLED ? (u32)cc_ncomp(tot, cap) : 1u;
+    if (LABELLED && row == 0 && tot[1] > (u64)cap) cc_flag(flags, CC_F_CAP);
+    u32 comp = 0;                                           // component + 1 the thread is adding up, 0: none
+    CcSumAcc acc = {euler, ncomp, 0};
+    if (row < nrows) {
+        const int y = (int)(row % ny);
+        const bool up = y + 1 < ny, down = y > 0, front = row + ny < nrows, back = row >= ny;
+        const u64 *self = bits + row * wx;
+        const u64 *r[NR];
+        r[0] = self;
+        if constexpr (K == 6) {
+            r[1] = up ? self + wx : nullptr;
+            r[2] = front ? self + (int64_t)ny * wx : nullptr;
+            r[3] = up && front ? self + (int64_t)(ny + 1) * wx : nullptr;
+        } else {
+            r[1] = down ? self - wx : nullptr;
+            r[2] = back ? self - (int64_t)ny * wx : nullptr;
+            r[3] = back && down ? self - (int64_t)(ny + 1) * wx : nullptr;
+            r[4] = back && up ? self - (int64_t)(ny - 1) * wx : nullptr;
+        }
+        CcWin win[NR];
+#pragma unroll
+        for (int i = 0; i < NR; i++) {
+            win[i].prv = 0;
+            win[i].cur = cc_word_or0(r[i], nx, wx, 0);
+            win[i].nxt = cc_word_or0(r[i], nx, wx, 1);
+        }
+        CcWordRuns it = {0, LABELLED ? row_off[row] : 0u, false};
+        for (int w = 0; w < wx; w++) {
+            const u64 m = win[0].cur;
+            if (m) {
+                u64 pos[CC_EULER_POS], neg[CC_EULER_NEG];
+                cc_euler_terms<K>(win, pos, neg);
+                if (!LABELLED) {
+                    comp = 1;
+                    acc.sum += cc_euler_under(pos, neg, m);
+                }
+                it.m = LABELLED ? m : 0;
+                while (cc_word_runs_next(it)) {
+                    if (it.run < nruns) {
+                        cc_change(comp, cc_component(parent, rank, it.run) + 1, acc);
+                        acc.sum += cc_euler_under(pos, neg, it.mask);
+                    } else {
+                        cc_flag(flags, CC_F_RANGE);
+                    }
+                }
+            }
+            it.carry = (m >> 63) != 0;                      // the word ended inside a run
+#pragma unroll
+            for (int i = 0; i < NR; i++) {
+                win[i].prv = win[i].cur;
+                win[i].cur = win[i].nxt;
+                win[i].nxt = cc_word_or0(r[i], nx, wx, w + 2);
+            }
+        }
+    }
+    cc_wave_tail<false>(comp, 0u, acc);
+}
+
+TOMO_API int tomo_cc_euler(const uint64_t *bits, int nz, int ny, int nx, int connectivity, const uint32_t *row_off, int64_t cap_runs,
+                           const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, int64_t *euler, int64_t cap,
+                           void *stream)
+{
+    int64_t nrows;
+    int wx;
+    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
+    if (g != TOMO_OK) return g;
+    if (!euler || cap <= 0 || (connectivity != 6 && connectivity != 26)) return TOMO_E_ARG;
+    if (parent && (!row_off || !rank || !tot || cap_runs <= 0)) return TOMO_E_ARG;
+    if (cap >= ((int64_t)1 << 31) || (parent && cap_runs >= ((int64_t)1 << 31))) return TOMO_E_SIZE;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(euler, 0, (size_t)cap * sizeof(int64_t), st) != hipSuccess) return TOMO_E_LAUNCH;
+    const dim3 grid((unsigned)ceil_div64(nrows, CC_THREADS)), block(CC_THREADS);
+    const u64 *b = (const u64 *)bits, *t = (const u64 *)tot;
+    const u32 *ro = (const u32 *)row_off, *pa = (const u32 *)parent, *ra = (const u32 *)rank;
+    unsigned long long *e = (unsigned long long *)euler;
+    u64 *flags = tot ? (u64 *)tot + 2 : nullptr;
+    if (parent) {
+        if (connectivity == 6)
+            hipLaunchKernelGGL((cc_euler_kernel<6, true>), grid, block, 0, st, b, nrows, ny, nx, wx, ro, t, cap_runs, pa, ra, e, cap, flags);
+        else
+            hipLaunchKernelGGL((cc_euler_kernel<26, true>), grid, block, 0, st, b, nrows, ny, nx, wx, ro, t, cap_runs, pa, ra, e, cap, flags);
+    } else {
+        if (connectivity == 6)
+            hipLaunchKernelGGL((cc_euler_kernel<6, false>), grid, block, 0, st, b, nrows, ny, nx, wx, ro, t, cap_runs, pa, ra, e, cap, flags);
+        else
+            hipLaunchKernelGGL((cc_euler_kernel<26, false>), grid, block, 0, st, b, nrows, ny, nx, wx, ro, t, cap_runs, pa, ra, e, cap, flags);
+    }
+    return tomo_status();
+}
+
+// out = the complement inside the stack: ~word, the bits at x >= nx clear
+__global__ __launch_bounds__(CC_THREADS) void cc_complement_kernel(const u64 *__restrict__ bits, int64_t nwords, int nx, int wx,
+                                                                   u64 *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    if (i >= nwords) return;
+    out[i] = ~bits[i] & cc_tail_mask(nx, wx, (int)(i % wx));
+}
+
+TOMO_API int tomo_cc_complement(const uint64_t *bits, int nz, int ny, int nx, uint64_t *out, void *stream)
+{
+    int64_t nrows;
+    int wx;
+    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
+    if (g != TOMO_OK) return g;
+    if (!out || out == bits) return TOMO_E_ARG;
+    const int64_t nwords = nrows * wx;
+    hipLaunchKernelGGL(cc_complement_kernel, dim3((unsigned)ceil_div64(nwords, CC_THREADS)), dim3(CC_THREADS), 0, (hipStream_t)stream,
+                       (const u64 *)bits, nwords, nx, wx, (u64 *)out);
+    return tomo_status();
+}
+
+// x of the k-th (0-based) run of a row, -1 if the row has no such run (at most wx + 64 turns)
+__device__ static inline int cc_run_start(const u64 *__restrict__ row, int nx, int wx, u32 k)
+{
+    for (int w = 0; w < wx; w++) {
+        u64 s = cc_starts(row, nx, wx, w, cc_word(row, nx, wx, w));
+        const u32 c = (u32)__popcll(s);
+        if (k < c) {
+            while (k--) s &= s - 1;
+            return 64 * w + __ffsll((long long)s) - 1;
+        }
+        k -= c;
+    }
+    return -1;
+}
+
+// topo (device int64[cap][3]): row c = (euler[c], 0, 0) for c < n, zeros behind
+__global__ __launch_bounds__(CC_THREADS) void cc_topology_init_kernel(const u64 *__restrict__ euler, const u64 *__restrict__ tot,
+                                                                      int64_t cap, u64 *__restrict__ topo)
+{
+    const int64_t c = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    if (c >= cap) return;
+    topo[3 * c] = c < cc_ncomp(tot, cap) ? euler[c] : 0ull;
+    topo[3 * c + 1] = 0;
+    topo[3 * c + 2] = 0;
+}
+
+// One thread per run of the BACKGROUND (the complement, labelled under the complementary connectivity; bg_table = its
+// measurement table).  A run that is its own root is the first run of its component in raster order; if the component's box
+// touches no face of the stack it is a cavity, the voxel left of the run's start is set and belongs to the foreground
+// component that encloses it: its run is found as cc_expand_kernel maps a bit to a run, and that component counts one more.
+__global__ __launch_bounds__(CC_THREADS) void cc_cavities_kernel(const u64 *__restrict__ bits, int64_t nrows, int ny, int nx, int wx,
+                                                                 const u32 *__restrict__ row_off, const u64 *__restrict__ tot,
+                                                                 int64_t cap_runs, const u32 *__restrict__ parent,
+                                                                 const u32 *__restrict__ rank, int64_t cap,
+                                                                 const u64 *__restrict__ bg_bits, const u32 *__restrict__ bg_row_off,
+                                                                 const u64 *__restrict__ bg_tot, int64_t bg_cap_runs,
+                                                                 const u32 *__restrict__ bg_parent, const u32 *__restrict__ bg_rank,
+                                                                 const u64 *__restrict__ bg_table, int64_t bg_cap,
+                                                                 unsigned long long *__restrict__ topo, u64 *flags)
+{
+    const int64_t i = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    if (i == 0 && (tot[0] > (u64)cap_runs || tot[1] > (u64)cap || bg_tot[0] > (u64)bg_cap_runs || bg_tot[1] > (u64)bg_cap))
+        cc_flag(flags, CC_F_CAP);
+    const u32 nruns = (u32)cc_count(tot, cap_runs), ncomp = (u32)cc_ncomp(tot, cap);
+    const u32 nbg_comp = (u32)cc_ncomp(bg_tot, bg_cap);
+    if (i >= cc_count(bg_tot, bg_cap_runs) || nruns == 0 || ncomp == 0 || nbg_comp == 0) return;
+    const u32 run = (u32)i;
+    if (bg_parent[run] != run) return;
+    const u32 c = bg_rank[run];
+    if (c >= nbg_comp) {
+        cc_flag(flags, CC_F_RANGE);
+        return;
+    }
+    const u64 *box = bg_table + (int64_t)c * CC_COLS;
+    const u64 nz = (u64)(nrows / ny);
+    if (box[1] == 0 || box[2] + 1 >= nz || box[3] == 0 || box[4] + 1 >= (u64)ny || box[5] == 0 || box[6] + 1 >= (u64)nx) return;
+    int64_t lo = 0, hi = nrows - 1;                         // the row of the run: the last one with bg_row_off[row] <= run
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (bg_row_off[mid] <= run) lo = mid;
+        else hi = mid - 1;
+    }
+    const u32 first = bg_row_off[lo];
+    const int s = first <= run ? cc_run_start(bg_bits + lo * wx, nx, wx, run - first) : -1;
+    bool ok = s > 0;
+    if (ok) {
+        const int x = s - 1, wj = x >> 6, b = x & 63;
+        const u64 *r = bits + lo * wx;
+        const u64 cur = cc_word(r, nx, wx, wj);
+        ok = ((cur >> b) & 1) != 0;
+        if (ok) {
+            const u32 fr = cc_run_of_bit(r, nx, wx, wj, b, row_off[lo]);
+            ok = fr < nruns;
+            if (ok) {
+                const u32 fc = cc_component(parent, rank, fr);
+                ok = fc < ncomp;
+                if (ok) atomicAdd(topo + 3 * (int64_t)fc + 1, 1ull);
+            }
+        }
+    }
+    if (!ok) cc_flag(flags, CC_F_RANGE);
+}
+
+// handles = 1 - euler + cavities
+__global__ __launch_bounds__(CC_THREADS) void cc_handles_kernel(const u64 *__restrict__ tot, int64_t cap, u64 *__restrict__ topo)
+{
+    const int64_t c = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    if (c >= cc_ncomp(tot, cap)) return;
+    topo[3 * c + 2] = 1ull - topo[3 * c] + topo[3 * c + 1];
+}
+
+TOMO_API int tomo_cc_cavities(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                              const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, int64_t cap,
+                              const uint64_t *bg_bits, const uint32_t *bg_row_off, int64_t bg_cap_runs, const uint32_t *bg_parent,
+                              const uint32_t *bg_rank, const unsigned long long *bg_tot, const int64_t *bg_table, int64_t bg_cap,
+                              const int64_t *euler, int64_t *topo, void *stream)
+{
+    int64_t nrows;
+    int wx;
+    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
+    if (g != TOMO_OK) return g;
+    if (!row_off || !parent || !rank || !tot || !euler || !topo || cap_runs <= 0 || cap <= 0 || bg_cap_runs < 0) return TOMO_E_ARG;
+    if (bg_cap_runs > 0 && (!bg_bits || !bg_row_off || !bg_parent || !bg_rank || !bg_tot || !bg_table || bg_cap <= 0)) return TOMO_E_ARG;
+    if (cap_runs >= ((int64_t)1 << 31) || cap >= ((int64_t)1 << 31) || bg_cap_runs >= ((int64_t)1 << 31) || bg_cap >= ((int64_t)1 << 31))
+        return TOMO_E_SIZE;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned comp_blocks = (unsigned)ceil_div64(cap, CC_THREADS);
+    hipLaunchKernelGGL(cc_topology_init_kernel, dim3(comp_blocks), dim3(CC_THREADS), 0, st, (const u64 *)euler, (const u64 *)tot, cap,
+                       (u64 *)topo);
+    if (bg_cap_runs > 0)                                    // a full volume has no background run: nothing to attribute
+        hipLaunchKernelGGL(cc_cavities_kernel, dim3((unsigned)ceil_div64(bg_cap_runs, CC_THREADS)), dim3(CC_THREADS), 0, st,
+                           (const u64 *)bits, nrows, ny, nx, wx, (const u32 *)row_off, (const u64 *)tot, cap_runs, (const u32 *)parent,
+                           (const u32 *)rank, cap, (const u64 *)bg_bits, (const u32 *)bg_row_off, (const u64 *)bg_tot, bg_cap_runs,
+                           (const u32 *)bg_parent, (const u32 *)bg_rank, (const u64 *)bg_table, bg_cap, (unsigned long long *)topo,
+                           (u64 *)tot + 2);
+    hipLaunchKernelGGL(cc_handles_kernel, dim3(comp_blocks), dim3(CC_THREADS), 0, st, (const u64 *)tot, cap, (u64 *)topo);
+    return tomo_status();
+}
+
+// out[slot[c]] = (c + 1, voxels, euler, cavities, handles) for every selected component c (sel, slot, tot[5]: tomo_cc_zhist_offsets)
+__global__ __launch_bounds__(CC_THREADS) void cc_topology_rows_kernel(const u64 *__restrict__ table, const u64 *__restrict__ topo,
+                                                                      const u64 *__restrict__ tot, int64_t cap,
+                                                                      const uint8_t *__restrict__ sel, const u32 *__restrict__ slot,
+                                                                      u64 *__restrict__ out, int64_t cap_sel, u64 *flags)
+{
+    const int64_t c = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    const bool fits = tot[5] <= (u64)cap_sel && tot[1] <= (u64)cap;
+    if (c == 0 && !fits) cc_flag(flags, CC_F_CAP);
+    if (!fits || c >= cc_ncomp(tot, cap) || !sel[c]) return;
+    const u32 k = slot[c];
+    if ((int64_t)k >= cap_sel) {
+        cc_flag(flags, CC_F_RANGE);
+        return;
+    }
+    u64 *o = out + 5 * (int64_t)k;
+    o[0] = (u64)c + 1;
+    o[1] = table[c * CC_COLS];
+    o[2] = topo[3 * c];
+    o[3] = topo[3 * c + 1];
+    o[4] = topo[3 * c + 2];
+}
+
+TOMO_API int tomo_cc_topology_rows(const int64_t *table, const int64_t *topo, int64_t cap, unsigned long long *tot, const uint8_t *sel,
+                                   const uint32_t *slot, int64_t *out, int64_t cap_sel, void *stream)
+{
+    if (!table || !topo || !tot || !sel || !slot || !out || cap <= 0 || cap_sel <= 0) return TOMO_E_ARG;
+    if (cap >= ((int64_t)1 << 31) || cap_sel >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
+    hipLaunchKernelGGL(cc_topology_rows_kernel, dim3((unsigned)ceil_div64(cap, CC_THREADS)), dim3(CC_THREADS), 0, (hipStream_t)stream,
+                       (const u64 *)table, (const u64 *)topo, (const u64 *)tot, cap, sel, (const u32 *)slot, (u64 *)out, cap_sel,
+                       (u64 *)tot + 2);
+    return tomo_status();
+}

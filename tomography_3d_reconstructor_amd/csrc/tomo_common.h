@@ -76,6 +76,34 @@ __device__ static inline u32 wave_inclusive_scan(u32 v)
     }
     return v;
 }
+__device__ static inline u64 wave_inclusive_scan64(u64 v)
+{
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const u64 o = __shfl_up(v, d, 64);
+        if (lane >= d) v += o;
+    }
+    return v;
+}
+__device__ static inline u32 wave_min32(u32 v)
+{
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const u32 o = __shfl_xor(v, d, 64);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+__device__ static inline u32 wave_max32(u32 v)
+{
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const u32 o = __shfl_xor(v, d, 64);
+        v = o > v ? o : v;
+    }
+    return v;
+}
 __device__ static inline u32 wave_sum(u32 v)
 {
 #pragma unroll

@@ -247,6 +247,17 @@ MOMENT_COLUMNS = 22          # float64 per row of tomo_cc_moments: W, centre (3)
 TOPOLOGY_COLUMNS = 3         # euler, cavities, handles (tomo_cc_cavities)
 
 
+@dataclass
+class ComponentSelection:
+    """ComponentRuns.select's answer: device tensors over the n components, and the two counts read from the device."""
+    table: torch.Tensor          # int64 (n, 10): the measurement table the rule was applied to (ComponentRuns.table)
+    sel: torch.Tensor            # uint8 (n,): 1 where the component is selected
+    off: torch.Tensor            # int64 (n + 1,): where the per-slice entries of a component start, one per slice of its box
+    slot: torch.Tensor           # int32 (n,): the row of a selected component in the results = its rank among the selected
+    total: int                   # per-slice entries of all selected components
+    m: int                       # selected components
+
+
 class ComponentRuns:
     """The run tables of one BitVolume under one connectivity: scipy.ndimage.label's components, held per X-RUN (a maximal
     run of set bits in a row) and never per voxel.  Two host reads: the number of runs (it sizes the tables) and the
@@ -322,6 +333,32 @@ class ComponentRuns:
         if fresh and table.shape[0]:
             self._checked()
         return table
+
+    def select(self, min_voxels=0, largest=False):
+        """The keep rule of keep() on the measurement table: the components of at least min_voxels voxels -- largest: only the
+        largest of those, the lowest label among equals -- in ascending label -> ComponentSelection, or None when there is no
+        component or none is selected.  One host read: the counters, with the guards of everything enqueued so far."""
+        table = self._measure()
+        n = table.shape[0]
+        if n == 0:
+            return None
+        L, dev = _lib.lib(), self.vol.device
+        sel = torch.empty(n, dtype=torch.uint8, device=dev)
+        off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        slot = torch.empty(n, dtype=torch.int32, device=dev)
+        blk = torch.empty(2 * L.tomo_cc_scan_blocks(n), dtype=torch.int64, device=dev)
+        _lib.check(L.tomo_cc_zhist_offsets(_p(table), n, _p(self.tot), max(0, int(min_voxels)), int(bool(largest)), _p(sel), _p(off),
+                                           _p(slot), _p(blk), _stream()), "tomo_cc_zhist_offsets")
+        self._checked()                                             # ... and the guards of the measuring pass
+        total, m = self.host[4], self.host[5]
+        return ComponentSelection(table, sel, off, slot, total, m) if m else None
+
+    def _download_checked(self, name, *tensors):
+        """The tensors on the host, downloaded together with the flag word; raises when a guard of the kernels fired."""
+        *host, flags = [t.cpu().numpy() for t in (*tensors, self.tot[2:3])]
+        if flags[0]:
+            raise _lib.TomoError("%s: the tables do not fit the volume (flags %d)" % (name, flags[0]))
+        return host
 
     def topology(self) -> torch.Tensor:
         """Per component 1..n: Euler number, cavities (enclosed voids, b2) and handles (tunnels, b1 = 1 - euler + cavities) of
@@ -404,6 +441,21 @@ def component_table(vol: BitVolume, connectivity=6) -> torch.Tensor:
     return ComponentRuns(vol, connectivity).table()
 
 
+def _slice_weights(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x) -> np.ndarray:
+    """float64 (2 nz,): the weight (mm_x * mm_y) * depth[k] of a voxel of slice k, then the slice centres zc[k] of
+    distance_positions.  slice_depths=None: depth 1.0 per slice."""
+    zt, _, _ = distance_positions(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x)
+    depth = np.ones(nz) if slice_depths is None else np.asarray(slice_depths, dtype=np.float64).reshape(-1)
+    return np.concatenate([(float(mm_per_pixel_x) * float(mm_per_pixel_y)) * depth, zt[1:-1]])
+
+
+def _check_hist_budget(name, what, picked: ComponentSelection, entry_bytes):
+    """The per-slice entries of more than one selected component must fit COMPONENT_HIST_BUDGET (read when called)."""
+    if entry_bytes * picked.total > COMPONENT_HIST_BUDGET and picked.m > 1:
+        raise _lib.TomoError("%s: %d components selected, their %s take %d bytes, more than COMPONENT_HIST_BUDGET (%d): raise "
+                             "min_voxels" % (name, picked.m, what, entry_bytes * picked.total, COMPONENT_HIST_BUDGET))
+
+
 @dataclass
 class ComponentProperties:
     """component_properties' answer: host arrays, one row per selected component in ascending label."""
@@ -445,47 +497,27 @@ def component_properties(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, 
     if connectivity not in CONNECTIVITIES:
         raise ValueError("connectivity must be 6 or 26")
     nz, ny, nx = vol.shape
-    zt, _, _ = distance_positions(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x)
+    tables = _slice_weights(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x)
     mm_y, mm_x = float(mm_per_pixel_y), float(mm_per_pixel_x)
-    depth = np.ones(nz) if slice_depths is None else np.asarray(slice_depths, dtype=np.float64).reshape(-1)
-    tables = np.concatenate([(mm_x * mm_y) * depth, zt[1:-1]])
-    min_voxels = max(0, int(min_voxels))
-    none = np.zeros((0, TABLE_COLUMNS), dtype=np.int64)
-    empty = _component_properties_from(none, none[:, 0].copy(), np.zeros((0, 2)), mm_y, mm_x)
     cr = ComponentRuns(vol, connectivity)
-    table = cr._measure()
-    n = table.shape[0]
-    if n == 0:
-        return empty
+    picked = cr.select(min_voxels, largest)
+    if picked is None or picked.total == 0:
+        none = np.zeros((0, TABLE_COLUMNS), dtype=np.int64)
+        return _component_properties_from(none, none[:, 0].copy(), np.zeros((0, 2)), mm_y, mm_x)
+    _check_hist_budget("component_properties", "voxels-per-slice counters", picked, 8)
     L, dev, st = _lib.lib(), vol.device, _stream()
-    sel = torch.empty(n, dtype=torch.uint8, device=dev)
-    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    slot = torch.empty(n, dtype=torch.int32, device=dev)
-    blk = torch.empty(2 * L.tomo_cc_scan_blocks(n), dtype=torch.int64, device=dev)
-    _lib.check(L.tomo_cc_zhist_offsets(_p(table), n, _p(cr.tot), min_voxels, int(bool(largest)), _p(sel), _p(off), _p(slot), _p(blk),
-                                       st), "tomo_cc_zhist_offsets")
-    cr._checked()                                               # ... and the guards of the measuring pass
-    total, m = cr.host[4], cr.host[5]
-    if m == 0 or total == 0:
-        return empty
-    if 8 * total > COMPONENT_HIST_BUDGET and m > 1:
-        raise _lib.TomoError("component_properties: %d components selected, their voxels-per-slice counters take %d bytes, more "
-                             "than COMPONENT_HIST_BUDGET (%d): raise min_voxels" % (m, 8 * total, COMPONENT_HIST_BUDGET))
+    table, n, total, m = picked.table, picked.table.shape[0], picked.total, picked.m
     hist = torch.empty(total, dtype=torch.int64, device=dev)
     COUNTERS["components_zhist"] += 1
-    _lib.check(L.tomo_cc_zhist(_p(cr.bits), nz, ny, nx, *cr._tables(), _p(cr.tot), _p(table), n, _p(sel), _p(off), _p(hist), total,
-                               st), "tomo_cc_zhist")
+    _lib.check(L.tomo_cc_zhist(_p(cr.bits), nz, ny, nx, *cr._tables(), _p(cr.tot), _p(table), n, _p(picked.sel), _p(picked.off),
+                               _p(hist), total, st), "tomo_cc_zhist")
     tab = torch.from_numpy(tables).to(dev)
     sums = torch.empty((m, 2), dtype=torch.float64, device=dev)
     labels = torch.ones(m, dtype=torch.int64, device=dev)       # a valid row for the gather below even where a guard fired
-    _lib.check(L.tomo_cc_zsums(_p(table), n, _p(cr.tot), _p(sel), _p(off), _p(slot), _p(hist), total, _p(tab[:nz]), _p(tab[nz:]), nz,
-                               _p(sums), _p(labels), m, st), "tomo_cc_zsums")
+    _lib.check(L.tomo_cc_zsums(_p(table), n, _p(cr.tot), _p(picked.sel), _p(picked.off), _p(picked.slot), _p(hist), total,
+                               _p(tab[:nz]), _p(tab[nz:]), nz, _p(sums), _p(labels), m, st), "tomo_cc_zsums")
     rows = table.index_select(0, labels - 1)
-    flags = cr.tot[2:3]
-    host = [t.cpu().numpy() for t in (rows, labels, sums, flags)]
-    if host[3][0]:
-        raise _lib.TomoError("component_properties: the tables do not fit the volume (flags %d)" % host[3][0])
-    return _component_properties_from(host[0], host[1], host[2], mm_y, mm_x)
+    return _component_properties_from(*cr._download_checked("component_properties", rows, labels, sums), mm_y, mm_x)
 
 
 @dataclass
@@ -536,47 +568,27 @@ def component_moments(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_
     if connectivity not in CONNECTIVITIES:
         raise ValueError("connectivity must be 6 or 26")
     nz, ny, nx = vol.shape
-    zt, _, _ = distance_positions(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x)
+    tables = _slice_weights(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x)
     mm_y, mm_x = float(mm_per_pixel_y), float(mm_per_pixel_x)
-    depth = np.ones(nz) if slice_depths is None else np.asarray(slice_depths, dtype=np.float64).reshape(-1)
-    tables = np.concatenate([(mm_x * mm_y) * depth, zt[1:-1]])
-    min_voxels = max(0, int(min_voxels))
-    none = np.zeros(0, dtype=np.int64)
-    empty = _component_moments_from(none, none.copy(), np.zeros((0, MOMENT_COLUMNS)))
     cr = ComponentRuns(vol, connectivity)
-    table = cr._measure()
-    n = table.shape[0]
-    if n == 0:
-        return empty
+    picked = cr.select(min_voxels, largest)
+    if picked is None or picked.total == 0:
+        none = np.zeros(0, dtype=np.int64)
+        return _component_moments_from(none, none.copy(), np.zeros((0, MOMENT_COLUMNS)))
+    _check_hist_budget("component_moments", "moment sums per slice", picked, 8 * MOMENT_SUMS)
     L, dev, st = _lib.lib(), vol.device, _stream()
-    sel = torch.empty(n, dtype=torch.uint8, device=dev)
-    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    slot = torch.empty(n, dtype=torch.int32, device=dev)
-    blk = torch.empty(2 * L.tomo_cc_scan_blocks(n), dtype=torch.int64, device=dev)
-    _lib.check(L.tomo_cc_zhist_offsets(_p(table), n, _p(cr.tot), min_voxels, int(bool(largest)), _p(sel), _p(off), _p(slot), _p(blk),
-                                       st), "tomo_cc_zhist_offsets")
-    cr._checked()                                               # ... and the guards of the measuring pass
-    total, m = cr.host[4], cr.host[5]
-    if m == 0 or total == 0:
-        return empty
-    if 8 * MOMENT_SUMS * total > COMPONENT_HIST_BUDGET and m > 1:
-        raise _lib.TomoError("component_moments: %d components selected, their moment sums per slice take %d bytes, more than "
-                             "COMPONENT_HIST_BUDGET (%d): raise min_voxels" % (m, 8 * MOMENT_SUMS * total, COMPONENT_HIST_BUDGET))
+    table, n, total, m = picked.table, picked.table.shape[0], picked.total, picked.m
     mom = torch.empty(MOMENT_SUMS * total, dtype=torch.int64, device=dev)
     COUNTERS["components_moments"] += 1
-    _lib.check(L.tomo_cc_moment_hist(_p(cr.bits), nz, ny, nx, *cr._tables(), _p(cr.tot), _p(table), n, _p(sel), _p(off), _p(mom),
-                                     total, st), "tomo_cc_moment_hist")
+    _lib.check(L.tomo_cc_moment_hist(_p(cr.bits), nz, ny, nx, *cr._tables(), _p(cr.tot), _p(table), n, _p(picked.sel), _p(picked.off),
+                                     _p(mom), total, st), "tomo_cc_moment_hist")
     tab = torch.from_numpy(tables).to(dev)
     rows = torch.empty((m, MOMENT_COLUMNS), dtype=torch.float64, device=dev)
     labels = torch.ones(m, dtype=torch.int64, device=dev)       # a valid row for the gather below even where a guard fired
-    _lib.check(L.tomo_cc_moments(_p(table), n, _p(cr.tot), _p(sel), _p(off), _p(slot), _p(mom), total, _p(tab[:nz]), _p(tab[nz:]), nz,
-                                 mm_y, mm_x, _p(rows), _p(labels), m, st), "tomo_cc_moments")
+    _lib.check(L.tomo_cc_moments(_p(table), n, _p(cr.tot), _p(picked.sel), _p(picked.off), _p(picked.slot), _p(mom), total,
+                                 _p(tab[:nz]), _p(tab[nz:]), nz, mm_y, mm_x, _p(rows), _p(labels), m, st), "tomo_cc_moments")
     voxels = table[:, 0].index_select(0, labels - 1)
-    flags = cr.tot[2:3]
-    host = [t.cpu().numpy() for t in (voxels, labels, rows, flags)]
-    if host[3][0]:
-        raise _lib.TomoError("component_moments: the tables do not fit the volume (flags %d)" % host[3][0])
-    return _component_moments_from(host[0], host[1], host[2])
+    return _component_moments_from(*cr._download_checked("component_moments", voxels, labels, rows))
 
 
 # ----------------------------------------------------------------------------- Euler number, cavities and handles
@@ -624,31 +636,15 @@ def component_topology(vol: BitVolume, connectivity=6, min_voxels=0, largest=Fal
     runs of the volume and of its complement, and the components -- never with the voxels."""
     if connectivity not in CONNECTIVITIES:
         raise ValueError("connectivity must be 6 or 26")
-    min_voxels = max(0, int(min_voxels))
-    empty = _component_topology_from(np.zeros((0, 2 + TOPOLOGY_COLUMNS), dtype=np.int64))
     cr = ComponentRuns(vol, connectivity)
     topo = cr.topology()
-    n = topo.shape[0]
-    if n == 0:
-        return empty
-    table = cr._measure()
-    L, dev, st = _lib.lib(), vol.device, _stream()
-    sel = torch.empty(n, dtype=torch.uint8, device=dev)
-    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    slot = torch.empty(n, dtype=torch.int32, device=dev)
-    blk = torch.empty(2 * L.tomo_cc_scan_blocks(n), dtype=torch.int64, device=dev)
-    _lib.check(L.tomo_cc_zhist_offsets(_p(table), n, _p(cr.tot), min_voxels, int(bool(largest)), _p(sel), _p(off), _p(slot), _p(blk),
-                                       st), "tomo_cc_zhist_offsets")
-    cr._checked()                                               # ... and the guards of the measuring pass
-    m = cr.host[5]
-    if m == 0:
-        return empty
-    rows = torch.empty((m, 2 + TOPOLOGY_COLUMNS), dtype=torch.int64, device=dev)
-    _lib.check(L.tomo_cc_topology_rows(_p(table), _p(topo), n, _p(cr.tot), _p(sel), _p(slot), _p(rows), m, st), "tomo_cc_topology_rows")
-    host = [t.cpu().numpy() for t in (rows, cr.tot[2:3])]
-    if host[1][0]:
-        raise _lib.TomoError("component_topology: the tables do not fit the volume (flags %d)" % host[1][0])
-    return _component_topology_from(host[0])
+    picked = cr.select(min_voxels, largest) if topo.shape[0] else None
+    if picked is None:
+        return _component_topology_from(np.zeros((0, 2 + TOPOLOGY_COLUMNS), dtype=np.int64))
+    rows = torch.empty((picked.m, 2 + TOPOLOGY_COLUMNS), dtype=torch.int64, device=vol.device)
+    _lib.check(_lib.lib().tomo_cc_topology_rows(_p(picked.table), _p(topo), topo.shape[0], _p(cr.tot), _p(picked.sel), _p(picked.slot),
+                                                _p(rows), picked.m, _stream()), "tomo_cc_topology_rows")
+    return _component_topology_from(*cr._download_checked("component_topology", rows))
 
 
 def volume_topology(vol: BitVolume, connectivity=6) -> dict:
