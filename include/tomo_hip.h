@@ -348,6 +348,38 @@ int tomo_edt_threshold(const uint64_t *bits, int nz, int ny, int nx, const doubl
                        double r2, int keep_greater, uint64_t *out, void *workspace, int64_t workspace_bytes, void *stream);
 int tomo_edt_argmax(const uint64_t *bits, int nz, int ny, int nx, const double *zt, const double *yt, const double *xt, int inside,
                     int64_t *result, void *workspace, int64_t workspace_bytes, void *stream);
+/* Local thickness (Hildebrand & Ruegsegger) and ball openings by levels, on the coordinates and the background of the
+ * transform above.  D2(q) = the float64 squared inside distance of set voxel q, |pq|^2 = ((dx^2 + dy^2) + dz^2) in float64,
+ * every d a difference of two table entries, no contraction.  For ascending squared radii r_1^2 < ... < r_K^2
+ *     level(p) = max{ k : there is a set voxel q with D2(q) >= r_k^2 and |pq|^2 < r_k^2 }      at a set voxel p,
+ * 0 without such a k and at an unset voxel: {D2 >= r_k^2} are the centres where the OPEN ball of radius r_k fits, {level
+ * reaches k} is the opening of the volume by that ball.  Digital openings are not monotone in r, hence the maximum.  One
+ * outside transform of a bit volume per level:
+ *   tomo_edt_squared           out float64 (nz, ny, nx) = d2 of tomo_edt_distance, unrounded (+inf without a site)
+ *   tomo_edt_at_least          out uint64 (nz, ny, words) (!= bits): bit = set in bits && d2 >= r2, d2 float64 (nz, ny, nx) as
+ *                              tomo_edt_squared wrote it; tail bits zero; no workspace.  r2 >= 0
+ *   tomo_edt_cover             one level: the outside transform of `sites` (virtual positions never sites); where d2 < r2 at a
+ *                              set voxel of `bits`, map int32 (nz, ny, nx) = level (>= 1); every other entry is left alone, so
+ *                              levels run ascending over one zeroed map.  An unset voxel is never written, whatever d2 reads
+ *   tomo_edt_threshold_masked  out uint64 (nz, ny, words) (!= sites, != mask) = mask & (d2 >= r2), or mask & (d2 < r2) with
+ *                              keep_less, d2 the transform of `sites`; tail bits zero; no float volume is made.  The ball
+ *                              opening is two calls: (bits, inside = 1, keep_less = 0, mask = bits) gives the eroded set,
+ *                              (eroded, inside = 0, keep_less = 1, mask = bits) the opening
+ *   tomo_edt_thickness_finish  map int32 -> float32 IN PLACE: values[level - 1] (device float32[levels], made on the host) at
+ *                              a set voxel of level >= 1, +0.0 at every other voxel; counts int64 (nz, levels + 1) is zeroed
+ *                              and then holds the set voxels of slice z at level l in [z][l] (column 0: set, below r_1).
+ *                              Integer atomics only: the same bytes on every run.  levels >= 0
+ * TOMO_E_ARG for a null pointer, a size < 1, r2 < 0 or NaN, level < 1 or an output that is one of the inputs, before any launch. */
+int tomo_edt_squared(const uint64_t *bits, int nz, int ny, int nx, const double *zt, const double *yt, const double *xt, int inside,
+                     double *out, void *workspace, int64_t workspace_bytes, void *stream);
+int tomo_edt_at_least(const double *d2, const uint64_t *bits, int nz, int ny, int nx, double r2, uint64_t *out, void *stream);
+int tomo_edt_cover(const uint64_t *sites, const uint64_t *bits, int nz, int ny, int nx, const double *zt, const double *yt,
+                   const double *xt, double r2, int level, int32_t *map, void *workspace, int64_t workspace_bytes, void *stream);
+int tomo_edt_threshold_masked(const uint64_t *sites, int nz, int ny, int nx, const double *zt, const double *yt, const double *xt,
+                              int inside, double r2, int keep_less, const uint64_t *mask, uint64_t *out, void *workspace,
+                              int64_t workspace_bytes, void *stream);
+int tomo_edt_thickness_finish(int32_t *map, const uint64_t *bits, int nz, int ny, int nx, const float *values, int levels,
+                              int64_t *counts, void *stream);
 /* image_loader.py:108 (`img >= threshold`) fused with the packing: grey = uint8 (nz, ny, nx) on the device. */
 int tomo_pack_threshold(const uint8_t *grey, uint64_t *bits, int nz, int ny, int nx, int threshold, void *stream);
 /* obj_exporter.py:17-38, byte for byte ("v %.6f %.6f %.6f" per vertex, "f a+1 b+1 c+1" per face), HOST arrays:

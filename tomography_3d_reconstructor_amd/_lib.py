@@ -80,6 +80,11 @@ SIGNATURES = {
     "tomo_edt_distance": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_i, _c_p, _c_p, _c_i64, _c_p]),
     "tomo_edt_threshold": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_i, _c_d, _c_i, _c_p, _c_p, _c_i64, _c_p]),
     "tomo_edt_argmax": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_i, _c_p, _c_p, _c_i64, _c_p]),
+    "tomo_edt_squared": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_i, _c_p, _c_p, _c_i64, _c_p]),
+    "tomo_edt_at_least": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_d, _c_p, _c_p]),
+    "tomo_edt_cover": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_d, _c_i, _c_p, _c_p, _c_i64, _c_p]),
+    "tomo_edt_threshold_masked": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_i, _c_d, _c_i, _c_p, _c_p, _c_p, _c_i64, _c_p]),
+    "tomo_edt_thickness_finish": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_p, _c_i, _c_p, _c_p]),
     "tomo_pack_threshold": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_p]),
     "tomo_obj_write": (_c_i, [ctypes.c_char_p, _c_p, _c_i, _c_i64, _c_p, _c_i64, _c_i]),
     "tomo_obj_block_format": (_c_i, [_c_i, _c_p, _c_i64, _c_i, ctypes.POINTER(_c_p), ctypes.POINTER(_c_i64)]),

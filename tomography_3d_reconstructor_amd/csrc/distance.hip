@@ -21,6 +21,12 @@
 // nz * ny * cw and the stack, never a per-voxel array of the whole volume.  The last pass ends in one of three tails: float32
 // sqrt, a comparison of d2 with r^2 that is balloted into bit words, or a (maximum, first index) reduction -- per thread, then
 // one workgroup folds the partials in a fixed order: no float atomics, the same answer on every run.
+//
+// Local thickness (Hildebrand & Ruegsegger) by levels, contract in include/tomo_hip.h: one inside transform whose tail keeps
+// d2 itself (float64, the only per-voxel float64 array), then per squared radius r2 the eroded set {set && d2 >= r2} balloted
+// into bits, one OUTSIDE transform of those bits whose tail stores the level where d2 < r2 at a set voxel of the original
+// volume (levels ascend, later ones overwrite: the maximum), and one finishing pass that turns the level map into float32
+// through a host-made table and counts the voxels per (slice, level) with integer atomics only.
 #include "tomo_common.h"
 #include <math.h>
 
@@ -30,6 +36,11 @@
 #define EDT_TAIL_GT 2                // bit = d2 > r2
 #define EDT_TAIL_LE 3                // bit = d2 <= r2
 #define EDT_TAIL_ARGMAX 4
+#define EDT_TAIL_SQUARED 5           // float64 d2 (nz, ny, nx)
+#define EDT_TAIL_GE_AND 6            // bit = d2 >= r2 && mask bit
+#define EDT_TAIL_LT_AND 7            // bit = d2 < r2 && mask bit
+#define EDT_TAIL_COVER 8             // map = level where d2 < r2 && mask bit
+#define EDT_FINISH_LDS 4096          // levels (K + 1) the finishing pass counts in LDS; beyond: straight global atomics
 
 struct EdtPlan {
     int64_t cw;                      // columns per chunk
@@ -157,6 +168,10 @@ struct EdtPass {
     u64 *obits;                      // EDT_TAIL_GT / LE: (nz, ny, wx)
     float *pval;                     // EDT_TAIL_ARGMAX: one partial per thread
     int64_t *pidx;
+    double *out2;                    // EDT_TAIL_SQUARED: (nz, ny, nx)
+    const u64 *mask;                 // EDT_TAIL_GE_AND / LT_AND / COVER: (nz, ny, wx), the volume the answer is confined to
+    int32_t *map;                    // EDT_TAIL_COVER: (nz, ny, nx)
+    int level;
 };
 
 template <int TAIL>
@@ -234,6 +249,14 @@ __global__ __launch_bounds__(EDT_THREADS) void edt_line_kernel(const EdtPass P)
             const int64_t row = (int64_t)q * P.ny + o;       // z pass: q = z, o = y
             if (TAIL == EDT_TAIL_FLOAT) {
                 if (live) P.out[row * P.nx + x] = (float)sqrt(d2);
+            } else if (TAIL == EDT_TAIL_SQUARED) {
+                if (live) P.out2[row * P.nx + x] = d2;
+            } else if (TAIL == EDT_TAIL_COVER) {             // an unset voxel keeps its 0 even where d2 is an ulp off
+                if (live && d2 < P.r2 && ((P.mask[row * P.wx + (x >> 6)] >> (x & 63)) & 1)) P.map[row * P.nx + x] = P.level;
+            } else if (TAIL == EDT_TAIL_GE_AND || TAIL == EDT_TAIL_LT_AND) {
+                const bool bit = live && (TAIL == EDT_TAIL_GE_AND ? d2 >= P.r2 : d2 < P.r2);
+                const u64 word = __ballot(bit);              // bits past nx are not live: the tail stays zero
+                if ((threadIdx.x & 63) == 0) P.obits[row * P.wx + (x >> 6)] = word & P.mask[row * P.wx + (x >> 6)];
             } else if (TAIL == EDT_TAIL_ARGMAX) {
                 const float v = (float)sqrt(d2);
                 if (live && v > best) {                      // q ascends = the flat index ascends: the first maximum stays
@@ -296,12 +319,69 @@ __global__ void edt_argmax_init_kernel(int64_t *res)
     res[1] = -1;
 }
 
+// ---------------------------------------------------------------------------------------------- local thickness
+// out word (row, w) = the set voxels of `bits` with d2 >= r2; a wave is one word, tail bits zero
+__global__ __launch_bounds__(EDT_THREADS) void edt_at_least_kernel(const double *__restrict__ d2, const u64 *__restrict__ bits,
+                                                                   int64_t nwords, int nx, int wx, double r2, u64 *__restrict__ out)
+{
+    const int64_t t = (int64_t)blockIdx.x * EDT_THREADS + threadIdx.x;
+    const int64_t word = t >> 6;                             // the same for the 64 lanes of a wave
+    if (word >= nwords) return;
+    const int64_t row = word / wx;
+    const int b = (int)(t & 63);
+    const int x = (int)(word - row * wx) * 64 + b;
+    const bool bit = x < nx && ((bits[word] >> b) & 1) && d2[row * nx + x] >= r2;
+    const u64 w = __ballot(bit);
+    if (b == 0) out[word] = w;
+}
+
+// map int32 (nz, ny, nx) -> float32 in place: values[level - 1] at a set voxel of level >= 1, 0.0f elsewhere; counts[z][l] +=
+// the set voxels of slice z at level l.  A workgroup stays inside one slice: its counters are private in LDS (K + 1 <=
+// EDT_FINISH_LDS) and are added to the table once.  Integer atomics only: the same bytes on every run.
+__global__ __launch_bounds__(EDT_THREADS) void edt_finish_kernel(int32_t *map, const u64 *__restrict__ bits, int64_t slice, int nx, int wx,
+                                                                 const float *__restrict__ values, int K, unsigned long long *counts,
+                                                                 int blocks_per_slice, int lds)
+{
+    extern __shared__ unsigned int edt_hist[];
+    const int z = blockIdx.x / blocks_per_slice;
+    const int64_t per = (slice + blocks_per_slice - 1) / blocks_per_slice;
+    const int64_t a = (int64_t)(blockIdx.x - z * blocks_per_slice) * per;
+    const int64_t e = a + per < slice ? a + per : slice;
+    unsigned long long *cz = counts + (int64_t)z * (K + 1);
+    if (lds) {
+        for (int l = threadIdx.x; l <= K; l += EDT_THREADS) edt_hist[l] = 0;
+        __syncthreads();
+    }
+    for (int64_t i = a + threadIdx.x; i < e; i += EDT_THREADS) {
+        const int64_t y = i / nx;
+        const int x = (int)(i - y * nx);
+        const int64_t at = (int64_t)z * slice + i;
+        int l = map[at];
+        if ((unsigned)l > (unsigned)K) l = 0;                // nothing writes such a level; never index past the tables
+        const bool set = (bits[((int64_t)z * (slice / nx) + y) * wx + (x >> 6)] >> (x & 63)) & 1;
+        float v = 0.0f;
+        if (set) {
+            if (l > 0) v = values[l - 1];
+            if (lds) atomicAdd(&edt_hist[l], 1u);
+            else atomicAdd(&cz[l], 1ull);
+        }
+        ((float *)map)[at] = v;
+    }
+    if (lds) {
+        __syncthreads();
+        for (int l = threadIdx.x; l <= K; l += EDT_THREADS)
+            if (edt_hist[l]) atomicAdd(&cz[l], (unsigned long long)edt_hist[l]);
+    }
+}
+
 static int edt_run(const uint64_t *bits, int nz, int ny, int nx, const double *zt, const double *yt, const double *xt, int inside,
-                   int tail, double r2, void *result, void *workspace, int64_t workspace_bytes, void *stream)
+                   int tail, double r2, void *result, void *workspace, int64_t workspace_bytes, void *stream,
+                   const uint64_t *mask = nullptr, int level = 0)
 {
     if (!bits || !zt || !yt || !xt || !result || !workspace || nz <= 0 || ny <= 0 || nx <= 0 || workspace_bytes <= 0 ||
         result == (const void *)bits)
         return TOMO_E_ARG;
+    if (tail >= EDT_TAIL_GE_AND && (!mask || result == (const void *)mask)) return TOMO_E_ARG;
     if (!(r2 >= 0.0)) return TOMO_E_ARG;
     const int64_t cw = tomo_edt_chunk_columns(nz, ny, nx, workspace_bytes);
     if (cw < 0) return (int)cw;
@@ -345,6 +425,10 @@ static int edt_run(const uint64_t *bits, int nz, int ny, int nx, const double *z
         P.obits = nullptr;
         P.pval = nullptr;
         P.pidx = nullptr;
+        P.out2 = nullptr;
+        P.mask = (const u64 *)mask;
+        P.map = nullptr;
+        P.level = level;
         hipLaunchKernelGGL(edt_line_kernel<EDT_TAIL_PLANE>, dim3((unsigned)ceil_div64((int64_t)nz * w, EDT_THREADS)), dim3(EDT_THREADS),
                            0, st, P);
         P.in = H;
@@ -366,6 +450,18 @@ static int edt_run(const uint64_t *bits, int nz, int ny, int nx, const double *z
         } else if (tail == EDT_TAIL_LE) {
             P.obits = (u64 *)result;
             hipLaunchKernelGGL(edt_line_kernel<EDT_TAIL_LE>, grid, dim3(EDT_THREADS), 0, st, P);
+        } else if (tail == EDT_TAIL_SQUARED) {
+            P.out2 = (double *)result;
+            hipLaunchKernelGGL(edt_line_kernel<EDT_TAIL_SQUARED>, grid, dim3(EDT_THREADS), 0, st, P);
+        } else if (tail == EDT_TAIL_GE_AND) {
+            P.obits = (u64 *)result;
+            hipLaunchKernelGGL(edt_line_kernel<EDT_TAIL_GE_AND>, grid, dim3(EDT_THREADS), 0, st, P);
+        } else if (tail == EDT_TAIL_LT_AND) {
+            P.obits = (u64 *)result;
+            hipLaunchKernelGGL(edt_line_kernel<EDT_TAIL_LT_AND>, grid, dim3(EDT_THREADS), 0, st, P);
+        } else if (tail == EDT_TAIL_COVER) {
+            P.map = (int32_t *)result;
+            hipLaunchKernelGGL(edt_line_kernel<EDT_TAIL_COVER>, grid, dim3(EDT_THREADS), 0, st, P);
         } else {
             P.pval = pval;
             P.pidx = pidx;
@@ -395,4 +491,56 @@ TOMO_API int tomo_edt_argmax(const uint64_t *bits, int nz, int ny, int nx, const
                              int inside, int64_t *result, void *workspace, int64_t workspace_bytes, void *stream)
 {
     return edt_run(bits, nz, ny, nx, zt, yt, xt, inside ? 1 : 0, EDT_TAIL_ARGMAX, 0.0, result, workspace, workspace_bytes, stream);
+}
+
+TOMO_API int tomo_edt_squared(const uint64_t *bits, int nz, int ny, int nx, const double *zt, const double *yt, const double *xt,
+                              int inside, double *out, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    return edt_run(bits, nz, ny, nx, zt, yt, xt, inside ? 1 : 0, EDT_TAIL_SQUARED, 0.0, out, workspace, workspace_bytes, stream);
+}
+
+TOMO_API int tomo_edt_threshold_masked(const uint64_t *sites, int nz, int ny, int nx, const double *zt, const double *yt,
+                                       const double *xt, int inside, double r2, int keep_less, const uint64_t *mask, uint64_t *out,
+                                       void *workspace, int64_t workspace_bytes, void *stream)
+{
+    return edt_run(sites, nz, ny, nx, zt, yt, xt, inside ? 1 : 0, keep_less ? EDT_TAIL_LT_AND : EDT_TAIL_GE_AND, r2, out, workspace,
+                   workspace_bytes, stream, mask);
+}
+
+TOMO_API int tomo_edt_at_least(const double *d2, const uint64_t *bits, int nz, int ny, int nx, double r2, uint64_t *out, void *stream)
+{
+    if (!d2 || !bits || !out || nz <= 0 || ny <= 0 || nx <= 0 || out == bits || (const void *)out == (const void *)d2) return TOMO_E_ARG;
+    if (!(r2 >= 0.0)) return TOMO_E_ARG;
+    const int wx = (int)tomo_words_per_row(nx);
+    const int64_t nwords = (int64_t)nz * ny * wx;
+    if (ceil_div64(nwords * 64, EDT_THREADS) >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
+    hipLaunchKernelGGL(edt_at_least_kernel, dim3((unsigned)ceil_div64(nwords * 64, EDT_THREADS)), dim3(EDT_THREADS), 0,
+                       (hipStream_t)stream, d2, (const u64 *)bits, nwords, nx, wx, r2, (u64 *)out);
+    return tomo_status();
+}
+
+TOMO_API int tomo_edt_cover(const uint64_t *sites, const uint64_t *bits, int nz, int ny, int nx, const double *zt, const double *yt,
+                            const double *xt, double r2, int level, int32_t *map, void *workspace, int64_t workspace_bytes,
+                            void *stream)
+{
+    if (level < 1) return TOMO_E_ARG;
+    return edt_run(sites, nz, ny, nx, zt, yt, xt, 0, EDT_TAIL_COVER, r2, map, workspace, workspace_bytes, stream, bits, level);
+}
+
+TOMO_API int tomo_edt_thickness_finish(int32_t *map, const uint64_t *bits, int nz, int ny, int nx, const float *values, int levels,
+                                       int64_t *counts, void *stream)
+{
+    if (!map || !bits || !counts || nz <= 0 || ny <= 0 || nx <= 0 || levels < 0 || (levels > 0 && !values) ||
+        (const void *)map == (const void *)bits || (const void *)counts == (const void *)map || (const void *)counts == (const void *)bits)
+        return TOMO_E_ARG;
+    const int64_t slice = (int64_t)ny * nx;
+    int64_t bps = ceil_div64(slice, 16 * EDT_THREADS);           // 16 voxels a thread: the LDS counters are worth their flush
+    if (bps * nz >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
+    const int lds = levels + 1 <= EDT_FINISH_LDS;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(counts, 0, (size_t)nz * (levels + 1) * 8, st) != hipSuccess) return tomo_status();
+    hipLaunchKernelGGL(edt_finish_kernel, dim3((unsigned)(bps * nz)), dim3(EDT_THREADS), lds ? (size_t)(levels + 1) * 4 : 0, st, map,
+                       (const u64 *)bits, slice, nx, (int)tomo_words_per_row(nx), values, levels, (unsigned long long *)counts, (int)bps,
+                       lds);
+    return tomo_status();
 }

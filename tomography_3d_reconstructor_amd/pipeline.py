@@ -24,7 +24,7 @@ COUNTERS = dict.fromkeys(("na_hint_hit", "na_hint_miss", "mc3_hint_hit", "mc3_hi
                           "components_filter", "slab_components_label", "slab_components_seam", "slab_components_merge",
                           "slab_components_expand", "slab_components_filter", "distance_transform", "distance_offset",
                           "components_measure", "components_zhist", "components_moments", "components_euler",
-                          "components_cavities"), 0)
+                          "components_cavities", "local_thickness", "opening_volume"), 0)
 NA_HINTS = os.environ.get("TOMO_NA_HINTS", "1") not in ("", "0")   # marching_cubes: launch ahead of the first count download
 _NA_HINT = {}
 LIST_LIMIT = 2 ** 31        # active-voxel list entries / vertices / triangles one pass can index (int32 offsets in mc.hip, mesh.hip);
@@ -763,6 +763,142 @@ def inscribed_sphere(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_p
     if flat < 0 or not radius > 0:
         return None
     return radius, (flat // (ny * nx), flat // nx % ny, flat % nx)
+
+
+# ----------------------------------------------------------------------------- local thickness and ball openings
+LOCAL_THICKNESS_MAX_LEVELS = 512               # distinct squared distances local_thickness' exact mode takes as levels
+# bytes the float64 squared distances of a local_thickness call may take (8 B per voxel): 8 GiB admits 512^3 (1 GiB) and
+# 1024^3 (exactly 8 GiB), not 2048 x 1024^2
+LOCAL_THICKNESS_VOLUME_BUDGET = 1 << 33
+
+
+@dataclass
+class LocalThickness:
+    """local_thickness' answer.  Level k (0-based here) is the open ball of radius radii_mm[k]."""
+    thickness: torch.Tensor        # float32 (nz, ny, nx) on the device: the diameter 2 r of the voxel's level, 0.0 where none
+    radii_mm: np.ndarray           # float64 (K,): the levels used, ascending
+    level_voxels: np.ndarray       # int64 (K,): set voxels whose level is k
+    level_volume_mm3: np.ndarray   # float64 (K,): their volume under the slice depths
+    uncovered_voxels: int          # set voxels below radii_mm[0]
+    mean_mm: float                 # of the diameter over the covered set voxels, weighted by volume
+    std_mm: float
+    max_mm: float
+
+
+def _check_radii(radii_mm) -> np.ndarray:
+    r = np.asarray(radii_mm, dtype=np.float64).reshape(-1)
+    if len(r) == 0 or not (np.isfinite(r).all() and (r > 0).all() and (np.diff(r) > 0).all()):
+        raise ValueError("radii_mm must be a non-empty, strictly ascending list of positive finite radii")
+    return r
+
+
+def _thickness_statistics(radii, level_volume):
+    """(mean, std, max) of the diameter 2 r over the covered voxels, weighted by volume; exactly rounded sums (math.fsum)."""
+    d = [2.0 * float(r) for r in radii]
+    w = [float(v) for v in level_volume]
+    total = math.fsum(w)
+    if not total > 0:
+        return 0.0, 0.0, 0.0
+    mean = math.fsum(wi * di for wi, di in zip(w, d)) / total
+    var = math.fsum(wi * ((di - mean) * (di - mean)) for wi, di in zip(w, d)) / total
+    return mean, math.sqrt(var), max(di for wi, di in zip(w, d) if wi > 0)
+
+
+def local_thickness(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, radii_mm=None,
+                    max_levels=LOCAL_THICKNESS_MAX_LEVELS) -> LocalThickness:
+    """Local thickness (Hildebrand & Ruegsegger) of a resident volume in millimetres -> LocalThickness.
+    Coordinates and background are distance_transform's: voxel (k, j, i) sits at (zt[k + 1], yt[j + 1], xt[i + 1]) of
+    distance_positions, everything outside the stack is background.  D2(q) is the float64 squared inside distance of set voxel
+    q, |pq|^2 = ((dx^2 + dy^2) + dz^2) in float64, every d a difference of two table entries.  For the ascending squared radii
+    r_1^2 < ... < r_K^2
+        level(p) = max{ k : there is a set voxel q with D2(q) >= r_k^2 and |pq|^2 < r_k^2 }
+    at a set voxel p, 0 without such a k: {D2 >= r_k^2} are the centres where the open ball of radius r_k fits, and {level
+    reaches k} is the opening by that ball (opening_volume).  Digital openings are not monotone in r -- a level can cover fewer
+    voxels than the next larger one -- hence the maximum.  thickness = float32(2 r_level) at a set voxel of level >= 1, 0.0 at
+    a set voxel below r_1, +0.0 at every unset voxel.
+    radii_mm=None (exact): the levels are all distinct values of D2 over the set voxels and the result is exactly
+    2 max{D(q) : |pq| < D(q)}: every set voxel reads at least 2 D(p), the maximum is twice the inscribed radius, nothing is
+    uncovered.  More than max_levels distinct values: ValueError before any level runs -- pass radii_mm then.  That happens for
+    any sizeable solid, and with spacings that are not exactly representable: values equal on paper differ in the last bit and
+    count as distinct.  Exact mode is for unit or binary-fraction spacings and for thin structures.
+    radii_mm = a strictly ascending list of positive finite radii: r_k^2 = r_k * r_k in float64; levels above the largest D2
+    are never launched and count 0.
+    level_volume_mm3: per level the voxels per slice times (mm_x * mm_y) * depth, added in ascending z in float64
+    (component_properties' order).  mean_mm / std_mm / max_mm: of the diameter 2 r_k over the covered set voxels, weighted by
+    that volume; 0.0 for an empty volume.
+    Cost: one inside transform, then per level one ballot pass and one outside transform of a bit volume (the cheap bit-scan x
+    pass), then one finishing pass.  Memory: D2 at 8 B per voxel (beyond LOCAL_THICKNESS_VOLUME_BUDGET bytes: ValueError before
+    anything is allocated), the result at 4 B per voxel, one extra bit volume and distance_transform's chunked workspace; exact
+    mode also pays torch.unique's sort of the positive D2.  Three host reads in exact mode (the level count, the levels, the
+    counts), two with radii (the largest D2, the counts)."""
+    exact = radii_mm is None
+    radii = None if exact else _check_radii(radii_mm)
+    max_levels = int(max_levels)
+    if max_levels < 1:
+        raise ValueError("max_levels must be at least 1")
+    nz, ny, nx = vol.shape
+    distance_positions(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x)      # the depth and pixel checks, before any device use
+    if 8 * nz * ny * nx > LOCAL_THICKNESS_VOLUME_BUDGET:
+        raise ValueError("local_thickness: the squared distances of a %d x %d x %d volume take %d bytes, more than "
+                         "LOCAL_THICKNESS_VOLUME_BUDGET (%d)" % (nz, ny, nx, 8 * nz * ny * nx, LOCAL_THICKNESS_VOLUME_BUDGET))
+    weights = _slice_weights(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x)[:nz]
+    plan = _DistancePlan(vol, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    L, dev = _lib.lib(), vol.device
+    COUNTERS["local_thickness"] += 1
+    d2 = torch.empty(vol.shape, dtype=torch.float64, device=dev)
+    _lib.check(L.tomo_edt_squared(*plan.head(), 1, _p(d2), *plan.tail()), "tomo_edt_squared")
+    if exact:
+        levels = d2[d2 > 0].unique()                             # torch.unique: ascending; D2 > 0 exactly at the set voxels
+        if levels.numel() > max_levels:
+            raise ValueError("local_thickness: %d distinct squared distances, more than max_levels (%d): give the levels in "
+                             "radii_mm" % (levels.numel(), max_levels))
+        r2 = levels.cpu().numpy()
+        radii = np.sqrt(r2)
+        live = len(r2)
+    else:
+        r2 = radii * radii
+        live = int(np.searchsorted(r2, float(d2.max().item()), side="right"))     # r_k^2 <= the largest D2: a centre exists
+    K = len(r2)
+    level_map = torch.zeros(vol.shape, dtype=torch.int32, device=dev)
+    if live:
+        eroded = torch.empty_like(plan.bits)
+    bits, nzyx, tables = plan.head()[0], plan.head()[1:4], plan.head()[4:]
+    for k in range(live):
+        _lib.check(L.tomo_edt_at_least(_p(d2), bits, *nzyx, float(r2[k]), _p(eroded), _stream()), "tomo_edt_at_least")
+        _lib.check(L.tomo_edt_cover(_p(eroded), bits, *nzyx, *tables, float(r2[k]), k + 1, _p(level_map), *plan.tail()), "tomo_edt_cover")
+    del d2
+    values = torch.from_numpy((2.0 * radii).astype(np.float32)).to(dev) if K else None
+    counts = torch.empty((nz, K + 1), dtype=torch.int64, device=dev)
+    _lib.check(L.tomo_edt_thickness_finish(_p(level_map), bits, *nzyx, _p(values), K, _p(counts), _stream()),
+               "tomo_edt_thickness_finish")
+    per_slice = counts.cpu().numpy()
+    volume = np.zeros(K, dtype=np.float64)
+    for z in range(nz):                                          # ascending z, one float64 addition per slice and level
+        volume += per_slice[z, 1:] * weights[z]
+    voxels = per_slice.sum(axis=0)
+    mean, std, top = _thickness_statistics(radii, volume)
+    return LocalThickness(level_map.view(torch.float32), radii, voxels[1:].copy(), volume, int(voxels[0]), mean, std, top)
+
+
+def opening_volume(vol: BitVolume, radius_mm, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0) -> BitVolume:
+    """The opening of a resident volume by the OPEN ball of radius_mm millimetres -> a NEW BitVolume; `vol` is left untouched:
+    the set voxels p with a set voxel q such that D2(q) >= radius_mm ** 2 and |pq|^2 < radius_mm ** 2 (local_thickness'
+    definitions), i.e. local_thickness(vol, ..., radii_mm=[radius_mm]).thickness > 0.  radius_mm == 0: a copy.
+    One inside transform whose tail ballots the eroded set, one outside transform of those bits whose tail ballots d2 < r^2
+    and ANDs the original words: two bit volumes and distance_transform's chunked workspace, never a float per voxel."""
+    r = float(radius_mm)
+    if not (math.isfinite(r) and r >= 0):
+        raise ValueError("radius_mm must be finite and not negative")
+    plan = _DistancePlan(vol, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    COUNTERS["opening_volume"] += 1
+    if r == 0:
+        return BitVolume(plan.bits.clone(), vol.shape)
+    L = _lib.lib()
+    bits, rest = plan.head()[0], plan.head()[1:]
+    eroded, out = torch.empty_like(plan.bits), torch.empty_like(plan.bits)
+    _lib.check(L.tomo_edt_threshold_masked(bits, *rest, 1, r * r, 0, bits, _p(eroded), *plan.tail()), "tomo_edt_threshold_masked")
+    _lib.check(L.tomo_edt_threshold_masked(_p(eroded), *rest, 0, r * r, 1, bits, _p(out), *plan.tail()), "tomo_edt_threshold_masked")
+    return BitVolume(out, vol.shape)
 
 
 def pack_closed(mask: torch.Tensor) -> BitVolume:

@@ -100,6 +100,26 @@ def largest_inscribed_sphere(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_d
             'center_mm': (float(zt[z + 1]), float(yt[y + 1]), float(xt[x + 1]))}
 
 
+def thickness_statistics(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, radii_mm=None):
+    """How thick the object is, and where the volume sits in that scale (no counterpart in the reference): the local thickness
+    of Hildebrand & Ruegsegger -- at a voxel the diameter of the largest ball that fits inside the object and contains it
+    (pipeline.local_thickness: per-slice depths honoured, everything outside the stack is background) -> {'mean_mm', 'std_mm',
+    'max_mm', 'uncovered_voxels', 'histogram': [(diameter_mm, voxels, volume_mm3), ...]}, the histogram in ascending diameter,
+    one entry per level.  radii_mm=None: the exact thickness, for thin structures and unit or binary-fraction spacings (a
+    ValueError names radii_mm where the object has too many distinct distances); otherwise the ascending ball radii to
+    measure with -- the granulometry used to choose a smoothing radius.  An empty volume gives zeros and, in exact mode, an
+    empty histogram.  voxel_data: the bool (nz, ny, nx) array the other calculations take; anything else is a TypeError -- there
+    is no host path for this one."""
+    if not _on_device(voxel_data):
+        raise TypeError("thickness_statistics needs a bool (nz, ny, nx) array")
+    if radii_mm is not None:
+        pipeline._check_radii(radii_mm)                          # the argument checks, before anything is uploaded
+    pipeline.distance_positions(slice_depths, voxel_data.shape[0], mm_per_pixel_y, mm_per_pixel_x)
+    t = pipeline.local_thickness(to_device_volume(voxel_data), slice_depths, mm_per_pixel_y, mm_per_pixel_x, radii_mm)
+    return {'mean_mm': t.mean_mm, 'std_mm': t.std_mm, 'max_mm': t.max_mm, 'uncovered_voxels': t.uncovered_voxels,
+            'histogram': [(2.0 * float(r), int(n), float(v)) for r, n, v in zip(t.radii_mm, t.level_voxels, t.level_volume_mm3)]}
+
+
 def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=6, min_voxels=0, largest=False,
                          shape=False, topology=False):
     """The calculations of the class per connected component (no counterpart in the reference, which would be handed the mask
