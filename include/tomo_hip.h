@@ -283,6 +283,47 @@ int tomo_cc_cavities(const uint64_t *bits, int nz, int ny, int nx, const uint32_
                      const int64_t *bg_table, int64_t bg_cap, const int64_t *euler, int64_t *topo, void *stream);
 int tomo_cc_topology_rows(const int64_t *table, const int64_t *topo, int64_t cap, unsigned long long *tot, const uint8_t *sel,
                           const uint32_t *slot, int64_t *out, int64_t cap_sel, void *stream);
+/* Surface area per component by the discretised Crofton formula (Ohser & Muecklich; no counterpart in the reference, whose
+ * calculate_surface_area needs a mesh of the whole volume).  Coordinates, spacing and background are the distance transform's:
+ * pixel sizes mm_x, mm_y, slice depths d[k], everything outside the stack is background, the virtual slices -1 and nz have the
+ * depth of the edge slice next to them.
+ * Counts: for a set voxel p of slice k and each of its 26 neighbours q that is clear or outside the stack, one count in
+ * n[k][c], for the component of p (no labelling: for the volume as a whole).  The column c follows (|dz|, |dy|, |dx|) of q - p
+ * and the sign of dz:   0, 1, 2 = x, y, xy in the slice (2, 2, 4 neighbours);   3, 4, 5, 6 = z, xz, yz, xyz towards slice k + 1
+ * (1, 2, 2, 4);   7, 8, 9, 10 = the same towards slice k - 1.  A neighbour that is set but belongs to another component
+ * (diagonal contact under connectivity 6) is no transition: under both connectivities the counts of all components add up
+ * exactly to the counts of the unlabelled volume.
+ * Factors: the lattice height h = d[k] for c < 3, (d[k] + d[k + 1]) / 2 for c = 3 .. 6, (d[k - 1] + d[k]) / 2 for c = 7 .. 10.
+ * With (a_z, a_y, a_x) the class of column c and L = sqrt((a_z h)^2 + (a_y mm_y)^2 + (a_x mm_x)^2):
+ *     F[k][c] = 2 * w_c(mm_x, mm_y, h) * (mm_x * mm_y * h) / L
+ * directions = 13: w_c is twice the fraction of the unit sphere that is closer to (a_z h, a_y mm_y, a_x mm_x) / L than to any
+ * other of the 26 normalised lattice directions of the box (h, mm_y, mm_x); the weights of the 13 directions sum to 1 (cubic
+ * lattice: 0.09155578240952 for the axes, 0.07396125575216 for the face diagonals, 0.07039127956464 for the cube diagonals).
+ * directions = 3: w = 1 / 3 for x, y and z, 0 otherwise.  The host computes F (pipeline.surface_factors).
+ * Sum: S = sum over k ascending over the slices of the component's box, over c = 0 .. 10, of (double)n[k][c] * F[k][c]:
+ * sequential float64, never contracted (tomo_cc_zsums' discipline).  An axis-aligned flat face is underestimated (an 8^3
+ * cube reads 0.8615 of its 384): the known bias of the 13-direction estimator.
+ *   tomo_cc_surface_hist  surf uint64[11 * hist_cap], zeroed here: surf[11 * (off[c] + z - zmin[c]) + 0 .. 10] = n[z][0 .. 10] of
+ *                         selected component c + 1 (tables and selection: tomo_cc_zhist_offsets').  One thread per row slides
+ *                         the row and its eight neighbour rows along x, popcounts under the masks of the runs; integer atomics
+ *                         only: the same on every run.  tot[4] > hist_cap: bit 1 of tot[2] and nothing is added; a slice outside
+ *                         the component's box or a run id outside the tables: bit 2.  parent == NULL: no table is read (row_off,
+ *                         rank, tot, table, sel and off may be NULL), the volume is one component with the box 0 .. nz - 1 at
+ *                         entry 0: surf[11 * z + c] = n[z][c]; hist_cap < nz is TOMO_E_ARG then
+ *   tomo_cc_surface       one thread per selected component, its slices in ascending z: F = device float64[nz][11]; out
+ *                         float64[cap_sel] entry slot[c] = S; counts int64[cap_sel][7] row slot[c] = the counters summed over the
+ *                         slices with up and down folded: x, y, xy, z, xz, yz, xyz; labels int64[cap_sel] entry slot[c] = c + 1.
+ *                         directions = 3 leaves the columns whose factor is 0 out of the sum (the same S).  tot[4] > hist_cap or
+ *                         tot[5] > cap_sel: bit 1 of tot[2], nothing is written.  table == NULL: the unlabelled form (tot, sel, off
+ *                         and slot may be NULL), row 0 alone is written, from the entries 0 .. nz - 1, labels[0] = 1
+ * TOMO_E_ARG for a null pointer, a non-positive size or directions other than 3 / 13; TOMO_E_SIZE from 2^31 words, runs,
+ * components or selected components on (2^60 / 11 histogram entries). */
+int tomo_cc_surface_hist(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                         const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const int64_t *table, int64_t cap,
+                         const uint8_t *sel, const uint64_t *off, uint64_t *surf, int64_t hist_cap, void *stream);
+int tomo_cc_surface(const int64_t *table, int64_t cap, unsigned long long *tot, const uint8_t *sel, const uint64_t *off,
+                    const uint32_t *slot, const uint64_t *surf, int64_t hist_cap, const double *F, int nz, int directions,
+                    double *out, int64_t *counts, int64_t *labels, int64_t cap_sel, void *stream);
 /* The same across Z-slabs (slab_components.py): rank r labels its slab with the functions above (n_r components); local
  * component c has the global id base_r + c, base_r = n_0 + .. + n_(r-1).  Pieces that touch across a cut are united, the roots
  * (smallest id = the piece with the component's first voxel) numbered in ascending id: scipy's numbering of the whole stack.

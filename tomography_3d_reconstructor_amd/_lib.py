@@ -68,6 +68,10 @@ SIGNATURES = {
     "tomo_cc_cavities": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p,
                                 _c_i64, _c_p, _c_p, _c_p]),
     "tomo_cc_topology_rows": (_c_i, [_c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p]),
+    "tomo_cc_surface_hist": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64,
+                                    _c_p]),
+    "tomo_cc_surface": (_c_i, [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_i64,
+                               _c_p]),
     "tomo_cc_slice_components": (_c_i, [_c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p]),
     "tomo_cc_seam_union": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p,
                                   _c_p, _c_p]),

@@ -24,7 +24,8 @@ static int cc_geometry(const void *bits, int nz, int ny, int nx, int64_t *nrows,
     return TOMO_OK;
 }
 
-__device__ static inline void cc_flag(u64 *flags, u64 f) { atomicOr((unsigned long long *)flags, f); }
+// (flags == NULL: a call without tables, which has no guard that could fire)
+__device__ static inline void cc_flag(u64 *flags, u64 f) { if (flags) atomicOr((unsigned long long *)flags, f); }
 
 // ---------------------------------------------------------------------------------------------- rows and runs
 __device__ static inline u64 cc_tail_mask(int nx, int wx, int w)

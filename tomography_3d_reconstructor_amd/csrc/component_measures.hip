@@ -1,8 +1,10 @@
 // component_measures.hip -- what is measured per component on the run tables of components.hip: the measurement table
 // (voxels, box, index sums), the selection and its slice histograms (voxels, or six moment sums, per component and slice),
-// volume and centroid in mm, second moments and principal axes, Euler number, cavities and handles.  Every pass over the
-// rows is an accumulator for the row pass of cc_runs.h; the integer tables are integer atomics only, the float results are
-// sequential sums over those integers (nothing is contracted in this file: -ffp-contract=off).
+// volume and centroid in mm, second moments and principal axes, Euler number, cavities and handles, surface area (Crofton).
+// Every pass over the rows is an accumulator for the row pass of cc_runs.h -- over the runs, or, where a voxel's neighbours
+// decide (Euler number, surface area), over the words of the row with windows of the neighbour rows slid along; the integer
+// tables are integer atomics only, the float results are sequential sums over those integers (nothing is contracted in this
+// file: -ffp-contract=off).
 #include "cc_runs.h"
 
 // ---------------------------------------------------------------------------------------------- measurements per component
@@ -248,7 +250,7 @@ __device__ static inline u64 cc_squares_below(u64 n)
 }
 
 struct CcHist {
-    const u64 *table, *off;
+    const u64 *table, *off;                                 // both NULL: the whole volume is component 0, one entry per slice
     u64 *hist;
     u64 total;                                              // entries of the histogram
     u64 *flags;
@@ -258,8 +260,8 @@ struct CcHist {
 template <int SUMS>
 __device__ static inline void cc_hist_add(const CcHist &h, u32 c, u32 z, const u64 (&v)[SUMS])
 {
-    const u64 z0 = h.table[(int64_t)c * CC_COLS + 1], z1 = h.table[(int64_t)c * CC_COLS + 2];
-    const u64 pos = h.off[c] + ((u64)z - z0);
+    const u64 z0 = h.table ? h.table[(int64_t)c * CC_COLS + 1] : 0ull, z1 = h.table ? h.table[(int64_t)c * CC_COLS + 2] : h.total - 1;
+    const u64 pos = (h.off ? h.off[c] : 0ull) + ((u64)z - z0);
     if (z < z0 || z > z1 || pos >= h.total) {
         cc_flag(h.flags, CC_F_RANGE);
         return;
@@ -700,10 +702,68 @@ __device__ static inline u64 cc_euler_under(const u64 *pos, const u64 *neg, u64 
     return (u64)(int64_t)v;
 }
 
-// One thread per row (z, y) over its words and, LABELLED, over the runs in every word (as cc_filter_kernel walks them): a
-// thread adds up neighbouring runs of one component, a wave whose lanes all hold the same component adds once, then one signed
-// 64-bit atomic add (two's complement on u64) into euler[rank[parent[run]]].  Not LABELLED: no table is read and everything
-// goes to euler[0] -- the Euler number of the whole volume.
+// The WINDOW WALK: the row pass for what a voxel's neighbours decide.  One thread per row (z, y) slides CcWin windows of the row
+// r[0] and of NR - 1 neighbour rows along x (r[i] == NULL: a row outside the stack, it reads as 0) and, LABELLED, walks the runs
+// in every word (as cc_filter_kernel walks them): neighbouring runs of one component are added up, flushed when the component
+// changes -> the component + 1 the thread is left adding up.  Not LABELLED: no table is read, everything is component 1.  The
+// accumulator is the row pass's (cc_runs.h) with, in place of add(run):
+//   void word(const CcWin *win)              a word of the row that holds a set bit: what every run of it shares
+//   void add(const CcWin *win, u64 mask)     the bits `mask` of that word belong to the component begun
+template <int NR, bool LABELLED, bool FILTER, class Acc>
+__device__ static inline u32 cc_window_walk(const u64 *const *r, int nx, int wx, u32 first, u32 nruns,
+                                            const u32 *__restrict__ parent, const u32 *__restrict__ rank, u64 *flags, Acc &acc)
+{
+    u32 comp = 0;
+    CcWin win[NR];
+#pragma unroll
+    for (int i = 0; i < NR; i++) {
+        win[i].prv = 0;
+        win[i].cur = cc_word_or0(r[i], nx, wx, 0);
+        win[i].nxt = cc_word_or0(r[i], nx, wx, 1);
+    }
+    CcWordRuns it = {0, first, false};
+    for (int w = 0; w < wx; w++) {
+        const u64 m = win[0].cur;
+        if (m) {
+            acc.word(win);
+            if (!LABELLED) {
+                cc_change(comp, 1u, acc);
+                acc.add(win, m);
+            }
+            it.m = LABELLED ? m : 0;
+            while (cc_word_runs_next(it)) {
+                if (it.run < nruns) {
+                    u32 c = cc_component(parent, rank, it.run) + 1;
+                    if constexpr (FILTER) c = acc.filter(c);
+                    c = cc_change(comp, c, acc);
+                    if (!FILTER || c) acc.add(win, it.mask);
+                } else {
+                    cc_flag(flags, CC_F_RANGE);
+                }
+            }
+        }
+        it.carry = (m >> 63) != 0;                          // the word ended inside a run
+#pragma unroll
+        for (int i = 0; i < NR; i++) {
+            win[i].prv = win[i].cur;
+            win[i].cur = win[i].nxt;
+            win[i].nxt = cc_word_or0(r[i], nx, wx, w + 2);
+        }
+    }
+    return comp;
+}
+
+// chi per component: the terms of a word once, their popcounts under every run's mask
+template <int K>
+struct CcEulerAcc : CcSumAcc {
+    u64 pos[CC_EULER_POS], neg[CC_EULER_NEG];
+    __device__ void word(const CcWin *win) { cc_euler_terms<K>(win, pos, neg); }
+    __device__ void add(const CcWin *, u64 mask) { sum += cc_euler_under(pos, neg, mask); }
+};
+
+// The window walk with the rows the terms of chi read; a wave whose lanes all hold the same component adds once, then one signed
+// 64-bit atomic add (two's complement on u64) into euler[rank[parent[run]]].  Not LABELLED: everything goes to euler[0] -- the
+// Euler number of the whole volume.
 template <int K, bool LABELLED>
 __global__ __launch_bounds__(CC_THREADS) void cc_euler_kernel(const u64 *__restrict__ bits, int64_t nrows, int ny, int nx, int wx,
                                                               const u32 *__restrict__ row_off, const u64 *__restrict__ tot,
@@ -717,7 +777,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_euler_kernel(const u64 *__restr
     const u32 ncomp = LABELLED ? (u32)cc_ncomp(tot, cap) : 1u;
     if (LABELLED && row == 0 && tot[1] > (u64)cap) cc_flag(flags, CC_F_CAP);
     u32 comp = 0;                                           // component + 1 the thread is adding up, 0: none
-    CcSumAcc acc = {euler, ncomp, 0};
+    CcEulerAcc<K> acc = {{euler, ncomp, 0}, {}, {}};
     if (row < nrows) {
         const int y = (int)(row % ny);
         const bool up = y + 1 < ny, down = y > 0, front = row + ny < nrows, back = row >= ny;
@@ -734,41 +794,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_euler_kernel(const u64 *__restr
             r[3] = back && down ? self - (int64_t)(ny + 1) * wx : nullptr;
             r[4] = back && up ? self - (int64_t)(ny - 1) * wx : nullptr;
         }
-        CcWin win[NR];
-#pragma unroll
-        for (int i = 0; i < NR; i++) {
-            win[i].prv = 0;
-            win[i].cur = cc_word_or0(r[i], nx, wx, 0);
-            win[i].nxt = cc_word_or0(r[i], nx, wx, 1);
-        }
-        CcWordRuns it = {0, LABELLED ? row_off[row] : 0u, false};
-        for (int w = 0; w < wx; w++) {
-            const u64 m = win[0].cur;
-            if (m) {
-                u64 pos[CC_EULER_POS], neg[CC_EULER_NEG];
-                cc_euler_terms<K>(win, pos, neg);
-                if (!LABELLED) {
-                    comp = 1;
-                    acc.sum += cc_euler_under(pos, neg, m);
-                }
-                it.m = LABELLED ? m : 0;
-                while (cc_word_runs_next(it)) {
-                    if (it.run < nruns) {
-                        cc_change(comp, cc_component(parent, rank, it.run) + 1, acc);
-                        acc.sum += cc_euler_under(pos, neg, it.mask);
-                    } else {
-                        cc_flag(flags, CC_F_RANGE);
-                    }
-                }
-            }
-            it.carry = (m >> 63) != 0;                      // the word ended inside a run
-#pragma unroll
-            for (int i = 0; i < NR; i++) {
-                win[i].prv = win[i].cur;
-                win[i].cur = win[i].nxt;
-                win[i].nxt = cc_word_or0(r[i], nx, wx, w + 2);
-            }
-        }
+        comp = cc_window_walk<NR, LABELLED, false>(r, nx, wx, LABELLED ? row_off[row] : 0u, nruns, parent, rank, flags, acc);
     }
     cc_wave_tail<false>(comp, 0u, acc);
 }
@@ -977,5 +1003,173 @@ TOMO_API int tomo_cc_topology_rows(const int64_t *table, const int64_t *topo, in
     hipLaunchKernelGGL(cc_topology_rows_kernel, dim3((unsigned)ceil_div64(cap, CC_THREADS)), dim3(CC_THREADS), 0, (hipStream_t)stream,
                        (const u64 *)table, (const u64 *)topo, (const u64 *)tot, cap, sel, (const u32 *)slot, (u64 *)out, cap_sel,
                        (u64 *)tot + 2);
+    return tomo_status();
+}
+
+// ---------------------------------------------------------------------------------------------- surface area (Crofton)
+// The discretised Crofton formula: per set voxel p of slice k and each of its 26 neighbours q that is clear or outside the
+// stack, one count in column c of slice k, for the component of p; c by (|dz|, |dy|, |dx|) of q - p and the sign of dz:
+//   0, 1, 2: x, y, xy in the slice    3 .. 6: z, xz, yz, xyz towards slice k + 1    7 .. 10: the same towards slice k - 1
+// A set neighbour of another component (diagonal contact under connectivity 6) is no transition, so only the bits decide: per
+// word the 26 words `t & ~neighbour`, popcounted under each run's mask.  The area is the sequential float64 sum over the
+// slices of count * factor (tomo_cc_surface); the factors carry the spacing and the direction weights (pipeline.py).
+#define CC_SURF 11                   // counters per component and slice
+#define CC_SURF_CLASSES 7            // x, y, xy, z, xz, yz, xyz: the counters with up and down folded
+
+// the bits of mask whose neighbour in row r is clear: at the same x -> centre, at x + 1 and at x - 1 -> side
+__device__ static inline void cc_clear_beside(const CcWin &r, u64 mask, u64 &centre, u64 &side)
+{
+    centre += (u64)__popcll(mask & ~r.cur);
+    side += (u64)(__popcll(mask & ~cc_xp(r)) + __popcll(mask & ~cc_xm(r)));
+}
+
+// The accumulator of row (z, y) for the window walk over the row, (z, y - 1), (z, y + 1), then (z + 1, y - 1 .. y + 1), then
+// (z - 1, y - 1 .. y + 1).  sel == NULL: no labelling, everything counts.  Every run ends at a clear bit or at the edge of the
+// stack, so n[0] != 0 wherever a voxel was seen.
+struct CcSurfaceAcc {
+    CcHist h;
+    const uint8_t *sel;
+    u32 ncomp, z;
+    u64 n[CC_SURF];
+    __device__ u32 filter(u32 c) const { return (c - 1 >= ncomp || !sel[c - 1]) ? 0u : c; }
+    __device__ bool any() const { return n[0] != 0; }
+    __device__ u32 begin(u32 c)
+    {
+#pragma unroll
+        for (int k = 0; k < CC_SURF; k++) n[k] = 0;
+        return c;
+    }
+    __device__ void word(const CcWin *) {}
+    __device__ void add(const CcWin *win, u64 mask)
+    {
+        u64 self = 0;                                       // a bit of the mask is set in the row itself
+        cc_clear_beside(win[0], mask, self, n[0]);
+        cc_clear_beside(win[1], mask, n[1], n[2]);
+        cc_clear_beside(win[2], mask, n[1], n[2]);
+        cc_clear_beside(win[3], mask, n[5], n[6]);
+        cc_clear_beside(win[4], mask, n[3], n[4]);
+        cc_clear_beside(win[5], mask, n[5], n[6]);
+        cc_clear_beside(win[6], mask, n[9], n[10]);
+        cc_clear_beside(win[7], mask, n[7], n[8]);
+        cc_clear_beside(win[8], mask, n[9], n[10]);
+    }
+    __device__ CcSliceSum<CC_SURF> combine(bool mine, u32 zz) const
+    {
+        CcSliceSum<CC_SURF> w = {h, zz};
+#pragma unroll
+        for (int k = 0; k < CC_SURF; k++) w.v[k] = wave_sum64(mine ? n[k] : 0);
+        return w;
+    }
+    __device__ void flush(u32 c) const { cc_hist_add<CC_SURF>(h, c, z, n); }
+};
+
+template <bool LABELLED>
+__global__ __launch_bounds__(CC_THREADS) void cc_surface_hist_kernel(const u64 *__restrict__ bits, int64_t nrows, int ny, int nx, int wx,
+                                                                     const u32 *__restrict__ row_off, const u64 *__restrict__ tot,
+                                                                     int64_t cap_runs, const u32 *__restrict__ parent,
+                                                                     const u32 *__restrict__ rank, const u64 *__restrict__ table,
+                                                                     int64_t cap, const uint8_t *__restrict__ sel,
+                                                                     const u64 *__restrict__ off, u64 *__restrict__ surf,
+                                                                     int64_t hist_cap, u64 *flags)
+{
+    const int64_t row = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    const u32 nruns = LABELLED ? (u32)cc_count(tot, cap_runs) : 0u;
+    const u64 total = LABELLED ? tot[4] : (u64)(nrows / ny);    // no labelling: one entry per slice (the host checked hist_cap)
+    const bool fits = total <= (u64)hist_cap;
+    const u32 ncomp = !fits ? 0u : LABELLED ? (u32)cc_ncomp(tot, cap) : 1u;      // a histogram that is too short: nothing is touched
+    if (LABELLED && row == 0 && (!fits || tot[1] > (u64)cap)) cc_flag(flags, CC_F_CAP);
+    const bool live = row < nrows && ncomp != 0;
+    CcSurfaceAcc acc = {{table, off, surf, total, flags}, sel, ncomp, live ? (u32)(row / ny) : 0u, {}};
+    u32 comp = 0;                                           // SELECTED component + 1 the thread is left with, 0: none
+    if (live) {
+        const int y = (int)(row % ny);
+        const bool up = y + 1 < ny, down = y > 0, front = row + ny < nrows, back = row >= ny;
+        const u64 *self = bits + row * wx;
+        const u64 *r[9];
+        r[0] = self;
+        r[1] = down ? self - wx : nullptr;
+        r[2] = up ? self + wx : nullptr;
+        r[3] = front && down ? self + (int64_t)(ny - 1) * wx : nullptr;
+        r[4] = front ? self + (int64_t)ny * wx : nullptr;
+        r[5] = front && up ? self + (int64_t)(ny + 1) * wx : nullptr;
+        r[6] = back && down ? self - (int64_t)(ny + 1) * wx : nullptr;
+        r[7] = back ? self - (int64_t)ny * wx : nullptr;
+        r[8] = back && up ? self - (int64_t)(ny - 1) * wx : nullptr;
+        comp = cc_window_walk<9, LABELLED, LABELLED>(r, nx, wx, LABELLED ? row_off[row] : 0u, nruns, parent, rank, flags, acc);
+    }
+    cc_wave_tail<true>(comp, acc.z, acc);
+}
+
+TOMO_API int tomo_cc_surface_hist(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                                  const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const int64_t *table,
+                                  int64_t cap, const uint8_t *sel, const uint64_t *off, uint64_t *surf, int64_t hist_cap, void *stream)
+{
+    int64_t nrows;
+    int wx;
+    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
+    if (g != TOMO_OK) return g;
+    if (!surf || hist_cap <= 0) return TOMO_E_ARG;
+    if (parent && (!row_off || !rank || !tot || !table || !sel || !off || cap_runs <= 0 || cap <= 0)) return TOMO_E_ARG;
+    if (!parent && hist_cap < nz) return TOMO_E_ARG;
+    if (hist_cap >= ((int64_t)1 << 60) / CC_SURF || (parent && (cap_runs >= ((int64_t)1 << 31) || cap >= ((int64_t)1 << 31))))
+        return TOMO_E_SIZE;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(surf, 0, (size_t)hist_cap * CC_SURF * sizeof(u64), st) != hipSuccess) return TOMO_E_LAUNCH;
+    const dim3 grid((unsigned)ceil_div64(nrows, CC_THREADS)), block(CC_THREADS);
+    if (parent)
+        hipLaunchKernelGGL(cc_surface_hist_kernel<true>, grid, block, 0, st, (const u64 *)bits, nrows, ny, nx, wx, (const u32 *)row_off,
+                           (const u64 *)tot, cap_runs, (const u32 *)parent, (const u32 *)rank, (const u64 *)table, cap, sel,
+                           (const u64 *)off, (u64 *)surf, hist_cap, (u64 *)tot + 2);
+    else
+        hipLaunchKernelGGL(cc_surface_hist_kernel<false>, grid, block, 0, st, (const u64 *)bits, nrows, ny, nx, wx, (const u32 *)nullptr,
+                           (const u64 *)nullptr, (int64_t)0, (const u32 *)nullptr, (const u32 *)nullptr, (const u64 *)nullptr, (int64_t)1,
+                           (const uint8_t *)nullptr, (const u64 *)nullptr, (u64 *)surf, hist_cap, (u64 *)nullptr);
+    return tomo_status();
+}
+
+// One thread per component, as cc_zsums_kernel; a selected one walks its slices in ascending z and the columns 0 .. 10 of
+// each: S += (double)count * F[z][column], plain sequential float64.  directions == 3: only the columns of x, y and z enter the
+// sum (the factors of the others are 0 there).  table == NULL: no labelling, thread 0 sums the slices 0 .. nz - 1 into row 0.
+__global__ __launch_bounds__(CC_THREADS) void cc_surface_kernel(const u64 *__restrict__ table, const u64 *__restrict__ tot, int64_t cap,
+                                                                const uint8_t *__restrict__ sel, const u64 *__restrict__ off,
+                                                                const u32 *__restrict__ slot, const u64 *__restrict__ surf,
+                                                                int64_t hist_cap, const double *__restrict__ F, int nz, int directions,
+                                                                double *__restrict__ out, u64 *__restrict__ counts,
+                                                                int64_t *__restrict__ labels, int64_t cap_sel, u64 *flags)
+{
+    const int64_t c = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    CcSegment s = {0, (u64)nz - 1, 0, 0};
+    if (table ? !cc_segment(table, tot, cap, sel, off, slot, hist_cap, nz, cap_sel, c, flags, s) : c != 0) return;
+    const u64 *m = surf + CC_SURF * s.o;
+    double area = 0.0;
+    u64 n[CC_SURF_CLASSES] = {};
+    for (u64 z = s.z0; z <= s.z1; z++) {
+#pragma unroll
+        for (int k = 0; k < CC_SURF; k++) {
+            const u64 v = m[CC_SURF * (z - s.z0) + k];
+            if (directions == 13 || k == 0 || k == 1 || k == 3 || k == 7) area += (double)v * F[CC_SURF * z + k];
+            n[k < CC_SURF_CLASSES ? k : k - 4] += v;
+        }
+    }
+    out[s.k] = area;
+#pragma unroll
+    for (int k = 0; k < CC_SURF_CLASSES; k++) counts[CC_SURF_CLASSES * (int64_t)s.k + k] = n[k];
+    labels[s.k] = c + 1;
+}
+
+TOMO_API int tomo_cc_surface(const int64_t *table, int64_t cap, unsigned long long *tot, const uint8_t *sel, const uint64_t *off,
+                             const uint32_t *slot, const uint64_t *surf, int64_t hist_cap, const double *F, int nz, int directions,
+                             double *out, int64_t *counts, int64_t *labels, int64_t cap_sel, void *stream)
+{
+    if (!surf || !F || !out || !counts || !labels || hist_cap <= 0 || nz <= 0 || cap_sel <= 0 || (directions != 3 && directions != 13))
+        return TOMO_E_ARG;
+    if (table && (!tot || !sel || !off || !slot || cap <= 0)) return TOMO_E_ARG;
+    if (!table && hist_cap < nz) return TOMO_E_ARG;
+    if (cap_sel >= ((int64_t)1 << 31) || hist_cap >= ((int64_t)1 << 60) / CC_SURF || (table && cap >= ((int64_t)1 << 31)))
+        return TOMO_E_SIZE;
+    hipLaunchKernelGGL(cc_surface_kernel, dim3(table ? (unsigned)ceil_div64(cap, CC_THREADS) : 1u), dim3(CC_THREADS), 0,
+                       (hipStream_t)stream, (const u64 *)table, (const u64 *)tot, cap, sel, (const u64 *)off, (const u32 *)slot,
+                       (const u64 *)surf, hist_cap, F, nz, directions, out, (u64 *)counts, labels, cap_sel,
+                       tot ? (u64 *)tot + 2 : (u64 *)nullptr);
     return tomo_status();
 }

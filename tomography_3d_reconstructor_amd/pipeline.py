@@ -24,7 +24,7 @@ COUNTERS = dict.fromkeys(("na_hint_hit", "na_hint_miss", "mc3_hint_hit", "mc3_hi
                           "components_filter", "slab_components_label", "slab_components_seam", "slab_components_merge",
                           "slab_components_expand", "slab_components_filter", "distance_transform", "distance_offset",
                           "components_measure", "components_zhist", "components_moments", "components_euler",
-                          "components_cavities", "local_thickness", "opening_volume"), 0)
+                          "components_cavities", "local_thickness", "opening_volume", "components_surface"), 0)
 NA_HINTS = os.environ.get("TOMO_NA_HINTS", "1") not in ("", "0")   # marching_cubes: launch ahead of the first count download
 _NA_HINT = {}
 LIST_LIMIT = 2 ** 31        # active-voxel list entries / vertices / triangles one pass can index (int32 offsets in mc.hip, mesh.hip);
@@ -239,12 +239,15 @@ def point_cloud(vol: BitVolume, slice_depths, mm_per_pixel_x, mm_per_pixel_y, su
 CONNECTIVITIES = (6, 26)     # generate_binary_structure(3, 1) -- the cross of voxel_processor.py:88,91 -- and (3, 3)
 RUN_LIMIT = 2 ** 31          # run ids are 32-bit in csrc/components.hip
 TABLE_COLUMNS = 10           # voxels, zmin, zmax, ymin, ymax, xmin, xmax, sum z, sum y, sum x (tomo_cc_measure)
-# bytes component_properties / component_moments may take for the per-slice entries of the selected components (8 bytes an entry
-# for the voxel counts, 48 for the six moment sums); one component (at most nz entries) is always granted
+# bytes component_properties / component_moments / component_surface may take for the per-slice entries of the selected components
+# (8 bytes an entry for the voxel counts, 48 for the six moment sums, 88 for the surface counters); one component (at most nz
+# entries) is always granted
 COMPONENT_HIST_BUDGET = 1 << 30
 MOMENT_SUMS = 6              # uint64 per component and slice: N, sum j', sum i', sum j'^2, sum i'^2, sum j' i' (tomo_cc_moment_hist)
 MOMENT_COLUMNS = 22          # float64 per row of tomo_cc_moments: W, centre (3), covariance (6), variances (3), axes (9)
 TOPOLOGY_COLUMNS = 3         # euler, cavities, handles (tomo_cc_cavities)
+SURFACE_COUNTERS = 11        # uint64 per component and slice: x, y, xy, then z, xz, yz, xyz upwards and downwards (tomo_cc_surface_hist)
+SURFACE_CLASSES = 7          # direction classes: x, y, xy, z, xz, yz, xyz
 
 
 @dataclass
@@ -653,6 +656,186 @@ def volume_topology(vol: BitVolume, connectivity=6) -> dict:
     topo = ComponentRuns(vol, connectivity).topology()
     euler, cavities, handles = (int(v) for v in topo.sum(dim=0).cpu()) if topo.shape[0] else (0, 0, 0)
     return {"components": int(topo.shape[0]), "cavities": cavities, "handles": handles, "euler": euler}
+
+
+# ----------------------------------------------------------------------------- surface area (Crofton)
+_SURFACE_CLASS_STEPS = ((0, 0, 1), (0, 1, 0), (0, 1, 1), (1, 0, 0), (1, 0, 1), (1, 1, 0), (1, 1, 1))   # (a_z, a_y, a_x): x y xy z xz yz xyz
+_CROFTON_WEIGHTS = {}
+
+
+def _voronoi_cell_area(a, others):
+    """Area on the unit sphere of the set of unit vectors u closer to the unit vector `a` than to any row of `others`: the
+    spherical polygon the half-spaces u . (a - b) >= 0 cut out.  Its corners lie among the normalised +-cross products of pairs
+    of those normals; the ones that satisfy every constraint are ordered around a, and the area is the sum of the solid angles
+    of the triangles (a, v_i, v_i+1) (Van Oosterom & Strackee)."""
+    normals = a[None, :] - others
+    i, j = np.triu_indices(len(normals), 1)
+    cand = np.cross(normals[i], normals[j])
+    length = np.linalg.norm(cand, axis=1)
+    cand = cand[length > 1e-12] / length[length > 1e-12, None]
+    cand = np.concatenate([cand, -cand])
+    cand = cand[(cand @ normals.T >= -1e-12).all(axis=1)]
+    corners = []
+    for v in cand:                                                  # a corner where more than three cells meet comes several times
+        if not any(np.linalg.norm(v - c) < 1e-9 for c in corners):
+            corners.append(v)
+    corners = np.asarray(corners)
+    if len(corners) < 3:
+        raise ValueError("crofton_weights: the spacings are too far apart for float64")
+    e1 = corners[0] - (corners[0] @ a) * a                         # a frame of the tangent plane at a
+    e1 /= np.linalg.norm(e1)
+    e2 = np.cross(a, e1)
+    corners = corners[np.argsort(np.arctan2(corners @ e2, corners @ e1))]
+    nxt = np.roll(corners, -1, axis=0)
+    det = np.abs(np.cross(corners, nxt) @ a)
+    return float(np.sum(2.0 * np.arctan2(det, 1.0 + corners @ a + nxt @ a + np.sum(corners * nxt, axis=1))))
+
+
+def crofton_weights(mm_x, mm_y, h, directions=13) -> np.ndarray:
+    """The direction weights of the discretised Crofton formula for a lattice of spacing (h, mm_y, mm_x) along (z, y, x) ->
+    float64 (7,), one per class in the order x, y, xy, z, xz, yz, xyz.  directions=13: twice the fraction of the unit sphere
+    that is closer to the class's normalised lattice direction than to any other of the 26 (the area of its spherical Voronoi
+    cell over 2 pi); over the 13 directions -- 1 + 1 + 2 + 1 + 2 + 2 + 4 of the classes -- the weights sum to 1.  A cubic
+    lattice gives the published 0.0915558, 0.0739613 and 0.0703913.  directions=3: 1 / 3 for x, y and z, 0 otherwise.  Only
+    the ratios of the spacings matter.  Pure NumPy, remembered per argument tuple."""
+    if directions not in (3, 13):
+        raise ValueError("directions must be 3 or 13")
+    mm_x, mm_y, h = _positive(mm_x, "mm_x"), _positive(mm_y, "mm_y"), _positive(h, "h")
+    key = (mm_x, mm_y, h, directions)
+    w = _CROFTON_WEIGHTS.get(key)
+    if w is None:
+        if directions == 3:
+            w = np.array([1, 1, 0, 1, 0, 0, 0], dtype=np.float64) / 3.0
+        else:
+            steps = np.array([(dz, dy, dx) for dz in (-1, 0, 1) for dy in (-1, 0, 1) for dx in (-1, 0, 1) if dz or dy or dx],
+                             dtype=np.float64)
+            units = steps * np.array([h, mm_y, mm_x])
+            units /= np.linalg.norm(units, axis=1)[:, None]
+            w = np.empty(SURFACE_CLASSES, dtype=np.float64)
+            for c, step in enumerate(_SURFACE_CLASS_STEPS):
+                own = (steps == np.array(step, dtype=np.float64)).all(axis=1)
+                w[c] = _voronoi_cell_area(units[own][0], units[~own]) / (2.0 * math.pi)
+        w.setflags(write=False)
+        if len(_CROFTON_WEIGHTS) >= 64:
+            _CROFTON_WEIGHTS.clear()
+        _CROFTON_WEIGHTS[key] = w
+    return w.copy()
+
+
+def surface_factors(slice_depths, nz, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, directions=13) -> np.ndarray:
+    """What one count of tomo_cc_surface_hist's column c in slice k adds to the area -> float64 (nz, 11):
+    F[k][c] = 2 * w * (mm_x * mm_y * h) / L with h the lattice height of the column -- depth[k] in the slice, (depth[k] +
+    depth[k + 1]) / 2 towards slice k + 1 (columns 3 .. 6), (depth[k - 1] + depth[k]) / 2 towards slice k - 1 (7 .. 10), the
+    virtual slices -1 and nz as deep as the edge slice next to them -- w = crofton_weights(mm_x, mm_y, h, directions) of the
+    column's class (a_z, a_y, a_x) and L = sqrt((a_z h)^2 + (a_y mm_y)^2 + (a_x mm_x)^2).  slice_depths=None: 1.0 per slice."""
+    if directions not in (3, 13):
+        raise ValueError("directions must be 3 or 13")
+    zt, _, _ = distance_positions(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x)        # the argument checks
+    nz = len(zt) - 2
+    mm_y, mm_x = float(mm_per_pixel_y), float(mm_per_pixel_x)
+    d = np.ones(nz) if slice_depths is None else np.asarray(slice_depths, dtype=np.float64).reshape(-1)
+    d = np.concatenate([d[:1], d, d[-1:]])
+    rows = {}
+
+    def row(h):
+        """The seven factors of a lattice of height h, computed once per distinct height."""
+        h = float(h)
+        if h not in rows:
+            w = crofton_weights(mm_x, mm_y, h, directions)
+            rows[h] = [2.0 * w[cls] * (mm_x * mm_y * h) / math.sqrt((az * h) ** 2 + (ay * mm_y) ** 2 + (ax * mm_x) ** 2)
+                       for cls, (az, ay, ax) in enumerate(_SURFACE_CLASS_STEPS)]
+        return rows[h]
+
+    F = np.empty((nz, SURFACE_COUNTERS), dtype=np.float64)
+    for cols, classes, heights in ((slice(0, 3), slice(0, 3), d[1:-1]), (slice(3, 7), slice(3, 7), (d[1:-1] + d[2:]) / 2.0),
+                                   (slice(7, 11), slice(3, 7), (d[:-2] + d[1:-1]) / 2.0)):
+        distinct, which = np.unique(heights, return_inverse=True)
+        F[:, cols] = np.array([row(h) for h in distinct], dtype=np.float64)[which.reshape(-1), classes]
+    return F
+
+
+@dataclass
+class SurfaceArea:
+    """surface_area's answer."""
+    surface_area_mm2: float
+    pair_counts: np.ndarray      # int64 (7,): object / background transitions per class x, y, xy, z, xz, yz, xyz
+
+
+@dataclass
+class ComponentSurface:
+    """component_surface's answer: host arrays, one row per selected component in ascending label."""
+    labels: np.ndarray            # int64 (m,)
+    voxels: np.ndarray            # int64 (m,)
+    pair_counts: np.ndarray       # int64 (m, 7): transitions per class x, y, xy, z, xz, yz, xyz
+    surface_area_mm2: np.ndarray  # float64 (m,)
+
+    def __len__(self):
+        return len(self.labels)
+
+
+def surface_area(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, directions=13) -> SurfaceArea:
+    """The surface area of a resident volume in mm^2 by the discretised Crofton formula (Ohser & Muecklich; the method of ITK's
+    Perimeter and MorphoLibJ), without a mesh and without labelling.  For every set voxel and each of its 26 neighbours that is
+    clear or outside the stack one transition is counted, per slice and per direction class; the area is the sequential
+    float64 sum over the slices in ascending z of count * surface_factors(...), the spacing being distance_transform's
+    (slice_depths=None: 1.0 per slice).  directions=3 uses the x, y and z transitions only: 2 / 3 of the exposed-face area.
+    A ball is met within about half a percent; an axis-aligned flat face is underestimated (a cube of 8^3 voxels reads 0.8615
+    of its face area): the known bias of the estimator.  Two launches, one host read."""
+    nz, ny, nx = vol.shape
+    F = surface_factors(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x, directions)
+    L, dev, st = _lib.lib(), vol.device, _stream()
+    surf = torch.empty(SURFACE_COUNTERS * nz, dtype=torch.int64, device=dev)
+    COUNTERS["components_surface"] += 1
+    _lib.check(L.tomo_cc_surface_hist(_p(vol.bits.contiguous()), nz, ny, nx, None, 0, None, None, None, None, 0, None, None, _p(surf),
+                                      nz, st), "tomo_cc_surface_hist")
+    tab = torch.from_numpy(F).to(dev)
+    out = torch.empty(2 + SURFACE_CLASSES, dtype=torch.float64, device=dev)       # the area, the label, the seven counts: one read
+    words = out.view(torch.int64)
+    _lib.check(L.tomo_cc_surface(None, 0, None, None, None, None, _p(surf), nz, _p(tab), nz, int(directions),
+                                 _p(out), _p(words[2:]), _p(words[1:2]), 1, st), "tomo_cc_surface")
+    host = out.cpu().numpy()
+    return SurfaceArea(float(host[0]), host[2:].view(np.int64).copy())
+
+
+def _component_surface_from(voxels, labels, counts, area) -> ComponentSurface:
+    return ComponentSurface(labels, voxels, np.ascontiguousarray(counts, dtype=np.int64).reshape(-1, SURFACE_CLASSES), area)
+
+
+def component_surface(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, connectivity=6, min_voxels=0,
+                      largest=False, directions=13) -> ComponentSurface:
+    """Surface area per component of a resident volume by the discretised Crofton formula (surface_area) -> ComponentSurface,
+    one row per component the keep rule of component_properties selects (at least min_voxels voxels; largest: only the largest
+    of those, the lowest label among equals), in ascending label: the rows, in the same order, component_properties returns
+    for the same arguments.  A transition is a set voxel of the component next to a voxel that is clear or outside the stack;
+    a set neighbour of ANOTHER component (diagonal contact under connectivity 6) is none, so under both connectivities the
+    counts of all components add up to surface_area's.  The same four host reads as component_properties; working memory
+    scales with the runs, the components and eleven counters per slice of the box of every SELECTED component (88 bytes an
+    entry; beyond COMPONENT_HIST_BUDGET bytes for more than one component: TomoError) -- never with the voxels."""
+    if connectivity not in CONNECTIVITIES:
+        raise ValueError("connectivity must be 6 or 26")
+    nz, ny, nx = vol.shape
+    F = surface_factors(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x, directions)
+    cr = ComponentRuns(vol, connectivity)
+    picked = cr.select(min_voxels, largest)
+    if picked is None or picked.total == 0:
+        none = np.zeros(0, dtype=np.int64)
+        return _component_surface_from(none, none.copy(), np.zeros((0, SURFACE_CLASSES), dtype=np.int64), np.zeros(0))
+    _check_hist_budget("component_surface", "surface counters per slice", picked, 8 * SURFACE_COUNTERS)
+    L, dev, st = _lib.lib(), vol.device, _stream()
+    table, n, total, m = picked.table, picked.table.shape[0], picked.total, picked.m
+    surf = torch.empty(SURFACE_COUNTERS * total, dtype=torch.int64, device=dev)
+    COUNTERS["components_surface"] += 1
+    _lib.check(L.tomo_cc_surface_hist(_p(cr.bits), nz, ny, nx, *cr._tables(), _p(cr.tot), _p(table), n, _p(picked.sel), _p(picked.off),
+                                      _p(surf), total, st), "tomo_cc_surface_hist")
+    tab = torch.from_numpy(F).to(dev)
+    area = torch.empty(m, dtype=torch.float64, device=dev)
+    counts = torch.empty((m, SURFACE_CLASSES), dtype=torch.int64, device=dev)
+    labels = torch.ones(m, dtype=torch.int64, device=dev)       # a valid row for the gather below even where a guard fired
+    _lib.check(L.tomo_cc_surface(_p(table), n, _p(cr.tot), _p(picked.sel), _p(picked.off), _p(picked.slot), _p(surf), total,
+                                 _p(tab), nz, int(directions), _p(area), _p(counts), _p(labels), m, st),
+               "tomo_cc_surface")
+    voxels = table[:, 0].index_select(0, labels - 1)
+    return _component_surface_from(*cr._download_checked("component_surface", voxels, labels, counts, area))
 
 
 # ----------------------------------------------------------------------------- Euclidean distance in millimetres
