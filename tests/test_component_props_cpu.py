@@ -146,6 +146,66 @@ def test_pipeline_rejects_bad_arguments_before_it_touches_the_device():
     for kw in ({"mm_per_pixel_y": 0.0}, {"mm_per_pixel_x": -1.0}, {"mm_per_pixel_x": float("inf")}):
         with pytest.raises(ValueError):
             pipeline.component_properties(vol, [1.0] * 3, **kw)
+    # the four module functions are one construction and one method call: the checks still come before the device
+    measured = (pipeline.component_properties, pipeline.component_moments, pipeline.component_surface)
+    for fn in measured + (pipeline.component_topology,):
+        with pytest.raises(ValueError):
+            fn(vol, connectivity=18)
+    for fn in measured:
+        for bad in ([1.0, 1.0], [1.0] * 4, [1.0, 0.0, 1.0], [1.0, -2.0, 1.0], [1.0, float("nan"), 1.0], [1.0, float("inf"), 1.0]):
+            with pytest.raises(ValueError):
+                fn(vol, bad)
+        for kw in ({"mm_per_pixel_y": 0.0}, {"mm_per_pixel_x": -1.0}, {"mm_per_pixel_x": float("inf")}):
+            with pytest.raises(ValueError):
+                fn(vol, [1.0] * 3, **kw)
+    for directions in (0, 5, 26):
+        with pytest.raises(ValueError):
+            pipeline.component_surface(vol, directions=directions)
+
+
+def test_volume_calculator_function_rejects_bad_arguments_before_it_touches_the_device():
+    """Everything is checked before the upload, surface_directions too: without a device a ValueError is all that can come."""
+    v, d = np.ones((3, 4, 5), dtype=bool), np.ones(3)
+    with pytest.raises(ValueError):
+        volume_calculator.component_properties(v, 1.0, 1.0, d, surface=True, surface_directions=5)
+    with pytest.raises(ValueError):
+        volume_calculator.component_properties(v, 1.0, 1.0, d, shape=True, topology=True, surface=True, surface_directions=5)
+    with pytest.raises(ValueError):
+        volume_calculator.component_properties(v, 1.0, 1.0, d, connectivity=18)
+    for bad in ([1.0, 1.0], [1.0, 0.0, 1.0], [1.0, float("nan"), 1.0]):
+        with pytest.raises(ValueError):
+            volume_calculator.component_properties(v, 1.0, 1.0, bad)
+    with pytest.raises(ValueError):
+        volume_calculator.component_properties(v, 0.0, 1.0, d)
+
+
+def test_the_empty_answer_comes_out_of_the_description():
+    """The zero-row arrays every measurement declares, through its own _from: the dtypes and shapes the "empty volume" tests
+    of the GPU tier assert."""
+    p = pipeline._component_properties_from(*pipeline._PROPERTIES.empty(), MM_Y, MM_X)
+    assert len(p) == 0 and p.index_box.shape == (0, 6) and p.index_sums.shape == (0, 3) and p.centroid_mm.shape == (0, 3)
+    assert p.centroid_index.shape == (0, 3) and p.labels.shape == (0,) and p.voxels.shape == (0,) and p.volume_mm3.shape == (0,)
+    assert all(getattr(p, k).dtype == np.int64 for k in ("labels", "voxels", "index_box", "index_sums"))
+    assert all(getattr(p, k).dtype == np.float64 for k in ("volume_mm3", "centroid_index", "centroid_mm"))
+    q = pipeline._component_moments_from(*pipeline._MOMENTS.empty())
+    assert len(q) == 0 and q.labels.dtype == np.int64 and q.voxels.dtype == np.int64 and q.labels.shape == q.voxels.shape == (0,)
+    assert q.volume_mm3.shape == (0,) and q.center_of_mass_mm.shape == (0, 3) and q.covariance_mm2.shape == (0, 3, 3)
+    assert q.principal_variances_mm2.shape == (0, 3) and q.principal_axes.shape == (0, 3, 3) and q.ellipsoid_axes_mm.shape == (0, 3)
+    assert all(getattr(q, k).dtype == np.float64 for k in ("volume_mm3", "center_of_mass_mm", "covariance_mm2",
+                                                           "principal_variances_mm2", "principal_axes", "ellipsoid_axes_mm"))
+    t = pipeline._component_topology_from(*pipeline._TOPOLOGY.empty())
+    assert len(t) == 0
+    for k in ("labels", "voxels", "euler", "cavities", "handles"):
+        assert getattr(t, k).shape == (0,) and getattr(t, k).dtype == np.int64
+    voxels, labels, area, counts = pipeline._SURFACE.empty()       # in the order the finishing entry point takes them
+    a = pipeline._component_surface_from(voxels, labels, counts, area)
+    assert len(a) == 0 and a.labels.shape == (0,) and a.voxels.shape == (0,) and a.surface_area_mm2.shape == (0,)
+    assert a.labels.dtype == np.int64 and a.voxels.dtype == np.int64
+    assert a.pair_counts.shape == (0, 7) and a.pair_counts.dtype == np.int64 and a.surface_area_mm2.dtype == np.float64
+    histograms = ((pipeline._PROPERTIES, 1), (pipeline._MOMENTS, pipeline.MOMENT_SUMS), (pipeline._SURFACE, pipeline.SURFACE_COUNTERS))
+    for spec, words in histograms:
+        assert spec.words == words and all(hasattr(_lib.lib(), name) for name in (spec.hist, spec.finish))
+        assert spec.counter in pipeline.COUNTERS
 
 
 def test_volume_calculator_function_takes_bool_volumes_only():

@@ -196,9 +196,9 @@ def test_the_voxel_counts_are_the_first_moment_sum(dev, name, conn):
         assert host[2] == 0 and m > 0 and total >= m, (what, host)
         hist = torch.empty(total, dtype=torch.int64, device=dev)
         mom = torch.empty(pipeline.MOMENT_SUMS * total, dtype=torch.int64, device=dev)
-        _lib.check(L.tomo_cc_zhist(*geo, *cr._tables(), _p(cr.tot), _p(table), n, _p(sel), _p(off), _p(hist), total, st), "tomo_cc_zhist")
-        _lib.check(L.tomo_cc_moment_hist(*geo, *cr._tables(), _p(cr.tot), _p(table), n, _p(sel), _p(off), _p(mom), total, st),
-                   "tomo_cc_moment_hist")
+        head = cr.hist_head(pipeline.ComponentSelection(table, sel, off, slot, total, m))
+        _lib.check(L.tomo_cc_zhist(*head, _p(hist), total, st), "tomo_cc_zhist")
+        _lib.check(L.tomo_cc_moment_hist(*head, _p(mom), total, st), "tomo_cc_moment_hist")
         assert torch.equal(mom.view(total, pipeline.MOMENT_SUMS)[:, 0], hist), what
         assert int(hist.sum()) == int(sizes[sel.cpu().numpy() != 0].sum()), what       # ... and neither is empty
         assert pipeline._download(cr.tot)[2] == 0, what
@@ -297,5 +297,5 @@ def test_fenced(dev, poison, conn):
         with fz.unchanged(vol.bits):
             held(pipeline.component_moments(vol, d, MM_Y, MM_X, conn, 2), exp, "fenced")
             held(pipeline.component_moments(vol, d, MM_Y, MM_X, conn, 2, True), exp_largest, "fenced largest")
-        assert fz.ran("_measure") == 2 and fz.ran("select") >= 2 * 4 and fz.ran("component_moments") >= 2 * 3
+        assert fz.ran("_measure") == 2 and fz.ran("select") >= 2 * 4 and fz.ran("_rows") >= 2 * 3
     T.run_fenced(poison, body, "%s/%d" % (name, conn))

@@ -272,5 +272,5 @@ def test_fenced(dev, poison, conn):
             assert np.array_equal(pipeline.component_table(vol, conn).cpu().numpy(), tab)
             same(pipeline.component_properties(vol, d, MM_Y, MM_X, conn, 2), exp, "fenced")
             same(pipeline.component_properties(vol, d, MM_Y, MM_X, conn, 2, True), exp_largest, "fenced largest")
-        assert fz.ran("_measure") == 3 and fz.ran("select") >= 2 * 4 and fz.ran("component_properties") >= 2 * 3
+        assert fz.ran("_measure") == 3 and fz.ran("select") >= 2 * 4 and fz.ran("_rows") >= 2 * 3
     run_fenced(poison, body, "%s/%d" % (name, conn))

@@ -7,6 +7,7 @@ SciPy's spherical Voronoi cells, held to hand values by tests/test_surface_cpu.p
 test.  The counts are integers and compared with ==; the area is bit for bit the sequential float64 sum of the reference's
 counts times pipeline.surface_factors, and within 1e-11 (relative) of the sum with the reference's own factors: the two
 weight computations agree to 1e-14, the sum has a few thousand terms."""
+import dataclasses
 import math
 import os
 import sys
@@ -253,27 +254,25 @@ def test_the_guards_flag_instead_of_writing_outside_a_table(dev, monkeypatch):
     nz = v.shape[0]
     cr = pipeline.ComponentRuns(vol, 6)
     picked = cr.select(0, False)
-    table, n, total, m = picked.table, picked.table.shape[0], picked.total, picked.m
+    n, total, m = picked.table.shape[0], picked.total, picked.m
     assert n == 293 and total > m
     surf = torch.full((11 * total,), 77, dtype=torch.int64, device=dev)
-    head = (_p(cr.bits), nz, v.shape[1], v.shape[2], *cr._tables(), _p(cr.tot), _p(table), n, _p(picked.sel), _p(picked.off))
-    _lib.check(L.tomo_cc_surface_hist(*head, _p(surf), total - 1, st), "tomo_cc_surface_hist")
+    _lib.check(L.tomo_cc_surface_hist(*cr.hist_head(picked), _p(surf), total - 1, st), "tomo_cc_surface_hist")
     assert pipeline._download(cr.tot)[2] == 2
     assert surf[:11 * (total - 1)].eq(0).all() and surf[11 * (total - 1):].eq(77).all()
     area = torch.full((m,), 77.0, dtype=torch.float64, device=dev)
     counts = torch.full((m, 7), 77, dtype=torch.int64, device=dev)
     labels = torch.full((m,), 77, dtype=torch.int64, device=dev)
     tab = torch.from_numpy(pipeline.surface_factors(None, nz)).to(dev)
-    _lib.check(L.tomo_cc_surface(_p(table), n, _p(cr.tot), _p(picked.sel), _p(picked.off), _p(picked.slot), _p(surf), total - 1,
-                                 _p(tab), nz, 13, _p(area), _p(counts), _p(labels), m, st), "tomo_cc_surface")
+    _lib.check(L.tomo_cc_surface(*cr.finish_head(picked), _p(surf), total - 1, _p(tab), nz, 13, _p(area), _p(counts), _p(labels), m, st),
+               "tomo_cc_surface")
     assert area.eq(77.0).all() and counts.eq(77).all() and labels.eq(77).all()
     with pytest.raises(_lib.TomoError):
         cr._checked()
 
     cr = pipeline.ComponentRuns(vol, 6)                          # ... and one result row short
     picked = cr.select(0, False)
-    head = (_p(cr.bits), nz, v.shape[1], v.shape[2], *cr._tables(), _p(cr.tot), _p(picked.table), n, _p(picked.sel), _p(picked.off))
-    _lib.check(L.tomo_cc_surface_hist(*head, _p(surf), total, st), "tomo_cc_surface_hist")
+    _lib.check(L.tomo_cc_surface_hist(*cr.hist_head(picked), _p(surf), total, st), "tomo_cc_surface_hist")
     assert pipeline._download(cr.tot)[2] == 0
     per = reference("noise_030", 6)[2]
     got = surf.cpu().numpy().reshape(total, 11)
@@ -281,8 +280,8 @@ def test_the_guards_flag_instead_of_writing_outside_a_table(dev, monkeypatch):
     box = picked.table.cpu().numpy()[:, 1:3]
     for c in (0, 1, n // 2, n - 1):
         assert np.array_equal(got[off[c]:off[c + 1]], per[c, box[c, 0]:box[c, 1] + 1])
-    _lib.check(L.tomo_cc_surface(_p(picked.table), n, _p(cr.tot), _p(picked.sel), _p(picked.off), _p(picked.slot), _p(surf), total,
-                                 _p(tab), nz, 13, _p(area), _p(counts), _p(labels), m - 1, st), "tomo_cc_surface")
+    _lib.check(L.tomo_cc_surface(*cr.finish_head(picked), _p(surf), total, _p(tab), nz, 13, _p(area), _p(counts), _p(labels), m - 1, st),
+               "tomo_cc_surface")
     assert pipeline._download(cr.tot)[2] == 2
     assert area.eq(77.0).all() and counts.eq(77).all() and labels.eq(77).all()
 
@@ -294,9 +293,10 @@ def test_the_guards_flag_instead_of_writing_outside_a_table(dev, monkeypatch):
         cr = pipeline.ComponentRuns(vol, 6)
         picked = cr.select(0, False)
         padded = torch.full((11 * total + 64,), 77, dtype=torch.int64, device=dev)
-        _lib.check(L.tomo_cc_surface_hist(_p(cr.bits), nz, v.shape[1], v.shape[2], _p(cr.row_off), cap_runs, _p(cr.parent), _p(cr.rank),
-                                          _p(cr.tot), _p(tables), n, _p(picked.sel), _p(picked.off), _p(padded), total, st),
-                   "tomo_cc_surface_hist")
+        head = list(cr.hist_head(dataclasses.replace(picked, table=tables)))
+        assert head[5] == cr.runs
+        head[5] = cap_runs                                       # the one argument that is wrong on purpose
+        _lib.check(L.tomo_cc_surface_hist(*head, _p(padded), total, st), "tomo_cc_surface_hist")
         assert pipeline._download(cr.tot)[2] == 4
         assert padded[11 * total:].eq(77).all()
         got = padded[:11 * total].cpu().numpy().reshape(total, 11)
@@ -338,7 +338,7 @@ def test_fenced(dev, poison):
                     assert np.array_equal(whole.pair_counts, S.fold(S.counts(v).sum(axis=0)))
                     same_area(whole.surface_area_mm2, S.counts(v), d, 13, "fenced whole")
             fz.check()
-            assert fz.ran("component_surface") >= 2 * 2 * 4 and fz.ran("surface_area") >= 2 * 2
+            assert fz.ran("_rows") >= 2 * 2 * 4 and fz.ran("surface_area") >= 2 * 2
     try:
         once(poison)
     except AssertionError as e:

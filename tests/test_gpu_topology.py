@@ -258,5 +258,5 @@ def test_fenced(dev, poison, conn):
                 same(pipeline.component_topology(vol, conn, 0, True), P.selected(sizes, 0, True).astype(np.int64) + 1, sizes, tab,
                      "fenced largest")
                 assert pipeline.euler_number(vol, conn) == int(tab[:, 0].sum())
-        assert fz.ran("topology") >= 3 * 3 * 3 and fz.ran("select") >= 3 * 2 * 4 and fz.ran("component_topology") >= 3 * 2 * 1 and fz.ran("euler_number") == 3
+        assert fz.ran("topology") >= 3 * 3 * 3 and fz.ran("select") >= 3 * 2 * 4 and fz.ran("topology_rows") >= 3 * 2 * 1 and fz.ran("euler_number") == 3
     run_fenced(poison, body, "noise/%d" % conn)

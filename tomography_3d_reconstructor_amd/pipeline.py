@@ -250,9 +250,46 @@ SURFACE_COUNTERS = 11        # uint64 per component and slice: x, y, xy, then z,
 SURFACE_CLASSES = 7          # direction classes: x, y, xy, z, xz, yz, xyz
 
 
+def _check_connectivity(connectivity) -> int:
+    if connectivity not in CONNECTIVITIES:
+        raise ValueError("connectivity must be 6 or 26")
+    return int(connectivity)
+
+
+@dataclass(frozen=True)
+class _Measurement:
+    """What tells one per-component measurement from the next in ComponentRuns._rows: a histogram per slice of every selected
+    component's box, then one thread per component.  A measurement without a histogram (topology) fills in name and results."""
+    name: str                    # the public function, in the error texts
+    results: tuple               # (dtype, trailing shape) per result tensor of m rows, in the order the finishing entry point takes them
+    columns: object = None       # the columns of the measurement table that ride along in the download, in front of the labels
+    words: int = 0               # uint64 per histogram entry
+    what: str = ""               # those entries in the words of the budget error
+    hist: str = ""               # the histogram entry point ...
+    counter: str = ""            # ... and its COUNTERS key
+    finish: str = ""             # the finishing entry point
+    tables: int = 1              # the host table is that many tables of equal length, handed over one pointer each
+
+    def empty(self):
+        """The download of no selected component: zero-row host arrays of the declared dtypes and shapes, in its order."""
+        ride = [] if self.columns is None else [np.zeros((0, TABLE_COLUMNS), dtype=np.int64)[:, self.columns], np.zeros(0, dtype=np.int64)]
+        return ride + [torch.zeros((0, *shape), dtype=dtype).numpy() for dtype, shape in self.results]
+
+
+_PROPERTIES = _Measurement("component_properties", ((torch.float64, (2,)),), slice(None), 1, "voxels-per-slice counters",
+                           "tomo_cc_zhist", "components_zhist", "tomo_cc_zsums", 2)
+_MOMENTS = _Measurement("component_moments", ((torch.float64, (MOMENT_COLUMNS,)),), 0, MOMENT_SUMS, "moment sums per slice",
+                        "tomo_cc_moment_hist", "components_moments", "tomo_cc_moments", 2)
+_SURFACE = _Measurement("component_surface", ((torch.float64, ()), (torch.int64, (SURFACE_CLASSES,))), 0, SURFACE_COUNTERS,
+                        "surface counters per slice", "tomo_cc_surface_hist", "components_surface", "tomo_cc_surface")
+_TOPOLOGY = _Measurement("component_topology", ((torch.int64, (2 + TOPOLOGY_COLUMNS,)),))
+
+
 @dataclass
 class ComponentSelection:
-    """ComponentRuns.select's answer: device tensors over the n components, and the two counts read from the device."""
+    """ComponentRuns.select's answer: device tensors over the n components, and the two counts read from the device.  The
+    ComponentRuns that made it owns it: its counter block holds total and m for the finishing kernels, so it is good until
+    that object selects under another rule -- and the measuring methods take the rule, never one of these."""
     table: torch.Tensor          # int64 (n, 10): the measurement table the rule was applied to (ComponentRuns.table)
     sel: torch.Tensor            # uint8 (n,): 1 where the component is selected
     off: torch.Tensor            # int64 (n + 1,): where the per-slice entries of a component start, one per slice of its box
@@ -264,14 +301,15 @@ class ComponentSelection:
 class ComponentRuns:
     """The run tables of one BitVolume under one connectivity: scipy.ndimage.label's components, held per X-RUN (a maximal
     run of set bits in a row) and never per voxel.  Two host reads: the number of runs (it sizes the tables) and the
-    counters after the labelling.  n = components; labels() / sizes() / keep() read the tables."""
+    counters after the labelling.  n = components; labels() / sizes() / keep() read the tables.
+    One object serves every per-component measurement of its volume: properties(), moments(), topology_rows() and surface()
+    share the labelling, the measurement table and ONE selection, which the object owns (select)."""
 
     def __init__(self, vol: BitVolume, connectivity=6):
-        if connectivity not in CONNECTIVITIES:
-            raise ValueError("connectivity must be 6 or 26")
+        connectivity = _check_connectivity(connectivity)
         nz, ny, nx = vol.shape
         L, dev, st = _lib.lib(), vol.device, _stream()
-        self.vol, self.bits, self.connectivity = vol, vol.bits.contiguous(), int(connectivity)
+        self.vol, self.bits, self.connectivity = vol, vol.bits.contiguous(), connectivity
         nrows = nz * ny
         self.tot = torch.empty(8, dtype=torch.int64, device=dev)
         self.row_off = torch.empty(nrows + 1, dtype=torch.int32, device=dev)
@@ -282,6 +320,7 @@ class ComponentRuns:
         self.n = 0
         self._table = None
         self._topology = None
+        self._rule = self._picked = None
         COUNTERS["components_label"] += 1
         if self.runs == 0:
             return
@@ -340,21 +379,41 @@ class ComponentRuns:
     def select(self, min_voxels=0, largest=False):
         """The keep rule of keep() on the measurement table: the components of at least min_voxels voxels -- largest: only the
         largest of those, the lowest label among equals -- in ascending label -> ComponentSelection, or None when there is no
-        component or none is selected.  One host read: the counters, with the guards of everything enqueued so far."""
+        component or none is selected.  One host read: the counters, with the guards of everything enqueued so far.
+        The object keeps ONE selection: the kernel leaves its entry total and row count in the counter block, where every
+        finishing kernel reads them, so the answer (None too) is kept for as long as the normalised rule stays the one last
+        run, and replaced -- every ComponentSelection handed out before is then void -- when another rule is asked for."""
+        rule = (max(0, int(min_voxels)), bool(largest))
+        if rule == self._rule:
+            return self._picked
         table = self._measure()
         n = table.shape[0]
-        if n == 0:
-            return None
-        L, dev = _lib.lib(), self.vol.device
-        sel = torch.empty(n, dtype=torch.uint8, device=dev)
-        off = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        slot = torch.empty(n, dtype=torch.int32, device=dev)
-        blk = torch.empty(2 * L.tomo_cc_scan_blocks(n), dtype=torch.int64, device=dev)
-        _lib.check(L.tomo_cc_zhist_offsets(_p(table), n, _p(self.tot), max(0, int(min_voxels)), int(bool(largest)), _p(sel), _p(off),
-                                           _p(slot), _p(blk), _stream()), "tomo_cc_zhist_offsets")
-        self._checked()                                             # ... and the guards of the measuring pass
-        total, m = self.host[4], self.host[5]
-        return ComponentSelection(table, sel, off, slot, total, m) if m else None
+        picked = None
+        if n:
+            L, dev = _lib.lib(), self.vol.device
+            sel = torch.empty(n, dtype=torch.uint8, device=dev)
+            off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            slot = torch.empty(n, dtype=torch.int32, device=dev)
+            blk = torch.empty(2 * L.tomo_cc_scan_blocks(n), dtype=torch.int64, device=dev)
+            self._rule = None                                           # the counter block is about to change hands
+            _lib.check(L.tomo_cc_zhist_offsets(_p(table), n, _p(self.tot), rule[0], int(rule[1]), _p(sel), _p(off), _p(slot), _p(blk),
+                                               _stream()), "tomo_cc_zhist_offsets")
+            self._checked()                                             # ... and the guards of the measuring pass
+            total, m = self.host[4], self.host[5]
+            picked = ComponentSelection(table, sel, off, slot, total, m) if m else None
+        self._rule, self._picked = rule, picked
+        return picked
+
+    def hist_head(self, picked: ComponentSelection):
+        """The leading arguments of every histogram entry point (tomo_cc_zhist, tomo_cc_moment_hist, tomo_cc_surface_hist): bits,
+        geometry, run tables, tot, table, n, sel, off; the histogram and its capacity follow."""
+        return (_p(self.bits), *self.vol.shape, *self._tables(), _p(self.tot), _p(picked.table), picked.table.shape[0],
+                _p(picked.sel), _p(picked.off))
+
+    def finish_head(self, picked: ComponentSelection):
+        """The leading arguments of every finishing entry point (tomo_cc_zsums, tomo_cc_moments, tomo_cc_surface): table, n, tot,
+        sel, off, slot; the histogram and its capacity follow."""
+        return _p(picked.table), picked.table.shape[0], _p(self.tot), _p(picked.sel), _p(picked.off), _p(picked.slot)
 
     def _download_checked(self, name, *tensors):
         """The tensors on the host, downloaded together with the flag word; raises when a guard of the kernels fired."""
@@ -362,6 +421,56 @@ class ComponentRuns:
         if flags[0]:
             raise _lib.TomoError("%s: the tables do not fit the volume (flags %d)" % (name, flags[0]))
         return host
+
+    def _rows(self, spec: _Measurement, min_voxels, largest, host_table, *scalars):
+        """One measurement of the components the rule selects: spec.words uint64 per slice of every selected component's box
+        from spec.hist, then spec.finish with one thread per component -> the host arrays (table columns, labels, *results),
+        spec.empty() when nothing is selected.  host_table: the float64 table(s) the finishing kernel reads, uploaded here;
+        scalars: its arguments between nz and the result tensors."""
+        picked = self.select(min_voxels, largest)
+        if picked is None or picked.total == 0:
+            return spec.empty()
+        total, m, nbytes = picked.total, picked.m, 8 * spec.words * picked.total
+        if nbytes > COMPONENT_HIST_BUDGET and m > 1:                # read when called; one component is always granted
+            raise _lib.TomoError("%s: %d components selected, their %s take %d bytes, more than COMPONENT_HIST_BUDGET (%d): raise "
+                                 "min_voxels" % (spec.name, m, spec.what, nbytes, COMPONENT_HIST_BUDGET))
+        L, dev, st = _lib.lib(), self.vol.device, _stream()
+        hist = torch.empty(spec.words * total, dtype=torch.int64, device=dev)
+        COUNTERS[spec.counter] += 1
+        _lib.check(getattr(L, spec.hist)(*self.hist_head(picked), _p(hist), total, st), spec.hist)
+        tab = torch.from_numpy(host_table).to(dev).view(spec.tables, -1)
+        results = []
+        for dtype, shape in spec.results:
+            results.append(torch.empty((m, *shape), dtype=dtype, device=dev))
+        labels = torch.ones(m, dtype=torch.int64, device=dev)       # a valid row for the gather below even where a guard fired
+        _lib.check(getattr(L, spec.finish)(*self.finish_head(picked), _p(hist), total, *map(_p, tab), self.vol.shape[0], *scalars,
+                                           *map(_p, results), _p(labels), m, st), spec.finish)
+        ride = picked.table[:, spec.columns].index_select(0, labels - 1)
+        return self._download_checked(spec.name, ride, labels, *results)
+
+    def properties(self, tables, mm_y, mm_x, min_voxels=0, largest=False) -> "ComponentProperties":
+        """component_properties of this volume; tables: _slice_weights' (2 nz,)."""
+        return _component_properties_from(*self._rows(_PROPERTIES, min_voxels, largest, tables), float(mm_y), float(mm_x))
+
+    def moments(self, tables, mm_y, mm_x, min_voxels=0, largest=False) -> "ComponentMoments":
+        """component_moments of this volume; tables: _slice_weights' (2 nz,)."""
+        return _component_moments_from(*self._rows(_MOMENTS, min_voxels, largest, tables, float(mm_y), float(mm_x)))
+
+    def surface(self, factors, directions, min_voxels=0, largest=False) -> "ComponentSurface":
+        """component_surface of this volume; factors: surface_factors' (nz, 11) for the same directions."""
+        voxels, labels, area, counts = self._rows(_SURFACE, min_voxels, largest, factors, int(directions))
+        return _component_surface_from(voxels, labels, counts, area)
+
+    def topology_rows(self, min_voxels=0, largest=False) -> "ComponentTopology":
+        """component_topology of this volume: the rows of topology() the rule selects."""
+        topo = self.topology()
+        picked = self.select(min_voxels, largest) if topo.shape[0] else None
+        if picked is None:
+            return _component_topology_from(*_TOPOLOGY.empty())
+        rows = torch.empty((picked.m, *_TOPOLOGY.results[0][1]), dtype=torch.int64, device=self.vol.device)
+        _lib.check(_lib.lib().tomo_cc_topology_rows(_p(picked.table), _p(topo), topo.shape[0], _p(self.tot), _p(picked.sel), _p(picked.slot),
+                                                    _p(rows), picked.m, _stream()), "tomo_cc_topology_rows")
+        return _component_topology_from(*self._download_checked(_TOPOLOGY.name, rows))
 
     def topology(self) -> torch.Tensor:
         """Per component 1..n: Euler number, cavities (enclosed voids, b2) and handles (tunnels, b1 = 1 - euler + cavities) of
@@ -452,13 +561,6 @@ def _slice_weights(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x) -> np.ndarr
     return np.concatenate([(float(mm_per_pixel_x) * float(mm_per_pixel_y)) * depth, zt[1:-1]])
 
 
-def _check_hist_budget(name, what, picked: ComponentSelection, entry_bytes):
-    """The per-slice entries of more than one selected component must fit COMPONENT_HIST_BUDGET (read when called)."""
-    if entry_bytes * picked.total > COMPONENT_HIST_BUDGET and picked.m > 1:
-        raise _lib.TomoError("%s: %d components selected, their %s take %d bytes, more than COMPONENT_HIST_BUDGET (%d): raise "
-                             "min_voxels" % (name, picked.m, what, entry_bytes * picked.total, COMPONENT_HIST_BUDGET))
-
-
 @dataclass
 class ComponentProperties:
     """component_properties' answer: host arrays, one row per selected component in ascending label."""
@@ -497,30 +599,8 @@ def component_properties(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, 
     Four host reads (the run count, the counters after the labelling, the histogram's length, the results); working memory
     scales with the runs, the components and the voxels-per-slice counters of the SELECTED components (one per slice of a
     component's box; beyond COMPONENT_HIST_BUDGET bytes for more than one component: TomoError) -- never with the voxels."""
-    if connectivity not in CONNECTIVITIES:
-        raise ValueError("connectivity must be 6 or 26")
-    nz, ny, nx = vol.shape
-    tables = _slice_weights(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x)
-    mm_y, mm_x = float(mm_per_pixel_y), float(mm_per_pixel_x)
-    cr = ComponentRuns(vol, connectivity)
-    picked = cr.select(min_voxels, largest)
-    if picked is None or picked.total == 0:
-        none = np.zeros((0, TABLE_COLUMNS), dtype=np.int64)
-        return _component_properties_from(none, none[:, 0].copy(), np.zeros((0, 2)), mm_y, mm_x)
-    _check_hist_budget("component_properties", "voxels-per-slice counters", picked, 8)
-    L, dev, st = _lib.lib(), vol.device, _stream()
-    table, n, total, m = picked.table, picked.table.shape[0], picked.total, picked.m
-    hist = torch.empty(total, dtype=torch.int64, device=dev)
-    COUNTERS["components_zhist"] += 1
-    _lib.check(L.tomo_cc_zhist(_p(cr.bits), nz, ny, nx, *cr._tables(), _p(cr.tot), _p(table), n, _p(picked.sel), _p(picked.off),
-                               _p(hist), total, st), "tomo_cc_zhist")
-    tab = torch.from_numpy(tables).to(dev)
-    sums = torch.empty((m, 2), dtype=torch.float64, device=dev)
-    labels = torch.ones(m, dtype=torch.int64, device=dev)       # a valid row for the gather below even where a guard fired
-    _lib.check(L.tomo_cc_zsums(_p(table), n, _p(cr.tot), _p(picked.sel), _p(picked.off), _p(picked.slot), _p(hist), total,
-                               _p(tab[:nz]), _p(tab[nz:]), nz, _p(sums), _p(labels), m, st), "tomo_cc_zsums")
-    rows = table.index_select(0, labels - 1)
-    return _component_properties_from(*cr._download_checked("component_properties", rows, labels, sums), mm_y, mm_x)
+    tables = _slice_weights(slice_depths, vol.shape[0], mm_per_pixel_y, mm_per_pixel_x)
+    return ComponentRuns(vol, connectivity).properties(tables, mm_per_pixel_y, mm_per_pixel_x, min_voxels, largest)
 
 
 @dataclass
@@ -568,30 +648,8 @@ def component_moments(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_
     The same four host reads as component_properties; working memory scales with the runs, the components and six sums per
     slice of the box of every SELECTED component (48 bytes an entry; beyond COMPONENT_HIST_BUDGET bytes for more than one
     component: TomoError) -- never with the voxels."""
-    if connectivity not in CONNECTIVITIES:
-        raise ValueError("connectivity must be 6 or 26")
-    nz, ny, nx = vol.shape
-    tables = _slice_weights(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x)
-    mm_y, mm_x = float(mm_per_pixel_y), float(mm_per_pixel_x)
-    cr = ComponentRuns(vol, connectivity)
-    picked = cr.select(min_voxels, largest)
-    if picked is None or picked.total == 0:
-        none = np.zeros(0, dtype=np.int64)
-        return _component_moments_from(none, none.copy(), np.zeros((0, MOMENT_COLUMNS)))
-    _check_hist_budget("component_moments", "moment sums per slice", picked, 8 * MOMENT_SUMS)
-    L, dev, st = _lib.lib(), vol.device, _stream()
-    table, n, total, m = picked.table, picked.table.shape[0], picked.total, picked.m
-    mom = torch.empty(MOMENT_SUMS * total, dtype=torch.int64, device=dev)
-    COUNTERS["components_moments"] += 1
-    _lib.check(L.tomo_cc_moment_hist(_p(cr.bits), nz, ny, nx, *cr._tables(), _p(cr.tot), _p(table), n, _p(picked.sel), _p(picked.off),
-                                     _p(mom), total, st), "tomo_cc_moment_hist")
-    tab = torch.from_numpy(tables).to(dev)
-    rows = torch.empty((m, MOMENT_COLUMNS), dtype=torch.float64, device=dev)
-    labels = torch.ones(m, dtype=torch.int64, device=dev)       # a valid row for the gather below even where a guard fired
-    _lib.check(L.tomo_cc_moments(_p(table), n, _p(cr.tot), _p(picked.sel), _p(picked.off), _p(picked.slot), _p(mom), total,
-                                 _p(tab[:nz]), _p(tab[nz:]), nz, mm_y, mm_x, _p(rows), _p(labels), m, st), "tomo_cc_moments")
-    voxels = table[:, 0].index_select(0, labels - 1)
-    return _component_moments_from(*cr._download_checked("component_moments", voxels, labels, rows))
+    tables = _slice_weights(slice_depths, vol.shape[0], mm_per_pixel_y, mm_per_pixel_x)
+    return ComponentRuns(vol, connectivity).moments(tables, mm_per_pixel_y, mm_per_pixel_x, min_voxels, largest)
 
 
 # ----------------------------------------------------------------------------- Euler number, cavities and handles
@@ -619,12 +677,11 @@ def euler_number(vol: BitVolume, connectivity=6) -> int:
     closed unit cubes of the set voxels; under 6, voxels - face-adjacent pairs + full 2 x 2 blocks - full 2 x 2 x 2 blocks
     (the dual complex).  Everything outside the stack is background.  It equals components - handles + cavities
     (volume_topology) without any labelling: one pass over the rows, one host read."""
-    if connectivity not in CONNECTIVITIES:
-        raise ValueError("connectivity must be 6 or 26")
+    connectivity = _check_connectivity(connectivity)
     nz, ny, nx = vol.shape
     chi = torch.empty(1, dtype=torch.int64, device=vol.device)
     COUNTERS["components_euler"] += 1
-    _lib.check(_lib.lib().tomo_cc_euler(_p(vol.bits.contiguous()), nz, ny, nx, int(connectivity), None, 0, None, None, None, _p(chi), 1,
+    _lib.check(_lib.lib().tomo_cc_euler(_p(vol.bits.contiguous()), nz, ny, nx, connectivity, None, 0, None, None, None, _p(chi), 1,
                                         _stream()), "tomo_cc_euler")
     return int(chi.item())
 
@@ -637,17 +694,7 @@ def component_topology(vol: BitVolume, connectivity=6, min_voxels=0, largest=Fal
     a face of the stack is no cavity; an island floating in a void does not split it, and the island's own voids are the
     island's.  There are no slice depths here: topology does not depend on them.  Working memory scales with the rows, the
     runs of the volume and of its complement, and the components -- never with the voxels."""
-    if connectivity not in CONNECTIVITIES:
-        raise ValueError("connectivity must be 6 or 26")
-    cr = ComponentRuns(vol, connectivity)
-    topo = cr.topology()
-    picked = cr.select(min_voxels, largest) if topo.shape[0] else None
-    if picked is None:
-        return _component_topology_from(np.zeros((0, 2 + TOPOLOGY_COLUMNS), dtype=np.int64))
-    rows = torch.empty((picked.m, 2 + TOPOLOGY_COLUMNS), dtype=torch.int64, device=vol.device)
-    _lib.check(_lib.lib().tomo_cc_topology_rows(_p(picked.table), _p(topo), topo.shape[0], _p(cr.tot), _p(picked.sel), _p(picked.slot),
-                                                _p(rows), picked.m, _stream()), "tomo_cc_topology_rows")
-    return _component_topology_from(*cr._download_checked("component_topology", rows))
+    return ComponentRuns(vol, connectivity).topology_rows(min_voxels, largest)
 
 
 def volume_topology(vol: BitVolume, connectivity=6) -> dict:
@@ -811,31 +858,8 @@ def component_surface(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_
     counts of all components add up to surface_area's.  The same four host reads as component_properties; working memory
     scales with the runs, the components and eleven counters per slice of the box of every SELECTED component (88 bytes an
     entry; beyond COMPONENT_HIST_BUDGET bytes for more than one component: TomoError) -- never with the voxels."""
-    if connectivity not in CONNECTIVITIES:
-        raise ValueError("connectivity must be 6 or 26")
-    nz, ny, nx = vol.shape
-    F = surface_factors(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x, directions)
-    cr = ComponentRuns(vol, connectivity)
-    picked = cr.select(min_voxels, largest)
-    if picked is None or picked.total == 0:
-        none = np.zeros(0, dtype=np.int64)
-        return _component_surface_from(none, none.copy(), np.zeros((0, SURFACE_CLASSES), dtype=np.int64), np.zeros(0))
-    _check_hist_budget("component_surface", "surface counters per slice", picked, 8 * SURFACE_COUNTERS)
-    L, dev, st = _lib.lib(), vol.device, _stream()
-    table, n, total, m = picked.table, picked.table.shape[0], picked.total, picked.m
-    surf = torch.empty(SURFACE_COUNTERS * total, dtype=torch.int64, device=dev)
-    COUNTERS["components_surface"] += 1
-    _lib.check(L.tomo_cc_surface_hist(_p(cr.bits), nz, ny, nx, *cr._tables(), _p(cr.tot), _p(table), n, _p(picked.sel), _p(picked.off),
-                                      _p(surf), total, st), "tomo_cc_surface_hist")
-    tab = torch.from_numpy(F).to(dev)
-    area = torch.empty(m, dtype=torch.float64, device=dev)
-    counts = torch.empty((m, SURFACE_CLASSES), dtype=torch.int64, device=dev)
-    labels = torch.ones(m, dtype=torch.int64, device=dev)       # a valid row for the gather below even where a guard fired
-    _lib.check(L.tomo_cc_surface(_p(table), n, _p(cr.tot), _p(picked.sel), _p(picked.off), _p(picked.slot), _p(surf), total,
-                                 _p(tab), nz, int(directions), _p(area), _p(counts), _p(labels), m, st),
-               "tomo_cc_surface")
-    voxels = table[:, 0].index_select(0, labels - 1)
-    return _component_surface_from(*cr._download_checked("component_surface", voxels, labels, counts, area))
+    F = surface_factors(slice_depths, vol.shape[0], mm_per_pixel_y, mm_per_pixel_x, directions)
+    return ComponentRuns(vol, connectivity).surface(F, directions, min_voxels, largest)
 
 
 # ----------------------------------------------------------------------------- Euclidean distance in millimetres

@@ -157,42 +157,42 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
     order): 'center_of_mass_mm', 'covariance_mm2' (3 x 3 nested tuples), 'principal_variances_mm2' (descending),
     'principal_axes' (3 rows, unit vectors in that order) and 'ellipsoid_axes_mm' (the full axes of the solid ellipsoid with
     the same second moments).  topology=True: every dict also carries 'euler_number', 'cavities' (enclosed voids; one that
-    reaches a face of the stack is none) and 'handles' (tunnels) of the component as Python ints
-    (pipeline.component_topology: a ball reads 1, 0, 0, a hollow shell 2, 1, 0, a ring 0, 0, 1; the background has the
-    complementary connectivity).  surface=True: every dict also carries 'surface_area_mm2' -- the discretised Crofton formula
-    on the component's voxels (pipeline.component_surface; surface_directions = 13 or 3; a voxel of another component is not
-    background) -- and 'sphericity' = pi^(1/3) (6 voxel_volume_mm3)^(2/3) / surface_area_mm2 as Python floats.
-    With the defaults nothing more is launched and the dicts are as before.  voxel_data: the
-    bool (nz, ny, nx) array the other calculations take; anything else is a TypeError -- there is no host path for this one."""
+    reaches a face of the stack is none) and 'handles' (tunnels) of the component as Python ints (pipeline.component_topology:
+    a ball reads 1, 0, 0, a hollow shell 2, 1, 0, a ring 0, 0, 1; the background has the complementary connectivity).
+    surface=True: every dict also carries 'surface_area_mm2' -- the discretised Crofton formula on the component's voxels
+    (pipeline.component_surface; surface_directions = 13 or 3; a voxel of another component is not background) -- and
+    'sphericity' = pi^(1/3) (6 voxel_volume_mm3)^(2/3) / surface_area_mm2 as Python floats.  Whatever the flags, the volume is
+    uploaded and labelled ONCE: one pipeline.ComponentRuns serves all four measurements and owns the one selection their rows
+    come from.  Arguments are checked before the first launch.  voxel_data: a bool (nz, ny, nx) array, else a TypeError."""
     if not _on_device(voxel_data):
         raise TypeError("component_properties needs a bool (nz, ny, nx) array")
     depths = np.asarray(slice_depths, dtype=np.float64).reshape(-1)
-    p = pipeline.component_properties(to_device_volume(voxel_data), depths, mm_per_pixel_y, mm_per_pixel_x, connectivity,
-                                      min_voxels, largest)
-    out = []
-    for i in range(len(p)):
-        box = box_variable_depth(tuple(p.index_box[i]), mm_per_pixel_x, mm_per_pixel_y, depths)
-        out.append({'label': int(p.labels[i]), 'voxels': int(p.voxels[i]), 'voxel_volume_mm3': float(p.volume_mm3[i]),
-                    'bounding_box': {axis: box[axis] for axis in ('x', 'y', 'z')}, 'dimensions': box['dimensions'],
-                    'centroid_mm': tuple(float(v) for v in p.centroid_mm[i]),
-                    'centroid_index': tuple(float(v) for v in p.centroid_index[i])})
-    if shape:
-        q = pipeline.component_moments(to_device_volume(voxel_data), depths, mm_per_pixel_y, mm_per_pixel_x, connectivity,
-                                       min_voxels, largest)
-        for i, d in enumerate(out):                              # the same rule on the same volume: the same rows
+    rule = (min_voxels, largest)
+    pipeline._check_connectivity(connectivity)
+    tables = pipeline._slice_weights(depths, len(voxel_data), mm_per_pixel_y, mm_per_pixel_x)
+    factors = pipeline.surface_factors(depths, len(voxel_data), mm_per_pixel_y, mm_per_pixel_x, surface_directions) if surface else None
+    runs = pipeline.ComponentRuns(to_device_volume(voxel_data), connectivity)
+    if runs.select(*rule) is None:
+        return []
+    p = runs.properties(tables, mm_per_pixel_y, mm_per_pixel_x, *rule)
+    boxes = [box_variable_depth(tuple(b), mm_per_pixel_x, mm_per_pixel_y, depths) for b in p.index_box]
+    out = [{'label': int(p.labels[i]), 'voxels': int(p.voxels[i]), 'voxel_volume_mm3': float(p.volume_mm3[i]),
+            'bounding_box': {axis: box[axis] for axis in ('x', 'y', 'z')}, 'dimensions': box['dimensions'],
+            'centroid_mm': tuple(float(v) for v in p.centroid_mm[i]),
+            'centroid_index': tuple(float(v) for v in p.centroid_index[i])} for i, box in enumerate(boxes)]
+    q = runs.moments(tables, mm_per_pixel_y, mm_per_pixel_x, *rule) if shape else None
+    t = runs.topology_rows(*rule) if topology else None
+    a = runs.surface(factors, surface_directions, *rule) if surface else None
+    for i, d in enumerate(out):                                  # row i of every answer: they come from the one selection of `runs`
+        if shape:
             d['center_of_mass_mm'] = tuple(float(v) for v in q.center_of_mass_mm[i])
             d['covariance_mm2'] = tuple(tuple(float(v) for v in row) for row in q.covariance_mm2[i])
             d['principal_variances_mm2'] = tuple(float(v) for v in q.principal_variances_mm2[i])
             d['principal_axes'] = tuple(tuple(float(v) for v in row) for row in q.principal_axes[i])
             d['ellipsoid_axes_mm'] = tuple(float(v) for v in q.ellipsoid_axes_mm[i])
-    if topology:
-        t = pipeline.component_topology(to_device_volume(voxel_data), connectivity, min_voxels, largest)
-        for i, d in enumerate(out):                              # the same rule on the same volume: the same rows
+        if topology:
             d['euler_number'], d['cavities'], d['handles'] = int(t.euler[i]), int(t.cavities[i]), int(t.handles[i])
-    if surface:
-        a = pipeline.component_surface(to_device_volume(voxel_data), depths, mm_per_pixel_y, mm_per_pixel_x, connectivity,
-                                       min_voxels, largest, surface_directions)
-        for i, d in enumerate(out):                              # the same rule on the same volume: the same rows
+        if surface:
             d['surface_area_mm2'] = float(a.surface_area_mm2[i])
             d['sphericity'] = sphericity(d['voxel_volume_mm3'], d['surface_area_mm2'])
     return out

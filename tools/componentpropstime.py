@@ -58,16 +58,16 @@ def device_steps(vol, depths, warmup, reps, moments=False):
     hist = torch.empty(total, dtype=torch.int64, device=dev)
     sums = torch.empty((m, 2), dtype=torch.float64, device=dev)
     labels = torch.empty(m, dtype=torch.int64, device=dev)
-    steps["zhist"] = lambda: L.tomo_cc_zhist(*geo, *cr._tables(), _p(cr.tot), _p(table), n, _p(sel), _p(off), _p(hist), total, st)
-    steps["zsums"] = lambda: L.tomo_cc_zsums(_p(table), n, _p(cr.tot), _p(sel), _p(off), _p(slot), _p(hist), total, _p(tab[:nz]),
-                                             _p(tab[nz:]), nz, _p(sums), _p(labels), m, st)
+    picked = pipeline.ComponentSelection(table, sel, off, slot, total, m)
+    hist_head, finish_head = cr.hist_head(picked), cr.finish_head(picked)
+    steps["zhist"] = lambda: L.tomo_cc_zhist(*hist_head, _p(hist), total, st)
+    steps["zsums"] = lambda: L.tomo_cc_zsums(*finish_head, _p(hist), total, _p(tab[:nz]), _p(tab[nz:]), nz, _p(sums), _p(labels), m, st)
     if moments:
         mom = torch.empty(pipeline.MOMENT_SUMS * total, dtype=torch.int64, device=dev)
         rows = torch.empty((m, pipeline.MOMENT_COLUMNS), dtype=torch.float64, device=dev)
-        steps["moment_hist"] = lambda: L.tomo_cc_moment_hist(*geo, *cr._tables(), _p(cr.tot), _p(table), n, _p(sel), _p(off), _p(mom),
-                                                             total, st)
-        steps["moments"] = lambda: L.tomo_cc_moments(_p(table), n, _p(cr.tot), _p(sel), _p(off), _p(slot), _p(mom), total, _p(tab[:nz]),
-                                                     _p(tab[nz:]), nz, 0.45, 0.7, _p(rows), _p(labels), m, st)
+        steps["moment_hist"] = lambda: L.tomo_cc_moment_hist(*hist_head, _p(mom), total, st)
+        steps["moments"] = lambda: L.tomo_cc_moments(*finish_head, _p(mom), total, _p(tab[:nz]), _p(tab[nz:]), nz, 0.45, 0.7, _p(rows),
+                                                     _p(labels), m, st)
     out = {"runs": cr.runs, "components": n, "selected": m, "hist_entries": total}
     for name, fn in steps.items():
         for _ in range(warmup):

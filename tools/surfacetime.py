@@ -49,9 +49,9 @@ def device_steps(vol, conn, warmup, reps):
     L, dev, st = _lib.lib(), vol.device, _stream()
     cr = pipeline.ComponentRuns(vol, conn)
     picked = cr.select(0, False)
-    table, n, total, m = picked.table, picked.table.shape[0], picked.total, picked.m
+    n, total, m = picked.table.shape[0], picked.total, picked.m
     geo = (_p(cr.bits), nz, ny, nx)
-    tables = (*cr._tables(), _p(cr.tot), _p(table), n, _p(picked.sel), _p(picked.off))
+    hist_head, finish_head = cr.hist_head(picked), cr.finish_head(picked)
     whole = torch.empty(pipeline.SURFACE_COUNTERS * nz, dtype=torch.int64, device=dev)
     surf = torch.empty(pipeline.SURFACE_COUNTERS * total, dtype=torch.int64, device=dev)
     mom = torch.empty(pipeline.MOMENT_SUMS * total, dtype=torch.int64, device=dev)
@@ -62,11 +62,10 @@ def device_steps(vol, conn, warmup, reps):
     steps = {
         "surface_hist_whole_volume": lambda: _lib.check(L.tomo_cc_surface_hist(*geo, None, 0, None, None, None, None, 0, None, None,
                                                                                _p(whole), nz, st), "tomo_cc_surface_hist"),
-        "surface_hist_per_component": lambda: _lib.check(L.tomo_cc_surface_hist(*geo, *tables, _p(surf), total, st), "tomo_cc_surface_hist"),
-        "moment_hist": lambda: _lib.check(L.tomo_cc_moment_hist(*geo, *tables, _p(mom), total, st), "tomo_cc_moment_hist"),
-        "surface_finish": lambda: _lib.check(L.tomo_cc_surface(_p(table), n, _p(cr.tot), _p(picked.sel), _p(picked.off), _p(picked.slot),
-                                                               _p(surf), total, _p(tab), nz, 13, _p(area), _p(counts), _p(labels), m, st),
-                                             "tomo_cc_surface"),
+        "surface_hist_per_component": lambda: _lib.check(L.tomo_cc_surface_hist(*hist_head, _p(surf), total, st), "tomo_cc_surface_hist"),
+        "moment_hist": lambda: _lib.check(L.tomo_cc_moment_hist(*hist_head, _p(mom), total, st), "tomo_cc_moment_hist"),
+        "surface_finish": lambda: _lib.check(L.tomo_cc_surface(*finish_head, _p(surf), total, _p(tab), nz, 13, _p(area), _p(counts),
+                                                               _p(labels), m, st), "tomo_cc_surface"),
     }
     out = {"runs": cr.runs, "components": n, "slice_entries": total, "surface_hist_bytes": 8 * pipeline.SURFACE_COUNTERS * total}
     for name, fn in steps.items():
