@@ -203,6 +203,12 @@ int tomo_cc_filter(const uint64_t *bits, int nz, int ny, int nx, const uint32_t 
  *                          which sizes `hist`; slot uint32[cap], the first n = selected components in front of c; tot[5] =
  *                          selected components.  cap = rows of the table >= n (else bit 1 of tot[2], nothing is written);
  *                          blk: 2 * tomo_cc_scan_blocks(cap) words
+ *   tomo_cc_select         tomo_cc_zhist_offsets with the whole keep rule: min_voxels <= voxels <= max_voxels (INT64_MAX: no upper
+ *                          bound) and, with enclosed != 0, only a component whose inclusive index box touches no face of the
+ *                          stack nz, ny, nx (zmin > 0, zmax < nz - 1, likewise y and x; read only then): on the tables of a
+ *                          complement, its cavities.  The same outputs, counter words and scratch; tomo_cc_zhist_offsets is this
+ *                          call without an upper bound and without the face test.  largest with enclosed or a finite max_voxels:
+ *                          TOMO_E_ARG, like max_voxels < 0
  *   tomo_cc_zhist          hist uint64[hist_cap], zeroed here: hist[off[c] + z - zmin[c]] = voxels of selected component c + 1
  *                          in slice z.  tot[4] > hist_cap: bit 1 of tot[2] and nothing is added; a slice outside the
  *                          component's box (the bits changed): bit 2
@@ -217,6 +223,8 @@ int tomo_cc_measure(const uint64_t *bits, int nz, int ny, int nx, const uint32_t
                     const uint32_t *rank, unsigned long long *tot, int64_t *table, int64_t cap, void *stream);
 int tomo_cc_zhist_offsets(const int64_t *table, int64_t cap, unsigned long long *tot, int64_t min_voxels, int largest, uint8_t *sel,
                           uint64_t *off, uint32_t *slot, uint64_t *blk, void *stream);
+int tomo_cc_select(const int64_t *table, int64_t cap, unsigned long long *tot, int64_t min_voxels, int64_t max_voxels, int largest,
+                   int enclosed, int nz, int ny, int nx, uint8_t *sel, uint64_t *off, uint32_t *slot, uint64_t *blk, void *stream);
 int tomo_cc_zhist(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
                   const uint32_t *rank, unsigned long long *tot, const int64_t *table, int64_t cap, const uint8_t *sel,
                   const uint64_t *off, uint64_t *hist, int64_t hist_cap, void *stream);
@@ -270,6 +278,11 @@ int tomo_cc_moments(const int64_t *table, int64_t cap, unsigned long long *tot, 
  *                          cavity's first run.  topo int64[cap][3], every row written: (euler[c], cavities, handles) for c < n,
  *                          zeros behind.  A table that does not fit its counters: bit 1 of tot[2]; a left neighbour that is clear
  *                          or outside the tables: bit 2.  bg_tot is only read
+ *   tomo_cc_cavity_owners  the argument head of tomo_cc_cavities (through bg_cap), the same owner search: owner int64[bg_cap], every
+ *                          entry written, entry c = the label (1-based) of the component that owns background component c + 1
+ *                          where that is a cavity, 0 where it reaches a face and behind the bg_tot[1] components.  An island
+ *                          floating in a void does not own it.  The guards are tomo_cc_cavities', in tot[2].  bg_cap_runs = 0:
+ *                          nothing is written (owner may be NULL)
  *   tomo_cc_topology_rows  out int64[cap_sel][5] row slot[c] = (c + 1, voxels, euler, cavities, handles) for the components
  *                          tomo_cc_zhist_offsets selected (sel, slot, tot[5]); tot[5] > cap_sel: bit 1 of tot[2], nothing is written
  * TOMO_E_ARG for a null pointer, a non-positive size or a connectivity other than 6 / 26; TOMO_E_SIZE from 2^31 words, runs or
@@ -281,6 +294,10 @@ int tomo_cc_cavities(const uint64_t *bits, int nz, int ny, int nx, const uint32_
                      const uint32_t *rank, unsigned long long *tot, int64_t cap, const uint64_t *bg_bits, const uint32_t *bg_row_off,
                      int64_t bg_cap_runs, const uint32_t *bg_parent, const uint32_t *bg_rank, const unsigned long long *bg_tot,
                      const int64_t *bg_table, int64_t bg_cap, const int64_t *euler, int64_t *topo, void *stream);
+int tomo_cc_cavity_owners(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                          const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, int64_t cap, const uint64_t *bg_bits,
+                          const uint32_t *bg_row_off, int64_t bg_cap_runs, const uint32_t *bg_parent, const uint32_t *bg_rank,
+                          const unsigned long long *bg_tot, const int64_t *bg_table, int64_t bg_cap, int64_t *owner, void *stream);
 int tomo_cc_topology_rows(const int64_t *table, const int64_t *topo, int64_t cap, unsigned long long *tot, const uint8_t *sel,
                           const uint32_t *slot, int64_t *out, int64_t cap_sel, void *stream);
 /* Surface area per component by the discretised Crofton formula (Ohser & Muecklich; no counterpart in the reference, whose
@@ -345,6 +362,10 @@ int tomo_cc_surface(const int64_t *table, int64_t cap, unsigned long long *tot, 
  *                             on the global sizes (largest: the label goes to tot[3]) and / or label int32[n_local] = the global
  *                             label; either may be NULL, not both
  *   tomo_cc_filter_map        tomo_cc_filter with `keep` in place of the sizes      (tot: the slab's own counters)
+ *   tomo_cc_fill_map          tomo_cc_filter_map ORed with a second volume: out (!= bits, != solid) = (solid ? solid : 0) | the bits
+ *                             of the runs of `bits` whose component c has keep[c] != 0.  With the tables of a complement and
+ *                             keep = the selection of its cavities (tomo_cc_select, enclosed), solid = the volume fills them,
+ *                             solid = NULL extracts them.  One pass, one thread per word; tail bits of out are zero
  *   tomo_cc_expand_map        tomo_cc_expand with `label` in place of the numbering */
 int tomo_cc_slice_components(int nz, int ny, int z, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
                              const uint32_t *rank, unsigned long long *tot, int32_t *out, int64_t cap_out, void *stream);
@@ -360,6 +381,9 @@ int tomo_cc_local_maps(const uint32_t *table, const uint32_t *num, const int64_t
 int tomo_cc_filter_map(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
                        const uint32_t *rank, unsigned long long *tot, const uint8_t *keep, int64_t n_local, uint64_t *out,
                        void *stream);
+int tomo_cc_fill_map(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
+                     const uint32_t *rank, unsigned long long *tot, const uint8_t *keep, int64_t n_local, const uint64_t *solid,
+                     uint64_t *out, void *stream);
 int tomo_cc_expand_map(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
                        const uint32_t *rank, unsigned long long *tot, const int32_t *label, int64_t n_local, int32_t *labels,
                        void *stream);

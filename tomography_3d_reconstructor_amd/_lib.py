@@ -57,6 +57,7 @@ SIGNATURES = {
     "tomo_cc_filter": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i, _c_p, _c_p]),
     "tomo_cc_measure": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p]),
     "tomo_cc_zhist_offsets": (_c_i, [_c_p, _c_i64, _c_p, _c_i64, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p]),
+    "tomo_cc_select": (_c_i, [_c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i, _c_i, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p]),
     "tomo_cc_zhist": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p]),
     "tomo_cc_zsums": (_c_i, [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_i, _c_p, _c_p, _c_i64, _c_p]),
     "tomo_cc_moment_hist": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64,
@@ -67,6 +68,8 @@ SIGNATURES = {
     "tomo_cc_complement": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_p]),
     "tomo_cc_cavities": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p,
                                 _c_i64, _c_p, _c_p, _c_p]),
+    "tomo_cc_cavity_owners": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p,
+                                     _c_p, _c_i64, _c_p, _c_p]),
     "tomo_cc_topology_rows": (_c_i, [_c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p]),
     "tomo_cc_surface_hist": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64,
                                     _c_p]),
@@ -78,6 +81,7 @@ SIGNATURES = {
     "tomo_cc_merge_tables": (_c_i, [_c_p, _c_i, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
     "tomo_cc_local_maps": (_c_i, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i, _c_p, _c_p, _c_p]),
     "tomo_cc_filter_map": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p]),
+    "tomo_cc_fill_map": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p]),
     "tomo_cc_expand_map": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p]),
     "tomo_edt_workspace_bytes": (_c_i64, [_c_i, _c_i, _c_i, _c_i64]),
     "tomo_edt_chunk_columns": (_c_i64, [_c_i, _c_i, _c_i, _c_i64]),

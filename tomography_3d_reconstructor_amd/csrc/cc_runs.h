@@ -4,7 +4,7 @@
 //
 // tot (device uint64[8]): [0] runs  [1] components  [2] flags (1: 2^31 runs or more, 2: more runs than the caller's buffers
 // hold, 4: a run id outside the tables -- the bits changed between the calls)  [3] label tomo_cc_filter(largest) kept (0: none)
-// [4] counters of the slice histogram  [5] components tomo_cc_zhist_offsets selected.
+// [4] counters of the slice histogram  [5] components tomo_cc_select (tomo_cc_zhist_offsets) selected.
 #pragma once
 #include "tomo_common.h"
 

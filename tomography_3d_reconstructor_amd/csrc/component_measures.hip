@@ -120,25 +120,40 @@ TOMO_API int tomo_cc_measure(const uint64_t *bits, int nz, int ny, int nx, const
 // exclusive scan of the segment lengths, 0-length for the others, in 64 bits (2^31 components of up to 2^31 slices), and
 // slot = the exclusive scan of the selection = the row of a selected component in the compacted results.
 // tot[4] = all counters, tot[5] = selected components.
-__device__ static inline bool cc_selected(const u64 *__restrict__ table, const u64 *__restrict__ tot, int64_t c, u64 min_voxels,
-                                          int largest)
+// The keep rule, in full: the size window min_voxels <= voxels <= max_voxels on column 0 -- largest: only the label in tot[3]
+// -- and, with enclosed, only a component whose box touches no face of the stack (cc_enclosed): a cavity, where the table is
+// the complement's.  Both scan kernels apply it through cc_selected, nothing else does.
+struct CcRule {
+    u64 min_voxels, max_voxels;
+    int largest, enclosed;
+    u64 nz, ny, nx;
+};
+
+// the inclusive index box of a row of the measurement table touches no face of the stack
+__device__ static inline bool cc_enclosed(const u64 *__restrict__ box, u64 nz, u64 ny, u64 nx)
 {
-    return largest ? (u64)c + 1 == tot[3] : table[c * CC_COLS] >= min_voxels;
+    return !(box[1] == 0 || box[2] + 1 >= nz || box[3] == 0 || box[4] + 1 >= ny || box[5] == 0 || box[6] + 1 >= nx);
+}
+
+__device__ static inline bool cc_selected(const u64 *__restrict__ table, const u64 *__restrict__ tot, int64_t c, const CcRule &r)
+{
+    if (r.largest) return (u64)c + 1 == tot[3];
+    const u64 *row = table + c * CC_COLS;
+    return row[0] >= r.min_voxels && row[0] <= r.max_voxels && (!r.enclosed || cc_enclosed(row, r.nz, r.ny, r.nx));
 }
 
 // length of the segment of component c (0: not selected, or a box that is none)
-__device__ static inline u64 cc_zspan(const u64 *__restrict__ table, const u64 *__restrict__ tot, int64_t c, u64 min_voxels,
-                                      int largest, bool *sel)
+__device__ static inline u64 cc_zspan(const u64 *__restrict__ table, const u64 *__restrict__ tot, int64_t c, const CcRule &r, bool *sel)
 {
     const u64 z0 = table[c * CC_COLS + 1], z1 = table[c * CC_COLS + 2];
-    *sel = cc_selected(table, tot, c, min_voxels, largest);
+    *sel = cc_selected(table, tot, c, r);
     return *sel && z1 >= z0 ? z1 - z0 + 1 : 0;
 }
 
 
 // per tile of CC_SCAN_TILE components: blk[b] = its counters, blk[nblk + b] = its selected components; sel[c] on the way
 __global__ __launch_bounds__(CC_THREADS) void cc_zspan_blocksum_kernel(const u64 *__restrict__ table, const u64 *__restrict__ tot,
-                                                                       int64_t cap, u64 min_voxels, int largest,
+                                                                       int64_t cap, CcRule rule,
                                                                        uint8_t *__restrict__ sel, u64 *__restrict__ blk, int64_t nblk,
                                                                        u64 *flags)
 {
@@ -151,7 +166,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_zspan_blocksum_kernel(const u64
     for (int j = 0; j < 4; j++) {
         if (i0 + j < n) {
             bool s;
-            span += cc_zspan(table, tot, i0 + j, min_voxels, largest, &s);
+            span += cc_zspan(table, tot, i0 + j, rule, &s);
             cnt += s ? 1 : 0;
             sel[i0 + j] = s ? 1 : 0;
         }
@@ -171,7 +186,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_zspan_blocksum_kernel(const u64
 
 // off[c], slot[c] for every c < n and off[n] = all counters (written by the thread that holds component n - 1)
 __global__ __launch_bounds__(CC_THREADS) void cc_zspan_apply_kernel(const u64 *__restrict__ table, const u64 *__restrict__ tot,
-                                                                    int64_t cap, u64 min_voxels, int largest,
+                                                                    int64_t cap, CcRule rule,
                                                                     const u64 *__restrict__ blk, int64_t nblk, u64 *__restrict__ off,
                                                                     u32 *__restrict__ slot)
 {
@@ -183,7 +198,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_zspan_apply_kernel(const u64 *_
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         bool s = false;
-        x[j] = i0 + j < n ? cc_zspan(table, tot, i0 + j, min_voxels, largest, &s) : 0;
+        x[j] = i0 + j < n ? cc_zspan(table, tot, i0 + j, rule, &s) : 0;
         k[j] = s ? 1 : 0;
         span += x[j];
         cnt += k[j];
@@ -212,25 +227,36 @@ __global__ __launch_bounds__(CC_THREADS) void cc_zspan_apply_kernel(const u64 *_
     }
 }
 
-TOMO_API int tomo_cc_zhist_offsets(const int64_t *table, int64_t cap, unsigned long long *tot, int64_t min_voxels, int largest,
-                                   uint8_t *sel, uint64_t *off, uint32_t *slot, uint64_t *blk, void *stream)
+TOMO_API int tomo_cc_select(const int64_t *table, int64_t cap, unsigned long long *tot, int64_t min_voxels, int64_t max_voxels,
+                            int largest, int enclosed, int nz, int ny, int nx, uint8_t *sel, uint64_t *off, uint32_t *slot, uint64_t *blk,
+                            void *stream)
 {
-    if (!table || !tot || !sel || !off || !slot || !blk || cap <= 0 || min_voxels < 0) return TOMO_E_ARG;
+    if (!table || !tot || !sel || !off || !slot || !blk || cap <= 0 || min_voxels < 0 || max_voxels < 0) return TOMO_E_ARG;
+    if (largest && (enclosed || max_voxels != (int64_t)0x7fffffffffffffffll)) return TOMO_E_ARG;
+    if (enclosed && (nz <= 0 || ny <= 0 || nx <= 0)) return TOMO_E_ARG;
     if (cap >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
     hipStream_t st = (hipStream_t)stream;
     const u64 *t = (const u64 *)table;
     u64 *tt = (u64 *)tot;
     const int64_t nblk = ceil_div64(cap, CC_SCAN_TILE);
+    const CcRule rule = {(u64)min_voxels, (u64)max_voxels, largest ? 1 : 0, enclosed ? 1 : 0, (u64)nz, (u64)ny, (u64)nx};
     if (largest)                                            // no run table is read here: only the count of components is capped
         hipLaunchKernelGGL(cc_largest_kernel<CC_COLS>, dim3(1), dim3(1024), 0, st, (const unsigned long long *)t, tt, cap,
                            (int64_t)0x7fffffffffffffffll, (u64)min_voxels);
-    hipLaunchKernelGGL(cc_zspan_blocksum_kernel, dim3((unsigned)nblk), dim3(CC_THREADS), 0, st, t, (const u64 *)tt, cap,
-                       (u64)min_voxels, largest ? 1 : 0, sel, (u64 *)blk, nblk, tt + 2);
+    hipLaunchKernelGGL(cc_zspan_blocksum_kernel, dim3((unsigned)nblk), dim3(CC_THREADS), 0, st, t, (const u64 *)tt, cap, rule, sel,
+                       (u64 *)blk, nblk, tt + 2);
     hipLaunchKernelGGL(cc_scan1_kernel, dim3(1), dim3(1024), 0, st, (u64 *)blk, nblk, tt + 4, (u64 *)nullptr);
     hipLaunchKernelGGL(cc_scan1_kernel, dim3(1), dim3(1024), 0, st, (u64 *)blk + nblk, nblk, tt + 5, (u64 *)nullptr);
-    hipLaunchKernelGGL(cc_zspan_apply_kernel, dim3((unsigned)nblk), dim3(CC_THREADS), 0, st, t, (const u64 *)tt, cap, (u64)min_voxels,
-                       largest ? 1 : 0, (const u64 *)blk, nblk, (u64 *)off, (u32 *)slot);
+    hipLaunchKernelGGL(cc_zspan_apply_kernel, dim3((unsigned)nblk), dim3(CC_THREADS), 0, st, t, (const u64 *)tt, cap, rule,
+                       (const u64 *)blk, nblk, (u64 *)off, (u32 *)slot);
     return tomo_status();
+}
+
+// the rule without an upper bound and without the face test
+TOMO_API int tomo_cc_zhist_offsets(const int64_t *table, int64_t cap, unsigned long long *tot, int64_t min_voxels, int largest,
+                                   uint8_t *sel, uint64_t *off, uint32_t *slot, uint64_t *blk, void *stream)
+{
+    return tomo_cc_select(table, cap, tot, min_voxels, (int64_t)0x7fffffffffffffffll, largest, 0, 0, 0, 0, sel, off, slot, blk, stream);
 }
 
 // ---------------------------------------------------------------------------------------------- sums per component and slice
@@ -879,61 +905,91 @@ __global__ __launch_bounds__(CC_THREADS) void cc_topology_init_kernel(const u64 
     topo[3 * c + 2] = 0;
 }
 
-// One thread per run of the BACKGROUND (the complement, labelled under the complementary connectivity; bg_table = its
-// measurement table).  A run that is its own root is the first run of its component in raster order; if the component's box
+// The tables both sides of a cavity: the volume's (bits .. cap) and those of the BACKGROUND (the complement, labelled under the
+// complementary connectivity; bg_table = its measurement table).
+struct CcCavityIn {
+    const u64 *bits;
+    int64_t nrows;
+    int ny, nx, wx;
+    const u32 *row_off;
+    const u64 *tot;
+    int64_t cap_runs;
+    const u32 *parent, *rank;
+    int64_t cap;
+    const u64 *bg_bits;
+    const u32 *bg_row_off;
+    const u64 *bg_tot;
+    int64_t bg_cap_runs;
+    const u32 *bg_parent, *bg_rank;
+    const u64 *bg_table;
+    int64_t bg_cap;
+};
+
+// Background run i.  A run that is its own root is the first run of its component in raster order; if the component's box
 // touches no face of the stack it is a cavity, the voxel left of the run's start is set and belongs to the foreground
-// component that encloses it: its run is found as cc_expand_kernel maps a bit to a run, and that component counts one more.
-__global__ __launch_bounds__(CC_THREADS) void cc_cavities_kernel(const u64 *__restrict__ bits, int64_t nrows, int ny, int nx, int wx,
-                                                                 const u32 *__restrict__ row_off, const u64 *__restrict__ tot,
-                                                                 int64_t cap_runs, const u32 *__restrict__ parent,
-                                                                 const u32 *__restrict__ rank, int64_t cap,
-                                                                 const u64 *__restrict__ bg_bits, const u32 *__restrict__ bg_row_off,
-                                                                 const u64 *__restrict__ bg_tot, int64_t bg_cap_runs,
-                                                                 const u32 *__restrict__ bg_parent, const u32 *__restrict__ bg_rank,
-                                                                 const u64 *__restrict__ bg_table, int64_t bg_cap,
-                                                                 unsigned long long *__restrict__ topo, u64 *flags)
+// component that encloses it: its run is found as cc_expand_kernel maps a bit to a run.  -> true: *bc = the background
+// component, *fc = its owner (both 0-based, both inside their tables).  The guards of the tables are flagged here.
+__device__ static inline bool cc_cavity_owner(const CcCavityIn &a, int64_t i, u32 *bc, u32 *fc, u64 *flags)
 {
-    const int64_t i = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
-    if (i == 0 && (tot[0] > (u64)cap_runs || tot[1] > (u64)cap || bg_tot[0] > (u64)bg_cap_runs || bg_tot[1] > (u64)bg_cap))
+    if (i == 0 && (a.tot[0] > (u64)a.cap_runs || a.tot[1] > (u64)a.cap || a.bg_tot[0] > (u64)a.bg_cap_runs || a.bg_tot[1] > (u64)a.bg_cap))
         cc_flag(flags, CC_F_CAP);
-    const u32 nruns = (u32)cc_count(tot, cap_runs), ncomp = (u32)cc_ncomp(tot, cap);
-    const u32 nbg_comp = (u32)cc_ncomp(bg_tot, bg_cap);
-    if (i >= cc_count(bg_tot, bg_cap_runs) || nruns == 0 || ncomp == 0 || nbg_comp == 0) return;
+    const u32 nruns = (u32)cc_count(a.tot, a.cap_runs), ncomp = (u32)cc_ncomp(a.tot, a.cap);
+    const u32 nbg_comp = (u32)cc_ncomp(a.bg_tot, a.bg_cap);
+    if (i >= cc_count(a.bg_tot, a.bg_cap_runs) || nruns == 0 || ncomp == 0 || nbg_comp == 0) return false;
     const u32 run = (u32)i;
-    if (bg_parent[run] != run) return;
-    const u32 c = bg_rank[run];
+    if (a.bg_parent[run] != run) return false;
+    const u32 c = a.bg_rank[run];
     if (c >= nbg_comp) {
         cc_flag(flags, CC_F_RANGE);
-        return;
+        return false;
     }
-    const u64 *box = bg_table + (int64_t)c * CC_COLS;
-    const u64 nz = (u64)(nrows / ny);
-    if (box[1] == 0 || box[2] + 1 >= nz || box[3] == 0 || box[4] + 1 >= (u64)ny || box[5] == 0 || box[6] + 1 >= (u64)nx) return;
-    int64_t lo = 0, hi = nrows - 1;                         // the row of the run: the last one with bg_row_off[row] <= run
+    if (!cc_enclosed(a.bg_table + (int64_t)c * CC_COLS, (u64)(a.nrows / a.ny), (u64)a.ny, (u64)a.nx)) return false;
+    int64_t lo = 0, hi = a.nrows - 1;                       // the row of the run: the last one with bg_row_off[row] <= run
     while (lo < hi) {
         const int64_t mid = (lo + hi + 1) >> 1;
-        if (bg_row_off[mid] <= run) lo = mid;
+        if (a.bg_row_off[mid] <= run) lo = mid;
         else hi = mid - 1;
     }
-    const u32 first = bg_row_off[lo];
-    const int s = first <= run ? cc_run_start(bg_bits + lo * wx, nx, wx, run - first) : -1;
+    const u32 first = a.bg_row_off[lo];
+    const int s = first <= run ? cc_run_start(a.bg_bits + lo * a.wx, a.nx, a.wx, run - first) : -1;
     bool ok = s > 0;
     if (ok) {
         const int x = s - 1, wj = x >> 6, b = x & 63;
-        const u64 *r = bits + lo * wx;
-        const u64 cur = cc_word(r, nx, wx, wj);
+        const u64 *r = a.bits + lo * a.wx;
+        const u64 cur = cc_word(r, a.nx, a.wx, wj);
         ok = ((cur >> b) & 1) != 0;
         if (ok) {
-            const u32 fr = cc_run_of_bit(r, nx, wx, wj, b, row_off[lo]);
+            const u32 fr = cc_run_of_bit(r, a.nx, a.wx, wj, b, a.row_off[lo]);
             ok = fr < nruns;
             if (ok) {
-                const u32 fc = cc_component(parent, rank, fr);
-                ok = fc < ncomp;
-                if (ok) atomicAdd(topo + 3 * (int64_t)fc + 1, 1ull);
+                *fc = cc_component(a.parent, a.rank, fr);
+                *bc = c;
+                ok = *fc < ncomp;
             }
         }
     }
     if (!ok) cc_flag(flags, CC_F_RANGE);
+    return ok;
+}
+
+// one thread per run of the background: the owner of a cavity counts one more
+__global__ __launch_bounds__(CC_THREADS) void cc_cavities_kernel(CcCavityIn a, unsigned long long *__restrict__ topo, u64 *flags)
+{
+    u32 bc, fc;
+    if (cc_cavity_owner(a, (int64_t)blockIdx.x * CC_THREADS + threadIdx.x, &bc, &fc, flags)) atomicAdd(topo + 3 * (int64_t)fc + 1, 1ull);
+}
+
+// ... or is written down: owner[c] = the label of the owner of background component c + 1 (one root per component: one store)
+__global__ __launch_bounds__(CC_THREADS) void cc_cavity_owners_kernel(CcCavityIn a, u64 *__restrict__ owner, u64 *flags)
+{
+    u32 bc, fc;
+    if (cc_cavity_owner(a, (int64_t)blockIdx.x * CC_THREADS + threadIdx.x, &bc, &fc, flags)) owner[bc] = (u64)fc + 1;
+}
+
+__global__ __launch_bounds__(CC_THREADS) void cc_zero64_kernel(u64 *__restrict__ out, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    if (i < n) out[i] = 0;
 }
 
 // handles = 1 - euler + cavities
@@ -944,31 +1000,64 @@ __global__ __launch_bounds__(CC_THREADS) void cc_handles_kernel(const u64 *__res
     topo[3 * c + 2] = 1ull - topo[3 * c] + topo[3 * c + 1];
 }
 
+// the argument head tomo_cc_cavities and tomo_cc_cavity_owners share: checked, then gathered for the kernels
+static int cc_cavity_in(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
+                        const uint32_t *rank, const unsigned long long *tot, int64_t cap, const uint64_t *bg_bits,
+                        const uint32_t *bg_row_off, int64_t bg_cap_runs, const uint32_t *bg_parent, const uint32_t *bg_rank,
+                        const unsigned long long *bg_tot, const int64_t *bg_table, int64_t bg_cap, CcCavityIn *a)
+{
+    int64_t nrows;
+    int wx;
+    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
+    if (g != TOMO_OK) return g;
+    if (!row_off || !parent || !rank || !tot || cap_runs <= 0 || cap <= 0 || bg_cap_runs < 0) return TOMO_E_ARG;
+    if (bg_cap_runs > 0 && (!bg_bits || !bg_row_off || !bg_parent || !bg_rank || !bg_tot || !bg_table || bg_cap <= 0)) return TOMO_E_ARG;
+    if (cap_runs >= ((int64_t)1 << 31) || cap >= ((int64_t)1 << 31) || bg_cap_runs >= ((int64_t)1 << 31) || bg_cap >= ((int64_t)1 << 31))
+        return TOMO_E_SIZE;
+    *a = {(const u64 *)bits, nrows, ny, nx, wx, (const u32 *)row_off, (const u64 *)tot, cap_runs, (const u32 *)parent, (const u32 *)rank,
+          cap, (const u64 *)bg_bits, (const u32 *)bg_row_off, (const u64 *)bg_tot, bg_cap_runs, (const u32 *)bg_parent,
+          (const u32 *)bg_rank, (const u64 *)bg_table, bg_cap};
+    return TOMO_OK;
+}
+
 TOMO_API int tomo_cc_cavities(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
                               const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, int64_t cap,
                               const uint64_t *bg_bits, const uint32_t *bg_row_off, int64_t bg_cap_runs, const uint32_t *bg_parent,
                               const uint32_t *bg_rank, const unsigned long long *bg_tot, const int64_t *bg_table, int64_t bg_cap,
                               const int64_t *euler, int64_t *topo, void *stream)
 {
-    int64_t nrows;
-    int wx;
-    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
+    CcCavityIn a;
+    const int g = cc_cavity_in(bits, nz, ny, nx, row_off, cap_runs, parent, rank, tot, cap, bg_bits, bg_row_off, bg_cap_runs, bg_parent,
+                               bg_rank, bg_tot, bg_table, bg_cap, &a);
     if (g != TOMO_OK) return g;
-    if (!row_off || !parent || !rank || !tot || !euler || !topo || cap_runs <= 0 || cap <= 0 || bg_cap_runs < 0) return TOMO_E_ARG;
-    if (bg_cap_runs > 0 && (!bg_bits || !bg_row_off || !bg_parent || !bg_rank || !bg_tot || !bg_table || bg_cap <= 0)) return TOMO_E_ARG;
-    if (cap_runs >= ((int64_t)1 << 31) || cap >= ((int64_t)1 << 31) || bg_cap_runs >= ((int64_t)1 << 31) || bg_cap >= ((int64_t)1 << 31))
-        return TOMO_E_SIZE;
+    if (!euler || !topo) return TOMO_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     const unsigned comp_blocks = (unsigned)ceil_div64(cap, CC_THREADS);
     hipLaunchKernelGGL(cc_topology_init_kernel, dim3(comp_blocks), dim3(CC_THREADS), 0, st, (const u64 *)euler, (const u64 *)tot, cap,
                        (u64 *)topo);
     if (bg_cap_runs > 0)                                    // a full volume has no background run: nothing to attribute
-        hipLaunchKernelGGL(cc_cavities_kernel, dim3((unsigned)ceil_div64(bg_cap_runs, CC_THREADS)), dim3(CC_THREADS), 0, st,
-                           (const u64 *)bits, nrows, ny, nx, wx, (const u32 *)row_off, (const u64 *)tot, cap_runs, (const u32 *)parent,
-                           (const u32 *)rank, cap, (const u64 *)bg_bits, (const u32 *)bg_row_off, (const u64 *)bg_tot, bg_cap_runs,
-                           (const u32 *)bg_parent, (const u32 *)bg_rank, (const u64 *)bg_table, bg_cap, (unsigned long long *)topo,
-                           (u64 *)tot + 2);
+        hipLaunchKernelGGL(cc_cavities_kernel, dim3((unsigned)ceil_div64(bg_cap_runs, CC_THREADS)), dim3(CC_THREADS), 0, st, a,
+                           (unsigned long long *)topo, (u64 *)tot + 2);
     hipLaunchKernelGGL(cc_handles_kernel, dim3(comp_blocks), dim3(CC_THREADS), 0, st, (const u64 *)tot, cap, (u64 *)topo);
+    return tomo_status();
+}
+
+TOMO_API int tomo_cc_cavity_owners(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                                   const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, int64_t cap,
+                                   const uint64_t *bg_bits, const uint32_t *bg_row_off, int64_t bg_cap_runs, const uint32_t *bg_parent,
+                                   const uint32_t *bg_rank, const unsigned long long *bg_tot, const int64_t *bg_table, int64_t bg_cap,
+                                   int64_t *owner, void *stream)
+{
+    CcCavityIn a;
+    const int g = cc_cavity_in(bits, nz, ny, nx, row_off, cap_runs, parent, rank, tot, cap, bg_bits, bg_row_off, bg_cap_runs, bg_parent,
+                               bg_rank, bg_tot, bg_table, bg_cap, &a);
+    if (g != TOMO_OK) return g;
+    if (bg_cap_runs == 0) return TOMO_OK;                   // a full volume has no background component: nothing to write
+    if (!owner) return TOMO_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(cc_zero64_kernel, dim3((unsigned)ceil_div64(bg_cap, CC_THREADS)), dim3(CC_THREADS), 0, st, (u64 *)owner, bg_cap);
+    hipLaunchKernelGGL(cc_cavity_owners_kernel, dim3((unsigned)ceil_div64(bg_cap_runs, CC_THREADS)), dim3(CC_THREADS), 0, st, a,
+                       (u64 *)owner, (u64 *)tot + 2);
     return tomo_status();
 }
 

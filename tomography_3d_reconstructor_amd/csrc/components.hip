@@ -298,13 +298,15 @@ TOMO_API int tomo_cc_expand(const uint64_t *bits, int nz, int ny, int nx, const 
 }
 
 // ---------------------------------------------------------------------------------------------- the keep rule (cc_largest_kernel: cc_runs.h)
-// out word = the bits of the word's runs whose component is kept (MAP: kept = map[c] != 0 for c < nmap, whatever the sizes say)
-template <bool MAP>
+// out word = the bits of the word's runs whose component is kept (MAP: kept = map[c] != 0 for c < nmap, whatever the sizes say;
+// SOLID: ORed with the word of a second volume, its bits at x >= nx cleared)
+template <bool MAP, bool SOLID>
 __global__ __launch_bounds__(CC_THREADS) void cc_filter_kernel(const u64 *__restrict__ bits, int64_t nwords, int nx, int wx,
                                                                const u32 *__restrict__ row_off, const u64 *__restrict__ tot, int64_t cap,
                                                                const u32 *__restrict__ parent, const u32 *__restrict__ rank,
                                                                const unsigned long long *__restrict__ sizes, u64 min_voxels, int largest,
-                                                               const uint8_t *__restrict__ map, u32 nmap, u64 *__restrict__ out, u64 *flags)
+                                                               const uint8_t *__restrict__ map, u32 nmap,
+                                                               const u64 *__restrict__ solid, u64 *__restrict__ out, u64 *flags)
 {
     const int64_t i = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
     if (i >= nwords) return;
@@ -314,7 +316,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_filter_kernel(const u64 *__rest
     const int wj = (int)(i - row * wx);
     const u64 *r = bits + row * wx;
     const u64 m = cc_word(r, nx, wx, wj);
-    u64 res = 0;
+    u64 res = SOLID ? solid[i] & cc_tail_mask(nx, wx, wj) : 0;
     if (m) {
         CcWordRuns it = {m, cc_before(r, nx, wx, wj, row_off[row]), wj > 0 && (r[wj - 1] >> 63)};
         while (cc_word_runs_next(it)) {
@@ -351,10 +353,10 @@ TOMO_API int tomo_cc_filter(const uint64_t *bits, int nz, int ny, int nx, const 
     if (largest)
         hipLaunchKernelGGL(cc_largest_kernel<1>, dim3(1), dim3(1024), 0, st, (const unsigned long long *)sizes, (u64 *)tot, cap_runs,
                            cap_runs, (u64)min_voxels);
-    hipLaunchKernelGGL(cc_filter_kernel<false>, dim3((unsigned)ceil_div64(nwords, CC_THREADS)), dim3(CC_THREADS), 0, st, (const u64 *)bits,
-                       nwords, nx, wx, (const u32 *)row_off, (const u64 *)tot, cap_runs, (const u32 *)parent, (const u32 *)rank,
-                       (const unsigned long long *)sizes, (u64)min_voxels, largest ? 1 : 0, (const uint8_t *)nullptr, 0u, (u64 *)out,
-                       (u64 *)tot + 2);
+    hipLaunchKernelGGL((cc_filter_kernel<false, false>), dim3((unsigned)ceil_div64(nwords, CC_THREADS)), dim3(CC_THREADS), 0, st,
+                       (const u64 *)bits, nwords, nx, wx, (const u32 *)row_off, (const u64 *)tot, cap_runs, (const u32 *)parent,
+                       (const u32 *)rank, (const unsigned long long *)sizes, (u64)min_voxels, largest ? 1 : 0, (const uint8_t *)nullptr, 0u,
+                       (const u64 *)nullptr, (u64 *)out, (u64 *)tot + 2);
     return tomo_status();
 }
 
@@ -595,22 +597,38 @@ TOMO_API int tomo_cc_local_maps(const uint32_t *table, const uint32_t *num, cons
     return tomo_status();
 }
 
-TOMO_API int tomo_cc_filter_map(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
-                                const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const uint8_t *keep,
-                                int64_t n_local, uint64_t *out, void *stream)
+// the keep map applied to the runs of `bits`; solid (may be NULL): a second volume of the same geometry every word is ORed with
+TOMO_API int tomo_cc_fill_map(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                              const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const uint8_t *keep,
+                              int64_t n_local, const uint64_t *solid, uint64_t *out, void *stream)
 {
     int64_t nrows;
     int wx;
     const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
     if (g != TOMO_OK) return g;
-    if (!row_off || !parent || !rank || !tot || !keep || !out || out == bits || cap_runs <= 0 || n_local <= 0 || n_local > cap_runs)
+    if (!row_off || !parent || !rank || !tot || !keep || !out || out == bits || out == solid || cap_runs <= 0 || n_local <= 0 ||
+        n_local > cap_runs)
         return TOMO_E_ARG;
     if (cap_runs >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
     const int64_t nwords = nrows * wx;
-    hipLaunchKernelGGL(cc_filter_kernel<true>, dim3((unsigned)ceil_div64(nwords, CC_THREADS)), dim3(CC_THREADS), 0, (hipStream_t)stream,
-                       (const u64 *)bits, nwords, nx, wx, (const u32 *)row_off, (const u64 *)tot, cap_runs, (const u32 *)parent,
-                       (const u32 *)rank, (const unsigned long long *)nullptr, (u64)0, 0, keep, (u32)n_local, (u64 *)out, (u64 *)tot + 2);
+    const dim3 grid((unsigned)ceil_div64(nwords, CC_THREADS)), block(CC_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+    if (solid)
+        hipLaunchKernelGGL((cc_filter_kernel<true, true>), grid, block, 0, st, (const u64 *)bits, nwords, nx, wx, (const u32 *)row_off,
+                           (const u64 *)tot, cap_runs, (const u32 *)parent, (const u32 *)rank, (const unsigned long long *)nullptr, (u64)0, 0,
+                           keep, (u32)n_local, (const u64 *)solid, (u64 *)out, (u64 *)tot + 2);
+    else
+        hipLaunchKernelGGL((cc_filter_kernel<true, false>), grid, block, 0, st, (const u64 *)bits, nwords, nx, wx, (const u32 *)row_off,
+                           (const u64 *)tot, cap_runs, (const u32 *)parent, (const u32 *)rank, (const unsigned long long *)nullptr, (u64)0, 0,
+                           keep, (u32)n_local, (const u64 *)nullptr, (u64 *)out, (u64 *)tot + 2);
     return tomo_status();
+}
+
+TOMO_API int tomo_cc_filter_map(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                                const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const uint8_t *keep,
+                                int64_t n_local, uint64_t *out, void *stream)
+{
+    return tomo_cc_fill_map(bits, nz, ny, nx, row_off, cap_runs, parent, rank, tot, keep, n_local, nullptr, out, stream);
 }
 
 TOMO_API int tomo_cc_expand_map(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,

@@ -24,7 +24,8 @@ COUNTERS = dict.fromkeys(("na_hint_hit", "na_hint_miss", "mc3_hint_hit", "mc3_hi
                           "components_filter", "slab_components_label", "slab_components_seam", "slab_components_merge",
                           "slab_components_expand", "slab_components_filter", "distance_transform", "distance_offset",
                           "components_measure", "components_zhist", "components_moments", "components_euler",
-                          "components_cavities", "local_thickness", "opening_volume", "components_surface"), 0)
+                          "components_cavities", "local_thickness", "opening_volume", "components_surface", "components_fill",
+                          "components_cavity_owners"), 0)
 NA_HINTS = os.environ.get("TOMO_NA_HINTS", "1") not in ("", "0")   # marching_cubes: launch ahead of the first count download
 _NA_HINT = {}
 LIST_LIMIT = 2 ** 31        # active-voxel list entries / vertices / triangles one pass can index (int32 offsets in mc.hip, mesh.hip);
@@ -256,6 +257,35 @@ def _check_connectivity(connectivity) -> int:
     return int(connectivity)
 
 
+NO_MAX_VOXELS = 2 ** 63 - 1  # max_voxels=None as the kernels take it
+
+
+def _keep_rule(min_voxels=0, largest=False, max_voxels=None, enclosed=False) -> tuple:
+    """The normalised keep rule (min_voxels, largest, max_voxels, enclosed): what ComponentRuns.select compares and runs.
+    A negative min_voxels is 0; max_voxels=None is no upper bound, a negative one a ValueError; largest goes with neither
+    max_voxels nor enclosed (ValueError: the largest cavity is an argmax over the returned table)."""
+    rule = (max(0, int(min_voxels)), bool(largest), None if max_voxels is None else int(max_voxels), bool(enclosed))
+    if rule[2] is not None and rule[2] < 0:
+        raise ValueError("max_voxels must be non-negative or None")
+    if rule[1] and (rule[2] is not None or rule[3]):
+        raise ValueError("largest cannot be combined with max_voxels or enclosed")
+    return rule
+
+
+def _whole_size(v, name) -> int:
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError("%s must be a non-negative whole number" % name)
+    if not (math.isfinite(v) and v >= 0 and int(v) == v):
+        raise ValueError("%s must be a non-negative whole number" % name)
+    return int(v)
+
+
+def _check_size_window(min_voxels, max_voxels):
+    """The size window of the cavity calls -> (min_voxels, max_voxels) as ints (max_voxels=None stays None); a size that is
+    negative or no whole number is a ValueError.  min_voxels > max_voxels selects nothing and is no error."""
+    return _whole_size(min_voxels, "min_voxels"), None if max_voxels is None else _whole_size(max_voxels, "max_voxels")
+
+
 @dataclass(frozen=True)
 class _Measurement:
     """What tells one per-component measurement from the next in ComponentRuns._rows: a histogram per slice of every selected
@@ -303,7 +333,8 @@ class ComponentRuns:
     run of set bits in a row) and never per voxel.  Two host reads: the number of runs (it sizes the tables) and the
     counters after the labelling.  n = components; labels() / sizes() / keep() read the tables.
     One object serves every per-component measurement of its volume: properties(), moments(), topology_rows() and surface()
-    share the labelling, the measurement table and ONE selection, which the object owns (select)."""
+    share the labelling, the measurement table and ONE selection, which the object owns (select).  background() is the same
+    kind of object for the complement: its enclosed components are the cavities of this volume (cavity_owners)."""
 
     def __init__(self, vol: BitVolume, connectivity=6):
         connectivity = _check_connectivity(connectivity)
@@ -320,6 +351,7 @@ class ComponentRuns:
         self.n = 0
         self._table = None
         self._topology = None
+        self._background = self._owners = None
         self._rule = self._picked = None
         COUNTERS["components_label"] += 1
         if self.runs == 0:
@@ -376,14 +408,17 @@ class ComponentRuns:
             self._checked()
         return table
 
-    def select(self, min_voxels=0, largest=False):
+    def select(self, min_voxels=0, largest=False, *, max_voxels=None, enclosed=False):
         """The keep rule of keep() on the measurement table: the components of at least min_voxels voxels -- largest: only the
         largest of those, the lowest label among equals -- in ascending label -> ComponentSelection, or None when there is no
-        component or none is selected.  One host read: the counters, with the guards of everything enqueued so far.
+        component or none is selected.  max_voxels: at most that many voxels as well; enclosed: only the components whose index
+        box touches no face of the stack -- on the ComponentRuns of a complement (background()) those are the cavities.  Neither
+        goes with largest (ValueError, before anything is launched).  One host read: the counters, with the guards of everything
+        enqueued so far.
         The object keeps ONE selection: the kernel leaves its entry total and row count in the counter block, where every
         finishing kernel reads them, so the answer (None too) is kept for as long as the normalised rule stays the one last
         run, and replaced -- every ComponentSelection handed out before is then void -- when another rule is asked for."""
-        rule = (max(0, int(min_voxels)), bool(largest))
+        rule = _keep_rule(min_voxels, largest, max_voxels, enclosed)
         if rule == self._rule:
             return self._picked
         table = self._measure()
@@ -396,8 +431,8 @@ class ComponentRuns:
             slot = torch.empty(n, dtype=torch.int32, device=dev)
             blk = torch.empty(2 * L.tomo_cc_scan_blocks(n), dtype=torch.int64, device=dev)
             self._rule = None                                           # the counter block is about to change hands
-            _lib.check(L.tomo_cc_zhist_offsets(_p(table), n, _p(self.tot), rule[0], int(rule[1]), _p(sel), _p(off), _p(slot), _p(blk),
-                                               _stream()), "tomo_cc_zhist_offsets")
+            _lib.check(L.tomo_cc_select(_p(table), n, _p(self.tot), rule[0], NO_MAX_VOXELS if rule[2] is None else rule[2], int(rule[1]),
+                                        int(rule[3]), *self.vol.shape, _p(sel), _p(off), _p(slot), _p(blk), _stream()), "tomo_cc_select")
             self._checked()                                             # ... and the guards of the measuring pass
             total, m = self.host[4], self.host[5]
             picked = ComponentSelection(table, sel, off, slot, total, m) if m else None
@@ -422,12 +457,12 @@ class ComponentRuns:
             raise _lib.TomoError("%s: the tables do not fit the volume (flags %d)" % (name, flags[0]))
         return host
 
-    def _rows(self, spec: _Measurement, min_voxels, largest, host_table, *scalars):
-        """One measurement of the components the rule selects: spec.words uint64 per slice of every selected component's box
+    def _rows(self, spec: _Measurement, rule, host_table, *scalars):
+        """One measurement of the components the rule (_keep_rule's tuple) selects: spec.words uint64 per slice of every selected component's box
         from spec.hist, then spec.finish with one thread per component -> the host arrays (table columns, labels, *results),
         spec.empty() when nothing is selected.  host_table: the float64 table(s) the finishing kernel reads, uploaded here;
         scalars: its arguments between nz and the result tensors."""
-        picked = self.select(min_voxels, largest)
+        picked = self.select(rule[0], rule[1], max_voxels=rule[2], enclosed=rule[3])
         if picked is None or picked.total == 0:
             return spec.empty()
         total, m, nbytes = picked.total, picked.m, 8 * spec.words * picked.total
@@ -448,23 +483,27 @@ class ComponentRuns:
         ride = picked.table[:, spec.columns].index_select(0, labels - 1)
         return self._download_checked(spec.name, ride, labels, *results)
 
-    def properties(self, tables, mm_y, mm_x, min_voxels=0, largest=False) -> "ComponentProperties":
-        """component_properties of this volume; tables: _slice_weights' (2 nz,)."""
-        return _component_properties_from(*self._rows(_PROPERTIES, min_voxels, largest, tables), float(mm_y), float(mm_x))
+    def properties(self, tables, mm_y, mm_x, min_voxels=0, largest=False, *, max_voxels=None, enclosed=False) -> "ComponentProperties":
+        """component_properties of this volume; tables: _slice_weights' (2 nz,).  The rule: select's."""
+        rule = _keep_rule(min_voxels, largest, max_voxels, enclosed)
+        return _component_properties_from(*self._rows(_PROPERTIES, rule, tables), float(mm_y), float(mm_x))
 
-    def moments(self, tables, mm_y, mm_x, min_voxels=0, largest=False) -> "ComponentMoments":
-        """component_moments of this volume; tables: _slice_weights' (2 nz,)."""
-        return _component_moments_from(*self._rows(_MOMENTS, min_voxels, largest, tables, float(mm_y), float(mm_x)))
+    def moments(self, tables, mm_y, mm_x, min_voxels=0, largest=False, *, max_voxels=None, enclosed=False) -> "ComponentMoments":
+        """component_moments of this volume; tables: _slice_weights' (2 nz,).  The rule: select's."""
+        rule = _keep_rule(min_voxels, largest, max_voxels, enclosed)
+        return _component_moments_from(*self._rows(_MOMENTS, rule, tables, float(mm_y), float(mm_x)))
 
-    def surface(self, factors, directions, min_voxels=0, largest=False) -> "ComponentSurface":
-        """component_surface of this volume; factors: surface_factors' (nz, 11) for the same directions."""
-        voxels, labels, area, counts = self._rows(_SURFACE, min_voxels, largest, factors, int(directions))
+    def surface(self, factors, directions, min_voxels=0, largest=False, *, max_voxels=None, enclosed=False) -> "ComponentSurface":
+        """component_surface of this volume; factors: surface_factors' (nz, 11) for the same directions.  The rule: select's."""
+        rule = _keep_rule(min_voxels, largest, max_voxels, enclosed)
+        voxels, labels, area, counts = self._rows(_SURFACE, rule, factors, int(directions))
         return _component_surface_from(voxels, labels, counts, area)
 
-    def topology_rows(self, min_voxels=0, largest=False) -> "ComponentTopology":
-        """component_topology of this volume: the rows of topology() the rule selects."""
+    def topology_rows(self, min_voxels=0, largest=False, *, max_voxels=None, enclosed=False) -> "ComponentTopology":
+        """component_topology of this volume: the rows of topology() the rule (select's) selects."""
+        rule = _keep_rule(min_voxels, largest, max_voxels, enclosed)
         topo = self.topology()
-        picked = self.select(min_voxels, largest) if topo.shape[0] else None
+        picked = self.select(rule[0], rule[1], max_voxels=rule[2], enclosed=rule[3]) if topo.shape[0] else None
         if picked is None:
             return _component_topology_from(*_TOPOLOGY.empty())
         rows = torch.empty((picked.m, *_TOPOLOGY.results[0][1]), dtype=torch.int64, device=self.vol.device)
@@ -478,7 +517,8 @@ class ComponentRuns:
         connectivity (26 for 6, 6 for 26) and everything outside the stack is background: a void that reaches a face of the
         stack is no cavity.  The Euler pass runs over the rows of this object; the cavities come from a second ComponentRuns
         over the complement: every component of it whose box touches no face is a cavity of the component left of its first
-        voxel.  Working memory: one more bit volume and the run tables of the complement, never a label array."""
+        voxel.  That object is kept (background()).  Working memory: one more bit volume and the run tables of the complement,
+        never a label array."""
         if self._topology is None:
             dev = self.vol.device
             n = self._checked() if self.runs else 0
@@ -501,8 +541,40 @@ class ComponentRuns:
             COUNTERS["components_cavities"] += 1
             _lib.check(L.tomo_cc_cavities(*geo, *self._tables(), _p(self.tot), n, *bg_args, _p(euler), _p(topo), st), "tomo_cc_cavities")
             self._checked()
-            self._topology = topo
+            self._topology, self._background = topo, bg
         return self._topology
+
+    def background(self) -> "ComponentRuns":
+        """The complement of this volume inside the stack as a ComponentRuns under the complementary connectivity 32 - k: the
+        object topology() builds (it runs first if it has not), labelled once and kept.  Its components in ascending label are
+        the voids of the volume in the raster order of their first voxel; select(enclosed=True) on it picks the cavities, and
+        properties / moments / surface measure them like any component."""
+        if self._background is None:
+            self.topology()
+        if self._background is None:                                    # no component here: topology() had nothing to build
+            self._background = _complement_runs(BitVolume(self.bits, self.vol.shape), self.connectivity)
+        return self._background
+
+    def cavity_owners(self) -> torch.Tensor:
+        """Per component 1..n_bg of background(): the label of the component of this volume that owns it -- the one holding the
+        voxel left of the cavity's first run in raster order -- or 0 for a void that reaches a face of the stack -> int64 (n_bg,)
+        device tensor, computed once and kept.  An island floating in a void does not own that void."""
+        if self._owners is None:
+            bg = self.background()
+            bg_table = bg.table()
+            dev, n_bg = self.vol.device, bg_table.shape[0]
+            n = self._checked() if self.runs else 0
+            if n == 0 or n_bg == 0:
+                self._owners = torch.zeros(n_bg, dtype=torch.int64, device=dev)
+            else:
+                owner = torch.empty(n_bg, dtype=torch.int64, device=dev)
+                COUNTERS["components_cavity_owners"] += 1
+                _lib.check(_lib.lib().tomo_cc_cavity_owners(_p(self.bits), *self.vol.shape, *self._tables(), _p(self.tot), n, _p(bg.bits),
+                                                            _p(bg.row_off), bg.runs, _p(bg.parent), _p(bg.rank), _p(bg.tot), _p(bg_table),
+                                                            n_bg, _p(owner), _stream()), "tomo_cc_cavity_owners")
+                self._checked()
+                self._owners = owner
+        return self._owners
 
     def labels(self):
         """-> (int32 (nz, ny, nx) device tensor as scipy.ndimage.label returns it, n)."""
@@ -703,6 +775,94 @@ def volume_topology(vol: BitVolume, connectivity=6) -> dict:
     topo = ComponentRuns(vol, connectivity).topology()
     euler, cavities, handles = (int(v) for v in topo.sum(dim=0).cpu()) if topo.shape[0] else (0, 0, 0)
     return {"components": int(topo.shape[0]), "cavities": cavities, "handles": handles, "euler": euler}
+
+
+# ----------------------------------------------------------------------------- cavities: closed porosity
+def _complement_runs(vol: BitVolume, connectivity) -> ComponentRuns:
+    """The voids of a volume: its complement inside the stack, labelled under the complementary connectivity."""
+    nz, ny, nx = vol.shape
+    bits = vol.bits.contiguous()
+    outside = torch.empty_like(bits)
+    _lib.check(_lib.lib().tomo_cc_complement(_p(bits), nz, ny, nx, _p(outside), _stream()), "tomo_cc_complement")
+    return ComponentRuns(BitVolume(outside, vol.shape), 32 - connectivity)
+
+
+@dataclass
+class Cavities:
+    """cavity_table's answer: host arrays, one row per selected cavity in ascending cavity label."""
+    labels: np.ndarray           # int64 (m,): the label of the cavity among the components of the complement
+    owner: np.ndarray            # int64 (m,): the label of the component of the volume that encloses it
+    voxels: np.ndarray           # int64 (m,)
+    index_box: np.ndarray        # int64 (m, 6): zmin, zmax, ymin, ymax, xmin, xmax, inclusive
+    volume_mm3: np.ndarray       # float64 (m,)
+    centroid_mm: np.ndarray      # float64 (m, 3): z, y, x in the coordinates of distance_positions
+    centroid_index: np.ndarray   # float64 (m, 3)
+
+    def __len__(self):
+        return len(self.labels)
+
+
+def _cavities_from(runs: ComponentRuns, p: ComponentProperties) -> Cavities:
+    """The rows of background().properties(enclosed=True) with the owners of runs.cavity_owners() gathered next to them."""
+    if len(p):
+        owner = runs.cavity_owners().index_select(0, torch.from_numpy(p.labels - 1).to(runs.vol.device)).cpu().numpy()
+    else:
+        owner = np.zeros(0, dtype=np.int64)
+    return Cavities(p.labels, owner, p.voxels, p.index_box, p.volume_mm3, p.centroid_mm, p.centroid_index)
+
+
+def cavity_table(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, connectivity=6, min_voxels=0,
+                 max_voxels=None) -> Cavities:
+    """The enclosed voids of a resident volume, one row each -> Cavities.  The volume has connectivity k = 6 or 26, its
+    complement the complementary 32 - k, everything outside the stack is background.  A cavity is a component of the
+    complement whose inclusive index box touches no face of the stack; its label is its label there (raster order of the
+    first voxel), its owner the component of the volume (label under k) that holds the voxel left of the cavity's first run: an
+    island floating in a void does not own that void, and is no part of its size.  Rows: the cavities with min_voxels <=
+    voxels <= max_voxels (None: no upper bound; min > max selects nothing), in ascending label.  voxels, index_box, volume_mm3,
+    centroid_mm and centroid_index are component_properties' numbers for the mask of the cavity, bit for bit.  One labelling
+    of the volume and one of the complement; an empty or a full volume has no rows.  Arguments are checked before the first
+    launch; the budget of the per-slice counters is component_properties'."""
+    connectivity = _check_connectivity(connectivity)
+    lo, hi = _check_size_window(min_voxels, max_voxels)
+    tables = _slice_weights(slice_depths, vol.shape[0], mm_per_pixel_y, mm_per_pixel_x)
+    runs = ComponentRuns(vol, connectivity)
+    if runs.runs == 0:                                                  # nothing encloses anything
+        return _cavities_from(runs, _component_properties_from(*_PROPERTIES.empty(), float(mm_per_pixel_y), float(mm_per_pixel_x)))
+    p = runs.background().properties(tables, mm_per_pixel_y, mm_per_pixel_x, lo, max_voxels=hi, enclosed=True)
+    return _cavities_from(runs, p)
+
+
+def _cavity_map(vol: BitVolume, connectivity, min_voxels, max_voxels, solid) -> BitVolume:
+    """The voxels of the selected cavities of `vol`, ORed with `vol` itself when solid: complement, one labelling under the
+    complementary connectivity, one selection, one pass over the words.  No labelling of the volume."""
+    connectivity = _check_connectivity(connectivity)
+    lo, hi = _check_size_window(min_voxels, max_voxels)
+    bits = vol.bits.contiguous()
+    COUNTERS["components_fill"] += 1
+    bg = _complement_runs(BitVolume(bits, vol.shape), connectivity)
+    picked = bg.select(lo, max_voxels=hi, enclosed=True) if bg.runs else None
+    if picked is None:                                                  # empty, full, or no cavity in the window
+        return BitVolume(bits.clone() if solid else torch.zeros_like(bits), vol.shape)
+    out = torch.empty_like(bits)
+    _lib.check(_lib.lib().tomo_cc_fill_map(_p(bg.bits), *vol.shape, *bg._tables(), _p(bg.tot), _p(picked.sel), picked.sel.shape[0],
+                                           _p(bits) if solid else None, _p(out), _stream()), "tomo_cc_fill_map")
+    bg._checked()
+    return BitVolume(out, vol.shape)
+
+
+def cavity_volume(vol: BitVolume, connectivity=6, min_voxels=0, max_voxels=None) -> BitVolume:
+    """A NEW volume holding only the voxels of the cavities of `vol` (cavity_table's definition and size window): the pore
+    space as a bit volume -- local_thickness of it is the pore-size distribution.  `vol` is left untouched; an empty or a full
+    volume gives an empty one."""
+    return _cavity_map(vol, connectivity, min_voxels, max_voxels, False)
+
+
+def fill_cavities(vol: BitVolume, connectivity=6, min_voxels=0, max_voxels=None) -> BitVolume:
+    """A NEW volume: `vol` with its cavities filled (cavity_table's definition; only those inside the size window).  Without a
+    window it is scipy.ndimage.binary_fill_holes(volume, generate_binary_structure(3, 1 if connectivity == 26 else 3)) -- the
+    structure is the BACKGROUND's -- on the resident bits: the 3-D counterpart of the fill close_ends does in the two end
+    slices.  `vol` is left untouched; an empty volume comes back empty, a full one as a copy."""
+    return _cavity_map(vol, connectivity, min_voxels, max_voxels, True)
 
 
 # ----------------------------------------------------------------------------- surface area (Crofton)

@@ -145,8 +145,42 @@ def surface_area(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, direc
     return {'surface_area_mm2': s, 'voxel_volume_mm3': v, 'sphericity': sphericity(v, s)}
 
 
+def closed_porosity(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=6, min_voxels=0, max_voxels=None):
+    """The enclosed voids of the volume, listed and added up (no counterpart in the reference): pipeline.cavity_table -- a
+    cavity is a component of the complement, under the complementary connectivity, that reaches no face of the stack; per-slice
+    depths honoured -> {'cavities', 'cavity_voxels', 'cavity_volume_mm3', 'voxel_volume_mm3', 'closed_porosity', 'table'}.
+    table: one dict per cavity with min_voxels <= voxels <= max_voxels (None: no upper bound) in ascending label: {'label',
+    'owner' (the label of the component that encloses it), 'voxels', 'volume_mm3', 'bounding_box': {'x', 'y', 'z'},
+    'dimensions', 'centroid_mm': (z, y, x), 'centroid_index': (z, y, x), 'equivalent_diameter_mm'} -- volume, box and centroids
+    as component_properties gives them for the mask of the cavity, equivalent_diameter_mm = cbrt(6 V / pi).
+    cavity_volume_mm3: the rows' volumes added in that order; voxel_volume_mm3: calculate_voxel_volume_variable_depth's number
+    for the solid; closed_porosity = cavity / (solid + cavity), 0.0 for an empty volume.  voxel_data: the bool (nz, ny, nx) array
+    the other calculations take; anything else is a TypeError -- there is no host path for this one."""
+    if not _on_device(voxel_data):
+        raise TypeError("closed_porosity needs a bool (nz, ny, nx) array")
+    depths = np.asarray(slice_depths, dtype=np.float64).reshape(-1)
+    pipeline._check_connectivity(connectivity)                  # the argument checks, before anything is uploaded
+    pipeline._check_size_window(min_voxels, max_voxels)
+    pipeline._slice_weights(depths, len(voxel_data), mm_per_pixel_y, mm_per_pixel_x)
+    vol = to_device_volume(voxel_data)
+    t = pipeline.cavity_table(vol, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_voxels, max_voxels)
+    solid = float(volume_from_slice_counts(pipeline.slice_counts(vol).cpu().numpy(), mm_per_pixel_x, mm_per_pixel_y, depths))
+    boxes = [box_variable_depth(tuple(b), mm_per_pixel_x, mm_per_pixel_y, depths) for b in t.index_box]
+    table = [{'label': int(t.labels[i]), 'owner': int(t.owner[i]), 'voxels': int(t.voxels[i]), 'volume_mm3': float(t.volume_mm3[i]),
+              'bounding_box': {axis: box[axis] for axis in ('x', 'y', 'z')}, 'dimensions': box['dimensions'],
+              'centroid_mm': tuple(float(v) for v in t.centroid_mm[i]),
+              'centroid_index': tuple(float(v) for v in t.centroid_index[i]),
+              'equivalent_diameter_mm': float(np.cbrt(6.0 * t.volume_mm3[i] / np.pi))} for i, box in enumerate(boxes)]
+    cavity = 0.0
+    for row in table:
+        cavity += row['volume_mm3']
+    whole = solid + cavity
+    return {'cavities': len(table), 'cavity_voxels': int(t.voxels.sum()), 'cavity_volume_mm3': cavity, 'voxel_volume_mm3': solid,
+            'closed_porosity': cavity / whole if whole else 0.0, 'table': table}
+
+
 def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=6, min_voxels=0, largest=False,
-                         shape=False, topology=False, surface=False, surface_directions=13):
+                         shape=False, topology=False, surface=False, surface_directions=13, porosity=False):
     """The calculations of the class per connected component (no counterpart in the reference, which would be handed the mask
     `labels == c` once per component) -> a list of dicts, one per component with at least min_voxels voxels (largest: only the
     largest of those), in label order: {'label', 'voxels', 'voxel_volume_mm3', 'bounding_box': {'x', 'y', 'z'}, 'dimensions',
@@ -161,9 +195,11 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
     a ball reads 1, 0, 0, a hollow shell 2, 1, 0, a ring 0, 0, 1; the background has the complementary connectivity).
     surface=True: every dict also carries 'surface_area_mm2' -- the discretised Crofton formula on the component's voxels
     (pipeline.component_surface; surface_directions = 13 or 3; a voxel of another component is not background) -- and
-    'sphericity' = pi^(1/3) (6 voxel_volume_mm3)^(2/3) / surface_area_mm2 as Python floats.  Whatever the flags, the volume is
-    uploaded and labelled ONCE: one pipeline.ComponentRuns serves all four measurements and owns the one selection their rows
-    come from.  Arguments are checked before the first launch.  voxel_data: a bool (nz, ny, nx) array, else a TypeError."""
+    'sphericity' = pi^(1/3) (6 voxel_volume_mm3)^(2/3) / surface_area_mm2 as Python floats.  porosity=True: every dict also
+    carries 'cavity_voxels' (int), 'cavity_volume_mm3' -- the volumes of the cavities the component owns (closed_porosity's
+    table), added in ascending cavity label -- and 'closed_porosity' = cavity / (voxel_volume_mm3 + cavity).  Whatever the
+    flags, the volume is uploaded and labelled ONCE, and so is its complement: one pipeline.ComponentRuns serves all the
+    measurements and owns the one selection their rows come from.  Arguments are checked before the first launch.  voxel_data: a bool (nz, ny, nx) array, else a TypeError."""
     if not _on_device(voxel_data):
         raise TypeError("component_properties needs a bool (nz, ny, nx) array")
     depths = np.asarray(slice_depths, dtype=np.float64).reshape(-1)
@@ -183,6 +219,12 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
     q = runs.moments(tables, mm_per_pixel_y, mm_per_pixel_x, *rule) if shape else None
     t = runs.topology_rows(*rule) if topology else None
     a = runs.surface(factors, surface_directions, *rule) if surface else None
+    pores = {}
+    if porosity:                                                 # every cavity of the volume, credited to its owner
+        c = pipeline._cavities_from(runs, runs.background().properties(tables, mm_per_pixel_y, mm_per_pixel_x, enclosed=True))
+        for owner, n, v in zip(c.owner, c.voxels, c.volume_mm3):
+            have = pores.get(int(owner), (0, 0.0))
+            pores[int(owner)] = (have[0] + int(n), have[1] + float(v))
     for i, d in enumerate(out):                                  # row i of every answer: they come from the one selection of `runs`
         if shape:
             d['center_of_mass_mm'] = tuple(float(v) for v in q.center_of_mass_mm[i])
@@ -195,6 +237,10 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
         if surface:
             d['surface_area_mm2'] = float(a.surface_area_mm2[i])
             d['sphericity'] = sphericity(d['voxel_volume_mm3'], d['surface_area_mm2'])
+        if porosity:
+            d['cavity_voxels'], d['cavity_volume_mm3'] = pores.get(d['label'], (0, 0.0))
+            whole = d['voxel_volume_mm3'] + d['cavity_volume_mm3']
+            d['closed_porosity'] = d['cavity_volume_mm3'] / whole if whole else 0.0
     return out
 
 

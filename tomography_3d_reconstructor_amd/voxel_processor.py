@@ -316,7 +316,12 @@ class VoxelProcessor:
     TOMO_KEEP_LARGEST=1 in the environment set the first two for every new object, which is how the unchanged orchestrator
     gets them): with min_component_voxels > 0 or keep_largest_component set, every volume create_voxel_data and
     smooth_voxel_data hand out holds only the connected components (component_connectivity 6 or 26, scipy.ndimage.label's
-    meaning) of at least that many voxels, respectively only the largest of those.  Off by default: nothing is launched then."""
+    meaning) of at least that many voxels, respectively only the largest of those.  Off by default: nothing is launched then.
+
+    Likewise optional: filling enclosed cavities.  fill_cavities (TOMO_FILL_CAVITIES=1) and max_cavity_voxels
+    (TOMO_MAX_CAVITY_VOXELS=N; 0: no limit): every volume handed out has its enclosed voids -- those of at most that many voxels
+    -- filled (pipeline.fill_cavities under component_connectivity), after the islands are gone and, in smooth_voxel_data,
+    after the smoothing, because a closing can seal a void.  Off by default: nothing is launched then."""
 
     def __init__(self):
         self.voxel_data = None
@@ -326,6 +331,8 @@ class VoxelProcessor:
         self.min_component_voxels = _env_count("TOMO_MIN_COMPONENT_VOXELS")
         self.keep_largest_component = os.environ.get("TOMO_KEEP_LARGEST", "0") not in ("", "0")
         self.component_connectivity = 6
+        self.fill_cavities = os.environ.get("TOMO_FILL_CAVITIES", "0") not in ("", "0")
+        self.max_cavity_voxels = _env_count("TOMO_MAX_CAVITY_VOXELS")
 
     def _component_options(self):
         """(min voxels, largest, connectivity) when island removal is on, else None."""
@@ -336,10 +343,25 @@ class VoxelProcessor:
             raise ValueError("component_connectivity must be 6 or 26")
         return max(n, 0), largest, int(self.component_connectivity)
 
+    def _fill_options(self):
+        """(connectivity, largest cavity filled or None) when cavity filling is on, else None."""
+        if not self.fill_cavities:
+            return None
+        n = int(self.max_cavity_voxels)
+        if n < 0:
+            raise ValueError("max_cavity_voxels must be a non-negative integer")
+        if self.component_connectivity not in pipeline.CONNECTIVITIES:
+            raise ValueError("component_connectivity must be 6 or 26")
+        return int(self.component_connectivity), n if n > 0 else None
+
     def _keep_components(self, vol):
-        """`vol` without its islands (a new volume), or `vol` itself when the option is off."""
-        opts = self._component_options()
-        return vol if opts is None else pipeline.keep_components(vol, *opts)
+        """`vol` without its islands, then with its cavities filled (a new volume), or `vol` itself when both options are off."""
+        opts, fill = self._component_options(), self._fill_options()
+        if opts is not None:
+            vol = pipeline.keep_components(vol, *opts)
+        if fill is not None:
+            vol = pipeline.fill_cavities(vol, fill[0], 0, fill[1])
+        return vol
 
     def create_voxel_data(self, mask_images: list, close_ends: bool = True,
                           side_0_count: int = 0, side_1_count: int = 0, side_2_count: int = 0) -> np.ndarray:
@@ -379,7 +401,7 @@ class VoxelProcessor:
         else:
             stacked = np.stack(mask_images, axis=0)          # the reference returns a new array here
             vol = cached if cached is not None else upload_volume(stacked)
-            if self._component_options() is not None:
+            if self._component_options() is not None or self._fill_options() is not None:
                 vol = self._keep_components(vol)             # the array handed out is the download of the filtered volume
                 active = int(pipeline.popcount_async(vol).item())
                 self.voxel_data = to_host_volume(vol)
@@ -409,7 +431,7 @@ class VoxelProcessor:
             except Exception as e:                                       # noqa: BLE001 -- the reference catches Exception here
                 print(f"tomography_3d_reconstructor_amd: smoothing failed ({e}); closings only", file=sys.stderr)
                 return to_host_volume(self._keep_components(pipeline.smooth(vol, iterations, False)))
-        opts = self._component_options()
+        opts = (self._component_options(), self._fill_options())
         return with_device_volume(voxel_data, work)
 
     def generate_point_cloud(self, voxel_data: np.ndarray, mm_per_pixel_x: float, mm_per_pixel_y: float,
