@@ -163,6 +163,11 @@ __device__ static inline u32 cc_find_compress(u32 *parent, u32 x)
     return r;
 }
 
+// Only a ROOT is ever hooked (compare-and-swap): the parent of a run that has one is changed by cc_find_compress alone, to an
+// ancestor further up, so a root a thread has found stays an ancestor of every run it found it from.  Hooking with atomicMin
+// would also re-parent a run that somebody else hooked in the meantime, into ANOTHER tree; a cc_find_compress still on its way
+// to the root it found before that then walks on in that other tree and points its runs at the old root, which cuts them off
+// from their own, smaller root for good (seen past 900 000 runs: one to three components split per labelling).
 __device__ static inline void cc_union(u32 *parent, u32 a, u32 b)
 {
     while (true) {
@@ -170,10 +175,8 @@ __device__ static inline void cc_union(u32 *parent, u32 a, u32 b)
         b = cc_find_compress(parent, b);
         if (a == b) return;
         if (a < b) { const u32 t = a; a = b; b = t; }       // a > b: hook a under b
-        const u32 old = atomicMin(parent + a, b);
-        if (old >= a) return;                               // a was a root: hooked (old == a; > a cannot be)
-        a = old;                                            // somebody hooked a first, under old < a: unite old and b
-    }
+        if (atomicCAS(parent + a, a, b) == a) return;       // a was still a root: hooked
+    }                                                       // somebody hooked a first: look again from where it points now
 }
 
 // 0-based component of a run once the trees are flat and the roots are numbered (a parent above its run cannot be: the run

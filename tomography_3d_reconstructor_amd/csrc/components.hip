@@ -5,12 +5,13 @@
 // The unit of work is the X-RUN, a maximal run of set bits in a row, never the voxel.  Run ids are handed out in raster order
 // (exclusive scan of the runs per row), every run starts as its own tree (linked to its first neighbour in the row above, which
 // needs no atomic), overlapping runs of neighbouring rows are united by hooking the larger root under the smaller one with
-// atomicMin, and the trees are flattened in a launch of their own.  A root is the smallest run id of its component = the
+// a compare-and-swap, and the trees are flattened in a launch of their own.  A root is the smallest run id of its component = the
 // component's first run in raster order, so numbering the roots with a scan IS scipy's numbering, whatever the schedule did.
 // Sizes are integer atomics per component.  Nothing here holds a per-voxel array except tomo_cc_expand's output.
 //
-// Termination: parent[r] <= r always and a parent only ever decreases (atomicMin, or a store of a smaller ancestor); cc_find
-// follows strictly decreasing ids; every turn of cc_union's loop that does not end it lowers a + b.  No kernel waits for
+// Termination: parent[r] <= r always and a parent only ever decreases (the swap of a root, atomicMin or a store of a smaller
+// ancestor); cc_find follows strictly decreasing ids; a turn of cc_union's loop that does not end it has seen another thread
+// hook a root, which happens fewer times than there are runs.  No kernel waits for
 // another workgroup: the phases are separate launches.
 //
 // The vocabulary of the run tables and the layout of tot are in cc_runs.h; what is measured per component on these tables
