@@ -375,6 +375,35 @@ def test_first_touch_numbering_on_noise(dev):
         assert np.array_equal(f.cpu().numpy(), d[name + "_faces"])
 
 
+@pytest.mark.parametrize("shape", [(2, 2, 40), (3, 4, 300), (3, 3, 600)])
+def test_list_lookup_at_segment_and_volume_borders(dev, shape):
+    """The one list lookup behind both marching-cubes chains (csrc/mc.hip: segment address + ballot rank, the edge-owner
+    table) at its corners.  Segment s covers float columns [256 s - 224, 256 s + 32): (2, 2, 40) is one cell layer -- every
+    +y / +z owner lies on the last row / slice -- across the first segment boundary X = 32; (3, 4, 300) crosses X = 32 and
+    X = 288, so an owner (y+1, x+1) sits in the next segment; (3, 3, 600) has three segments per row, with lanes 0 and 63
+    and all four k populated.  Noise at 0.5 hits every MC33 case and centre vertices.  Both chains equal the oracle bit for
+    bit, and neither counts a triangle corner without a vertex."""
+    rng = np.random.default_rng(sum(shape))
+    mask = rng.random(shape) < 0.5
+    vol = mask.astype(np.float32)
+    # manifold=False passes (list / eval / emit / first_touch): skimage's own numbering
+    mesh = pipeline.marching_cubes(pipeline.field_from_dense(torch.from_numpy(vol).to(dev)), 0.5)
+    v, f = pipeline.first_touch_order(mesh)
+    ev, ef = O.marching_cubes(vol, 0.5)
+    assert v.cpu().numpy().tobytes() == ev.tobytes()
+    assert np.array_equal(f.cpu().numpy(), ef)
+    assert int(mesh._stats[7].item()) == 0                     # totals[3] of emit and first_touch
+    # the mc3 chain
+    depths = np.full(shape[0], 0.5)
+    ev, ef = O.SurfaceExtractor().extract_manifold_surface(mask, depths, 0.7, 0.9)
+    got = pipeline.extract_surface(to_vol(mask, dev), depths, 0.7, 0.9)
+    assert got[0].cpu().numpy().tobytes() == ev.tobytes() and np.array_equal(got[1].cpu().numpy(), ef)
+    # the same pass again, with its counters
+    m = pipeline.mc3_vertices(pipeline.make_field(to_vol(mask, dev), sparse=pipeline.FIELD_SPARSE), depths, 0.7, 0.9)
+    assert torch.equal(m.uniq, got[0]) and torch.equal(m.faces_final, got[1])
+    assert int(m.tot[6].item()) == 0                           # corners without vertex
+
+
 def test_mc_none_cases(dev):
     z = torch.zeros((4, 5, 6), device=dev)
     assert pipeline.marching_cubes(pipeline.field_from_dense(z), 0.5) is None

@@ -63,6 +63,93 @@ __device__ static inline u64 make_key(int64_t row, int X, int slot)
 {
     return ((u64)row << (KEY_XBITS + 2)) | ((u64)(u32)X << 2) | (u64)slot;
 }
+__device__ static inline int64_t key_row(u64 key) { return (int64_t)(key >> (KEY_XBITS + 2)); }
+__device__ static inline int key_x(u64 key) { return (int)((u32)(key >> 2) & ((1u << KEY_XBITS) - 1u)); }
+
+// ------------------------------------------------------------------------------------------ the active-voxel list
+// THE list invariant.  Segment number row * segs_per_row + s holds the voxels of row `row` (= Z * Ny + Y) whose shifted
+// column cc = X + xorg + SEG_SHIFT has cc >> 8 == s; voxel cc is lane L = (cc & 255) >> 2, element k = cc & 3 of it, and is
+// active iff bit L of the segment's ballot k is set (one Rec4 per NON-EMPTY segment, written by pass 1; the record of an
+// empty segment is never written and never trusted).  The list holds the active voxels segment by segment and, inside a
+// segment, LANES ASCENDING, THEN k = 0..3 WITHIN A LANE:
+//     list position of a voxel = offset of its segment + its rank among the set bits of the four ballots in that order
+// -- two dependent loads and a few popcounts instead of a binary search over vox_key.  seg_write_keys is the only writer
+// of the order (both list kernels), seg_of_key + seg_rank the only reader (find_vertex, emit, far_owner_positions).
+struct Rec4 { u64 b[4]; };
+
+__device__ static inline Rec4 load_rec(const u64 *__restrict__ signs, int64_t idx)
+{
+    const ulonglong2 *q = (const ulonglong2 *)(signs + idx * 4);
+    ulonglong2 lo = q[0], hi = q[1];
+    Rec4 r; r.b[0] = lo.x; r.b[1] = lo.y; r.b[2] = hi.x; r.b[3] = hi.y;
+    return r;
+}
+
+// the writer: the keys of non-empty segment `seg` into vox_key[o ...]
+__device__ static inline void seg_write_keys(const McGrid &g, int64_t seg, const u64 *__restrict__ seg_act, u32 o, u64 *__restrict__ vox_key)
+{
+    int64_t row;
+    const int s = divmod_pos(seg, g.segs_per_row, &row);
+    const Rec4 r = load_rec(seg_act, seg);
+    const int Xs = s * SEG - SEG_SHIFT - g.xorg;
+    u64 any = r.b[0] | r.b[1] | r.b[2] | r.b[3];
+    while (any) {                                   // lanes (groups of 4 voxels) that hold an active voxel, ascending
+        const int L = __ffsll((long long)any) - 1;
+        any &= any - 1;
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if ((r.b[k] >> L) & 1ull) vox_key[o++] = make_key(row, Xs + 4 * L + k, 0);
+    }
+}
+
+// the address: segment number of a voxel key, and its shifted column
+__device__ static inline u64 seg_of_key(u64 key, const McGrid &g, u32 &cc)
+{
+    cc = (u32)key_x(key) + (u32)g.xorg + SEG_SHIFT;
+    return (u64)key_row(key) * (u64)g.segs_per_row + (cc >> 8);
+}
+
+// the reader: is voxel cc of the segment with record r in the list, and its rank inside the segment.  (The record by value
+// and its words copied out: on a reference into an array of records the optimizer folds the select of word k into one load
+// at a run-time address, and the whole array stays in scratch memory -- 176 B per lane in mc_emit_kernel.)
+__device__ static inline bool seg_rank(const Rec4 r, u32 cc, u32 &rank)
+{
+    const int L = (int)((cc & 255u) >> 2), k = (int)(cc & 3u);
+    const u64 b0 = r.b[0], b1 = r.b[1], b2 = r.b[2], b3 = r.b[3];
+    const u64 bk = k == 0 ? b0 : (k == 1 ? b1 : (k == 2 ? b2 : b3));
+    const u64 m = (1ull << L) - 1ull;                             // the lanes below
+    rank = (u32)(__popcll(b0 & m) + __popcll(b1 & m) + __popcll(b2 & m) + __popcll(b3 & m));
+    rank += (k > 0 ? (u32)((b0 >> L) & 1ull) : 0u) + (k > 1 ? (u32)((b1 >> L) & 1ull) : 0u) + (k > 2 ? (u32)((b2 >> L) & 1ull) : 0u);
+    return (bk >> L) & 1ull;
+}
+
+// ------------------------------------------------------------------------------------------ the cube's edge owners
+// THE table of who owns the vertex on each cube edge (Lewiner numbering, 12 = the cell-centre vertex).  Owner voxels by
+// offset (dz, dy, dx) from the cell's own voxel: the first two are found without a lookup (this list entry; the next one,
+// if that is (x+1) at all), the other five cost one segment-ballot lookup each.  Edges: E(edge, owner, slot).
+#define MC_NEAR_OWNERS(O) O(0, 0, 0, 0) O(1, 0, 0, 1)
+#define MC_FAR_OWNERS(O) O(2, 0, 1, 0) O(3, 1, 0, 0) O(4, 0, 1, 1) O(5, 1, 0, 1) O(6, 1, 1, 0)
+#define MC_EDGES(E)                                                                                                       \
+    E(0, 0, 0) E(1, 1, 1) E(2, 2, 0) E(3, 0, 1) E(4, 3, 0) E(5, 5, 1) E(6, 6, 0) E(7, 3, 1) E(8, 0, 2) E(9, 1, 2) E(10, 4, 2)  \
+    E(11, 2, 2) E(12, 0, 3)
+
+// masks over the 13 edges, all compile-time constants: the edges of owner n, the edges whose owner is displaced along
+// axis a (0 = x, 1 = y, 2 = z), the edges whose slot has bit b set
+#define MC_E_OF_OWNER(e, o, sl) | ((o) == n ? 1u << (e) : 0u)
+#define MC_O_DISPLACED(o, dz, dy, dx) | (((((dz) << 2 | (dy) << 1 | (dx)) >> a) & 1) ? mc_owner_edges(o) : 0u)
+#define MC_E_SLOT_BIT(e, o, sl) | ((((u32)(sl) >> b) & 1u) << (e))
+__host__ __device__ constexpr u32 mc_owner_edges(int n) { return 0u MC_EDGES(MC_E_OF_OWNER); }
+__host__ __device__ constexpr u32 mc_edges_displaced(int a) { return 0u MC_NEAR_OWNERS(MC_O_DISPLACED) MC_FAR_OWNERS(MC_O_DISPLACED); }
+__host__ __device__ constexpr u32 mc_edges_slot_bit(int b) { return 0u MC_EDGES(MC_E_SLOT_BIT); }
+
+// the cube edges 0..11 that carry a vertex: every MC33 tiling uses exactly the bichromatic edges of its cube
+__host__ __device__ static inline u32 mc_used_edges(int index)
+{
+#define MC_BI(e, a, b) ((u32)(((index >> (a)) ^ (index >> (b))) & 1) << (e))      // edge e joins corners a and b
+    return MC_BI(0, 0, 1) | MC_BI(1, 1, 2) | MC_BI(2, 2, 3) | MC_BI(3, 3, 0) | MC_BI(4, 4, 5) | MC_BI(5, 5, 6) | MC_BI(6, 6, 7) |
+           MC_BI(7, 7, 4) | MC_BI(8, 0, 4) | MC_BI(9, 1, 5) | MC_BI(10, 2, 6) | MC_BI(11, 3, 7);
+#undef MC_BI
+}
 
 // ------------------------------------------------------------------------------------------ pass 1
 // Sign records: for every (slice Z, segment s, row Y) four 64-bit words, bit L of word k = [field > iso] at
@@ -98,16 +185,6 @@ __global__ __launch_bounds__(256) void field_signs_kernel(const float *__restric
 // Every segment gets its number of active voxels in seg_cnt (what the scan reads: 4 B instead of 32 B per segment);
 // the four ballots of a NON-EMPTY segment go, as one aligned 32-byte record, into seg_act (other records stay unwritten
 // and are never read).
-struct Rec4 { u64 b[4]; };
-
-__device__ static inline Rec4 load_rec(const u64 *__restrict__ signs, int64_t idx)
-{
-    const ulonglong2 *q = (const ulonglong2 *)(signs + idx * 4);
-    ulonglong2 lo = q[0], hi = q[1];
-    Rec4 r; r.b[0] = lo.x; r.b[1] = lo.y; r.b[2] = hi.x; r.b[3] = hi.y;
-    return r;
-}
-
 __device__ static inline Rec4 rec_of(const u64 *__restrict__ signs, int64_t idx, int gc)
 {   // record idx of a group of class gc: all zero / all one without touching memory, or the stored record
     if (gc == 2) return load_rec(signs, idx);
@@ -187,21 +264,29 @@ __global__ __launch_bounds__(256) void mc_classify_bits_kernel(const u64 *__rest
     }
 }
 
-static inline int make_grid(McGrid &g, const float *field, int Nz, int Ny, int Nx, int64_t pitch, int xorg, double iso)
+// the grid of the passes that index voxels, segments and keys but never read the field
+static int index_grid(McGrid &g, int Nz, int Ny, int Nx, int xorg)
 {
-    if (!field || Nz < 2 || Ny < 2 || Nx < 2 || pitch < Nx + xorg) return TOMO_E_ARG;
+    if (Nz < 2 || Ny < 2 || Nx < 2) return TOMO_E_ARG;
     if (Nx >= (1 << KEY_XBITS)) return TOMO_E_SIZE;
-    g.Nz = Nz; g.Ny = Ny; g.Nx = Nx; g.pitch = pitch; g.xorg = xorg; g.iso = iso;
+    g.Nz = Nz; g.Ny = Ny; g.Nx = Nx; g.pitch = 0; g.xorg = xorg; g.iso = 0.0;
     g.segs_per_row = (int)tomo_mc_segments_per_row(Nx, xorg);
     return TOMO_OK;
+}
+
+static int make_grid(McGrid &g, const float *field, int Nz, int Ny, int Nx, int64_t pitch, int xorg, double iso)
+{
+    if (!field || pitch < Nx + xorg) return TOMO_E_ARG;
+    const int rc = index_grid(g, Nz, Ny, Nx, xorg);
+    g.pitch = pitch; g.iso = iso;
+    return rc;
 }
 
 TOMO_API int tomo_field_signs(const float *field, int Nz, int Ny, int Nx, int64_t pitch, int xorg, double iso,
                               int z_begin, int z_end, unsigned long long *signs, uint8_t *gcls, void *stream)
 {
     McGrid g;
-    int rc = make_grid(g, field, Nz, Ny, Nx, pitch, xorg, iso);
-    if (rc) return rc;
+    if (const int rc = make_grid(g, field, Nz, Ny, Nx, pitch, xorg, iso)) return rc;
     if (!signs || !gcls || z_begin < 0 || z_end > Nz || z_begin > z_end) return TOMO_E_ARG;
     {   // every group of these slices has stored records
         const int64_t per_slice = (tomo_sign_rows(Ny) >> 4) * g.segs_per_row;
@@ -221,10 +306,9 @@ TOMO_API int tomo_field_signs(const float *field, int Nz, int Ny, int Nx, int64_
 TOMO_API int tomo_mc_classify(const unsigned long long *signs, const uint8_t *gcls, int Nz, int Ny, int Nx, int xorg,
                               unsigned long long *seg_act, uint32_t *seg_cnt, void *stream)
 {
-    if (!signs || !gcls || !seg_act || !seg_cnt || Nz < 2 || Ny < 2 || Nx < 2) return TOMO_E_ARG;
-    if (Nx >= (1 << KEY_XBITS)) return TOMO_E_SIZE;
-    McGrid g; g.Nz = Nz; g.Ny = Ny; g.Nx = Nx; g.pitch = 0; g.xorg = xorg; g.iso = 0.0;
-    g.segs_per_row = (int)tomo_mc_segments_per_row(Nx, xorg);
+    if (!signs || !gcls || !seg_act || !seg_cnt) return TOMO_E_ARG;
+    McGrid g;
+    if (const int rc = index_grid(g, Nz, Ny, Nx, xorg)) return rc;
     int64_t nseg = (int64_t)Nz * Ny * g.segs_per_row;
     int64_t blocks = ceil_div64(nseg, 256);
     if (blocks > 0x7fffffff) return TOMO_E_SIZE;
@@ -313,7 +397,7 @@ TOMO_API int tomo_mc_scan_segments(const uint32_t *seg_cnt, int64_t nseg, uint32
 
 // ------------------------------------------------------------------------------------------ pass 2
 // one LANE per segment; the non-empty ones (consecutive lanes write consecutive ranges of vox_key) expand the four
-// ballots written by pass 1 into voxel keys, in x order
+// ballots written by pass 1 into voxel keys
 __global__ __launch_bounds__(256) void mc_list_kernel(const McGrid g, const u32 *__restrict__ seg_aoff,
                                                       const u64 *__restrict__ seg_act, int64_t nseg,
                                                       u64 *__restrict__ vox_key, u32 cap)
@@ -322,27 +406,22 @@ __global__ __launch_bounds__(256) void mc_list_kernel(const McGrid g, const u32 
     if (seg >= nseg) return;
     if (seg_aoff[seg + 1] == seg_aoff[seg]) return;             // empty: its ballot record was never written
     if (seg_aoff[seg + 1] > cap) return;                        // (capped call) the list is longer than the buffer: the caller redoes it
-    int64_t row;
-    int s = divmod_pos(seg, g.segs_per_row, &row);
-    const ulonglong2 *q = (const ulonglong2 *)(seg_act + seg * 4);
-    ulonglong2 lo = q[0], hi = q[1];
-    u64 b0 = lo.x, b1 = lo.y, b2 = hi.x, b3 = hi.y;
-    u32 o = seg_aoff[seg];
-    const int Xs = s * SEG - SEG_SHIFT - g.xorg;
-    u64 any = b0 | b1 | b2 | b3;
-    while (any) {                                   // lanes (groups of 4 voxels) that hold an active voxel, ascending
-        int L = __ffsll((long long)any) - 1;
-        any &= any - 1;
-        int X0 = Xs + 4 * L;
-        if ((b0 >> L) & 1ull) vox_key[o++] = make_key(row, X0, 0);
-        if ((b1 >> L) & 1ull) vox_key[o++] = make_key(row, X0 + 1, 0);
-        if ((b2 >> L) & 1ull) vox_key[o++] = make_key(row, X0 + 2, 0);
-        if ((b3 >> L) & 1ull) vox_key[o++] = make_key(row, X0 + 3, 0);
-    }
+    seg_write_keys(g, seg, seg_act, seg_aoff[seg], vox_key);
 }
 
 static int mc_list_launch(int Nz, int Ny, int Nx, int xorg, const uint32_t *seg_aoff, const unsigned long long *seg_act,
-                          unsigned long long *vox_key, u32 cap, void *stream);
+                          unsigned long long *vox_key, u32 cap, void *stream)
+{
+    if (!seg_aoff || !seg_act || !vox_key) return TOMO_E_ARG;
+    McGrid g;
+    if (const int rc = index_grid(g, Nz, Ny, Nx, xorg)) return rc;
+    const int64_t nseg = (int64_t)Nz * Ny * g.segs_per_row;
+    int64_t blocks = ceil_div64(nseg, 256);
+    if (blocks > 0x7fffffff) return TOMO_E_SIZE;
+    hipLaunchKernelGGL(mc_list_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g, seg_aoff,
+                       (const u64 *)seg_act, nseg, (u64 *)vox_key, cap);
+    return tomo_status();
+}
 
 TOMO_API int tomo_mc_list(int Nz, int Ny, int Nx, int xorg, const uint32_t *seg_aoff, const unsigned long long *seg_act,
                           unsigned long long *vox_key, void *stream)
@@ -359,20 +438,6 @@ TOMO_API int tomo_mc_list_capped(int Nz, int Ny, int Nx, int xorg, const uint32_
     return mc_list_launch(Nz, Ny, Nx, xorg, seg_aoff, seg_act, vox_key, (u32)cap, stream);
 }
 
-static int mc_list_launch(int Nz, int Ny, int Nx, int xorg, const uint32_t *seg_aoff, const unsigned long long *seg_act,
-                          unsigned long long *vox_key, u32 cap, void *stream)
-{
-    if (Nz < 2 || Ny < 2 || Nx < 2 || !seg_aoff || !seg_act || !vox_key) return TOMO_E_ARG;
-    McGrid g; g.Nz = Nz; g.Ny = Ny; g.Nx = Nx; g.pitch = 0; g.xorg = xorg; g.iso = 0.0;
-    g.segs_per_row = (int)tomo_mc_segments_per_row(Nx, xorg);
-    const int64_t nseg = (int64_t)Nz * Ny * g.segs_per_row;
-    int64_t blocks = ceil_div64(nseg, 256);
-    if (blocks > 0x7fffffff) return TOMO_E_SIZE;
-    hipLaunchKernelGGL(mc_list_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g, seg_aoff,
-                       (const u64 *)seg_act, nseg, (u64 *)vox_key, cap);
-    return tomo_status();
-}
-
 // ------------------------------------------------------------------------------------------ pass 3 / 4
 struct Cell {
     double v[8];       // corner values minus iso, Lewiner order
@@ -385,8 +450,8 @@ struct Cell {
 
 __device__ static inline void load_cell(const float *__restrict__ field, const McGrid &g, u64 key, Cell &c)
 {
-    c.row = (int64_t)(key >> (KEY_XBITS + 2));
-    c.X = (int)((key >> 2) & ((1u << KEY_XBITS) - 1u));
+    c.row = key_row(key);
+    c.X = key_x(key);
     int64_t zq;
     c.Y = divmod_pos(c.row, g.Ny, &zq);
     c.Z = (int)zq;
@@ -449,7 +514,18 @@ __global__ __launch_bounds__(256) void mc_eval_kernel(const float *__restrict__ 
 
 static int mc_eval_launch(const float *field, int Nz, int Ny, int Nx, int64_t pitch, int xorg, double iso,
                           const unsigned long long *vox_key, int64_t na, uint32_t *vox_counts, uint8_t *vox_flags,
-                          const unsigned long long *na_dev, void *stream);
+                          const unsigned long long *na_dev, void *stream)
+{
+    McGrid g;
+    if (const int rc = make_grid(g, field, Nz, Ny, Nx, pitch, xorg, iso)) return rc;
+    if (!vox_key || !vox_counts || !vox_flags) return TOMO_E_ARG;
+    if (na <= 0) return TOMO_OK;
+    int64_t blocks = ceil_div64(na, 256);
+    if (blocks > 0x7fffffff) return TOMO_E_SIZE;
+    hipLaunchKernelGGL(mc_eval_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, field, g,
+                       (const u64 *)vox_key, na, vox_counts, vox_flags, (const u64 *)na_dev);
+    return tomo_status();
+}
 
 TOMO_API int tomo_mc_eval(const float *field, int Nz, int Ny, int Nx, int64_t pitch, int xorg, double iso,
                           const unsigned long long *vox_key, int64_t na, uint32_t *vox_counts, uint8_t *vox_flags,
@@ -468,52 +544,51 @@ TOMO_API int tomo_mc_eval_capped(const float *field, int Nz, int Ny, int Nx, int
     return mc_eval_launch(field, Nz, Ny, Nx, pitch, xorg, iso, vox_key, cap, vox_counts, vox_flags, na_dev, stream);
 }
 
-static int mc_eval_launch(const float *field, int Nz, int Ny, int Nx, int64_t pitch, int xorg, double iso,
-                          const unsigned long long *vox_key, int64_t na, uint32_t *vox_counts, uint8_t *vox_flags,
-                          const unsigned long long *na_dev, void *stream)
-{
-    McGrid g;
-    int rc = make_grid(g, field, Nz, Ny, Nx, pitch, xorg, iso);
-    if (rc) return rc;
-    if (!vox_key || !vox_counts || !vox_flags) return TOMO_E_ARG;
-    if (na <= 0) return TOMO_OK;
-    int64_t blocks = ceil_div64(na, 256);
-    if (blocks > 0x7fffffff) return TOMO_E_SIZE;
-    hipLaunchKernelGGL(mc_eval_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, field, g,
-                       (const u64 *)vox_key, na, vox_counts, vox_flags, (const u64 *)na_dev);
-    return tomo_status();
-}
-
-// index of the vertex (owner voxel key, slot).  The owner's position in the active-voxel list is its segment's offset
-// plus its rank among the set bits of the segment's four ballots (list order: lanes ascending, k ascending within a lane,
-// see mc_list_kernel) -- two independent loads and a few popcounts instead of a binary search over vox_key.
-__device__ static inline u32 find_vertex(u64 okey, int slot, const McGrid &g, const u64 *__restrict__ seg_act,
-                                         const u32 *__restrict__ seg_aoff, const u32 *__restrict__ vox_voff,
-                                         const uint8_t *__restrict__ vox_flags)
-{
-    const u64 row = okey >> (KEY_XBITS + 2);
-    const u32 c = ((u32)(okey >> 2) & ((1u << KEY_XBITS) - 1u)) + (u32)g.xorg + SEG_SHIFT;      // float column + shift
-    const u64 seg = row * (u64)g.segs_per_row + (c >> 8);
-    const u32 a0 = seg_aoff[seg], a1 = seg_aoff[seg + 1];
-    if (a1 == a0) return 0xffffffffu;                    // empty segment: its ballot record was never written
-    const Rec4 r = load_rec(seg_act, (int64_t)seg);
-    const int L = (int)((c & 255u) >> 2), k = (int)(c & 3u);
-    const u64 bk = k == 0 ? r.b[0] : (k == 1 ? r.b[1] : (k == 2 ? r.b[2] : r.b[3]));
-    if (!((bk >> L) & 1ull)) return 0xffffffffu;
-    const u64 m = (1ull << L) - 1ull;
-    u32 rank = (u32)(__popcll(r.b[0] & m) + __popcll(r.b[1] & m) + __popcll(r.b[2] & m) + __popcll(r.b[3] & m));
-    rank += (k > 0 ? (u32)((r.b[0] >> L) & 1ull) : 0u) + (k > 1 ? (u32)((r.b[1] >> L) & 1ull) : 0u) +
-            (k > 2 ? (u32)((r.b[2] >> L) & 1ull) : 0u);
-    const u32 pos = a0 + rank;
-    const u32 fl = vox_flags[pos];
-    if (!(fl & (1u << slot))) return 0xffffffffu;
-    return vox_voff[pos] + (u32)__popc(fl & ((1u << slot) - 1u));
-}
-
 __device__ static inline u32 slot_vertex(u32 base, u32 flags, int slot)
 {   // index of the vertex in `slot` of a voxel whose first vertex is `base`, 0xffffffff if it has none there
     if (base == 0xffffffffu || !(flags & (1u << slot))) return 0xffffffffu;
     return base + (u32)__popc(flags & ((1u << slot) - 1u));
+}
+
+// index of the vertex (owner voxel key, slot): one list lookup
+__device__ static inline u32 find_vertex(u64 okey, int slot, const McGrid &g, const u64 *__restrict__ seg_act,
+                                         const u32 *__restrict__ seg_aoff, const u32 *__restrict__ vox_voff,
+                                         const uint8_t *__restrict__ vox_flags)
+{
+    u32 cc, rank;
+    const u64 seg = seg_of_key(okey, g, cc);
+    const u32 a0 = seg_aoff[seg], a1 = seg_aoff[seg + 1];
+    if (a1 == a0) return 0xffffffffu;                    // empty segment: its ballot record was never written
+    const Rec4 r = load_rec(seg_act, (int64_t)seg);
+    if (!seg_rank(r, cc, rank)) return 0xffffffffu;
+    return slot_vertex(vox_voff[a0 + rank], vox_flags[a0 + rank], slot);
+}
+
+// List positions of the five far owners of list entry i (voxel `key`): pos[n] and have[n] for n = 2..6, have[n] only if one
+// of the owner's edges is in `used` and the owner is in the list.  A lookup is a chain of dependent loads (segment offsets
+// -> ballot record -> what the caller keeps per list position); run as straight-line code in phases, all five in flight per
+// phase, instead of five branches that each serialise their own chain.
+// A lookup that is not needed (edge not bichromatic) goes to this voxel's own key: always a valid address.
+__device__ static inline void far_owner_positions(const McGrid &g, u64 key, u32 used, u32 i, const u64 *__restrict__ seg_act,
+                                                  const u32 *__restrict__ seg_aoff, u32 pos[7], bool have[7])
+{
+    const int64_t row = key_row(key), rowY = (int64_t)g.Ny;
+    const int X = key_x(key);
+#define MC_ADDR(n, dz, dy, dx)                                                                                            \
+    const bool need##n = (used & mc_owner_edges(n)) != 0;                                                                 \
+    u32 cc##n;                                                                                                            \
+    const u64 seg##n = seg_of_key(need##n ? make_key(row + dy + dz * rowY, X + dx, 0) : key, g, cc##n);                   \
+    const u32x2u aa##n = *(const u32x2u *)(seg_aoff + seg##n);      /* (offset, next offset): one 8-byte, 4-byte aligned load */
+#define MC_REC(n, dz, dy, dx) const Rec4 rec##n = load_rec(seg_act, (int64_t)seg##n);     /* garbage for an empty segment: masked below */
+#define MC_RANK(n, dz, dy, dx)                                                                                            \
+    u32 rank##n;                                                                                                          \
+    const bool listed##n = seg_rank(rec##n, cc##n, rank##n);                                                              \
+    have[n] = need##n && aa##n.x != aa##n.y && listed##n;                                                                 \
+    pos[n] = have[n] ? aa##n.x + rank##n : i;
+    MC_FAR_OWNERS(MC_ADDR) MC_FAR_OWNERS(MC_REC) MC_FAR_OWNERS(MC_RANK)
+#undef MC_ADDR
+#undef MC_REC
+#undef MC_RANK
 }
 
 __global__ __launch_bounds__(256) void mc_emit_kernel(const float *__restrict__ field, const McGrid g,
@@ -561,40 +636,31 @@ __global__ __launch_bounds__(256) void mc_emit_kernel(const float *__restrict__ 
     }
     if (!(c.cell_ok && c.index != 0 && c.index != 255)) return;
     u32 fo = vox_foff[i];
-    const int64_t rowY = (int64_t)g.Ny;
-    // Vertex index of every cube edge that carries one (the edge is bichromatic), ONE list lookup per owner voxel:
-    // edges 1,9 belong to voxel (x+1,y,z), 2,11 to (x,y+1,z), 4,7 to (x,y,z+1), 10 / 5 / 6 to the three diagonal ones.
-    const int ix = c.index;
-#define BICH(a, b) ((((ix >> (a)) ^ (ix >> (b))) & 1) != 0)
-    const bool e1 = BICH(1, 2), e2 = BICH(2, 3), e4 = BICH(4, 5), e5 = BICH(5, 6), e6 = BICH(6, 7), e7 = BICH(7, 4);
-    const bool e9 = BICH(1, 5), e10 = BICH(2, 6), e11 = BICH(3, 7);
-#undef BICH
-    u32 id[13];
-    id[0] = slot_vertex(vox_voff[i], (u32)flags, 0);
-    id[3] = slot_vertex(vox_voff[i], (u32)flags, 1);
-    id[8] = slot_vertex(vox_voff[i], (u32)flags, 2);
-    id[12] = slot_vertex(vox_voff[i], (u32)flags, 3);
+    // Vertex index of every cube edge that carries one (the edge is bichromatic), ONE list position per owner voxel
+    const u32 used = mc_used_edges(c.index);
+    u32 fl[7], base[7];                       // flags and first vertex of the seven owners (MC_NEAR_OWNERS, MC_FAR_OWNERS)
+    fl[0] = (u32)flags;
+    base[0] = vox_voff[i];
     {   // (x+1, y, z): the next entry of the list if it is active at all (coalesced loads)
         const int64_t in = i + 1 < na ? i + 1 : i;
         const u64 kn = vox_key[in];
-        u32 base = vox_voff[in], fl = vox_flags[in];
-        if (!((e1 || e9) && kn == key + 4ull)) { base = 0xffffffffu; fl = 0; }
-        id[1] = slot_vertex(base, fl, 1); id[9] = slot_vertex(base, fl, 2);
+        fl[1] = vox_flags[in];
+        base[1] = vox_voff[in];
+        if (!((used & mc_owner_edges(1)) != 0 && kn == key + 4ull)) { base[1] = 0xffffffffu; fl[1] = 0; }
     }
-    {   // The five other owner voxels: (y+1), (z+1), (y+1,x+1), (z+1,x+1), (y+1,z+1).  Their lookups are three dependent
-        // loads each (segment offsets -> ballot record -> flags / vertex base); run as straight-line code in three
-        // phases, all five in flight per phase, instead of five branches that each serialise their own chain.
-        // A lookup that is not needed (edge not bichromatic) goes to this voxel's own key: always a valid address.
-        const bool need[5] = {e2 || e11, e4 || e7, e10, e5, e6};
-        const u64 okey[5] = {make_key(c.row + 1, c.X, 0), make_key(c.row + rowY, c.X, 0), make_key(c.row + 1, c.X + 1, 0),
-                             make_key(c.row + rowY, c.X + 1, 0), make_key(c.row + 1 + rowY, c.X, 0)};
+    {   // The five far owners: the phases of far_owner_positions as loops over arrays, then flags / vertex base.  (Each of the
+        // two kernels keeps its 5 waves per SIMD only in its own form: that function costs 97 VGPRs here, these loops 98 there.)
+#define MC_NEED(n, dz, dy, dx) (used & mc_owner_edges(n)) != 0,
+#define MC_OKEY(n, dz, dy, dx) make_key(c.row + dy + dz * (int64_t)g.Ny, c.X + dx, 0),
+        const bool need[5] = {MC_FAR_OWNERS(MC_NEED)};
+        const u64 okey[5] = {MC_FAR_OWNERS(MC_OKEY)};
+#undef MC_NEED
+#undef MC_OKEY
         u64 seg[5];
         u32 cc[5], a0[5], a1[5];
 #pragma unroll
         for (int n = 0; n < 5; n++) {
-            const u64 k = need[n] ? okey[n] : key;
-            cc[n] = ((u32)(k >> 2) & ((1u << KEY_XBITS) - 1u)) + (u32)g.xorg + SEG_SHIFT;
-            seg[n] = (k >> (KEY_XBITS + 2)) * (u64)g.segs_per_row + (cc[n] >> 8);
+            seg[n] = seg_of_key(need[n] ? okey[n] : key, g, cc[n]);
             a0[n] = seg_aoff[seg[n]];
             a1[n] = seg_aoff[seg[n] + 1];
         }
@@ -605,27 +671,20 @@ __global__ __launch_bounds__(256) void mc_emit_kernel(const float *__restrict__ 
         bool have[5];
 #pragma unroll
         for (int n = 0; n < 5; n++) {
-            const Rec4 &r = rec[n];
-            const int L = (int)((cc[n] & 255u) >> 2), k = (int)(cc[n] & 3u);
-            const u64 bk = k == 0 ? r.b[0] : (k == 1 ? r.b[1] : (k == 2 ? r.b[2] : r.b[3]));
-            const u64 m = (1ull << L) - 1ull;
-            u32 rank = (u32)(__popcll(r.b[0] & m) + __popcll(r.b[1] & m) + __popcll(r.b[2] & m) + __popcll(r.b[3] & m));
-            rank += (k > 0 ? (u32)((r.b[0] >> L) & 1ull) : 0u) + (k > 1 ? (u32)((r.b[1] >> L) & 1ull) : 0u) +
-                    (k > 2 ? (u32)((r.b[2] >> L) & 1ull) : 0u);
-            have[n] = need[n] && a1[n] != a0[n] && ((bk >> L) & 1ull);
+            u32 rank;
+            const bool listed = seg_rank(rec[n], cc[n], rank);
+            have[n] = need[n] && a1[n] != a0[n] && listed;
             pos[n] = have[n] ? a0[n] + rank : (u32)i;
         }
-        u32 fl[5], base[5];
 #pragma unroll
-        for (int n = 0; n < 5; n++) { fl[n] = vox_flags[pos[n]]; base[n] = vox_voff[pos[n]]; }
+        for (int n = 0; n < 5; n++) { fl[2 + n] = vox_flags[pos[n]]; base[2 + n] = vox_voff[pos[n]]; }
 #pragma unroll
-        for (int n = 0; n < 5; n++) if (!have[n]) { fl[n] = 0; base[n] = 0xffffffffu; }
-        id[2] = slot_vertex(base[0], fl[0], 0); id[11] = slot_vertex(base[0], fl[0], 2);
-        id[4] = slot_vertex(base[1], fl[1], 0); id[7] = slot_vertex(base[1], fl[1], 1);
-        id[10] = slot_vertex(base[2], fl[2], 2);
-        id[5] = slot_vertex(base[3], fl[3], 1);
-        id[6] = slot_vertex(base[4], fl[4], 0);
+        for (int n = 0; n < 5; n++) if (!have[n]) { fl[2 + n] = 0; base[2 + n] = 0xffffffffu; }
     }
+    u32 id[13];
+#define MC_E(e, o, sl) id[e] = slot_vertex(base[o], fl[o], sl);
+    MC_EDGES(MC_E)
+#undef MC_E
     // the tiling (table walks, the ambiguity tests) after the lookups were issued: their latency hides behind it
     McTiling t = mc_cell_tiling(c.v, c.index);
     bool bad = false;
@@ -654,8 +713,7 @@ TOMO_API int tomo_mc_emit(const float *field, int Nz, int Ny, int Nx, int64_t pi
                           unsigned long long *totals, void *stream)
 {
     McGrid g;
-    int rc = make_grid(g, field, Nz, Ny, Nx, pitch, xorg, iso);
-    if (rc) return rc;
+    if (const int rc = make_grid(g, field, Nz, Ny, Nx, pitch, xorg, iso)) return rc;
     if (!vox_key || !seg_act || !seg_aoff || !vox_voff || !vox_foff || !vox_flags || !vkey || !vpos || !faces || !totals)
         return TOMO_E_ARG;
     if (na <= 0) return TOMO_OK;
@@ -697,10 +755,10 @@ __global__ __launch_bounds__(256) void mc_first_touch_kernel(const float *__rest
             int ed = t.tris[k];
             if (seen & (1u << ed)) continue;
             seen |= 1u << ed;
-            int dx = (ed == 1 || ed == 5 || ed == 9 || ed == 10) ? 1 : 0;
-            int dy = (ed == 2 || ed == 6 || ed == 10 || ed == 11) ? 1 : 0;
-            int dz = (ed >= 4 && ed <= 7) ? 1 : 0;
-            int slot = ed == 12 ? 3 : (ed >= 8 ? 2 : (ed & 1));
+            // the edge's owner offset and slot (MC_EDGES), as bits of compile-time masks
+            const int dx = (mc_edges_displaced(0) >> ed) & 1, dy = (mc_edges_displaced(1) >> ed) & 1;
+            const int dz = (mc_edges_displaced(2) >> ed) & 1;
+            const int slot = ((mc_edges_slot_bit(0) >> ed) & 1) | ((mc_edges_slot_bit(1) >> ed) & 1) << 1;
             int ox = c.X + dx, oy = c.Y + dy, oz = c.Z + dz;
             bool creator;
             if (slot == 0) creator = (dy == (oy > 0 ? 1 : 0)) && (dz == (oz > 0 ? 1 : 0));
@@ -710,7 +768,7 @@ __global__ __launch_bounds__(256) void mc_first_touch_kernel(const float *__rest
             if (!creator) continue;
             if (mode == 1) {
                 u32 v;
-                if ((dx | dy | dz) == 0) v = (flags & (1 << slot)) ? vox_voff[i] + (u32)__popc(flags & ((1 << slot) - 1)) : 0xffffffffu;
+                if ((dx | dy | dz) == 0) v = slot_vertex(vox_voff[i], (u32)flags, slot);
                 else v = find_vertex(make_key(c.row + dy + dz * rowY, ox, 0), slot, g, seg_act, seg_aoff, vox_voff, vox_flags);
                 if (v == 0xffffffffu) atomicAdd(&totals[3], 1ull);
                 else ft_rank[v] = (int32_t)(base[i] + n);
@@ -728,8 +786,7 @@ TOMO_API int tomo_mc_first_touch(const float *field, int Nz, int Ny, int Nx, int
                                  const uint32_t *base, int32_t *ft_rank, unsigned long long *totals, void *stream)
 {
     McGrid g;
-    int rc = make_grid(g, field, Nz, Ny, Nx, pitch, xorg, iso);
-    if (rc) return rc;
+    if (const int rc = make_grid(g, field, Nz, Ny, Nx, pitch, xorg, iso)) return rc;
     if (!vox_key || !seg_act || !seg_aoff || !vox_voff || !vox_flags || !totals || (mode == 0 && !created) ||
         (mode == 1 && (!base || !ft_rank)) || (mode != 0 && mode != 1))
         return TOMO_E_ARG;
@@ -898,33 +955,17 @@ __global__ __launch_bounds__(MC3_BLK) void mc3_list_kernel(const McGrid g, const
         if (o <= cap) atomicOr((unsigned long long *)&tot[3], 1ull);
         return;
     }
-    int64_t row;
-    const int s = divmod_pos(seg, g.segs_per_row, &row);
-    const ulonglong2 *q = (const ulonglong2 *)(seg_act + seg * 4);
-    const ulonglong2 lo = q[0], hi = q[1];
-    const u64 b0 = lo.x, b1 = lo.y, b2 = hi.x, b3 = hi.y;
-    const int Xs = s * SEG - SEG_SHIFT - g.xorg;
-    u64 any = b0 | b1 | b2 | b3;
-    while (any) {
-        const int L = __ffsll((long long)any) - 1;
-        any &= any - 1;
-        const int X0 = Xs + 4 * L;
-        if ((b0 >> L) & 1ull) vox_key[o++] = make_key(row, X0, 0);
-        if ((b1 >> L) & 1ull) vox_key[o++] = make_key(row, X0 + 1, 0);
-        if ((b2 >> L) & 1ull) vox_key[o++] = make_key(row, X0 + 2, 0);
-        if ((b3 >> L) & 1ull) vox_key[o++] = make_key(row, X0 + 3, 0);
-    }
+    seg_write_keys(g, seg, seg_act, o, vox_key);
 }
 
 TOMO_API int tomo_mc3_list(int Nz, int Ny, int Nx, int xorg, const uint32_t *seg_cnt, const unsigned long long *seg_act,
                            uint32_t *seg_blk, uint32_t *seg_aoff, unsigned long long *vox_key, int64_t cap,
                            unsigned long long *tot, void *stream)
 {
-    if (Nz < 2 || Ny < 2 || Nx < 2 || !seg_cnt || !seg_act || !seg_blk || !seg_aoff || !vox_key || !tot) return TOMO_E_ARG;
+    if (!seg_cnt || !seg_act || !seg_blk || !seg_aoff || !vox_key || !tot) return TOMO_E_ARG;
+    McGrid g;
+    if (const int rc = index_grid(g, Nz, Ny, Nx, xorg)) return rc;
     if (cap <= 0 || cap >= 0x1fffffffll) return TOMO_E_SIZE;        // ids are 4 * position + slot in a signed 32-bit index
-    if (Nx >= (1 << KEY_XBITS)) return TOMO_E_SIZE;
-    McGrid g; g.Nz = Nz; g.Ny = Ny; g.Nx = Nx; g.pitch = 0; g.xorg = xorg; g.iso = 0.0;
-    g.segs_per_row = (int)tomo_mc_segments_per_row(Nx, xorg);
     const int64_t nseg = (int64_t)Nz * Ny * g.segs_per_row, nblk = ceil_div64(nseg, MC3_BLK);
     if (nblk > 0x7fffffff) return TOMO_E_SIZE;
     hipStream_t s = (hipStream_t)stream;
@@ -964,14 +1005,9 @@ __global__ __launch_bounds__(MC3_BLK) void mc3_eval_kernel(const float *__restri
             ntri = t.ntri;
             if (t.centre) c.flags |= 8;
             til = (int32_t)(((intptr_t)t.tris - (intptr_t)LUT_TILING1) * 16 + ntri);
-            // the cube edges that carry a vertex (every MC33 tiling uses exactly the bichromatic edges of its cube), bit 12: the
-            // centre vertex -- what the faces pass looks up, from the corner signs (a loop over the tiling row would do, but
-            // it sends the faces kernel's registers to scratch memory)
-            const int ix = c.index;
-#define BICH(a, b) ((u32)(((ix >> (a)) ^ (ix >> (b))) & 1))
-            used = BICH(0, 1) | BICH(1, 2) << 1 | BICH(2, 3) << 2 | BICH(3, 0) << 3 | BICH(4, 5) << 4 | BICH(5, 6) << 5 | BICH(6, 7) << 6 |
-                   BICH(7, 4) << 7 | BICH(0, 4) << 8 | BICH(1, 5) << 9 | BICH(2, 6) << 10 | BICH(3, 7) << 11 | (t.centre ? 1u << 12 : 0u);
-#undef BICH
+            // the cube edges that carry a vertex, bit 12: the centre vertex -- what the faces pass looks up, from the corner
+            // signs (a loop over the tiling row would do, but it sends the faces kernel's registers to scratch memory)
+            used = mc_used_edges(c.index) | (t.centre ? 1u << 12 : 0u);
             if (ntri == 0) used = 0;
         }
         const int Zg = c.Z + z_offset;
@@ -1137,10 +1173,9 @@ __global__ __launch_bounds__(MC3_BLK) void mc3_vertices_kernel(const McGrid g, c
     const u32 l = vox_loc[i];
     const float3u f3 = *(const float3u *)(vox_f3 + 3 * i);
     const u32 bA = blk3[i >> 8], bB = blk3[nblk + (i >> 8)];
-    const int64_t row = (int64_t)(key >> (KEY_XBITS + 2));
-    const int X = (int)((key >> 2) & ((1u << KEY_XBITS) - 1u));
+    const int X = key_x(key);
     int64_t zq;
-    const int Y = divmod_pos(row, g.Ny, &zq), Z = (int)zq;
+    const int Y = divmod_pos(key_row(key), g.Ny, &zq), Z = (int)zq;
     const u32 *sliceA = slice_tab, *sliceB = slice_tab + (g.Nz + 1);
     const u32 sB = sliceB[Z], sA1 = sliceA[Z + 1];
     if (!flags) return;
@@ -1200,56 +1235,22 @@ __global__ __launch_bounds__(MC3_BLK) void mc3_faces_kernel(const McGrid g, cons
     if (ntri > 0) {
         tloc = MC3_LOC_T(vox_loc[i]);
         const u64 key = vox_key[i];
-        const int64_t row = (int64_t)(key >> (KEY_XBITS + 2));
-        const int X = (int)((key >> 2) & ((1u << KEY_XBITS) - 1u));
-        const int64_t rowY = (int64_t)g.Ny;
         const u32 used = vox_used[i];
-        // owner voxels of the 13 possible vertices: this voxel (edges 0, 3, 8, centre 12), (x+1) edges 1, 9, then the five of
-        // mc_emit_kernel: (y+1) 2, 11; (z+1) 4, 7; (y+1, x+1) 10; (z+1, x+1) 5; (y+1, z+1) 6.
-        // A lookup that is not needed goes to this voxel's own key: always a valid address.
-#define MC3_USED(mask) ((used & (mask)) != 0)
-#define MC3_OWNER(n, needed, okey)                                                                                                  \
-        const bool need##n = (needed);                                                                                             \
-        const u64 k##n = need##n ? (okey) : key;                                                                                   \
-        const u32 cc##n = ((u32)(k##n >> 2) & ((1u << KEY_XBITS) - 1u)) + (u32)g.xorg + SEG_SHIFT;                                 \
-        const u64 seg##n = (k##n >> (KEY_XBITS + 2)) * (u64)g.segs_per_row + (cc##n >> 8);                                         \
-        const u32x2u aa##n = *(const u32x2u *)(seg_aoff + seg##n);      /* (offset, next offset): one 8-byte, 4-byte aligned load */  \
-        const u32 a0_##n = aa##n.x, a1_##n = aa##n.y;                                                                              \
-        const Rec4 rec##n = load_rec(seg_act, (int64_t)seg##n);       /* garbage for an empty segment: masked below */
-        MC3_OWNER(2, MC3_USED((1u << 2) | (1u << 11)), make_key(row + 1, X, 0))
-        MC3_OWNER(3, MC3_USED((1u << 4) | (1u << 7)), make_key(row + rowY, X, 0))
-        MC3_OWNER(4, MC3_USED(1u << 10), make_key(row + 1, X + 1, 0))
-        MC3_OWNER(5, MC3_USED(1u << 5), make_key(row + rowY, X + 1, 0))
-        MC3_OWNER(6, MC3_USED(1u << 6), make_key(row + 1 + rowY, X, 0))
-#undef MC3_OWNER
-        // (x+1, y, z) is the next list entry if it is active at all
-        const int64_t inx = (u64)(i + 1) < na ? i + 1 : i;
-        const bool have1 = vox_key[inx] == key + 4ull;
-        const u32 pos0 = (u32)i, pos1 = (u32)inx;
-#define MC3_RANK(n)                                                                                                                 \
-        bool have##n;                                                                                                              \
-        u32 pos##n;                                                                                                                \
-        {                                                                                                                          \
-            const int L = (int)((cc##n & 255u) >> 2), k = (int)(cc##n & 3u);                                                       \
-            const u64 b0 = rec##n.b[0], b1 = rec##n.b[1], b2 = rec##n.b[2], b3 = rec##n.b[3];                                      \
-            const u64 bk = k == 0 ? b0 : (k == 1 ? b1 : (k == 2 ? b2 : b3));                                                      \
-            const u64 m = (1ull << L) - 1ull;                                                                                      \
-            u32 rank = (u32)(__popcll(b0 & m) + __popcll(b1 & m) + __popcll(b2 & m) + __popcll(b3 & m));                          \
-            rank += (k > 0 ? (u32)((b0 >> L) & 1ull) : 0u) + (k > 1 ? (u32)((b1 >> L) & 1ull) : 0u) +                             \
-                    (k > 2 ? (u32)((b2 >> L) & 1ull) : 0u);                                                                        \
-            have##n = need##n && a1_##n != a0_##n && ((bk >> L) & 1ull);                                                           \
-            pos##n = have##n ? a0_##n + rank : (u32)i;                                                                             \
+        // list position of the owner voxel of each of the 13 possible vertices (MC_EDGES)
+        u32 pos[7];
+        bool have[7];
+        pos[0] = (u32)i;
+        have[0] = true;
+        {   // (x+1, y, z) is the next list entry if it is active at all
+            const int64_t inx = (u64)(i + 1) < na ? i + 1 : i;
+            pos[1] = (u32)inx;
+            have[1] = vox_key[inx] == key + 4ull;
         }
-        MC3_RANK(2) MC3_RANK(3) MC3_RANK(4) MC3_RANK(5) MC3_RANK(6)
-#undef MC3_RANK
-        const bool have0 = true;
-        // edge e: owner number o, slot sl
-#define MC3_EDGE(e, o, sl)                                                                                                          \
-        if (used & (1u << e)) { if (have##o) id##e = table[(int64_t)pos##o * 4 + sl]; else bad = true; }
-        MC3_EDGE(0, 0, 0) MC3_EDGE(1, 1, 1) MC3_EDGE(2, 2, 0) MC3_EDGE(3, 0, 1) MC3_EDGE(4, 3, 0) MC3_EDGE(5, 5, 1) MC3_EDGE(6, 6, 0)
-        MC3_EDGE(7, 3, 1) MC3_EDGE(8, 0, 2) MC3_EDGE(9, 1, 2) MC3_EDGE(10, 4, 2) MC3_EDGE(11, 2, 2) MC3_EDGE(12, 0, 3)
-#undef MC3_EDGE
-#undef MC3_USED
+        far_owner_positions(g, key, used, (u32)i, seg_act, seg_aoff, pos, have);
+#define MC_E(e, o, sl)                                                                                                    \
+        if (used & (1u << e)) { if (have[o]) id##e = table[(int64_t)pos[o] * 4 + sl]; else bad = true; }
+        MC_EDGES(MC_E)
+#undef MC_E
     }
     int degen = 0;
     for (u32 w0 = 0; w0 < total; w0 += MC3_FWIN) {
@@ -1298,8 +1299,7 @@ TOMO_API int tomo_mc3_eval(const float *field, int Nz, int Ny, int Nx, int64_t p
                            float *vox_c3, uint32_t *blk3, void *stream)
 {
     McGrid g;
-    int rc = make_grid(g, field, Nz, Ny, Nx, pitch, xorg, iso);
-    if (rc) return rc;
+    if (const int rc = make_grid(g, field, Nz, Ny, Nx, pitch, xorg, iso)) return rc;
     if (!vox_key || !tot || !vox_loc || !vox_til || !vox_flags || !vox_used || !vox_f3 || !vox_c3 || !blk3 || cap <= 0) return TOMO_E_ARG;
     const int64_t nblk = ceil_div64(cap, MC3_BLK);
     if (nblk > 0x7fffffff) return TOMO_E_SIZE;
@@ -1315,10 +1315,10 @@ TOMO_API int tomo_mc3_scan(int Nz, int Ny, int Nx, int xorg, const uint32_t *seg
                            uint32_t *blk3, uint32_t *slice_tab, unsigned long long *tot, int64_t cap_v, int64_t cap_f,
                            void *stream)
 {
-    if (Nz < 2 || Ny < 2 || Nx < 2 || !seg_aoff || !vox_loc || !blk3 || !slice_tab || !tot || cap <= 0) return TOMO_E_ARG;
+    if (!seg_aoff || !vox_loc || !blk3 || !slice_tab || !tot || cap <= 0) return TOMO_E_ARG;
+    McGrid g;
+    if (const int rc = index_grid(g, Nz, Ny, Nx, xorg)) return rc;
     if (cap_v >= 0x7fffffffll || cap_f >= 0x7fffffffll) return TOMO_E_SIZE;
-    McGrid g; g.Nz = Nz; g.Ny = Ny; g.Nx = Nx; g.pitch = 0; g.xorg = xorg; g.iso = 0.0;
-    g.segs_per_row = (int)tomo_mc_segments_per_row(Nx, xorg);
     hipLaunchKernelGGL(mc3_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, g, seg_aoff, vox_loc, cap, blk3,
                        ceil_div64(cap, MC3_BLK), slice_tab, (u64 *)tot, cap_v, cap_f);
     const int64_t nseg = tomo_mc3_sort_segments(Nz, Ny);
@@ -1334,11 +1334,11 @@ TOMO_API int tomo_mc3_vertices(int Nz, int Ny, int Nx, int xorg, const unsigned 
                                int z_offset, int shift, const double *cum, int64_t ncum, const double *adj, int64_t nadj,
                                float mm_y, float mm_x, float *vrec, uint32_t *keys, uint32_t *idx, void *stream)
 {
-    if (Nz < 2 || Ny < 2 || Nx < 2 || !vox_key || !tot || !vox_loc || !vox_flags || !vox_f3 || !vox_c3 || !blk3 || !slice_tab ||
-        !vrec || !keys || cap <= 0 || (nadj > 0 && (!cum || !adj || ncum != nadj + 1)))
+    if (!vox_key || !tot || !vox_loc || !vox_flags || !vox_f3 || !vox_c3 || !blk3 || !slice_tab || !vrec || !keys || cap <= 0 ||
+        (nadj > 0 && (!cum || !adj || ncum != nadj + 1)))
         return TOMO_E_ARG;
-    McGrid g; g.Nz = Nz; g.Ny = Ny; g.Nx = Nx; g.pitch = 0; g.xorg = xorg; g.iso = 0.0;
-    g.segs_per_row = (int)tomo_mc_segments_per_row(Nx, xorg);
+    McGrid g;
+    if (const int rc = index_grid(g, Nz, Ny, Nx, xorg)) return rc;
     Mc3Final fin; fin.cum = cum; fin.adj = adj; fin.ncum = ncum; fin.nadj = nadj; fin.shift = shift; fin.mm_y = mm_y; fin.mm_x = mm_x;
     const int64_t nblk = ceil_div64(cap, MC3_BLK);
     hipLaunchKernelGGL(mc3_vertices_kernel, dim3((unsigned)nblk), dim3(MC3_BLK), 0, (hipStream_t)stream, g, (const u64 *)vox_key, cap,
@@ -1352,11 +1352,10 @@ TOMO_API int tomo_mc3_faces(int Nz, int Ny, int Nx, int xorg, const unsigned lon
                             const uint32_t *vox_loc, const int32_t *vox_til, const uint16_t *vox_used, const uint32_t *blk3,
                             const int32_t *table, int64_t *faces, int64_t cap_f, void *stream)
 {
-    if (Nz < 2 || Ny < 2 || Nx < 2 || !vox_key || !tot || !seg_act || !seg_aoff || !vox_loc || !vox_til || !vox_used || !blk3 || !table || !faces ||
-        cap <= 0 || cap_f < 0)
+    if (!vox_key || !tot || !seg_act || !seg_aoff || !vox_loc || !vox_til || !vox_used || !blk3 || !table || !faces || cap <= 0 || cap_f < 0)
         return TOMO_E_ARG;
-    McGrid g; g.Nz = Nz; g.Ny = Ny; g.Nx = Nx; g.pitch = 0; g.xorg = xorg; g.iso = 0.0;
-    g.segs_per_row = (int)tomo_mc_segments_per_row(Nx, xorg);
+    McGrid g;
+    if (const int rc = index_grid(g, Nz, Ny, Nx, xorg)) return rc;
     const int64_t nblk = ceil_div64(cap, MC3_BLK);
     hipLaunchKernelGGL(mc3_faces_kernel<false>, dim3((unsigned)nblk), dim3(MC3_BLK), 0, (hipStream_t)stream, g, (const u64 *)vox_key, cap,
                        (u64 *)tot, (const u64 *)seg_act, seg_aoff, vox_loc, vox_til, vox_used, blk3, nblk, table, faces, cap_f,
@@ -1370,11 +1369,11 @@ TOMO_API int tomo_mc3_faces_slab(int Nz, int Ny, int Nx, int xorg, const unsigne
                                  const int32_t *table, int64_t *faces, int64_t cap_f, const int64_t *gathered, int rank, int world,
                                  const int32_t *ids_next, int64_t cap_top, int64_t cap_v, void *stream)
 {
-    if (Nz < 2 || Ny < 2 || Nx < 2 || !vox_key || !tot || !seg_act || !seg_aoff || !vox_loc || !vox_til || !vox_used || !blk3 || !table || !faces ||
-        cap <= 0 || cap_f < 0 || !gathered || rank < 0 || rank >= world || cap_v < 1 || cap_top < 0)
+    if (!vox_key || !tot || !seg_act || !seg_aoff || !vox_loc || !vox_til || !vox_used || !blk3 || !table || !faces || cap <= 0 || cap_f < 0 ||
+        !gathered || rank < 0 || rank >= world || cap_v < 1 || cap_top < 0)
         return TOMO_E_ARG;
-    McGrid g; g.Nz = Nz; g.Ny = Ny; g.Nx = Nx; g.pitch = 0; g.xorg = xorg; g.iso = 0.0;
-    g.segs_per_row = (int)tomo_mc_segments_per_row(Nx, xorg);
+    McGrid g;
+    if (const int rc = index_grid(g, Nz, Ny, Nx, xorg)) return rc;
     const int64_t nblk = ceil_div64(cap, MC3_BLK);
     hipLaunchKernelGGL(mc3_faces_kernel<true>, dim3((unsigned)nblk), dim3(MC3_BLK), 0, (hipStream_t)stream, g, (const u64 *)vox_key, cap,
                        (u64 *)tot, (const u64 *)seg_act, seg_aoff, vox_loc, vox_til, vox_used, blk3, nblk, table, faces, cap_f,
