@@ -21,6 +21,8 @@
  *
  * Removed in ABI 7 (none had a caller left): tomo_mesh_unique_presorted, tomo_mesh_faces, tomo_mesh_faces_direct, tomo_mesh_faces_workspace_bytes, tomo_mc3_sort_rank, tomo_close_stencil, tomo_pack_close_slab.
  * Removed in ABI 8 (none had a caller left): tomo_morph_pass, tomo_field_signs_fused; tomo_morph_fused accepts nops 2 and 4 only.
+ * Removed in ABI 9 (none had a caller left): tomo_close_ends_gp and the separate slab lookup and slab summary entry points
+ * (tomo_slab_lookup_summary is both); tomo_mc_scan lost the parameter that had to be NULL.
  */
 #ifndef TOMO_HIP_H
 #define TOMO_HIP_H
@@ -125,9 +127,6 @@ int tomo_slab_edges(const uint8_t *mask, uint64_t *bits, int nz, int ny, int nx,
  * workspace: tomo_close_ends_workspace_words() uint64 words. */
 int64_t tomo_close_ends_workspace_words(int nz, int ny, int nx);
 int tomo_close_ends_scan(uint64_t *bits, int nz, int ny, int nx, uint64_t *workspace, void *stream);
-/* The same chain reduced to a pair of bit planes gp_out = [G | P] (2 * ny * wx words) over slices 1 .. nz-2:
- * c'[nz-2] = G | (P & c'[0]).  What a Z-slab rank publishes in the multi-GPU path (same workspace size). */
-int tomo_close_ends_gp(const uint64_t *bits, int nz, int ny, int nx, uint64_t *workspace, uint64_t *gp_out, void *stream);
 /* nops (2 or 4; anything else is TOMO_E_ARG) 6-neighbour passes (skimage binary_erosion / binary_dilation,
  * voxel_processor.py:88,91) fused into one kernel, in != out: bit j of `ops` is the op of pass j, 0 = erosion with
  * border_value 1, 1 = dilation with border value 0.  The masks tomo_smooth plans (E D | D E = ops 0b0110 with nops 4,
@@ -515,9 +514,9 @@ int tomo_mc_scan_segments(const uint32_t *seg_cnt, int64_t nseg, uint32_t *seg_a
                           void *workspace, int64_t workspace_bytes, void *stream);
 /* Exclusive scan of packed counts (low 16 bits -> off_a, high 16 bits -> off_b; both uint32[n + 1]; with off_b = NULL
  * the counts are plain numbers and off_a their exclusive scan), totals (device uint64[4]) = {sum low, sum high, 0, 0}.
- * nz_ids must be NULL (kept for the call shape).  workspace: tomo_mc_scan_workspace_bytes(n) bytes. */
+ * workspace: tomo_mc_scan_workspace_bytes(n) bytes. */
 int64_t tomo_mc_scan_workspace_bytes(int64_t n);
-int tomo_mc_scan(const uint32_t *counts, int64_t n, uint32_t *off_a, uint32_t *off_b, uint32_t *nz_ids,
+int tomo_mc_scan(const uint32_t *counts, int64_t n, uint32_t *off_a, uint32_t *off_b,
                  unsigned long long *totals, void *workspace, int64_t workspace_bytes, void *stream);
 /* 2. list: vox_key[na] = keys of the active voxels, ascending (cell scan order), from seg_act. */
 int tomo_mc_list(int Nz, int Ny, int Nx, int xorg, const uint32_t *seg_aoff, const unsigned long long *seg_act,
@@ -627,24 +626,22 @@ int tomo_mesh_lookup(const float *uniq, int64_t nu, const float *query, int64_t 
                      unsigned long long *missing, void *stream);
 /* Z-slab numbering without host round trips (scale-out of the path; no counterpart in the single-process
  * reference): all counts come from `tot` of the rank's mc3 chain (tot[1] rows, tot[7] of them on the shared top plane).
- *   tomo_slab_top_rows  msg float32[(cap + 1) * 3]: row 0 = {n_top as uint32 bits, 0, 0}, then the top-plane rows, zero padded
- *   tomo_slab_lookup    out[i] = index of row i of a received message in this rank's uniq, -1 past its count or when the
- *                       row is not there (then *missing += 1; zero before the first call -- tomo_slab_summary reads it and
- *                       clears it again)
- *   tomo_slab_summary   out int64[8] = kept rows | missing | flags (1 chain overflow, 2 rows not strictly ascending,
- *                       4 n_top > cap_top, 8 caller_flags != 0) | rows | top rows | rows announced from below | list length |
- *                       triangles -- what the ranks all-gather
- *   tomo_mc3_faces_slab tomo_mc3_faces with GLOBAL indices: row r of this rank's list (what `table` names) leaves as r + this
- *                       rank's offset (the sum of the lower ranks' kept rows in `gathered`, int64[world][8]) while r < kept
- *                       rows, and as ids_next[r - kept] (what the upper rank's tomo_slab_lookup found) + the upper rank's
- *                       offset for the rows on the shared top plane */
+ *   tomo_slab_top_rows        msg float32[(cap + 1) * 3]: row 0 = {n_top as uint32 bits, 0, 0}, then the top-plane rows, zero
+ *                             padded
+ *   tomo_slab_lookup_summary  ONE launch for the lookup of a received message and this rank's summary:
+ *                             out[i] (int32[cap]) = index of row i of `msg` in this rank's uniq, -1 past the message's count
+ *                             or when the row is not there;
+ *                             summary int64[8] = kept rows | rows of `msg` not found | flags (1 the chain's counts cannot be
+ *                             trusted: a buffer overflowed, 2 rows not strictly ascending, 4 n_top > cap_top, 8 caller_flags
+ *                             != 0) | rows | top rows | rows announced from below | list length | triangles -- what the
+ *                             ranks all-gather.  The workgroup that finishes last writes it.  scratch: uint64[2] (a ticket
+ *                             and the misses), zeroed once by the caller, left zero by every call.  msg == NULL (the lowest
+ *                             rank): the summary alone, out and cap unused.
+ *   tomo_mc3_faces_slab       tomo_mc3_faces with GLOBAL indices: row r of this rank's list (what `table` names) leaves as r +
+ *                             this rank's offset (the sum of the lower ranks' kept rows in `gathered`, int64[world][8]) while
+ *                             r < kept rows, and as ids_next[r - kept] (the `out` of the upper rank's lookup) + the upper
+ *                             rank's offset for the rows on the shared top plane */
 int tomo_slab_top_rows(const float *uniq, const unsigned long long *tot, int64_t cap_v, int64_t cap, float *msg, void *stream);
-int tomo_slab_lookup(const float *uniq, const unsigned long long *tot, int64_t cap_v, const float *msg, int64_t cap,
-                     int32_t *out, unsigned long long *missing, void *stream);
-int tomo_slab_summary(const unsigned long long *tot, int64_t cap_v, const float *msg_in, unsigned long long *missing,
-                      int64_t cap_top, int64_t caller_flags, int64_t *out, void *stream);
-/* tomo_slab_lookup + tomo_slab_summary in ONE launch (the workgroup that finishes last writes the summary).  scratch: uint64[2],
- * zeroed once by the caller, left zero by every call.  msg == NULL (the lowest rank): the summary alone. */
 int tomo_slab_lookup_summary(const float *uniq, const unsigned long long *tot, int64_t cap_v, const float *msg, int64_t cap,
                              int32_t *out, int64_t cap_top, int64_t caller_flags, unsigned long long *scratch, int64_t *summary,
                              void *stream);

@@ -1,5 +1,5 @@
 """Test-only engine for tomography_3d_reconstructor_amd.slab.SlabJob: the CPU oracle behind the engine
-interface, so the Z-slab orchestration (halo exchange, carry fold, global numbering) can be exercised on CPU
+interface, so the Z-slab orchestration (halo exchange, close-ends stencil, global numbering) can be exercised on CPU
 ranks (gloo) without a GPU.  Lives under tests/: the product never imports it."""
 import numpy as np
 import torch
@@ -61,25 +61,11 @@ class OracleEngine:
             a[z] = O.fill_holes_2d(a[z])
             vol.set(a)
 
-    def close_gp(self, vol):
-        a = vol.arr()
-        n = a.shape[0]
-        G = np.zeros(a.shape[1:], bool)
-        P = np.ones(a.shape[1:], bool)
-        for z in range(1, n - 1):
-            G = a[z] | (a[z + 1] & G)
-            P = a[z + 1] & P
-        pk = np_pack(np.stack([G, P]))
-        return torch.from_numpy(pk[0].copy()), torch.from_numpy(pk[1].copy())
-
     def close_scan(self, vol):
         a = vol.arr()
         for z in range(1, a.shape[0] - 1):
             a[z] = a[z] | (a[z - 1] & a[z + 1])
         vol.set(a)
-
-    def popcount(self, vol):
-        return int(vol.arr().sum())
 
     def smooth(self, vol, iterations, create_manifold):
         a = O.smooth(vol.arr(), iterations, create_manifold)

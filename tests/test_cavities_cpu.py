@@ -84,7 +84,7 @@ def test_new_symbols_are_declared_bound_and_exported():
     for s in NEW_SYMBOLS:
         assert re.search(r"\b%s\s*\(" % s, text), s
         assert s in _lib.SIGNATURES and hasattr(L, s), s
-    assert _lib.lib().tomo_abi_version() == 8                        # additions only
+    assert _lib.lib().tomo_abi_version() == 9                        # additions only
     for k in ("components_fill", "components_cavity_owners"):
         assert pipeline.COUNTERS[k] >= 0
 

@@ -159,7 +159,7 @@ def test_new_symbols_are_declared_bound_and_exported():
     for s in NEW_SYMBOLS:
         assert re.search(r"\b%s\s*\(" % s, text), s
         assert s in _lib.SIGNATURES and hasattr(L, s), s
-    assert _lib.lib().tomo_abi_version() == 8                      # additive
+    assert _lib.lib().tomo_abi_version() == 9                      # additive
     assert pipeline.COUNTERS["components_moments"] >= 0
     assert pipeline.MOMENT_SUMS == 6 and pipeline.MOMENT_COLUMNS == 22
 

@@ -96,7 +96,7 @@ def test_new_symbols_are_declared_bound_and_exported():
     for s in NEW_SYMBOLS:
         assert re.search(r"\b%s\s*\(" % s, text), s
         assert s in _lib.SIGNATURES and hasattr(L, s), s
-    assert _lib.lib().tomo_abi_version() == 8                      # additive
+    assert _lib.lib().tomo_abi_version() == 9                      # additive
     for k in ("components_measure", "components_zhist"):
         assert pipeline.COUNTERS[k] >= 0
     assert pipeline.COMPONENT_HIST_BUDGET > 0 and pipeline.TABLE_COLUMNS == P.COLUMNS

@@ -62,7 +62,7 @@ def test_new_entry_points_of_the_c_abi():
     L = _lib.lib()
     for name in ("tomo_mesh_vertex_normals_workspace_bytes", "tomo_mesh_vertex_normals"):
         assert name in _lib.SIGNATURES and hasattr(L, name)
-    assert L.tomo_abi_version() == 8
+    assert L.tomo_abi_version() == 9
     assert L.tomo_mesh_vertex_normals(None, 4, None, 0, 4, None, 0, None, None, None) == -1          # TOMO_E_ARG, no GPU needed
     buf = np.zeros(1024, np.uint8)
     p = (buf.ctypes.data + 255) & ~255

@@ -146,8 +146,8 @@ def test_deferred_pass_with_coinciding_rows(dev):
 
 
 def test_slab_kernels_take_counts_from_device_memory(dev):
-    """tomo_slab_top_rows / lookup / summary on hand-made inputs against NumPy (the mapping to global indices inside the triangle
-    kernel is covered by every deferred pass of this file)."""
+    """tomo_slab_top_rows / tomo_slab_lookup_summary on hand-made inputs against NumPy (the mapping to global indices inside the
+    triangle kernel is covered by every deferred pass of this file)."""
     e = slab.HipEngine()
     rng = np.random.default_rng(4)
     nv, nt, cap_v, cap = 500, 37, 640, 64
@@ -167,22 +167,61 @@ def test_slab_kernels_take_counts_from_device_memory(dev):
     tot2 = torch.tensor([1, nu2, 1, 0, 0, 0, 0, 0], dtype=torch.int64, device=dev)
     m2 = msg.copy()
     m2[3 + 3 * 5] = 98.5                                                 # row 5 is not there
-    idx, miss = e.slab_lookup(uniq2, tot2, nu2 + 50, torch.from_numpy(m2).to(dev), cap)
-    idx = idx.cpu().numpy()
+
+    def summary_of(*args):
+        s = torch.full((8,), -7, dtype=torch.int64, device=dev)
+        idx = e.slab_lookup_summary(*args, s)
+        return (None if idx is None else idx.cpu().numpy()), [int(x) for x in s.cpu()]
+
+    idx, s2 = summary_of(uniq2, tot2, nu2 + 50, torch.from_numpy(m2).to(dev), cap, 0, 1)
     want = np.array([np.flatnonzero((up_rows == r).all(1))[0] for r in rows[nv - nt:]])
-    assert int(miss.item()) == 1 and idx[5] == -1 and np.array_equal(np.delete(idx[:nt], 5), np.delete(want, 5))
+    assert s2[1] == 1 and idx[5] == -1 and np.array_equal(np.delete(idx[:nt], 5), np.delete(want, 5))
     assert (idx[nt:] == -1).all()
-    s = e.slab_summary(tot, cap_v, None, None, cap, 0).cpu().numpy()
-    assert list(s) == [nv - nt, 0, 0, nv, nt, 0, 123, 77]
-    s2 = e.slab_summary(tot2, nu2 + 50, torch.from_numpy(m2).to(dev), miss, 0, 1).cpu().numpy()
-    assert list(s2) == [nu2, 1, 8, nu2, 0, nt, 1, 1]
-    assert int(miss.item()) == 0                                           # read once, cleared for the next pass
+    assert s2 == [nu2, 1, 8, nu2, 0, nt, 1, 1]
+    # the scratch words were left zero: the next call on this engine and stream, every row present, starts from zero
+    idx, s3 = summary_of(uniq2, tot2, nu2 + 50, torch.from_numpy(msg).to(dev), cap, 0, 1)
+    assert s3 == [nu2, 0, 8, nu2, 0, nt, 1, 1] and np.array_equal(idx[:nt], want) and (idx[nt:] == -1).all()
+    idx, s = summary_of(uniq, tot, cap_v, None, cap, cap, 0)             # msg = NULL (the lowest rank): the summary alone
+    assert idx is None and s == [nv - nt, 0, 0, nv, nt, 0, 123, 77]
     tot_small = tot.clone()
-    assert int(e.slab_summary(tot_small, cap_v, None, None, nt - 1, 0)[2].item()) == 4        # message capacity too small
+    assert summary_of(uniq, tot_small, cap_v, None, cap, nt - 1, 0)[1][2] == 4       # message capacity too small
     tot_small[4] = 3
-    assert int(e.slab_summary(tot_small, cap_v, None, None, cap, 0)[2].item()) == 2           # rows not strictly ascending
+    assert summary_of(uniq, tot_small, cap_v, None, cap, cap, 0)[1][2] == 2          # rows not strictly ascending
     tot_small[3] = 1
-    assert int(e.slab_summary(tot_small, cap_v, None, None, cap, 0)[2].item()) & 1            # a chain buffer overflowed
+    assert summary_of(uniq, tot_small, cap_v, None, cap, cap, 0)[1][2] & 1           # a chain buffer overflowed
+
+
+@pytest.mark.parametrize("n_rows,unknown", [(300, (5, 290)), (560, (5, 530))])
+def test_slab_lookup_summary_counts_misses_across_workgroups(dev, n_rows, unknown):
+    """A message capacity of 600 is looked up by three workgroups of 256; whichever of them draws the last ticket writes the
+    summary and must see the misses of ALL of them: one unknown row in the first workgroup's share, one in the last
+    workgroup's that holds announced rows (560 rows: the third; 300 rows: the second, the third only fills -1).  The call
+    after it, every row present, starts from zero again."""
+    e = slab.HipEngine()
+    rng = np.random.default_rng(n_rows)
+    cap = 600
+    rows = np.unique(rng.integers(0, 40, (6000, 3)).astype(np.float32), axis=0)
+    nu = len(rows)
+    assert nu > 2 * n_rows
+    uniq = torch.zeros((nu + 50, 3), dtype=torch.float32, device=dev)
+    uniq[:nu] = torch.from_numpy(rows).to(dev)
+    tot = torch.tensor([1, nu, 1, 0, 0, 0, 0, 0], dtype=torch.int64, device=dev)
+    want = np.sort(rng.choice(nu, n_rows, replace=False))
+    msg = np.zeros((cap + 1, 3), np.float32)
+    msg[0, :1].view(np.uint32)[0] = n_rows
+    msg[1:1 + n_rows] = rows[want]
+    bad = msg.copy()
+    for i in unknown:
+        bad[1 + i, 0] += 0.5                                             # the lists hold whole numbers only
+    for m, misses in ((bad, len(unknown)), (msg, 0), (bad, len(unknown)), (msg, 0)):
+        s = torch.full((8,), -7, dtype=torch.int64, device=dev)
+        idx = e.slab_lookup_summary(uniq, tot, nu + 50, torch.from_numpy(m.reshape(-1)).to(dev), cap, 0, 0, s).cpu().numpy()
+        exp = np.full(cap, -1, np.int64)
+        exp[:n_rows] = want
+        if misses:
+            exp[list(unknown)] = -1
+        assert [int(x) for x in s.cpu()] == [nu, misses, 0, nu, 0, n_rows, 1, 1]
+        assert np.array_equal(idx, exp)
 
 
 @pytest.mark.parametrize("world,nz", [(2, 300), (3, 391)])

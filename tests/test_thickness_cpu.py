@@ -218,4 +218,4 @@ def test_new_exports_answer_bad_arguments_without_a_gpu():
     assert L.tomo_edt_thickness_finish(p, q, 4, 4, 4, r, -1, s, None) == -1
     assert L.tomo_edt_thickness_finish(p, p, 4, 4, 4, r, 1, s, None) == -1
     assert L.tomo_edt_thickness_finish(p, q, 4, -4, 4, r, 1, s, None) == -1
-    assert L.tomo_abi_version() == 8
+    assert L.tomo_abi_version() == 9

@@ -1074,7 +1074,6 @@ TOMO_API int tomo_slab_edges(const uint8_t *mask, uint64_t *bits, int nz, int ny
 // the np.any guards there are pure short-cuts).  A carry chain per (y,x) column:
 //   c'[z] = G | (P & carry_in)  with  G' = c[z] | (c[z+1] & G),  P' = c[z+1] & P.
 // Three small kernels: per z-chunk composite (G,P); sequential combine over the chunks; apply.
-// The same composite is what a Z-slab rank publishes to its neighbours in the multi-GPU path.
 #define CE_CHUNK 64
 
 __global__ __launch_bounds__(256) void close_reduce_kernel(const u64 *__restrict__ bits, u64 *__restrict__ GP,
@@ -1166,37 +1165,6 @@ TOMO_API int tomo_close_ends_scan(uint64_t *bits, int nz, int ny, int nx, uint64
     hipLaunchKernelGGL(close_carry_kernel, dim3(grid.x), dim3(256), 0, s, (const u64 *)bits, GP, sw, nchunks);
     hipLaunchKernelGGL(close_apply_snap_kernel, grid, dim3(256), 0, s, (u64 *)bits, (const u64 *)GP, (const u64 *)snap, nz,
                        sw, nchunks);
-    return tomo_status();
-}
-
-// (G, P) of the whole chain over slices 1 .. nz-2: composition of the per-chunk pairs.  This is what a Z-slab
-// rank publishes to the other ranks (multi-GPU close-ends): c'[nz-2] = G | (P & c'[0]).
-__global__ __launch_bounds__(256) void close_compose_kernel(const u64 *__restrict__ GP, u64 *__restrict__ out,
-                                                            int64_t slice_words, int nchunks)
-{
-    int64_t col = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (col >= slice_words) return;
-    u64 G = 0, P = ~0ull;
-    for (int k = 0; k < nchunks; k++) {
-        u64 Gk = GP[((int64_t)k * 2) * slice_words + col], Pk = GP[((int64_t)k * 2 + 1) * slice_words + col];
-        G = Gk | (Pk & G);
-        P = Pk & P;
-    }
-    out[col] = G;
-    out[slice_words + col] = P;
-}
-
-TOMO_API int tomo_close_ends_gp(const uint64_t *bits, int nz, int ny, int nx, uint64_t *workspace, uint64_t *gp_out,
-                                void *stream)
-{
-    if (!bits || !workspace || !gp_out || nz < 3 || ny <= 0 || nx <= 0) return TOMO_E_ARG;
-    int64_t sw = (int64_t)ny * tomo_words_per_row(nx);
-    int nchunks = (nz - 2 + CE_CHUNK - 1) / CE_CHUNK;
-    u64 *GP = (u64 *)workspace;
-    dim3 grid((unsigned)ceil_div64(sw, 256), (unsigned)nchunks);
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(close_reduce_kernel, grid, dim3(256), 0, s, (const u64 *)bits, GP, nz, sw, nchunks);
-    hipLaunchKernelGGL(close_compose_kernel, dim3(grid.x), dim3(256), 0, s, (const u64 *)GP, (u64 *)gp_out, sw, nchunks);
     return tomo_status();
 }
 

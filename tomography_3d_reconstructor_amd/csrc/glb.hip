@@ -606,7 +606,7 @@ static int normals_run(const float *pos, int64_t nv, const void *idx, int idx_i6
             else
                 hipLaunchKernelGGL(normals_count_kernel<uint32_t>, dim3(gf), dim3(BLOCK), 0, st, (const uint32_t *)idx, nf, nv, deg, counters);
         }
-        const int rc = tomo_mc_scan(deg, nv, off, nullptr, nullptr, (unsigned long long *)(base + w.totals), base + w.scan, w.scan_bytes, st);
+        const int rc = tomo_mc_scan(deg, nv, off, nullptr, (unsigned long long *)(base + w.totals), base + w.scan, w.scan_bytes, st);
         if (rc != TOMO_OK) return rc;
         if (nf > 0) {
             if (idx_i64)

@@ -382,10 +382,9 @@ static int scan_launch(const u32 *counts, int64_t n, uint32_t *off_a, uint32_t *
     return tomo_status();
 }
 
-TOMO_API int tomo_mc_scan(const uint32_t *counts, int64_t n, uint32_t *off_a, uint32_t *off_b, uint32_t *nz_ids,
+TOMO_API int tomo_mc_scan(const uint32_t *counts, int64_t n, uint32_t *off_a, uint32_t *off_b,
                           unsigned long long *totals, void *workspace, int64_t workspace_bytes, void *stream)
 {
-    if (nz_ids) return TOMO_E_ARG;            // the list of non-zero entries is no longer produced (ABI 2)
     return scan_launch(counts, n, off_a, off_b, totals, workspace, workspace_bytes, stream);
 }
 
@@ -1199,7 +1198,7 @@ __global__ __launch_bounds__(MC3_BLK) void mc3_vertices_kernel(const McGrid g, c
 #define MC3_FWIN 1024
 // SLAB: the triangles of a Z-slab rank leave with GLOBAL vertex indices (slab.py, the pass without host round trips): row r of
 // this rank's list is r + the sum of the lower ranks' kept rows while r < k = rows - rows on the shared top plane, and
-// ids_next[r - k] + the upper rank's offset for the shared rows (what the upper rank's tomo_slab_lookup found); every count
+// ids_next[r - k] + the upper rank's offset for the shared rows (what the upper rank's lookup found); every count
 // comes from device memory (tot, the all-gathered summaries) and the mapping is applied where the staged indices leave LDS.
 struct Mc3SlabMap { const int64_t *gathered; const int32_t *ids_next; int64_t cap_top, cap_v; int rank; };
 template <bool SLAB>

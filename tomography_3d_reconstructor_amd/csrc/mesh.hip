@@ -691,16 +691,10 @@ TOMO_API int tomo_mc3_sort_rank_fused(const float *vrec, const uint32_t *keys, i
 }
 
 // ------------------------------------------------------------------------------------------ lookup
-// Index of every query row in a lexicographically sorted, duplicate-free (U,3) row list (binary search); a row that is
-// not there gets -1 and is counted in *missing.  The Z-slab job uses it to number the few thousand shared-plane vertices
-// a rank receives from below against its own unique list instead of sorting them in.
-__global__ __launch_bounds__(256) void rows_lookup_kernel(const float *__restrict__ uniq, int64_t nu,
-                                                          const float *__restrict__ query, int64_t nq,
-                                                          int32_t *__restrict__ out, u64 *__restrict__ missing)
+// Lower bound of the row (qz, qy, qx) in a lexicographically sorted, duplicate-free (nu, 3) row list (binary search):
+// -> the first position whose row is not less, *found = the row there is the query.
+__device__ static inline int64_t rows_lower_bound(const float *__restrict__ uniq, int64_t nu, float qz, float qy, float qx, bool *found)
 {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nq) return;
-    const float qz = query[3 * i], qy = query[3 * i + 1], qx = query[3 * i + 2];
     int64_t lo = 0, hi = nu;
     while (lo < hi) {
         const int64_t mid = lo + ((hi - lo) >> 1);
@@ -708,7 +702,21 @@ __global__ __launch_bounds__(256) void rows_lookup_kernel(const float *__restric
         const bool less = m[0] < qz || (m[0] == qz && (m[1] < qy || (m[1] == qy && m[2] < qx)));
         if (less) lo = mid + 1; else hi = mid;
     }
-    const bool found = lo < nu && uniq[3 * lo] == qz && uniq[3 * lo + 1] == qy && uniq[3 * lo + 2] == qx;
+    *found = lo < nu && uniq[3 * lo] == qz && uniq[3 * lo + 1] == qy && uniq[3 * lo + 2] == qx;
+    return lo;
+}
+
+// Index of every query row in a lexicographically sorted, duplicate-free (U,3) row list; a row that is not there gets -1
+// and is counted in *missing.  The Z-slab job uses it to number the few thousand shared-plane vertices a rank receives
+// from below against its own unique list instead of sorting them in.
+__global__ __launch_bounds__(256) void rows_lookup_kernel(const float *__restrict__ uniq, int64_t nu,
+                                                          const float *__restrict__ query, int64_t nq,
+                                                          int32_t *__restrict__ out, u64 *__restrict__ missing)
+{
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nq) return;
+    bool found;
+    const int64_t lo = rows_lower_bound(uniq, nu, query[3 * i], query[3 * i + 1], query[3 * i + 2], &found);
     out[i] = found ? (int32_t)lo : -1;
     if (!found) atomicAdd(missing, 1ull);
 }
@@ -728,7 +736,7 @@ TOMO_API int tomo_mesh_lookup(const float *uniq, int64_t nu, const float *query,
 // A Z-slab rank (slab.py) numbers its vertices against its neighbours': the rows on the plane it shares with the rank above
 // close its sorted list (tot[7] of them, counted by uq3_rank_kernel), go up, are looked up there, and their indices come
 // back.  With the message capacities known from the last pass none of the counts has to reach the host before the triangles
-// are written: these three kernels (and mc3_faces_kernel<true>, which writes the GLOBAL indices) take every count from device memory.
+// are written: these two kernels (and mc3_faces_kernel<true>, which writes the GLOBAL indices) take every count from device memory.
 //   message up   float32 (cap + 1, 3): row 0 = {number of rows as uint32 bits, 0, 0}, then the rows, zero padded
 //   summary      int64[8] per rank, all-gathered: kept rows | rows from below not found | flags | nv | n_top |
 //                rows announced from below | list length | triangles
@@ -757,52 +765,9 @@ __global__ __launch_bounds__(256) void slab_top_rows_kernel(const float *__restr
     msg[3 + 3 * i] = z; msg[4 + 3 * i] = y; msg[5 + 3 * i] = x;
 }
 
-__global__ __launch_bounds__(256) void slab_lookup_kernel(const float *__restrict__ uniq, const u64 *__restrict__ tot,
-                                                          int64_t cap_v, const float *__restrict__ msg, int64_t cap,
-                                                          int32_t *__restrict__ out, u64 *__restrict__ missing)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= cap) return;
-    const int64_t nu = slab_counts_ok(tot, cap_v) ? (int64_t)tot[1] : 0;
-    const int64_t nq = (int64_t)__float_as_uint(msg[0]);
-    if (i >= nq) { out[i] = -1; return; }
-    const float qz = msg[3 + 3 * i], qy = msg[4 + 3 * i], qx = msg[5 + 3 * i];
-    int64_t lo = 0, hi = nu;
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        const float *m = uniq + 3 * mid;
-        const bool less = m[0] < qz || (m[0] == qz && (m[1] < qy || (m[1] == qy && m[2] < qx)));
-        if (less) lo = mid + 1; else hi = mid;
-    }
-    const bool found = lo < nu && uniq[3 * lo] == qz && uniq[3 * lo + 1] == qy && uniq[3 * lo + 2] == qx;
-    out[i] = found ? (int32_t)lo : -1;
-    if (!found) atomicAdd((unsigned long long *)missing, 1ull);
-}
-
-__global__ void slab_summary_kernel(const u64 *__restrict__ tot, int64_t cap_v, const float *__restrict__ msg_in,
-                                    u64 *__restrict__ missing, int64_t cap_top, int64_t caller_flags,
-                                    int64_t *__restrict__ out)
-{
-    if (blockIdx.x | threadIdx.x) return;
-    int64_t flags = caller_flags ? 8 : 0;
-    if (tot[3] != 0 || tot[1] > (u64)cap_v || tot[7] > tot[1]) flags |= 1;
-    if (tot[4] != 0) flags |= 2;
-    if (tot[7] > (u64)cap_top) flags |= 4;
-    const int64_t from_prev = msg_in ? (int64_t)__float_as_uint(msg_in[0]) : 0;
-    out[0] = (flags & 1) ? 0 : (int64_t)(tot[1] - tot[7]);
-    out[1] = missing ? (int64_t)*missing : 0;
-    if (missing) *missing = 0ull;               // read once per pass: cleared here for the next lookup (no memset per pass)
-    out[2] = flags;
-    out[3] = (int64_t)tot[1];
-    out[4] = (int64_t)tot[7];
-    out[5] = from_prev;
-    out[6] = (int64_t)tot[0];
-    out[7] = (int64_t)tot[2];
-}
-
-// tomo_slab_lookup + tomo_slab_summary in ONE launch: every workgroup looks its share of the received rows up (a binary search
-// each: ~22 dependent loads, so the few thousand rows of a shared plane are spread over many workgroups -- one workgroup alone
-// took 36 us), adds its misses to scratch[1] and takes a ticket from scratch[0]; the workgroup that draws the last ticket sees
+// Lookup and summary in ONE launch: every workgroup looks its share of the received rows up (a binary search each: ~22
+// dependent loads, so the few thousand rows of a shared plane are spread over many workgroups -- one workgroup alone took
+// 36 us), adds its misses to scratch[1] and takes a ticket from scratch[0]; the workgroup that draws the last ticket sees
 // every miss (fence + atomic), writes the summary and leaves both words zero for the next pass.  scratch: uint64[2], zeroed
 // ONCE by the caller.  msg == null (the lowest rank): the summary alone.
 __global__ __launch_bounds__(256) void slab_lookup_summary_kernel(const float *__restrict__ uniq, const u64 *__restrict__ tot,
@@ -819,15 +784,8 @@ __global__ __launch_bounds__(256) void slab_lookup_summary_kernel(const float *_
         if (i < cap) {
             if (i >= nq) out[i] = -1;
             else {
-                const float qz = msg[3 + 3 * i], qy = msg[4 + 3 * i], qx = msg[5 + 3 * i];
-                int64_t lo = 0, hi = nu;
-                while (lo < hi) {
-                    const int64_t mid = lo + ((hi - lo) >> 1);
-                    const float *m = uniq + 3 * mid;
-                    const bool less = m[0] < qz || (m[0] == qz && (m[1] < qy || (m[1] == qy && m[2] < qx)));
-                    if (less) lo = mid + 1; else hi = mid;
-                }
-                const bool found = lo < nu && uniq[3 * lo] == qz && uniq[3 * lo + 1] == qy && uniq[3 * lo + 2] == qx;
+                bool found;
+                const int64_t lo = rows_lower_bound(uniq, nu, msg[3 + 3 * i], msg[4 + 3 * i], msg[5 + 3 * i], &found);
                 out[i] = found ? (int32_t)lo : -1;
                 missed = !found;
             }
@@ -844,7 +802,7 @@ __global__ __launch_bounds__(256) void slab_lookup_summary_kernel(const float *_
     const u64 misses = atomicExch((unsigned long long *)&scratch[1], 0ull);
     scratch[0] = 0ull;
     int64_t flags = caller_flags ? 8 : 0;
-    if (tot[3] != 0 || tot[1] > (u64)cap_v || tot[7] > tot[1]) flags |= 1;
+    if (!slab_counts_ok(tot, cap_v)) flags |= 1;
     if (tot[4] != 0) flags |= 2;
     if (tot[7] > (u64)cap_top) flags |= 4;
     summary[0] = (flags & 1) ? 0 : (int64_t)(tot[1] - tot[7]);
@@ -874,24 +832,6 @@ TOMO_API int tomo_slab_top_rows(const float *uniq, const unsigned long long *tot
     if (!uniq || !tot || !msg || cap < 1 || cap_v < 1) return TOMO_E_ARG;
     hipLaunchKernelGGL(slab_top_rows_kernel, dim3((unsigned)ceil_div64(cap, 256)), dim3(256), 0, (hipStream_t)stream, uniq,
                        (const u64 *)tot, cap_v, cap, msg);
-    return tomo_status();
-}
-
-TOMO_API int tomo_slab_lookup(const float *uniq, const unsigned long long *tot, int64_t cap_v, const float *msg, int64_t cap,
-                              int32_t *out, unsigned long long *missing, void *stream)
-{
-    if (!uniq || !tot || !msg || !out || !missing || cap < 1 || cap_v < 1) return TOMO_E_ARG;
-    hipLaunchKernelGGL(slab_lookup_kernel, dim3((unsigned)ceil_div64(cap, 256)), dim3(256), 0, (hipStream_t)stream, uniq,
-                       (const u64 *)tot, cap_v, msg, cap, out, (u64 *)missing);
-    return tomo_status();
-}
-
-TOMO_API int tomo_slab_summary(const unsigned long long *tot, int64_t cap_v, const float *msg_in, unsigned long long *missing,
-                               int64_t cap_top, int64_t caller_flags, int64_t *out, void *stream)
-{
-    if (!tot || !out || cap_v < 1 || cap_top < 0) return TOMO_E_ARG;
-    hipLaunchKernelGGL(slab_summary_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const u64 *)tot, cap_v, msg_in,
-                       (u64 *)missing, cap_top, caller_flags, out);
     return tomo_status();
 }
 

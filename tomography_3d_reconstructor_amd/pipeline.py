@@ -1284,15 +1284,16 @@ def pack_closed(mask: torch.Tensor) -> BitVolume:
     return BitVolume(bits, (nz, ny, nx))
 
 
-def close_ends(vol: BitVolume, inplace: bool = False) -> BitVolume:
+def close_ends(vol: BitVolume, inplace: bool = False, fill: bool = True) -> BitVolume:
     """_close_volume_ends (voxel_processor.py:56-77): fill holes of the two end slices, then the z recurrence.
-    inplace=True overwrites `vol` (for a volume the caller owns, e.g. fresh from pack) instead of copying it first."""
+    inplace=True overwrites `vol` (for a volume the caller owns, e.g. fresh from pack) instead of copying it first.
+    fill=False: the z recurrence alone, the end slices taken as they are (a Z-slab rank puts its neighbours' slices there)."""
     nz, ny, nx = vol.shape
     L = _lib.lib()
     out = vol if inplace else BitVolume(vol.bits.clone(), vol.shape)
-    wx = out.bits.shape[2]
-    scratch = torch.empty(ny * wx + 8, dtype=torch.int64, device=vol.device)
-    _lib.check(L.tomo_fill_holes_ends(_p(out.bits), nz, ny, nx, _p(scratch), _stream()), "tomo_fill_holes_ends")
+    if fill:
+        scratch = torch.empty(ny * out.bits.shape[2] + 8, dtype=torch.int64, device=vol.device)
+        _lib.check(L.tomo_fill_holes_ends(_p(out.bits), nz, ny, nx, _p(scratch), _stream()), "tomo_fill_holes_ends")
     if nz > 2:
         ws = torch.empty(L.tomo_close_ends_workspace_words(nz, ny, nx), dtype=torch.int64, device=vol.device)
         _lib.check(L.tomo_close_ends_scan(_p(out.bits), nz, ny, nx, _p(ws), _stream()), "tomo_close_ends_scan")
@@ -1438,7 +1439,7 @@ def marching_cubes(f: Field, level: float = 0.5, z_offset: int = 0):
                        "tomo_mc_list_capped")
             _lib.check(L.tomo_mc_eval_capped(_p(f.data), *geo, _p(vox_key), cap, _p(totals), _p(vox_counts), _p(vox_flags), st),
                        "tomo_mc_eval_capped")
-            _lib.check(L.tomo_mc_scan(_p(vox_counts), cap, _p(vox_voff), _p(vox_foff), None, _p(tot2), _p(ws2), wsb2, st),
+            _lib.check(L.tomo_mc_scan(_p(vox_counts), cap, _p(vox_voff), _p(vox_foff), _p(tot2), _p(ws2), wsb2, st),
                        "tomo_mc_scan")
             host = totals.cpu()
             na, nv, nf = int(host[0]), int(host[4]), int(host[5])
@@ -1461,7 +1462,7 @@ def marching_cubes(f: Field, level: float = 0.5, z_offset: int = 0):
         vox_foff = torch.empty(na + 1, dtype=torch.int32, device=dev)
         wsb2 = L.tomo_mc_scan_workspace_bytes(na)
         ws2 = torch.empty(wsb2, dtype=torch.uint8, device=dev)
-        _lib.check(L.tomo_mc_scan(_p(vox_counts), na, _p(vox_voff), _p(vox_foff), None, _p(tot2), _p(ws2), wsb2, st),
+        _lib.check(L.tomo_mc_scan(_p(vox_counts), na, _p(vox_voff), _p(vox_foff), _p(tot2), _p(ws2), wsb2, st),
                    "tomo_mc_scan")
         nv, nf = [int(x) for x in tot2[:2].cpu()]
     del seg_cnt
@@ -1567,7 +1568,7 @@ def first_touch_order(mesh: RawMesh):
     base = torch.empty(na + 1, dtype=torch.int32, device=dev)
     wsb = L.tomo_mc_scan_workspace_bytes(na)
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    _lib.check(L.tomo_mc_scan(_p(created), na, _p(base), None, None, _p(totals), _p(ws), wsb, st), "tomo_mc_scan")
+    _lib.check(L.tomo_mc_scan(_p(created), na, _p(base), None, _p(totals), _p(ws), wsb, st), "tomo_mc_scan")
     ft_rank = torch.full((nv,), -1, dtype=torch.int32, device=dev)
     _lib.check(L.tomo_mc_first_touch(*args, 1, None, _p(base), _p(ft_rank), _p(totals), st), "tomo_mc_first_touch")
     ncreated, _, _, nbad = [int(x) for x in totals.cpu()]

@@ -265,7 +265,20 @@ class ThreadComm:
 
 # ----------------------------------------------------------------------------- the HIP engine
 class HipEngine:
-    """Device operations of the slab job, on BitVolume / torch tensors (libtomo_hip.so kernels)."""
+    """Device operations of the slab job, on BitVolume / torch tensors (libtomo_hip.so kernels).
+
+    The engine contract -- what SlabJob asks of ANY engine (this one, the CPU oracle engine of the tests):
+      every engine   pack, bits, from_bits, fill_holes, close_scan, smooth, field, field_slices, finalize_vertices, unique;
+                     slice_counts and bbox for the consumers of a finished run() (point_cloud: asked for by
+                     SlabJob.point_cloud alone, so only an engine that serves it has one)
+      optional       SlabJob looks for exactly these four, once each, and for nothing else:
+        pack_closed_slab  pack + close ends + halo exchange in one pass over the mask (else pack, _close_ends, exchange)
+        pack_into         the slab packed into the middle of its halo-extended buffer (else pack, and torch.cat for the halos)
+        mc3_vertices      the mc3 surface chain, as a WHOLE: an engine that has it also has mc3_ready, slab_top_rows,
+                          slab_lookup_summary and download_start (the pass with ONE download needs all of them).  An engine
+                          without it has marching_cubes instead: plain marching cubes, numbered through unique
+        lookup_async      the rows from below looked up in this rank's sorted list (else the two lists are merged through
+                          unique -- which any engine also needs for the rare row from below that is new to it)"""
 
     def pack(self, mask):
         return pipeline.pack(mask)
@@ -381,29 +394,8 @@ class HipEngine:
         _lib.check(_lib.lib().tomo_fill_holes_slice(vol.bits.data_ptr(), nz, ny, nx, z, scratch.data_ptr(),
                                                     torch.cuda.current_stream().cuda_stream), "tomo_fill_holes_slice")
 
-    def close_gp(self, vol):
-        """(G, P) bit planes of the carry chain over slices 1 .. nz-2 of `vol` (nz >= 3)."""
-        from . import _lib
-        L = _lib.lib()
-        nz, ny, nx = vol.shape
-        wx = vol.bits.shape[2]
-        ws = torch.empty(L.tomo_close_ends_workspace_words(nz, ny, nx), dtype=torch.int64, device=vol.bits.device)
-        gp = torch.empty((2, ny, wx), dtype=torch.int64, device=vol.bits.device)
-        _lib.check(L.tomo_close_ends_gp(vol.bits.data_ptr(), nz, ny, nx, ws.data_ptr(), gp.data_ptr(),
-                                        torch.cuda.current_stream().cuda_stream), "tomo_close_ends_gp")
-        return gp[0], gp[1]
-
     def close_scan(self, vol):
-        from . import _lib
-        L = _lib.lib()
-        nz, ny, nx = vol.shape
-        if nz > 2:
-            ws = torch.empty(L.tomo_close_ends_workspace_words(nz, ny, nx), dtype=torch.int64, device=vol.bits.device)
-            _lib.check(L.tomo_close_ends_scan(vol.bits.data_ptr(), nz, ny, nx, ws.data_ptr(),
-                                              torch.cuda.current_stream().cuda_stream), "tomo_close_ends_scan")
-
-    def popcount(self, vol):
-        return int(pipeline.popcount_async(vol).item())
+        pipeline.close_ends(vol, inplace=True, fill=False)
 
     def smooth(self, vol, iterations, create_manifold):
         return pipeline.smooth(vol, iterations, create_manifold)
@@ -424,12 +416,10 @@ class HipEngine:
         """-> (uniq (U,3), rank (V,) int32 final index of every input row)."""
         return pipeline.unique_rows(vpos)
 
-    # optional fast paths (engines without them -- the CPU oracle engine of the tests -- use unique() and torch ops)
-    def lookup(self, uniq, query):
-        return pipeline.lookup_rows(uniq, query)
-
+    # optional capabilities (the class docstring lists them)
     def lookup_async(self, uniq, query):
-        """lookup() without the host round trip: the miss count stays on the device (a 1-element int64 tensor)."""
+        """-> (idx (Q,) int32: the index of every query row in uniq, -1 where it is not there; the number of such rows, which
+        stays on the device: a 1-element int64 tensor)."""
         return pipeline.lookup_rows(uniq, query, sync=False)
 
     def mc3_vertices(self, f, z_offset, depths, mm_y, mm_x, z_top=None, defer=False, tot=None):
@@ -450,26 +440,9 @@ class HipEngine:
                                                  torch.cuda.current_stream().cuda_stream), "tomo_slab_top_rows")
         return msg
 
-    def slab_lookup(self, uniq, tot, cap_v, msg, cap, miss=None):
-        """miss: a zeroed int64[1] the caller keeps between passes (slab_summary reads and clears it), or None: a fresh one."""
-        from . import _lib
-        out = torch.empty(cap, dtype=torch.int32, device=uniq.device)
-        if miss is None:
-            miss = torch.zeros(1, dtype=torch.int64, device=uniq.device)
-        _lib.check(_lib.lib().tomo_slab_lookup(uniq.data_ptr(), tot.data_ptr(), cap_v, msg.data_ptr(), cap, out.data_ptr(),
-                                               miss.data_ptr(), torch.cuda.current_stream().cuda_stream), "tomo_slab_lookup")
-        return out, miss
-
-    def slab_summary(self, tot, cap_v, msg_in, miss, cap_top, caller_flags):
-        from . import _lib
-        out = torch.empty(8, dtype=torch.int64, device=tot.device)
-        _lib.check(_lib.lib().tomo_slab_summary(tot.data_ptr(), cap_v, None if msg_in is None else msg_in.data_ptr(),
-                                                None if miss is None else miss.data_ptr(), cap_top, caller_flags, out.data_ptr(),
-                                                torch.cuda.current_stream().cuda_stream), "tomo_slab_summary")
-        return out
-
     def slab_lookup_summary(self, uniq, tot, cap_v, msg_in, cap, cap_top, caller_flags, summary):
-        """slab_lookup + slab_summary in one launch; `summary` = int64[8] to fill."""
+        """The rows of the message from below looked up in uniq (-> int32 (cap,): index, -1 past the message's count or where
+        a row is not there; None without a message) and this rank's `summary` (int64[8] to fill) in one launch."""
         from . import _lib
         key = (str(uniq.device), torch.cuda.current_stream().cuda_stream)
         scratch = self._ls_scratch.get(key) if hasattr(self, "_ls_scratch") else None
@@ -483,9 +456,6 @@ class HipEngine:
                                                        scratch.data_ptr(), summary.data_ptr(), torch.cuda.current_stream().cuda_stream),
                    "tomo_slab_lookup_summary")
         return out
-
-    def download(self, t):
-        return pipeline._download(t)
 
     def download_start(self, t):
         """-> an object whose wait() returns the list of ints (the copy runs on the current stream, into its own page-locked buffer)."""
@@ -714,13 +684,13 @@ class SlabJob:
         dev = mask.device
         if hasattr(e, "mc3_vertices"):
             z_top = None if (last or self.world == 1) else self._z_top(slice_depths, dev)
-            deferred = self._deferred_ok and DEFERRED_NUMBERING and self.world > 1 and hasattr(e, "slab_lookup_summary")
+            deferred = self._deferred_ok and DEFERRED_NUMBERING and self.world > 1
             # the counters of a deferred pass live in ONE buffer -- the chain's eight, then every rank's summary -- so that one
             # copy brings them to the host
             counters = torch.empty(8 + 8 * self.world, dtype=torch.int64, device=dev) if deferred else None
             m = (e.mc3_vertices(f, Za, slice_depths, mm_y, mm_x, z_top=z_top, defer=True, tot=counters[:8]) if deferred else
                  e.mc3_vertices(f, Za, slice_depths, mm_y, mm_x, z_top=z_top, defer=False))
-            ready = m is not None and hasattr(e, "mc3_ready") and bool(e.mc3_ready(f, Za))
+            ready = m is not None and bool(e.mc3_ready(f, Za))
             if deferred:
                 ticket["pending"] = self._numbering_deferred(m, f, Za, slice_depths, mm_y, mm_x, z_top, dev, counters)
             else:
@@ -793,11 +763,8 @@ class SlabJob:
             prev_rows = from_prev.reshape(-1, 3).contiguous()
             if hasattr(e, "lookup_async") and nu:
                 idx_prev, miss = e.lookup_async(uniq, prev_rows)
-            elif hasattr(e, "lookup") and nu:
-                idx_prev, m = e.lookup(uniq, prev_rows)
-                miss = torch.full((1,), int(m), dtype=torch.int64, device=dev)
             else:
-                miss = torch.ones(1, dtype=torch.int64, device=dev)   # an engine without lookup: merge the two lists
+                miss = torch.ones(1, dtype=torch.int64, device=dev)   # an engine without lookup_async: merge the two lists
         # the kept counts give every rank its offset; the same all-gather tells every rank whether ANY rank found a row from
         # below that is new to it -- that rank merges the two sorted lists properly, which changes its count, and the counts
         # are gathered once more (rare with the HIP engine: the lower rank's shared-plane rows are this rank's own)
@@ -899,9 +866,8 @@ class SlabJob:
         faces = None
         if live:
             faces = m.faces(slab_map=(gathered, r, w, None if last else ids_next, cap_top, cap_v))
-        dl = e.download_start(counters) if hasattr(e, "download_start") else None
-        return {"down": dl, "counters": counters, "m": m, "faces": faces, "f": f, "Za": Za, "depths": slice_depths, "mm": (mm_y, mm_x),
-                "z_top": z_top, "dev": dev}
+        return {"down": e.download_start(counters), "counters": counters, "m": m, "faces": faces, "f": f, "Za": Za, "depths": slice_depths,
+                "mm": (mm_y, mm_x), "z_top": z_top, "dev": dev}
 
     def _numbering_deferred_finish(self, t):
         """The host side of _numbering_deferred: read the counters (possibly one pass late), decide, publish."""
@@ -909,10 +875,7 @@ class SlabJob:
         r, w = self.rank, self.world
         m, faces, f, Za, slice_depths, z_top, dev = t["m"], t["faces"], t["f"], t["Za"], t["depths"], t["z_top"], t["dev"]
         mm_y, mm_x = t["mm"]
-        if t["down"] is not None:
-            host = t["down"].wait(TIMEOUT_S or None) if w > 1 else t["down"].wait()
-        else:
-            host = e.download(t["counters"])
+        host = t["down"].wait(TIMEOUT_S or None) if w > 1 else t["down"].wait()
         own, g = host[:8], [host[8 + 8 * i:16 + 8 * i] for i in range(w)]
         bad = any(row[1] or row[2] for row in g) or any(g[i][4] != g[i + 1][5] for i in range(w - 1))
         if bad:

@@ -18,8 +18,6 @@ if os.environ.get("TOMO_EXT"):            # debugging switches
     pipeline.FIELD_FROM_BITS = False
 if os.environ.get("TOMO_SLAB_NOPACKINTO"):
     delattr(slab.HipEngine, "pack_into")
-if os.environ.get("TOMO_SLAB_NOFAST"):
-    delattr(slab.HipEngine, "lookup")
 gz = nzr * world
 depths = np.full(gz, 1.0)
 steps = 12
