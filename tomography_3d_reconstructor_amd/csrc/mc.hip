@@ -564,30 +564,54 @@ __device__ static inline u32 find_vertex(u64 okey, int slot, const McGrid &g, co
 }
 
 // List positions of the five far owners of list entry i (voxel `key`): pos[n] and have[n] for n = 2..6, have[n] only if one
-// of the owner's edges is in `used` and the owner is in the list.  A lookup is a chain of dependent loads (segment offsets
-// -> ballot record -> what the caller keeps per list position); run as straight-line code in phases, all five in flight per
-// phase, instead of five branches that each serialise their own chain.
-// A lookup that is not needed (edge not bichromatic) goes to this voxel's own key: always a valid address.
+// of the owner's edges is in `used` and the owner is in the list.  The owners sit in three rows: (y+1) holds owners 2 (x) and
+// 4 (x+1), (z+1) owners 3 and 5, (z+1, y+1) owner 6, all at this voxel's column.  The two of a row are neighbours in the list
+// order, so ONE offset pair and ONE ballot record serve both -- unless x+1 opens the next segment (one column in 256: its
+// voxel 0, a lookup of its own) -- and a row none of whose owners is needed is not looked up at all: three records in
+// registers where five lookups held five (92 -> 62 VGPRs, 5 -> 8 waves per SIMD in mc3_faces_kernel; profiles/r28_faces_owners.md).
+// A lookup is a chain of dependent loads (segment offsets + ballot record -> what the caller keeps per list position): phase 1
+// issues the loads of every needed row, phase 2 ranks, so the rows are in flight together.
 __device__ static inline void far_owner_positions(const McGrid &g, u64 key, u32 used, u32 i, const u64 *__restrict__ seg_act,
                                                   const u32 *__restrict__ seg_aoff, u32 pos[7], bool have[7])
 {
-    const int64_t row = key_row(key), rowY = (int64_t)g.Ny;
-    const int X = key_x(key);
-#define MC_ADDR(n, dz, dy, dx)                                                                                            \
-    const bool need##n = (used & mc_owner_edges(n)) != 0;                                                                 \
-    u32 cc##n;                                                                                                            \
-    const u64 seg##n = seg_of_key(need##n ? make_key(row + dy + dz * rowY, X + dx, 0) : key, g, cc##n);                   \
-    const u32x2u aa##n = *(const u32x2u *)(seg_aoff + seg##n);      /* (offset, next offset): one 8-byte, 4-byte aligned load */
-#define MC_REC(n, dz, dy, dx) const Rec4 rec##n = load_rec(seg_act, (int64_t)seg##n);     /* garbage for an empty segment: masked below */
-#define MC_RANK(n, dz, dy, dx)                                                                                            \
-    u32 rank##n;                                                                                                          \
-    const bool listed##n = seg_rank(rec##n, cc##n, rank##n);                                                              \
-    have[n] = need##n && aa##n.x != aa##n.y && listed##n;                                                                 \
-    pos[n] = have[n] ? aa##n.x + rank##n : i;
-    MC_FAR_OWNERS(MC_ADDR) MC_FAR_OWNERS(MC_REC) MC_FAR_OWNERS(MC_RANK)
-#undef MC_ADDR
-#undef MC_REC
-#undef MC_RANK
+#define MC_NEED(n, dz, dy, dx) const bool need##n = (used & mc_owner_edges(n)) != 0;
+#define MC_AT(n, dz, dy, dx) && (dz << 2 | dy << 1 | dx) == (n == 2 ? 2 : n == 3 ? 4 : n == 4 ? 3 : n == 5 ? 5 : 6)
+    MC_FAR_OWNERS(MC_NEED)
+    static_assert(true MC_FAR_OWNERS(MC_AT), "the rows below pair the owners by their offsets in MC_FAR_OWNERS");
+#undef MC_NEED
+#undef MC_AT
+    u32 cc;
+    const u64 seg0 = seg_of_key(key, g, cc), spr = (u64)g.segs_per_row;
+    const u64 segA = seg0 + spr, segB = seg0 + (u64)g.Ny * spr, segC = segB + spr;    // rows (y+1), (z+1), (z+1, y+1)
+    u32x2u aaA = {0u, 0u}, aaB = {0u, 0u}, aaC = {0u, 0u};        // (offset, next offset): one 8-byte, 4-byte aligned load
+    Rec4 recA = {{0, 0, 0, 0}}, recB = {{0, 0, 0, 0}}, recC = {{0, 0, 0, 0}};
+    if (need2 || need4) { aaA = *(const u32x2u *)(seg_aoff + segA); recA = load_rec(seg_act, (int64_t)segA); }
+    if (need3 || need5) { aaB = *(const u32x2u *)(seg_aoff + segB); recB = load_rec(seg_act, (int64_t)segB); }
+    if (need6) { aaC = *(const u32x2u *)(seg_aoff + segC); recC = load_rec(seg_act, (int64_t)segC); }
+    const bool last = (cc & 255u) == 255u;                        // (x+1) is voxel 0 of the next segment
+    u32 rank;
+    // owner n0 at this column, owner n1 at the next one; the record of an empty segment is garbage (never written): masked
+#define MC_PAIR(aa, rec, seg, n0, n1)                                                                                      \
+    have[n0] = need##n0 && seg_rank(rec, cc, rank) && aa.x != aa.y;                                                        \
+    pos[n0] = have[n0] ? aa.x + rank : i;                                                                                 \
+    have[n1] = false;                                                                                                     \
+    if (need##n1) {                                                                                                       \
+        if (!last) {                                                                                                      \
+            have[n1] = seg_rank(rec, cc + 1u, rank) && aa.x != aa.y;                                                      \
+            rank += aa.x;                                                                                                 \
+        } else {                                                                                                          \
+            const u32x2u ab = *(const u32x2u *)(seg_aoff + seg + 1);                                                      \
+            const Rec4 rb = load_rec(seg_act, (int64_t)seg + 1);                                                          \
+            have[n1] = ab.x != ab.y && (rb.b[0] & 1ull) != 0;                                                             \
+            rank = ab.x;                                                                                                  \
+        }                                                                                                                 \
+    }                                                                                                                     \
+    pos[n1] = have[n1] ? rank : i;
+    MC_PAIR(aaA, recA, segA, 2, 4)
+    MC_PAIR(aaB, recB, segB, 3, 5)
+#undef MC_PAIR
+    have[6] = need6 && seg_rank(recC, cc, rank) && aaC.x != aaC.y;
+    pos[6] = have[6] ? aaC.x + rank : i;
 }
 
 __global__ __launch_bounds__(256) void mc_emit_kernel(const float *__restrict__ field, const McGrid g,
@@ -647,8 +671,9 @@ __global__ __launch_bounds__(256) void mc_emit_kernel(const float *__restrict__ 
         base[1] = vox_voff[in];
         if (!((used & mc_owner_edges(1)) != 0 && kn == key + 4ull)) { base[1] = 0xffffffffu; fl[1] = 0; }
     }
-    {   // The five far owners: the phases of far_owner_positions as loops over arrays, then flags / vertex base.  (Each of the
-        // two kernels keeps its 5 waves per SIMD only in its own form: that function costs 97 VGPRs here, these loops 98 there.)
+    {   // The five far owners, one lookup each, in phases as loops over arrays, then flags / vertex base.  (Each of the
+        // two kernels kept its 5 waves per SIMD only in its own form: five lookups as scalars per owner cost 97 VGPRs here, these loops 98
+        // in the faces kernel, which has since gone to one lookup per row of owners, far_owner_positions.)
 #define MC_NEED(n, dz, dy, dx) (used & mc_owner_edges(n)) != 0,
 #define MC_OKEY(n, dz, dy, dx) make_key(c.row + dy + dz * (int64_t)g.Ny, c.X + dx, 0),
         const bool need[5] = {MC_FAR_OWNERS(MC_NEED)};
@@ -1226,25 +1251,30 @@ __global__ __launch_bounds__(MC3_BLK) void mc3_faces_kernel(const McGrid g, cons
     int32_t id0 = -1, id1 = -1, id2 = -1, id3 = -1, id4 = -1, id5 = -1, id6 = -1, id7 = -1, id8 = -1, id9 = -1, id10 = -1, id11 = -1,
             id12 = -1;
     bool bad = false;
+    // everything this lane reads from the list by its own position is fetched up front, none of it behind the triangle count
+    // (entries without triangles are border cells: few): one load level, then the owner lookups, then the table gathers
+    int32_t til = 0;
+    u32 loc = 0, used = 0;
+    u64 key = 0, keyx = 0;
+    const int64_t inx = (u64)(i + 1) < na ? i + 1 : i;
     if (i < cap && (u64)i < na) {
-        const int32_t til = vox_til[i];
+        til = vox_til[i];
+        loc = vox_loc[i];
+        key = vox_key[i];
+        keyx = vox_key[inx];
+        used = vox_used[i];
         ntri = til & 15;
         tris = (const signed char *)((intptr_t)LUT_TILING1 + (intptr_t)(til >> 4));
     }
     if (ntri > 0) {
-        tloc = MC3_LOC_T(vox_loc[i]);
-        const u64 key = vox_key[i];
-        const u32 used = vox_used[i];
+        tloc = MC3_LOC_T(loc);
         // list position of the owner voxel of each of the 13 possible vertices (MC_EDGES)
         u32 pos[7];
         bool have[7];
         pos[0] = (u32)i;
         have[0] = true;
-        {   // (x+1, y, z) is the next list entry if it is active at all
-            const int64_t inx = (u64)(i + 1) < na ? i + 1 : i;
-            pos[1] = (u32)inx;
-            have[1] = vox_key[inx] == key + 4ull;
-        }
+        pos[1] = (u32)inx;                                       // (x+1, y, z) is the next list entry if it is active at all
+        have[1] = keyx == key + 4ull;
         far_owner_positions(g, key, used, (u32)i, seg_act, seg_aoff, pos, have);
 #define MC_E(e, o, sl)                                                                                                    \
         if (used & (1u << e)) { if (have[o]) id##e = table[(int64_t)pos[o] * 4 + sl]; else bad = true; }
