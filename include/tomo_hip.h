@@ -340,6 +340,48 @@ int tomo_cc_surface_hist(const uint64_t *bits, int nz, int ny, int nx, const uin
 int tomo_cc_surface(const int64_t *table, int64_t cap, unsigned long long *tot, const uint8_t *sel, const uint64_t *off,
                     const uint32_t *slot, const uint64_t *surf, int64_t hist_cap, const double *F, int nz, int directions,
                     double *out, int64_t *counts, int64_t *labels, int64_t cap_sel, void *stream);
+/* Inscribed sphere and local thickness per component (no counterpart in the reference).  Distance and local thickness are local
+ * to a component: the nearest site of a voxel of component A is never a voxel of another component (stepping from such a site
+ * towards the voxel ends at an unset voxel that is no farther), and the open digital ball round a centre where it fits is
+ * 6-connected through set voxels.  So D2 of the whole volume equals D2 of the mask `labels == c` under that mask, bit for bit,
+ * and so does the level map; ONE transform serves every component -- and every cavity, on the tables of the complement -- and
+ * what is left is a reduction of a per-voxel value over the run tables.  One wave per 64-bit word of a row, one lane per bit: the
+ * per-voxel array is read in whole rows; the runs of the word and their components are wave-uniform.  The value of a set voxel
+ * is v = (float)sqrt(d2): read from dist, the float32 map of tomo_edt_distance, or formed from d2, the float64 map of
+ * tomo_edt_squared -- the same bits; exactly one of the two is not NULL.  Integer min / max / add atomics only: the same bytes
+ * on every run.
+ *   tomo_cc_value_max    best uint32[cap], zeroed here: best[c] = the largest float32 bit pattern of v over component c + 1 (v >=
+ *                        0: unsigned order is float order); per run of a word one wave maximum and one atomicMax
+ *   tomo_cc_value_first  after tomo_cc_value_max, on the same arrays: first uint64[cap], set to all ones here: first[c] = the
+ *                        smallest flat index (z * ny + y) * nx + x whose v has the bits best[c]; per run one 64-bit atomicMin
+ *   tomo_cc_value_rows   out int64[cap_sel][4] row slot[c] = (c + 1, voxels, best[c], first[c]) for the components tomo_cc_select
+ *                        selected (sel, slot, tot[5]); tot[5] > cap_sel: bit 1 of tot[2], nothing is written
+ *   tomo_cc_level_hist   hist uint64[(levels + 1) * hist_cap], zeroed here: hist[(levels + 1) * (off[c] + z - zmin[c]) + l] = the
+ *                        voxels of selected component c + 1 in slice z whose entry of level, the int32 (nz, ny, nx) level map of
+ *                        the local thickness (tomo_edt_cover), is l; an entry outside 0 .. levels counts as 0.  Inside a run the
+ *                        lanes of one level add once.  tot[4] > hist_cap: bit 1 of tot[2] and nothing is added; a slice outside
+ *                        the component's box or a run id outside the tables: bit 2
+ *   tomo_cc_level_sums   per selected component and level l its slices in ascending z, w = device float64[nz]: voxels
+ *                        int64[cap_sel][levels + 1] row slot[c] = the counts summed; volume float64[cap_sel][levels] entry l - 1
+ *                        = acc, acc = acc + (double)count * w[z], sequential float64, never contracted (tomo_cc_zsums'
+ *                        discipline); labels int64[cap_sel] entry slot[c] = c + 1.  tot[4] > hist_cap or tot[5] > cap_sel: bit 1
+ *                        of tot[2], nothing is written
+ * TOMO_E_ARG for a null pointer, a non-positive size, levels < 0, both or neither of dist and d2; TOMO_E_SIZE from 2^31 words,
+ * runs, components or selected components on (2^60 / (levels + 1) histogram entries). */
+int tomo_cc_value_max(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
+                      const uint32_t *rank, unsigned long long *tot, const float *dist, const double *d2, uint32_t *best,
+                      int64_t cap, void *stream);
+int tomo_cc_value_first(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                        const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const float *dist, const double *d2,
+                        const uint32_t *best, uint64_t *first, int64_t cap, void *stream);
+int tomo_cc_value_rows(const int64_t *table, const uint32_t *best, const uint64_t *first, int64_t cap, unsigned long long *tot,
+                       const uint8_t *sel, const uint32_t *slot, int64_t *out, int64_t cap_sel, void *stream);
+int tomo_cc_level_hist(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
+                       const uint32_t *rank, unsigned long long *tot, const int64_t *table, int64_t cap, const uint8_t *sel,
+                       const uint64_t *off, uint64_t *hist, int64_t hist_cap, const int32_t *level, int levels, void *stream);
+int tomo_cc_level_sums(const int64_t *table, int64_t cap, unsigned long long *tot, const uint8_t *sel, const uint64_t *off,
+                       const uint32_t *slot, const uint64_t *hist, int64_t hist_cap, const double *w, int nz, int levels,
+                       int64_t *voxels, double *volume, int64_t *labels, int64_t cap_sel, void *stream);
 /* The same across Z-slabs (slab_components.py): rank r labels its slab with the functions above (n_r components); local
  * component c has the global id base_r + c, base_r = n_0 + .. + n_(r-1).  Pieces that touch across a cut are united, the roots
  * (smallest id = the piece with the component's first voxel) numbered in ascending id: scipy's numbering of the whole stack.

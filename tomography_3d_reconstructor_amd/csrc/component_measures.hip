@@ -1,6 +1,7 @@
 // component_measures.hip -- what is measured per component on the run tables of components.hip: the measurement table
 // (voxels, box, index sums), the selection and its slice histograms (voxels, or six moment sums, per component and slice),
-// volume and centroid in mm, second moments and principal axes, Euler number, cavities and handles, surface area (Crofton).
+// volume and centroid in mm, second moments and principal axes, Euler number, cavities and handles, surface area (Crofton),
+// and what a per-voxel array gives per component (the inscribed sphere from the distance map, voxels per thickness level).
 // Every pass over the rows is an accumulator for the row pass of cc_runs.h -- over the runs, or, where a voxel's neighbours
 // decide (Euler number, surface area), over the words of the row with windows of the neighbour rows slid along; the integer
 // tables are integer atomics only, the float results are sequential sums over those integers (nothing is contracted in this
@@ -1260,5 +1261,276 @@ TOMO_API int tomo_cc_surface(const int64_t *table, int64_t cap, unsigned long lo
                        (hipStream_t)stream, (const u64 *)table, (const u64 *)tot, cap, sel, (const u64 *)off, (const u32 *)slot,
                        (const u64 *)surf, hist_cap, F, nz, directions, out, (u64 *)counts, labels, cap_sel,
                        tot ? (u64 *)tot + 2 : (u64 *)nullptr);
+    return tomo_status();
+}
+
+// ---------------------------------------------------------------------------------------------- per-voxel values: inscribed sphere, thickness
+// What a per-voxel array gives per component: the maximum of the inside distance with the first voxel that attains it (the
+// inscribed sphere), and the voxels per slice and thickness level.  Distance and local thickness are local to a component --
+// the nearest site of a voxel of A is never a voxel of another component, and a ball that fits lies in the component of its
+// centre -- so ONE transform of the whole volume serves every component, and what is left is a reduction over the run tables.
+// The WORD PASS: one wave per 64-bit word of a row, one lane per bit (edt_at_least_kernel's shape), so that the per-voxel array
+// is read in whole 256- or 512-byte rows.  The runs that touch the word are walked by all lanes together (CcWordRuns: the word,
+// hence every run and its component, is wave-uniform); a lane takes part under the run's mask.
+struct CcWordAt {
+    int64_t row;                                            // z * ny + y
+    int wj, bit;                                            // the word of the row, the lane's bit: x = 64 * wj + bit
+    u64 cur;                                                // the word, tail bits clear
+    CcWordRuns it;                                          // its runs
+};
+
+// -> false: the wave has no word, or a word without a set bit (wave-uniform)
+__device__ static inline bool cc_word_at(const u64 *__restrict__ bits, int64_t nwords, int nx, int wx, const u32 *__restrict__ row_off,
+                                         CcWordAt &a)
+{
+    const int64_t t = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    const int64_t word = t >> 6;                            // the same for the 64 lanes of a wave
+    if (word >= nwords) return false;
+    a.row = word / wx;
+    a.wj = (int)(word - a.row * wx);
+    a.bit = (int)(t & 63);
+    const u64 *r = bits + a.row * wx;
+    a.cur = cc_word(r, nx, wx, a.wj);
+    if (!a.cur) return false;
+    a.it = {a.cur, cc_before(r, nx, wx, a.wj, row_off[a.row]), a.wj > 0 && (r[a.wj - 1] >> 63) != 0, 0, 0};
+    return true;
+}
+
+// the float32 bits of the value of a SET voxel: the distance map itself, or (float)sqrt(d2) -- what EDT_TAIL_FLOAT stores
+__device__ static inline u32 cc_value_bits(const float *__restrict__ dist, const double *__restrict__ d2, int64_t at)
+{
+    return __float_as_uint(dist ? dist[at] : (float)sqrt(d2[at]));
+}
+
+// best[c] = the largest float32 bit pattern over component c + 1 (values >= 0: unsigned order is float order); FIRST: first[c] =
+// the smallest flat index whose value has the bits best[c].  Per run of the word one wave reduction and at most one atomic: a
+// maximum that does not beat what best[c] already holds is not sent (one solid body would otherwise queue every word of the
+// volume on one address), and only the runs that attain the maximum send an index.
+template <bool FIRST>
+__global__ __launch_bounds__(CC_THREADS) void cc_value_kernel(const u64 *__restrict__ bits, int64_t nwords, int nx, int wx,
+                                                              const u32 *__restrict__ row_off, const u64 *__restrict__ tot,
+                                                              int64_t cap_runs, const u32 *__restrict__ parent,
+                                                              const u32 *__restrict__ rank, const float *__restrict__ dist,
+                                                              const double *__restrict__ d2, u32 *best,
+                                                              unsigned long long *__restrict__ first, int64_t cap, u64 *flags)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0 && tot[1] > (u64)cap) cc_flag(flags, CC_F_CAP);
+    CcWordAt a;
+    if (!cc_word_at(bits, nwords, nx, wx, row_off, a)) return;
+    const u32 nruns = (u32)cc_count(tot, cap_runs), ncomp = (u32)cc_ncomp(tot, cap);
+    const bool set = (a.cur >> a.bit) & 1;
+    const int64_t at = a.row * nx + 64 * a.wj + a.bit;      // a set bit lies below nx: inside the array
+    const u32 v = set ? cc_value_bits(dist, d2, at) : 0u;
+    while (cc_word_runs_next(a.it)) {                       // wave-uniform
+        if (a.it.run >= nruns) {
+            if (a.bit == 0) cc_flag(flags, CC_F_RANGE);
+            continue;
+        }
+        const u32 c = cc_component(parent, rank, a.it.run);
+        if (c >= ncomp) continue;                           // more components than the tables hold: CC_F_CAP, above
+        const bool mine = (a.it.mask >> a.bit) & 1;
+        if constexpr (!FIRST) {
+            const u32 top = wave_max32(mine ? v : 0u);          // best[c] only rises: a stale read costs an atomic, never the answer
+            if (a.bit == 0 && top > cc_load(best + c)) atomicMax(best + c, top);
+        } else {
+            const u64 hit = __ballot(mine && v == best[c]);
+            if (hit && a.bit == 0) atomicMin(first + c, (unsigned long long)(at + (__ffsll((long long)hit) - 1)));
+        }
+    }
+}
+
+static int cc_value_launch(bool first_pass, const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                           const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const float *dist, const double *d2,
+                           uint32_t *best, uint64_t *first, int64_t cap, void *stream)
+{
+    int64_t nrows;
+    int wx;
+    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
+    if (g != TOMO_OK) return g;
+    if (!row_off || !parent || !rank || !tot || !best || (first_pass && !first) || cap_runs <= 0 || cap <= 0 || (dist != nullptr) == (d2 != nullptr))
+        return TOMO_E_ARG;
+    if (cap_runs >= ((int64_t)1 << 31) || cap >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t nwords = nrows * wx;                      // < 2^31 (cc_geometry): the grid has fewer than 2^29 workgroups
+    const dim3 grid((unsigned)ceil_div64(nwords * 64, CC_THREADS)), block(CC_THREADS);
+    if (!first_pass) {
+        if (hipMemsetAsync(best, 0, (size_t)cap * sizeof(u32), st) != hipSuccess) return TOMO_E_LAUNCH;
+        hipLaunchKernelGGL(cc_value_kernel<false>, grid, block, 0, st, (const u64 *)bits, nwords, nx, wx, (const u32 *)row_off,
+                           (const u64 *)tot, cap_runs, (const u32 *)parent, (const u32 *)rank, dist, d2, (u32 *)best,
+                           (unsigned long long *)nullptr, cap, (u64 *)tot + 2);
+    } else {
+        if (hipMemsetAsync(first, 0xff, (size_t)cap * sizeof(u64), st) != hipSuccess) return TOMO_E_LAUNCH;
+        hipLaunchKernelGGL(cc_value_kernel<true>, grid, block, 0, st, (const u64 *)bits, nwords, nx, wx, (const u32 *)row_off,
+                           (const u64 *)tot, cap_runs, (const u32 *)parent, (const u32 *)rank, dist, d2, (u32 *)best,
+                           (unsigned long long *)first, cap, (u64 *)tot + 2);
+    }
+    return tomo_status();
+}
+
+TOMO_API int tomo_cc_value_max(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                               const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const float *dist,
+                               const double *d2, uint32_t *best, int64_t cap, void *stream)
+{
+    return cc_value_launch(false, bits, nz, ny, nx, row_off, cap_runs, parent, rank, tot, dist, d2, best, nullptr, cap, stream);
+}
+
+TOMO_API int tomo_cc_value_first(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                                 const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const float *dist,
+                                 const double *d2, const uint32_t *best, uint64_t *first, int64_t cap, void *stream)
+{
+    if ((const void *)best == (const void *)first) return TOMO_E_ARG;
+    return cc_value_launch(true, bits, nz, ny, nx, row_off, cap_runs, parent, rank, tot, dist, d2, (uint32_t *)best, first, cap, stream);
+}
+
+// out[slot[c]] = (c + 1, voxels, best[c], first[c]) for every selected component c (sel, slot, tot[5]: tomo_cc_select)
+__global__ __launch_bounds__(CC_THREADS) void cc_value_rows_kernel(const u64 *__restrict__ table, const u32 *__restrict__ best,
+                                                                   const u64 *__restrict__ first, const u64 *__restrict__ tot,
+                                                                   int64_t cap, const uint8_t *__restrict__ sel,
+                                                                   const u32 *__restrict__ slot, u64 *__restrict__ out, int64_t cap_sel,
+                                                                   u64 *flags)
+{
+    const int64_t c = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    const bool fits = tot[5] <= (u64)cap_sel && tot[1] <= (u64)cap;
+    if (c == 0 && !fits) cc_flag(flags, CC_F_CAP);
+    if (!fits || c >= cc_ncomp(tot, cap) || !sel[c]) return;
+    const u32 k = slot[c];
+    if ((int64_t)k >= cap_sel) {
+        cc_flag(flags, CC_F_RANGE);
+        return;
+    }
+    u64 *o = out + 4 * (int64_t)k;
+    o[0] = (u64)c + 1;
+    o[1] = table[c * CC_COLS];
+    o[2] = best[c];
+    o[3] = first[c];
+}
+
+TOMO_API int tomo_cc_value_rows(const int64_t *table, const uint32_t *best, const uint64_t *first, int64_t cap, unsigned long long *tot,
+                                const uint8_t *sel, const uint32_t *slot, int64_t *out, int64_t cap_sel, void *stream)
+{
+    if (!table || !best || !first || !tot || !sel || !slot || !out || cap <= 0 || cap_sel <= 0) return TOMO_E_ARG;
+    if (cap >= ((int64_t)1 << 31) || cap_sel >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
+    hipLaunchKernelGGL(cc_value_rows_kernel, dim3((unsigned)ceil_div64(cap, CC_THREADS)), dim3(CC_THREADS), 0, (hipStream_t)stream,
+                       (const u64 *)table, (const u32 *)best, (const u64 *)first, (const u64 *)tot, cap, sel, (const u32 *)slot,
+                       (u64 *)out, cap_sel, (u64 *)tot + 2);
+    return tomo_status();
+}
+
+// hist[(K + 1) * (off[c] + z - zmin[c]) + level] += 1 for every set voxel of a selected component; level: the int32 level map of
+// the local thickness, outside 0 .. K it counts as 0.  The word pass; inside a run the lanes are aggregated by level: the first
+// lane still to count names its level, the lanes that share it are balloted, the leader adds their number, they retire -- a
+// solid body costs one or two atomics per word, not 64.
+__global__ __launch_bounds__(CC_THREADS) void cc_level_hist_kernel(const u64 *__restrict__ bits, int64_t nwords, int ny, int nx, int wx,
+                                                                   const u32 *__restrict__ row_off, const u64 *__restrict__ tot,
+                                                                   int64_t cap_runs, const u32 *__restrict__ parent,
+                                                                   const u32 *__restrict__ rank, const u64 *__restrict__ table,
+                                                                   int64_t cap, const uint8_t *__restrict__ sel,
+                                                                   const u64 *__restrict__ off, unsigned long long *__restrict__ hist,
+                                                                   int64_t hist_cap, const int32_t *__restrict__ level, int K, u64 *flags)
+{
+    const u64 total = tot[4];
+    const bool fits = total <= (u64)hist_cap;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && (!fits || tot[1] > (u64)cap)) cc_flag(flags, CC_F_CAP);
+    if (!fits) return;                                      // a histogram that is too short: nothing is touched
+    CcWordAt a;
+    if (!cc_word_at(bits, nwords, nx, wx, row_off, a)) return;
+    const u32 nruns = (u32)cc_count(tot, cap_runs), ncomp = (u32)cc_ncomp(tot, cap);
+    const bool set = (a.cur >> a.bit) & 1;
+    int l = set ? level[a.row * nx + 64 * a.wj + a.bit] : 0;
+    if ((unsigned)l > (unsigned)K) l = 0;                   // nothing writes such a level; never index past the entry
+    const u64 z = (u64)(a.row / ny);
+    while (cc_word_runs_next(a.it)) {                       // wave-uniform
+        if (a.it.run >= nruns) {
+            if (a.bit == 0) cc_flag(flags, CC_F_RANGE);
+            continue;
+        }
+        const u32 c = cc_component(parent, rank, a.it.run);
+        if (c >= ncomp || !sel[c]) continue;
+        const u64 z0 = table[(int64_t)c * CC_COLS + 1], z1 = table[(int64_t)c * CC_COLS + 2];
+        const u64 pos = off[c] + (z - z0);
+        if (z < z0 || z > z1 || pos >= total) {             // a slice outside the component's box: the bits changed
+            if (a.bit == 0) cc_flag(flags, CC_F_RANGE);
+            continue;
+        }
+        unsigned long long *entry = hist + (u64)(K + 1) * pos;
+        u64 left = a.it.mask;                               // the lanes still to count, wave-uniform
+        while (left) {                                      // every turn retires at least the leader: at most 64 turns
+            const int leader = __ffsll((long long)left) - 1;
+            const int ll = __shfl(l, leader, 64);
+            const u64 same = __ballot(l == ll) & left;
+            if (a.bit == leader) atomicAdd(entry + ll, (unsigned long long)__popcll(same));
+            left &= ~same;
+        }
+    }
+}
+
+TOMO_API int tomo_cc_level_hist(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                                const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const int64_t *table, int64_t cap,
+                                const uint8_t *sel, const uint64_t *off, uint64_t *hist, int64_t hist_cap, const int32_t *level,
+                                int levels, void *stream)
+{
+    int64_t nrows;
+    int wx;
+    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
+    if (g != TOMO_OK) return g;
+    if (!row_off || !parent || !rank || !tot || !table || !sel || !off || !hist || !level || cap_runs <= 0 || cap <= 0 ||
+        hist_cap <= 0 || levels < 0 || (const void *)hist == (const void *)level)
+        return TOMO_E_ARG;
+    if (cap_runs >= ((int64_t)1 << 31) || cap >= ((int64_t)1 << 31) || hist_cap >= ((int64_t)1 << 60) / ((int64_t)levels + 1))
+        return TOMO_E_SIZE;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(hist, 0, (size_t)hist_cap * ((size_t)levels + 1) * sizeof(u64), st) != hipSuccess) return TOMO_E_LAUNCH;
+    const int64_t nwords = nrows * wx;
+    hipLaunchKernelGGL(cc_level_hist_kernel, dim3((unsigned)ceil_div64(nwords * 64, CC_THREADS)), dim3(CC_THREADS), 0, st,
+                       (const u64 *)bits, nwords, ny, nx, wx, (const u32 *)row_off, (const u64 *)tot, cap_runs, (const u32 *)parent,
+                       (const u32 *)rank, (const u64 *)table, cap, sel, (const u64 *)off, (unsigned long long *)hist, hist_cap, level,
+                       levels, (u64 *)tot + 2);
+    return tomo_status();
+}
+
+// One thread per (component, level); a selected component walks its slices in ascending z: voxels[slot[c]][level] = the sum of the
+// counts, volume[slot[c]][level - 1] = acc, acc = acc + (double)count * w[z], plain sequential float64 (cc_zsums_kernel's
+// discipline: the float a host loop over ALL slices of the mask gives, the slices outside the box add 0.0 there).
+__global__ __launch_bounds__(CC_THREADS) void cc_level_sums_kernel(const u64 *__restrict__ table, const u64 *__restrict__ tot,
+                                                                   int64_t cap, const uint8_t *__restrict__ sel,
+                                                                   const u64 *__restrict__ off, const u32 *__restrict__ slot,
+                                                                   const u64 *__restrict__ hist, int64_t hist_cap,
+                                                                   const double *__restrict__ w, int nz, int K,
+                                                                   u64 *__restrict__ voxels, double *__restrict__ volume,
+                                                                   int64_t *__restrict__ labels, int64_t cap_sel, u64 *flags)
+{
+    const int64_t t = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    const int64_t c = t / (K + 1);
+    const int level = (int)(t - c * (K + 1));
+    if (c >= cap) return;
+    CcSegment s;
+    if (!cc_segment(table, tot, cap, sel, off, slot, hist_cap, nz, cap_sel, c, flags, s)) return;
+    const u64 *m = hist + (u64)(K + 1) * s.o + level;
+    u64 n = 0;
+    double acc = 0.0;
+    for (u64 z = s.z0; z <= s.z1; z++) {
+        const u64 count = m[(u64)(K + 1) * (z - s.z0)];
+        n += count;
+        acc = acc + (double)count * w[z];
+    }
+    voxels[(int64_t)(K + 1) * s.k + level] = n;
+    if (level > 0) volume[(int64_t)K * s.k + (level - 1)] = acc;
+    else labels[s.k] = c + 1;
+}
+
+TOMO_API int tomo_cc_level_sums(const int64_t *table, int64_t cap, unsigned long long *tot, const uint8_t *sel, const uint64_t *off,
+                                const uint32_t *slot, const uint64_t *hist, int64_t hist_cap, const double *w, int nz, int levels,
+                                int64_t *voxels, double *volume, int64_t *labels, int64_t cap_sel, void *stream)
+{
+    if (!table || !tot || !sel || !off || !slot || !hist || !w || !voxels || !labels || cap <= 0 || hist_cap <= 0 || nz <= 0 ||
+        cap_sel <= 0 || levels < 0 || (levels > 0 && !volume))
+        return TOMO_E_ARG;
+    const int64_t per = (int64_t)levels + 1;
+    if (cap >= ((int64_t)1 << 31) || cap_sel >= ((int64_t)1 << 31) || hist_cap >= ((int64_t)1 << 60) / per ||
+        ceil_div64(cap * per, CC_THREADS) >= ((int64_t)1 << 31))
+        return TOMO_E_SIZE;
+    hipLaunchKernelGGL(cc_level_sums_kernel, dim3((unsigned)ceil_div64(cap * per, CC_THREADS)), dim3(CC_THREADS), 0,
+                       (hipStream_t)stream, (const u64 *)table, (const u64 *)tot, cap, sel, (const u64 *)off, (const u32 *)slot,
+                       (const u64 *)hist, hist_cap, w, nz, levels, (u64 *)voxels, volume, labels, cap_sel, (u64 *)tot + 2);
     return tomo_status();
 }

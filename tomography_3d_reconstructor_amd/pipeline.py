@@ -25,7 +25,7 @@ COUNTERS = dict.fromkeys(("na_hint_hit", "na_hint_miss", "mc3_hint_hit", "mc3_hi
                           "slab_components_expand", "slab_components_filter", "distance_transform", "distance_offset",
                           "components_measure", "components_zhist", "components_moments", "components_euler",
                           "components_cavities", "local_thickness", "opening_volume", "components_surface", "components_fill",
-                          "components_cavity_owners"), 0)
+                          "components_cavity_owners", "component_thickness", "components_value", "components_levels"), 0)
 NA_HINTS = os.environ.get("TOMO_NA_HINTS", "1") not in ("", "0")   # marching_cubes: launch ahead of the first count download
 _NA_HINT = {}
 LIST_LIMIT = 2 ** 31        # active-voxel list entries / vertices / triangles one pass can index (int32 offsets in mc.hip, mesh.hip);
@@ -332,8 +332,8 @@ class ComponentRuns:
     """The run tables of one BitVolume under one connectivity: scipy.ndimage.label's components, held per X-RUN (a maximal
     run of set bits in a row) and never per voxel.  Two host reads: the number of runs (it sizes the tables) and the
     counters after the labelling.  n = components; labels() / sizes() / keep() read the tables.
-    One object serves every per-component measurement of its volume: properties(), moments(), topology_rows() and surface()
-    share the labelling, the measurement table and ONE selection, which the object owns (select).  background() is the same
+    One object serves every per-component measurement of its volume: properties(), moments(), topology_rows(), surface() and
+    thickness() share the labelling, the measurement table and ONE selection, which the object owns (select).  background() is the same
     kind of object for the complement: its enclosed components are the cavities of this volume (cavity_owners)."""
 
     def __init__(self, vol: BitVolume, connectivity=6):
@@ -457,22 +457,28 @@ class ComponentRuns:
             raise _lib.TomoError("%s: the tables do not fit the volume (flags %d)" % (name, flags[0]))
         return host
 
-    def _rows(self, spec: _Measurement, rule, host_table, *scalars):
+    @staticmethod
+    def _hist_budget(spec: _Measurement, picked: ComponentSelection):
+        """TomoError where the histogram of the selection takes more than COMPONENT_HIST_BUDGET bytes; nothing is allocated here."""
+        nbytes = 8 * spec.words * picked.total
+        if nbytes > COMPONENT_HIST_BUDGET and picked.m > 1:         # read when called; one component is always granted
+            raise _lib.TomoError("%s: %d components selected, their %s take %d bytes, more than COMPONENT_HIST_BUDGET (%d): raise "
+                                 "min_voxels" % (spec.name, picked.m, spec.what, nbytes, COMPONENT_HIST_BUDGET))
+
+    def _rows(self, spec: _Measurement, rule, host_table, *scalars, hist_args=()):
         """One measurement of the components the rule (_keep_rule's tuple) selects: spec.words uint64 per slice of every selected component's box
         from spec.hist, then spec.finish with one thread per component -> the host arrays (table columns, labels, *results),
         spec.empty() when nothing is selected.  host_table: the float64 table(s) the finishing kernel reads, uploaded here;
-        scalars: its arguments between nz and the result tensors."""
+        scalars: its arguments between nz and the result tensors; hist_args: what spec.hist takes behind the histogram's capacity."""
         picked = self.select(rule[0], rule[1], max_voxels=rule[2], enclosed=rule[3])
         if picked is None or picked.total == 0:
             return spec.empty()
-        total, m, nbytes = picked.total, picked.m, 8 * spec.words * picked.total
-        if nbytes > COMPONENT_HIST_BUDGET and m > 1:                # read when called; one component is always granted
-            raise _lib.TomoError("%s: %d components selected, their %s take %d bytes, more than COMPONENT_HIST_BUDGET (%d): raise "
-                                 "min_voxels" % (spec.name, m, spec.what, nbytes, COMPONENT_HIST_BUDGET))
+        self._hist_budget(spec, picked)
+        total, m = picked.total, picked.m
         L, dev, st = _lib.lib(), self.vol.device, _stream()
         hist = torch.empty(spec.words * total, dtype=torch.int64, device=dev)
         COUNTERS[spec.counter] += 1
-        _lib.check(getattr(L, spec.hist)(*self.hist_head(picked), _p(hist), total, st), spec.hist)
+        _lib.check(getattr(L, spec.hist)(*self.hist_head(picked), _p(hist), total, *hist_args, st), spec.hist)
         tab = torch.from_numpy(host_table).to(dev).view(spec.tables, -1)
         results = []
         for dtype, shape in spec.results:
@@ -510,6 +516,52 @@ class ComponentRuns:
         _lib.check(_lib.lib().tomo_cc_topology_rows(_p(picked.table), _p(topo), topo.shape[0], _p(self.tot), _p(picked.sel), _p(picked.slot),
                                                     _p(rows), picked.m, _stream()), "tomo_cc_topology_rows")
         return _component_topology_from(*self._download_checked(_TOPOLOGY.name, rows))
+
+    def thickness(self, slice_depths, mm_y, mm_x, radii_mm=None, min_voxels=0, largest=False, *, max_voxels=None,
+                  enclosed=False) -> "ComponentThickness":
+        """component_thickness of this volume.  The rule: select's.  ONE transform of the whole volume (distance and local
+        thickness are local to a component), then reductions over the run tables: the value passes for the inscribed sphere
+        and, with radii_mm, the level histogram behind the driver of the other measurements.  On background() with
+        enclosed=True the rows are the cavities: their pore sizes."""
+        rule = _keep_rule(min_voxels, largest, max_voxels, enclosed)
+        radii, weights = _component_thickness_args(self.vol.shape, slice_depths, mm_y, mm_x, radii_mm)
+        COUNTERS["component_thickness"] += 1
+        picked = self.select(rule[0], rule[1], max_voxels=rule[2], enclosed=rule[3])
+        if picked is None:
+            return _component_thickness_from(self.vol.shape, slice_depths, mm_y, mm_x, np.zeros((0, 4), dtype=np.int64), radii)
+        spec = None if radii is None else _thickness_measurement(len(radii))
+        if spec is not None:
+            self._hist_budget(spec, picked)                             # before the transform allocates anything
+        L, dev, st = _lib.lib(), self.vol.device, _stream()
+        plan = _DistancePlan(BitVolume(self.bits, self.vol.shape), slice_depths, mm_y, mm_x)
+        n = picked.table.shape[0]
+        dist = d2 = None
+        if radii is None:                                               # 4 B per voxel, no d2
+            dist = torch.empty(self.vol.shape, dtype=torch.float32, device=dev)
+            _lib.check(L.tomo_edt_distance(*plan.head(), 1, _p(dist), *plan.tail()), "tomo_edt_distance")
+        else:                                                           # one float64 transform serves both parts
+            d2 = torch.empty(self.vol.shape, dtype=torch.float64, device=dev)
+            _lib.check(L.tomo_edt_squared(*plan.head(), 1, _p(d2), *plan.tail()), "tomo_edt_squared")
+        best = torch.empty(n, dtype=torch.int32, device=dev)
+        first = torch.empty(n, dtype=torch.int64, device=dev)
+        rows = torch.empty((picked.m, 4), dtype=torch.int64, device=dev)
+        head = (_p(self.bits), *self.vol.shape, *self._tables(), _p(self.tot), _p(dist), _p(d2))
+        COUNTERS["components_value"] += 1
+        _lib.check(L.tomo_cc_value_max(*head, _p(best), n, st), "tomo_cc_value_max")
+        _lib.check(L.tomo_cc_value_first(*head, _p(best), _p(first), n, st), "tomo_cc_value_first")
+        _lib.check(L.tomo_cc_value_rows(_p(picked.table), _p(best), _p(first), n, _p(self.tot), _p(picked.sel), _p(picked.slot),
+                                        _p(rows), picked.m, st), "tomo_cc_value_rows")
+        levels = None
+        if spec is not None:
+            r2 = radii * radii
+            live = int(np.searchsorted(r2, float(d2.max().item()), side="right"))
+            level_map = torch.zeros(self.vol.shape, dtype=torch.int32, device=dev)
+            eroded = torch.empty_like(plan.bits) if live else None
+            _thickness_levels(plan, d2, r2, live, level_map, eroded)
+            del d2
+            levels = self._rows(spec, rule, weights, len(radii), hist_args=(_p(level_map), len(radii)))
+        (host,) = self._download_checked("component_thickness", rows)
+        return _component_thickness_from(self.vol.shape, slice_depths, mm_y, mm_x, host, radii, levels)
 
     def topology(self) -> torch.Tensor:
         """Per component 1..n: Euler number, cavities (enclosed voids, b2) and handles (tunnels, b1 = 1 - euler + cavities) of
@@ -830,6 +882,26 @@ def cavity_table(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_p
         return _cavities_from(runs, _component_properties_from(*_PROPERTIES.empty(), float(mm_per_pixel_y), float(mm_per_pixel_x)))
     p = runs.background().properties(tables, mm_per_pixel_y, mm_per_pixel_x, lo, max_voxels=hi, enclosed=True)
     return _cavities_from(runs, p)
+
+
+def cavity_sizes(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, connectivity=6, min_voxels=0,
+                 max_voxels=None):
+    """cavity_table and, row for row, the pore size of every cavity -> (Cavities, ComponentThickness): the inscribed sphere of
+    the cavity from ComponentRuns.thickness on the complement's tables -- the inside
+    transform of the COMPLEMENT, the `enclosed` rule and the size window.  A cavity touches no face of the stack, so its nearest
+    virtual site outside is never closer than a solid voxel: the numbers are those of the mask of the cavity.  One labelling of
+    the volume and one of the complement serve both answers.  Arguments are checked before the first launch."""
+    connectivity = _check_connectivity(connectivity)
+    lo, hi = _check_size_window(min_voxels, max_voxels)
+    tables = _slice_weights(slice_depths, vol.shape[0], mm_per_pixel_y, mm_per_pixel_x)
+    runs = ComponentRuns(vol, connectivity)
+    if runs.runs == 0:                                                  # nothing encloses anything
+        p = _component_properties_from(*_PROPERTIES.empty(), float(mm_per_pixel_y), float(mm_per_pixel_x))
+        empty = _component_thickness_from(vol.shape, slice_depths, mm_per_pixel_y, mm_per_pixel_x, np.zeros((0, 4), dtype=np.int64))
+        return _cavities_from(runs, p), empty
+    bg = runs.background()
+    p = bg.properties(tables, mm_per_pixel_y, mm_per_pixel_x, lo, max_voxels=hi, enclosed=True)
+    return _cavities_from(runs, p), bg.thickness(slice_depths, mm_per_pixel_y, mm_per_pixel_x, None, lo, max_voxels=hi, enclosed=True)
 
 
 def _cavity_map(vol: BitVolume, connectivity, min_voxels, max_voxels, solid) -> BitVolume:
@@ -1171,6 +1243,129 @@ def _thickness_statistics(radii, level_volume):
     return mean, math.sqrt(var), max(di for wi, di in zip(w, d) if wi > 0)
 
 
+def _thickness_levels(plan: _DistancePlan, d2, r2, live, level_map, eroded):
+    """The level loop local_thickness and ComponentRuns.thickness share: for the first `live` squared radii, ascending, the
+    eroded set {set && d2 >= r2} balloted into `eroded` and its outside transform, whose tail writes the level into the zeroed
+    int32 level_map where it covers a set voxel.  The caller owns both buffers (eroded: None without a live level)."""
+    L = _lib.lib()
+    bits, nzyx, tables = plan.head()[0], plan.head()[1:4], plan.head()[4:]
+    for k in range(live):
+        _lib.check(L.tomo_edt_at_least(_p(d2), bits, *nzyx, float(r2[k]), _p(eroded), _stream()), "tomo_edt_at_least")
+        _lib.check(L.tomo_edt_cover(_p(eroded), bits, *nzyx, *tables, float(r2[k]), k + 1, _p(level_map), *plan.tail()), "tomo_edt_cover")
+
+
+# ----------------------------------------------------------------------------- inscribed sphere and thickness per component
+@dataclass
+class ComponentThickness:
+    """component_thickness' answer: host arrays, one row per selected component in ascending label.  The fields from radii_mm
+    on are None without radii."""
+    labels: np.ndarray             # int64 (m,)
+    voxels: np.ndarray             # int64 (m,)
+    radius_mm: np.ndarray          # float64 (m,): the largest float32 inside distance of the component, widened
+    center_index: np.ndarray       # int64 (m, 3): (k, j, i) of the first voxel in raster order that attains it
+    center_mm: np.ndarray          # float64 (m, 3): that voxel in the coordinates of distance_positions
+    radii_mm: np.ndarray = None            # float64 (K,): the levels, ascending
+    level_voxels: np.ndarray = None        # int64 (m, K): voxels of the component whose level is k
+    level_volume_mm3: np.ndarray = None    # float64 (m, K): their volume under the slice depths
+    uncovered_voxels: np.ndarray = None    # int64 (m,): voxels of the component below radii_mm[0]
+    mean_mm: np.ndarray = None             # float64 (m,): _thickness_statistics per row
+    std_mm: np.ndarray = None
+    max_mm: np.ndarray = None
+
+    def __len__(self):
+        return len(self.labels)
+
+
+def _thickness_measurement(K) -> _Measurement:
+    """The level histogram of K levels as a measurement of ComponentRuns._rows: K + 1 words per slice of a selected box."""
+    return _Measurement("component_thickness", ((torch.int64, (K + 1,)), (torch.float64, (K,))), 0, K + 1,
+                        "voxels per slice and thickness level", "tomo_cc_level_hist", "components_levels", "tomo_cc_level_sums")
+
+
+def _component_thickness_args(shape, slice_depths, mm_per_pixel_y, mm_per_pixel_x, radii_mm):
+    """The argument checks of component_thickness, all on the host -> (radii or None, slice weights): the radii, the depths and
+    pixel sizes, and with radii the memory guard of local_thickness, raised before anything is allocated."""
+    radii = None if radii_mm is None else _check_radii(radii_mm)
+    nz, ny, nx = shape
+    weights = _slice_weights(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x)[:nz]
+    if radii is not None and 8 * nz * ny * nx > LOCAL_THICKNESS_VOLUME_BUDGET:
+        raise ValueError("component_thickness: the squared distances of a %d x %d x %d volume take %d bytes, more than "
+                         "LOCAL_THICKNESS_VOLUME_BUDGET (%d)" % (nz, ny, nx, 8 * nz * ny * nx, LOCAL_THICKNESS_VOLUME_BUDGET))
+    return radii, weights
+
+
+def _thickness_statistics_rows(radii, volume) -> np.ndarray:
+    """_thickness_statistics of every row of volume float64 (m, K) -> float64 (m, 3).  Millions of specks share a handful of
+    level tables, so the rows are grouped first and the statistics computed once per distinct row: a 64-bit mix of the bits of
+    a row is the key (one flat sort), and every row is then compared with the one that stands for its key -- a collision
+    falls back to sorting the rows themselves."""
+    m, K = volume.shape
+    if m == 0:
+        return np.zeros((0, 3), dtype=np.float64)
+    words = volume.view(np.uint64)
+    key = np.zeros(m, dtype=np.uint64)
+    for k in range(K):
+        key = (key ^ words[:, k]) * np.uint64(0x9E3779B97F4A7C15) + np.uint64(k + 1)       # wraps: that is the mix
+    _, first, row = np.unique(key, return_index=True, return_inverse=True)
+    distinct = volume[first]
+    if not np.array_equal(distinct[row].view(np.uint64), words):
+        distinct, row = np.unique(volume, axis=0, return_inverse=True)
+    stats = np.array([_thickness_statistics(radii, v) for v in distinct], dtype=np.float64).reshape(-1, 3)
+    return stats[np.asarray(row).reshape(-1)]
+
+
+def _component_thickness_from(shape, slice_depths, mm_per_pixel_y, mm_per_pixel_x, rows, radii=None, levels=None) -> ComponentThickness:
+    """Host side of the downloaded rows: rows int64 (m, 4) as tomo_cc_value_rows writes them; levels: _rows' download of the
+    level histogram (voxels, labels, level counts (m, K + 1), level volumes (m, K)), None for no selected component."""
+    nz, ny, nx = shape
+    rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1, 4)
+    m = len(rows)
+    flat = rows[:, 3]
+    index = np.stack([flat // (ny * nx), flat // nx % ny, flat % nx], axis=1).astype(np.int64)
+    zt, yt, xt = distance_positions(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x, ny, nx)
+    centre = np.stack([zt[index[:, 0] + 1], yt[index[:, 1] + 1], xt[index[:, 2] + 1]], axis=1).astype(np.float64)
+    out = ComponentThickness(rows[:, 0].copy(), rows[:, 1].copy(), rows[:, 2].astype(np.uint32).view(np.float32).astype(np.float64),
+                             index, centre)
+    if radii is None:
+        return out
+    K = len(radii)
+    if levels is None:
+        counts, volume = np.zeros((0, K + 1), dtype=np.int64), np.zeros((0, K), dtype=np.float64)
+    else:
+        _, labels, counts, volume = levels
+        if not np.array_equal(labels, out.labels):
+            raise _lib.TomoError("component_thickness: the rows of the level histogram are not the rows of the selection")
+    stats = _thickness_statistics_rows(radii, np.ascontiguousarray(volume, dtype=np.float64))
+    out.radii_mm, out.level_voxels, out.level_volume_mm3 = radii, counts[:, 1:].copy(), np.ascontiguousarray(volume)
+    out.uncovered_voxels = counts[:, 0].copy()
+    out.mean_mm, out.std_mm, out.max_mm = stats[:, 0].copy(), stats[:, 1].copy(), stats[:, 2].copy()
+    return out
+
+
+def component_thickness(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, connectivity=6, min_voxels=0,
+                        largest=False, radii_mm=None) -> ComponentThickness:
+    """The inscribed sphere and, with radii_mm, the local thickness per component of a resident volume -> ComponentThickness,
+    one row per component the keep rule of component_properties selects (at least min_voxels voxels; largest: only the largest
+    of those, the lowest label among equals), in ascending label: the rows component_properties returns for the same rule.
+    radius_mm is the maximum of distance_transform(inside=True) over the component and center_index the first voxel in raster
+    order that attains it: inscribed_sphere of the mask `labels == c`, bit for bit.  radii_mm (a strictly ascending list of
+    positive finite radii): level_voxels, level_volume_mm3, uncovered_voxels, mean_mm, std_mm and max_mm are what
+    local_thickness(mask of the component, radii_mm=radii_mm) returns, per row.
+    Neither number needs the mask: the nearest background site of a voxel is never a voxel of ANOTHER component (stepping from it
+    towards the voxel ends at an unset voxel that is no farther), and an open digital ball round a centre where it fits is
+    connected through set voxels, so the transform and the level map of the whole volume, read under the component, are the
+    component's own.  Cost without radii: one float32 inside transform (4 B per voxel) and two passes over it; with radii: ONE
+    float64 transform for both parts, local_thickness' level loop once for the whole volume, and a histogram of K + 1 counters
+    per slice of every selected component's box (beyond COMPONENT_HIST_BUDGET bytes for more than one component: TomoError) --
+    never a transform per component.  With radii the squared distances take 8 B per voxel: beyond
+    LOCAL_THICKNESS_VOLUME_BUDGET a ValueError before anything is allocated.  Integer atomics only: the same bytes on every run.
+    An empty volume, or nothing selected, gives zero rows.  Arguments are checked before the first launch."""
+    _check_connectivity(connectivity)
+    _keep_rule(min_voxels, largest)
+    _component_thickness_args(vol.shape, slice_depths, mm_per_pixel_y, mm_per_pixel_x, radii_mm)
+    return ComponentRuns(vol, connectivity).thickness(slice_depths, mm_per_pixel_y, mm_per_pixel_x, radii_mm, min_voxels, largest)
+
+
 def local_thickness(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, radii_mm=None,
                     max_levels=LOCAL_THICKNESS_MAX_LEVELS) -> LocalThickness:
     """Local thickness (Hildebrand & Ruegsegger) of a resident volume in millimetres -> LocalThickness.
@@ -1227,12 +1422,9 @@ def local_thickness(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_pe
         live = int(np.searchsorted(r2, float(d2.max().item()), side="right"))     # r_k^2 <= the largest D2: a centre exists
     K = len(r2)
     level_map = torch.zeros(vol.shape, dtype=torch.int32, device=dev)
-    if live:
-        eroded = torch.empty_like(plan.bits)
-    bits, nzyx, tables = plan.head()[0], plan.head()[1:4], plan.head()[4:]
-    for k in range(live):
-        _lib.check(L.tomo_edt_at_least(_p(d2), bits, *nzyx, float(r2[k]), _p(eroded), _stream()), "tomo_edt_at_least")
-        _lib.check(L.tomo_edt_cover(_p(eroded), bits, *nzyx, *tables, float(r2[k]), k + 1, _p(level_map), *plan.tail()), "tomo_edt_cover")
+    eroded = torch.empty_like(plan.bits) if live else None
+    bits, nzyx = plan.head()[0], plan.head()[1:4]
+    _thickness_levels(plan, d2, r2, live, level_map, eroded)
     del d2
     values = torch.from_numpy((2.0 * radii).astype(np.float32)).to(dev) if K else None
     counts = torch.empty((nz, K + 1), dtype=torch.int64, device=dev)

@@ -145,7 +145,8 @@ def surface_area(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, direc
     return {'surface_area_mm2': s, 'voxel_volume_mm3': v, 'sphericity': sphericity(v, s)}
 
 
-def closed_porosity(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=6, min_voxels=0, max_voxels=None):
+def closed_porosity(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=6, min_voxels=0, max_voxels=None,
+                    pore_size=False):
     """The enclosed voids of the volume, listed and added up (no counterpart in the reference): pipeline.cavity_table -- a
     cavity is a component of the complement, under the complementary connectivity, that reaches no face of the stack; per-slice
     depths honoured -> {'cavities', 'cavity_voxels', 'cavity_volume_mm3', 'voxel_volume_mm3', 'closed_porosity', 'table'}.
@@ -154,8 +155,12 @@ def closed_porosity(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, co
     'dimensions', 'centroid_mm': (z, y, x), 'centroid_index': (z, y, x), 'equivalent_diameter_mm'} -- volume, box and centroids
     as component_properties gives them for the mask of the cavity, equivalent_diameter_mm = cbrt(6 V / pi).
     cavity_volume_mm3: the rows' volumes added in that order; voxel_volume_mm3: calculate_voxel_volume_variable_depth's number
-    for the solid; closed_porosity = cavity / (solid + cavity), 0.0 for an empty volume.  voxel_data: the bool (nz, ny, nx) array
-    the other calculations take; anything else is a TypeError -- there is no host path for this one."""
+    for the solid; closed_porosity = cavity / (solid + cavity), 0.0 for an empty volume.  pore_size=True: every row also carries
+    'inscribed_diameter_mm' -- twice the largest inside distance of the cavity, the widest ball that fits in the pore: for a
+    crack-shaped pore the size that equivalent_diameter_mm is not -- and 'inscribed_center_index' (z, y, x), and the report
+    'largest_pore_diameter_mm' (0.0 without pores): pipeline.cavity_sizes, ONE transform of the complement for all pores together.
+    voxel_data: the bool (nz, ny, nx) array the other calculations take; anything else is a TypeError -- there is no host path
+    for this one."""
     if not _on_device(voxel_data):
         raise TypeError("closed_porosity needs a bool (nz, ny, nx) array")
     depths = np.asarray(slice_depths, dtype=np.float64).reshape(-1)
@@ -163,7 +168,10 @@ def closed_porosity(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, co
     pipeline._check_size_window(min_voxels, max_voxels)
     pipeline._slice_weights(depths, len(voxel_data), mm_per_pixel_y, mm_per_pixel_x)
     vol = to_device_volume(voxel_data)
-    t = pipeline.cavity_table(vol, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_voxels, max_voxels)
+    if pore_size:
+        t, size = pipeline.cavity_sizes(vol, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_voxels, max_voxels)
+    else:
+        t = pipeline.cavity_table(vol, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_voxels, max_voxels)
     solid = float(volume_from_slice_counts(pipeline.slice_counts(vol).cpu().numpy(), mm_per_pixel_x, mm_per_pixel_y, depths))
     boxes = [box_variable_depth(tuple(b), mm_per_pixel_x, mm_per_pixel_y, depths) for b in t.index_box]
     table = [{'label': int(t.labels[i]), 'owner': int(t.owner[i]), 'voxels': int(t.voxels[i]), 'volume_mm3': float(t.volume_mm3[i]),
@@ -175,12 +183,20 @@ def closed_porosity(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, co
     for row in table:
         cavity += row['volume_mm3']
     whole = solid + cavity
-    return {'cavities': len(table), 'cavity_voxels': int(t.voxels.sum()), 'cavity_volume_mm3': cavity, 'voxel_volume_mm3': solid,
-            'closed_porosity': cavity / whole if whole else 0.0, 'table': table}
+    report = {'cavities': len(table), 'cavity_voxels': int(t.voxels.sum()), 'cavity_volume_mm3': cavity, 'voxel_volume_mm3': solid,
+              'closed_porosity': cavity / whole if whole else 0.0, 'table': table}
+    if pore_size:                                                # row i of both answers: one selection of the complement's tables
+        assert np.array_equal(size.labels, t.labels)
+        for i, row in enumerate(table):
+            row['inscribed_diameter_mm'] = 2 * float(size.radius_mm[i])
+            row['inscribed_center_index'] = tuple(int(v) for v in size.center_index[i])
+        report['largest_pore_diameter_mm'] = max((row['inscribed_diameter_mm'] for row in table), default=0.0)
+    return report
 
 
 def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=6, min_voxels=0, largest=False,
-                         shape=False, topology=False, surface=False, surface_directions=13, porosity=False):
+                         shape=False, topology=False, surface=False, surface_directions=13, porosity=False, thickness=False,
+                         thickness_radii_mm=None):
     """The calculations of the class per connected component (no counterpart in the reference, which would be handed the mask
     `labels == c` once per component) -> a list of dicts, one per component with at least min_voxels voxels (largest: only the
     largest of those), in label order: {'label', 'voxels', 'voxel_volume_mm3', 'bounding_box': {'x', 'y', 'z'}, 'dimensions',
@@ -197,7 +213,13 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
     (pipeline.component_surface; surface_directions = 13 or 3; a voxel of another component is not background) -- and
     'sphericity' = pi^(1/3) (6 voxel_volume_mm3)^(2/3) / surface_area_mm2 as Python floats.  porosity=True: every dict also
     carries 'cavity_voxels' (int), 'cavity_volume_mm3' -- the volumes of the cavities the component owns (closed_porosity's
-    table), added in ascending cavity label -- and 'closed_porosity' = cavity / (voxel_volume_mm3 + cavity).  Whatever the
+    table), added in ascending cavity label -- and 'closed_porosity' = cavity / (voxel_volume_mm3 + cavity).  thickness=True:
+    every dict also carries the inscribed sphere of the component -- 'inscribed_radius_mm', 'inscribed_diameter_mm',
+    'inscribed_center_index' (z, y, x) and 'inscribed_center_mm', as largest_inscribed_sphere gives them for the mask -- and, with
+    thickness_radii_mm (ascending ball radii), its local thickness as thickness_statistics gives it for the mask:
+    'thickness_mean_mm', 'thickness_std_mm', 'thickness_max_mm', 'thickness_uncovered_voxels' and 'thickness_histogram' =
+    [(diameter_mm, voxels, volume_mm3), ...] (pipeline.component_thickness: one transform of the whole volume, never one per
+    component).  Whatever the
     flags, the volume is uploaded and labelled ONCE, and so is its complement: one pipeline.ComponentRuns serves all the
     measurements and owns the one selection their rows come from.  Arguments are checked before the first launch.  voxel_data: a bool (nz, ny, nx) array, else a TypeError."""
     if not _on_device(voxel_data):
@@ -207,6 +229,8 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
     pipeline._check_connectivity(connectivity)
     tables = pipeline._slice_weights(depths, len(voxel_data), mm_per_pixel_y, mm_per_pixel_x)
     factors = pipeline.surface_factors(depths, len(voxel_data), mm_per_pixel_y, mm_per_pixel_x, surface_directions) if surface else None
+    if thickness:
+        pipeline._component_thickness_args(voxel_data.shape, depths, mm_per_pixel_y, mm_per_pixel_x, thickness_radii_mm)
     runs = pipeline.ComponentRuns(to_device_volume(voxel_data), connectivity)
     if runs.select(*rule) is None:
         return []
@@ -219,6 +243,7 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
     q = runs.moments(tables, mm_per_pixel_y, mm_per_pixel_x, *rule) if shape else None
     t = runs.topology_rows(*rule) if topology else None
     a = runs.surface(factors, surface_directions, *rule) if surface else None
+    h = runs.thickness(depths, mm_per_pixel_y, mm_per_pixel_x, thickness_radii_mm, *rule) if thickness else None
     pores = {}
     if porosity:                                                 # every cavity of the volume, credited to its owner
         c = pipeline._cavities_from(runs, runs.background().properties(tables, mm_per_pixel_y, mm_per_pixel_x, enclosed=True))
@@ -241,6 +266,16 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
             d['cavity_voxels'], d['cavity_volume_mm3'] = pores.get(d['label'], (0, 0.0))
             whole = d['voxel_volume_mm3'] + d['cavity_volume_mm3']
             d['closed_porosity'] = d['cavity_volume_mm3'] / whole if whole else 0.0
+        if thickness:
+            d['inscribed_radius_mm'] = float(h.radius_mm[i])
+            d['inscribed_diameter_mm'] = 2 * d['inscribed_radius_mm']
+            d['inscribed_center_index'] = tuple(int(v) for v in h.center_index[i])
+            d['inscribed_center_mm'] = tuple(float(v) for v in h.center_mm[i])
+            if h.radii_mm is not None:
+                d['thickness_mean_mm'], d['thickness_std_mm'] = float(h.mean_mm[i]), float(h.std_mm[i])
+                d['thickness_max_mm'], d['thickness_uncovered_voxels'] = float(h.max_mm[i]), int(h.uncovered_voxels[i])
+                d['thickness_histogram'] = [(2.0 * float(r), int(n), float(v))
+                                            for r, n, v in zip(h.radii_mm, h.level_voxels[i], h.level_volume_mm3[i])]
     return out
 
 
