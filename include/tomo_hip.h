@@ -382,6 +382,46 @@ int tomo_cc_level_hist(const uint64_t *bits, int nz, int ny, int nx, const uint3
 int tomo_cc_level_sums(const int64_t *table, int64_t cap, unsigned long long *tot, const uint8_t *sel, const uint64_t *off,
                        const uint32_t *slot, const uint64_t *hist, int64_t hist_cap, const double *w, int nz, int levels,
                        int64_t *voxels, double *volume, int64_t *labels, int64_t cap_sel, void *stream);
+/* Caliper (Feret) diameters and the oriented box per component (no counterpart in the reference): the extent of a component
+ * between two parallel planes with unit normal u = (u_z, u_y, u_x), float64; u and -u give the same width.
+ * Coordinates: those of the distance transform.  Voxel (k, j, i) sits at (zc[k], yt[j], xt[i]) = (zc[k], j * mm_y, i * mm_x),
+ * the inner entries of the tables of tomo_edt_distance; d_k is the depth of slice k.
+ * Shared directions: M directions for all components, as three host-built float64 tables PZ[m][k] = zc[k] * u_z, PY[m][j] =
+ * yt[j] * u_y, PX[m][i] = xt[i] * u_x.  The projection of a voxel is p = ((PZ[m][k] + PY[m][j]) + PX[m][i]) + 0.0: additions
+ * only, in this order; the + 0.0 turns -0.0 into +0.0 so that a maximum of keys is well defined.
+ * Extent: centres (H == NULL): hi = max p, lo = min p over the voxels of the component.  voxels: the union of the voxel boxes,
+ * hi = max (p + H[m][k]), lo = min (p - H[m][k]), H[m][k] = 0.5 * ((|u_z| * d_k + |u_y| * mm_y) + |u_x| * mm_x) built on the host:
+ * a single voxel reads its own box width along u, not 0.  width = hi - lo in both cases.
+ * Per-component directions: the three directions of component c are the rows a = (a_z, a_y, a_x) of axes[slot[c]] (the
+ * principal axes of tomo_cc_moments).  No table per component, so the kernel multiplies: p = ((zc[k] * a_z + yt[j] * a_y) +
+ * xt[i] * a_x) + 0.0 and H = 0.5 * ((|a_z| * d_k + |a_y| * mm_y) + |a_x| * mm_x), every product and sum rounded on its own,
+ * never contracted.
+ * Every operation is monotone in i, so hi / lo of a run [s, e) are attained at s or e - 1: the kernels evaluate the two ends of
+ * every run only.  One thread per row (the row pass); results go to the compacted row slot[c] of the SELECTED components
+ * (tomo_cc_select: sel, slot, tot[5]) as order-preserving uint64 keys of the float64 by 64-bit atomicMax / atomicMin -- integer
+ * atomics only: the same bytes on every run.
+ *   tomo_cc_caliper       hi, lo uint64[cap_sel][M], initialised here: the keys of hi / lo of selected component c + 1 in row
+ *                         slot[c]; pz float64[M][nz], py [M][ny], px [M][nx], ph = H float64[M][nz] or NULL (centres)
+ *   tomo_cc_caliper_axes  the same with M = 3 and the component's own directions: axes float64[cap_sel][9], zc float64[nz], yt
+ *                         [ny], xt [nx], depth float64[nz] or NULL (centres; mm_y and mm_x are not read then)
+ *   tomo_cc_caliper_rows  one thread per selected component: decodes hi / lo IN PLACE to float64[cap_sel][M], width
+ *                         float64[cap_sel][M] = hi - lo, rows int64[cap_sel][4] row slot[c] = (c + 1, voxels, index of the largest
+ *                         width, index of the smallest width; the lowest index among equals), ext float64[cap_sel][2] = (largest
+ *                         width, smallest width)
+ * tot[5] > cap_sel or tot[1] > cap: bit 1 of tot[2], nothing is written; a run id outside the tables, a slot outside cap_sel or
+ * a selected component no voxel reached: bit 2.  TOMO_E_ARG for a null pointer (ph / depth excepted), hi == lo, a non-positive
+ * size or M, and with depth a pixel size that is not positive and finite; TOMO_E_SIZE from 2^31 words, runs, components or
+ * selected components, 524 280 directions or 2^57 cells on. */
+int tomo_cc_caliper(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
+                    const uint32_t *rank, unsigned long long *tot, const uint8_t *sel, const uint32_t *slot, int64_t cap,
+                    const double *pz, const double *py, const double *px, const double *ph, int M, uint64_t *hi, uint64_t *lo,
+                    int64_t cap_sel, void *stream);
+int tomo_cc_caliper_axes(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                         const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const uint8_t *sel,
+                         const uint32_t *slot, int64_t cap, const double *axes, const double *zc, const double *yt, const double *xt,
+                         const double *depth, double mm_y, double mm_x, uint64_t *hi, uint64_t *lo, int64_t cap_sel, void *stream);
+int tomo_cc_caliper_rows(const int64_t *table, int64_t cap, unsigned long long *tot, const uint8_t *sel, const uint32_t *slot,
+                         uint64_t *hi, uint64_t *lo, int M, double *width, int64_t *rows, double *ext, int64_t cap_sel, void *stream);
 /* The same across Z-slabs (slab_components.py): rank r labels its slab with the functions above (n_r components); local
  * component c has the global id base_r + c, base_r = n_0 + .. + n_(r-1).  Pieces that touch across a cut are united, the roots
  * (smallest id = the piece with the component's first voxel) numbered in ascending id: scipy's numbering of the whole stack.

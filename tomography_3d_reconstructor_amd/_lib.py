@@ -82,7 +82,12 @@ SIGNATURES = {
                                   _c_p, _c_i, _c_p]),
     "tomo_cc_level_sums": (_c_i, [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_i64,
                                   _c_p]),
-    "tomo_cc_slice_components": (_c_i, [_c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p]),
+    "tomo_cc_caliper": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i,
+                               _c_p, _c_p, _c_i64, _c_p]),
+    "tomo_cc_caliper_axes": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p,
+                                    _c_p, _c_d, _c_d, _c_p, _c_p, _c_i64, _c_p]),
+    "tomo_cc_caliper_rows": (_c_i, [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i, _c_p, _c_p, _c_p, _c_i64, _c_p]),
+    "tomo_cc_slice_components":(_c_i, [_c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p]),
     "tomo_cc_seam_union": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p,
                                   _c_p, _c_p]),
     "tomo_cc_merge_tables": (_c_i, [_c_p, _c_i, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),

@@ -1,7 +1,8 @@
 // component_measures.hip -- what is measured per component on the run tables of components.hip: the measurement table
 // (voxels, box, index sums), the selection and its slice histograms (voxels, or six moment sums, per component and slice),
 // volume and centroid in mm, second moments and principal axes, Euler number, cavities and handles, surface area (Crofton),
-// and what a per-voxel array gives per component (the inscribed sphere from the distance map, voxels per thickness level).
+// what a per-voxel array gives per component (the inscribed sphere from the distance map, voxels per thickness level), and
+// caliper diameters along shared directions and along a component's own axes.
 // Every pass over the rows is an accumulator for the row pass of cc_runs.h -- over the runs, or, where a voxel's neighbours
 // decide (Euler number, surface area), over the words of the row with windows of the neighbour rows slid along; the integer
 // tables are integer atomics only, the float results are sequential sums over those integers (nothing is contracted in this
@@ -1532,5 +1533,355 @@ TOMO_API int tomo_cc_level_sums(const int64_t *table, int64_t cap, unsigned long
     hipLaunchKernelGGL(cc_level_sums_kernel, dim3((unsigned)ceil_div64(cap * per, CC_THREADS)), dim3(CC_THREADS), 0,
                        (hipStream_t)stream, (const u64 *)table, (const u64 *)tot, cap, sel, (const u64 *)off, (const u32 *)slot,
                        (const u64 *)hist, hist_cap, w, nz, levels, (u64 *)voxels, volume, labels, cap_sel, (u64 *)tot + 2);
+    return tomo_status();
+}
+
+// ---------------------------------------------------------------------------------------------- caliper (Feret) diameters
+// The extent of a component between two parallel planes with normal u: width = hi - lo, hi / lo the largest / smallest
+// projection p of its voxels on u (centres), or of p + H / p - H with H half the width of the voxel's own box along u (voxels).
+// p is a sum of three table entries (shared directions) or of three products (the component's own axes), rounded one by one
+// in a fixed order, + 0.0 so that no -0.0 reaches the keys -- include/tomo_hip.h has the definition.  Every term is monotone
+// in x, so a run [s, e) attains its extremes at s or at e - 1: the row pass evaluates the two ends of every run, whatever its
+// length.  A float64 that is no NaN becomes a uint64 key whose unsigned order is the float order; the extremes of a thread's
+// row, then of a wave whose lanes hold one component, go to hi / lo [slot[c]][m] by 64-bit atomicMax / atomicMin -- only where
+// they beat what a plain load of the cell shows (the cells only rise / fall: a stale read costs an atomic, never the answer;
+// one solid body would otherwise queue every wave of the volume on 2 M addresses).  Integer atomics only: the same bytes on
+// every run.  Results are compacted: nothing here has a row per component of the volume.
+#define CC_CAL_BATCH 8               // shared directions per workgroup row (blockIdx.y): 4 float64 per direction in registers
+
+__device__ static inline u64 cc_f64_key(double v)
+{
+    const u64 b = (u64)__double_as_longlong(v);
+    return (b >> 63) ? ~b : b | (1ull << 63);
+}
+
+__device__ static inline double cc_key_f64(u64 k)
+{
+    return __longlong_as_double((long long)((k >> 63) ? k & ~(1ull << 63) : ~k));
+}
+
+__device__ static inline u64 cc_load64(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+struct CcCaliperOut {
+    u64 *hi, *lo;                                           // keys [cap_sel][M]
+    const uint8_t *sel;
+    const u32 *slot;
+    u32 ncomp;
+    int64_t cap_sel;
+    int M, m0, nb;                                          // directions per row; the first of this batch, how many it holds
+    u64 *flags;
+};
+
+// what a thread, or a wave, flushes for ONE component: the keys of D directions, the first o.nb of them real
+template <int D>
+struct CcCaliperKeys {
+    const CcCaliperOut &o;
+    u64 hi[D], lo[D];
+    bool has;
+    __device__ bool any() const { return has; }
+    __device__ void flush(u32 c) const
+    {
+        if (c >= o.ncomp) return;
+        const u32 k = o.slot[c];
+        if ((int64_t)k >= o.cap_sel) {
+            cc_flag(o.flags, CC_F_RANGE);
+            return;
+        }
+        u64 *h = o.hi + (int64_t)k * o.M + o.m0, *l = o.lo + (int64_t)k * o.M + o.m0;
+#pragma unroll
+        for (int d = 0; d < D; d++) {
+            if (d >= o.nb) break;
+            if (hi[d] > cc_load64(h + d)) atomicMax(h + d, hi[d]);
+            if (lo[d] < cc_load64(l + d)) atomicMin(l + d, lo[d]);
+        }
+    }
+};
+
+// the part the two accumulators share: the extremes of D directions as float64 (no NaN, no -0.0), their keys when they leave
+template <int D>
+struct CcCaliperExtremes {
+    CcCaliperOut o;
+    double hi[D], lo[D];
+    bool has;
+    __device__ u32 filter(u32 c) const { return (c - 1 >= o.ncomp || !o.sel[c - 1]) ? 0u : c; }
+    __device__ bool any() const { return has; }
+    __device__ void reset()
+    {
+        has = false;
+#pragma unroll
+        for (int d = 0; d < D; d++) {
+            hi[d] = -__builtin_inf();
+            lo[d] = __builtin_inf();
+        }
+    }
+    __device__ void widen(int d, double ps, double pe, double h)
+    {
+        hi[d] = fmax(hi[d], fmax(ps + h, pe + h));
+        lo[d] = fmin(lo[d], fmin(ps - h, pe - h));
+    }
+    __device__ void flush(u32 c) const
+    {
+        CcCaliperKeys<D> k = {o, {}, {}, has};
+#pragma unroll
+        for (int d = 0; d < D; d++) {
+            k.hi[d] = cc_f64_key(hi[d]);
+            k.lo[d] = cc_f64_key(lo[d]);
+        }
+        k.flush(c);
+    }
+    __device__ CcCaliperKeys<D> combine(bool mine, u32) const
+    {
+        CcCaliperKeys<D> k = {o, {}, {}, __any(mine) != 0};
+#pragma unroll
+        for (int d = 0; d < D; d++) {
+            k.hi[d] = wave_max64(mine ? cc_f64_key(hi[d]) : 0ull);
+            k.lo[d] = wave_min64(mine ? cc_f64_key(lo[d]) : ~0ull);
+        }
+        return k;
+    }
+};
+
+// shared directions: the row brings base = PZ[m][z] + PY[m][y] and h = H[m][z] per direction of the batch, a run adds PX[m][x]
+// at its two ends.  A batch that is not full repeats its last direction (every load stays inside the tables); the flush
+// leaves the repeats out.
+struct CcCaliperAcc : CcCaliperExtremes<CC_CAL_BATCH> {
+    const double *px;                                       // PX of the first direction of the batch
+    int nx;
+    double base[CC_CAL_BATCH], h[CC_CAL_BATCH];
+    __device__ u32 begin(u32 c, const CcRuns &)
+    {
+        reset();
+        return c;
+    }
+    __device__ void add(const CcRuns &a)
+    {
+        has = true;
+#pragma unroll
+        for (int d = 0; d < CC_CAL_BATCH; d++) {
+            const double *t = px + (int64_t)(d < o.nb ? d : o.nb - 1) * nx;
+            widen(d, (base[d] + t[a.s]) + 0.0, (base[d] + t[a.e - 1]) + 0.0, h[d]);
+        }
+    }
+};
+
+__global__ __launch_bounds__(CC_THREADS) void cc_caliper_kernel(const u64 *__restrict__ bits, int64_t nrows, int nz, int ny, int nx,
+                                                                int wx, const u32 *__restrict__ row_off, const u64 *__restrict__ tot,
+                                                                int64_t cap_runs, const u32 *__restrict__ parent,
+                                                                const u32 *__restrict__ rank, const uint8_t *__restrict__ sel,
+                                                                const u32 *__restrict__ slot, int64_t cap,
+                                                                const double *__restrict__ pz, const double *__restrict__ py,
+                                                                const double *__restrict__ px, const double *__restrict__ ph, int M,
+                                                                u64 *hi, u64 *lo, int64_t cap_sel, u64 *flags)
+{
+    const int64_t row = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    const u32 nruns = (u32)cc_count(tot, cap_runs);
+    const bool fits = tot[5] <= (u64)cap_sel && tot[1] <= (u64)cap;
+    if (row == 0 && blockIdx.y == 0 && !fits) cc_flag(flags, CC_F_CAP);
+    const bool live = row < nrows;
+    const int m0 = (int)blockIdx.y * CC_CAL_BATCH, nb = M - m0 < CC_CAL_BATCH ? M - m0 : CC_CAL_BATCH;      // nb >= 1: the grid
+    const int64_t z = live ? row / ny : 0, y = live ? row % ny : 0;
+    CcCaliperAcc acc;
+    acc.o = {hi, lo, sel, slot, fits ? (u32)cc_ncomp(tot, cap) : 0u, cap_sel, M, m0, nb, flags};
+    acc.px = px + (int64_t)m0 * nx;
+    acc.nx = nx;
+    acc.reset();
+#pragma unroll
+    for (int d = 0; d < CC_CAL_BATCH; d++) {
+        const int64_t m = m0 + (d < nb ? d : nb - 1);
+        acc.base[d] = pz[m * nz + z] + py[m * ny + y];
+        acc.h[d] = ph ? ph[m * nz + z] : 0.0;
+    }
+    u32 comp = 0;
+    if (live) comp = cc_row_walk<true>(bits, row, nx, wx, row_off, nruns, parent, rank, flags, acc);
+    cc_wave_tail<false>(comp, 0u, acc);
+}
+
+// a 2^57 cells bound keeps the byte counts of the memsets below 2^60
+static int cc_caliper_args(const void *bits, int nz, int ny, int nx, const void *row_off, int64_t cap_runs, const void *parent,
+                           const void *rank, const void *tot, const void *sel, const void *slot, int64_t cap, int M, const void *hi,
+                           const void *lo, int64_t cap_sel, int64_t *nrows, int *wx)
+{
+    const int g = cc_geometry(bits, nz, ny, nx, nrows, wx);
+    if (g != TOMO_OK) return g;
+    if (!row_off || !parent || !rank || !tot || !sel || !slot || !hi || !lo || hi == lo || cap_runs <= 0 || cap <= 0 || cap_sel <= 0 ||
+        M <= 0)
+        return TOMO_E_ARG;
+    if (cap_runs >= ((int64_t)1 << 31) || cap >= ((int64_t)1 << 31) || cap_sel >= ((int64_t)1 << 31) ||
+        M > 65535 * CC_CAL_BATCH || cap_sel * M >= ((int64_t)1 << 57))
+        return TOMO_E_SIZE;
+    return TOMO_OK;
+}
+
+static int cc_caliper_init(u64 *hi, u64 *lo, int64_t cells, hipStream_t st)
+{
+    if (hipMemsetAsync(hi, 0, (size_t)cells * sizeof(u64), st) != hipSuccess) return TOMO_E_LAUNCH;         // below every key
+    if (hipMemsetAsync(lo, 0xff, (size_t)cells * sizeof(u64), st) != hipSuccess) return TOMO_E_LAUNCH;      // above every key
+    return TOMO_OK;
+}
+
+TOMO_API int tomo_cc_caliper(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                             const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const uint8_t *sel,
+                             const uint32_t *slot, int64_t cap, const double *pz, const double *py, const double *px, const double *ph,
+                             int M, uint64_t *hi, uint64_t *lo, int64_t cap_sel, void *stream)
+{
+    int64_t nrows;
+    int wx;
+    const int g = cc_caliper_args(bits, nz, ny, nx, row_off, cap_runs, parent, rank, tot, sel, slot, cap, M, hi, lo, cap_sel, &nrows, &wx);
+    if (g != TOMO_OK) return g;
+    if (!pz || !py || !px) return TOMO_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const int i = cc_caliper_init((u64 *)hi, (u64 *)lo, cap_sel * M, st);
+    if (i != TOMO_OK) return i;
+    const dim3 grid((unsigned)ceil_div64(nrows, CC_THREADS), (unsigned)((M + CC_CAL_BATCH - 1) / CC_CAL_BATCH));
+    hipLaunchKernelGGL(cc_caliper_kernel, grid, dim3(CC_THREADS), 0, st, (const u64 *)bits, nrows, nz, ny, nx, wx, (const u32 *)row_off,
+                       (const u64 *)tot, cap_runs, (const u32 *)parent, (const u32 *)rank, sel, (const u32 *)slot, cap, pz, py, px, ph, M,
+                       (u64 *)hi, (u64 *)lo, cap_sel, (u64 *)tot + 2);
+    return tomo_status();
+}
+
+// the component's own three directions: rows of axes[slot[c]] as (a_z, a_y, a_x).  There is no table per component, so the
+// projection is three products, p = ((zc[z] * a_z + yt[y] * a_y) + xt[x] * a_x) + 0.0, every product and sum rounded on its
+// own (-ffp-contract=off: an FMA would break the equality with a host that multiplies and adds), and
+// H = 0.5 * ((|a_z| * depth[z] + |a_y| * mm_y) + |a_x| * mm_x); depth == NULL: centres, H = 0.
+struct CcCaliperAxesAcc : CcCaliperExtremes<3> {
+    const double *axes, *xt, *depth;
+    double zc, yt, dk, mm_y, mm_x;                          // of the thread's row
+    double ax[3], base[3], h[3];
+    __device__ u32 begin(u32 c, const CcRuns &)
+    {
+        reset();
+        if (c) {
+            const u32 k = o.slot[c - 1];
+            if ((int64_t)k >= o.cap_sel) {
+                cc_flag(o.flags, CC_F_RANGE);
+                return 0;
+            }
+            const double *a = axes + 9 * (int64_t)k;
+#pragma unroll
+            for (int r = 0; r < 3; r++) {
+                const double az = a[3 * r], ay = a[3 * r + 1];
+                ax[r] = a[3 * r + 2];
+                base[r] = zc * az + yt * ay;
+                h[r] = depth ? 0.5 * ((fabs(az) * dk + fabs(ay) * mm_y) + fabs(ax[r]) * mm_x) : 0.0;
+            }
+        }
+        return c;
+    }
+    __device__ void add(const CcRuns &a)
+    {
+        has = true;
+        const double xs = xt[a.s], xe = xt[a.e - 1];
+#pragma unroll
+        for (int r = 0; r < 3; r++) widen(r, (base[r] + xs * ax[r]) + 0.0, (base[r] + xe * ax[r]) + 0.0, h[r]);
+    }
+};
+
+__global__ __launch_bounds__(CC_THREADS) void cc_caliper_axes_kernel(const u64 *__restrict__ bits, int64_t nrows, int ny, int nx, int wx,
+                                                                     const u32 *__restrict__ row_off, const u64 *__restrict__ tot,
+                                                                     int64_t cap_runs, const u32 *__restrict__ parent,
+                                                                     const u32 *__restrict__ rank, const uint8_t *__restrict__ sel,
+                                                                     const u32 *__restrict__ slot, int64_t cap,
+                                                                     const double *__restrict__ axes, const double *__restrict__ zc,
+                                                                     const double *__restrict__ yt, const double *__restrict__ xt,
+                                                                     const double *__restrict__ depth, double mm_y, double mm_x,
+                                                                     u64 *hi, u64 *lo, int64_t cap_sel, u64 *flags)
+{
+    const int64_t row = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    const u32 nruns = (u32)cc_count(tot, cap_runs);
+    const bool fits = tot[5] <= (u64)cap_sel && tot[1] <= (u64)cap;
+    if (row == 0 && !fits) cc_flag(flags, CC_F_CAP);
+    const bool live = row < nrows;
+    const int64_t z = live ? row / ny : 0, y = live ? row % ny : 0;
+    CcCaliperAxesAcc acc;
+    acc.o = {hi, lo, sel, slot, fits ? (u32)cc_ncomp(tot, cap) : 0u, cap_sel, 3, 0, 3, flags};
+    acc.axes = axes;
+    acc.xt = xt;
+    acc.depth = depth;
+    acc.zc = zc[z];
+    acc.yt = yt[y];
+    acc.dk = depth ? depth[z] : 0.0;
+    acc.mm_y = mm_y;
+    acc.mm_x = mm_x;
+    acc.reset();
+    u32 comp = 0;
+    if (live) comp = cc_row_walk<true>(bits, row, nx, wx, row_off, nruns, parent, rank, flags, acc);
+    cc_wave_tail<false>(comp, 0u, acc);
+}
+
+TOMO_API int tomo_cc_caliper_axes(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                                  const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const uint8_t *sel,
+                                  const uint32_t *slot, int64_t cap, const double *axes, const double *zc, const double *yt,
+                                  const double *xt, const double *depth, double mm_y, double mm_x, uint64_t *hi, uint64_t *lo,
+                                  int64_t cap_sel, void *stream)
+{
+    int64_t nrows;
+    int wx;
+    const int g = cc_caliper_args(bits, nz, ny, nx, row_off, cap_runs, parent, rank, tot, sel, slot, cap, 3, hi, lo, cap_sel, &nrows, &wx);
+    if (g != TOMO_OK) return g;
+    if (!axes || !zc || !yt || !xt) return TOMO_E_ARG;
+    if (depth && (!(mm_y > 0.0 && mm_y < __builtin_inf()) || !(mm_x > 0.0 && mm_x < __builtin_inf()))) return TOMO_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const int i = cc_caliper_init((u64 *)hi, (u64 *)lo, cap_sel * 3, st);
+    if (i != TOMO_OK) return i;
+    hipLaunchKernelGGL(cc_caliper_axes_kernel, dim3((unsigned)ceil_div64(nrows, CC_THREADS)), dim3(CC_THREADS), 0, st, (const u64 *)bits,
+                       nrows, ny, nx, wx, (const u32 *)row_off, (const u64 *)tot, cap_runs, (const u32 *)parent, (const u32 *)rank, sel,
+                       (const u32 *)slot, cap, axes, zc, yt, xt, depth, mm_y, mm_x, (u64 *)hi, (u64 *)lo, cap_sel, (u64 *)tot + 2);
+    return tomo_status();
+}
+
+// One thread per component; a selected one decodes its M keys IN PLACE (hi / lo hold float64 afterwards), writes width = hi - lo
+// and finds the largest and the smallest width, the lowest direction index among equals.  rows[slot[c]] = (c + 1, voxels, index
+// of the largest width, index of the smallest), ext[slot[c]] = (largest width, smallest width).  A cell no voxel reached (the
+// bits changed since the selection) is CC_F_RANGE.
+__global__ __launch_bounds__(CC_THREADS) void cc_caliper_rows_kernel(const u64 *__restrict__ table, const u64 *__restrict__ tot,
+                                                                     int64_t cap, const uint8_t *__restrict__ sel,
+                                                                     const u32 *__restrict__ slot, u64 *hi, u64 *lo, int M,
+                                                                     double *__restrict__ width, int64_t *__restrict__ rows,
+                                                                     double *__restrict__ ext, int64_t cap_sel, u64 *flags)
+{
+    const int64_t c = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    const bool fits = tot[5] <= (u64)cap_sel && tot[1] <= (u64)cap;
+    if (c == 0 && !fits) cc_flag(flags, CC_F_CAP);
+    if (!fits || c >= cc_ncomp(tot, cap) || !sel[c]) return;
+    const u32 k = slot[c];
+    if ((int64_t)k >= cap_sel) {
+        cc_flag(flags, CC_F_RANGE);
+        return;
+    }
+    u64 *h = hi + (int64_t)k * M, *l = lo + (int64_t)k * M;
+    double *w = width + (int64_t)k * M;
+    double wmax = 0.0, wmin = 0.0;
+    int imax = 0, imin = 0;
+    bool reached = true;
+    for (int m = 0; m < M; m++) {
+        const u64 kh = h[m], kl = l[m];
+        if (kh == 0ull || kl == ~0ull) reached = false;
+        const double a = cc_key_f64(kh), b = cc_key_f64(kl), d = a - b;
+        ((double *)h)[m] = a;
+        ((double *)l)[m] = b;
+        w[m] = d;
+        if (m == 0 || d > wmax) { wmax = d; imax = m; }
+        if (m == 0 || d < wmin) { wmin = d; imin = m; }
+    }
+    if (!reached) cc_flag(flags, CC_F_RANGE);
+    rows[4 * (int64_t)k] = c + 1;
+    rows[4 * (int64_t)k + 1] = (int64_t)table[c * CC_COLS];
+    rows[4 * (int64_t)k + 2] = imax;
+    rows[4 * (int64_t)k + 3] = imin;
+    ext[2 * (int64_t)k] = wmax;
+    ext[2 * (int64_t)k + 1] = wmin;
+}
+
+TOMO_API int tomo_cc_caliper_rows(const int64_t *table, int64_t cap, unsigned long long *tot, const uint8_t *sel, const uint32_t *slot,
+                                  uint64_t *hi, uint64_t *lo, int M, double *width, int64_t *rows, double *ext, int64_t cap_sel,
+                                  void *stream)
+{
+    if (!table || !tot || !sel || !slot || !hi || !lo || hi == lo || !width || !rows || !ext || cap <= 0 || cap_sel <= 0 || M <= 0)
+        return TOMO_E_ARG;
+    if (cap >= ((int64_t)1 << 31) || cap_sel >= ((int64_t)1 << 31) || M > 65535 * CC_CAL_BATCH || cap_sel * M >= ((int64_t)1 << 57))
+        return TOMO_E_SIZE;
+    hipLaunchKernelGGL(cc_caliper_rows_kernel, dim3((unsigned)ceil_div64(cap, CC_THREADS)), dim3(CC_THREADS), 0, (hipStream_t)stream,
+                       (const u64 *)table, (const u64 *)tot, cap, sel, (const u32 *)slot, (u64 *)hi, (u64 *)lo, M, width, rows, ext,
+                       cap_sel, (u64 *)tot + 2);
     return tomo_status();
 }

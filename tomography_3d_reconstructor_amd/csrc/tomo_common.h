@@ -104,6 +104,24 @@ __device__ static inline u32 wave_max32(u32 v)
     }
     return v;
 }
+__device__ static inline u64 wave_min64(u64 v)
+{
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const u64 o = __shfl_xor(v, d, 64);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+__device__ static inline u64 wave_max64(u64 v)
+{
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const u64 o = __shfl_xor(v, d, 64);
+        v = o > v ? o : v;
+    }
+    return v;
+}
 __device__ static inline u32 wave_sum(u32 v)
 {
 #pragma unroll

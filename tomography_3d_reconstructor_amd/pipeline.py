@@ -25,7 +25,7 @@ COUNTERS = dict.fromkeys(("na_hint_hit", "na_hint_miss", "mc3_hint_hit", "mc3_hi
                           "slab_components_expand", "slab_components_filter", "distance_transform", "distance_offset",
                           "components_measure", "components_zhist", "components_moments", "components_euler",
                           "components_cavities", "local_thickness", "opening_volume", "components_surface", "components_fill",
-                          "components_cavity_owners", "component_thickness", "components_value", "components_levels"), 0)
+                          "components_cavity_owners", "component_thickness", "components_value", "components_levels", "component_caliper"), 0)
 NA_HINTS = os.environ.get("TOMO_NA_HINTS", "1") not in ("", "0")   # marching_cubes: launch ahead of the first count download
 _NA_HINT = {}
 LIST_LIMIT = 2 ** 31        # active-voxel list entries / vertices / triangles one pass can index (int32 offsets in mc.hip, mesh.hip);
@@ -332,8 +332,8 @@ class ComponentRuns:
     """The run tables of one BitVolume under one connectivity: scipy.ndimage.label's components, held per X-RUN (a maximal
     run of set bits in a row) and never per voxel.  Two host reads: the number of runs (it sizes the tables) and the
     counters after the labelling.  n = components; labels() / sizes() / keep() read the tables.
-    One object serves every per-component measurement of its volume: properties(), moments(), topology_rows(), surface() and
-    thickness() share the labelling, the measurement table and ONE selection, which the object owns (select).  background() is the same
+    One object serves every per-component measurement of its volume: properties(), moments(), topology_rows(), surface(),
+    thickness() and caliper() share the labelling, the measurement table and ONE selection, which the object owns (select).  background() is the same
     kind of object for the complement: its enclosed components are the cavities of this volume (cavity_owners)."""
 
     def __init__(self, vol: BitVolume, connectivity=6):
@@ -562,6 +562,63 @@ class ComponentRuns:
             levels = self._rows(spec, rule, weights, len(radii), hist_args=(_p(level_map), len(radii)))
         (host,) = self._download_checked("component_thickness", rows)
         return _component_thickness_from(self.vol.shape, slice_depths, mm_y, mm_x, host, radii, levels)
+
+    def caliper(self, slice_depths, mm_y, mm_x, directions=None, extent="voxels", oriented=False, min_voxels=0, largest=False, *,
+                max_voxels=None, enclosed=False) -> "ComponentCaliper":
+        """component_caliper of this volume.  The rule: select's.  One row pass per batch of directions over the run tables, the
+        two ends of every run; with oriented, moments() runs first under the same rule -- the one selection, so the rows line
+        up -- and one more pass measures every component along its own principal axes.  On background() with enclosed=True
+        the rows are the cavities."""
+        rule = _keep_rule(min_voxels, largest, max_voxels, enclosed)
+        dirs, tabs = _caliper_args(self.vol.shape, slice_depths, mm_y, mm_x, directions, extent)
+        COUNTERS["component_caliper"] += 1
+        picked = self.select(rule[0], rule[1], max_voxels=rule[2], enclosed=rule[3])
+        if picked is None:
+            return _component_caliper_from(dirs, oriented=bool(oriented))
+        M, m = len(dirs), picked.m
+        nbytes = 16 * M * m
+        if nbytes > COMPONENT_HIST_BUDGET and m > 1:                    # read when called; one component is always granted
+            raise _lib.TomoError("component_caliper: %d components selected, their extremes along %d directions take %d bytes, more "
+                                 "than COMPONENT_HIST_BUDGET (%d): raise min_voxels" % (m, M, nbytes, COMPONENT_HIST_BUDGET))
+        q = None
+        if oriented:                                                    # the same rule: the selection stays, the rows line up
+            q = self.moments(_slice_weights(slice_depths, self.vol.shape[0], mm_y, mm_x), mm_y, mm_x, rule[0], rule[1], max_voxels=rule[2],
+                             enclosed=rule[3])
+            if len(q) != m:
+                raise _lib.TomoError("component_caliper: the rows of the moments are not the rows of the selection")
+        L, dev, st = _lib.lib(), self.vol.device, _stream()
+        n = picked.table.shape[0]
+        head = (_p(self.bits), *self.vol.shape, *self._tables(), _p(self.tot), _p(picked.sel), _p(picked.slot), n)
+
+        def rows_of(count, launch):
+            """hi / lo keys of `count` directions filled by launch(hi, lo), then decoded -> device (rows, hi, lo, width, ext)"""
+            hi = torch.empty((m, count), dtype=torch.float64, device=dev)
+            lo = torch.empty((m, count), dtype=torch.float64, device=dev)
+            width = torch.empty((m, count), dtype=torch.float64, device=dev)
+            rows = torch.empty((m, 4), dtype=torch.int64, device=dev)
+            ext = torch.empty((m, 2), dtype=torch.float64, device=dev)
+            launch(hi, lo)
+            _lib.check(L.tomo_cc_caliper_rows(_p(picked.table), n, _p(self.tot), _p(picked.sel), _p(picked.slot), _p(hi), _p(lo), count,
+                                              _p(width), _p(rows), _p(ext), m, st), "tomo_cc_caliper_rows")
+            return rows, hi, lo, width, ext
+
+        shared = torch.from_numpy(np.concatenate([t.reshape(-1) for t in (tabs.pz, tabs.py, tabs.px, tabs.h) if t is not None])).to(dev)
+        nz, ny, nx = self.vol.shape
+        ptr = [shared.data_ptr() + 8 * M * o for o in (0, nz, nz + ny, nz + ny + nx)]
+        out = rows_of(M, lambda hi, lo: _lib.check(L.tomo_cc_caliper(*head, ptr[0], ptr[1], ptr[2], None if tabs.h is None else ptr[3], M,
+                                                                    _p(hi), _p(lo), m, st), "tomo_cc_caliper"))
+        own = None
+        if oriented:
+            axes = torch.from_numpy(np.ascontiguousarray(q.principal_axes).reshape(-1)).to(dev)
+            pos = torch.from_numpy(np.concatenate([tabs.zc, tabs.yt, tabs.xt, tabs.depth])).to(dev)
+            at = [pos.data_ptr() + 8 * o for o in (0, nz, nz + ny, nz + ny + nx)]
+            own = rows_of(3, lambda hi, lo: _lib.check(L.tomo_cc_caliper_axes(*head, _p(axes), at[0], at[1], at[2],
+                                                                              at[3] if tabs.h is not None else None, float(mm_y), float(mm_x),
+                                                                              _p(hi), _p(lo), m, st), "tomo_cc_caliper_axes"))
+        host = self._download_checked("component_caliper", *out, *(own or ()))
+        if oriented and not np.array_equal(host[5][:, 0], q.labels):
+            raise _lib.TomoError("component_caliper: the rows of the moments are not the rows of the selection")
+        return _component_caliper_from(dirs, host[:5], q, host[5:] if oriented else None, oriented=bool(oriented))
 
     def topology(self) -> torch.Tensor:
         """Per component 1..n: Euler number, cavities (enclosed voids, b2) and handles (tunnels, b1 = 1 - euler + cavities) of
@@ -1364,6 +1421,185 @@ def component_thickness(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, m
     _keep_rule(min_voxels, largest)
     _component_thickness_args(vol.shape, slice_depths, mm_per_pixel_y, mm_per_pixel_x, radii_mm)
     return ComponentRuns(vol, connectivity).thickness(slice_depths, mm_per_pixel_y, mm_per_pixel_x, radii_mm, min_voxels, largest)
+
+
+# ----------------------------------------------------------------------------- caliper (Feret) diameters and the oriented box
+CALIPER_DIRECTIONS = 64      # directions of the default set: the three axes and a Fibonacci lattice on the upper hemisphere
+CALIPER_EXTENTS = ("voxels", "centres")
+CALIPER_PROBES = 200000      # probe vectors of caliper_cover
+
+
+def caliper_directions(count=CALIPER_DIRECTIONS) -> np.ndarray:
+    """The default direction set -> float64 (count, 3) unit vectors as (z, y, x).  Rows 0-2 are the axes z, y, x; the other
+    n = count - 3 rows are a Fibonacci lattice on the upper hemisphere (u and -u measure the same width): z_i = (i + 0.5) / n,
+    phi_i = i pi (3 - sqrt 5), row (z, r sin phi, r cos phi) with r = sqrt(1 - z^2).  count < 3: ValueError."""
+    count = int(count)
+    if count < 3:
+        raise ValueError("caliper_directions: count must be at least 3 (the axes)")
+    out = np.zeros((count, 3), dtype=np.float64)
+    out[0, 0] = out[1, 1] = out[2, 2] = 1.0
+    n = count - 3
+    if n:
+        i = np.arange(n, dtype=np.float64)
+        z = (i + 0.5) / n
+        r = np.sqrt(1.0 - z * z)
+        phi = i * (np.pi * (3.0 - np.sqrt(5.0)))
+        rows = np.stack([z, r * np.sin(phi), r * np.cos(phi)], axis=1)
+        out[3:] = rows / np.sqrt((rows * rows).sum(axis=1))[:, None]
+    return out
+
+
+def caliper_cover(directions) -> float:
+    """How far the largest width over a direction set can fall short of the true max Feret diameter: the smallest max_m |q . u_m|
+    over CALIPER_PROBES unit probe vectors q (normalised normal deviates of numpy.random.default_rng(0)).  A segment of length D
+    along q has width D |q . u| along u, so max_mm >= cover * D.  Measured: 0.9669 for caliper_directions(64), 0.9823 for 128,
+    0.9922 for 256."""
+    u = _check_directions(directions)
+    q = np.random.default_rng(0).standard_normal((CALIPER_PROBES, 3))
+    q /= np.sqrt((q * q).sum(axis=1))[:, None]
+    worst = 1.0
+    for a in range(0, len(q), 20000):                                   # 20 000 x M products at a time
+        worst = min(worst, float(np.abs(q[a:a + 20000] @ u.T).max(axis=1).min()))
+    return worst
+
+
+def _check_directions(directions) -> np.ndarray:
+    """directions=None: the default set; else float64 (M, 3) C-contiguous, M >= 1, finite, unit within 1e-12 (ValueError)."""
+    if directions is None:
+        return caliper_directions()
+    try:
+        u = np.ascontiguousarray(directions, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("directions must be a float (M, 3) array") from None
+    if u.ndim != 2 or u.shape[1] != 3 or u.shape[0] < 1:
+        raise ValueError("directions must have the shape (M, 3) with M >= 1, not %s" % (u.shape,))
+    if not np.isfinite(u).all():
+        raise ValueError("directions must be finite")
+    if (np.abs(np.sqrt((u * u).sum(axis=1)) - 1.0) > 1e-12).any():
+        raise ValueError("directions must be unit vectors (within 1e-12)")
+    return u
+
+
+@dataclass
+class _CaliperTables:
+    """The host tables of one caliper call (include/tomo_hip.h, tomo_cc_caliper)."""
+    zc: np.ndarray               # float64 (nz,), (ny,), (nx,): where a voxel sits, the inner entries of distance_positions
+    yt: np.ndarray
+    xt: np.ndarray
+    depth: np.ndarray            # float64 (nz,): the real depth of every slice
+    pz: np.ndarray               # float64 (M, nz), (M, ny), (M, nx): the projections of those on every direction
+    py: np.ndarray
+    px: np.ndarray
+    h: np.ndarray                # float64 (M, nz): half the width of a voxel's box along every direction; None: extent="centres"
+
+
+def _caliper_args(shape, slice_depths, mm_per_pixel_y, mm_per_pixel_x, directions, extent):
+    """The argument checks of component_caliper, all on the host -> (directions float64 (M, 3), _CaliperTables)."""
+    if extent not in CALIPER_EXTENTS:
+        raise ValueError("extent must be 'voxels' or 'centres'")
+    u = _check_directions(directions)
+    nz, ny, nx = shape
+    zt, yt, xt = distance_positions(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x, ny, nx)
+    zc, yt, xt = zt[1:-1].copy(), yt[1:-1].copy(), xt[1:-1].copy()
+    depth = np.ones(nz) if slice_depths is None else np.asarray(slice_depths, dtype=np.float64).reshape(-1).copy()
+    mm_y, mm_x = float(mm_per_pixel_y), float(mm_per_pixel_x)
+    a = np.abs(u)
+    h = None if extent == "centres" else 0.5 * ((a[:, 0:1] * depth[None, :] + a[:, 1:2] * mm_y) + a[:, 2:3] * mm_x)
+    return u, _CaliperTables(zc, yt, xt, depth, zc[None, :] * u[:, 0:1], yt[None, :] * u[:, 1:2], xt[None, :] * u[:, 2:3], h)
+
+
+@dataclass
+class ComponentCaliper:
+    """component_caliper's answer: host arrays, one row per selected component in ascending label; vectors in (z, y, x) order.
+    The fields from axes on are None without oriented."""
+    labels: np.ndarray                     # int64 (m,)
+    voxels: np.ndarray                     # int64 (m,)
+    directions: np.ndarray                 # float64 (M, 3): the shared directions
+    hi_mm: np.ndarray                      # float64 (m, M): the largest projection (extent="voxels": of the voxel boxes)
+    lo_mm: np.ndarray                      # float64 (m, M): the smallest
+    width_mm: np.ndarray                   # float64 (m, M): hi_mm - lo_mm, the caliper diameter along every direction
+    max_mm: np.ndarray                     # float64 (m,): the largest width ...
+    max_index: np.ndarray                  # int64 (m,): ... its direction, the lowest index among equals ...
+    max_direction: np.ndarray              # float64 (m, 3): ... and that row of directions
+    min_mm: np.ndarray                     # float64 (m,): the smallest width, likewise
+    min_index: np.ndarray
+    min_direction: np.ndarray
+    axes: np.ndarray = None                # float64 (m, 3, 3): component_moments' principal_axes, rows
+    oriented_extent_mm: np.ndarray = None  # float64 (m, 3): the widths along those
+    oriented_center_mm: np.ndarray = None  # float64 (m, 3): the midpoints (hi + lo) / 2 along the axes, mapped back to (z, y, x)
+    oriented_volume_mm3: np.ndarray = None  # float64 (m,): the product of the three extents
+
+    def __len__(self):
+        return len(self.labels)
+
+
+def _component_caliper_from(dirs, shared=None, moments=None, own=None, oriented=False) -> ComponentCaliper:
+    """Host side of the downloaded rows: shared / own = (rows int64 (m, 4), hi, lo, width float64 (m, M), ext float64 (m, 2)) as
+    tomo_cc_caliper_rows writes them for the shared directions / the component's own axes; shared=None: no selected component."""
+    M = len(dirs)
+    if shared is None:
+        shared = (np.zeros((0, 4), dtype=np.int64), *(np.zeros((0, M), dtype=np.float64) for _ in range(3)), np.zeros((0, 2), dtype=np.float64))
+        if oriented:
+            own = (np.zeros((0, 4), dtype=np.int64), *(np.zeros((0, 3), dtype=np.float64) for _ in range(3)), np.zeros((0, 2), dtype=np.float64))
+    rows, hi, lo, width, ext = shared
+    rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1, 4)
+    imax, imin = rows[:, 2].copy(), rows[:, 3].copy()
+    out = ComponentCaliper(rows[:, 0].copy(), rows[:, 1].copy(), dirs, np.ascontiguousarray(hi), np.ascontiguousarray(lo),
+                           np.ascontiguousarray(width), ext[:, 0].copy(), imax, dirs[imax], ext[:, 1].copy(), imin, dirs[imin])
+    if oriented:
+        _, ohi, olo, owidth, _ = own
+        axes = np.zeros((0, 3, 3), dtype=np.float64) if moments is None else np.ascontiguousarray(moments.principal_axes)
+        mid = 0.5 * (ohi + olo)
+        centre = (mid[:, 0:1] * axes[:, 0, :] + mid[:, 1:2] * axes[:, 1, :]) + mid[:, 2:3] * axes[:, 2, :]
+        out.axes, out.oriented_extent_mm, out.oriented_center_mm = axes, np.ascontiguousarray(owidth), np.ascontiguousarray(centre)
+        out.oriented_volume_mm3 = (owidth[:, 0] * owidth[:, 1]) * owidth[:, 2]
+    return out
+
+
+def component_caliper(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, connectivity=6, min_voxels=0,
+                      largest=False, directions=None, extent="voxels", oriented=False) -> ComponentCaliper:
+    """Caliper (Feret) diameters per component of a resident volume -> ComponentCaliper, one row per component the keep rule of
+    component_properties selects (at least min_voxels voxels; largest: only the largest of those, the lowest label among
+    equals), in ascending label: the rows component_properties returns for the same rule.
+    The caliper diameter along a unit vector u = (u_z, u_y, u_x) is the distance between the two planes with normal u that
+    hold the component between them: width = hi - lo.  Voxel (k, j, i) sits at (zc[k], j mm_y, i mm_x), the coordinates of
+    distance_transform, and projects to p = ((zc[k] u_z + j mm_y u_y) + i mm_x u_x) + 0.0, every product and sum rounded on
+    its own.  extent="centres": hi = max p, lo = min p over the voxels.  extent="voxels" (the default): the union of the voxel
+    boxes, hi = max(p + H), lo = min(p - H) with H = 0.5 ((|u_z| d_k + |u_y| mm_y) + |u_x| mm_x), d_k the depth of slice k: one
+    voxel reads its own box width along u, not 0.  directions: float (M, 3) unit vectors (within 1e-12) shared by all
+    components; None: caliper_directions(), CALIPER_DIRECTIONS = 64 of them.  max_mm / min_mm are the largest and the
+    smallest width over the set, with the index and the row of the direction (the lowest index among equals).  max_mm is the
+    max Feret diameter up to the set's cover factor (caliper_cover: max_mm >= 0.9669 D for the default set, 0.9823 for 128
+    directions, 0.9922 for 256) and never above it; min_mm is an UPPER bound of the min Feret diameter: the width a sieve must
+    have for the grain to pass is at most that.
+    oriented=True: component_moments runs first under the same rule, and every component is also measured along its own
+    principal axes: axes (component_moments' principal_axes, bytes equal), oriented_extent_mm (the widths along them: the box
+    aligned with the moment axes -- not the minimum-volume box), oriented_center_mm (the midpoints along the axes mapped back
+    to (z, y, x) mm) and oriented_volume_mm3 (the product of the extents).
+    Cost: a projection is monotone along an x-run, so only the two ends of every run are evaluated: one pass over the rows per
+    8 directions, nothing per voxel.  Memory: 16 M bytes per SELECTED component for the extremes (beyond COMPONENT_HIST_BUDGET
+    for more than one component: TomoError naming min_voxels) -- nothing per component of the volume.  Maxima and minima of
+    integer keys only: the same bytes on every run, and bit for bit what NumPy gives over all voxels.  An empty volume, or
+    nothing selected, gives zero rows.  Arguments are checked before the first launch."""
+    _check_connectivity(connectivity)
+    _keep_rule(min_voxels, largest)
+    _caliper_args(vol.shape, slice_depths, mm_per_pixel_y, mm_per_pixel_x, directions, extent)
+    return ComponentRuns(vol, connectivity).caliper(slice_depths, mm_per_pixel_y, mm_per_pixel_x, directions, extent, oriented,
+                                                    min_voxels, largest)
+
+
+def cavity_caliper(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, connectivity=6, min_voxels=0,
+                   max_voxels=None, directions=None, extent="voxels", oriented=False) -> ComponentCaliper:
+    """component_caliper of the enclosed voids of a resident volume, one row per cavity of cavity_table under the same size
+    window (min_voxels <= voxels <= max_voxels), in ascending cavity label: how long and how wide a pore is -- a crack reads its
+    length in max_mm and its opening in min_mm, where the equivalent diameter is no size at all.  One labelling of the
+    complement under the complementary connectivity; an empty or a full volume has no rows.  Arguments are checked before the
+    first launch."""
+    connectivity = _check_connectivity(connectivity)
+    lo, hi = _check_size_window(min_voxels, max_voxels)
+    _caliper_args(vol.shape, slice_depths, mm_per_pixel_y, mm_per_pixel_x, directions, extent)
+    bg = _complement_runs(vol, connectivity)
+    return bg.caliper(slice_depths, mm_per_pixel_y, mm_per_pixel_x, directions, extent, oriented, lo, max_voxels=hi, enclosed=True)
 
 
 def local_thickness(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, radii_mm=None,

@@ -146,7 +146,7 @@ def surface_area(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, direc
 
 
 def closed_porosity(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=6, min_voxels=0, max_voxels=None,
-                    pore_size=False):
+                    pore_size=False, pore_caliper=False):
     """The enclosed voids of the volume, listed and added up (no counterpart in the reference): pipeline.cavity_table -- a
     cavity is a component of the complement, under the complementary connectivity, that reaches no face of the stack; per-slice
     depths honoured -> {'cavities', 'cavity_voxels', 'cavity_volume_mm3', 'voxel_volume_mm3', 'closed_porosity', 'table'}.
@@ -159,6 +159,10 @@ def closed_porosity(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, co
     'inscribed_diameter_mm' -- twice the largest inside distance of the cavity, the widest ball that fits in the pore: for a
     crack-shaped pore the size that equivalent_diameter_mm is not -- and 'inscribed_center_index' (z, y, x), and the report
     'largest_pore_diameter_mm' (0.0 without pores): pipeline.cavity_sizes, ONE transform of the complement for all pores together.
+    pore_caliper=True: every row also carries 'max_caliper_mm' and 'min_caliper_mm' -- the largest and the smallest caliper
+    (Feret) diameter of the pore over pipeline.caliper_directions(), voxel extents included (pipeline.ComponentRuns.caliper on the
+    complement's tables): the length and the opening of a crack -- and the report 'longest_pore_mm', the largest 'max_caliper_mm'
+    of the rows (0.0 without pores).
     voxel_data: the bool (nz, ny, nx) array the other calculations take; anything else is a TypeError -- there is no host path
     for this one."""
     if not _on_device(voxel_data):
@@ -168,7 +172,16 @@ def closed_porosity(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, co
     pipeline._check_size_window(min_voxels, max_voxels)
     pipeline._slice_weights(depths, len(voxel_data), mm_per_pixel_y, mm_per_pixel_x)
     vol = to_device_volume(voxel_data)
-    if pore_size:
+    if pore_caliper:                                             # the steps of cavity_table / cavity_sizes on ONE object
+        lo, hi = pipeline._check_size_window(min_voxels, max_voxels)
+        runs = pipeline.ComponentRuns(vol, connectivity)
+        bg = runs.background()
+        tables = pipeline._slice_weights(depths, len(voxel_data), mm_per_pixel_y, mm_per_pixel_x)
+        t = pipeline._cavities_from(runs, bg.properties(tables, mm_per_pixel_y, mm_per_pixel_x, lo, max_voxels=hi, enclosed=True))
+        if pore_size:
+            size = bg.thickness(depths, mm_per_pixel_y, mm_per_pixel_x, None, lo, max_voxels=hi, enclosed=True)
+        feret = bg.caliper(depths, mm_per_pixel_y, mm_per_pixel_x, min_voxels=lo, max_voxels=hi, enclosed=True)
+    elif pore_size:
         t, size = pipeline.cavity_sizes(vol, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_voxels, max_voxels)
     else:
         t = pipeline.cavity_table(vol, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_voxels, max_voxels)
@@ -191,12 +204,17 @@ def closed_porosity(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, co
             row['inscribed_diameter_mm'] = 2 * float(size.radius_mm[i])
             row['inscribed_center_index'] = tuple(int(v) for v in size.center_index[i])
         report['largest_pore_diameter_mm'] = max((row['inscribed_diameter_mm'] for row in table), default=0.0)
+    if pore_caliper:
+        assert np.array_equal(feret.labels, t.labels)
+        for i, row in enumerate(table):
+            row['max_caliper_mm'], row['min_caliper_mm'] = float(feret.max_mm[i]), float(feret.min_mm[i])
+        report['longest_pore_mm'] = max((row['max_caliper_mm'] for row in table), default=0.0)
     return report
 
 
 def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=6, min_voxels=0, largest=False,
                          shape=False, topology=False, surface=False, surface_directions=13, porosity=False, thickness=False,
-                         thickness_radii_mm=None):
+                         thickness_radii_mm=None, caliper=False, caliper_directions=None, caliper_oriented=False):
     """The calculations of the class per connected component (no counterpart in the reference, which would be handed the mask
     `labels == c` once per component) -> a list of dicts, one per component with at least min_voxels voxels (largest: only the
     largest of those), in label order: {'label', 'voxels', 'voxel_volume_mm3', 'bounding_box': {'x', 'y', 'z'}, 'dimensions',
@@ -219,7 +237,11 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
     thickness_radii_mm (ascending ball radii), its local thickness as thickness_statistics gives it for the mask:
     'thickness_mean_mm', 'thickness_std_mm', 'thickness_max_mm', 'thickness_uncovered_voxels' and 'thickness_histogram' =
     [(diameter_mm, voxels, volume_mm3), ...] (pipeline.component_thickness: one transform of the whole volume, never one per
-    component).  Whatever the
+    component).  caliper=True: every dict also carries the caliper (Feret) diameters of the component over caliper_directions
+    (float (M, 3) unit vectors; None: pipeline.caliper_directions()), voxel extents included (pipeline.component_caliper):
+    'max_caliper_mm', 'max_caliper_direction' (z, y, x), 'min_caliper_mm', 'min_caliper_direction', and with caliper_oriented
+    also 'oriented_box_mm' -- the extents along the component's principal axes -- and 'oriented_box_center_mm' (z, y, x).
+    Whatever the
     flags, the volume is uploaded and labelled ONCE, and so is its complement: one pipeline.ComponentRuns serves all the
     measurements and owns the one selection their rows come from.  Arguments are checked before the first launch.  voxel_data: a bool (nz, ny, nx) array, else a TypeError."""
     if not _on_device(voxel_data):
@@ -231,6 +253,8 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
     factors = pipeline.surface_factors(depths, len(voxel_data), mm_per_pixel_y, mm_per_pixel_x, surface_directions) if surface else None
     if thickness:
         pipeline._component_thickness_args(voxel_data.shape, depths, mm_per_pixel_y, mm_per_pixel_x, thickness_radii_mm)
+    if caliper:
+        pipeline._caliper_args(voxel_data.shape, depths, mm_per_pixel_y, mm_per_pixel_x, caliper_directions, "voxels")
     runs = pipeline.ComponentRuns(to_device_volume(voxel_data), connectivity)
     if runs.select(*rule) is None:
         return []
@@ -244,6 +268,7 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
     t = runs.topology_rows(*rule) if topology else None
     a = runs.surface(factors, surface_directions, *rule) if surface else None
     h = runs.thickness(depths, mm_per_pixel_y, mm_per_pixel_x, thickness_radii_mm, *rule) if thickness else None
+    f = runs.caliper(depths, mm_per_pixel_y, mm_per_pixel_x, caliper_directions, "voxels", caliper_oriented, *rule) if caliper else None
     pores = {}
     if porosity:                                                 # every cavity of the volume, credited to its owner
         c = pipeline._cavities_from(runs, runs.background().properties(tables, mm_per_pixel_y, mm_per_pixel_x, enclosed=True))
@@ -276,6 +301,14 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
                 d['thickness_max_mm'], d['thickness_uncovered_voxels'] = float(h.max_mm[i]), int(h.uncovered_voxels[i])
                 d['thickness_histogram'] = [(2.0 * float(r), int(n), float(v))
                                             for r, n, v in zip(h.radii_mm, h.level_voxels[i], h.level_volume_mm3[i])]
+        if caliper:
+            d['max_caliper_mm'] = float(f.max_mm[i])
+            d['max_caliper_direction'] = tuple(float(v) for v in f.max_direction[i])
+            d['min_caliper_mm'] = float(f.min_mm[i])
+            d['min_caliper_direction'] = tuple(float(v) for v in f.min_direction[i])
+            if caliper_oriented:
+                d['oriented_box_mm'] = tuple(float(v) for v in f.oriented_extent_mm[i])
+                d['oriented_box_center_mm'] = tuple(float(v) for v in f.oriented_center_mm[i])
     return out
 
 
