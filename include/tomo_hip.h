@@ -422,6 +422,55 @@ int tomo_cc_caliper_axes(const uint64_t *bits, int nz, int ny, int nx, const uin
                          const double *depth, double mm_y, double mm_x, uint64_t *hi, uint64_t *lo, int64_t cap_sel, void *stream);
 int tomo_cc_caliper_rows(const int64_t *table, int64_t cap, unsigned long long *tot, const uint8_t *sel, const uint32_t *slot,
                          uint64_t *hi, uint64_t *lo, int M, double *width, int64_t *rows, double *ext, int64_t cap_sel, void *stream);
+/* Geodesic distance inside the set voxels (no counterpart in the reference): the length in mm of the shortest path that never
+ * leaves the object, from a set of seeds.
+ * The metric, one definition.  Voxel (k, j, i) sits at (zc[k], j * mm_y, i * mm_x), the coordinates of tomo_edt_distance.  A step
+ * goes from a set voxel to a set voxel that is its neighbour under the connectivity, 6 or 26: the 26-adjacency of the two ends
+ * alone, no corner-cutting test -- the adjacency of tomo_cc_label_runs, so a path never leaves a component.  The weight of a step
+ * is its Euclidean length, computed on the host in float64 as sqrt(((dx * mm_x)^2 + (dy * mm_y)^2) + dzc^2), dzc = zc[k + 1] -
+ * zc[k] between slices k and k + 1, and rounded ONCE to float32: wxy float32[3] for the steps x, y, xy; wz float32[max(nz - 1,
+ * 1)][4] for the steps z, zx, zy, zyx across the boundary between slice k and k + 1 (connectivity 6 reads x, y and z only).
+ * dist(p) = the minimum over the paths from a seed to p of the left-to-right float32 sum of the weights: 0.0 at a seed that is
+ * set, +inf at a set voxel no seed reaches and at every unset voxel; a seed on an unset voxel is ignored.  This is the path
+ * length on the 6 / 26 lattice: exact along the lattice directions, an overestimate between them like any chamfer metric, and
+ * a float32 sum carries float32's relative precision along a very long path.
+ * The fixed point.  The device only adds and takes minima (no contraction): d' = fl32(d + w) is monotone in d, so the system
+ * dist(p) = min(seed(p), min over neighbours q of fl32(dist(q) + w)) has a unique least fixed point below the seeded map, and
+ * values only fall through a finite set.  Every order of relaxations, every tiling and every race between tiles ends at the same
+ * bytes: those Dijkstra's algorithm with the same float32 additions returns.
+ * Tiles: 8 x 8 x 64 voxels (z, y, x), one word of the bit volume wide; tile (bz, by, bx) has the number (bz * ty + by) * wx + bx,
+ * ty = ceil(ny / 8).  dirty arrays: uint32 per tile, zero or one.
+ *   tomo_geo_tiles       the number of tiles (< 0: error)
+ *   tomo_geo_seed_bits   one pass over the volume: dist = 0.0 where bits & seeds, +inf elsewhere; dirty[t] = 1 for every tile that
+ *                        holds a seed, and for every neighbouring tile next to a seed on a face, an edge or a corner of its tile
+ *                        (a seed is a change no sweep made, so no sweep would announce it); the caller zeroes both dirty arrays
+ *   tomo_geo_seed_index  dist is prefilled with +inf by the caller.  One thread per entry c < n writes 0.0 at the flat index
+ *                        index[c] = (z * ny + y) * nx + x where sel is NULL or sel[c] is set, and marks the tiles likewise; an entry of all
+ *                        ones is skipped; an index outside the volume or on an unset voxel sets bit 2 of counters[1] and writes
+ *                        nothing
+ *   tomo_geo_sweep       one relaxation sweep: one workgroup of 256 threads per tile.  A workgroup whose flag in dirty_cur is
+ *                        clear returns at once, otherwise it clears that flag (only it reads it), loads its interior and a
+ *                        one-voxel halo of dist into LDS (unset voxels and everything outside the stack: +inf) and relaxes the
+ *                        interior to convergence against the fixed halo, in race-free rounds bounded by the number of interior
+ *                        voxels; a tile that hits the bound marks itself in dirty_next.  If something changed it stores the
+ *                        changed voxels, adds 1 to counters[0] (once per workgroup) and sets dirty_next of every neighbouring
+ *                        tile (up to 26; 6: up to 6) next to a face, edge or corner voxel that changed.  Only the owning
+ *                        workgroup writes a dist entry: no atomics on dist.  A neighbouring tile may read an interior while it
+ *                        is written: a stale value is a valid upper bound, aligned 32-bit accesses do not tear, and the writer
+ *                        marks the reader for the next sweep -- that is the whole correctness argument.  Nothing waits on
+ *                        another workgroup.  The caller swaps the two dirty arrays between sweeps and stops at a sweep (a batch
+ *                        of sweeps) that left counters[0] unchanged: all flags are clear then.
+ *   tomo_geo_reach       out = the set voxels with dist <= max_mm as a bit volume; max_mm = +inf: with a finite dist
+ * counters: unsigned long long[2], zeroed by the caller.  TOMO_E_ARG for a null pointer (sel excepted), a non-positive size or n,
+ * dirty_cur == dirty_next, a connectivity other than 6 / 26, a max_mm that is negative or NaN; TOMO_E_SIZE from 2^31 tiles or
+ * words on. */
+int64_t tomo_geo_tiles(int nz, int ny, int nx);
+int tomo_geo_seed_bits(const uint64_t *bits, const uint64_t *seeds, int nz, int ny, int nx, float *dist, uint32_t *dirty, void *stream);
+int tomo_geo_seed_index(const uint64_t *bits, int nz, int ny, int nx, const uint64_t *index, const uint8_t *sel, int64_t n,
+                        float *dist, uint32_t *dirty, unsigned long long *counters, void *stream);
+int tomo_geo_sweep(const uint64_t *bits, int nz, int ny, int nx, int connectivity, const float *wxy, const float *wz, float *dist,
+                   uint32_t *dirty_cur, uint32_t *dirty_next, unsigned long long *counters, void *stream);
+int tomo_geo_reach(const uint64_t *bits, const float *dist, int nz, int ny, int nx, double max_mm, uint64_t *out, void *stream);
 /* The same across Z-slabs (slab_components.py): rank r labels its slab with the functions above (n_r components); local
  * component c has the global id base_r + c, base_r = n_0 + .. + n_(r-1).  Pieces that touch across a cut are united, the roots
  * (smallest id = the piece with the component's first voxel) numbered in ascending id: scipy's numbering of the whole stack.

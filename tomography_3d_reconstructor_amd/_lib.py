@@ -105,6 +105,11 @@ SIGNATURES = {
     "tomo_edt_cover": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_d, _c_i, _c_p, _c_p, _c_i64, _c_p]),
     "tomo_edt_threshold_masked": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_i, _c_d, _c_i, _c_p, _c_p, _c_p, _c_i64, _c_p]),
     "tomo_edt_thickness_finish": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_p, _c_i, _c_p, _c_p]),
+    "tomo_geo_tiles": (_c_i64, [_c_i, _c_i, _c_i]),
+    "tomo_geo_seed_bits": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p]),
+    "tomo_geo_seed_index": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p]),
+    "tomo_geo_sweep": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
+    "tomo_geo_reach": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_d, _c_p, _c_p]),
     "tomo_pack_threshold": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_p]),
     "tomo_obj_write": (_c_i, [ctypes.c_char_p, _c_p, _c_i, _c_i64, _c_p, _c_i64, _c_i]),
     "tomo_obj_block_format": (_c_i, [_c_i, _c_p, _c_i64, _c_i, ctypes.POINTER(_c_p), ctypes.POINTER(_c_i64)]),

@@ -1297,6 +1297,8 @@ __device__ static inline bool cc_word_at(const u64 *__restrict__ bits, int64_t n
     return true;
 }
 
+__device__ static inline u64 cc_load64(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
 // the float32 bits of the value of a SET voxel: the distance map itself, or (float)sqrt(d2) -- what EDT_TAIL_FLOAT stores
 __device__ static inline u32 cc_value_bits(const float *__restrict__ dist, const double *__restrict__ d2, int64_t at)
 {
@@ -1306,7 +1308,8 @@ __device__ static inline u32 cc_value_bits(const float *__restrict__ dist, const
 // best[c] = the largest float32 bit pattern over component c + 1 (values >= 0: unsigned order is float order); FIRST: first[c] =
 // the smallest flat index whose value has the bits best[c].  Per run of the word one wave reduction and at most one atomic: a
 // maximum that does not beat what best[c] already holds is not sent (one solid body would otherwise queue every word of the
-// volume on one address), and only the runs that attain the maximum send an index.
+// volume on one address), and only the runs that attain the maximum send an index -- and of those only the ones whose index is
+// below what first[c] already shows (a map that is constant over a body, all 0.0 or all +inf, would queue every word again).
 template <bool FIRST>
 __global__ __launch_bounds__(CC_THREADS) void cc_value_kernel(const u64 *__restrict__ bits, int64_t nwords, int nx, int wx,
                                                               const u32 *__restrict__ row_off, const u64 *__restrict__ tot,
@@ -1335,7 +1338,10 @@ __global__ __launch_bounds__(CC_THREADS) void cc_value_kernel(const u64 *__restr
             if (a.bit == 0 && top > cc_load(best + c)) atomicMax(best + c, top);
         } else {
             const u64 hit = __ballot(mine && v == best[c]);
-            if (hit && a.bit == 0) atomicMin(first + c, (unsigned long long)(at + (__ffsll((long long)hit) - 1)));
+            if (hit && a.bit == 0) {                            // first[c] only falls: a stale read costs an atomic, never the answer
+                const u64 cand = (u64)(at + (__ffsll((long long)hit) - 1));
+                if (cand < cc_load64((const u64 *)first + c)) atomicMin(first + c, (unsigned long long)cand);
+            }
         }
     }
 }
@@ -1559,8 +1565,6 @@ __device__ static inline double cc_key_f64(u64 k)
 {
     return __longlong_as_double((long long)((k >> 63) ? k & ~(1ull << 63) : ~k));
 }
-
-__device__ static inline u64 cc_load64(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 struct CcCaliperOut {
     u64 *hi, *lo;                                           // keys [cap_sel][M]

@@ -1,0 +1,395 @@
+// geodesic.hip -- geodesic distance inside the set voxels of the resident bit volume, in millimetres (no counterpart in the
+// reference).  Contract, metric and the fixed-point argument: include/tomo_hip.h.
+//
+// The map is float32 (nz, ny, nx).  dist(p) = min over the set neighbours q of p of fl32(dist(q) + w(q, p)) -- additions and
+// minima only, the file is built with -ffp-contract=off.  Rounded addition is monotone in dist(q), so the relaxation has ONE
+// least fixed point below the seeded map, and every order of relaxations ends there: the kernel is free to relax tile by tile,
+// in any order, with stale neighbours.
+//
+// Tiles.  A tile is GEO_TZ x GEO_TY x 64 voxels, one 64-bit word of the bit volume wide: the mask of a tile row is one word plus
+// bit 63 / bit 0 of the two neighbouring words.  One workgroup of 256 threads per tile; lane = x, so every LDS access of a wave is
+// 64 consecutive floats (no bank conflict, the x - 1 / x + 1 reads included), and a thread owns the 16 rows wave + 4 k of its
+// column in registers.  LDS: the (TZ + 2) x (TY + 2) x 66 halo box of floats, 26 400 bytes, the row masks and the z weights.
+//
+// One sweep (tomo_geo_sweep).  A workgroup whose flag in dirty_cur is clear leaves at once; otherwise it clears the flag (only it
+// reads it), loads its box -- unset voxels and everything outside the stack are +inf -- and relaxes the interior against the
+// FIXED halo until a round changes nothing.  A round is race free: every thread forms the candidates of its voxels from the
+// published LDS copy, all pass a barrier, the changed values are published, __syncthreads_or ends the round.  The rounds are
+// bounded by GEO_ROUNDS, the number of interior voxels (a shortest path inside the tile has fewer steps); a tile that hits the
+// bound marks itself in dirty_next.  Only the changed voxels are stored back, by their owner alone: dist needs no atomics.  A
+// neighbouring tile may read such a voxel while it is written: it gets the old or the new value (aligned 32-bit accesses do not
+// tear), both are upper bounds of the fixed point, and the writer marks every neighbouring tile next to a changed face, edge or
+// corner voxel in dirty_next, so the reader runs again in the next sweep, after the kernel boundary has published the store.
+// Nothing waits on another workgroup: no grid barrier, no persistent grid, no spin.  The host stops when a sweep changed nothing.
+#include "tomo_common.h"
+#include <math.h>
+
+#define GEO_THREADS 256
+#define GEO_TZ 8
+#define GEO_TY 8
+#define GEO_ROWS (GEO_TZ * GEO_TY)                 // rows of the interior
+#define GEO_PER (GEO_ROWS / 4)                     // voxels per thread: 4 waves
+#define GEO_HZ (GEO_TZ + 2)
+#define GEO_HY (GEO_TY + 2)
+#define GEO_HX 66
+#define GEO_HROWS (GEO_HZ * GEO_HY)
+#define GEO_BOX (GEO_HROWS * GEO_HX)
+#define GEO_ROUNDS (GEO_ROWS * 64)                 // the bound of the inner loop: the interior voxels
+#define GEO_F_SEED 4ull                            // counters[1]: a seed index outside the volume or on an unset voxel
+
+struct GeoGrid {
+    int64_t tz, ty, wx, tiles, words;
+};
+
+static int geo_grid(int nz, int ny, int nx, GeoGrid *g)
+{
+    if (nz <= 0 || ny <= 0 || nx <= 0) return TOMO_E_ARG;
+    g->tz = ((int64_t)nz + GEO_TZ - 1) / GEO_TZ;
+    g->ty = ((int64_t)ny + GEO_TY - 1) / GEO_TY;
+    g->wx = tomo_words_per_row(nx);
+    g->words = (int64_t)nz * ny * g->wx;
+    if (g->words >= ((int64_t)1 << 31)) return TOMO_E_SIZE;      // then tz * ty * wx < 2^31 as well
+    g->tiles = g->tz * g->ty * g->wx;
+    if (g->tiles >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
+    return TOMO_OK;
+}
+
+TOMO_API int64_t tomo_geo_tiles(int nz, int ny, int nx)
+{
+    GeoGrid g;
+    const int r = geo_grid(nz, ny, nx, &g);
+    return r != TOMO_OK ? r : g.tiles;
+}
+
+// the set voxels of word w of a row, whatever the buffer holds in the tail bits
+__device__ static inline u64 geo_word(const u64 *__restrict__ row, int nx, int wx, int w)
+{
+    const int r = nx - 64 * (wx - 1);
+    const u64 tail = (w == wx - 1 && r < 64) ? ((1ull << r) - 1) : ~0ull;
+    return row[w] & tail;
+}
+
+// ---------------------------------------------------------------------------------------------- seeding
+// A seed is a change nobody relaxed: its own tile is dirty, and so is every neighbouring tile next to it when it lies on a face,
+// an edge or a corner of its tile -- the sweep marks neighbours only for voxels IT lowered, and a seed is at its minimum already.
+// Every writer stores the same 1.
+__device__ static inline void geo_mark_seed(u32 *__restrict__ dirty, int z, int y, int x, int nz, int ty, int wx)
+{
+    const int bz = z / GEO_TZ, by = y / GEO_TY, bx = x >> 6;
+    const int lz = z % GEO_TZ, ly = y % GEO_TY, lx = x & 63;
+    const int tz = (nz + GEO_TZ - 1) / GEO_TZ;
+    for (int dz = -1; dz <= 1; dz++) {
+        if ((dz < 0 && lz != 0) || (dz > 0 && lz != GEO_TZ - 1) || bz + dz < 0 || bz + dz >= tz) continue;
+        for (int dy = -1; dy <= 1; dy++) {
+            if ((dy < 0 && ly != 0) || (dy > 0 && ly != GEO_TY - 1) || by + dy < 0 || by + dy >= ty) continue;
+            for (int dx = -1; dx <= 1; dx++) {
+                if ((dx < 0 && lx != 0) || (dx > 0 && lx != 63) || bx + dx < 0 || bx + dx >= wx) continue;
+                dirty[((int64_t)(bz + dz) * ty + (by + dy)) * wx + (bx + dx)] = 1u;
+            }
+        }
+    }
+}
+
+// a wave is one word of a row, a lane one voxel: dist = 0.0 at a set seed, +inf elsewhere
+__global__ __launch_bounds__(GEO_THREADS) void geo_seed_bits_kernel(const u64 *__restrict__ bits, const u64 *__restrict__ seeds,
+                                                                    int64_t nwords, int nz, int ny, int nx, int wx, int ty,
+                                                                    float *__restrict__ dist, u32 *__restrict__ dirty)
+{
+    const int64_t t = (int64_t)blockIdx.x * GEO_THREADS + threadIdx.x;
+    const int64_t word = t >> 6;                             // the same for the 64 lanes of a wave
+    if (word >= nwords) return;
+    const int64_t row = word / wx;
+    const int w = (int)(word - row * wx);
+    const int b = (int)(t & 63);
+    const int x = 64 * w + b;
+    const u64 m = geo_word(bits + row * wx, nx, wx, w) & seeds[word];
+    const bool seed = (m >> b) & 1;                          // below nx: the tail bits of m are zero
+    if (x < nx) dist[row * nx + x] = seed ? 0.0f : INFINITY;
+    if (seed) {
+        const int z = (int)(row / ny), y = (int)(row - (int64_t)z * ny);
+        if (b == 0 || b == 63 || b == __ffsll((long long)m) - 1)      // one lane for the tile itself, the two ends for the x faces
+            geo_mark_seed(dirty, z, y, x, nz, ty, wx);
+    }
+}
+
+// one thread per entry: 0.0 at flat index index[c] where sel is NULL or sel[c] is set; all ones: skipped
+__global__ __launch_bounds__(GEO_THREADS) void geo_seed_index_kernel(const u64 *__restrict__ bits, int64_t total, int nz, int ny, int nx,
+                                                                     int wx, int ty, const u64 *__restrict__ index,
+                                                                     const uint8_t *__restrict__ sel, int64_t n,
+                                                                     float *__restrict__ dist, u32 *__restrict__ dirty,
+                                                                     unsigned long long *counters)
+{
+    const int64_t c = (int64_t)blockIdx.x * GEO_THREADS + threadIdx.x;
+    if (c >= n || (sel && !sel[c])) return;
+    const u64 at = index[c];
+    if (at == ~0ull) return;
+    if (at >= (u64)total) {
+        atomicOr(counters + 1, GEO_F_SEED);
+        return;
+    }
+    const int64_t row = (int64_t)(at / (u64)nx);
+    const int x = (int)((int64_t)at - row * nx);
+    if (!((geo_word(bits + row * wx, nx, wx, x >> 6) >> (x & 63)) & 1)) {
+        atomicOr(counters + 1, GEO_F_SEED);
+        return;
+    }
+    const int z = (int)(row / ny), y = (int)(row - (int64_t)z * ny);
+    dist[at] = 0.0f;                                         // a plain vector store; equal entries store the same value
+    geo_mark_seed(dirty, z, y, x, nz, ty, wx);
+}
+
+// ---------------------------------------------------------------------------------------------- one sweep
+// the 13 neighbours behind a voxel and the 13 in front of it are visited by their offset into the halo box; class of the step:
+// 0 x, 1 y, 2 xy (wxy), then 0 z, 1 zx, 2 zy, 3 zyx (a row of wz)
+template <int CONN>
+__device__ static inline float geo_relax(const float *__restrict__ p, float d, const float wx_, const float wy_, const float wxy_,
+                                         const float *__restrict__ wlo, const float *__restrict__ whi)
+{
+    // p points at the voxel inside the halo box; strides: x 1, y GEO_HX, z GEO_HY * GEO_HX
+    const int sy = GEO_HX, sz = GEO_HY * GEO_HX;
+    float c = d;
+    c = fminf(c, p[-1] + wx_);
+    c = fminf(c, p[1] + wx_);
+    c = fminf(c, p[-sy] + wy_);
+    c = fminf(c, p[sy] + wy_);
+    c = fminf(c, p[-sz] + wlo[0]);
+    c = fminf(c, p[sz] + whi[0]);
+    if (CONN == 26) {
+        c = fminf(c, p[-sy - 1] + wxy_);
+        c = fminf(c, p[-sy + 1] + wxy_);
+        c = fminf(c, p[sy - 1] + wxy_);
+        c = fminf(c, p[sy + 1] + wxy_);
+#pragma unroll
+        for (int s = -1; s <= 1; s += 2) {
+            const float *q = p + s * sz;
+            const float *w = s < 0 ? wlo : whi;
+            c = fminf(c, q[-1] + w[1]);
+            c = fminf(c, q[1] + w[1]);
+            c = fminf(c, q[-sy] + w[2]);
+            c = fminf(c, q[sy] + w[2]);
+            c = fminf(c, q[-sy - 1] + w[3]);
+            c = fminf(c, q[-sy + 1] + w[3]);
+            c = fminf(c, q[sy - 1] + w[3]);
+            c = fminf(c, q[sy + 1] + w[3]);
+        }
+    }
+    return c;
+}
+
+// Two workgroups per CU at least: unbounded, the 26-neighbour variant unrolls into 256 VGPRs and one workgroup per CU; bounded it
+// takes 170, spills nothing, and a sweep takes 0.6 of the time (profiles/r31_geodesic.md).  The 6-neighbour variant takes 127.
+template <int CONN>
+__global__ __launch_bounds__(GEO_THREADS, 2) void geo_sweep_kernel(const u64 *__restrict__ bits, int nz, int ny, int nx, int wx, int ty,
+                                                                const float *__restrict__ wxy, const float *__restrict__ wz,
+                                                                float *dist, u32 *dirty_cur, u32 *dirty_next,
+                                                                unsigned long long *counters)
+{
+    __shared__ float box[GEO_BOX];
+    __shared__ u64 smid[GEO_HROWS];                          // the word of a halo row; 0 outside the stack
+    __shared__ u32 sside[GEO_HROWS];                         // bit 0: the voxel left of the word is set, bit 1: right
+    __shared__ float swz[(GEO_TZ + 1) * 4];                  // boundary b: between halo slices b and b + 1
+    __shared__ u32 snb;                                      // the neighbouring tiles to mark, one bit per (dz, dy, dx)
+
+    const int tid = threadIdx.x;
+    const int64_t tile = blockIdx.x;
+    if (!__syncthreads_or((int)dirty_cur[tile])) return;     // uniform: every thread has read the flag before it is cleared
+    if (tid == 0) {
+        dirty_cur[tile] = 0u;
+        snb = 0u;
+    }
+    const int bx = (int)(tile % wx);
+    const int64_t rest = tile / wx;
+    const int by = (int)(rest % ty), bz = (int)(rest / ty);
+    const int z0 = bz * GEO_TZ - 1, y0 = by * GEO_TY - 1;    // the halo box starts here
+
+    // the masks of the 100 halo rows and the z weights
+    if (tid < GEO_HROWS) {
+        const int z = z0 + tid / GEO_HY, y = y0 + tid % GEO_HY;
+        u64 mid = 0;
+        u32 side = 0;
+        if (z >= 0 && z < nz && y >= 0 && y < ny) {
+            const u64 *r = bits + ((int64_t)z * ny + y) * wx;
+            mid = geo_word(r, nx, wx, bx);
+            if (bx > 0 && (geo_word(r, nx, wx, bx - 1) >> 63)) side |= 1u;
+            if (bx + 1 < wx && (geo_word(r, nx, wx, bx + 1) & 1)) side |= 2u;
+        }
+        smid[tid] = mid;
+        sside[tid] = side;
+    } else if (tid >= 128 && tid < 128 + (GEO_TZ + 1) * 4) {
+        const int b = (tid - 128) >> 2, k = (tid - 128) & 3;
+        const int z = z0 + b;                                // the boundary between slices z and z + 1
+        swz[tid - 128] = (z >= 0 && z + 1 < nz) ? wz[4 * (int64_t)z + k] : INFINITY;
+    }
+    __syncthreads();
+
+    // the box: dist under the mask, +inf at unset voxels and outside the stack
+    for (int i = tid; i < GEO_BOX; i += GEO_THREADS) {
+        const int hr = i / GEO_HX, xx = i - hr * GEO_HX;
+        bool set;
+        if (xx == 0) set = sside[hr] & 1u;
+        else if (xx == GEO_HX - 1) set = (sside[hr] >> 1) & 1u;
+        else set = (smid[hr] >> (xx - 1)) & 1;
+        float v = INFINITY;
+        if (set) {                                           // a set voxel lies inside the stack and below nx
+            const int z = z0 + hr / GEO_HY, y = y0 + hr % GEO_HY;
+            v = dist[((int64_t)z * ny + y) * nx + (64 * bx + xx - 1)];
+        }
+        box[i] = v;
+    }
+    __syncthreads();
+
+    const int lane = tid & 63, wave = tid >> 6;
+    const float w_x = wxy[0], w_y = wxy[1], w_xy = wxy[2];
+    float d[GEO_PER];
+    u32 mine = 0, moved = 0;                                 // bit k: voxel k is set / has changed since the load
+#pragma unroll
+    for (int k = 0; k < GEO_PER; k++) {
+        const int r = wave + 4 * k;                          // interior row: z = r / TY, y = r % TY
+        const int hr = (r / GEO_TY + 1) * GEO_HY + (r % GEO_TY + 1);
+        d[k] = box[hr * GEO_HX + lane + 1];
+        if ((smid[hr] >> lane) & 1) mine |= 1u << k;
+    }
+
+    int more = 1, round = 0;
+    for (; round < GEO_ROUNDS && more; round++) {            // bounded: a tile that needs more marks itself below
+        u32 now = 0;
+#pragma unroll
+        for (int k = 0; k < GEO_PER; k++) {
+            if (!((mine >> k) & 1)) continue;
+            const int r = wave + 4 * k;
+            const int lz = r / GEO_TY;
+            const int hr = (lz + 1) * GEO_HY + (r % GEO_TY + 1);
+            const float c = geo_relax<CONN>(box + hr * GEO_HX + lane + 1, d[k], w_x, w_y, w_xy, swz + 4 * lz, swz + 4 * (lz + 1));
+            if (c < d[k]) {
+                d[k] = c;
+                now |= 1u << k;
+            }
+        }
+        __syncthreads();                                     // every candidate of the round is formed: publish
+#pragma unroll
+        for (int k = 0; k < GEO_PER; k++) {
+            if ((now >> k) & 1) {
+                const int r = wave + 4 * k;
+                box[((r / GEO_TY + 1) * GEO_HY + (r % GEO_TY + 1)) * GEO_HX + lane + 1] = d[k];
+            }
+        }
+        moved |= now;
+        more = __syncthreads_or((int)now);
+    }
+
+    // store what changed, and name the neighbouring tiles next to a changed face, edge or corner voxel
+    u32 nb = 0;
+#pragma unroll
+    for (int k = 0; k < GEO_PER; k++) {
+        if (!((moved >> k) & 1)) continue;
+        const int r = wave + 4 * k;
+        const int lz = r / GEO_TY, ly = r % GEO_TY;
+        const int z = z0 + 1 + lz, y = y0 + 1 + ly;
+        dist[((int64_t)z * ny + y) * nx + (64 * bx + lane)] = d[k];
+        const u32 zs = 2u | (lz == 0 ? 1u : 0u) | (lz == GEO_TZ - 1 ? 4u : 0u);     // bit 0 / 1 / 2: step -1 / 0 / +1
+        const u32 ys = 2u | (ly == 0 ? 1u : 0u) | (ly == GEO_TY - 1 ? 4u : 0u);
+        const u32 xs = 2u | (lane == 0 ? 1u : 0u) | (lane == 63 ? 4u : 0u);
+#pragma unroll
+        for (int a = 0; a < 3; a++)
+#pragma unroll
+            for (int b = 0; b < 3; b++)
+#pragma unroll
+                for (int c = 0; c < 3; c++)
+                    if (((zs >> a) & 1) && ((ys >> b) & 1) && ((xs >> c) & 1)) nb |= 1u << (9 * a + 3 * b + c);
+    }
+    if (nb) atomicOr(&snb, nb);                              // an LDS atomic
+    __syncthreads();
+    const u32 all = snb;
+    if (!(all || more)) return;                              // nothing changed: nothing is stored, nothing is marked
+    if (tid == 0) {
+        atomicAdd(counters, 1ull);                           // once per workgroup that changed something
+        if (more) dirty_next[tile] = 1u;                     // the round bound was hit
+    }
+    if (tid < 27 && tid != 13 && ((all >> tid) & 1)) {
+        const int dz = tid / 9 - 1, dy = (tid / 3) % 3 - 1, dx = tid % 3 - 1;
+        const int steps = (dz != 0) + (dy != 0) + (dx != 0);
+        const int tzn = (nz + GEO_TZ - 1) / GEO_TZ;
+        const int nbz = bz + dz, nby = by + dy, nbx = bx + dx;
+        if ((CONN == 26 || steps == 1) && nbz >= 0 && nbz < tzn && nby >= 0 && nby < ty && nbx >= 0 && nbx < wx)
+            dirty_next[((int64_t)nbz * ty + nby) * wx + nbx] = 1u;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- reach
+// out word = the set voxels with dist <= max_mm (max_mm = +inf: with a finite dist); a wave is one word, tail bits zero
+__global__ __launch_bounds__(GEO_THREADS) void geo_reach_kernel(const u64 *__restrict__ bits, const float *__restrict__ dist,
+                                                                int64_t nwords, int nx, int wx, double max_mm, int finite,
+                                                                u64 *__restrict__ out)
+{
+    const int64_t t = (int64_t)blockIdx.x * GEO_THREADS + threadIdx.x;
+    const int64_t word = t >> 6;
+    if (word >= nwords) return;
+    const int64_t row = word / wx;
+    const int w = (int)(word - row * wx);
+    const int b = (int)(t & 63);
+    const int x = 64 * w + b;
+    bool bit = false;
+    if (x < nx && ((bits[word] >> b) & 1)) {
+        const float v = dist[row * nx + x];
+        bit = finite ? v < INFINITY : (double)v <= max_mm;
+    }
+    const u64 m = __ballot(bit);
+    if (b == 0) out[word] = m;
+}
+
+// ---------------------------------------------------------------------------------------------- entry points
+TOMO_API int tomo_geo_seed_bits(const uint64_t *bits, const uint64_t *seeds, int nz, int ny, int nx, float *dist, uint32_t *dirty,
+                                void *stream)
+{
+    GeoGrid g;
+    if (!bits || !seeds || !dist || !dirty) return TOMO_E_ARG;
+    const int r = geo_grid(nz, ny, nx, &g);
+    if (r != TOMO_OK) return r;
+    hipLaunchKernelGGL(geo_seed_bits_kernel, dim3((unsigned)ceil_div64(g.words * 64, GEO_THREADS)), dim3(GEO_THREADS), 0,
+                       (hipStream_t)stream, (const u64 *)bits, (const u64 *)seeds, g.words, nz, ny, nx, (int)g.wx, (int)g.ty, dist, dirty);
+    return tomo_status();
+}
+
+TOMO_API int tomo_geo_seed_index(const uint64_t *bits, int nz, int ny, int nx, const uint64_t *index, const uint8_t *sel, int64_t n,
+                                 float *dist, uint32_t *dirty, unsigned long long *counters, void *stream)
+{
+    GeoGrid g;
+    if (!bits || !index || !dist || !dirty || !counters || n <= 0) return TOMO_E_ARG;
+    const int r = geo_grid(nz, ny, nx, &g);
+    if (r != TOMO_OK) return r;
+    if (ceil_div64(n, GEO_THREADS) >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
+    hipLaunchKernelGGL(geo_seed_index_kernel, dim3((unsigned)ceil_div64(n, GEO_THREADS)), dim3(GEO_THREADS), 0, (hipStream_t)stream,
+                       (const u64 *)bits, (int64_t)nz * ny * nx, nz, ny, nx, (int)g.wx, (int)g.ty, (const u64 *)index, sel, n, dist, dirty,
+                       counters);
+    return tomo_status();
+}
+
+TOMO_API int tomo_geo_sweep(const uint64_t *bits, int nz, int ny, int nx, int connectivity, const float *wxy, const float *wz,
+                            float *dist, uint32_t *dirty_cur, uint32_t *dirty_next, unsigned long long *counters, void *stream)
+{
+    GeoGrid g;
+    if (!bits || !wxy || !wz || !dist || !dirty_cur || !dirty_next || !counters || dirty_cur == dirty_next ||
+        (connectivity != 6 && connectivity != 26))
+        return TOMO_E_ARG;
+    const int r = geo_grid(nz, ny, nx, &g);
+    if (r != TOMO_OK) return r;
+    const dim3 grid((unsigned)g.tiles), block(GEO_THREADS);
+    if (connectivity == 6)
+        hipLaunchKernelGGL(geo_sweep_kernel<6>, grid, block, 0, (hipStream_t)stream, (const u64 *)bits, nz, ny, nx, (int)g.wx, (int)g.ty,
+                           wxy, wz, dist, dirty_cur, dirty_next, counters);
+    else
+        hipLaunchKernelGGL(geo_sweep_kernel<26>, grid, block, 0, (hipStream_t)stream, (const u64 *)bits, nz, ny, nx, (int)g.wx, (int)g.ty,
+                           wxy, wz, dist, dirty_cur, dirty_next, counters);
+    return tomo_status();
+}
+
+TOMO_API int tomo_geo_reach(const uint64_t *bits, const float *dist, int nz, int ny, int nx, double max_mm, uint64_t *out, void *stream)
+{
+    GeoGrid g;
+    if (!bits || !dist || !out || out == bits || (const void *)out == (const void *)dist || !(max_mm >= 0.0)) return TOMO_E_ARG;
+    const int r = geo_grid(nz, ny, nx, &g);
+    if (r != TOMO_OK) return r;
+    hipLaunchKernelGGL(geo_reach_kernel, dim3((unsigned)ceil_div64(g.words * 64, GEO_THREADS)), dim3(GEO_THREADS), 0,
+                       (hipStream_t)stream, (const u64 *)bits, dist, g.words, nx, (int)g.wx, max_mm, isinf(max_mm) ? 1 : 0, (u64 *)out);
+    return tomo_status();
+}

@@ -25,7 +25,8 @@ COUNTERS = dict.fromkeys(("na_hint_hit", "na_hint_miss", "mc3_hint_hit", "mc3_hi
                           "slab_components_expand", "slab_components_filter", "distance_transform", "distance_offset",
                           "components_measure", "components_zhist", "components_moments", "components_euler",
                           "components_cavities", "local_thickness", "opening_volume", "components_surface", "components_fill",
-                          "components_cavity_owners", "component_thickness", "components_value", "components_levels", "component_caliper"), 0)
+                          "components_cavity_owners", "component_thickness", "components_value", "components_levels", "component_caliper",
+                          "geodesic_calls", "geodesic_sweeps", "component_geodesic"), 0)
 NA_HINTS = os.environ.get("TOMO_NA_HINTS", "1") not in ("", "0")   # marching_cubes: launch ahead of the first count download
 _NA_HINT = {}
 LIST_LIMIT = 2 ** 31        # active-voxel list entries / vertices / triangles one pass can index (int32 offsets in mc.hip, mesh.hip);
@@ -333,7 +334,7 @@ class ComponentRuns:
     run of set bits in a row) and never per voxel.  Two host reads: the number of runs (it sizes the tables) and the
     counters after the labelling.  n = components; labels() / sizes() / keep() read the tables.
     One object serves every per-component measurement of its volume: properties(), moments(), topology_rows(), surface(),
-    thickness() and caliper() share the labelling, the measurement table and ONE selection, which the object owns (select).  background() is the same
+    thickness(), caliper() and geodesic() share the labelling, the measurement table and ONE selection, which the object owns (select).  background() is the same
     kind of object for the complement: its enclosed components are the cavities of this volume (cavity_owners)."""
 
     def __init__(self, vol: BitVolume, connectivity=6):
@@ -619,6 +620,55 @@ class ComponentRuns:
         if oriented and not np.array_equal(host[5][:, 0], q.labels):
             raise _lib.TomoError("component_caliper: the rows of the moments are not the rows of the selection")
         return _component_caliper_from(dirs, host[:5], q, host[5:] if oriented else None, oriented=bool(oriented))
+
+    def geodesic(self, slice_depths, mm_y, mm_x, sweeps=3, min_voxels=0, largest=False, *, max_voxels=None,
+                 enclosed=False) -> "ComponentGeodesic":
+        """component_geodesic of this volume.  The rule: select's.  The repeated farthest-point search for all selected
+        components at once (propagation stays inside a component): a0 = the first voxel of the component in raster order -- the
+        value kernels on an all-zero map -- then `sweeps` times: propagate from a(s - 1) inside the selected components (the
+        others keep +inf, their tiles are never dirty), and tomo_cc_value_max / tomo_cc_value_first on the map give a_s, the
+        farthest voxel, the lowest flat index among equals.  The steps use the connectivity of this object.  The map of the last
+        search stays in last_geodesic_map.  On background() with enclosed=True the rows are the cavities."""
+        rule = _keep_rule(min_voxels, largest, max_voxels, enclosed)
+        sweeps = _geodesic_search_sweeps(sweeps)
+        tables = _geodesic_tables(self.vol.shape, slice_depths, mm_y, mm_x)
+        COUNTERS["component_geodesic"] += 1
+        self.last_geodesic_map = None
+        picked = self.select(rule[0], rule[1], max_voxels=rule[2], enclosed=rule[3])
+        if picked is None:
+            return _component_geodesic_from(tables, np.zeros((0, 4), dtype=np.int64), np.zeros((0, 4), dtype=np.int64))
+        L, dev, st = _lib.lib(), self.vol.device, _stream()
+        plan = _GeodesicPlan(BitVolume(self.bits, self.vol.shape), tables, self.connectivity)
+        n = picked.table.shape[0]
+        dist = torch.zeros(self.vol.shape, dtype=torch.float32, device=dev)
+        best = torch.empty(n, dtype=torch.int32, device=dev)
+        first = torch.empty(n, dtype=torch.int64, device=dev)
+        head = (_p(self.bits), *self.vol.shape, *self._tables(), _p(self.tot), _p(dist), None)
+
+        def farthest():
+            COUNTERS["components_value"] += 1
+            _lib.check(L.tomo_cc_value_max(*head, _p(best), n, st), "tomo_cc_value_max")
+            _lib.check(L.tomo_cc_value_first(*head, _p(best), _p(first), n, st), "tomo_cc_value_first")
+
+        farthest()                                                      # on the all-zero map: the first voxel of every component
+        prev = None
+        for _ in range(sweeps):
+            prev = first.clone()
+            dist.fill_(float("inf"))
+            _lib.check(L.tomo_geo_seed_index(_p(self.bits), *self.vol.shape, _p(prev), _p(picked.sel), n, _p(dist), *plan.seed_tail(), st),
+                       "tomo_geo_seed_index")
+            plan.propagate(dist)
+            farthest()
+        rows = torch.empty((picked.m, 4), dtype=torch.int64, device=dev)
+        rows_prev = torch.empty((picked.m, 4), dtype=torch.int64, device=dev)
+        for b, f, out in ((best, first, rows), (best, prev, rows_prev)):
+            _lib.check(L.tomo_cc_value_rows(_p(picked.table), _p(b), _p(f), n, _p(self.tot), _p(picked.sel), _p(picked.slot), _p(out),
+                                            picked.m, st), "tomo_cc_value_rows")
+        host, host_prev, flags = self._download_checked("component_geodesic", rows, rows_prev, plan.counters[1:2])
+        if flags[0]:
+            raise _lib.TomoError("component_geodesic: a seed does not lie on its component (flags %d)" % flags[0])
+        self.last_geodesic_map = dist
+        return _component_geodesic_from(tables, host, host_prev)
 
     def topology(self) -> torch.Tensor:
         """Per component 1..n: Euler number, cavities (enclosed voids, b2) and handles (tunnels, b1 = 1 - euler + cavities) of
@@ -1600,6 +1650,257 @@ def cavity_caliper(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per
     _caliper_args(vol.shape, slice_depths, mm_per_pixel_y, mm_per_pixel_x, directions, extent)
     bg = _complement_runs(vol, connectivity)
     return bg.caliper(slice_depths, mm_per_pixel_y, mm_per_pixel_x, directions, extent, oriented, lo, max_voxels=hi, enclosed=True)
+
+
+# ----------------------------------------------------------------------------- geodesic distance
+GEODESIC_SWEEP_BATCH = 8             # sweeps enqueued between two reads of the change counter (a sweep of a clean volume returns at once)
+GEODESIC_SWEEP_LIMIT = 1 << 16       # a guard against an endless host loop, no tuning knob; read when called
+GEODESIC_VOLUME_BUDGET = 1 << 33     # bytes of the float32 map; read when called
+
+
+def geodesic_weights(slice_depths, nz, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0):
+    """The step weights of the geodesic metric, on the host -> (wxy float32 (3,): the steps x, y, xy; wz float32
+    (max(nz - 1, 1), 4): the steps z, zx, zy, zyx across the boundary between slice k and k + 1).  A weight is the Euclidean
+    length of the step in mm, float64 sqrt(((dx mm_x)^2 + (dy mm_y)^2) + dzc^2) with dzc = zc[k + 1] - zc[k] of
+    distance_positions, rounded once to float32."""
+    zt, _, _ = distance_positions(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x)
+    mm_y, mm_x = float(mm_per_pixel_y), float(mm_per_pixel_x)
+    dzc = np.diff(zt[1:-1])
+    steps = np.array([(1.0, 0.0), (0.0, 1.0), (1.0, 1.0)])               # (dx, dy) of x, y, xy
+    plane = (steps[:, 0] * mm_x) * (steps[:, 0] * mm_x) + (steps[:, 1] * mm_y) * (steps[:, 1] * mm_y)
+    wxy = np.sqrt(plane + 0.0 * 0.0).astype(np.float32)
+    wz = np.zeros((max(int(nz) - 1, 1), 4), dtype=np.float32)
+    if len(dzc):
+        inplane = np.concatenate([[0.0], plane[[0, 1, 2]]])             # z, zx, zy, zyx
+        wz[:] = np.sqrt(inplane[None, :] + (dzc * dzc)[:, None]).astype(np.float32)
+    return wxy, wz
+
+
+@dataclass
+class _GeodesicTables:
+    """The host side of one geodesic call: the weights and where a voxel sits."""
+    wxy: np.ndarray
+    wz: np.ndarray
+    zc: np.ndarray
+    mm_y: float
+    mm_x: float
+    shape: tuple
+
+
+def _geodesic_tables(shape, slice_depths, mm_per_pixel_y, mm_per_pixel_x) -> _GeodesicTables:
+    """The argument checks every geodesic call shares, all on the host."""
+    nz = shape[0]
+    wxy, wz = geodesic_weights(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x)
+    zt, _, _ = distance_positions(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x)
+    if not ((wxy > 0).all() and np.isfinite(wxy).all() and (nz < 2 or ((wz > 0).all() and np.isfinite(wz).all()))):
+        raise ValueError("the spacing does not give positive finite float32 step lengths")
+    return _GeodesicTables(wxy, wz, zt[1:-1].copy(), float(mm_per_pixel_y), float(mm_per_pixel_x), tuple(int(a) for a in shape))
+
+
+def _geodesic_search_sweeps(sweeps) -> int:
+    if isinstance(sweeps, (bool, np.bool_)) or not isinstance(sweeps, (int, np.integer)) or sweeps < 2:
+        raise ValueError("sweeps must be a whole number of at least 2")
+    return int(sweeps)
+
+
+class _GeodesicPlan:
+    """What the sweeps of one geodesic call share: the bits, the weights on the device, the two dirty arrays and the counters."""
+
+    def __init__(self, vol: BitVolume, tables: _GeodesicTables, connectivity):
+        nz, ny, nx = vol.shape
+        nbytes = 4 * nz * ny * nx
+        if nbytes > GEODESIC_VOLUME_BUDGET:                              # read when called, before anything is allocated
+            raise _lib.TomoError("geodesic distance: the float32 map of %d x %d x %d voxels takes %d bytes, more than "
+                                 "GEODESIC_VOLUME_BUDGET (%d)" % (nz, ny, nx, nbytes, GEODESIC_VOLUME_BUDGET))
+        L = _lib.lib()
+        self.tiles = int(L.tomo_geo_tiles(nz, ny, nx))
+        if self.tiles <= 0:
+            raise _lib.TomoError("tomo_geo_tiles failed (%d)" % self.tiles)
+        dev = vol.device
+        self.vol, self.bits, self.connectivity = vol, vol.bits.contiguous(), int(connectivity)
+        w = torch.from_numpy(np.concatenate([tables.wxy, tables.wz.reshape(-1)])).to(dev)
+        self.w, self.wxy, self.wz = w, w[:3], w[3:]
+        self.dirty = torch.zeros((2, self.tiles), dtype=torch.int32, device=dev)
+        self.counters = torch.zeros(2, dtype=torch.int64, device=dev)
+        self.cur = 0                                                     # the dirty array the next sweep reads
+        self.changed = 0                                                 # counters[0] as last read
+
+    def seed_tail(self):
+        """What the two seeding entry points take behind dist (tomo_geo_seed_bits: without the counters)."""
+        return _p(self.dirty[self.cur]), _p(self.counters)
+
+    def propagate(self, dist: torch.Tensor) -> int:
+        """Sweeps until a batch changes nothing -> the sweeps launched.  No seed: none.  Termination is guaranteed -- values only
+        fall and come from a finite set; GEODESIC_SWEEP_LIMIT only guards the host loop."""
+        L, st = _lib.lib(), _stream()
+        nz, ny, nx = self.vol.shape
+        limit, batch = int(GEODESIC_SWEEP_LIMIT), max(1, int(GEODESIC_SWEEP_BATCH))
+        if not bool(self.dirty[self.cur].any().item()):
+            return 0
+        done = 0
+        while True:
+            if done >= limit:
+                raise _lib.TomoError("geodesic distance: no fixed point after %d sweeps (GEODESIC_SWEEP_LIMIT)" % done)
+            k = min(batch, limit - done)
+            for _ in range(k):
+                _lib.check(L.tomo_geo_sweep(_p(self.bits), nz, ny, nx, self.connectivity, _p(self.wxy), _p(self.wz), _p(dist),
+                                            _p(self.dirty[self.cur]), _p(self.dirty[1 - self.cur]), _p(self.counters), st),
+                           "tomo_geo_sweep")
+                self.cur = 1 - self.cur
+            done += k
+            COUNTERS["geodesic_sweeps"] += k
+            changed = _download(self.counters)[0]
+            if changed == self.changed:
+                return done
+            self.changed = changed
+
+
+def _geodesic_seeds(shape, seeds):
+    """seeds -> ("bits", BitVolume) or ("index", int64 host array of flat indices); ValueError for anything else."""
+    nz, ny, nx = shape
+    if isinstance(seeds, BitVolume):
+        if tuple(seeds.shape) != tuple(shape):
+            raise ValueError("seeds must have the shape of the volume")
+        return "bits", seeds
+    a = seeds.detach().cpu().numpy() if isinstance(seeds, torch.Tensor) else np.asarray(seeds)
+    if a.size == 0:
+        return "index", np.zeros(0, dtype=np.int64)
+    if a.ndim != 2 or a.shape[1] != 3 or a.dtype.kind not in "iu":
+        raise ValueError("seeds must be a BitVolume or an integer array (n, 3) of (z, y, x)")
+    a = a.astype(np.int64)
+    if (a < 0).any() or (a >= np.array([nz, ny, nx])).any():
+        raise ValueError("a seed lies outside the volume")
+    return "index", (a[:, 0] * ny + a[:, 1]) * nx + a[:, 2]
+
+
+def _geodesic_map(vol: BitVolume, seeds, tables: _GeodesicTables, connectivity):
+    """-> (float32 map, the plan that made it)."""
+    kind, s = seeds
+    L, dev, st = _lib.lib(), vol.device, _stream()
+    nz, ny, nx = vol.shape
+    plan = _GeodesicPlan(vol, tables, connectivity)
+    COUNTERS["geodesic_calls"] += 1
+    if kind == "bits":
+        dist = torch.empty(vol.shape, dtype=torch.float32, device=dev)
+        _lib.check(L.tomo_geo_seed_bits(_p(plan.bits), _p(s.bits.contiguous()), nz, ny, nx, _p(dist), plan.seed_tail()[0], st),
+                   "tomo_geo_seed_bits")
+    else:
+        dist = torch.full(vol.shape, float("inf"), dtype=torch.float32, device=dev)
+        if len(s):
+            index = torch.from_numpy(s).to(dev)
+            _lib.check(L.tomo_geo_seed_index(_p(plan.bits), nz, ny, nx, _p(index), None, len(s), _p(dist), *plan.seed_tail(), st),
+                       "tomo_geo_seed_index")                            # a seed on an unset voxel is ignored: the flag is not read
+    plan.propagate(dist)
+    return dist, plan
+
+
+def geodesic_distance(vol: BitVolume, seeds, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, connectivity=26) -> torch.Tensor:
+    """Geodesic distance from the seeds through the set voxels of a resident volume, in millimetres -> float32 (nz, ny, nx)
+    device tensor: 0.0 at a seed that is set, +inf at a set voxel no seed reaches and at every unset voxel.  seeds: a BitVolume
+    of the same shape, or an integer array (n, 3) of (z, y, x); a seed on an unset voxel is ignored.
+    The metric: voxel (k, j, i) sits at (zc[k], j mm_y, i mm_x), the coordinates of distance_transform; a step goes between
+    two set voxels that are neighbours under the connectivity (6 or 26; the 26-adjacency of the two ends alone, no
+    corner-cutting test: label_components' adjacency, so a path never leaves a component) and weighs its Euclidean length in
+    mm (geodesic_weights); the distance is the minimum over the paths of the left-to-right float32 sum of the weights.  That
+    is the path length on the 6 / 26 lattice: exact along the lattice directions and an overestimate between them, like any
+    chamfer metric, and a float32 sum carries float32's relative precision along a very long path.
+    The device relaxes 8 x 8 x 64 tiles in LDS, sweep after sweep, until a batch of GEODESIC_SWEEP_BATCH sweeps changes
+    nothing; d' = fl32(d + w) is monotone in d, so every order of relaxations ends at the same bytes -- those Dijkstra's
+    algorithm with the same float32 additions returns.  More than GEODESIC_SWEEP_LIMIT sweeps: TomoError; a map of more than
+    GEODESIC_VOLUME_BUDGET bytes: TomoError before anything is allocated.  An empty volume, or no seed on a set voxel: no
+    sweep is launched.  Arguments are checked before the first launch."""
+    connectivity = _check_connectivity(connectivity)
+    tables = _geodesic_tables(vol.shape, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    return _geodesic_map(vol, _geodesic_seeds(vol.shape, seeds), tables, connectivity)[0]
+
+
+def geodesic_reach(vol: BitVolume, seeds, max_mm=None, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0,
+                   connectivity=26) -> BitVolume:
+    """The set voxels within max_mm millimetres of a seed along geodesic_distance's paths (dist <= max_mm) -> a NEW BitVolume:
+    the geodesic ball.  max_mm=None: every voxel a seed reaches -- the binary reconstruction of the seeds in the volume, the
+    components a seed touches."""
+    connectivity = _check_connectivity(connectivity)
+    r = float("inf") if max_mm is None else float(max_mm)
+    if not r >= 0:
+        raise ValueError("max_mm must be non-negative or None")
+    tables = _geodesic_tables(vol.shape, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    dist, plan = _geodesic_map(vol, _geodesic_seeds(vol.shape, seeds), tables, connectivity)
+    out = torch.empty_like(plan.bits)
+    _lib.check(_lib.lib().tomo_geo_reach(_p(plan.bits), _p(dist), *vol.shape, r, _p(out), _stream()), "tomo_geo_reach")
+    return BitVolume(out, vol.shape)
+
+
+@dataclass
+class ComponentGeodesic:
+    """component_geodesic's answer: host arrays, one row per selected component in ascending label; vectors in (z, y, x) order."""
+    labels: np.ndarray           # int64 (m,)
+    voxels: np.ndarray           # int64 (m,)
+    length_mm: np.ndarray        # float64 (m,): the distance of the last search (a float32 value), centre to centre
+    ends_index: np.ndarray       # int64 (m, 2, 3): the two ends of that search, (z, y, x)
+    ends_mm: np.ndarray          # float64 (m, 2, 3): where they sit
+    chord_mm: np.ndarray         # float64 (m,): the straight distance between the two end centres
+    tortuosity: np.ndarray       # float64 (m,): length_mm / chord_mm, 1.0 where the chord is 0
+
+    def __len__(self):
+        return len(self.labels)
+
+
+def _component_geodesic_from(tables: _GeodesicTables, rows, rows_prev) -> ComponentGeodesic:
+    """Host side of the downloaded rows (label, voxels, float32 bits of the distance, flat index) of the last search and of its
+    start."""
+    rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1, 4)
+    rows_prev = np.ascontiguousarray(rows_prev, dtype=np.int64).reshape(-1, 4)
+    m = len(rows)
+    length = rows[:, 2].astype(np.uint32).view(np.float32).astype(np.float64)
+    ends = np.zeros((m, 2, 3), dtype=np.int64)
+    mm = np.zeros((m, 2, 3), dtype=np.float64)
+    if m:
+        nz, ny, nx = tables.shape
+        for e, flat in enumerate((rows_prev[:, 3], rows[:, 3])):
+            ends[:, e, 0], rest = np.divmod(flat, ny * nx)
+            ends[:, e, 1], ends[:, e, 2] = np.divmod(rest, nx)
+        mm[:, :, 0] = tables.zc[ends[:, :, 0]]
+        mm[:, :, 1] = ends[:, :, 1] * tables.mm_y
+        mm[:, :, 2] = ends[:, :, 2] * tables.mm_x
+    d = mm[:, 1, :] - mm[:, 0, :]
+    chord = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+    tort = np.ones(m, dtype=np.float64)
+    np.divide(length, chord, out=tort, where=chord > 0)
+    return ComponentGeodesic(rows[:, 0].copy(), rows[:, 1].copy(), length, ends, mm, chord, tort)
+
+
+def component_geodesic(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, connectivity=6, sweeps=3,
+                       min_voxels=0, largest=False) -> ComponentGeodesic:
+    """Geodesic length per component of a resident volume -> ComponentGeodesic, one row per component the keep rule of
+    component_properties selects, in ascending label: the rows component_properties returns for the same rule.
+    The method is the repeated farthest-point search (as in MorphoLibJ's geodesic diameter), for all selected components at
+    once: a0 = the first voxel of the component in raster order; `sweeps` times (at least 2: ValueError) the geodesic distance
+    is propagated from a(s - 1) and a_s is the farthest voxel of the component, the lowest flat index among equals.
+    length_mm is the distance of the last search, ends_index / ends_mm its two ends (a(sweeps - 1), a_sweeps), chord_mm the
+    straight distance between the end centres and tortuosity their ratio (1.0 where the chord is 0).  The metric is
+    geodesic_distance's with the steps of `connectivity`; length_mm is a LOWER bound of the geodesic diameter on that metric,
+    and it is centre to centre: one voxel reads 0.0.  A coiled fibre or a bent crack reads its length here, where the caliper
+    diameter reads the width of the coil.  An empty volume, or nothing selected, gives zero rows.  Arguments are checked
+    before the first launch."""
+    _check_connectivity(connectivity)
+    _keep_rule(min_voxels, largest)
+    _geodesic_search_sweeps(sweeps)
+    _geodesic_tables(vol.shape, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    return ComponentRuns(vol, connectivity).geodesic(slice_depths, mm_per_pixel_y, mm_per_pixel_x, sweeps, min_voxels, largest)
+
+
+def cavity_geodesic(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, connectivity=6, sweeps=3,
+                    min_voxels=0, max_voxels=None) -> ComponentGeodesic:
+    """component_geodesic of the enclosed voids of a resident volume, one row per cavity of cavity_table under the same size
+    window, in ascending cavity label: how long a pore is along itself.  One labelling of the complement under the
+    complementary connectivity, whose steps the paths take; an empty or a full volume has no rows.  Arguments are checked
+    before the first launch."""
+    connectivity = _check_connectivity(connectivity)
+    lo, hi = _check_size_window(min_voxels, max_voxels)
+    _geodesic_search_sweeps(sweeps)
+    _geodesic_tables(vol.shape, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    bg = _complement_runs(vol, connectivity)
+    return bg.geodesic(slice_depths, mm_per_pixel_y, mm_per_pixel_x, sweeps, lo, max_voxels=hi, enclosed=True)
 
 
 def local_thickness(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, radii_mm=None,

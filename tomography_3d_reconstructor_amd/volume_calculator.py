@@ -146,7 +146,7 @@ def surface_area(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, direc
 
 
 def closed_porosity(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=6, min_voxels=0, max_voxels=None,
-                    pore_size=False, pore_caliper=False):
+                    pore_size=False, pore_geodesic=False, pore_caliper=False):
     """The enclosed voids of the volume, listed and added up (no counterpart in the reference): pipeline.cavity_table -- a
     cavity is a component of the complement, under the complementary connectivity, that reaches no face of the stack; per-slice
     depths honoured -> {'cavities', 'cavity_voxels', 'cavity_volume_mm3', 'voxel_volume_mm3', 'closed_porosity', 'table'}.
@@ -162,7 +162,10 @@ def closed_porosity(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, co
     pore_caliper=True: every row also carries 'max_caliper_mm' and 'min_caliper_mm' -- the largest and the smallest caliper
     (Feret) diameter of the pore over pipeline.caliper_directions(), voxel extents included (pipeline.ComponentRuns.caliper on the
     complement's tables): the length and the opening of a crack -- and the report 'longest_pore_mm', the largest 'max_caliper_mm'
-    of the rows (0.0 without pores).
+    of the rows (0.0 without pores).  pore_geodesic=True (a keyword, like the other flags): every row also carries
+    'geodesic_length_mm' -- the length of the pore along itself, the repeated farthest-point search of pipeline.cavity_geodesic on
+    the complement's tables, centre to centre: a lower bound of its geodesic diameter on the lattice metric -- and 'tortuosity',
+    that length over the straight distance of its two ends, and the report 'longest_pore_path_mm' (0.0 without pores).
     voxel_data: the bool (nz, ny, nx) array the other calculations take; anything else is a TypeError -- there is no host path
     for this one."""
     if not _on_device(voxel_data):
@@ -171,8 +174,10 @@ def closed_porosity(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, co
     pipeline._check_connectivity(connectivity)                  # the argument checks, before anything is uploaded
     pipeline._check_size_window(min_voxels, max_voxels)
     pipeline._slice_weights(depths, len(voxel_data), mm_per_pixel_y, mm_per_pixel_x)
+    if pore_geodesic:
+        pipeline._geodesic_tables(voxel_data.shape, depths, mm_per_pixel_y, mm_per_pixel_x)
     vol = to_device_volume(voxel_data)
-    if pore_caliper:                                             # the steps of cavity_table / cavity_sizes on ONE object
+    if pore_caliper or pore_geodesic:                            # the steps of cavity_table / cavity_sizes on ONE object
         lo, hi = pipeline._check_size_window(min_voxels, max_voxels)
         runs = pipeline.ComponentRuns(vol, connectivity)
         bg = runs.background()
@@ -180,7 +185,10 @@ def closed_porosity(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, co
         t = pipeline._cavities_from(runs, bg.properties(tables, mm_per_pixel_y, mm_per_pixel_x, lo, max_voxels=hi, enclosed=True))
         if pore_size:
             size = bg.thickness(depths, mm_per_pixel_y, mm_per_pixel_x, None, lo, max_voxels=hi, enclosed=True)
-        feret = bg.caliper(depths, mm_per_pixel_y, mm_per_pixel_x, min_voxels=lo, max_voxels=hi, enclosed=True)
+        if pore_caliper:
+            feret = bg.caliper(depths, mm_per_pixel_y, mm_per_pixel_x, min_voxels=lo, max_voxels=hi, enclosed=True)
+        if pore_geodesic:
+            path = bg.geodesic(depths, mm_per_pixel_y, mm_per_pixel_x, min_voxels=lo, max_voxels=hi, enclosed=True)
     elif pore_size:
         t, size = pipeline.cavity_sizes(vol, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_voxels, max_voxels)
     else:
@@ -209,12 +217,18 @@ def closed_porosity(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, co
         for i, row in enumerate(table):
             row['max_caliper_mm'], row['min_caliper_mm'] = float(feret.max_mm[i]), float(feret.min_mm[i])
         report['longest_pore_mm'] = max((row['max_caliper_mm'] for row in table), default=0.0)
+    if pore_geodesic:
+        assert np.array_equal(path.labels, t.labels)
+        for i, row in enumerate(table):
+            row['geodesic_length_mm'], row['tortuosity'] = float(path.length_mm[i]), float(path.tortuosity[i])
+        report['longest_pore_path_mm'] = max((row['geodesic_length_mm'] for row in table), default=0.0)
     return report
 
 
 def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=6, min_voxels=0, largest=False,
                          shape=False, topology=False, surface=False, surface_directions=13, porosity=False, thickness=False,
-                         thickness_radii_mm=None, caliper=False, caliper_directions=None, caliper_oriented=False):
+                         thickness_radii_mm=None, geodesic=False, geodesic_sweeps=3, caliper=False, caliper_directions=None,
+                         caliper_oriented=False):
     """The calculations of the class per connected component (no counterpart in the reference, which would be handed the mask
     `labels == c` once per component) -> a list of dicts, one per component with at least min_voxels voxels (largest: only the
     largest of those), in label order: {'label', 'voxels', 'voxel_volume_mm3', 'bounding_box': {'x', 'y', 'z'}, 'dimensions',
@@ -241,6 +255,10 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
     (float (M, 3) unit vectors; None: pipeline.caliper_directions()), voxel extents included (pipeline.component_caliper):
     'max_caliper_mm', 'max_caliper_direction' (z, y, x), 'min_caliper_mm', 'min_caliper_direction', and with caliper_oriented
     also 'oriented_box_mm' -- the extents along the component's principal axes -- and 'oriented_box_center_mm' (z, y, x).
+    geodesic=True (a keyword, like the other flags): every dict also carries 'geodesic_length_mm' -- the length of the component
+    along itself, the repeated farthest-point search of pipeline.component_geodesic with geodesic_sweeps searches (at least 2) and
+    the steps of `connectivity`, centre to centre: a lower bound of its geodesic diameter on the lattice metric --
+    'geodesic_ends_index' (the two ends, (z, y, x) each) and 'tortuosity', that length over the straight distance of the ends.
     Whatever the
     flags, the volume is uploaded and labelled ONCE, and so is its complement: one pipeline.ComponentRuns serves all the
     measurements and owns the one selection their rows come from.  Arguments are checked before the first launch.  voxel_data: a bool (nz, ny, nx) array, else a TypeError."""
@@ -255,6 +273,9 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
         pipeline._component_thickness_args(voxel_data.shape, depths, mm_per_pixel_y, mm_per_pixel_x, thickness_radii_mm)
     if caliper:
         pipeline._caliper_args(voxel_data.shape, depths, mm_per_pixel_y, mm_per_pixel_x, caliper_directions, "voxels")
+    if geodesic:
+        pipeline._geodesic_search_sweeps(geodesic_sweeps)
+        pipeline._geodesic_tables(voxel_data.shape, depths, mm_per_pixel_y, mm_per_pixel_x)
     runs = pipeline.ComponentRuns(to_device_volume(voxel_data), connectivity)
     if runs.select(*rule) is None:
         return []
@@ -269,6 +290,7 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
     a = runs.surface(factors, surface_directions, *rule) if surface else None
     h = runs.thickness(depths, mm_per_pixel_y, mm_per_pixel_x, thickness_radii_mm, *rule) if thickness else None
     f = runs.caliper(depths, mm_per_pixel_y, mm_per_pixel_x, caliper_directions, "voxels", caliper_oriented, *rule) if caliper else None
+    g = runs.geodesic(depths, mm_per_pixel_y, mm_per_pixel_x, geodesic_sweeps, *rule) if geodesic else None
     pores = {}
     if porosity:                                                 # every cavity of the volume, credited to its owner
         c = pipeline._cavities_from(runs, runs.background().properties(tables, mm_per_pixel_y, mm_per_pixel_x, enclosed=True))
@@ -309,6 +331,10 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
             if caliper_oriented:
                 d['oriented_box_mm'] = tuple(float(v) for v in f.oriented_extent_mm[i])
                 d['oriented_box_center_mm'] = tuple(float(v) for v in f.oriented_center_mm[i])
+        if geodesic:
+            d['geodesic_length_mm'] = float(g.length_mm[i])
+            d['geodesic_ends_index'] = tuple(tuple(int(v) for v in end) for end in g.ends_index[i])
+            d['tortuosity'] = float(g.tortuosity[i])
     return out
 
 
