@@ -471,6 +471,48 @@ int tomo_geo_seed_index(const uint64_t *bits, int nz, int ny, int nx, const uint
 int tomo_geo_sweep(const uint64_t *bits, int nz, int ny, int nx, int connectivity, const float *wxy, const float *wz, float *dist,
                    uint32_t *dirty_cur, uint32_t *dirty_next, unsigned long long *counters, void *stream);
 int tomo_geo_reach(const uint64_t *bits, const float *dist, int nz, int ny, int nx, double max_mm, uint64_t *out, void *stream);
+/* Geodesic zones of markers and the cut between them (csrc/geodesic.hip; no counterpart in the reference): which marker reaches
+ * a voxel first through the object, and the voxels to clear so that touching objects come apart.  Coordinates, connectivity,
+ * weights, tiles, dirty arrays and dist are those of the block above; its kernels are not touched.
+ * Markers: int32 (nz, ny, nx).  A positive entry on a set voxel is a marker voxel with that label; entries <= 0 and entries on
+ * unset voxels are ignored; labels need not be consecutive.
+ * Zones, one definition.  dist = the geodesic distance from the marker voxels.  An edge q -> p between neighbouring set voxels is
+ * TIGHT when fl32(dist(q) + w(q, p)) == dist(p) with dist(p) finite -- the float32 addition the distance sweep makes.  zone(p) =
+ * the smallest marker label among the markers from which p can be reached along tight edges; 0 at unset voxels and at set voxels
+ * no marker reaches.  A marker voxel keeps its label: no edge into a voxel at distance 0 is tight, the weights are positive.
+ * This is the least fixed point of zone(p) = min(zone(p), zone(q) over tight q -> p) over a FIXED graph: unique, so every order,
+ * tiling and race ends at the same bytes, also where dist stalled along a very long path (fl32(d + w) == d).  Distance and label
+ * are NOT relaxed as a pair: fl32(d + w) maps different d to one sum, so the pair operator is not monotone and its result would
+ * depend on the schedule.  Two phases: tomo_geo_sweep to its fixed point, then tomo_zone_sweep over the final dist.
+ * The map holds 0 for "no zone" at every moment; the kernels order labels by (uint32)(zone - 1), under which 0 is the largest.
+ *   tomo_zone_seed_labels  one pass over the volume: dist = 0.0 and zone = the label where the voxel is set and its marker entry is
+ *                          positive, dist = +inf and zone = 0 elsewhere; dirty is marked as tomo_geo_seed_bits marks it
+ *   tomo_zone_sweep        one label sweep, shaped like tomo_geo_sweep: one workgroup of 256 per tile, gone at once when its flag in
+ *                          dirty_cur is clear.  It loads the tile and a one-voxel halo of dist (read only here) and of zone into
+ *                          LDS, finds the tight edges into its interior voxels once, and lowers the interior labels against the
+ *                          fixed halo in race-free rounds bounded by the number of interior voxels (a tile that hits the bound
+ *                          marks itself in dirty_next).  It stores the labels that changed, adds 1 to counters[0] (once per
+ *                          workgroup that changed something) and sets dirty_next of the neighbouring tiles next to a changed
+ *                          face, edge or corner voxel (6: face neighbours only).  No atomics on the maps, nothing waits on
+ *                          another workgroup.  To start the phase the caller sets EVERY flag of dirty_cur once (one fill; the
+ *                          distance phase left both arrays clear): a tile without work changes nothing and marks nobody, so it
+ *                          is out after the first sweep.  The caller swaps the arrays between sweeps and stops at a batch that
+ *                          left counters[0] unchanged, as for tomo_geo_sweep.
+ *   tomo_zone_cut          out = bits without the set voxels p that have a SET neighbour q under the connectivity with
+ *                          0 < zone(q) < zone(p): the lower label keeps the contact, and afterwards no two voxels of different
+ *                          zones are adjacent; a component without a marker is untouched.  A wave takes a word at a time, a lane
+ *                          one bit, tail bits zero; it walks 32 consecutive words and then adds their cleared voxels to *counter
+ *                          (zeroed by the caller) with one integer atomic per wave.  Any int32 map is
+ *                          taken: entries <= 0 are no zone, entries on unset voxels are not read as neighbours.
+ * TOMO_E_ARG for a null pointer, a non-positive size, a connectivity other than 6 / 26, dirty_cur == dirty_next, markers == zone,
+ * dist == zone, out == bits or out == zone; TOMO_E_SIZE from 2^31 tiles or words on. */
+int tomo_zone_seed_labels(const uint64_t *bits, const int32_t *markers, int nz, int ny, int nx, float *dist, int32_t *zone,
+                          uint32_t *dirty, void *stream);
+int tomo_zone_sweep(const uint64_t *bits, int nz, int ny, int nx, int connectivity, const float *wxy, const float *wz,
+                    const float *dist, int32_t *zone, uint32_t *dirty_cur, uint32_t *dirty_next, unsigned long long *counters,
+                    void *stream);
+int tomo_zone_cut(const uint64_t *bits, const int32_t *zone, int nz, int ny, int nx, int connectivity, uint64_t *out,
+                  unsigned long long *counter, void *stream);
 /* The same across Z-slabs (slab_components.py): rank r labels its slab with the functions above (n_r components); local
  * component c has the global id base_r + c, base_r = n_0 + .. + n_(r-1).  Pieces that touch across a cut are united, the roots
  * (smallest id = the piece with the component's first voxel) numbered in ascending id: scipy's numbering of the whole stack.

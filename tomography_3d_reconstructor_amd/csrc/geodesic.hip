@@ -21,6 +21,9 @@
 // tear), both are upper bounds of the fixed point, and the writer marks every neighbouring tile next to a changed face, edge or
 // corner voxel in dirty_next, so the reader runs again in the next sweep, after the kernel boundary has published the store.
 // Nothing waits on another workgroup: no grid barrier, no persistent grid, no spin.  The host stops when a sweep changed nothing.
+//
+// Zones of markers (tomo_zone_seed_labels, tomo_zone_sweep, tomo_zone_cut) sit further down: a second phase over the FINAL map that
+// says which marker reached a voxel, on the same tiles and flags, and the cut between zones.  The kernels above are not touched.
 #include "tomo_common.h"
 #include <math.h>
 
@@ -337,6 +340,286 @@ __global__ __launch_bounds__(GEO_THREADS) void geo_reach_kernel(const u64 *__res
     if (b == 0) out[word] = m;
 }
 
+// ---------------------------------------------------------------------------------------------- zones of markers
+// Which marker reached a voxel (contract: include/tomo_hip.h).  Two phases: the distance sweeps above run to their fixed point
+// first, untouched; then labels fall along the TIGHT edges of the final map -- q -> p with fl32(dist(q) + w) == dist(p), the add
+// geo_relax makes -- until zone(p) = the smallest label that reaches p.  The graph is fixed in this phase, so the least fixed
+// point is unique and the argument of the distance sweep carries over word for word: labels only fall, a stale read is an upper
+// bound, the writer marks the reader.
+// The map holds 0 for "no zone" throughout; the kernels order labels by the key (u32)(zone - 1), which makes 0 the largest.
+#define ZONE_NONE 0xffffffffu
+
+__device__ static inline u32 zone_key(int zone) { return (u32)zone - 1u; }
+
+// a wave is one word of a row, a lane one voxel: a positive marker entry on a set voxel seeds dist = 0.0 and zone = the label
+__global__ __launch_bounds__(GEO_THREADS) void zone_seed_kernel(const u64 *__restrict__ bits, const int *__restrict__ markers,
+                                                                int64_t nwords, int nz, int ny, int nx, int wx, int ty,
+                                                                float *__restrict__ dist, int *__restrict__ zone, u32 *__restrict__ dirty)
+{
+    const int64_t t = (int64_t)blockIdx.x * GEO_THREADS + threadIdx.x;
+    const int64_t word = t >> 6;                             // the same for the 64 lanes of a wave
+    if (word >= nwords) return;
+    const int64_t row = word / wx;
+    const int w = (int)(word - row * wx);
+    const int b = (int)(t & 63);
+    const int x = 64 * w + b;
+    int label = 0;
+    if ((geo_word(bits + row * wx, nx, wx, w) >> b) & 1) {   // below nx: the tail bits are masked
+        const int v = markers[row * nx + x];
+        if (v > 0) label = v;
+    }
+    const u64 m = __ballot(label > 0);
+    if (x < nx) {
+        dist[row * nx + x] = label > 0 ? 0.0f : INFINITY;
+        zone[row * nx + x] = label;
+    }
+    if (label > 0) {
+        const int z = (int)(row / ny), y = (int)(row - (int64_t)z * ny);
+        if (b == 0 || b == 63 || b == __ffsll((long long)m) - 1)
+            geo_mark_seed(dirty, z, y, x, nz, ty, wx);
+    }
+}
+
+// the neighbours of a voxel of the halo box in ONE order: f(j, offset into the box, weight of the step), j = 0 .. CONN - 1
+template <int CONN, typename F>
+__device__ static inline void zone_neighbours(const float wx_, const float wy_, const float wxy_, const float *__restrict__ wlo,
+                                              const float *__restrict__ whi, F f)
+{
+    const int sy = GEO_HX, sz = GEO_HY * GEO_HX;
+    f(0, -1, wx_);
+    f(1, 1, wx_);
+    f(2, -sy, wy_);
+    f(3, sy, wy_);
+    f(4, -sz, wlo[0]);
+    f(5, sz, whi[0]);
+    if (CONN == 26) {
+        f(6, -sy - 1, wxy_);
+        f(7, -sy + 1, wxy_);
+        f(8, sy - 1, wxy_);
+        f(9, sy + 1, wxy_);
+#pragma unroll
+        for (int s = 0; s < 2; s++) {
+            const int o = s ? sz : -sz, j = 10 + 8 * s;
+            const float *w = s ? whi : wlo;
+            f(j + 0, o - 1, w[1]);
+            f(j + 1, o + 1, w[1]);
+            f(j + 2, o - sy, w[2]);
+            f(j + 3, o + sy, w[2]);
+            f(j + 4, o - sy - 1, w[3]);
+            f(j + 5, o - sy + 1, w[3]);
+            f(j + 6, o + sy - 1, w[3]);
+            f(j + 7, o + sy + 1, w[3]);
+        }
+    }
+}
+
+// One label sweep, shaped like geo_sweep_kernel: the same tiles, flags, rounds and marks.  dist is read only: the tight edges into
+// a thread's 16 voxels are found ONCE per visit (a bit per neighbour, in registers), the rounds then only take minima of keys
+// over those bits.  Two boxes in LDS, 54 148 bytes with the masks: two workgroups per CU (160 KiB), which the launch bound asks
+// of the registers as well.
+template <int CONN>
+__global__ __launch_bounds__(GEO_THREADS, 2) void zone_sweep_kernel(const u64 *__restrict__ bits, int nz, int ny, int nx, int wx, int ty,
+                                                                 const float *__restrict__ wxy, const float *__restrict__ wz,
+                                                                 const float *__restrict__ dist, int *zone, u32 *dirty_cur,
+                                                                 u32 *dirty_next, unsigned long long *counters)
+{
+    __shared__ float box[GEO_BOX];                           // dist: +inf at unset voxels and outside the stack
+    __shared__ u32 zbox[GEO_BOX];                            // keys: ZONE_NONE there
+    __shared__ u64 smid[GEO_HROWS];
+    __shared__ u32 sside[GEO_HROWS];
+    __shared__ float swz[(GEO_TZ + 1) * 4];
+    __shared__ u32 snb;
+
+    const int tid = threadIdx.x;
+    const int64_t tile = blockIdx.x;
+    if (!__syncthreads_or((int)dirty_cur[tile])) return;     // uniform: every thread has read the flag before it is cleared
+    if (tid == 0) {
+        dirty_cur[tile] = 0u;
+        snb = 0u;
+    }
+    const int bx = (int)(tile % wx);
+    const int64_t rest = tile / wx;
+    const int by = (int)(rest % ty), bz = (int)(rest / ty);
+    const int z0 = bz * GEO_TZ - 1, y0 = by * GEO_TY - 1;    // the halo box starts here
+
+    if (tid < GEO_HROWS) {
+        const int z = z0 + tid / GEO_HY, y = y0 + tid % GEO_HY;
+        u64 mid = 0;
+        u32 side = 0;
+        if (z >= 0 && z < nz && y >= 0 && y < ny) {
+            const u64 *r = bits + ((int64_t)z * ny + y) * wx;
+            mid = geo_word(r, nx, wx, bx);
+            if (bx > 0 && (geo_word(r, nx, wx, bx - 1) >> 63)) side |= 1u;
+            if (bx + 1 < wx && (geo_word(r, nx, wx, bx + 1) & 1)) side |= 2u;
+        }
+        smid[tid] = mid;
+        sside[tid] = side;
+    } else if (tid >= 128 && tid < 128 + (GEO_TZ + 1) * 4) {
+        const int b = (tid - 128) >> 2, k = (tid - 128) & 3;
+        const int z = z0 + b;                                // the boundary between slices z and z + 1
+        swz[tid - 128] = (z >= 0 && z + 1 < nz) ? wz[4 * (int64_t)z + k] : INFINITY;
+    }
+    __syncthreads();
+
+    for (int i = tid; i < GEO_BOX; i += GEO_THREADS) {
+        const int hr = i / GEO_HX, xx = i - hr * GEO_HX;
+        bool set;
+        if (xx == 0) set = sside[hr] & 1u;
+        else if (xx == GEO_HX - 1) set = (sside[hr] >> 1) & 1u;
+        else set = (smid[hr] >> (xx - 1)) & 1;
+        float v = INFINITY;
+        u32 key = ZONE_NONE;
+        if (set) {                                           // a set voxel lies inside the stack and below nx
+            const int z = z0 + hr / GEO_HY, y = y0 + hr % GEO_HY;
+            const int64_t at = ((int64_t)z * ny + y) * nx + (64 * bx + xx - 1);
+            v = dist[at];
+            key = zone_key(zone[at]);
+        }
+        box[i] = v;
+        zbox[i] = key;
+    }
+    __syncthreads();
+
+    const int lane = tid & 63, wave = tid >> 6;
+    const float w_x = wxy[0], w_y = wxy[1], w_xy = wxy[2];
+    u32 key[GEO_PER], tight[GEO_PER];                        // tight[k] bit j: the edge from neighbour j into voxel k is tight
+    u32 live = 0, moved = 0;                                 // bit k: voxel k has a tight edge / has changed since the load
+#pragma unroll
+    for (int k = 0; k < GEO_PER; k++) {
+        const int r = wave + 4 * k;                          // interior row: z = r / TY, y = r % TY
+        const int lz = r / GEO_TY;
+        const int at = ((lz + 1) * GEO_HY + (r % GEO_TY + 1)) * GEO_HX + lane + 1;
+        const float d = box[at];
+        const float *p = box + at;
+        key[k] = zbox[at];
+        u32 m = 0;
+        if (d < INFINITY)                                    // an unset or unreached voxel takes no part
+            zone_neighbours<CONN>(w_x, w_y, w_xy, swz + 4 * lz, swz + 4 * (lz + 1), [&](int j, int off, float w) {
+                if (p[off] + w == d) m |= 1u << j;           // the add of geo_relax; +inf + w is no finite d
+            });
+        tight[k] = m;
+        if (m) live |= 1u << k;
+    }
+
+    int more = 1, round = 0;
+    for (; round < GEO_ROUNDS && more; round++) {            // bounded: a tile that needs more marks itself below
+        u32 now = 0;
+#pragma unroll
+        for (int k = 0; k < GEO_PER; k++) {
+            if (!((live >> k) & 1)) continue;
+            const int r = wave + 4 * k;
+            const int lz = r / GEO_TY;
+            const u32 *q = zbox + ((lz + 1) * GEO_HY + (r % GEO_TY + 1)) * GEO_HX + lane + 1;
+            u32 loose = ~tight[k];
+            asm volatile("" : "+v"(loose));                  // opaque per round: the per-bit tests are not hoisted out of the loop
+            u32 c = key[k];                                  // (hoisted, 416 lane masks spill the scalar registers)
+            zone_neighbours<CONN>(w_x, w_y, w_xy, swz + 4 * lz, swz + 4 * (lz + 1), [&](int j, int off, float) {
+                c = min(c, q[off] | (u32)((int)(loose << (31 - j)) >> 31));      // a loose edge reads ZONE_NONE
+            });
+            if (c < key[k]) {
+                key[k] = c;
+                now |= 1u << k;
+            }
+        }
+        __syncthreads();                                     // every candidate of the round is formed: publish
+#pragma unroll
+        for (int k = 0; k < GEO_PER; k++) {
+            if ((now >> k) & 1) {
+                const int r = wave + 4 * k;
+                zbox[((r / GEO_TY + 1) * GEO_HY + (r % GEO_TY + 1)) * GEO_HX + lane + 1] = key[k];
+            }
+        }
+        moved |= now;
+        more = __syncthreads_or((int)now);
+    }
+
+    // store what changed, and name the neighbouring tiles next to a changed face, edge or corner voxel
+    u32 nb = 0;
+#pragma unroll
+    for (int k = 0; k < GEO_PER; k++) {
+        if (!((moved >> k) & 1)) continue;
+        const int r = wave + 4 * k;
+        const int lz = r / GEO_TY, ly = r % GEO_TY;
+        const int z = z0 + 1 + lz, y = y0 + 1 + ly;
+        zone[((int64_t)z * ny + y) * nx + (64 * bx + lane)] = (int)(key[k] + 1u);
+        const u32 zs = 2u | (lz == 0 ? 1u : 0u) | (lz == GEO_TZ - 1 ? 4u : 0u);     // bit 0 / 1 / 2: step -1 / 0 / +1
+        const u32 ys = 2u | (ly == 0 ? 1u : 0u) | (ly == GEO_TY - 1 ? 4u : 0u);
+        const u32 xs = 2u | (lane == 0 ? 1u : 0u) | (lane == 63 ? 4u : 0u);
+#pragma unroll
+        for (int a = 0; a < 3; a++)
+#pragma unroll
+            for (int b = 0; b < 3; b++)
+#pragma unroll
+                for (int c = 0; c < 3; c++)
+                    if (((zs >> a) & 1) && ((ys >> b) & 1) && ((xs >> c) & 1)) nb |= 1u << (9 * a + 3 * b + c);
+    }
+    if (nb) atomicOr(&snb, nb);                              // an LDS atomic
+    __syncthreads();
+    const u32 all = snb;
+    if (!(all || more)) return;                              // nothing changed: nothing is stored, nothing is marked
+    if (tid == 0) {
+        atomicAdd(counters, 1ull);                           // once per workgroup that changed something
+        if (more) dirty_next[tile] = 1u;                     // the round bound was hit
+    }
+    if (tid < 27 && tid != 13 && ((all >> tid) & 1)) {
+        const int dz = tid / 9 - 1, dy = (tid / 3) % 3 - 1, dx = tid % 3 - 1;
+        const int steps = (dz != 0) + (dy != 0) + (dx != 0);
+        const int tzn = (nz + GEO_TZ - 1) / GEO_TZ;
+        const int nbz = bz + dz, nby = by + dy, nbx = bx + dx;
+        if ((CONN == 26 || steps == 1) && nbz >= 0 && nbz < tzn && nby >= 0 && nby < ty && nbx >= 0 && nbx < wx)
+            dirty_next[((int64_t)nbz * ty + nby) * wx + nbx] = 1u;
+    }
+}
+
+// The cut: a wave takes ZONE_CUT_WORDS consecutive words one after the other, a lane is one voxel of the word.  A set voxel p goes
+// when a SET neighbour q has 0 < zone(q) < zone(p) -- the bits of q are tested, so a map handed in with entries on unset voxels
+// cuts nothing there.  out word = the survivors, tail bits zero.  The cleared voxels of a wave's words are added up in a register
+// and sent with ONE atomic per wave: one per word put 2.1 million atomics on one address at 512^3 and took 25 ms on 50 % noise.
+#define ZONE_CUT_WORDS 32
+
+template <int CONN>
+__global__ __launch_bounds__(GEO_THREADS) void zone_cut_kernel(const u64 *__restrict__ bits, const int *__restrict__ zone, int64_t nwords,
+                                                               int nz, int ny, int nx, int wx, u64 *__restrict__ out,
+                                                               unsigned long long *counter)
+{
+    const int64_t t = (int64_t)blockIdx.x * GEO_THREADS + threadIdx.x;
+    const int64_t first = (t >> 6) * ZONE_CUT_WORDS;         // the same for the 64 lanes of a wave, and so is the loop below
+    const int b = (int)(t & 63);
+    unsigned long long cleared = 0;
+    for (int64_t word = first; word < first + ZONE_CUT_WORDS && word < nwords; word++) {
+        const int64_t row = word / wx;
+        const int w = (int)(word - row * wx);
+        const int x = 64 * w + b;
+        const int z = (int)(row / ny), y = (int)(row - (int64_t)z * ny);
+        const u64 mid = geo_word(bits + row * wx, nx, wx, w);
+        bool clear = false;
+        if ((mid >> b) & 1) {
+            const int zp = zone[row * nx + x];
+            if (zp > 1) {                                    // no zone and zone 1 have nothing below them
+#pragma unroll
+                for (int dz = -1; dz <= 1; dz++)
+#pragma unroll
+                    for (int dy = -1; dy <= 1; dy++)
+#pragma unroll
+                        for (int dx = -1; dx <= 1; dx++) {
+                            const int steps = (dz != 0) + (dy != 0) + (dx != 0);
+                            if (steps == 0 || (CONN == 6 && steps != 1)) continue;
+                            const int zz = z + dz, yy = y + dy, xx = x + dx;
+                            if (zz < 0 || zz >= nz || yy < 0 || yy >= ny || xx < 0 || xx >= nx) continue;
+                            const int64_t r = (int64_t)zz * ny + yy;
+                            if (!((bits[r * wx + (xx >> 6)] >> (xx & 63)) & 1)) continue;      // xx < nx: no tail bit is read
+                            const int zq = zone[r * nx + xx];
+                            clear |= zq > 0 && zq < zp;
+                        }
+            }
+        }
+        const u64 gone = __ballot(clear);
+        if (b == 0) out[word] = mid & ~gone;
+        cleared += (unsigned long long)__popcll(gone);
+    }
+    if (b == 0 && cleared) atomicAdd(counter, cleared);      // one integer atomic per wave
+}
+
 // ---------------------------------------------------------------------------------------------- entry points
 TOMO_API int tomo_geo_seed_bits(const uint64_t *bits, const uint64_t *seeds, int nz, int ny, int nx, float *dist, uint32_t *dirty,
                                 void *stream)
@@ -391,5 +674,57 @@ TOMO_API int tomo_geo_reach(const uint64_t *bits, const float *dist, int nz, int
     if (r != TOMO_OK) return r;
     hipLaunchKernelGGL(geo_reach_kernel, dim3((unsigned)ceil_div64(g.words * 64, GEO_THREADS)), dim3(GEO_THREADS), 0,
                        (hipStream_t)stream, (const u64 *)bits, dist, g.words, nx, (int)g.wx, max_mm, isinf(max_mm) ? 1 : 0, (u64 *)out);
+    return tomo_status();
+}
+
+TOMO_API int tomo_zone_seed_labels(const uint64_t *bits, const int32_t *markers, int nz, int ny, int nx, float *dist, int32_t *zone,
+                                   uint32_t *dirty, void *stream)
+{
+    GeoGrid g;
+    if (!bits || !markers || !dist || !zone || !dirty || (const void *)markers == (const void *)zone) return TOMO_E_ARG;
+    const int r = geo_grid(nz, ny, nx, &g);
+    if (r != TOMO_OK) return r;
+    hipLaunchKernelGGL(zone_seed_kernel, dim3((unsigned)ceil_div64(g.words * 64, GEO_THREADS)), dim3(GEO_THREADS), 0,
+                       (hipStream_t)stream, (const u64 *)bits, (const int *)markers, g.words, nz, ny, nx, (int)g.wx, (int)g.ty, dist,
+                       (int *)zone, dirty);
+    return tomo_status();
+}
+
+TOMO_API int tomo_zone_sweep(const uint64_t *bits, int nz, int ny, int nx, int connectivity, const float *wxy, const float *wz,
+                             const float *dist, int32_t *zone, uint32_t *dirty_cur, uint32_t *dirty_next, unsigned long long *counters,
+                             void *stream)
+{
+    GeoGrid g;
+    if (!bits || !wxy || !wz || !dist || !zone || !dirty_cur || !dirty_next || !counters || dirty_cur == dirty_next ||
+        (const void *)dist == (const void *)zone || (connectivity != 6 && connectivity != 26))
+        return TOMO_E_ARG;
+    const int r = geo_grid(nz, ny, nx, &g);
+    if (r != TOMO_OK) return r;
+    const dim3 grid((unsigned)g.tiles), block(GEO_THREADS);
+    if (connectivity == 6)
+        hipLaunchKernelGGL(zone_sweep_kernel<6>, grid, block, 0, (hipStream_t)stream, (const u64 *)bits, nz, ny, nx, (int)g.wx, (int)g.ty,
+                           wxy, wz, dist, (int *)zone, dirty_cur, dirty_next, counters);
+    else
+        hipLaunchKernelGGL(zone_sweep_kernel<26>, grid, block, 0, (hipStream_t)stream, (const u64 *)bits, nz, ny, nx, (int)g.wx, (int)g.ty,
+                           wxy, wz, dist, (int *)zone, dirty_cur, dirty_next, counters);
+    return tomo_status();
+}
+
+TOMO_API int tomo_zone_cut(const uint64_t *bits, const int32_t *zone, int nz, int ny, int nx, int connectivity, uint64_t *out,
+                           unsigned long long *counter, void *stream)
+{
+    GeoGrid g;
+    if (!bits || !zone || !out || !counter || out == bits || (const void *)out == (const void *)zone ||
+        (connectivity != 6 && connectivity != 26))
+        return TOMO_E_ARG;
+    const int r = geo_grid(nz, ny, nx, &g);
+    if (r != TOMO_OK) return r;
+    const dim3 grid((unsigned)ceil_div64(ceil_div64(g.words, ZONE_CUT_WORDS) * 64, GEO_THREADS)), block(GEO_THREADS);
+    if (connectivity == 6)
+        hipLaunchKernelGGL(zone_cut_kernel<6>, grid, block, 0, (hipStream_t)stream, (const u64 *)bits, (const int *)zone, g.words, nz, ny,
+                           nx, (int)g.wx, (u64 *)out, counter);
+    else
+        hipLaunchKernelGGL(zone_cut_kernel<26>, grid, block, 0, (hipStream_t)stream, (const u64 *)bits, (const int *)zone, g.words, nz, ny,
+                           nx, (int)g.wx, (u64 *)out, counter);
     return tomo_status();
 }

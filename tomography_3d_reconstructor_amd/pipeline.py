@@ -26,7 +26,8 @@ COUNTERS = dict.fromkeys(("na_hint_hit", "na_hint_miss", "mc3_hint_hit", "mc3_hi
                           "components_measure", "components_zhist", "components_moments", "components_euler",
                           "components_cavities", "local_thickness", "opening_volume", "components_surface", "components_fill",
                           "components_cavity_owners", "component_thickness", "components_value", "components_levels", "component_caliper",
-                          "geodesic_calls", "geodesic_sweeps", "component_geodesic"), 0)
+                          "geodesic_calls", "geodesic_sweeps", "component_geodesic", "zone_calls", "zone_sweeps", "zone_cuts",
+                          "separate_components"), 0)
 NA_HINTS = os.environ.get("TOMO_NA_HINTS", "1") not in ("", "0")   # marching_cubes: launch ahead of the first count download
 _NA_HINT = {}
 LIST_LIMIT = 2 ** 31        # active-voxel list entries / vertices / triangles one pass can index (int32 offsets in mc.hip, mesh.hip);
@@ -1655,7 +1656,7 @@ def cavity_caliper(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per
 # ----------------------------------------------------------------------------- geodesic distance
 GEODESIC_SWEEP_BATCH = 8             # sweeps enqueued between two reads of the change counter (a sweep of a clean volume returns at once)
 GEODESIC_SWEEP_LIMIT = 1 << 16       # a guard against an endless host loop, no tuning knob; read when called
-GEODESIC_VOLUME_BUDGET = 1 << 33     # bytes of the float32 map; read when called
+GEODESIC_VOLUME_BUDGET = 1 << 33     # bytes of the float32 map (a zone call: of its three per-voxel maps); read when called
 
 
 def geodesic_weights(slice_depths, nz, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0):
@@ -1729,30 +1730,49 @@ class _GeodesicPlan:
         """What the two seeding entry points take behind dist (tomo_geo_seed_bits: without the counters)."""
         return _p(self.dirty[self.cur]), _p(self.counters)
 
+    def _sweeps(self, launch, what, counter) -> int:
+        """launch(cur, next) enqueues one sweep; batches of GEODESIC_SWEEP_BATCH until one changes nothing -> the sweeps launched."""
+        limit, batch = int(GEODESIC_SWEEP_LIMIT), max(1, int(GEODESIC_SWEEP_BATCH))
+        done = 0
+        while True:
+            if done >= limit:
+                raise _lib.TomoError("%s: no fixed point after %d sweeps (GEODESIC_SWEEP_LIMIT)" % (what, done))
+            k = min(batch, limit - done)
+            for _ in range(k):
+                launch(_p(self.dirty[self.cur]), _p(self.dirty[1 - self.cur]))
+                self.cur = 1 - self.cur
+            done += k
+            COUNTERS[counter] += k
+            changed = _download(self.counters)[0]
+            if changed == self.changed:
+                return done
+            self.changed = changed
+
     def propagate(self, dist: torch.Tensor) -> int:
         """Sweeps until a batch changes nothing -> the sweeps launched.  No seed: none.  Termination is guaranteed -- values only
         fall and come from a finite set; GEODESIC_SWEEP_LIMIT only guards the host loop."""
         L, st = _lib.lib(), _stream()
         nz, ny, nx = self.vol.shape
-        limit, batch = int(GEODESIC_SWEEP_LIMIT), max(1, int(GEODESIC_SWEEP_BATCH))
         if not bool(self.dirty[self.cur].any().item()):
             return 0
-        done = 0
-        while True:
-            if done >= limit:
-                raise _lib.TomoError("geodesic distance: no fixed point after %d sweeps (GEODESIC_SWEEP_LIMIT)" % done)
-            k = min(batch, limit - done)
-            for _ in range(k):
-                _lib.check(L.tomo_geo_sweep(_p(self.bits), nz, ny, nx, self.connectivity, _p(self.wxy), _p(self.wz), _p(dist),
-                                            _p(self.dirty[self.cur]), _p(self.dirty[1 - self.cur]), _p(self.counters), st),
-                           "tomo_geo_sweep")
-                self.cur = 1 - self.cur
-            done += k
-            COUNTERS["geodesic_sweeps"] += k
-            changed = _download(self.counters)[0]
-            if changed == self.changed:
-                return done
-            self.changed = changed
+
+        def sweep(cur, nxt):
+            _lib.check(L.tomo_geo_sweep(_p(self.bits), nz, ny, nx, self.connectivity, _p(self.wxy), _p(self.wz), _p(dist), cur, nxt,
+                                        _p(self.counters), st), "tomo_geo_sweep")
+        return self._sweeps(sweep, "geodesic distance", "geodesic_sweeps")
+
+    def propagate_zones(self, dist: torch.Tensor, zone: torch.Tensor) -> int:
+        """The label phase over the FINAL dist of propagate(), which left every flag clear -> the sweeps launched.  It starts with
+        every flag set (one fill): a tile without work changes nothing, marks nobody and is out after the first sweep.  Labels
+        only fall through a finite set, so it ends; the loop and its guard are propagate()'s."""
+        L, st = _lib.lib(), _stream()
+        nz, ny, nx = self.vol.shape
+        self.dirty[self.cur].fill_(1)
+
+        def sweep(cur, nxt):
+            _lib.check(L.tomo_zone_sweep(_p(self.bits), nz, ny, nx, self.connectivity, _p(self.wxy), _p(self.wz), _p(dist), _p(zone),
+                                         cur, nxt, _p(self.counters), st), "tomo_zone_sweep")
+        return self._sweeps(sweep, "geodesic zones", "zone_sweeps")
 
 
 def _geodesic_seeds(shape, seeds):
@@ -1901,6 +1921,146 @@ def cavity_geodesic(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_pe
     _geodesic_tables(vol.shape, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
     bg = _complement_runs(vol, connectivity)
     return bg.geodesic(slice_depths, mm_per_pixel_y, mm_per_pixel_x, sweeps, lo, max_voxels=hi, enclosed=True)
+
+
+# ----------------------------------------------------------------------------- zones of markers, the cut, the separation
+def _zone_markers(vol: BitVolume, markers):
+    """markers -> ("bits", BitVolume) or ("map", int32 device tensor); TypeError / ValueError for anything else, on the host."""
+    if isinstance(markers, BitVolume):
+        if tuple(markers.shape) != tuple(vol.shape):
+            raise ValueError("markers must have the shape of the volume")
+        if markers.device != vol.device:
+            raise ValueError("markers must be on the volume's device")
+        return "bits", markers
+    return "map", _zone_map(vol, markers, "markers")
+
+
+def _zone_map(vol: BitVolume, m, what) -> torch.Tensor:
+    if not isinstance(m, torch.Tensor):
+        raise TypeError("%s must be %san int32 tensor (nz, ny, nx)" % (what, "a BitVolume or " if what == "markers" else ""))
+    if m.dtype != torch.int32:
+        raise TypeError("%s must be int32" % what)
+    if tuple(m.shape) != tuple(vol.shape):
+        raise ValueError("%s must have the shape of the volume" % what)
+    if m.device != vol.device:
+        raise ValueError("%s must be on the volume's device" % what)
+    return m
+
+
+def _zone_budget(shape):
+    """Before anything is allocated: a zone call holds three per-voxel maps at once."""
+    nz, ny, nx = shape
+    nbytes = 12 * nz * ny * nx
+    if nbytes > GEODESIC_VOLUME_BUDGET:
+        raise _lib.TomoError("geodesic zones: the float32 distance map, the int32 zone map and the int32 marker map of %d x %d x %d "
+                             "voxels take %d bytes, more than GEODESIC_VOLUME_BUDGET (%d)" % (nz, ny, nx, nbytes, GEODESIC_VOLUME_BUDGET))
+
+
+def _geodesic_zones(vol: BitVolume, markers, tables: _GeodesicTables, connectivity):
+    """-> (zones, dist, (distance sweeps, label sweeps), the marker components of a BitVolume or None)."""
+    kind, m = markers
+    _zone_budget(vol.shape)
+    L, dev = _lib.lib(), vol.device
+    nz, ny, nx = vol.shape
+    count = None
+    if kind == "bits":
+        m, count = ComponentRuns(m, connectivity).labels()
+    plan = _GeodesicPlan(vol, tables, connectivity)
+    COUNTERS["zone_calls"] += 1
+    dist = torch.empty(vol.shape, dtype=torch.float32, device=dev)
+    zone = torch.empty(vol.shape, dtype=torch.int32, device=dev)
+    _lib.check(L.tomo_zone_seed_labels(_p(plan.bits), _p(m.contiguous()), nz, ny, nx, _p(dist), _p(zone), plan.seed_tail()[0], _stream()),
+               "tomo_zone_seed_labels")
+    far = plan.propagate(dist)                                           # phase one: the distances, to their fixed point
+    near = plan.propagate_zones(dist, zone) if far else 0               # phase two: the labels over the final distances
+    return zone, dist, (far, near), count
+
+
+def geodesic_zones(vol: BitVolume, markers, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, connectivity=26):
+    """Which marker reaches a voxel first through the object -> (zones int32 (nz, ny, nx) device tensor, dist float32 device
+    tensor): the geodesic influence zones of the markers inside the set voxels of a resident volume.
+    markers: an int32 device tensor of the volume's shape -- a positive entry on a set voxel is a marker voxel with that label,
+    entries <= 0 and entries on unset voxels are ignored, labels need not be consecutive -- or a BitVolume, which is labelled
+    under `connectivity` with ComponentRuns(markers, connectivity).labels(): 1 .. n in raster order.
+    dist is geodesic_distance(vol, the marker voxels) under the same spacing and connectivity, byte for byte.  An edge q -> p
+    between neighbouring set voxels is tight when fl32(dist(q) + w(q, p)) == dist(p) with dist(p) finite -- the float32 addition
+    the distance sweep makes; zone(p) is the smallest marker label among the markers from which p can be reached along tight
+    edges, 0 at unset voxels and at set voxels no marker reaches; a marker voxel keeps its label.  That is the least fixed point
+    of zone(p) = min(zone(p), zone(q) over tight q -> p) over a fixed graph: one answer, whatever the schedule.
+    Two phases on the device: the distance sweeps of geodesic_distance to their fixed point, then label sweeps over the final
+    distances (tomo_zone_sweep), in the same host loop: GEODESIC_SWEEP_BATCH sweeps between two counter reads, more than
+    GEODESIC_SWEEP_LIMIT: TomoError.  The call holds three per-voxel maps at once (dist, zones, the marker map); more than
+    GEODESIC_VOLUME_BUDGET bytes: TomoError before anything is allocated.  An empty volume, or no marker on a set voxel: zones
+    all 0, no sweep is launched.  Arguments are checked before the first launch."""
+    connectivity = _check_connectivity(connectivity)
+    tables = _geodesic_tables(vol.shape, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    zone, dist, _, _ = _geodesic_zones(vol, _zone_markers(vol, markers), tables, connectivity)
+    return zone, dist
+
+
+def _split_zones(vol: BitVolume, zones: torch.Tensor, connectivity):
+    """-> (the cut BitVolume, the 1-element int64 device counter of the cleared voxels)."""
+    bits = vol.bits.contiguous()
+    out = torch.empty_like(bits)
+    cleared = torch.zeros(1, dtype=torch.int64, device=vol.device)
+    COUNTERS["zone_cuts"] += 1
+    _lib.check(_lib.lib().tomo_zone_cut(_p(bits), _p(zones.contiguous()), *vol.shape, connectivity, _p(out), _p(cleared), _stream()),
+               "tomo_zone_cut")
+    return BitVolume(out, vol.shape), cleared
+
+
+def split_zones(vol: BitVolume, zones: torch.Tensor, connectivity=26) -> BitVolume:
+    """The cut between zones -> a NEW BitVolume; `vol` is left untouched.  A set voxel p is cleared when some neighbour q under
+    the connectivity is set with 0 < zones(q) < zones(p): the lower label keeps the contact.  Afterwards no two voxels of
+    different zones are adjacent, so every component of the result lies in one zone; a component without a marker (zones 0)
+    is untouched.  zones: geodesic_zones' map, or any int32 device tensor of the volume's shape (entries <= 0 are no zone)."""
+    connectivity = _check_connectivity(connectivity)
+    return _split_zones(vol, _zone_map(vol, zones, "zones"), connectivity)[0]
+
+
+@dataclass
+class Separation:
+    """separate_components' answer."""
+    volume: BitVolume            # the cut volume: every per-component measurement applies to it unchanged
+    markers: int                 # marker components the zones grew from
+    cut_voxels: int              # set voxels the cut cleared
+    zones: torch.Tensor          # int32 (nz, ny, nx) device tensor: geodesic_zones of the markers
+    sweeps: tuple                # (distance sweeps, label sweeps) launched
+
+
+def _separation_args(shape, radius_mm, slice_depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_marker_voxels):
+    """The argument checks of separate_components, all on the host -> (radius, tables, connectivity, min_marker_voxels)."""
+    if isinstance(radius_mm, (bool, np.bool_)) or not isinstance(radius_mm, (int, float, np.integer, np.floating)):
+        raise ValueError("radius_mm must be positive and finite")
+    r = _positive(radius_mm, "radius_mm")
+    connectivity = _check_connectivity(connectivity)
+    tables = _geodesic_tables(shape, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    return r, tables, connectivity, _whole_size(min_marker_voxels, "min_marker_voxels")
+
+
+def separate_components(vol: BitVolume, radius_mm, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, connectivity=6,
+                        min_marker_voxels=1) -> Separation:
+    """Marker-based separation of touching objects (grains joined by a neck, pore bodies joined by a throat) -> Separation.
+    1. markers = offset_volume(vol, -radius_mm, ...): the exact ball erosion, the voxels whose inside distance exceeds
+       radius_mm (positive and finite, else ValueError) -- the cores of the objects.
+    2. Markers of fewer than min_marker_voxels voxels under `connectivity` are dropped (keep_components).
+    3. geodesic_zones grows the markers back through the object; split_zones cuts where two growths meet.
+    Separation.volume is a plain BitVolume: volume, box, moments, Euler number, surface, thickness, caliper and geodesic length
+    per component apply to the separated objects unchanged (ComponentRuns(sep.volume, connectivity)).  An object thinner than
+    the radius everywhere has no marker and stays whole.  A fixed radius over-segments elongated or lobed objects: a grain
+    whose erosion falls into two cores is cut in two.  For another marker rule build the markers yourself and hand the map to
+    geodesic_zones and split_zones.  separate_components(cavity_volume(vol), ...) separates pore bodies at their throats.
+    Arguments are checked before the first launch."""
+    r, tables, connectivity, least = _separation_args(vol.shape, radius_mm, slice_depths, mm_per_pixel_y, mm_per_pixel_x,
+                                                      connectivity, min_marker_voxels)
+    _zone_budget(vol.shape)
+    COUNTERS["separate_components"] += 1
+    markers = offset_volume(vol, -r, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    if least > 1:
+        markers = keep_components(markers, least, False, connectivity)
+    zone, _, sweeps, count = _geodesic_zones(vol, ("bits", markers), tables, connectivity)
+    out, cleared = _split_zones(vol, zone, connectivity)
+    return Separation(out, int(count), int(_download(cleared)[0]), zone, sweeps)
 
 
 def local_thickness(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, radii_mm=None,

@@ -225,10 +225,32 @@ def closed_porosity(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, co
     return report
 
 
+def separate_grains(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, radius_mm, connectivity=6, min_marker_voxels=1):
+    """Touching objects taken apart (no counterpart in the reference): pipeline.separate_components -- the cores left by a ball
+    erosion of radius_mm millimetres are grown back through the object, and the object is cut where two growths meet; per-slice
+    depths honoured -> {'volume' (the separated volume, a NumPy bool array of the input's shape), 'components_before',
+    'components_after' (under `connectivity`), 'markers' (cores of at least min_marker_voxels voxels), 'cut_voxels', 'cut_share'
+    (cut voxels over the set voxels of the input; 0.0 for an empty volume)}.  An object thinner than the radius everywhere has no
+    core and stays whole; a fixed radius cuts an elongated grain whose erosion falls into two cores (pipeline.geodesic_zones takes
+    markers made by another rule).  component_properties(..., separate_mm=radius_mm) measures the separated grains.
+    voxel_data: the bool (nz, ny, nx) array the other calculations take; anything else is a TypeError."""
+    if not _on_device(voxel_data):
+        raise TypeError("separate_grains needs a bool (nz, ny, nx) array")
+    depths = np.asarray(slice_depths, dtype=np.float64).reshape(-1)
+    pipeline._separation_args(voxel_data.shape, radius_mm, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_marker_voxels)
+    vol = to_device_volume(voxel_data)
+    before = int(pipeline.ComponentRuns(vol, connectivity).sizes().shape[0])
+    solid = int(pipeline.popcount_async(vol).item())
+    sep = pipeline.separate_components(vol, radius_mm, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_marker_voxels)
+    after = int(pipeline.ComponentRuns(sep.volume, connectivity).sizes().shape[0])
+    return {'volume': pipeline.unpack(sep.volume).cpu().numpy(), 'components_before': before, 'components_after': after,
+            'markers': sep.markers, 'cut_voxels': sep.cut_voxels, 'cut_share': sep.cut_voxels / solid if solid else 0.0}
+
+
 def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=6, min_voxels=0, largest=False,
                          shape=False, topology=False, surface=False, surface_directions=13, porosity=False, thickness=False,
-                         thickness_radii_mm=None, geodesic=False, geodesic_sweeps=3, caliper=False, caliper_directions=None,
-                         caliper_oriented=False):
+                         thickness_radii_mm=None, geodesic=False, geodesic_sweeps=3, separate_mm=None, caliper=False,
+                         caliper_directions=None, caliper_oriented=False):
     """The calculations of the class per connected component (no counterpart in the reference, which would be handed the mask
     `labels == c` once per component) -> a list of dicts, one per component with at least min_voxels voxels (largest: only the
     largest of those), in label order: {'label', 'voxels', 'voxel_volume_mm3', 'bounding_box': {'x', 'y', 'z'}, 'dimensions',
@@ -259,6 +281,9 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
     along itself, the repeated farthest-point search of pipeline.component_geodesic with geodesic_sweeps searches (at least 2) and
     the steps of `connectivity`, centre to centre: a lower bound of its geodesic diameter on the lattice metric --
     'geodesic_ends_index' (the two ends, (z, y, x) each) and 'tortuosity', that length over the straight distance of the ends.
+    separate_mm=r (a keyword; None: off, nothing new is launched): touching objects are separated first -- the uploaded volume is
+    replaced by pipeline.separate_components(volume, r, ..., connectivity).volume BEFORE the one labelling, so the rows, and every
+    flag above, measure the separated grains (separate_grains returns that volume and its counts).
     Whatever the
     flags, the volume is uploaded and labelled ONCE, and so is its complement: one pipeline.ComponentRuns serves all the
     measurements and owns the one selection their rows come from.  Arguments are checked before the first launch.  voxel_data: a bool (nz, ny, nx) array, else a TypeError."""
@@ -276,7 +301,12 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
     if geodesic:
         pipeline._geodesic_search_sweeps(geodesic_sweeps)
         pipeline._geodesic_tables(voxel_data.shape, depths, mm_per_pixel_y, mm_per_pixel_x)
-    runs = pipeline.ComponentRuns(to_device_volume(voxel_data), connectivity)
+    if separate_mm is not None:
+        pipeline._separation_args(voxel_data.shape, separate_mm, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, 1)
+    vol = to_device_volume(voxel_data)
+    if separate_mm is not None:
+        vol = pipeline.separate_components(vol, separate_mm, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity).volume
+    runs = pipeline.ComponentRuns(vol, connectivity)
     if runs.select(*rule) is None:
         return []
     p = runs.properties(tables, mm_per_pixel_y, mm_per_pixel_x, *rule)
