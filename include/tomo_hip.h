@@ -513,6 +513,57 @@ int tomo_zone_sweep(const uint64_t *bits, int nz, int ny, int nx, int connectivi
                     void *stream);
 int tomo_zone_cut(const uint64_t *bits, const int32_t *zone, int nz, int ny, int nx, int connectivity, uint64_t *out,
                   unsigned long long *counter, void *stream);
+/* The contact table between zones (csrc/contacts.hip; no counterpart in the reference): which zones touch, over how large an
+ * interface, how wide the throat between them is and how long the way across.  One definition.
+ * zones: int32 (nz, ny, nx), tomo_zone_sweep's map or any map.  A voxel TAKES PART when it is set and its entry is positive.
+ * A CONTACT PAIR is an unordered pair {p, q} of voxels that take part, are 26-neighbours and have zones(p) != zones(q).  It is
+ * counted exactly once, at the raster-earlier voxel p, which looks at its 13 forward neighbours: (0, 0, +1) in its row,
+ * (0, +1, -1 .. +1) in the next row of the slice, (+1, -1 .. +1, -1 .. +1) in the next slice.  Neighbours outside the stack do
+ * not exist; a row never sees the end of the previous row.  The pair belongs to the ZONE PAIR (a, b) = (min, max) of the two
+ * labels, to slice k = the slice of p (the lower of the two) and to one of the seven direction classes of tomo_cc_surface_hist,
+ * in that order: x, y, xy, z, xz, yz, xyz.  Per zone pair:
+ *   pairs        the contact pairs;  pair_counts[7] the same per class;  z_lo, z_hi the lowest and the highest k
+ *   first_index  the smallest flat index (z * ny + y) * nx + x of a p
+ *   area         the sequential float64 sum, in ascending k and within a slice in ascending class c, of
+ *                (double)count[k][c] * F[k * 11 + c], F = the (nz, 11) table of tomo_cc_surface: columns 0 .. 2 use the slice's
+ *                own depth, 3 .. 6 are the columns towards slice k + 1.  One adjacent pair of unlike voxels is one crossing of
+ *                the interface by a lattice line, so the factor is that of the surface area.  directions == 3: x, y and z only.
+ *   value_max    with `values` (float32 (nz, ny, nx), NaN-free; -0.0 counts as +0.0): the largest value over all p and q of the
+ *                zone pair's contact pairs;  value_index the smallest flat index that attains it
+ *   path         with `dist` (float32, non-negative or +inf) and the step weights wxy, wz of tomo_geo_sweep: the minimum over the
+ *                contact pairs of fl32(fl32(dist(p) + w(p, q)) + dist(q)), p the raster-earlier voxel; +inf where none is finite
+ * The table is open-addressed over 64-bit keys (a << 32) | b -- never 0, so a zeroed table is empty -- of `cap` slots, cap a
+ * power of two; a 64-bit mixer, linear probing, a slot claimed by ONE compare-and-swap.  No thread waits for another and a probe
+ * ends after cap steps.  Integer atomics only: the same bytes on every run.
+ *   tomo_contact_count   *counter = the contact pairs N (zeroed here), one atomic per wave at most
+ *   tomo_contact_insert  clears the slot arrays, then per slot: keys, pairs (sum), z_lo (min, read as uint32), z_hi (max),
+ *                        first_index (min), value_max (max of an order-preserving uint32 key; with values), path (min of the bit
+ *                        pattern; with dist).  A lane that finds no slot adds its pairs to counters[0] (zeroed by the caller)
+ *                        and drops them: the caller must then discard the table (from then on no wave probes it any more,
+ *                        so counters[0] says that pairs were lost, not how many a full run would have lost).
+ *   tomo_contact_hist    lookup only.  row_of_slot: the row of an occupied slot, -1 elsewhere; offset[row]: the first slice entry
+ *                        of the row, its segment z_hi - z_lo + 1 entries long.  Clears hist (entries x 7 uint64) and, with
+ *                        values, value_index (rows uint64); adds to hist[(offset[row] + k - z_lo) * 7 + class] and takes the
+ *                        minimum index whose value equals the slot's maximum.  A key the table does not hold, or an entry
+ *                        outside [0, entries), is never written: its pairs are added to counters[1].
+ *   tomo_contact_finish  one thread per row: out[row * 17 ..] = a, b, pairs, pair_counts[7], the bits of area, z_lo, z_hi,
+ *                        first_index, the bits of value_max (float32), value_index, the bits of path (float32); a row whose
+ *                        segment does not fit adds 1 to counters[1] and is zeroed.
+ * values, dist (with wxy, wz, path), value_max and value_index may be NULL together as stated.  TOMO_E_ARG for a null or aliased
+ * pointer, a non-positive size, a cap that is no power of two, rows > cap, directions other than 3 / 13; TOMO_E_SIZE from 2^31
+ * words on and for cap > 2^30. */
+int tomo_contact_count(const uint64_t *bits, const int32_t *zones, int nz, int ny, int nx, unsigned long long *counter, void *stream);
+int tomo_contact_insert(const uint64_t *bits, const int32_t *zones, int nz, int ny, int nx, const float *values, const float *dist,
+                        const float *wxy, const float *wz, int64_t cap, uint64_t *keys, uint64_t *pairs, int32_t *z_lo, int32_t *z_hi,
+                        uint64_t *first_index, uint32_t *value_max, uint32_t *path, unsigned long long *counters, void *stream);
+int tomo_contact_hist(const uint64_t *bits, const int32_t *zones, int nz, int ny, int nx, const float *values, int64_t cap,
+                      const uint64_t *keys, const int32_t *row_of_slot, const int32_t *z_lo, const uint32_t *value_max,
+                      const int64_t *offset, int64_t rows, uint64_t *hist, int64_t entries, uint64_t *value_index,
+                      unsigned long long *counters, void *stream);
+int tomo_contact_finish(int64_t rows, const int32_t *slot_of_row, int64_t cap, const uint64_t *keys, const uint64_t *pairs,
+                        const int32_t *z_lo, const int32_t *z_hi, const uint64_t *first_index, const uint32_t *value_max,
+                        const uint32_t *path, const uint64_t *value_index, const int64_t *offset, const uint64_t *hist, int64_t entries,
+                        const double *F, int nz, int directions, int64_t *out, unsigned long long *counters, void *stream);
 /* The same across Z-slabs (slab_components.py): rank r labels its slab with the functions above (n_r components); local
  * component c has the global id base_r + c, base_r = n_0 + .. + n_(r-1).  Pieces that touch across a cut are united, the roots
  * (smallest id = the piece with the component's first voxel) numbered in ascending id: scipy's numbering of the whole stack.

@@ -27,7 +27,7 @@ COUNTERS = dict.fromkeys(("na_hint_hit", "na_hint_miss", "mc3_hint_hit", "mc3_hi
                           "components_cavities", "local_thickness", "opening_volume", "components_surface", "components_fill",
                           "components_cavity_owners", "component_thickness", "components_value", "components_levels", "component_caliper",
                           "geodesic_calls", "geodesic_sweeps", "component_geodesic", "zone_calls", "zone_sweeps", "zone_cuts",
-                          "separate_components"), 0)
+                          "separate_components", "zone_contacts", "contact_launches"), 0)
 NA_HINTS = os.environ.get("TOMO_NA_HINTS", "1") not in ("", "0")   # marching_cubes: launch ahead of the first count download
 _NA_HINT = {}
 LIST_LIMIT = 2 ** 31        # active-voxel list entries / vertices / triangles one pass can index (int32 offsets in mc.hip, mesh.hip);
@@ -2050,17 +2050,239 @@ def separate_components(vol: BitVolume, radius_mm, slice_depths=None, mm_per_pix
     the radius everywhere has no marker and stays whole.  A fixed radius over-segments elongated or lobed objects: a grain
     whose erosion falls into two cores is cut in two.  For another marker rule build the markers yourself and hand the map to
     geodesic_zones and split_zones.  separate_components(cavity_volume(vol), ...) separates pore bodies at their throats.
-    Arguments are checked before the first launch."""
-    r, tables, connectivity, least = _separation_args(vol.shape, radius_mm, slice_depths, mm_per_pixel_y, mm_per_pixel_x,
-                                                      connectivity, min_marker_voxels)
+    Arguments are checked before the first launch.  separate_with_contacts returns the contact table of the zones as well."""
+    args = _separation_args(vol.shape, radius_mm, slice_depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_marker_voxels)
+    return _separate(vol, args, slice_depths, mm_per_pixel_y, mm_per_pixel_x)[0]
+
+
+def _separate(vol: BitVolume, args, slice_depths, mm_per_pixel_y, mm_per_pixel_x):
+    """The separation itself -> (Separation, the zones' distance map)."""
+    r, tables, connectivity, least = args
     _zone_budget(vol.shape)
     COUNTERS["separate_components"] += 1
     markers = offset_volume(vol, -r, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
     if least > 1:
         markers = keep_components(markers, least, False, connectivity)
-    zone, _, sweeps, count = _geodesic_zones(vol, ("bits", markers), tables, connectivity)
+    zone, dist, sweeps, count = _geodesic_zones(vol, ("bits", markers), tables, connectivity)
     out, cleared = _split_zones(vol, zone, connectivity)
-    return Separation(out, int(count), int(_download(cleared)[0]), zone, sweeps)
+    return Separation(out, int(count), int(_download(cleared)[0]), zone, sweeps), dist
+
+
+# ----------------------------------------------------------------------------- the contact table between zones
+CONTACT_TABLE_BUDGET = 1 << 30       # bytes of the slot arrays of zone_contacts' hash table; read when called
+CONTACT_SLOT_BYTES = 44              # per slot: key, pairs, first index (8 each), z_lo, z_hi, value, path, row of the slot (4 each)
+CONTACT_ENTRY_BYTES = 56             # per slice entry of a row: seven uint64 counters, one per direction class
+CONTACT_COLUMNS = 17                 # int64 words per row of tomo_contact_finish
+CONTACT_SLOT_LIMIT = 1 << 30         # slots the kernels index
+
+
+@dataclass
+class ZoneContacts:
+    """zone_contacts' answer: host arrays, one row per pair of zones in contact, sorted by (zone_a, zone_b)."""
+    zone_a: np.ndarray            # int64 (P,): the lower label of the pair
+    zone_b: np.ndarray            # int64 (P,): the higher label
+    pairs: np.ndarray             # int64 (P,): 26-adjacent voxel pairs across the interface
+    pair_counts: np.ndarray       # int64 (P, 7): the same per class x, y, xy, z, xz, yz, xyz
+    area_mm2: np.ndarray          # float64 (P,): the Crofton estimate of the interface area
+    z_range: np.ndarray           # int64 (P, 2): the lowest and the highest slice of a contact pair (of its raster-earlier voxel)
+    first_index: np.ndarray       # int64 (P, 3): (z, y, x) of the first raster-earlier voxel of a contact pair
+    value_max: np.ndarray = None  # float32 (P,): the largest of `values` on the interface; None without values
+    value_index: np.ndarray = None  # int64 (P, 3): (z, y, x) of the first voxel that attains it
+    path_mm: np.ndarray = None    # float32 (P,): the shortest way between the two zones' markers across the interface; None without dist
+
+    def __len__(self):
+        return len(self.zone_a)
+
+    def coordination(self, labels=None):
+        """-> (labels int64, neighbours int64, area_mm2 float64): per zone the number of distinct zones it touches and its
+        summed contact area, the rows added in table order.  labels=None: the zones that occur in the table, ascending.  With
+        `labels` (distinct) the answer follows them, a zone without a contact reads 0, and zones not listed are left out."""
+        zs = np.concatenate([self.zone_a, self.zone_b]).astype(np.int64)
+        areas = np.concatenate([self.area_mm2, self.area_mm2]).astype(np.float64)
+        if labels is None:
+            labels = np.unique(zs)
+        labels = np.asarray(labels, dtype=np.int64).reshape(-1)
+        order = np.argsort(labels, kind="stable")
+        ranked = labels[order]
+        if len(ranked) > 1 and (ranked[1:] == ranked[:-1]).any():
+            raise ValueError("labels must be distinct")
+        neighbours = np.zeros(len(labels), dtype=np.int64)
+        area = np.zeros(len(labels), dtype=np.float64)
+        if len(labels) and len(zs):
+            pos = np.minimum(np.searchsorted(ranked, zs), len(ranked) - 1)
+            known = ranked[pos] == zs
+            at = order[pos[known]]
+            np.add.at(neighbours, at, 1)
+            np.add.at(area, at, areas[known])
+        return labels, neighbours, area
+
+
+def _contact_values(vol: BitVolume, m, what):
+    if m is None:
+        return None
+    if not isinstance(m, torch.Tensor):
+        raise TypeError("%s must be a float32 tensor (nz, ny, nx)" % what)
+    if m.dtype != torch.float32:
+        raise TypeError("%s must be float32" % what)
+    if tuple(m.shape) != tuple(vol.shape):
+        raise ValueError("%s must have the shape of the volume" % what)
+    if m.device != vol.device:
+        raise ValueError("%s must be on the volume's device" % what)
+    return m
+
+
+def _contact_args(vol: BitVolume, zones, slice_depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, directions, values, dist):
+    """The argument checks of zone_contacts, all on the host -> (zones, connectivity, F, directions, tables, values, dist)."""
+    zones = _zone_map(vol, zones, "zones")
+    connectivity = _check_connectivity(connectivity)
+    F = surface_factors(slice_depths, vol.shape[0], mm_per_pixel_y, mm_per_pixel_x, directions)
+    tables = _geodesic_tables(vol.shape, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    return zones, connectivity, F, int(directions), tables, _contact_values(vol, values, "values"), _contact_values(vol, dist, "dist")
+
+
+def _contact_capacity(pairs: int) -> int:
+    """The slots of the hash table for N contact pairs: a power of two, at least 2 N (the zone pairs cannot exceed N), capped by
+    CONTACT_TABLE_BUDGET and by what the kernels index."""
+    limit = min(int(CONTACT_TABLE_BUDGET) // CONTACT_SLOT_BYTES, CONTACT_SLOT_LIMIT)
+    if limit < 1:
+        raise _lib.TomoError("zone_contacts: CONTACT_TABLE_BUDGET (%d bytes) does not hold one slot of %d bytes"
+                             % (CONTACT_TABLE_BUDGET, CONTACT_SLOT_BYTES))
+    cap = 64
+    while cap < 2 * pairs and cap < CONTACT_SLOT_LIMIT:
+        cap <<= 1
+    while cap > limit:
+        cap >>= 1
+    return cap
+
+
+def _empty_contacts(values, dist) -> ZoneContacts:
+    i, f = np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.float32)
+    return ZoneContacts(i, i.copy(), i.copy(), np.zeros((0, SURFACE_CLASSES), dtype=np.int64), np.zeros(0, dtype=np.float64),
+                        np.zeros((0, 2), dtype=np.int64), np.zeros((0, 3), dtype=np.int64), None if values is None else f,
+                        None if values is None else np.zeros((0, 3), dtype=np.int64), None if dist is None else f.copy())
+
+
+def _zone_contacts(vol: BitVolume, args) -> ZoneContacts:
+    zones, connectivity, F, directions, tables, values, dist = args
+    L, dev, st = _lib.lib(), vol.device, _stream()
+    nz, ny, nx = vol.shape
+    bits, zones = vol.bits.contiguous(), zones.contiguous()
+    values = None if values is None else values.contiguous()
+    dist = None if dist is None else dist.contiguous()
+    head = (_p(bits), _p(zones), nz, ny, nx)
+    COUNTERS["zone_contacts"] += 1
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    COUNTERS["contact_launches"] += 1
+    _lib.check(L.tomo_contact_count(*head, _p(count), st), "tomo_contact_count")
+    pairs = _download(count)[0]
+    if pairs == 0:
+        return _empty_contacts(values, dist)
+    cap = _contact_capacity(pairs)
+    keys, total, first = (torch.empty(cap, dtype=torch.int64, device=dev) for _ in range(3))
+    z_lo, z_hi = (torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(2))
+    top = None if values is None else torch.empty(cap, dtype=torch.int32, device=dev)
+    path = wxy = wz = None
+    if dist is not None:
+        path = torch.empty(cap, dtype=torch.int32, device=dev)
+        wxy, wz = torch.from_numpy(tables.wxy).to(dev), torch.from_numpy(np.ascontiguousarray(tables.wz)).to(dev)
+    counters = torch.zeros(2, dtype=torch.int64, device=dev)          # pairs that found no slot, pairs whose key was not found
+    COUNTERS["contact_launches"] += 1
+    _lib.check(L.tomo_contact_insert(*head, _p(values), _p(dist), _p(wxy), _p(wz), cap, _p(keys), _p(total), _p(z_lo), _p(z_hi),
+                                     _p(first), _p(top), _p(path), _p(counters), st), "tomo_contact_insert")
+    # P rows, never voxels: the occupied slots, their keys sorted, the row of every slot, the slice segments of the rows
+    taken = keys != 0
+    span = (z_hi - z_lo + 1).to(torch.int64) * taken                   # an empty slot counts for nothing
+    rows, lost, entries = _download(torch.stack([taken.sum(), counters[0], span.sum()]))          # the one host read
+    if lost:
+        raise _lib.TomoError("zone_contacts: the hash table of %d slots (CONTACT_TABLE_BUDGET = %d bytes, %d bytes a slot) has no room "
+                             "for the zone pairs of %d contact pairs" % (cap, CONTACT_TABLE_BUDGET, CONTACT_SLOT_BYTES, pairs))
+    if entries * CONTACT_ENTRY_BYTES > COMPONENT_HIST_BUDGET:
+        raise _lib.TomoError("zone_contacts: the per-slice counters of %d zone pairs take %d bytes, more than COMPONENT_HIST_BUDGET (%d)"
+                             % (rows, entries * CONTACT_ENTRY_BYTES, COMPONENT_HIST_BUDGET))
+    slots = taken.nonzero_static(size=rows).reshape(-1)
+    order = keys[slots].sort()[1]                                 # the keys are unique: stability does not matter
+    slot_of_row = slots[order].to(torch.int32)
+    row_of_slot = torch.full((cap,), -1, dtype=torch.int32, device=dev)
+    row_of_slot[slot_of_row.long()] = torch.arange(rows, dtype=torch.int32, device=dev)
+    length = span[slot_of_row.long()]
+    offset = (length.cumsum(0) - length).contiguous()
+    hist = torch.empty(entries * SURFACE_CLASSES, dtype=torch.int64, device=dev)
+    where = None if values is None else torch.empty(rows, dtype=torch.int64, device=dev)
+    COUNTERS["contact_launches"] += 1
+    _lib.check(L.tomo_contact_hist(*head, _p(values), cap, _p(keys), _p(row_of_slot), _p(z_lo), _p(top), _p(offset), rows, _p(hist),
+                                   entries, _p(where), _p(counters), st), "tomo_contact_hist")
+    tab = torch.from_numpy(F).to(dev)
+    out = torch.empty(rows * CONTACT_COLUMNS + 2, dtype=torch.int64, device=dev)
+    COUNTERS["contact_launches"] += 1
+    _lib.check(L.tomo_contact_finish(rows, _p(slot_of_row), cap, _p(keys), _p(total), _p(z_lo), _p(z_hi), _p(first), _p(top), _p(path),
+                                     _p(where), _p(offset), _p(hist), entries, _p(tab), nz, directions, _p(out), _p(counters), st),
+               "tomo_contact_finish")
+    out[rows * CONTACT_COLUMNS:] = counters
+    host = out.cpu().numpy()
+    t = host[:rows * CONTACT_COLUMNS].reshape(rows, CONTACT_COLUMNS)
+    counts = t[:, 3:10]
+    if host[-1] or host[-2] or not np.array_equal(counts.sum(axis=1), t[:, 2]):
+        raise _lib.TomoError("zone_contacts: the three passes disagree about the contact pairs (internal error: %d pairs without a "
+                             "row)" % int(host[-1]))
+    if connectivity == 6:                                              # a contact needs a shared face: x, y or z
+        t = t[(counts[:, 0] + counts[:, 1] + counts[:, 3]) > 0]
+
+    def index(flat):
+        return np.stack(np.unravel_index(flat, (nz, ny, nx)), axis=1).astype(np.int64).reshape(-1, 3)
+
+    def f32(col):
+        return np.ascontiguousarray(t[:, col]).astype(np.uint32).view(np.float32)
+
+    return ZoneContacts(t[:, 0].copy(), t[:, 1].copy(), t[:, 2].copy(), np.ascontiguousarray(t[:, 3:10]),
+                        np.ascontiguousarray(t[:, 10]).view(np.float64), np.ascontiguousarray(t[:, 11:13]), index(t[:, 13]),
+                        None if values is None else f32(14), None if values is None else index(t[:, 15]),
+                        None if dist is None else f32(16))
+
+
+def zone_contacts(vol: BitVolume, zones: torch.Tensor, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, connectivity=26,
+                  directions=13, values=None, dist=None) -> ZoneContacts:
+    """The contact table between zones -> ZoneContacts, one row per pair of zones that touch, sorted by (zone_a, zone_b): the
+    edges that belong to the nodes a separation yields.  zones: geodesic_zones' map or any int32 device tensor of the volume's
+    shape.  A voxel takes part when it is set and its entry is positive.  A contact pair is an unordered pair of 26-adjacent
+    voxels that take part and lie in different zones, counted once at its raster-earlier voxel p, in the slice of p and in one
+    of surface_area's seven direction classes.  Per zone pair (a, b) = (min, max) of the two labels:
+    pairs / pair_counts  the contact pairs, and per class;  z_range the lowest and highest slice;  first_index the first p
+    area_mm2     the Crofton estimate of the interface: the sequential float64 sum over the slices in ascending z and the
+                 classes in ascending order of count * surface_factors(...)[k][class] -- one adjacent pair of unlike voxels is
+                 one crossing of the interface by a lattice line, so the factor is surface_area's (columns 3 .. 6: towards slice
+                 k + 1); directions=3 uses x, y and z only.  A flat interface is underestimated as surface_area's flat faces are.
+    value_max    with values (a float32 device map, NaN-free): the largest value over the voxels of the zone pair's contact
+                 pairs, value_index the first voxel that attains it.  values=distance_transform(vol) gives the throat: the
+                 radius of the largest ball centred on the interface that fits in the object.
+    path_mm      with dist (geodesic_zones' second result): the minimum over the contact pairs of fl32(fl32(dist(p) + w) +
+                 dist(q)), w the float32 step of geodesic_weights -- the shortest way from a marker of one zone to a marker of
+                 the other that crosses the interface there; +inf where no pair is finite.
+    connectivity does not change what is counted; it says which rows are contacts: 26 every zone pair with a contact pair, 6
+    those that share a face (pair_counts of x, y or z positive) -- the rows are filtered after the download and hold the same bytes.
+    On the device: tomo_contact_count gives the contact pairs N (none: the empty table, one launch); tomo_contact_insert fills
+    an open-addressed hash table of at least 2 N slots, a power of two, within CONTACT_TABLE_BUDGET bytes (44 a slot) -- a table
+    that would need more is allocated at the cap, and if it then overflows the call raises TomoError, it never returns a short
+    table; the rows are sorted and laid out in torch (P rows, never voxels; one host read); tomo_contact_hist counts per slice
+    and class (56 bytes a slice entry; beyond COMPONENT_HIST_BUDGET: TomoError before the allocation); tomo_contact_finish sums.
+    Integer atomics only: the same bytes on every run.  Arguments are checked before the first launch; the inputs are left
+    untouched.  The pore network of the closed pores is the same call on the zones of cavity_volume(vol)."""
+    return _zone_contacts(vol, _contact_args(vol, zones, slice_depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, directions,
+                                             values, dist))
+
+
+def separate_with_contacts(vol: BitVolume, radius_mm, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, connectivity=6,
+                           min_marker_voxels=1, directions=13):
+    """separate_components and the contact table of its zones -> (Separation, ZoneContacts): the separation as
+    separate_components makes it, then zone_contacts of the zones the call already holds under the same spacing and
+    connectivity, with values=distance_transform(vol, ...) -- value_max is the throat radius -- and dist = the zones' distance
+    map, so path_mm is the way from core to core.  separate_with_contacts(cavity_volume(vol), ...) is the pore network of the
+    closed pores: pore bodies, throats and the ways between them."""
+    args = _separation_args(vol.shape, radius_mm, slice_depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_marker_voxels)
+    surface_factors(slice_depths, vol.shape[0], mm_per_pixel_y, mm_per_pixel_x, directions)          # the argument check
+    sep, dist = _separate(vol, args, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    inside = distance_transform(vol, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    return sep, _zone_contacts(vol, _contact_args(vol, sep.zones, slice_depths, mm_per_pixel_y, mm_per_pixel_x, args[2], directions,
+                                                  inside, dist))
 
 
 def local_thickness(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, radii_mm=None,

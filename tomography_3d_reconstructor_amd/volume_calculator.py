@@ -247,6 +247,32 @@ def separate_grains(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, ra
             'markers': sep.markers, 'cut_voxels': sep.cut_voxels, 'cut_share': sep.cut_voxels / solid if solid else 0.0}
 
 
+def grain_contacts(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, radius_mm, connectivity=6, min_marker_voxels=1):
+    """Which grains touch, and how (no counterpart in the reference): pipeline.separate_with_contacts -- the separation of
+    separate_grains, then the contact table of its zones -> {'grains' (the markers), 'contacts' (zone pairs in contact under
+    `connectivity`), 'mean_coordination' (contacts per grain, 0.0 without grains), 'coordination' (a list, the neighbours of marker
+    label 1 .. n), 'table': one dict per contact, sorted by its zones: {'zones' (a, b), 'contact_voxel_pairs',
+    'contact_area_mm2' (the Crofton estimate of the interface), 'throat_diameter_mm' (twice the largest inside distance on the
+    interface), 'throat_index' ((z, y, x) of the voxel that attains it), 'path_mm' (the shortest way from core to core across
+    the interface), 'at_index' ((z, y, x) of the first voxel of the interface)}}.  The pore network of the closed pores is the
+    same call on the pore space -- pipeline.separate_with_contacts(pipeline.cavity_volume(vol), ...) on a resident volume: pore
+    bodies, throats and ways; there is no second wrapper.
+    voxel_data: the bool (nz, ny, nx) array the other calculations take; anything else is a TypeError."""
+    if not _on_device(voxel_data):
+        raise TypeError("grain_contacts needs a bool (nz, ny, nx) array")
+    depths = np.asarray(slice_depths, dtype=np.float64).reshape(-1)
+    pipeline._separation_args(voxel_data.shape, radius_mm, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_marker_voxels)
+    vol = to_device_volume(voxel_data)
+    sep, c = pipeline.separate_with_contacts(vol, radius_mm, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_marker_voxels)
+    _, neighbours, _ = c.coordination(np.arange(1, sep.markers + 1))
+    table = [{'zones': (int(c.zone_a[i]), int(c.zone_b[i])), 'contact_voxel_pairs': int(c.pairs[i]),
+              'contact_area_mm2': float(c.area_mm2[i]), 'throat_diameter_mm': 2.0 * float(c.value_max[i]),
+              'throat_index': tuple(int(a) for a in c.value_index[i]), 'path_mm': float(c.path_mm[i]),
+              'at_index': tuple(int(a) for a in c.first_index[i])} for i in range(len(c))]
+    return {'grains': sep.markers, 'contacts': len(c), 'mean_coordination': float(neighbours.sum()) / sep.markers if sep.markers else 0.0,
+            'coordination': neighbours.tolist(), 'table': table}
+
+
 def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=6, min_voxels=0, largest=False,
                          shape=False, topology=False, surface=False, surface_directions=13, porosity=False, thickness=False,
                          thickness_radii_mm=None, geodesic=False, geodesic_sweeps=3, separate_mm=None, caliper=False,
