@@ -513,6 +513,52 @@ int tomo_zone_sweep(const uint64_t *bits, int nz, int ny, int nx, int connectivi
                     void *stream);
 int tomo_zone_cut(const uint64_t *bits, const int32_t *zone, int nz, int ny, int nx, int connectivity, uint64_t *out,
                   unsigned long long *counter, void *stream);
+/* Greyscale morphological reconstruction by dilation inside the set voxels (csrc/reconstruct.hip; no counterpart in the
+ * reference): a map that rises under a ceiling, the primitive behind h-maxima, regional and extended maxima.  Tiles, dirty
+ * arrays and the adjacency (6 or 26 between two SET voxels) are those of tomo_geo_sweep.
+ * mask: float32 (nz, ny, nx), the ceiling f.  marker: float32 of the same shape.  Unset voxels and everything outside the stack
+ * take no part: they are never read as neighbours, their mask and marker entries are not read at all, and g holds 0.0 there.
+ * Order.  Values are ordered as float32 orders them, -0.0 is read as +0.0 (and written as +0.0), NaN on a set voxel is an
+ * error.  The kernels compare an order-preserving uint32 key of the bit pattern -- 0x80000000 + magnitude for a positive
+ * value, 0x80000000 - magnitude for a negative one -- never the floats, so no float mode or denormal setting matters.  The
+ * keys of -inf .. +inf are consecutive integers: "the float just below v" is the value of key(v) - 1 (below +0.0 lies the
+ * smallest negative denormal); nothing lies below -inf.
+ * Reconstruction, one definition.  m' = min(marker, f).  g is the least fixed point above m' of
+ *     g(p) = max(m'(p), min(f(p), max over the set neighbours q of g(q))).
+ * The operator only takes minima and maxima of values already present: it is monotone, and values only rise, through the
+ * finite set of the inputs.  Every order of updates, every tiling and every race between tiles therefore ends at the same
+ * bytes.  It is the argument of tomo_geo_sweep turned round: a neighbouring tile may read an interior while it is written and
+ * gets the old or the new value (aligned 32-bit accesses do not tear); a stale value is a valid LOWER bound of the fixed
+ * point, and the writer marks the reader for the next sweep.
+ * h-maxima: HMAX_h(f) = the reconstruction of fl32(f - h) under f, one float32 subtraction per voxel, h > 0 finite.  Regional
+ * maxima: RMAX(f) = the set voxels with reconstruction(f, the float just below f) < f -- the plateau definition: a connected
+ * set of equal values with no higher set neighbour (a plateau at -inf is not reported).  Extended maxima: RMAX(HMAX_h(f)).
+ *   tomo_recon_seed   one pass over the volume: g = min(marker, f) on a set voxel, 0.0 on an unset one.  mode 0 reads `marker`;
+ *                     mode 1 takes fl32(f - h) and mode 2 the float just below f (marker may be NULL in both; h is read in
+ *                     mode 1 only).  counters[1] |= 8 when the mask or the marker of a set voxel is NaN (the caller raises
+ *                     and discards g), |= 16 when some set voxel starts below its ceiling -- without that bit g is final
+ *                     and no sweep is needed.  One atomic per wave at most, and none once the bits are up.
+ *   tomo_recon_sweep  one sweep, shaped like tomo_zone_sweep: one workgroup of 256 per tile, gone at once when its flag in
+ *                     dirty_cur is clear; otherwise it clears the flag.  A thread holds the ceiling and g of its 16 voxels in
+ *                     registers (only the owner reads a ceiling); a tile whose voxels all sit at their ceiling returns there.
+ *                     g with a one-voxel halo goes into LDS as keys (unset voxels and outside: key 0, below every value), and
+ *                     the interior is raised against the fixed halo in race-free rounds bounded by the number of interior
+ *                     voxels (a tile that hits the bound marks itself in dirty_next).  It stores the voxels that changed,
+ *                     adds 1 to counters[0] (once per workgroup that changed something) and sets dirty_next of the
+ *                     neighbouring tiles next to a changed face, edge or corner voxel (6: face neighbours only).  No atomics
+ *                     on the maps, nothing waits on another workgroup.  To start, the caller sets EVERY flag of dirty_cur
+ *                     once: a tile without work changes nothing and marks nobody.  The caller swaps the arrays between
+ *                     sweeps and stops at a batch that left counters[0] unchanged, as for tomo_geo_sweep.
+ *   tomo_recon_below  out = the set voxels with g < mask (by the keys) as a bit volume; a wave is one word, tail bits zero
+ * counters: unsigned long long[2], zeroed by the caller.  TOMO_E_ARG for a null pointer (marker in modes 1 and 2 excepted), a
+ * non-positive size, a mode other than 0 .. 2, an h that is not positive and finite in mode 1, a connectivity other than
+ * 6 / 26, dirty_cur == dirty_next, g == mask, g == marker, g == bits, out == bits, out == mask or out == g; TOMO_E_SIZE from
+ * 2^31 tiles or words on.  All of it is decided before any device use. */
+int tomo_recon_seed(const uint64_t *bits, const float *mask, const float *marker, int mode, float h, int nz, int ny, int nx,
+                    float *g, unsigned long long *counters, void *stream);
+int tomo_recon_sweep(const uint64_t *bits, int nz, int ny, int nx, int connectivity, const float *mask, float *g,
+                     uint32_t *dirty_cur, uint32_t *dirty_next, unsigned long long *counters, void *stream);
+int tomo_recon_below(const uint64_t *bits, const float *mask, const float *g, int nz, int ny, int nx, uint64_t *out, void *stream);
 /* The contact table between zones (csrc/contacts.hip; no counterpart in the reference): which zones touch, over how large an
  * interface, how wide the throat between them is and how long the way across.  One definition.
  * zones: int32 (nz, ny, nx), tomo_zone_sweep's map or any map.  A voxel TAKES PART when it is set and its entry is positive.

@@ -113,6 +113,9 @@ SIGNATURES = {
     "tomo_zone_seed_labels": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p]),
     "tomo_zone_sweep": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
     "tomo_zone_cut": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p]),
+    "tomo_recon_seed": (_c_i, [_c_p, _c_p, _c_p, _c_i, _c_f, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p]),
+    "tomo_recon_sweep": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
+    "tomo_recon_below": (_c_i, [_c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_p, _c_p]),
     "tomo_contact_count": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_p, _c_p]),
     "tomo_contact_insert": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
                                    _c_p, _c_p]),

@@ -27,7 +27,7 @@ COUNTERS = dict.fromkeys(("na_hint_hit", "na_hint_miss", "mc3_hint_hit", "mc3_hi
                           "components_cavities", "local_thickness", "opening_volume", "components_surface", "components_fill",
                           "components_cavity_owners", "component_thickness", "components_value", "components_levels", "component_caliper",
                           "geodesic_calls", "geodesic_sweeps", "component_geodesic", "zone_calls", "zone_sweeps", "zone_cuts",
-                          "separate_components", "zone_contacts", "contact_launches"), 0)
+                          "separate_components", "zone_contacts", "contact_launches", "recon_calls", "recon_sweeps"), 0)
 NA_HINTS = os.environ.get("TOMO_NA_HINTS", "1") not in ("", "0")   # marching_cubes: launch ahead of the first count download
 _NA_HINT = {}
 LIST_LIMIT = 2 ** 31        # active-voxel list entries / vertices / triangles one pass can index (int32 offsets in mc.hip, mesh.hip);
@@ -1705,9 +1705,10 @@ def _geodesic_search_sweeps(sweeps) -> int:
 
 
 class _GeodesicPlan:
-    """What the sweeps of one geodesic call share: the bits, the weights on the device, the two dirty arrays and the counters."""
+    """What the sweeps of one geodesic call share: the bits, the weights on the device, the two dirty arrays and the counters.
+    tables=None: a plan without weights, for the sweeps that read none (propagate_reconstruction)."""
 
-    def __init__(self, vol: BitVolume, tables: _GeodesicTables, connectivity):
+    def __init__(self, vol: BitVolume, tables, connectivity):
         nz, ny, nx = vol.shape
         nbytes = 4 * nz * ny * nx
         if nbytes > GEODESIC_VOLUME_BUDGET:                              # read when called, before anything is allocated
@@ -1719,8 +1720,9 @@ class _GeodesicPlan:
             raise _lib.TomoError("tomo_geo_tiles failed (%d)" % self.tiles)
         dev = vol.device
         self.vol, self.bits, self.connectivity = vol, vol.bits.contiguous(), int(connectivity)
-        w = torch.from_numpy(np.concatenate([tables.wxy, tables.wz.reshape(-1)])).to(dev)
-        self.w, self.wxy, self.wz = w, w[:3], w[3:]
+        if tables is not None:
+            w = torch.from_numpy(np.concatenate([tables.wxy, tables.wz.reshape(-1)])).to(dev)
+            self.w, self.wxy, self.wz = w, w[:3], w[3:]
         self.dirty = torch.zeros((2, self.tiles), dtype=torch.int32, device=dev)
         self.counters = torch.zeros(2, dtype=torch.int64, device=dev)
         self.cur = 0                                                     # the dirty array the next sweep reads
@@ -1773,6 +1775,19 @@ class _GeodesicPlan:
             _lib.check(L.tomo_zone_sweep(_p(self.bits), nz, ny, nx, self.connectivity, _p(self.wxy), _p(self.wz), _p(dist), _p(zone),
                                          cur, nxt, _p(self.counters), st), "tomo_zone_sweep")
         return self._sweeps(sweep, "geodesic zones", "zone_sweeps")
+
+    def propagate_reconstruction(self, mask: torch.Tensor, g: torch.Tensor) -> int:
+        """The sweeps of a grey reconstruction over tomo_recon_seed's g -> the sweeps launched.  It starts with every flag set, as
+        propagate_zones does.  Values only rise through the finite set of the inputs, so it ends; the loop and its guard are
+        propagate()'s."""
+        L, st = _lib.lib(), _stream()
+        nz, ny, nx = self.vol.shape
+        self.dirty[self.cur].fill_(1)
+
+        def sweep(cur, nxt):
+            _lib.check(L.tomo_recon_sweep(_p(self.bits), nz, ny, nx, self.connectivity, _p(mask), _p(g), cur, nxt, _p(self.counters), st),
+                       "tomo_recon_sweep")
+        return self._sweeps(sweep, "reconstruction", "recon_sweeps")
 
 
 def _geodesic_seeds(shape, seeds):
@@ -2048,19 +2063,25 @@ def separate_components(vol: BitVolume, radius_mm, slice_depths=None, mm_per_pix
     Separation.volume is a plain BitVolume: volume, box, moments, Euler number, surface, thickness, caliper and geodesic length
     per component apply to the separated objects unchanged (ComponentRuns(sep.volume, connectivity)).  An object thinner than
     the radius everywhere has no marker and stays whole.  A fixed radius over-segments elongated or lobed objects: a grain
-    whose erosion falls into two cores is cut in two.  For another marker rule build the markers yourself and hand the map to
-    geodesic_zones and split_zones.  separate_components(cavity_volume(vol), ...) separates pore bodies at their throats.
-    Arguments are checked before the first launch.  separate_with_contacts returns the contact table of the zones as well."""
+    whose erosion falls into two cores is cut in two, and no single radius suits grains of different sizes: separate_by_height
+    takes its markers from the h-maxima of the distance map instead.  For another marker rule build the markers yourself and
+    hand the map to geodesic_zones and split_zones.  separate_components(cavity_volume(vol), ...) separates pore bodies at
+    their throats.  Arguments are checked before the first launch.  separate_with_contacts returns the contact table of the zones as well."""
     args = _separation_args(vol.shape, radius_mm, slice_depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_marker_voxels)
-    return _separate(vol, args, slice_depths, mm_per_pixel_y, mm_per_pixel_x)[0]
+    return _separate_by_radius(vol, args, slice_depths, mm_per_pixel_y, mm_per_pixel_x)[0]
 
 
-def _separate(vol: BitVolume, args, slice_depths, mm_per_pixel_y, mm_per_pixel_x):
-    """The separation itself -> (Separation, the zones' distance map)."""
+def _separate_by_radius(vol: BitVolume, args, slice_depths, mm_per_pixel_y, mm_per_pixel_x):
     r, tables, connectivity, least = args
+    return _separate(vol, lambda: offset_volume(vol, -r, slice_depths, mm_per_pixel_y, mm_per_pixel_x), tables, connectivity, least)
+
+
+def _separate(vol: BitVolume, marker_rule, tables: _GeodesicTables, connectivity, least):
+    """The separation itself -> (Separation, the zones' distance map).  marker_rule() -> the marker BitVolume: the one thing in
+    which separate_components and separate_by_height differ."""
     _zone_budget(vol.shape)
     COUNTERS["separate_components"] += 1
-    markers = offset_volume(vol, -r, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    markers = marker_rule()
     if least > 1:
         markers = keep_components(markers, least, False, connectivity)
     zone, dist, sweeps, count = _geodesic_zones(vol, ("bits", markers), tables, connectivity)
@@ -2279,10 +2300,179 @@ def separate_with_contacts(vol: BitVolume, radius_mm, slice_depths=None, mm_per_
     closed pores: pore bodies, throats and the ways between them."""
     args = _separation_args(vol.shape, radius_mm, slice_depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_marker_voxels)
     surface_factors(slice_depths, vol.shape[0], mm_per_pixel_y, mm_per_pixel_x, directions)          # the argument check
-    sep, dist = _separate(vol, args, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    sep, dist = _separate_by_radius(vol, args, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    return sep, _separation_contacts(vol, sep, dist, slice_depths, mm_per_pixel_y, mm_per_pixel_x, args[2], directions)
+
+
+def _separation_contacts(vol: BitVolume, sep: Separation, dist, slice_depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, directions):
+    """The contact table of a separation's zones: the throat from the inside distance, the way from the zones' distance map."""
     inside = distance_transform(vol, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
-    return sep, _zone_contacts(vol, _contact_args(vol, sep.zones, slice_depths, mm_per_pixel_y, mm_per_pixel_x, args[2], directions,
-                                                  inside, dist))
+    return _zone_contacts(vol, _contact_args(vol, sep.zones, slice_depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, directions,
+                                             inside, dist))
+
+
+# ----------------------------------------------------------------------------- grey reconstruction, h-maxima, separation by height
+RECON_F_NAN = 8                      # counters[1] of tomo_recon_seed: NaN on a set voxel
+RECON_F_WORK = 16                    # ... some set voxel starts below its ceiling: without it the seeded map is final
+
+
+def _recon_map(vol: BitVolume, m, what) -> torch.Tensor:
+    if m is None:
+        raise TypeError("%s must be a float32 tensor (nz, ny, nx)" % what)
+    return _contact_values(vol, m, what)
+
+
+def _recon_height(h, what="h") -> float:
+    """h as the device subtracts it: rounded once to float32, positive and finite there."""
+    if isinstance(h, (bool, np.bool_)) or not isinstance(h, (int, float, np.integer, np.floating)):
+        raise ValueError("%s must be positive and finite" % what)
+    with np.errstate(over="ignore"):
+        h32 = np.float32(h)
+    if not (np.isfinite(h32) and h32 > 0):
+        raise ValueError("%s must be positive and finite as a float32" % what)
+    return float(h32)
+
+
+def _recon_budget(shape, maps, what):
+    """Before anything is allocated: the call holds `maps` float32 maps at once, the caller's included."""
+    nz, ny, nx = shape
+    nbytes = 4 * maps * nz * ny * nx
+    if nbytes > GEODESIC_VOLUME_BUDGET:
+        raise _lib.TomoError("%s: %d float32 maps of %d x %d x %d voxels take %d bytes, more than GEODESIC_VOLUME_BUDGET (%d)"
+                             % (what, maps, nz, ny, nx, nbytes, GEODESIC_VOLUME_BUDGET))
+
+
+def _reconstruct(vol: BitVolume, mask: torch.Tensor, marker, mode, h, connectivity, what) -> torch.Tensor:
+    """Seed and sweep -> g.  mode: tomo_recon_seed's (0 the marker map, 1 mask - h, 2 the float just below the mask)."""
+    L, st = _lib.lib(), _stream()
+    nz, ny, nx = vol.shape
+    plan = _GeodesicPlan(vol, None, connectivity)
+    COUNTERS["recon_calls"] += 1
+    mask = mask.contiguous()
+    marker = None if marker is None else marker.contiguous()
+    g = torch.empty(vol.shape, dtype=torch.float32, device=vol.device)
+    _lib.check(L.tomo_recon_seed(_p(plan.bits), _p(mask), _p(marker), mode, h, nz, ny, nx, _p(g), _p(plan.counters), st), "tomo_recon_seed")
+    flags = int(_download(plan.counters)[1])
+    if flags & RECON_F_NAN:
+        raise ValueError("%s: NaN on a set voxel" % what)
+    if flags & RECON_F_WORK:                                             # an empty volume, or a marker at the ceiling everywhere: no sweep
+        plan.propagate_reconstruction(mask, g)
+    return g
+
+
+def reconstruct(vol: BitVolume, mask: torch.Tensor, marker: torch.Tensor, connectivity=26) -> torch.Tensor:
+    """Greyscale morphological reconstruction by dilation of `marker` under `mask` inside the set voxels of a resident volume ->
+    float32 (nz, ny, nx) device tensor g: the least fixed point above m' = min(marker, mask) of
+        g(p) = max(m'(p), min(mask(p), max over the set neighbours q of g(q))),
+    neighbours under `connectivity` (6 or 26 between two SET voxels, label_components' adjacency).  Every dome of the mask that
+    holds no marker value of its own is cut down to the level at which it is reached from outside.  mask, marker: float32 device
+    tensors of the volume's shape; unset voxels take no part -- their entries are not read, NaN included -- and g holds 0.0
+    there.  Values are ordered as float32 orders them, -0.0 counts as +0.0 and comes back as +0.0; NaN on a set voxel: ValueError.
+    On the device: tomo_recon_seed writes m', then tomo_recon_sweep raises 8 x 8 x 64 tiles in LDS, sweep after sweep, in
+    geodesic_distance's host loop (GEODESIC_SWEEP_BATCH sweeps between two counter reads, more than GEODESIC_SWEEP_LIMIT:
+    TomoError).  The operator takes minima and maxima only, so it is monotone and every order of tiles ends at the same bytes.
+    A plateau needs one sweep per tile it crosses.  The call holds three maps (mask, marker, g); more than
+    GEODESIC_VOLUME_BUDGET bytes: TomoError before anything is allocated.  An empty volume, or a marker that is nowhere below
+    the mask, launches no sweep.  Arguments are checked before the first launch; the inputs are left untouched."""
+    connectivity = _check_connectivity(connectivity)
+    mask, marker = _recon_map(vol, mask, "mask"), _recon_map(vol, marker, "marker")
+    _recon_budget(vol.shape, 3, "reconstruct")
+    return _reconstruct(vol, mask, marker, 0, 0.0, connectivity, "reconstruct")
+
+
+def h_maxima(vol: BitVolume, values: torch.Tensor, h, connectivity=26) -> torch.Tensor:
+    """The h-maxima transform HMAX_h(values) = reconstruct(vol, values, fl32(values - h)) -> float32 device tensor: every dome of
+    the map is cut down by h, or to its saddle when it stands less than h above it.  h: positive and finite as a float32 (else
+    ValueError); the subtraction is one float32 operation per voxel, made by the seeding pass, so no marker map is allocated:
+    the call holds two maps."""
+    connectivity = _check_connectivity(connectivity)
+    values, h = _recon_map(vol, values, "values"), _recon_height(h)
+    _recon_budget(vol.shape, 2, "h_maxima")
+    return _reconstruct(vol, values, None, 1, h, connectivity, "h_maxima")
+
+
+def _regional_maxima(vol: BitVolume, values: torch.Tensor, connectivity, what) -> BitVolume:
+    values = values.contiguous()
+    g = _reconstruct(vol, values, None, 2, 0.0, connectivity, what)
+    bits = vol.bits.contiguous()
+    out = torch.empty_like(bits)
+    _lib.check(_lib.lib().tomo_recon_below(_p(bits), _p(values), _p(g), *vol.shape, _p(out), _stream()), "tomo_recon_below")
+    return BitVolume(out, vol.shape)
+
+
+def regional_maxima(vol: BitVolume, values: torch.Tensor, connectivity=26) -> BitVolume:
+    """The regional maxima of a float32 map inside the set voxels -> a NEW BitVolume: the plateaus -- connected sets of equal
+    values under `connectivity` -- with no higher set neighbour.  Computed as the set voxels with reconstruct(values, the float
+    just below values) < values: a plateau with a higher neighbour is filled back to its own value, a maximum stays one float
+    below.  A plateau at -inf has nothing below it and is not reported.  The call holds two maps (8 bytes a voxel against
+    GEODESIC_VOLUME_BUDGET)."""
+    connectivity = _check_connectivity(connectivity)
+    values = _recon_map(vol, values, "values")
+    _recon_budget(vol.shape, 2, "regional_maxima")
+    return _regional_maxima(vol, values, connectivity, "regional_maxima")
+
+
+def extended_maxima(vol: BitVolume, values: torch.Tensor, h, connectivity=26) -> BitVolume:
+    """EMAX_h(values) = regional_maxima(h_maxima(values, h)) -> a NEW BitVolume: one connected marker on every dome of the map
+    that stands at least h above its saddle (MorphoLibJ's extended maxima).  On a distance map the markers of grains of any
+    size, while surface roughness below h makes none.  The call holds the caller's map and two more (12 bytes a voxel against
+    GEODESIC_VOLUME_BUDGET, checked before anything is allocated); the h-maxima map is freed before the call returns."""
+    connectivity = _check_connectivity(connectivity)
+    values, h = _recon_map(vol, values, "values"), _recon_height(h)
+    _recon_budget(vol.shape, 3, "extended_maxima")
+    domes = _reconstruct(vol, values, None, 1, h, connectivity, "extended_maxima")
+    out = _regional_maxima(vol, domes, connectivity, "extended_maxima")
+    del domes
+    return out
+
+
+def _height_args(shape, h_mm, slice_depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_marker_voxels, min_radius_mm):
+    """The argument checks of separate_by_height, all on the host -> (h, tables, connectivity, min_marker_voxels, min_radius)."""
+    h = _recon_height(h_mm, "h_mm")
+    connectivity = _check_connectivity(connectivity)
+    tables = _geodesic_tables(shape, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    least = _whole_size(min_marker_voxels, "min_marker_voxels")
+    if isinstance(min_radius_mm, (bool, np.bool_)) or not isinstance(min_radius_mm, (int, float, np.integer, np.floating)) or \
+            not (math.isfinite(min_radius_mm) and min_radius_mm >= 0):
+        raise ValueError("min_radius_mm must be non-negative and finite")
+    return h, tables, connectivity, least, float(min_radius_mm)
+
+
+def _separate_by_height(vol: BitVolume, args, slice_depths, mm_per_pixel_y, mm_per_pixel_x):
+    h, tables, connectivity, least, least_radius = args
+    spacing = (slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+
+    def markers():
+        domes = extended_maxima(vol, distance_transform(vol, *spacing), h, connectivity)
+        if least_radius > 0:                                             # domes of thin debris go
+            domes = BitVolume(domes.bits & offset_volume(vol, -least_radius, *spacing).bits, vol.shape)
+        return domes
+    return _separate(vol, markers, tables, connectivity, least)
+
+
+def separate_by_height(vol: BitVolume, h_mm, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, connectivity=6,
+                       min_marker_voxels=1, min_radius_mm=0.0) -> Separation:
+    """separate_components with h-maxima markers -> Separation: the markers are extended_maxima(vol, distance_transform(vol,
+    ...), h_mm, connectivity) -- one marker on every dome of the inside distance that stands at least h_mm above its saddle,
+    the rule of MorphoLibJ's distance-transform watershed.  A large and a small pair of touching grains are split by the same
+    h_mm, where no single erosion radius finds both, and roughness below h_mm makes no marker.  min_radius_mm > 0: the markers
+    are ANDed with offset_volume(vol, -min_radius_mm, ...), so the domes of debris thinner than that go.  Markers of fewer than
+    min_marker_voxels voxels are dropped; zones and cut are separate_components'.  h_mm must be positive and finite as a
+    float32, min_radius_mm non-negative and finite (ValueError).  While the markers are made the call holds three float32 maps
+    (the distance, its h-maxima, the reconstruction), freed before the zones take their three.  Arguments are checked before
+    the first launch.  separate_by_height_with_contacts returns the contact table as well."""
+    args = _height_args(vol.shape, h_mm, slice_depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_marker_voxels, min_radius_mm)
+    return _separate_by_height(vol, args, slice_depths, mm_per_pixel_y, mm_per_pixel_x)[0]
+
+
+def separate_by_height_with_contacts(vol: BitVolume, h_mm, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, connectivity=6,
+                                     min_marker_voxels=1, min_radius_mm=0.0, directions=13):
+    """separate_by_height and the contact table of its zones -> (Separation, ZoneContacts), as separate_with_contacts returns
+    them for the fixed radius: value_max is the throat radius, path_mm the way from marker to marker."""
+    args = _height_args(vol.shape, h_mm, slice_depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_marker_voxels, min_radius_mm)
+    surface_factors(slice_depths, vol.shape[0], mm_per_pixel_y, mm_per_pixel_x, directions)          # the argument check
+    sep, dist = _separate_by_height(vol, args, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    return sep, _separation_contacts(vol, sep, dist, slice_depths, mm_per_pixel_y, mm_per_pixel_x, args[2], directions)
 
 
 def local_thickness(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, radii_mm=None,

@@ -238,13 +238,33 @@ def separate_grains(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, ra
         raise TypeError("separate_grains needs a bool (nz, ny, nx) array")
     depths = np.asarray(slice_depths, dtype=np.float64).reshape(-1)
     pipeline._separation_args(voxel_data.shape, radius_mm, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_marker_voxels)
-    vol = to_device_volume(voxel_data)
+    return _separation_report(to_device_volume(voxel_data), connectivity, lambda vol: pipeline.separate_components(
+        vol, radius_mm, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_marker_voxels))
+
+
+def _separation_report(vol, connectivity, separate):
+    """separate_grains' dict for separate(vol) -> pipeline.Separation."""
     before = int(pipeline.ComponentRuns(vol, connectivity).sizes().shape[0])
     solid = int(pipeline.popcount_async(vol).item())
-    sep = pipeline.separate_components(vol, radius_mm, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_marker_voxels)
+    sep = separate(vol)
     after = int(pipeline.ComponentRuns(sep.volume, connectivity).sizes().shape[0])
     return {'volume': pipeline.unpack(sep.volume).cpu().numpy(), 'components_before': before, 'components_after': after,
             'markers': sep.markers, 'cut_voxels': sep.cut_voxels, 'cut_share': sep.cut_voxels / solid if solid else 0.0}
+
+
+def separate_grains_by_height(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, h_mm, connectivity=6, min_marker_voxels=1,
+                              min_radius_mm=0.0):
+    """separate_grains with h-maxima markers (no counterpart in the reference): pipeline.separate_by_height -- one marker on every
+    dome of the inside distance that stands at least h_mm millimetres above its saddle, so grains of different sizes are split
+    by one parameter and surface roughness below h_mm splits nothing; min_radius_mm > 0 drops the markers of debris thinner
+    than that -> the dict of separate_grains.  component_properties(..., separate_h_mm=h_mm) measures the separated grains.
+    voxel_data: the bool (nz, ny, nx) array the other calculations take; anything else is a TypeError."""
+    if not _on_device(voxel_data):
+        raise TypeError("separate_grains_by_height needs a bool (nz, ny, nx) array")
+    depths = np.asarray(slice_depths, dtype=np.float64).reshape(-1)
+    pipeline._height_args(voxel_data.shape, h_mm, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_marker_voxels, min_radius_mm)
+    return _separation_report(to_device_volume(voxel_data), connectivity, lambda vol: pipeline.separate_by_height(
+        vol, h_mm, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_marker_voxels, min_radius_mm))
 
 
 def grain_contacts(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, radius_mm, connectivity=6, min_marker_voxels=1):
@@ -263,7 +283,12 @@ def grain_contacts(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, rad
     depths = np.asarray(slice_depths, dtype=np.float64).reshape(-1)
     pipeline._separation_args(voxel_data.shape, radius_mm, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_marker_voxels)
     vol = to_device_volume(voxel_data)
-    sep, c = pipeline.separate_with_contacts(vol, radius_mm, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_marker_voxels)
+    return _contact_report(*pipeline.separate_with_contacts(vol, radius_mm, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity,
+                                                            min_marker_voxels))
+
+
+def _contact_report(sep, c):
+    """grain_contacts' dict for a pipeline.Separation and the pipeline.ZoneContacts of its zones."""
     _, neighbours, _ = c.coordination(np.arange(1, sep.markers + 1))
     table = [{'zones': (int(c.zone_a[i]), int(c.zone_b[i])), 'contact_voxel_pairs': int(c.pairs[i]),
               'contact_area_mm2': float(c.area_mm2[i]), 'throat_diameter_mm': 2.0 * float(c.value_max[i]),
@@ -273,9 +298,24 @@ def grain_contacts(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, rad
             'coordination': neighbours.tolist(), 'table': table}
 
 
+def grain_contacts_by_height(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, h_mm, connectivity=6, min_marker_voxels=1,
+                             min_radius_mm=0.0):
+    """grain_contacts for the separation of separate_grains_by_height (no counterpart in the reference):
+    pipeline.separate_by_height_with_contacts -> the dict of grain_contacts.
+    voxel_data: the bool (nz, ny, nx) array the other calculations take; anything else is a TypeError."""
+    if not _on_device(voxel_data):
+        raise TypeError("grain_contacts_by_height needs a bool (nz, ny, nx) array")
+    depths = np.asarray(slice_depths, dtype=np.float64).reshape(-1)
+    pipeline._height_args(voxel_data.shape, h_mm, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, min_marker_voxels, min_radius_mm)
+    vol = to_device_volume(voxel_data)
+    return _contact_report(*pipeline.separate_by_height_with_contacts(vol, h_mm, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity,
+                                                                      min_marker_voxels, min_radius_mm))
+
+
 def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=6, min_voxels=0, largest=False,
                          shape=False, topology=False, surface=False, surface_directions=13, porosity=False, thickness=False,
-                         thickness_radii_mm=None, geodesic=False, geodesic_sweeps=3, separate_mm=None, caliper=False,
+                         thickness_radii_mm=None, geodesic=False, geodesic_sweeps=3, separate_mm=None, separate_h_mm=None,
+                         caliper=False,
                          caliper_directions=None, caliper_oriented=False):
     """The calculations of the class per connected component (no counterpart in the reference, which would be handed the mask
     `labels == c` once per component) -> a list of dicts, one per component with at least min_voxels voxels (largest: only the
@@ -309,7 +349,9 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
     'geodesic_ends_index' (the two ends, (z, y, x) each) and 'tortuosity', that length over the straight distance of the ends.
     separate_mm=r (a keyword; None: off, nothing new is launched): touching objects are separated first -- the uploaded volume is
     replaced by pipeline.separate_components(volume, r, ..., connectivity).volume BEFORE the one labelling, so the rows, and every
-    flag above, measure the separated grains (separate_grains returns that volume and its counts).
+    flag above, measure the separated grains (separate_grains returns that volume and its counts).  separate_h_mm=h (a keyword;
+    None: off, nothing new is launched): the same with pipeline.separate_by_height(volume, h, ..., connectivity), the h-maxima
+    markers of separate_grains_by_height; giving both separate_mm and separate_h_mm is a ValueError.
     Whatever the
     flags, the volume is uploaded and labelled ONCE, and so is its complement: one pipeline.ComponentRuns serves all the
     measurements and owns the one selection their rows come from.  Arguments are checked before the first launch.  voxel_data: a bool (nz, ny, nx) array, else a TypeError."""
@@ -327,11 +369,17 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
     if geodesic:
         pipeline._geodesic_search_sweeps(geodesic_sweeps)
         pipeline._geodesic_tables(voxel_data.shape, depths, mm_per_pixel_y, mm_per_pixel_x)
+    if separate_mm is not None and separate_h_mm is not None:
+        raise ValueError("separate_mm and separate_h_mm are two marker rules: give one of them")
     if separate_mm is not None:
         pipeline._separation_args(voxel_data.shape, separate_mm, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, 1)
+    if separate_h_mm is not None:
+        pipeline._height_args(voxel_data.shape, separate_h_mm, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity, 1, 0.0)
     vol = to_device_volume(voxel_data)
     if separate_mm is not None:
         vol = pipeline.separate_components(vol, separate_mm, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity).volume
+    if separate_h_mm is not None:
+        vol = pipeline.separate_by_height(vol, separate_h_mm, depths, mm_per_pixel_y, mm_per_pixel_x, connectivity).volume
     runs = pipeline.ComponentRuns(vol, connectivity)
     if runs.select(*rule) is None:
         return []
