@@ -559,6 +559,60 @@ int tomo_recon_seed(const uint64_t *bits, const float *mask, const float *marker
 int tomo_recon_sweep(const uint64_t *bits, int nz, int ny, int nx, int connectivity, const float *mask, float *g,
                      uint32_t *dirty_cur, uint32_t *dirty_next, unsigned long long *counters, void *stream);
 int tomo_recon_below(const uint64_t *bits, const float *mask, const float *g, int nz, int ny, int nx, uint64_t *out, void *stream);
+/* Homotopic thinning of the bit volume: the curve skeleton (csrc/thin.hip; no counterpart in the reference).  One definition.
+ * Topology.  Everything outside the stack is background.  The foreground X has connectivity n = 26 or 6, the background the
+ * complementary one.  N(p) is the picture of the 26 neighbours of p, N18 its face and edge neighbours.
+ *   T26(M)  the number of 26-connected components of M
+ *   T6(M)   the number of 6-connected components of M n N18 that contain a 6-neighbour of p
+ * p is SIMPLE under 26 when T26(X n N) == 1 and T6(~X n N) == 1, under 6 when T6(X n N) == 1 and T26(~X n N) == 1; an
+ * isolated voxel is never simple.  p is an END when exactly one of its 26 neighbours is set.
+ * Order.  One ITERATION is 48 sub-passes: the six directions in the order -z, +z, -y, +y, -x, +x (direction 0 .. 5), and
+ * inside each direction the eight subfields s = 4 (z & 1) + 2 (y & 1) + (x & 1), ascending, on the stack's own indices.
+ * Sub-pass (d, s) clears, all at once, every voxel p that is set, is no anchor, lies in subfield s, whose neighbour in
+ * direction d is clear or outside the stack, that is simple and -- with curve -- is no end; every condition is evaluated on
+ * the volume as it stood when the sub-pass began.  The result is the volume after the first iteration that cleared nothing.
+ * Sound: two voxels of one subfield are never 26-neighbours, so "all at once" equals "one after the other in any order",
+ * every single deletion is the deletion of a simple point, and components, cavities and handles are those of the input.
+ * Deterministic, and in place: a candidate reads its own row, the rows y +- 1 and z +- 1 and the side bits of the neighbouring
+ * words.  The rows y +- 1 and z +- 1 have another parity and are not written in this sub-pass; in its own row every bit it
+ * reads lies at x +- 1, the other x-parity, which has the same value before and after any concurrent aligned 64-bit store of
+ * that word.  No second buffer, nobody waits on anybody, the same bytes on every run and under every tiling.
+ * curve = 0 gives the ultimate homotopic kernel (a ball becomes one voxel, a ring a closed one-voxel curve, a shell stays a
+ * closed surface), curve = 1 the curve skeleton; curve with connectivity 6 is refused (the 26-neighbour end rule eats a
+ * 6-connected staircase from its end).  The thinning is in voxel steps: spacing and slice depths play no part in it.
+ *   tomo_thin_pass   one sub-pass (direction, subfield), in place.  anchors: a bit volume of voxels that are never cleared, or
+ *                    NULL.  One workgroup of 256 per tile of tomo_geo_tiles (8 x 8 x 64); only the rows of the subfield's
+ *                    (z & 1, y & 1) do anything, a wave is one word of such a row, a lane a bit: the candidates of a word come
+ *                    from word-wide operations, the lane cuts its 27-bit picture out of wave-uniform words and COMPUTES the
+ *                    two component counts as bit floods; the wave ballots and one lane stores word & ~ballot (tail bits zero).
+ *                    No atomics on the volume, no table.  stamp: uint32 per tile, zeroed by the caller before the first
+ *                    sub-pass of a thinning; tick: the 1-based number of the sub-pass within that thinning, ascending by one.
+ *                    A tile is visited while stamp + 48 >= tick; a wave that clears something raises (atomicMax) the stamp of
+ *                    its tile and of the neighbouring tiles next to a cleared face, edge or corner voxel to tick.  A voxel's
+ *                    verdict in a kind of sub-pass can only change when its picture changed since that kind last ran, so
+ *                    skipping changes the work and never the bytes.  The voxels cleared are added to counters[16 k], k = 0 .. 63
+ *                    (one atomic per wave that cleared some, on one of 64 addresses 128 bytes apart: the waves of a
+ *                    launch do not queue on one address); their sum is the count.
+ *   tomo_thin_nodes  ends_out = the set voxels with exactly one set 26-neighbour, junctions_out = those with three or more, as
+ *                    bit volumes (every word written, tail bits zero).  counters[0 .. 3] += voxels, ends, junctions, isolated
+ *                    voxels (no set neighbour).
+ *   tomo_thin_count  over the run tables of a labelled volume (tomo_cc_label_runs; arguments and guards as tomo_cc_value_max,
+ *                    selection as tomo_cc_value_rows): out[columns * slot[c] + column] += the set bits of `other`, a second
+ *                    bit volume of the same shape, under the x-runs of the selected component c + 1.  One thread per word: the
+ *                    popcount of other & run mask, one 64-bit atomicAdd per run with a count.  out: int64 (cap_sel, columns),
+ *                    zeroed by the caller.
+ * counters: unsigned long long[1024] / [4], zeroed by the caller.  TOMO_E_ARG for a null pointer (anchors excepted), a
+ * non-positive size, a connectivity other than 6 / 26, a direction outside 0 .. 5, a subfield outside 0 .. 7, curve with
+ * connectivity 6, anchors == bits, a tick of 0 or within 48 of 2^32, an output that is an input, a column outside
+ * 0 .. columns - 1; TOMO_E_SIZE from 2^31 words, tiles, runs, components or selected components on.  All of it is decided
+ * before any device use. */
+int tomo_thin_pass(uint64_t *bits, const uint64_t *anchors, int nz, int ny, int nx, int connectivity, int curve, int direction,
+                   int subfield, uint32_t *stamp, uint32_t tick, unsigned long long *counters, void *stream);
+int tomo_thin_nodes(const uint64_t *bits, int nz, int ny, int nx, uint64_t *ends_out, uint64_t *junctions_out,
+                    unsigned long long *counters, void *stream);
+int tomo_thin_count(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
+                    const uint32_t *rank, unsigned long long *tot, const uint64_t *other, const uint8_t *sel, const uint32_t *slot,
+                    int64_t *out, int column, int columns, int64_t cap, int64_t cap_sel, void *stream);
 /* The contact table between zones (csrc/contacts.hip; no counterpart in the reference): which zones touch, over how large an
  * interface, how wide the throat between them is and how long the way across.  One definition.
  * zones: int32 (nz, ny, nx), tomo_zone_sweep's map or any map.  A voxel TAKES PART when it is set and its entry is positive.

@@ -116,6 +116,10 @@ SIGNATURES = {
     "tomo_recon_seed": (_c_i, [_c_p, _c_p, _c_p, _c_i, _c_f, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p]),
     "tomo_recon_sweep": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
     "tomo_recon_below": (_c_i, [_c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_p, _c_p]),
+    "tomo_thin_pass": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_p, ctypes.c_uint32, _c_p, _c_p]),
+    "tomo_thin_nodes": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p]),
+    "tomo_thin_count": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i, _c_i, _c_i64, _c_i64,
+                               _c_p]),
     "tomo_contact_count": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_p, _c_p]),
     "tomo_contact_insert": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
                                    _c_p, _c_p]),

@@ -27,7 +27,8 @@ COUNTERS = dict.fromkeys(("na_hint_hit", "na_hint_miss", "mc3_hint_hit", "mc3_hi
                           "components_cavities", "local_thickness", "opening_volume", "components_surface", "components_fill",
                           "components_cavity_owners", "component_thickness", "components_value", "components_levels", "component_caliper",
                           "geodesic_calls", "geodesic_sweeps", "component_geodesic", "zone_calls", "zone_sweeps", "zone_cuts",
-                          "separate_components", "zone_contacts", "contact_launches", "recon_calls", "recon_sweeps"), 0)
+                          "separate_components", "zone_contacts", "contact_launches", "recon_calls", "recon_sweeps",
+                          "thin_calls", "thin_iterations", "thin_passes", "thin_nodes", "component_skeleton"), 0)
 NA_HINTS = os.environ.get("TOMO_NA_HINTS", "1") not in ("", "0")   # marching_cubes: launch ahead of the first count download
 _NA_HINT = {}
 LIST_LIMIT = 2 ** 31        # active-voxel list entries / vertices / triangles one pass can index (int32 offsets in mc.hip, mesh.hip);
@@ -335,7 +336,7 @@ class ComponentRuns:
     run of set bits in a row) and never per voxel.  Two host reads: the number of runs (it sizes the tables) and the
     counters after the labelling.  n = components; labels() / sizes() / keep() read the tables.
     One object serves every per-component measurement of its volume: properties(), moments(), topology_rows(), surface(),
-    thickness(), caliper() and geodesic() share the labelling, the measurement table and ONE selection, which the object owns (select).  background() is the same
+    thickness(), caliper(), geodesic() and skeleton() share the labelling, the measurement table and ONE selection, which the object owns (select).  background() is the same
     kind of object for the complement: its enclosed components are the cavities of this volume (cavity_owners)."""
 
     def __init__(self, vol: BitVolume, connectivity=6):
@@ -670,6 +671,32 @@ class ComponentRuns:
             raise _lib.TomoError("component_geodesic: a seed does not lie on its component (flags %d)" % flags[0])
         self.last_geodesic_map = dist
         return _component_geodesic_from(tables, host, host_prev)
+
+    def skeleton(self, min_voxels=0, largest=False, curve=True, anchors=None, *, max_voxels=None, enclosed=False) -> "ComponentSkeleton":
+        """component_skeleton of this volume.  The rule: select's.  ONE thinning of the whole volume under the connectivity of this
+        object (thinning preserves components: every component owns exactly one piece of the skeleton), one tomo_thin_nodes over
+        it, then tomo_thin_count adds up the skeleton, its ends and its junctions under the ORIGINAL runs of the selected
+        components.  The skeleton stays in last_skeleton.  On background() with enclosed=True the rows are the cavities."""
+        rule = _keep_rule(min_voxels, largest, max_voxels, enclosed)
+        curve, anchors = _skeleton_args(self.vol, curve, self.connectivity, anchors)
+        COUNTERS["component_skeleton"] += 1
+        self.last_skeleton = None
+        picked = self.select(rule[0], rule[1], max_voxels=rule[2], enclosed=rule[3])
+        if picked is None:
+            return _component_skeleton_from(np.zeros((0, 2), dtype=np.int64), np.zeros((0, 3), dtype=np.int64))
+        L, dev, st = _lib.lib(), self.vol.device, _stream()
+        skel, _ = _skeleton(BitVolume(self.bits, self.vol.shape), curve, self.connectivity, anchors)
+        nodes = _skeleton_nodes(skel)
+        n = picked.table.shape[0]
+        counts = torch.zeros((picked.m, 3), dtype=torch.int64, device=dev)
+        for column, other in enumerate((skel, nodes.ends, nodes.junctions)):
+            _lib.check(L.tomo_thin_count(_p(self.bits), *self.vol.shape, *self._tables(), _p(self.tot), _p(other.bits), _p(picked.sel),
+                                         _p(picked.slot), _p(counts), column, 3, n, picked.m, st), "tomo_thin_count")
+        labels = picked.sel.nonzero().reshape(-1)
+        ride = torch.stack((labels + 1, picked.table[:, 0].index_select(0, labels)), dim=1)
+        host, rows = self._download_checked("component_skeleton", ride, counts)
+        self.last_skeleton = skel
+        return _component_skeleton_from(host, rows)
 
     def topology(self) -> torch.Tensor:
         """Per component 1..n: Euler number, cavities (enclosed voids, b2) and handles (tunnels, b1 = 1 - euler + cavities) of
@@ -2473,6 +2500,170 @@ def separate_by_height_with_contacts(vol: BitVolume, h_mm, slice_depths=None, mm
     surface_factors(slice_depths, vol.shape[0], mm_per_pixel_y, mm_per_pixel_x, directions)          # the argument check
     sep, dist = _separate_by_height(vol, args, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
     return sep, _separation_contacts(vol, sep, dist, slice_depths, mm_per_pixel_y, mm_per_pixel_x, args[2], directions)
+
+
+# ----------------------------------------------------------------------------- homotopic thinning: the curve skeleton
+THIN_SUBPASSES = 48                  # sub-passes of one iteration: six directions, eight subfields each (tomo_thin_pass)
+THIN_COUNTER_WORDS = 1024            # tomo_thin_pass spreads its count of cleared voxels over 64 counters, 128 bytes apart
+THIN_ITERATION_BATCH = 1             # iterations, each of 48 launches, enqueued between two reads of the counters; read when called
+THIN_ITERATION_LIMIT = 1 << 16       # a guard against an endless host loop, no tuning knob; read when called
+
+
+def _skeleton_args(vol, curve, connectivity, anchors):
+    """The argument checks of the thinning calls, all on the host -> (curve, anchors)."""
+    if not isinstance(vol, BitVolume):
+        raise TypeError("vol must be a BitVolume")
+    connectivity = _check_connectivity(connectivity)
+    curve = bool(curve)
+    if curve and connectivity == 6:
+        raise ValueError("curve=True needs connectivity 26: the end rule counts 26-neighbours and would eat a 6-connected staircase "
+                         "from its end (curve=False thins under 6)")
+    if anchors is not None:
+        if not isinstance(anchors, BitVolume):
+            raise TypeError("anchors must be a BitVolume or None")
+        if tuple(anchors.shape) != tuple(vol.shape) or tuple(anchors.bits.shape) != tuple(vol.bits.shape):
+            raise ValueError("anchors must have the shape of the volume")
+        if anchors.device != vol.device:
+            raise ValueError("anchors must be on the volume's device")
+    return curve, anchors
+
+
+def _skeleton(vol: BitVolume, curve, connectivity, anchors):
+    """Thin a copy of the volume -> (BitVolume, iterations).  Iterations of 48 sub-passes, THIN_ITERATION_BATCH of them between
+    two reads; every iteration has a counter row of its own, so the first one that cleared nothing is known whatever the batch."""
+    L, dev, st = _lib.lib(), vol.device, _stream()
+    nz, ny, nx = vol.shape
+    src = vol.bits.contiguous()
+    bits = torch.empty_like(src)
+    bits.copy_(src)
+    out = BitVolume(bits, (nz, ny, nx))
+    COUNTERS["thin_calls"] += 1
+    if _download(popcount_async(out))[0] == 0:                           # nothing to thin: no sub-pass is launched
+        return out, 0
+    tiles = int(L.tomo_geo_tiles(nz, ny, nx))
+    if tiles <= 0:
+        raise _lib.TomoError("tomo_geo_tiles failed (%d)" % tiles)
+    keep = None if anchors is None else anchors.bits.contiguous()
+    limit, batch = int(THIN_ITERATION_LIMIT), max(1, int(THIN_ITERATION_BATCH))
+    stamp = torch.zeros(tiles, dtype=torch.int32, device=dev)
+    counters = torch.zeros((batch, THIN_COUNTER_WORDS), dtype=torch.int64, device=dev)
+    done = 0
+    while True:
+        if done >= limit:
+            raise _lib.TomoError("skeleton: no fixed point after %d iterations (THIN_ITERATION_LIMIT)" % done)
+        k = min(batch, limit - done)
+        if done:
+            counters.zero_()
+        for j in range(k):
+            row = _p(counters[j])
+            for d in range(6):
+                for s in range(8):
+                    tick = THIN_SUBPASSES * (done + j) + 8 * d + s + 1
+                    _lib.check(L.tomo_thin_pass(_p(bits), _p(keep), nz, ny, nx, connectivity, int(curve), d, s, _p(stamp), tick, row, st),
+                               "tomo_thin_pass")
+        COUNTERS["thin_passes"] += THIN_SUBPASSES * k
+        host = _download(counters.sum(dim=1))
+        for j in range(k):
+            if host[j] == 0:                                             # the first iteration that cleared nothing: the fixed point
+                COUNTERS["thin_iterations"] += done + j + 1
+                return out, done + j + 1
+        done += k
+
+
+def skeleton(vol: BitVolume, curve=True, connectivity=26, anchors=None) -> BitVolume:
+    """The skeleton of a resident volume by homotopic thinning -> a NEW BitVolume; the input is left untouched (MorphoLibJ /
+    BoneJ Skeletonize3D, scikit-image skeletonize_3d answer the same question with another order of deletions).  One definition
+    (include/tomo_hip.h): an iteration is 48 sub-passes -- the directions -z, +z, -y, +y, -x, +x, inside each the eight
+    subfields 4 (z & 1) + 2 (y & 1) + (x & 1) in ascending order -- and a sub-pass clears, all at once, every set voxel of its
+    subfield whose neighbour in its direction is clear or outside the stack, that is a simple point under `connectivity` (26,
+    or 6; the background has the other one, outside the stack is background) and, with curve=True, is no end (exactly one set
+    26-neighbour).  The result is the volume after the first iteration that cleared nothing.  Two voxels of one subfield are
+    never 26-neighbours, so every deletion is the deletion of a simple point: components, cavities and handles are those of
+    the input.  curve=False gives the ultimate homotopic kernel (a ball becomes one voxel, a ring a closed curve, a shell stays
+    a closed surface); curve=True the curve skeleton; curve=True with connectivity 6 is a ValueError.  anchors: a BitVolume of
+    voxels that are never cleared (extended_maxima of the distance map pins the skeleton to the domes), or None.
+    The thinning is in voxel steps: spacing and slice depths play no part in it.
+    On the device: tomo_thin_pass in place on a copy -- a candidate only reads bits no sub-pass of its kind writes, so there is
+    no second buffer, and the bytes are the same on every run -- with one uint32 per 8 x 8 x 64 tile that lets a tile rest once
+    it and its neighbours lost nothing for 48 sub-passes.  Memory: the copy and 4 bytes a tile, nothing per voxel.  The host
+    enqueues THIN_ITERATION_BATCH iterations between two counter reads (more than THIN_ITERATION_LIMIT iterations: TomoError);
+    the bytes and the iteration count do not depend on the batch.  COUNTERS: thin_calls, thin_iterations (the last, idle one
+    included), thin_passes.  An empty volume launches no sub-pass (0 iterations).  Arguments are checked
+    before the first launch."""
+    curve, anchors = _skeleton_args(vol, curve, connectivity, anchors)
+    return _skeleton(vol, curve, int(connectivity), anchors)[0]
+
+
+@dataclass
+class SkeletonNodes:
+    """skeleton_nodes' answer: two bit volumes on the device and four counts."""
+    ends: BitVolume              # the set voxels with exactly one set 26-neighbour
+    junctions: BitVolume         # ... with three or more
+    voxels: int
+    end_points: int
+    junction_voxels: int
+    isolated: int                # set voxels without a set 26-neighbour
+
+
+def _skeleton_nodes(skel: BitVolume) -> SkeletonNodes:
+    L, dev = _lib.lib(), skel.device
+    bits = skel.bits.contiguous()
+    ends, junctions = torch.empty_like(bits), torch.empty_like(bits)
+    counters = torch.zeros(4, dtype=torch.int64, device=dev)
+    COUNTERS["thin_nodes"] += 1
+    _lib.check(L.tomo_thin_nodes(_p(bits), *skel.shape, _p(ends), _p(junctions), _p(counters), _stream()), "tomo_thin_nodes")
+    return SkeletonNodes(BitVolume(ends, skel.shape), BitVolume(junctions, skel.shape), *_download(counters))
+
+
+def skeleton_nodes(skel: BitVolume) -> SkeletonNodes:
+    """The free ends and the junctions of a skeleton (or of any volume) by 26-neighbour counts -> SkeletonNodes: a set voxel with
+    exactly one set neighbour is an end, one with three or more a junction voxel, one with none is isolated.  A junction of a
+    one-voxel curve is a small cluster of junction voxels, not one: junction_voxels counts voxels.  One pass, one host read."""
+    if not isinstance(skel, BitVolume):
+        raise TypeError("skel must be a BitVolume")
+    return _skeleton_nodes(skel)
+
+
+@dataclass
+class ComponentSkeleton:
+    """component_skeleton's answer: host arrays, one row per selected component in ascending label."""
+    labels: np.ndarray           # int64 (m,)
+    voxels: np.ndarray           # int64 (m,)
+    skeleton_voxels: np.ndarray  # int64 (m,): the voxels of the component's piece of the skeleton
+    end_points: np.ndarray       # int64 (m,): its free ends
+    junction_voxels: np.ndarray  # int64 (m,): its junction voxels
+
+    def __len__(self):
+        return len(self.labels)
+
+
+def _component_skeleton_from(ride, rows) -> ComponentSkeleton:
+    ride = np.ascontiguousarray(ride, dtype=np.int64).reshape(-1, 2)
+    rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1, 3)
+    return ComponentSkeleton(ride[:, 0].copy(), ride[:, 1].copy(), rows[:, 0].copy(), rows[:, 1].copy(), rows[:, 2].copy())
+
+
+def component_skeleton(vol: BitVolume, connectivity=26, min_voxels=0, largest=False, curve=True, anchors=None) -> ComponentSkeleton:
+    """Skeleton voxels, free ends and junction voxels per component of a resident volume -> ComponentSkeleton, one row per
+    component the keep rule of component_properties selects, in ascending label: the rows component_properties returns for the
+    same rule.  The volume is labelled under `connectivity` and thinned under the same connectivity (skeleton's arguments and
+    errors: curve=True needs 26).  Thinning preserves components, so every component owns exactly one piece of the skeleton,
+    and the counts are taken under the ORIGINAL runs of the labelling.  A fibre reads two ends and no junction, a ring none of
+    either, a branching crack its branch points.  An empty volume, or nothing selected, gives zero rows.  Arguments are
+    checked before the first launch."""
+    _skeleton_args(vol, curve, connectivity, anchors)
+    _keep_rule(min_voxels, largest)
+    return ComponentRuns(vol, connectivity).skeleton(min_voxels, largest, curve, anchors)
+
+
+def cavity_skeleton(vol: BitVolume, connectivity=6, min_voxels=0, max_voxels=None, curve=True, anchors=None) -> ComponentSkeleton:
+    """component_skeleton of the enclosed voids of a resident volume, one row per cavity of cavity_table under the same size
+    window, in ascending cavity label.  The complement is labelled and thinned under the complementary connectivity: the
+    default connectivity=6 of the solid gives 26-connected pores, which curve=True needs."""
+    connectivity = _check_connectivity(connectivity)
+    lo, hi = _check_size_window(min_voxels, max_voxels)
+    _skeleton_args(vol, curve, 32 - connectivity, anchors)
+    return _complement_runs(vol, connectivity).skeleton(lo, False, curve, anchors, max_voxels=hi, enclosed=True)
 
 
 def local_thickness(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, radii_mm=None,

@@ -312,10 +312,28 @@ def grain_contacts_by_height(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_d
                                                                       min_marker_voxels, min_radius_mm))
 
 
+def skeleton_report(voxel_data, connectivity=26, curve=True):
+    """The skeleton of a volume by homotopic thinning (no counterpart in the reference): pipeline.skeleton and
+    pipeline.skeleton_nodes -> {'skeleton': bool (nz, ny, nx) array, 'voxels', 'end_points', 'junction_voxels', 'isolated',
+    'iterations'} (Python ints; iterations counts the last one, which cleared nothing; an empty volume reads 0).  The thinning
+    is in voxel steps: it takes no spacing.  curve=True with connectivity=6 is a ValueError, before the first launch.
+    voxel_data: the bool (nz, ny, nx) array the other calculations take; anything else is a TypeError."""
+    if not _on_device(voxel_data):
+        raise TypeError("skeleton_report needs a bool (nz, ny, nx) array")
+    connectivity = pipeline._check_connectivity(connectivity)
+    if curve and connectivity == 6:
+        raise ValueError("curve=True needs connectivity=26: the curve skeleton is not defined under 6")
+    vol = to_device_volume(voxel_data)
+    skel, iterations = pipeline._skeleton(vol, bool(curve), connectivity, None)
+    nodes = pipeline.skeleton_nodes(skel)
+    return {'skeleton': pipeline.unpack(skel).cpu().numpy(), 'voxels': int(nodes.voxels), 'end_points': int(nodes.end_points),
+            'junction_voxels': int(nodes.junction_voxels), 'isolated': int(nodes.isolated), 'iterations': int(iterations)}
+
+
 def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=6, min_voxels=0, largest=False,
                          shape=False, topology=False, surface=False, surface_directions=13, porosity=False, thickness=False,
                          thickness_radii_mm=None, geodesic=False, geodesic_sweeps=3, separate_mm=None, separate_h_mm=None,
-                         caliper=False,
+                         skeleton=False, caliper=False,
                          caliper_directions=None, caliper_oriented=False):
     """The calculations of the class per connected component (no counterpart in the reference, which would be handed the mask
     `labels == c` once per component) -> a list of dicts, one per component with at least min_voxels voxels (largest: only the
@@ -352,6 +370,11 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
     flag above, measure the separated grains (separate_grains returns that volume and its counts).  separate_h_mm=h (a keyword;
     None: off, nothing new is launched): the same with pipeline.separate_by_height(volume, h, ..., connectivity), the h-maxima
     markers of separate_grains_by_height; giving both separate_mm and separate_h_mm is a ValueError.
+    skeleton=True (a keyword; off: nothing new is launched): every dict also carries 'skeleton_voxels', 'skeleton_ends' and
+    'skeleton_junctions' as Python ints -- the voxels, free ends and junction voxels of the component's piece of the curve
+    skeleton (pipeline.component_skeleton: ONE thinning of the whole volume under `connectivity`, counted under the runs of the
+    one labelling; in voxel steps, the spacing plays no part).  The curve skeleton needs connectivity=26: skeleton=True with
+    connectivity=6 is a ValueError.
     Whatever the
     flags, the volume is uploaded and labelled ONCE, and so is its complement: one pipeline.ComponentRuns serves all the
     measurements and owns the one selection their rows come from.  Arguments are checked before the first launch.  voxel_data: a bool (nz, ny, nx) array, else a TypeError."""
@@ -369,6 +392,8 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
     if geodesic:
         pipeline._geodesic_search_sweeps(geodesic_sweeps)
         pipeline._geodesic_tables(voxel_data.shape, depths, mm_per_pixel_y, mm_per_pixel_x)
+    if skeleton and connectivity == 6:
+        raise ValueError("skeleton=True needs connectivity=26: the curve skeleton is not defined under 6")
     if separate_mm is not None and separate_h_mm is not None:
         raise ValueError("separate_mm and separate_h_mm are two marker rules: give one of them")
     if separate_mm is not None:
@@ -395,6 +420,7 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
     h = runs.thickness(depths, mm_per_pixel_y, mm_per_pixel_x, thickness_radii_mm, *rule) if thickness else None
     f = runs.caliper(depths, mm_per_pixel_y, mm_per_pixel_x, caliper_directions, "voxels", caliper_oriented, *rule) if caliper else None
     g = runs.geodesic(depths, mm_per_pixel_y, mm_per_pixel_x, geodesic_sweeps, *rule) if geodesic else None
+    k = runs.skeleton(*rule) if skeleton else None
     pores = {}
     if porosity:                                                 # every cavity of the volume, credited to its owner
         c = pipeline._cavities_from(runs, runs.background().properties(tables, mm_per_pixel_y, mm_per_pixel_x, enclosed=True))
@@ -439,6 +465,9 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
             d['geodesic_length_mm'] = float(g.length_mm[i])
             d['geodesic_ends_index'] = tuple(tuple(int(v) for v in end) for end in g.ends_index[i])
             d['tortuosity'] = float(g.tortuosity[i])
+        if skeleton:
+            d['skeleton_voxels'], d['skeleton_ends'] = int(k.skeleton_voxels[i]), int(k.end_points[i])
+            d['skeleton_junctions'] = int(k.junction_voxels[i])
     return out
 
 
