@@ -11,8 +11,8 @@
 // 64 consecutive floats (no bank conflict, the x - 1 / x + 1 reads included), and a thread owns the 16 rows wave + 4 k of its
 // column in registers.  LDS: the (TZ + 2) x (TY + 2) x 66 halo box of floats, 26 400 bytes, the row masks and the z weights.
 //
-// One sweep (tomo_geo_sweep).  A workgroup whose flag in dirty_cur is clear leaves at once; otherwise it clears the flag (only it
-// reads it), loads its box -- unset voxels and everything outside the stack are +inf -- and relaxes the interior against the
+// One sweep (tomo_geo_sweep), on the skeleton of geo_tiles.h.  A workgroup whose flag in dirty_cur is clear leaves at once;
+// otherwise it clears the flag (only it reads it), loads its box -- unset voxels and everything outside the stack are +inf -- and relaxes the interior against the
 // FIXED halo until a round changes nothing.  A round is race free: every thread forms the candidates of its voxels from the
 // published LDS copy, all pass a barrier, the changed values are published, __syncthreads_or ends the round.  The rounds are
 // bounded by GEO_ROUNDS, the number of interior voxels (a shortest path inside the tile has fewer steps); a tile that hits the
@@ -24,7 +24,7 @@
 //
 // Zones of markers (tomo_zone_seed_labels, tomo_zone_sweep, tomo_zone_cut) sit further down: a second phase over the FINAL map that
 // says which marker reached a voxel, on the same tiles and flags, and the cut between zones.  The kernels above are not touched.
-#include "geo_tiles.h"                             // the tile sizes, GeoGrid / geo_grid and geo_word, shared with reconstruct.hip
+#include "geo_tiles.h"                             // the tiles and the skeleton of a sweep, shared with reconstruct.hip and thin.hip
 #include <math.h>
 
 #define GEO_F_SEED 4ull                            // counters[1]: a seed index outside the volume or on an unset voxel
@@ -62,20 +62,15 @@ __global__ __launch_bounds__(GEO_THREADS) void geo_seed_bits_kernel(const u64 *_
                                                                     int64_t nwords, int nz, int ny, int nx, int wx, int ty,
                                                                     float *__restrict__ dist, u32 *__restrict__ dirty)
 {
-    const int64_t t = (int64_t)blockIdx.x * GEO_THREADS + threadIdx.x;
-    const int64_t word = t >> 6;                             // the same for the 64 lanes of a wave
-    if (word >= nwords) return;
-    const int64_t row = word / wx;
-    const int w = (int)(word - row * wx);
-    const int b = (int)(t & 63);
-    const int x = 64 * w + b;
-    const u64 m = geo_word(bits + row * wx, nx, wx, w) & seeds[word];
-    const bool seed = (m >> b) & 1;                          // below nx: the tail bits of m are zero
-    if (x < nx) dist[row * nx + x] = seed ? 0.0f : INFINITY;
+    GeoLane p;
+    if (!geo_lane(nwords, wx, &p)) return;
+    const u64 m = geo_word(bits + p.row * wx, nx, wx, p.w) & seeds[p.word];
+    const bool seed = (m >> p.b) & 1;                        // below nx: the tail bits of m are zero
+    if (p.x < nx) dist[p.row * nx + p.x] = seed ? 0.0f : INFINITY;
     if (seed) {
-        const int z = (int)(row / ny), y = (int)(row - (int64_t)z * ny);
-        if (b == 0 || b == 63 || b == __ffsll((long long)m) - 1)      // one lane for the tile itself, the two ends for the x faces
-            geo_mark_seed(dirty, z, y, x, nz, ty, wx);
+        const int z = (int)(p.row / ny), y = (int)(p.row - (int64_t)z * ny);
+        if (p.b == 0 || p.b == 63 || p.b == __ffsll((long long)m) - 1)      // one lane for the tile itself, the two ends for the x faces
+            geo_mark_seed(dirty, z, y, p.x, nz, ty, wx);
     }
 }
 
@@ -159,49 +154,16 @@ __global__ __launch_bounds__(GEO_THREADS, 2) void geo_sweep_kernel(const u64 *__
 
     const int tid = threadIdx.x;
     const int64_t tile = blockIdx.x;
-    if (!__syncthreads_or((int)dirty_cur[tile])) return;     // uniform: every thread has read the flag before it is cleared
-    if (tid == 0) {
-        dirty_cur[tile] = 0u;
-        snb = 0u;
-    }
-    const int bx = (int)(tile % wx);
-    const int64_t rest = tile / wx;
-    const int by = (int)(rest % ty), bz = (int)(rest / ty);
-    const int z0 = bz * GEO_TZ - 1, y0 = by * GEO_TY - 1;    // the halo box starts here
-
-    // the masks of the 100 halo rows and the z weights
-    if (tid < GEO_HROWS) {
-        const int z = z0 + tid / GEO_HY, y = y0 + tid % GEO_HY;
-        u64 mid = 0;
-        u32 side = 0;
-        if (z >= 0 && z < nz && y >= 0 && y < ny) {
-            const u64 *r = bits + ((int64_t)z * ny + y) * wx;
-            mid = geo_word(r, nx, wx, bx);
-            if (bx > 0 && (geo_word(r, nx, wx, bx - 1) >> 63)) side |= 1u;
-            if (bx + 1 < wx && (geo_word(r, nx, wx, bx + 1) & 1)) side |= 2u;
-        }
-        smid[tid] = mid;
-        sside[tid] = side;
-    } else if (tid >= 128 && tid < 128 + (GEO_TZ + 1) * 4) {
-        const int b = (tid - 128) >> 2, k = (tid - 128) & 3;
-        const int z = z0 + b;                                // the boundary between slices z and z + 1
-        swz[tid - 128] = (z >= 0 && z + 1 < nz) ? wz[4 * (int64_t)z + k] : INFINITY;
-    }
+    if (!geo_enter(dirty_cur, tile, &snb)) return;
+    const GeoTile t = geo_tile(tile, wx, ty);
+    geo_halo_masks(bits, nz, ny, nx, wx, t, smid, sside);
+    geo_z_weights(wz, nz, t, swz);
     __syncthreads();
 
     // the box: dist under the mask, +inf at unset voxels and outside the stack
     for (int i = tid; i < GEO_BOX; i += GEO_THREADS) {
         const int hr = i / GEO_HX, xx = i - hr * GEO_HX;
-        bool set;
-        if (xx == 0) set = sside[hr] & 1u;
-        else if (xx == GEO_HX - 1) set = (sside[hr] >> 1) & 1u;
-        else set = (smid[hr] >> (xx - 1)) & 1;
-        float v = INFINITY;
-        if (set) {                                           // a set voxel lies inside the stack and below nx
-            const int z = z0 + hr / GEO_HY, y = y0 + hr % GEO_HY;
-            v = dist[((int64_t)z * ny + y) * nx + (64 * bx + xx - 1)];
-        }
-        box[i] = v;
+        box[i] = geo_halo_set(smid, sside, hr, xx) ? dist[geo_halo_voxel(t, hr, xx, ny, nx)] : INFINITY;
     }
     __syncthreads();
 
@@ -211,22 +173,19 @@ __global__ __launch_bounds__(GEO_THREADS, 2) void geo_sweep_kernel(const u64 *__
     u32 mine = 0, moved = 0;                                 // bit k: voxel k is set / has changed since the load
 #pragma unroll
     for (int k = 0; k < GEO_PER; k++) {
-        const int r = wave + 4 * k;                          // interior row: z = r / TY, y = r % TY
-        const int hr = (r / GEO_TY + 1) * GEO_HY + (r % GEO_TY + 1);
-        d[k] = box[hr * GEO_HX + lane + 1];
-        if ((smid[hr] >> lane) & 1) mine |= 1u << k;
+        const int r = wave + 4 * k, lz = r / GEO_TY, ly = r % GEO_TY;
+        d[k] = *geo_box_at(box, lz, ly, lane);
+        if ((smid[geo_halo_row(lz, ly)] >> lane) & 1) mine |= 1u << k;
     }
 
     int more = 1, round = 0;
-    for (; round < GEO_ROUNDS && more; round++) {            // bounded: a tile that needs more marks itself below
+    for (; round < GEO_ROUNDS && more; round++) {            // bounded: a tile that needs more marks itself in geo_leave
         u32 now = 0;
 #pragma unroll
         for (int k = 0; k < GEO_PER; k++) {
             if (!((mine >> k) & 1)) continue;
-            const int r = wave + 4 * k;
-            const int lz = r / GEO_TY;
-            const int hr = (lz + 1) * GEO_HY + (r % GEO_TY + 1);
-            const float c = geo_relax<CONN>(box + hr * GEO_HX + lane + 1, d[k], w_x, w_y, w_xy, swz + 4 * lz, swz + 4 * (lz + 1));
+            const int r = wave + 4 * k, lz = r / GEO_TY, ly = r % GEO_TY;
+            const float c = geo_relax<CONN>(geo_box_at(box, lz, ly, lane), d[k], w_x, w_y, w_xy, swz + 4 * lz, swz + 4 * (lz + 1));
             if (c < d[k]) {
                 d[k] = c;
                 now |= 1u << k;
@@ -235,10 +194,8 @@ __global__ __launch_bounds__(GEO_THREADS, 2) void geo_sweep_kernel(const u64 *__
         __syncthreads();                                     // every candidate of the round is formed: publish
 #pragma unroll
         for (int k = 0; k < GEO_PER; k++) {
-            if ((now >> k) & 1) {
-                const int r = wave + 4 * k;
-                box[((r / GEO_TY + 1) * GEO_HY + (r % GEO_TY + 1)) * GEO_HX + lane + 1] = d[k];
-            }
+            const int r = wave + 4 * k;
+            if ((now >> k) & 1) *geo_box_at(box, r / GEO_TY, r % GEO_TY, lane) = d[k];
         }
         moved |= now;
         more = __syncthreads_or((int)now);
@@ -249,37 +206,11 @@ __global__ __launch_bounds__(GEO_THREADS, 2) void geo_sweep_kernel(const u64 *__
 #pragma unroll
     for (int k = 0; k < GEO_PER; k++) {
         if (!((moved >> k) & 1)) continue;
-        const int r = wave + 4 * k;
-        const int lz = r / GEO_TY, ly = r % GEO_TY;
-        const int z = z0 + 1 + lz, y = y0 + 1 + ly;
-        dist[((int64_t)z * ny + y) * nx + (64 * bx + lane)] = d[k];
-        const u32 zs = 2u | (lz == 0 ? 1u : 0u) | (lz == GEO_TZ - 1 ? 4u : 0u);     // bit 0 / 1 / 2: step -1 / 0 / +1
-        const u32 ys = 2u | (ly == 0 ? 1u : 0u) | (ly == GEO_TY - 1 ? 4u : 0u);
-        const u32 xs = 2u | (lane == 0 ? 1u : 0u) | (lane == 63 ? 4u : 0u);
-#pragma unroll
-        for (int a = 0; a < 3; a++)
-#pragma unroll
-            for (int b = 0; b < 3; b++)
-#pragma unroll
-                for (int c = 0; c < 3; c++)
-                    if (((zs >> a) & 1) && ((ys >> b) & 1) && ((xs >> c) & 1)) nb |= 1u << (9 * a + 3 * b + c);
+        const int r = wave + 4 * k, lz = r / GEO_TY, ly = r % GEO_TY;
+        dist[geo_voxel(t, lz, ly, lane, ny, nx)] = d[k];
+        nb |= geo_marks(geo_steps(lz, GEO_TZ), geo_steps(ly, GEO_TY), geo_steps(lane, 64));
     }
-    if (nb) atomicOr(&snb, nb);                              // an LDS atomic
-    __syncthreads();
-    const u32 all = snb;
-    if (!(all || more)) return;                              // nothing changed: nothing is stored, nothing is marked
-    if (tid == 0) {
-        atomicAdd(counters, 1ull);                           // once per workgroup that changed something
-        if (more) dirty_next[tile] = 1u;                     // the round bound was hit
-    }
-    if (tid < 27 && tid != 13 && ((all >> tid) & 1)) {
-        const int dz = tid / 9 - 1, dy = (tid / 3) % 3 - 1, dx = tid % 3 - 1;
-        const int steps = (dz != 0) + (dy != 0) + (dx != 0);
-        const int tzn = (nz + GEO_TZ - 1) / GEO_TZ;
-        const int nbz = bz + dz, nby = by + dy, nbx = bx + dx;
-        if ((CONN == 26 || steps == 1) && nbz >= 0 && nbz < tzn && nby >= 0 && nby < ty && nbx >= 0 && nbx < wx)
-            dirty_next[((int64_t)nbz * ty + nby) * wx + nbx] = 1u;
-    }
+    geo_leave<CONN>(nb, more, &snb, tile, t, nz, ty, wx, dirty_next, counters);
 }
 
 // ---------------------------------------------------------------------------------------------- reach
@@ -288,20 +219,15 @@ __global__ __launch_bounds__(GEO_THREADS) void geo_reach_kernel(const u64 *__res
                                                                 int64_t nwords, int nx, int wx, double max_mm, int finite,
                                                                 u64 *__restrict__ out)
 {
-    const int64_t t = (int64_t)blockIdx.x * GEO_THREADS + threadIdx.x;
-    const int64_t word = t >> 6;
-    if (word >= nwords) return;
-    const int64_t row = word / wx;
-    const int w = (int)(word - row * wx);
-    const int b = (int)(t & 63);
-    const int x = 64 * w + b;
+    GeoLane p;
+    if (!geo_lane(nwords, wx, &p)) return;
     bool bit = false;
-    if (x < nx && ((bits[word] >> b) & 1)) {
-        const float v = dist[row * nx + x];
+    if (p.x < nx && ((bits[p.word] >> p.b) & 1)) {
+        const float v = dist[p.row * nx + p.x];
         bit = finite ? v < INFINITY : (double)v <= max_mm;
     }
     const u64 m = __ballot(bit);
-    if (b == 0) out[word] = m;
+    if (p.b == 0) out[p.word] = m;
 }
 
 // ---------------------------------------------------------------------------------------------- zones of markers
@@ -320,27 +246,22 @@ __global__ __launch_bounds__(GEO_THREADS) void zone_seed_kernel(const u64 *__res
                                                                 int64_t nwords, int nz, int ny, int nx, int wx, int ty,
                                                                 float *__restrict__ dist, int *__restrict__ zone, u32 *__restrict__ dirty)
 {
-    const int64_t t = (int64_t)blockIdx.x * GEO_THREADS + threadIdx.x;
-    const int64_t word = t >> 6;                             // the same for the 64 lanes of a wave
-    if (word >= nwords) return;
-    const int64_t row = word / wx;
-    const int w = (int)(word - row * wx);
-    const int b = (int)(t & 63);
-    const int x = 64 * w + b;
+    GeoLane p;
+    if (!geo_lane(nwords, wx, &p)) return;
     int label = 0;
-    if ((geo_word(bits + row * wx, nx, wx, w) >> b) & 1) {   // below nx: the tail bits are masked
-        const int v = markers[row * nx + x];
+    if ((geo_word(bits + p.row * wx, nx, wx, p.w) >> p.b) & 1) {      // below nx: the tail bits are masked
+        const int v = markers[p.row * nx + p.x];
         if (v > 0) label = v;
     }
     const u64 m = __ballot(label > 0);
-    if (x < nx) {
-        dist[row * nx + x] = label > 0 ? 0.0f : INFINITY;
-        zone[row * nx + x] = label;
+    if (p.x < nx) {
+        dist[p.row * nx + p.x] = label > 0 ? 0.0f : INFINITY;
+        zone[p.row * nx + p.x] = label;
     }
     if (label > 0) {
-        const int z = (int)(row / ny), y = (int)(row - (int64_t)z * ny);
-        if (b == 0 || b == 63 || b == __ffsll((long long)m) - 1)
-            geo_mark_seed(dirty, z, y, x, nz, ty, wx);
+        const int z = (int)(p.row / ny), y = (int)(p.row - (int64_t)z * ny);
+        if (p.b == 0 || p.b == 63 || p.b == __ffsll((long long)m) - 1)
+            geo_mark_seed(dirty, z, y, p.x, nz, ty, wx);
     }
 }
 
@@ -377,7 +298,7 @@ __device__ static inline void zone_neighbours(const float wx_, const float wy_, 
     }
 }
 
-// One label sweep, shaped like geo_sweep_kernel: the same tiles, flags, rounds and marks.  dist is read only: the tight edges into
+// One label sweep, on the same skeleton as geo_sweep_kernel (geo_tiles.h): tiles, flags, rounds and marks.  dist is read only: the tight edges into
 // a thread's 16 voxels are found ONCE per visit (a bit per neighbour, in registers), the rounds then only take minima of keys
 // over those bits.  Two boxes in LDS, 54 148 bytes with the masks: two workgroups per CU (160 KiB), which the launch bound asks
 // of the registers as well.
@@ -396,46 +317,18 @@ __global__ __launch_bounds__(GEO_THREADS, 2) void zone_sweep_kernel(const u64 *_
 
     const int tid = threadIdx.x;
     const int64_t tile = blockIdx.x;
-    if (!__syncthreads_or((int)dirty_cur[tile])) return;     // uniform: every thread has read the flag before it is cleared
-    if (tid == 0) {
-        dirty_cur[tile] = 0u;
-        snb = 0u;
-    }
-    const int bx = (int)(tile % wx);
-    const int64_t rest = tile / wx;
-    const int by = (int)(rest % ty), bz = (int)(rest / ty);
-    const int z0 = bz * GEO_TZ - 1, y0 = by * GEO_TY - 1;    // the halo box starts here
-
-    if (tid < GEO_HROWS) {
-        const int z = z0 + tid / GEO_HY, y = y0 + tid % GEO_HY;
-        u64 mid = 0;
-        u32 side = 0;
-        if (z >= 0 && z < nz && y >= 0 && y < ny) {
-            const u64 *r = bits + ((int64_t)z * ny + y) * wx;
-            mid = geo_word(r, nx, wx, bx);
-            if (bx > 0 && (geo_word(r, nx, wx, bx - 1) >> 63)) side |= 1u;
-            if (bx + 1 < wx && (geo_word(r, nx, wx, bx + 1) & 1)) side |= 2u;
-        }
-        smid[tid] = mid;
-        sside[tid] = side;
-    } else if (tid >= 128 && tid < 128 + (GEO_TZ + 1) * 4) {
-        const int b = (tid - 128) >> 2, k = (tid - 128) & 3;
-        const int z = z0 + b;                                // the boundary between slices z and z + 1
-        swz[tid - 128] = (z >= 0 && z + 1 < nz) ? wz[4 * (int64_t)z + k] : INFINITY;
-    }
+    if (!geo_enter(dirty_cur, tile, &snb)) return;
+    const GeoTile t = geo_tile(tile, wx, ty);
+    geo_halo_masks(bits, nz, ny, nx, wx, t, smid, sside);
+    geo_z_weights(wz, nz, t, swz);
     __syncthreads();
 
     for (int i = tid; i < GEO_BOX; i += GEO_THREADS) {
         const int hr = i / GEO_HX, xx = i - hr * GEO_HX;
-        bool set;
-        if (xx == 0) set = sside[hr] & 1u;
-        else if (xx == GEO_HX - 1) set = (sside[hr] >> 1) & 1u;
-        else set = (smid[hr] >> (xx - 1)) & 1;
         float v = INFINITY;
         u32 key = ZONE_NONE;
-        if (set) {                                           // a set voxel lies inside the stack and below nx
-            const int z = z0 + hr / GEO_HY, y = y0 + hr % GEO_HY;
-            const int64_t at = ((int64_t)z * ny + y) * nx + (64 * bx + xx - 1);
+        if (geo_halo_set(smid, sside, hr, xx)) {
+            const int64_t at = geo_halo_voxel(t, hr, xx, ny, nx);
             v = dist[at];
             key = zone_key(zone[at]);
         }
@@ -450,12 +343,10 @@ __global__ __launch_bounds__(GEO_THREADS, 2) void zone_sweep_kernel(const u64 *_
     u32 live = 0, moved = 0;                                 // bit k: voxel k has a tight edge / has changed since the load
 #pragma unroll
     for (int k = 0; k < GEO_PER; k++) {
-        const int r = wave + 4 * k;                          // interior row: z = r / TY, y = r % TY
-        const int lz = r / GEO_TY;
-        const int at = ((lz + 1) * GEO_HY + (r % GEO_TY + 1)) * GEO_HX + lane + 1;
-        const float d = box[at];
-        const float *p = box + at;
-        key[k] = zbox[at];
+        const int r = wave + 4 * k, lz = r / GEO_TY, ly = r % GEO_TY;
+        const float *p = geo_box_at(box, lz, ly, lane);
+        const float d = *p;
+        key[k] = zbox[p - box];                              // the two boxes have one layout
         u32 m = 0;
         if (d < INFINITY)                                    // an unset or unreached voxel takes no part
             zone_neighbours<CONN>(w_x, w_y, w_xy, swz + 4 * lz, swz + 4 * (lz + 1), [&](int j, int off, float w) {
@@ -466,14 +357,13 @@ __global__ __launch_bounds__(GEO_THREADS, 2) void zone_sweep_kernel(const u64 *_
     }
 
     int more = 1, round = 0;
-    for (; round < GEO_ROUNDS && more; round++) {            // bounded: a tile that needs more marks itself below
+    for (; round < GEO_ROUNDS && more; round++) {            // bounded: a tile that needs more marks itself in geo_leave
         u32 now = 0;
 #pragma unroll
         for (int k = 0; k < GEO_PER; k++) {
             if (!((live >> k) & 1)) continue;
-            const int r = wave + 4 * k;
-            const int lz = r / GEO_TY;
-            const u32 *q = zbox + ((lz + 1) * GEO_HY + (r % GEO_TY + 1)) * GEO_HX + lane + 1;
+            const int r = wave + 4 * k, lz = r / GEO_TY, ly = r % GEO_TY;
+            const u32 *q = geo_box_at(zbox, lz, ly, lane);
             u32 loose = ~tight[k];
             asm volatile("" : "+v"(loose));                  // opaque per round: the per-bit tests are not hoisted out of the loop
             u32 c = key[k];                                  // (hoisted, 416 lane masks spill the scalar registers)
@@ -488,10 +378,8 @@ __global__ __launch_bounds__(GEO_THREADS, 2) void zone_sweep_kernel(const u64 *_
         __syncthreads();                                     // every candidate of the round is formed: publish
 #pragma unroll
         for (int k = 0; k < GEO_PER; k++) {
-            if ((now >> k) & 1) {
-                const int r = wave + 4 * k;
-                zbox[((r / GEO_TY + 1) * GEO_HY + (r % GEO_TY + 1)) * GEO_HX + lane + 1] = key[k];
-            }
+            const int r = wave + 4 * k;
+            if ((now >> k) & 1) *geo_box_at(zbox, r / GEO_TY, r % GEO_TY, lane) = key[k];
         }
         moved |= now;
         more = __syncthreads_or((int)now);
@@ -502,37 +390,11 @@ __global__ __launch_bounds__(GEO_THREADS, 2) void zone_sweep_kernel(const u64 *_
 #pragma unroll
     for (int k = 0; k < GEO_PER; k++) {
         if (!((moved >> k) & 1)) continue;
-        const int r = wave + 4 * k;
-        const int lz = r / GEO_TY, ly = r % GEO_TY;
-        const int z = z0 + 1 + lz, y = y0 + 1 + ly;
-        zone[((int64_t)z * ny + y) * nx + (64 * bx + lane)] = (int)(key[k] + 1u);
-        const u32 zs = 2u | (lz == 0 ? 1u : 0u) | (lz == GEO_TZ - 1 ? 4u : 0u);     // bit 0 / 1 / 2: step -1 / 0 / +1
-        const u32 ys = 2u | (ly == 0 ? 1u : 0u) | (ly == GEO_TY - 1 ? 4u : 0u);
-        const u32 xs = 2u | (lane == 0 ? 1u : 0u) | (lane == 63 ? 4u : 0u);
-#pragma unroll
-        for (int a = 0; a < 3; a++)
-#pragma unroll
-            for (int b = 0; b < 3; b++)
-#pragma unroll
-                for (int c = 0; c < 3; c++)
-                    if (((zs >> a) & 1) && ((ys >> b) & 1) && ((xs >> c) & 1)) nb |= 1u << (9 * a + 3 * b + c);
+        const int r = wave + 4 * k, lz = r / GEO_TY, ly = r % GEO_TY;
+        zone[geo_voxel(t, lz, ly, lane, ny, nx)] = (int)(key[k] + 1u);
+        nb |= geo_marks(geo_steps(lz, GEO_TZ), geo_steps(ly, GEO_TY), geo_steps(lane, 64));
     }
-    if (nb) atomicOr(&snb, nb);                              // an LDS atomic
-    __syncthreads();
-    const u32 all = snb;
-    if (!(all || more)) return;                              // nothing changed: nothing is stored, nothing is marked
-    if (tid == 0) {
-        atomicAdd(counters, 1ull);                           // once per workgroup that changed something
-        if (more) dirty_next[tile] = 1u;                     // the round bound was hit
-    }
-    if (tid < 27 && tid != 13 && ((all >> tid) & 1)) {
-        const int dz = tid / 9 - 1, dy = (tid / 3) % 3 - 1, dx = tid % 3 - 1;
-        const int steps = (dz != 0) + (dy != 0) + (dx != 0);
-        const int tzn = (nz + GEO_TZ - 1) / GEO_TZ;
-        const int nbz = bz + dz, nby = by + dy, nbx = bx + dx;
-        if ((CONN == 26 || steps == 1) && nbz >= 0 && nbz < tzn && nby >= 0 && nby < ty && nbx >= 0 && nbx < wx)
-            dirty_next[((int64_t)nbz * ty + nby) * wx + nbx] = 1u;
-    }
+    geo_leave<CONN>(nb, more, &snb, tile, t, nz, ty, wx, dirty_next, counters);
 }
 
 // The cut: a wave takes ZONE_CUT_WORDS consecutive words one after the other, a lane is one voxel of the word.  A set voxel p goes
@@ -620,13 +482,8 @@ TOMO_API int tomo_geo_sweep(const uint64_t *bits, int nz, int ny, int nx, int co
         return TOMO_E_ARG;
     const int r = geo_grid(nz, ny, nx, &g);
     if (r != TOMO_OK) return r;
-    const dim3 grid((unsigned)g.tiles), block(GEO_THREADS);
-    if (connectivity == 6)
-        hipLaunchKernelGGL(geo_sweep_kernel<6>, grid, block, 0, (hipStream_t)stream, (const u64 *)bits, nz, ny, nx, (int)g.wx, (int)g.ty,
-                           wxy, wz, dist, dirty_cur, dirty_next, counters);
-    else
-        hipLaunchKernelGGL(geo_sweep_kernel<26>, grid, block, 0, (hipStream_t)stream, (const u64 *)bits, nz, ny, nx, (int)g.wx, (int)g.ty,
-                           wxy, wz, dist, dirty_cur, dirty_next, counters);
+    geo_launch<geo_sweep_kernel<6>, geo_sweep_kernel<26>>(connectivity, dim3((unsigned)g.tiles), stream, (const u64 *)bits, nz, ny, nx,
+                                                          (int)g.wx, (int)g.ty, wxy, wz, dist, dirty_cur, dirty_next, counters);
     return tomo_status();
 }
 
@@ -664,13 +521,9 @@ TOMO_API int tomo_zone_sweep(const uint64_t *bits, int nz, int ny, int nx, int c
         return TOMO_E_ARG;
     const int r = geo_grid(nz, ny, nx, &g);
     if (r != TOMO_OK) return r;
-    const dim3 grid((unsigned)g.tiles), block(GEO_THREADS);
-    if (connectivity == 6)
-        hipLaunchKernelGGL(zone_sweep_kernel<6>, grid, block, 0, (hipStream_t)stream, (const u64 *)bits, nz, ny, nx, (int)g.wx, (int)g.ty,
-                           wxy, wz, dist, (int *)zone, dirty_cur, dirty_next, counters);
-    else
-        hipLaunchKernelGGL(zone_sweep_kernel<26>, grid, block, 0, (hipStream_t)stream, (const u64 *)bits, nz, ny, nx, (int)g.wx, (int)g.ty,
-                           wxy, wz, dist, (int *)zone, dirty_cur, dirty_next, counters);
+    geo_launch<zone_sweep_kernel<6>, zone_sweep_kernel<26>>(connectivity, dim3((unsigned)g.tiles), stream, (const u64 *)bits, nz, ny, nx,
+                                                            (int)g.wx, (int)g.ty, wxy, wz, dist, (int *)zone, dirty_cur, dirty_next,
+                                                            counters);
     return tomo_status();
 }
 
@@ -683,12 +536,8 @@ TOMO_API int tomo_zone_cut(const uint64_t *bits, const int32_t *zone, int nz, in
         return TOMO_E_ARG;
     const int r = geo_grid(nz, ny, nx, &g);
     if (r != TOMO_OK) return r;
-    const dim3 grid((unsigned)ceil_div64(ceil_div64(g.words, ZONE_CUT_WORDS) * 64, GEO_THREADS)), block(GEO_THREADS);
-    if (connectivity == 6)
-        hipLaunchKernelGGL(zone_cut_kernel<6>, grid, block, 0, (hipStream_t)stream, (const u64 *)bits, (const int *)zone, g.words, nz, ny,
-                           nx, (int)g.wx, (u64 *)out, counter);
-    else
-        hipLaunchKernelGGL(zone_cut_kernel<26>, grid, block, 0, (hipStream_t)stream, (const u64 *)bits, (const int *)zone, g.words, nz, ny,
-                           nx, (int)g.wx, (u64 *)out, counter);
+    const dim3 grid((unsigned)ceil_div64(ceil_div64(g.words, ZONE_CUT_WORDS) * 64, GEO_THREADS));
+    geo_launch<zone_cut_kernel<6>, zone_cut_kernel<26>>(connectivity, grid, stream, (const u64 *)bits, (const int *)zone, g.words, nz, ny, nx,
+                                                        (int)g.wx, (u64 *)out, counter);
     return tomo_status();
 }

@@ -5,7 +5,7 @@
 // g(p) = max(m'(p), min(f(p), max over the set neighbours q of g(q))), m' = min(marker, f).  Minima and maxima only, of values
 // that are already present: the operator is monotone, values only rise through the finite set of the inputs, so there is ONE
 // least fixed point above m' and every order of updates ends there.  It is tomo_geo_sweep's argument turned round, and so is
-// the kernel: the same tiles (geo_tiles.h), flags, rounds and marks.
+// the kernel: the same tiles, flags, rounds and marks, on the skeleton of geo_tiles.h.
 //
 // Order.  Values are compared through recon_key(), an order-preserving uint32 image of the float: sign and magnitude folded
 // onto one ascending axis around 0x80000000.  -0.0 and +0.0 share a key, the keys of the finite values and the two infinities
@@ -48,18 +48,13 @@ __global__ __launch_bounds__(GEO_THREADS) void recon_seed_kernel(const u64 *__re
                                                                  const float *__restrict__ marker, int mode, float h, int64_t nwords,
                                                                  int nx, int wx, float *__restrict__ g, unsigned long long *counters)
 {
-    const int64_t t = (int64_t)blockIdx.x * GEO_THREADS + threadIdx.x;
-    const int64_t word = t >> 6;                             // the same for the 64 lanes of a wave
-    if (word >= nwords) return;
-    const int64_t row = word / wx;
-    const int w = (int)(word - row * wx);
-    const int b = (int)(t & 63);
-    const int x = 64 * w + b;
+    GeoLane p;
+    if (!geo_lane(nwords, wx, &p)) return;
     float out = 0.0f;
     bool nan = false, work = false;
-    if (x < nx && ((bits[word] >> b) & 1)) {                 // below nx: no tail bit is read
-        const float f = mask[row * nx + x];
-        const float m = mode == 0 ? marker[row * nx + x] : mode == 1 ? f - h : f;
+    if (p.x < nx && ((bits[p.word] >> p.b) & 1)) {           // below nx: no tail bit is read
+        const float f = mask[p.row * nx + p.x];
+        const float m = mode == 0 ? marker[p.row * nx + p.x] : mode == 1 ? f - h : f;
         nan = recon_nan(f) || recon_nan(m);
         const u32 kf = recon_key(f);
         u32 km = recon_key(m);
@@ -68,9 +63,9 @@ __global__ __launch_bounds__(GEO_THREADS) void recon_seed_kernel(const u64 *__re
         out = recon_value(k);
         work = k < kf;
     }
-    if (x < nx) g[row * nx + x] = out;
+    if (p.x < nx) g[p.row * nx + p.x] = out;
     const u64 nans = __ballot(nan), works = __ballot(work);
-    if (b == 0) {
+    if (p.b == 0) {
         const unsigned long long flags = (nans ? RECON_F_NAN : 0ull) | (works ? RECON_F_WORK : 0ull);
         if (flags & ~__atomic_load_n(counters + 1, __ATOMIC_RELAXED)) atomicOr(counters + 1, flags);
     }
@@ -95,7 +90,8 @@ __device__ static inline u32 recon_reach(const u32 *__restrict__ p)
     return c;
 }
 
-// interior row r = wave + 4 k of a thread -> its place in the halo box, without the lane
+// interior row r = wave + 4 k of a thread -> its place in the halo box, without the lane.  geo_box_at() is the same place; with
+// it the rounds of the 26-neighbour instance ran 3 to 5 % longer (profiles/r37_sweep_skeleton.md), so the rounds keep this form.
 __device__ static inline int recon_box_row(int r) { return ((r / GEO_TY + 1) * GEO_HY + (r % GEO_TY + 1)) * GEO_HX + 1; }
 
 // Two workgroups per CU, the bound of its siblings: the compiler fills it (244 VGPRs, nothing spilled).  Bounds of 3 and 4
@@ -112,29 +108,9 @@ __global__ __launch_bounds__(GEO_THREADS, 2) void recon_sweep_kernel(const u64 *
 
     const int tid = threadIdx.x;
     const int64_t tile = blockIdx.x;
-    if (!__syncthreads_or((int)dirty_cur[tile])) return;     // uniform: every thread has read the flag before it is cleared
-    if (tid == 0) {
-        dirty_cur[tile] = 0u;
-        snb = 0u;
-    }
-    const int bx = (int)(tile % wx);
-    const int64_t rest = tile / wx;
-    const int by = (int)(rest % ty), bz = (int)(rest / ty);
-    const int z0 = bz * GEO_TZ - 1, y0 = by * GEO_TY - 1;    // the halo box starts here
-
-    if (tid < GEO_HROWS) {                                   // the masks of the 100 halo rows
-        const int z = z0 + tid / GEO_HY, y = y0 + tid % GEO_HY;
-        u64 mid = 0;
-        u32 side = 0;
-        if (z >= 0 && z < nz && y >= 0 && y < ny) {
-            const u64 *r = bits + ((int64_t)z * ny + y) * wx;
-            mid = geo_word(r, nx, wx, bx);
-            if (bx > 0 && (geo_word(r, nx, wx, bx - 1) >> 63)) side |= 1u;
-            if (bx + 1 < wx && (geo_word(r, nx, wx, bx + 1) & 1)) side |= 2u;
-        }
-        smid[tid] = mid;
-        sside[tid] = side;
-    }
+    if (!geo_enter(dirty_cur, tile, &snb)) return;
+    const GeoTile t = geo_tile(tile, wx, ty);
+    geo_halo_masks(bits, nz, ny, nx, wx, t, smid, sside);
     __syncthreads();
 
     // the thread's 16 voxels: ceiling and value in registers.  A set voxel lies inside the stack and below nx.
@@ -143,10 +119,10 @@ __global__ __launch_bounds__(GEO_THREADS, 2) void recon_sweep_kernel(const u64 *
     u32 live = 0, moved = 0;                                 // bit k: voxel k is set and below its ceiling / has changed since the load
 #pragma unroll
     for (int k = 0; k < GEO_PER; k++) {
-        const int r = wave + 4 * k;                          // interior row: z = r / TY, y = r % TY
+        const int r = wave + 4 * k, lz = r / GEO_TY, ly = r % GEO_TY;
         f[k] = v[k] = 0u;
-        if ((smid[(r / GEO_TY + 1) * GEO_HY + (r % GEO_TY + 1)] >> lane) & 1) {
-            const int64_t at = ((int64_t)(z0 + 1 + r / GEO_TY) * ny + (y0 + 1 + r % GEO_TY)) * nx + (64 * bx + lane);
+        if ((smid[geo_halo_row(lz, ly)] >> lane) & 1) {
+            const int64_t at = geo_voxel(t, lz, ly, lane, ny, nx);
             f[k] = recon_key(mask[at]);
             v[k] = recon_key(g[at]);
             if (v[k] < f[k]) live |= 1u << k;
@@ -156,21 +132,12 @@ __global__ __launch_bounds__(GEO_THREADS, 2) void recon_sweep_kernel(const u64 *
 
     for (int i = tid; i < GEO_BOX; i += GEO_THREADS) {
         const int hr = i / GEO_HX, xx = i - hr * GEO_HX;
-        bool set;
-        if (xx == 0) set = sside[hr] & 1u;
-        else if (xx == GEO_HX - 1) set = (sside[hr] >> 1) & 1u;
-        else set = (smid[hr] >> (xx - 1)) & 1;
-        u32 key = 0u;
-        if (set) {
-            const int z = z0 + hr / GEO_HY, y = y0 + hr % GEO_HY;
-            key = recon_key(g[((int64_t)z * ny + y) * nx + (64 * bx + xx - 1)]);
-        }
-        box[i] = key;
+        box[i] = geo_halo_set(smid, sside, hr, xx) ? recon_key(g[geo_halo_voxel(t, hr, xx, ny, nx)]) : 0u;
     }
     __syncthreads();
 
     int more = 1, round = 0;
-    for (; round < GEO_ROUNDS && more; round++) {            // bounded: a tile that needs more marks itself below
+    for (; round < GEO_ROUNDS && more; round++) {            // bounded: a tile that needs more marks itself in geo_leave
         u32 now = 0;
 #pragma unroll
         for (int k = 0; k < GEO_PER; k++) {
@@ -198,36 +165,11 @@ __global__ __launch_bounds__(GEO_THREADS, 2) void recon_sweep_kernel(const u64 *
 #pragma unroll
     for (int k = 0; k < GEO_PER; k++) {
         if (!((moved >> k) & 1)) continue;
-        const int r = wave + 4 * k;
-        const int lz = r / GEO_TY, ly = r % GEO_TY;
-        g[((int64_t)(z0 + 1 + lz) * ny + (y0 + 1 + ly)) * nx + (64 * bx + lane)] = recon_value(v[k]);
-        const u32 zs = 2u | (lz == 0 ? 1u : 0u) | (lz == GEO_TZ - 1 ? 4u : 0u);     // bit 0 / 1 / 2: step -1 / 0 / +1
-        const u32 ys = 2u | (ly == 0 ? 1u : 0u) | (ly == GEO_TY - 1 ? 4u : 0u);
-        const u32 xs = 2u | (lane == 0 ? 1u : 0u) | (lane == 63 ? 4u : 0u);
-#pragma unroll
-        for (int a = 0; a < 3; a++)
-#pragma unroll
-            for (int b = 0; b < 3; b++)
-#pragma unroll
-                for (int c = 0; c < 3; c++)
-                    if (((zs >> a) & 1) && ((ys >> b) & 1) && ((xs >> c) & 1)) nb |= 1u << (9 * a + 3 * b + c);
+        const int r = wave + 4 * k, lz = r / GEO_TY, ly = r % GEO_TY;
+        g[geo_voxel(t, lz, ly, lane, ny, nx)] = recon_value(v[k]);
+        nb |= geo_marks(geo_steps(lz, GEO_TZ), geo_steps(ly, GEO_TY), geo_steps(lane, 64));
     }
-    if (nb) atomicOr(&snb, nb);                              // an LDS atomic
-    __syncthreads();
-    const u32 all = snb;
-    if (!(all || more)) return;                              // nothing changed: nothing is stored, nothing is marked
-    if (tid == 0) {
-        atomicAdd(counters, 1ull);                           // once per workgroup that changed something
-        if (more) dirty_next[tile] = 1u;                     // the round bound was hit
-    }
-    if (tid < 27 && tid != 13 && ((all >> tid) & 1)) {
-        const int dz = tid / 9 - 1, dy = (tid / 3) % 3 - 1, dx = tid % 3 - 1;
-        const int steps = (dz != 0) + (dy != 0) + (dx != 0);
-        const int tzn = (nz + GEO_TZ - 1) / GEO_TZ;
-        const int nbz = bz + dz, nby = by + dy, nbx = bx + dx;
-        if ((CONN == 26 || steps == 1) && nbz >= 0 && nbz < tzn && nby >= 0 && nby < ty && nbx >= 0 && nbx < wx)
-            dirty_next[((int64_t)nbz * ty + nby) * wx + nbx] = 1u;
-    }
+    geo_leave<CONN>(nb, more, &snb, tile, t, nz, ty, wx, dirty_next, counters);
 }
 
 // ---------------------------------------------------------------------------------------------- below the ceiling
@@ -236,17 +178,12 @@ __global__ __launch_bounds__(GEO_THREADS) void recon_below_kernel(const u64 *__r
                                                                   const float *__restrict__ g, int64_t nwords, int nx, int wx,
                                                                   u64 *__restrict__ out)
 {
-    const int64_t t = (int64_t)blockIdx.x * GEO_THREADS + threadIdx.x;
-    const int64_t word = t >> 6;
-    if (word >= nwords) return;
-    const int64_t row = word / wx;
-    const int w = (int)(word - row * wx);
-    const int b = (int)(t & 63);
-    const int x = 64 * w + b;
+    GeoLane p;
+    if (!geo_lane(nwords, wx, &p)) return;
     bool bit = false;
-    if (x < nx && ((bits[word] >> b) & 1)) bit = recon_key(g[row * nx + x]) < recon_key(mask[row * nx + x]);
+    if (p.x < nx && ((bits[p.word] >> p.b) & 1)) bit = recon_key(g[p.row * nx + p.x]) < recon_key(mask[p.row * nx + p.x]);
     const u64 m = __ballot(bit);
-    if (b == 0) out[word] = m;
+    if (p.b == 0) out[p.word] = m;
 }
 
 // ---------------------------------------------------------------------------------------------- entry points
@@ -273,13 +210,8 @@ TOMO_API int tomo_recon_sweep(const uint64_t *bits, int nz, int ny, int nx, int 
         return TOMO_E_ARG;
     const int r = geo_grid(nz, ny, nx, &grid);
     if (r != TOMO_OK) return r;
-    const dim3 blocks((unsigned)grid.tiles), block(GEO_THREADS);
-    if (connectivity == 6)
-        hipLaunchKernelGGL(recon_sweep_kernel<6>, blocks, block, 0, (hipStream_t)stream, (const u64 *)bits, nz, ny, nx, (int)grid.wx,
-                           (int)grid.ty, mask, g, dirty_cur, dirty_next, counters);
-    else
-        hipLaunchKernelGGL(recon_sweep_kernel<26>, blocks, block, 0, (hipStream_t)stream, (const u64 *)bits, nz, ny, nx, (int)grid.wx,
-                           (int)grid.ty, mask, g, dirty_cur, dirty_next, counters);
+    geo_launch<recon_sweep_kernel<6>, recon_sweep_kernel<26>>(connectivity, dim3((unsigned)grid.tiles), stream, (const u64 *)bits, nz, ny,
+                                                              nx, (int)grid.wx, (int)grid.ty, mask, g, dirty_cur, dirty_next, counters);
     return tomo_status();
 }
 

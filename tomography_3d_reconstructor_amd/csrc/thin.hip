@@ -126,18 +126,16 @@ __global__ __launch_bounds__(GEO_THREADS) void thin_pass_kernel(u64 *bits, const
     const u32 seen = __hip_atomic_load(stamp + tile, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (seen + THIN_KINDS < tick) return;                    // uniform: idle for a whole iteration
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int bx = (int)(tile % wx);
-    const int64_t rest = tile / wx;
-    const int by = (int)(rest % ty), bz = (int)(rest / ty);
+    const GeoTile t = geo_tile(tile, wx, ty);
     const int sx = subfield & 1, sy = (subfield >> 1) & 1, sz = (subfield >> 2) & 1;
-    const int z = bz * GEO_TZ + sz + 2 * wave;               // a wave: one slice of the tile, its four rows of the y-parity
+    const int z = t.bz * GEO_TZ + sz + 2 * wave;             // a wave: one slice of the tile, its four rows of the y-parity
     if (z >= nz) return;
     const u64 parity = sx ? 0xaaaaaaaaaaaaaaaaull : 0x5555555555555555ull;
     u32 cleared = 0, nb = 0;                                 // nb: the neighbouring tiles to stamp, one bit per (dz, dy, dx)
     for (int j = 0; j < GEO_TY / 2; j++) {
-        const int y = by * GEO_TY + sy + 2 * j;
+        const int y = t.by * GEO_TY + sy + 2 * j;
         if (y >= ny) break;                                  // wave-uniform
-        const u64 mine = thin_load(bits, nz, ny, nx, wx, z, y, bx, lane);
+        const u64 mine = thin_load(bits, nz, ny, nx, wx, z, y, t.bx, lane);
         const u64 w = __shfl(mine, 13, 64);
         if (!w) continue;
         u64 towards;                                         // the neighbours in the direction of the sub-pass: -z +z -y +y -x +x
@@ -150,7 +148,7 @@ __global__ __launch_bounds__(GEO_THREADS) void thin_pass_kernel(u64 *bits, const
         default: towards = (w >> 1) | (__shfl(mine, 14, 64) << 63); break;
         }
         u64 cand = w & ~towards & parity;
-        if (anchors) cand &= ~anchors[((int64_t)z * ny + y) * wx + bx];
+        if (anchors) cand &= ~anchors[((int64_t)z * ny + y) * wx + t.bx];
         if (!cand) continue;                                 // wave-uniform
         const u32 pic = thin_picture(mine, lane);
         bool del = false;
@@ -160,22 +158,15 @@ __global__ __launch_bounds__(GEO_THREADS) void thin_pass_kernel(u64 *bits, const
         }
         const u64 gone = __ballot(del);
         if (!gone) continue;
-        if (lane == 0) bits[((int64_t)z * ny + y) * wx + bx] = w & ~gone;    // the one writer of this word; tail bits zero
+        if (lane == 0) bits[((int64_t)z * ny + y) * wx + t.bx] = w & ~gone;  // the one writer of this word; tail bits zero
         cleared += (u32)__popcll(gone);
-        const int lz = z - bz * GEO_TZ, ly = y - by * GEO_TY;
-        const u32 zs = 2u | (lz == 0 ? 1u : 0u) | (lz == GEO_TZ - 1 ? 4u : 0u);      // bit 0 / 1 / 2: step -1 / 0 / +1
-        const u32 ys = 2u | (ly == 0 ? 1u : 0u) | (ly == GEO_TY - 1 ? 4u : 0u);
-        const u32 xs = 2u | ((gone & 1ull) ? 1u : 0u) | ((gone >> 63) ? 4u : 0u);
-#pragma unroll
-        for (int a = 0; a < 3; a++)
-#pragma unroll
-            for (int b = 0; b < 3; b++)
-                if (((zs >> a) & 1) && ((ys >> b) & 1)) nb |= xs << (9 * a + 3 * b);
+        const u32 xs = 2u | ((gone & 1ull) ? 1u : 0u) | ((gone >> 63) ? 4u : 0u);      // a cleared voxel at either end of the word
+        nb |= geo_marks(geo_steps(z - t.bz * GEO_TZ, GEO_TZ), geo_steps(y - t.by * GEO_TY, GEO_TY), xs);
     }
     if (!cleared) return;                                    // wave-uniform
     if (lane == 0) atomicAdd(counters + THIN_SLOT_WORDS * (int)((4 * tile + wave) % THIN_SLOTS), (unsigned long long)cleared);
     if (lane < 27 && ((nb >> lane) & 1)) {                   // bit 13, this tile, is always among them
-        const int nbz = bz + lane / 9 - 1, nby = by + (lane / 3) % 3 - 1, nbx = bx + lane % 3 - 1;
+        const int nbz = t.bz + lane / 9 - 1, nby = t.by + (lane / 3) % 3 - 1, nbx = t.bx + lane % 3 - 1;
         if (nbz >= 0 && nbz < tzn && nby >= 0 && nby < ty && nbx >= 0 && nbx < wx)
             atomicMax(stamp + ((int64_t)nbz * ty + nby) * wx + nbx, tick);
     }
@@ -280,13 +271,9 @@ TOMO_API int tomo_thin_pass(uint64_t *bits, const uint64_t *anchors, int nz, int
         return TOMO_E_ARG;
     const int r = geo_grid(nz, ny, nx, &grid);
     if (r != TOMO_OK) return r;
-    const dim3 blocks((unsigned)grid.tiles), block(GEO_THREADS);
-    if (connectivity == 6)
-        hipLaunchKernelGGL(thin_pass_kernel<6>, blocks, block, 0, (hipStream_t)stream, (u64 *)bits, (const u64 *)anchors, nz, ny, nx,
-                           (int)grid.wx, (int)grid.ty, (int)grid.tz, curve ? 1 : 0, direction, subfield, (u32 *)stamp, (u32)tick, counters);
-    else
-        hipLaunchKernelGGL(thin_pass_kernel<26>, blocks, block, 0, (hipStream_t)stream, (u64 *)bits, (const u64 *)anchors, nz, ny, nx,
-                           (int)grid.wx, (int)grid.ty, (int)grid.tz, curve ? 1 : 0, direction, subfield, (u32 *)stamp, (u32)tick, counters);
+    geo_launch<thin_pass_kernel<6>, thin_pass_kernel<26>>(connectivity, dim3((unsigned)grid.tiles), stream, (u64 *)bits, (const u64 *)anchors,
+                                                          nz, ny, nx, (int)grid.wx, (int)grid.ty, (int)grid.tz, curve ? 1 : 0, direction,
+                                                          subfield, (u32 *)stamp, (u32)tick, counters);
     return tomo_status();
 }
 
