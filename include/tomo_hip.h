@@ -613,6 +613,64 @@ int tomo_thin_nodes(const uint64_t *bits, int nz, int ny, int nx, uint64_t *ends
 int tomo_thin_count(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
                     const uint32_t *rank, unsigned long long *tot, const uint64_t *other, const uint8_t *sel, const uint32_t *slot,
                     int64_t *out, int column, int columns, int64_t cap, int64_t cap_sel, void *stream);
+/* The branch table of a skeleton (csrc/branches.hip; no counterpart in the reference; AnalyzeSkeleton in BoneJ / MorphoLibJ and
+ * skan answer the same question).  One definition.
+ * S is any bit volume -- usually a skeleton, nothing assumes thinness.  Adjacency is always 26, outside the stack nothing is
+ * set, deg(p) is the number of set 26-neighbours of a set voxel p.
+ *   R  the REGULAR voxels: deg == 2.        N = S \ R  the NODE voxels: ends (deg 1), isolated voxels (0), junction voxels (>= 3).
+ *   A BRANCH is a 26-connected component of R.  Inside R a voxel has at most two R-neighbours: a path or a closed cycle.
+ *   A NODE is a 26-connected component of N.  An end voxel next to a junction voxel belongs to that junction's node (a
+ *   one-step spur is part of its node, no branch); a two-voxel object is one node without a branch.  A node is a FREE END when
+ *   it has exactly one voxel and that voxel has deg 1.
+ * An EDGE is an unordered pair of 26-adjacent set voxels: R-R inside one branch, N-N inside one node, R-N an ATTACHMENT of a
+ * branch to a node.  A path has exactly two attachments, counted with multiplicity (both may go to one node, or to one voxel),
+ * a cycle none.
+ * Length.  An edge belongs to a branch when at least one of its ends does.  It is counted once, at a regular voxel p of the
+ * branch: for a neighbour q in N always, for a neighbour q in R only when q is raster-later (one of the 13 forward neighbours
+ * of tomo_contact_count).  The count is filed in the slice k of p and in the column of tomo_cc_surface_hist for q - p: 0, 1, 2 =
+ * x, y, xy in the slice, 3 .. 6 = z, xz, yz, xyz towards slice k + 1, 7 .. 10 the same towards k - 1; so the entries of a branch
+ * stay inside the index box of its own voxels.  length = the sequential float64 sum of (double)count[k][c] * steps[k][c] in
+ * ascending k, then ascending c, no product contracted into an FMA -- tomo_cc_surface with directions == 13 and F = steps, the
+ * (nz, 11) table of step lengths sqrt(((dx mm_x)^2 + (dy mm_y)^2) + dzc^2), dzc = zc[k + 1] - zc[k] upward, zc[k] - zc[k - 1]
+ * downward, 0.0 where that slice does not exist.  The length includes the two attaching steps.
+ * Rows are in ascending label of the labelling of R under 26 (tomo_cc_label_runs), node rows in that of N.
+ *   tomo_branch_split   regular_out = R, nodes_out = N as bit volumes (every word written, tail bits zero); counters[0 .. 3] +=
+ *                       voxels, regular voxels, node voxels, isolated voxels.  tomo_thin_nodes' pass: a wave is a word, a lane
+ *                       a bit; no atomics on the volumes.
+ *   tomo_branch_hist    the histogram of the steps: arguments as tomo_cc_surface_hist over the run tables of R, then other = the
+ *                       bits of S.  hist uint64[11 * hist_cap], zeroed here: hist[11 * (off[c] + z - zmin[c]) + 0 .. 10] by the
+ *                       counting rule above, for the selected branches.  One thread per row of R: the rows in front of a voxel
+ *                       are read from S alone, the rows behind it from S and R (14 row windows), popcounts under the run
+ *                       masks, integer atomics only.  Guards: the bits of tomo_cc_surface_hist in tot[2].
+ *   tomo_branch_attach  over the same tables and the selection of tomo_cc_select: attach uint64 (cap_sel, 2) and attach_count
+ *                       uint64 (cap_sel), initialised here to (all ones, 0) and 0; per selected branch the minimum / maximum
+ *                       (64-bit atomicMin / atomicMax) of the flat index (z * ny + y) * nx + x of every node voxel beside one of
+ *                       its voxels, and the attachments added up.  A wave sends an atomic only for a run with an attachment.
+ *   tomo_branch_lookup  labels_out[i] = the label (1-based) under the given run tables of the voxel at flat index queries[i];
+ *                       0 where the voxel is clear and where the query is negative or past the volume.  One thread per query.
+ *                       The tables hold no run starts: the run of a voxel is counted from the start bits of its row
+ *                       (as tomo_cc_expand does), not searched.
+ *   tomo_branch_clear   out (!= in, != bits) = in & ~(the runs of `bits` whose component c has flagged[c] != 0); flagged uint8
+ *                       [n_flagged], n_flagged = the components of the tables.  One thread per word, as tomo_cc_fill_map; tail
+ *                       bits of out are zero.  Pruning applies it twice: the tables of R with the flags of the branches, then
+ *                       the tables of N with the flags of their free ends.
+ * TOMO_E_ARG for a null pointer, a non-positive size, an output that is an input or another output; TOMO_E_SIZE from 2^31
+ * words, runs, components, selected components or queries on.  All of it is decided before any device use.  Nobody waits on
+ * anybody; the bytes are the same on every run. */
+int tomo_branch_split(const uint64_t *bits, int nz, int ny, int nx, uint64_t *regular_out, uint64_t *nodes_out,
+                      unsigned long long *counters, void *stream);
+int tomo_branch_hist(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
+                     const uint32_t *rank, unsigned long long *tot, const int64_t *table, int64_t cap, const uint8_t *sel,
+                     const uint64_t *off, uint64_t *hist, int64_t hist_cap, const uint64_t *other, void *stream);
+int tomo_branch_attach(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
+                       const uint32_t *rank, unsigned long long *tot, const uint64_t *other, const uint8_t *sel, const uint32_t *slot,
+                       uint64_t *attach, uint64_t *attach_count, int64_t cap, int64_t cap_sel, void *stream);
+int tomo_branch_lookup(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
+                       const uint32_t *rank, unsigned long long *tot, int64_t cap, const int64_t *queries, int64_t n,
+                       int64_t *labels_out, void *stream);
+int tomo_branch_clear(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
+                      const uint32_t *rank, unsigned long long *tot, const uint8_t *flagged, int64_t n_flagged, const uint64_t *in,
+                      uint64_t *out, void *stream);
 /* The contact table between zones (csrc/contacts.hip; no counterpart in the reference): which zones touch, over how large an
  * interface, how wide the throat between them is and how long the way across.  One definition.
  * zones: int32 (nz, ny, nx), tomo_zone_sweep's map or any map.  A voxel TAKES PART when it is set and its entry is positive.

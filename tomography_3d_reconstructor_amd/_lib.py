@@ -120,6 +120,13 @@ SIGNATURES = {
     "tomo_thin_nodes": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p]),
     "tomo_thin_count": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i, _c_i, _c_i64, _c_i64,
                                _c_p]),
+    "tomo_branch_split": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p]),
+    "tomo_branch_hist": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p,
+                                _c_p]),
+    "tomo_branch_attach": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64,
+                                  _c_p]),
+    "tomo_branch_lookup": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p]),
+    "tomo_branch_clear": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p]),
     "tomo_contact_count": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_p, _c_p]),
     "tomo_contact_insert": (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
                                    _c_p, _c_p]),

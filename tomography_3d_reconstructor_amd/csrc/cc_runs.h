@@ -1,6 +1,8 @@
 // cc_runs.h -- the device-side vocabulary of the run tables (components.hip labels them, component_measures.hip measures
-// what they hold): rows and their runs, the union-find over run ids, which run a bit lies in, and the ROW PASS -- one thread
-// per row adds up what its runs give per component, a wave combines -- that every per-component quantity goes through.
+// what they hold, branches.hip measures the branches of a skeleton): rows and their runs, the union-find over run ids, which
+// run a bit lies in, and the ROW PASS -- one thread per row adds up what its runs give per component, a wave combines -- that
+// every per-component quantity goes through; at the end the per-slice histogram and the WINDOW WALK, the row pass for what a
+// voxel's neighbours decide, which component_measures.hip and branches.hip share.
 //
 // tot (device uint64[8]): [0] runs  [1] components  [2] flags (1: 2^31 runs or more, 2: more runs than the caller's buffers
 // hold, 4: a run id outside the tables -- the bits changed between the calls)  [3] label tomo_cc_filter(largest) kept (0: none)
@@ -338,3 +340,93 @@ struct CcSumAcc {
     __device__ void flush(u32 c) const { if (c < bound) atomicAdd(out + c, (unsigned long long)sum); }
     __device__ CcSumAcc combine(bool mine, u32) const { return {out, bound, wave_sum64(mine ? sum : 0)}; }
 };
+
+// ---------------------------------------------------------------------------------------------- the per-slice histograms
+#define CC_SURF 11                   // counters per component and slice of tomo_cc_surface_hist and tomo_branch_hist
+#define CC_SURF_CLASSES 7            // x, y, xy, z, xz, yz, xyz: the counters with up and down folded
+
+struct CcHist {
+    const u64 *table, *off;                                 // both NULL: the whole volume is component 0, one entry per slice
+    u64 *hist;
+    u64 total;                                              // entries of the histogram
+    u64 *flags;
+};
+
+// hist[SUMS * (off[c] + z - zmin[c]) + k] += v[k]: checked against the component's box and the histogram's length before the adds
+template <int SUMS>
+__device__ static inline void cc_hist_add(const CcHist &h, u32 c, u32 z, const u64 (&v)[SUMS])
+{
+    const u64 z0 = h.table ? h.table[(int64_t)c * CC_COLS + 1] : 0ull, z1 = h.table ? h.table[(int64_t)c * CC_COLS + 2] : h.total - 1;
+    const u64 pos = (h.off ? h.off[c] : 0ull) + ((u64)z - z0);
+    if (z < z0 || z > z1 || pos >= h.total) {
+        cc_flag(h.flags, CC_F_RANGE);
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < SUMS; k++)
+        if (SUMS == 1 || v[k]) atomicAdd(h.hist + SUMS * pos + k, v[k]);
+}
+
+// ---------------------------------------------------------------------------------------------- the window walk
+struct CcWin {                                               // three neighbouring words of one row, slid along x
+    u64 prv, cur, nxt;
+};
+
+__device__ static inline u64 cc_word_or0(const u64 *__restrict__ row, int nx, int wx, int w)
+{
+    return (row && w < wx) ? cc_word(row, nx, wx, w) : 0ull;
+}
+
+__device__ static inline u64 cc_xp(const CcWin &r) { return (r.cur >> 1) | (r.nxt << 63); }      // bit x = voxel x + 1
+__device__ static inline u64 cc_xm(const CcWin &r) { return (r.cur << 1) | (r.prv >> 63); }      // bit x = voxel x - 1
+
+// The WINDOW WALK: the row pass for what a voxel's neighbours decide.  One thread per row (z, y) slides CcWin windows of the row
+// r[0] and of NR - 1 neighbour rows along x (r[i] == NULL: a row outside the stack, it reads as 0) and, LABELLED, walks the runs
+// in every word (as cc_filter_kernel walks them): neighbouring runs of one component are added up, flushed when the component
+// changes -> the component + 1 the thread is left adding up.  Not LABELLED: no table is read, everything is component 1.  The
+// accumulator is the row pass's with, in place of add(run):
+//   void word(const CcWin *win)              a word of the row that holds a set bit: what every run of it shares
+//   void add(const CcWin *win, u64 mask)     the bits `mask` of that word belong to the component begun
+template <int NR, bool LABELLED, bool FILTER, class Acc>
+__device__ static inline u32 cc_window_walk(const u64 *const *r, int nx, int wx, u32 first, u32 nruns,
+                                            const u32 *__restrict__ parent, const u32 *__restrict__ rank, u64 *flags, Acc &acc)
+{
+    u32 comp = 0;
+    CcWin win[NR];
+#pragma unroll
+    for (int i = 0; i < NR; i++) {
+        win[i].prv = 0;
+        win[i].cur = cc_word_or0(r[i], nx, wx, 0);
+        win[i].nxt = cc_word_or0(r[i], nx, wx, 1);
+    }
+    CcWordRuns it = {0, first, false};
+    for (int w = 0; w < wx; w++) {
+        const u64 m = win[0].cur;
+        if (m) {
+            acc.word(win);
+            if (!LABELLED) {
+                cc_change(comp, 1u, acc);
+                acc.add(win, m);
+            }
+            it.m = LABELLED ? m : 0;
+            while (cc_word_runs_next(it)) {
+                if (it.run < nruns) {
+                    u32 c = cc_component(parent, rank, it.run) + 1;
+                    if constexpr (FILTER) c = acc.filter(c);
+                    c = cc_change(comp, c, acc);
+                    if (!FILTER || c) acc.add(win, it.mask);
+                } else {
+                    cc_flag(flags, CC_F_RANGE);
+                }
+            }
+        }
+        it.carry = (m >> 63) != 0;                          // the word ended inside a run
+#pragma unroll
+        for (int i = 0; i < NR; i++) {
+            win[i].prv = win[i].cur;
+            win[i].cur = win[i].nxt;
+            win[i].nxt = cc_word_or0(r[i], nx, wx, w + 2);
+        }
+    }
+    return comp;
+}

@@ -277,28 +277,6 @@ __device__ static inline u64 cc_squares_below(u64 n)
     return (n - 1) * n * (2 * n - 1) / 6;                   // n = 0: the wrapped factor meets a 0
 }
 
-struct CcHist {
-    const u64 *table, *off;                                 // both NULL: the whole volume is component 0, one entry per slice
-    u64 *hist;
-    u64 total;                                              // entries of the histogram
-    u64 *flags;
-};
-
-// hist[SUMS * (off[c] + z - zmin[c]) + k] += v[k]: checked against the component's box and the histogram's length before the adds
-template <int SUMS>
-__device__ static inline void cc_hist_add(const CcHist &h, u32 c, u32 z, const u64 (&v)[SUMS])
-{
-    const u64 z0 = h.table ? h.table[(int64_t)c * CC_COLS + 1] : 0ull, z1 = h.table ? h.table[(int64_t)c * CC_COLS + 2] : h.total - 1;
-    const u64 pos = (h.off ? h.off[c] : 0ull) + ((u64)z - z0);
-    if (z < z0 || z > z1 || pos >= h.total) {
-        cc_flag(h.flags, CC_F_RANGE);
-        return;
-    }
-#pragma unroll
-    for (int k = 0; k < SUMS; k++)
-        if (SUMS == 1 || v[k]) atomicAdd(h.hist + SUMS * pos + k, v[k]);
-}
-
 template <int SUMS>
 struct CcSliceSum {
     const CcHist &h;
@@ -667,18 +645,7 @@ TOMO_API int tomo_cc_moments(const int64_t *table, int64_t cap, unsigned long lo
 // Per word these are ANDs / ORs of the row's word with up to four neighbour rows and their shifts by one bit, carried across
 // the word boundaries; a run's share is the popcount of every term under the run's mask.  Rows outside the stack and bits at
 // x >= nx read as 0.
-struct CcWin {                                               // three neighbouring words of one row, slid along x
-    u64 prv, cur, nxt;
-};
-
-__device__ static inline u64 cc_word_or0(const u64 *__restrict__ row, int nx, int wx, int w)
-{
-    return (row && w < wx) ? cc_word(row, nx, wx, w) : 0ull;
-}
-
-__device__ static inline u64 cc_xp(const CcWin &r) { return (r.cur >> 1) | (r.nxt << 63); }      // bit x = voxel x + 1
-__device__ static inline u64 cc_xm(const CcWin &r) { return (r.cur << 1) | (r.prv >> 63); }      // bit x = voxel x - 1
-
+// (CcWin, cc_xp, cc_xm and the window walk itself: cc_runs.h)
 #define CC_EULER_POS 5
 #define CC_EULER_NEG 4
 
@@ -728,57 +695,6 @@ __device__ static inline u64 cc_euler_under(const u64 *pos, const u64 *neg, u64 
 #pragma unroll
     for (int i = 0; i < CC_EULER_NEG; i++) v -= __popcll(neg[i] & mask);
     return (u64)(int64_t)v;
-}
-
-// The WINDOW WALK: the row pass for what a voxel's neighbours decide.  One thread per row (z, y) slides CcWin windows of the row
-// r[0] and of NR - 1 neighbour rows along x (r[i] == NULL: a row outside the stack, it reads as 0) and, LABELLED, walks the runs
-// in every word (as cc_filter_kernel walks them): neighbouring runs of one component are added up, flushed when the component
-// changes -> the component + 1 the thread is left adding up.  Not LABELLED: no table is read, everything is component 1.  The
-// accumulator is the row pass's (cc_runs.h) with, in place of add(run):
-//   void word(const CcWin *win)              a word of the row that holds a set bit: what every run of it shares
-//   void add(const CcWin *win, u64 mask)     the bits `mask` of that word belong to the component begun
-template <int NR, bool LABELLED, bool FILTER, class Acc>
-__device__ static inline u32 cc_window_walk(const u64 *const *r, int nx, int wx, u32 first, u32 nruns,
-                                            const u32 *__restrict__ parent, const u32 *__restrict__ rank, u64 *flags, Acc &acc)
-{
-    u32 comp = 0;
-    CcWin win[NR];
-#pragma unroll
-    for (int i = 0; i < NR; i++) {
-        win[i].prv = 0;
-        win[i].cur = cc_word_or0(r[i], nx, wx, 0);
-        win[i].nxt = cc_word_or0(r[i], nx, wx, 1);
-    }
-    CcWordRuns it = {0, first, false};
-    for (int w = 0; w < wx; w++) {
-        const u64 m = win[0].cur;
-        if (m) {
-            acc.word(win);
-            if (!LABELLED) {
-                cc_change(comp, 1u, acc);
-                acc.add(win, m);
-            }
-            it.m = LABELLED ? m : 0;
-            while (cc_word_runs_next(it)) {
-                if (it.run < nruns) {
-                    u32 c = cc_component(parent, rank, it.run) + 1;
-                    if constexpr (FILTER) c = acc.filter(c);
-                    c = cc_change(comp, c, acc);
-                    if (!FILTER || c) acc.add(win, it.mask);
-                } else {
-                    cc_flag(flags, CC_F_RANGE);
-                }
-            }
-        }
-        it.carry = (m >> 63) != 0;                          // the word ended inside a run
-#pragma unroll
-        for (int i = 0; i < NR; i++) {
-            win[i].prv = win[i].cur;
-            win[i].cur = win[i].nxt;
-            win[i].nxt = cc_word_or0(r[i], nx, wx, w + 2);
-        }
-    }
-    return comp;
 }
 
 // chi per component: the terms of a word once, their popcounts under every run's mask
@@ -1104,9 +1020,7 @@ TOMO_API int tomo_cc_topology_rows(const int64_t *table, const int64_t *topo, in
 // A set neighbour of another component (diagonal contact under connectivity 6) is no transition, so only the bits decide: per
 // word the 26 words `t & ~neighbour`, popcounted under each run's mask.  The area is the sequential float64 sum over the
 // slices of count * factor (tomo_cc_surface); the factors carry the spacing and the direction weights (pipeline.py).
-#define CC_SURF 11                   // counters per component and slice
-#define CC_SURF_CLASSES 7            // x, y, xy, z, xz, yz, xyz: the counters with up and down folded
-
+// (CC_SURF counters per component and slice, CC_SURF_CLASSES with up and down folded: cc_runs.h)
 // the bits of mask whose neighbour in row r is clear: at the same x -> centre, at x + 1 and at x - 1 -> side
 __device__ static inline void cc_clear_beside(const CcWin &r, u64 mask, u64 &centre, u64 &side)
 {

@@ -25,12 +25,12 @@
 // be -- it then clears nothing, by the same argument -- so the rule changes the work and never the bytes.
 #include "cc_runs.h"
 #include "geo_tiles.h"
+#include "thin_picture.h"
 
 #define THIN_SLOTS 64                              // the cleared voxels are added up in that many counters, 128 bytes apart:
 #define THIN_SLOT_WORDS 16                         // atomics of many waves on ONE address queue up behind each other
 #define THIN_KINDS 48u                             // sub-passes of one iteration: a tile rests after that many idle ticks
 #define THIN_ALL 0x07ffffffu                       // the 27 bits of the cube
-#define THIN_CENTRE (1u << 13)
 #define THIN_X0 0x01249249u                        // the cells with dx = -1: bits 0, 3, 6, ...
 #define THIN_X2 (THIN_X0 << 2)                     // dx = +1
 #define THIN_Y0 0x001c0e07u                        // dy = -1: bits 0 .. 2 of every slice of nine
@@ -91,30 +91,7 @@ __device__ static inline bool thin_simple(u32 pic)
     return CONN == 26 ? (thin_one26(x) && thin_one6(c)) : (thin_one6(x) && thin_one26(c));
 }
 
-// The 27 words around word bx of row (z, y), one per lane 0 .. 26: lane 9 a + 3 b + c holds word bx + c - 1 of row
-// (z + a - 1, y + b - 1), its tail bits clear, 0 outside the stack.  No __restrict__: the volume is written while it is read.
-__device__ static inline u64 thin_load(const u64 *bits, int nz, int ny, int nx, int wx, int z, int y, int bx, int lane)
-{
-    if (lane >= 27) return 0ull;
-    const int zz = z + lane / 9 - 1, yy = y + (lane / 3) % 3 - 1, ww = bx + lane % 3 - 1;
-    if (zz < 0 || zz >= nz || yy < 0 || yy >= ny || ww < 0 || ww >= wx) return 0ull;
-    return geo_word(bits + ((int64_t)zz * ny + yy) * wx, nx, wx, ww);
-}
-
-// the picture of bit `lane` of the middle word from the wave-uniform words of thin_load: per row of the cube the three bits
-// at x - 1, x, x + 1, the outer ones from the side words at lanes 0 and 63
-__device__ static inline u32 thin_picture(u64 mine, int lane)
-{
-    u32 pic = 0;
-#pragma unroll
-    for (int r = 0; r < 9; r++) {
-        const u64 l = __shfl(mine, 3 * r, 64), m = __shfl(mine, 3 * r + 1, 64), h = __shfl(mine, 3 * r + 2, 64);
-        const u32 lo = lane > 0 ? (u32)(m >> (lane - 1)) & 1u : (u32)(l >> 63);
-        const u32 hi = lane < 63 ? (u32)(m >> (lane + 1)) & 1u : (u32)(h & 1ull);
-        pic |= (lo | (((u32)(m >> lane) & 1u) << 1) | (hi << 2)) << (3 * r);
-    }
-    return pic;
-}
+// (thin_load, the 27 words around a word, and thin_picture, a lane's picture out of them: thin_picture.h)
 
 // ---------------------------------------------------------------------------------------------- one sub-pass
 template <int CONN>

@@ -28,7 +28,9 @@ COUNTERS = dict.fromkeys(("na_hint_hit", "na_hint_miss", "mc3_hint_hit", "mc3_hi
                           "components_cavity_owners", "component_thickness", "components_value", "components_levels", "component_caliper",
                           "geodesic_calls", "geodesic_sweeps", "component_geodesic", "zone_calls", "zone_sweeps", "zone_cuts",
                           "separate_components", "zone_contacts", "contact_launches", "recon_calls", "recon_sweeps",
-                          "thin_calls", "thin_iterations", "thin_passes", "thin_nodes", "component_skeleton"), 0)
+                          "thin_calls", "thin_iterations", "thin_passes", "thin_nodes", "component_skeleton",
+                          "skeleton_branches", "branch_split", "skeleton_branches_hist", "branch_attach", "branch_lookup", "branch_clear",
+                          "prune_rounds"), 0)
 NA_HINTS = os.environ.get("TOMO_NA_HINTS", "1") not in ("", "0")   # marching_cubes: launch ahead of the first count download
 _NA_HINT = {}
 LIST_LIMIT = 2 ** 31        # active-voxel list entries / vertices / triangles one pass can index (int32 offsets in mc.hip, mesh.hip);
@@ -316,6 +318,8 @@ _MOMENTS = _Measurement("component_moments", ((torch.float64, (MOMENT_COLUMNS,))
 _SURFACE = _Measurement("component_surface", ((torch.float64, ()), (torch.int64, (SURFACE_CLASSES,))), 0, SURFACE_COUNTERS,
                         "surface counters per slice", "tomo_cc_surface_hist", "components_surface", "tomo_cc_surface")
 _TOPOLOGY = _Measurement("component_topology", ((torch.int64, (2 + TOPOLOGY_COLUMNS,)),))
+_BRANCHES = _Measurement("skeleton_branches", ((torch.float64, ()), (torch.int64, (SURFACE_CLASSES,))), 0, SURFACE_COUNTERS,
+                         "step counters per slice", "tomo_branch_hist", "skeleton_branches_hist", "tomo_cc_surface")
 
 
 @dataclass
@@ -336,7 +340,9 @@ class ComponentRuns:
     run of set bits in a row) and never per voxel.  Two host reads: the number of runs (it sizes the tables) and the
     counters after the labelling.  n = components; labels() / sizes() / keep() read the tables.
     One object serves every per-component measurement of its volume: properties(), moments(), topology_rows(), surface(),
-    thickness(), caliper(), geodesic() and skeleton() share the labelling, the measurement table and ONE selection, which the object owns (select).  background() is the same
+    thickness(), caliper(), geodesic(), skeleton() and branch_rows() share the labelling, the measurement table and ONE selection,
+    which the object owns (select); label_at() answers which component a voxel lies in, clear() removes flagged components from
+    a volume.  background() is the same
     kind of object for the complement: its enclosed components are the cavities of this volume (cavity_owners)."""
 
     def __init__(self, vol: BitVolume, connectivity=6):
@@ -697,6 +703,63 @@ class ComponentRuns:
         host, rows = self._download_checked("component_skeleton", ride, counts)
         self.last_skeleton = skel
         return _component_skeleton_from(host, rows)
+
+    def branch_rows(self, steps, whole: BitVolume, min_voxels=0):
+        """skeleton_branches' rows for this volume as the regular voxels R of `whole` (S): per branch with at least min_voxels
+        voxels, in ascending label -> host arrays (voxels, labels, length_mm, step_counts (m, 7), attach (m, 2), attach_count (m,)).
+        steps: branch_steps' (nz, 11).  The step histogram goes through the driver of the other measurements
+        (COMPONENT_HIST_BUDGET, its error); tomo_branch_attach runs over the same selection.  attach is (-1, -1) for a cycle."""
+        rule = _keep_rule(min_voxels)
+        voxels, labels, length, counts = self._rows(_BRANCHES, rule, steps, 13, hist_args=(_p(whole.bits),))
+        m = len(labels)
+        if m == 0:
+            return voxels, labels, length, counts.reshape(0, SURFACE_CLASSES), np.zeros((0, 2), dtype=np.int64), np.zeros(0, dtype=np.int64)
+        picked = self.select(rule[0], rule[1], max_voxels=rule[2], enclosed=rule[3])    # the selection _rows just made
+        dev = self.vol.device
+        attach = torch.empty((m, 2), dtype=torch.int64, device=dev)
+        count = torch.empty(m, dtype=torch.int64, device=dev)
+        COUNTERS["branch_attach"] += 1
+        _lib.check(_lib.lib().tomo_branch_attach(_p(self.bits), *self.vol.shape, *self._tables(), _p(self.tot), _p(whole.bits),
+                                                 _p(picked.sel), _p(picked.slot), _p(attach), _p(count), picked.table.shape[0], m,
+                                                 _stream()), "tomo_branch_attach")
+        attach, count = self._download_checked("skeleton_branches", attach, count)
+        attach[count == 0] = -1                                         # a cycle: the entry point's (all ones, 0)
+        return voxels, labels, length, counts.reshape(m, SURFACE_CLASSES), attach, count
+
+    def label_at(self, indices) -> torch.Tensor:
+        """The label (1 .. n) of the voxels at the flat indices (z * ny + y) * nx + x -> int64 device tensor of the shape of
+        `indices` (an int64 tensor on the volume's device, or anything np.asarray takes); 0 where the voxel is clear and where the
+        index is negative or past the volume.  One launch; its guards are read with the next _checked()."""
+        dev = self.vol.device
+        if not isinstance(indices, torch.Tensor):
+            indices = torch.from_numpy(np.ascontiguousarray(indices, dtype=np.int64))
+        if indices.dtype != torch.int64:
+            raise TypeError("indices must be int64")
+        q = indices.to(dev).contiguous()
+        out = torch.zeros_like(q)
+        if q.numel() == 0 or self.runs == 0:
+            return out
+        n = self.n or self._checked()
+        COUNTERS["branch_lookup"] += 1
+        _lib.check(_lib.lib().tomo_branch_lookup(_p(self.bits), *self.vol.shape, *self._tables(), _p(self.tot), n, _p(q), q.numel(),
+                                                 _p(out), _stream()), "tomo_branch_lookup")
+        return out
+
+    def clear(self, flagged: torch.Tensor, src: BitVolume) -> BitVolume:
+        """A NEW volume: `src` (any volume of this shape) without the runs of the components of THIS volume whose entry of
+        flagged (uint8 (n,), on the device) is set."""
+        n = self._checked() if self.runs else 0
+        if tuple(src.shape) != tuple(self.vol.shape) or flagged.dtype != torch.uint8 or flagged.numel() != n:
+            raise ValueError("clear: one uint8 flag per component and a volume of this shape")
+        bits = src.bits.contiguous()
+        if n == 0:
+            return BitVolume(bits.clone(), src.shape)
+        out = torch.empty_like(bits)
+        COUNTERS["branch_clear"] += 1
+        _lib.check(_lib.lib().tomo_branch_clear(_p(self.bits), *self.vol.shape, *self._tables(), _p(self.tot), _p(flagged.contiguous()), n,
+                                                _p(bits), _p(out), _stream()), "tomo_branch_clear")
+        self._checked()
+        return BitVolume(out, src.shape)
 
     def topology(self) -> torch.Tensor:
         """Per component 1..n: Euler number, cavities (enclosed voids, b2) and handles (tunnels, b1 = 1 - euler + cavities) of
@@ -2664,6 +2727,238 @@ def cavity_skeleton(vol: BitVolume, connectivity=6, min_voxels=0, max_voxels=Non
     lo, hi = _check_size_window(min_voxels, max_voxels)
     _skeleton_args(vol, curve, 32 - connectivity, anchors)
     return _complement_runs(vol, connectivity).skeleton(lo, False, curve, anchors, max_voxels=hi, enclosed=True)
+
+
+# ----------------------------------------------------------------------------- the branch table of a skeleton
+def branch_steps(slice_depths, nz, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0) -> np.ndarray:
+    """The length in mm of one step per slice and column of tomo_branch_hist, on the host -> float64 (nz, 11): columns 0 .. 2 the
+    steps x, y, xy in the slice, 3 .. 6 the steps z, xz, yz, xyz towards slice k + 1, 7 .. 10 the same towards k - 1.  An entry is
+    sqrt(((dx mm_x)^2 + (dy mm_y)^2) + dzc^2) in float64 with dzc = zc[k + 1] - zc[k] upward, zc[k] - zc[k - 1] downward (zc: the
+    slice centres of distance_positions) and 0.0 where that slice does not exist -- no voxel steps there.  Rounded to float32,
+    the entries are geodesic_weights'.  slice_depths=None: depth 1.0 per slice."""
+    zt, _, _ = distance_positions(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x)        # the argument checks
+    zc = zt[1:-1]
+    nz = len(zc)
+    mm_y, mm_x = float(mm_per_pixel_y), float(mm_per_pixel_x)
+    up, down = np.zeros(nz), np.zeros(nz)
+    up[:-1] = zc[1:] - zc[:-1]
+    down[1:] = zc[1:] - zc[:-1]
+    out = np.empty((nz, SURFACE_COUNTERS), dtype=np.float64)
+    for cls, (az, ay, ax) in enumerate(_SURFACE_CLASS_STEPS):
+        plane = (ax * mm_x) * (ax * mm_x) + (ay * mm_y) * (ay * mm_y)
+        if az == 0:
+            out[:, cls] = np.sqrt(plane + 0.0 * 0.0)
+        else:
+            out[:, cls] = np.sqrt(plane + up * up)
+            out[:, cls + 4] = np.sqrt(plane + down * down)
+    return out
+
+
+@dataclass
+class SkeletonBranchRows:
+    """The branches of skeleton_branches: host arrays, one row per selected branch in ascending label."""
+    label: np.ndarray            # int64 (m,): the label of the branch in ComponentRuns(regular, 26)
+    voxels: np.ndarray           # int64 (m,)
+    length_mm: np.ndarray        # float64 (m,): the two attaching steps included
+    step_counts: np.ndarray      # int64 (m, 7): the edges per class x, y, xy, z, xz, yz, xyz
+    attach_index: np.ndarray     # int64 (m, 2): the flat indices of the attached node voxels, lo <= hi; -1, -1 for a cycle
+    nodes: np.ndarray            # int64 (m, 2): the labels of those voxels' nodes; 0, 0 for a cycle
+    chord_mm: np.ndarray         # float64 (m,): the distance between the two attached voxels; nan for a cycle
+    tortuosity: np.ndarray       # float64 (m,): length / chord; inf where the chord is 0, nan for a cycle
+    kind: np.ndarray             # int64 (m,): 0 closed cycle, 1 both nodes free ends, 2 exactly one (a spur), 3 neither
+
+    def __len__(self):
+        return len(self.label)
+
+
+@dataclass
+class SkeletonNodeRows:
+    """The nodes of skeleton_branches: host arrays, one row per node in ascending label."""
+    label: np.ndarray            # int64 (n,): the label of the node in ComponentRuns(node_voxels, 26)
+    voxels: np.ndarray           # int64 (n,)
+    end_voxels: np.ndarray       # int64 (n,): its voxels with at most one set neighbour
+    junction_voxels: np.ndarray  # int64 (n,): ... with three or more
+    branches: np.ndarray         # int64 (n,): the attachments of the selected branches, with multiplicity
+    index_box: np.ndarray        # int64 (n, 6): zmin, zmax, ymin, ymax, xmin, xmax, inclusive
+    centroid_index: np.ndarray   # float64 (n, 3)
+    centroid_mm: np.ndarray      # float64 (n, 3): component_properties' centroid
+    free_end: np.ndarray         # bool (n,): one voxel, and that voxel has exactly one set neighbour
+
+    def __len__(self):
+        return len(self.label)
+
+
+@dataclass
+class SkeletonBranches:
+    """skeleton_branches' answer."""
+    branches: SkeletonBranchRows
+    nodes: SkeletonNodeRows
+    regular: BitVolume           # on the device: the set voxels with exactly two set 26-neighbours
+    node_voxels: BitVolume       # ... and all the others
+    voxels: int
+    regular_voxels: int
+    node_voxel_count: int
+    isolated: int
+
+
+@dataclass
+class PrunedSkeleton:
+    """prune_skeleton's answer."""
+    volume: BitVolume            # a NEW volume
+    removed_branches: int
+    removed_voxels: int          # the voxels of those branches and the free ends they hung from
+    rounds: int                  # the rounds that removed something
+
+
+def _branch_args(skel, slice_depths, mm_per_pixel_y, mm_per_pixel_x, min_voxels=0):
+    """The argument checks of the branch calls, all on the host -> (steps, zc, mm_y, mm_x, min_voxels)."""
+    if not isinstance(skel, BitVolume):
+        raise TypeError("skel must be a BitVolume")
+    steps = branch_steps(slice_depths, skel.shape[0], mm_per_pixel_y, mm_per_pixel_x)
+    zt, _, _ = distance_positions(slice_depths, skel.shape[0], mm_per_pixel_y, mm_per_pixel_x)
+    return steps, zt[1:-1].copy(), float(mm_per_pixel_y), float(mm_per_pixel_x), _whole_size(min_voxels, "min_voxels")
+
+
+def _branch_rows_from(shape, zc, mm_y, mm_x, voxels, labels, length, counts, attach, count, node_of, free_end) -> SkeletonBranchRows:
+    """Host arithmetic on the downloaded rows.  chord_mm = sqrt(((dx)^2 + (dy)^2) + dz^2) between the two attached voxels at
+    (zc[k], j * mm_y, i * mm_x)."""
+    nz, ny, nx = shape
+    m = len(labels)
+    cycle = count == 0
+    at = np.where(attach < 0, 0, attach)
+    k, rest = at // (ny * nx), at % (ny * nx)
+    pz, py, px = zc[k] if m else np.zeros((0, 2)), (rest // nx) * mm_y, (rest % nx) * mm_x
+    dz, dy, dx = pz[:, 1] - pz[:, 0], py[:, 1] - py[:, 0], px[:, 1] - px[:, 0]
+    chord = np.where(cycle, np.nan, np.sqrt((dx * dx + dy * dy) + dz * dz))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        tortuosity = np.where(cycle, np.nan, np.where(chord == 0, np.inf, length / chord))
+    free = np.concatenate([[False], free_end])[node_of].reshape(m, 2)
+    kind = np.where(cycle, 0, 3 - free.sum(axis=1)).astype(np.int64)
+    return SkeletonBranchRows(labels, voxels, length, counts, attach, node_of, chord, tortuosity, kind)
+
+
+def _empty_branch_rows() -> SkeletonBranchRows:
+    i, f = (lambda *s: np.zeros(s, dtype=np.int64)), (lambda *s: np.zeros(s, dtype=np.float64))
+    return SkeletonBranchRows(i(0), i(0), f(0), i(0, SURFACE_CLASSES), i(0, 2), i(0, 2), f(0), f(0), i(0))
+
+
+def _empty_node_rows() -> SkeletonNodeRows:
+    i, f = (lambda *s: np.zeros(s, dtype=np.int64)), (lambda *s: np.zeros(s, dtype=np.float64))
+    return SkeletonNodeRows(i(0), i(0), i(0), i(0), i(0), i(0, 6), f(0, 3), f(0, 3), np.zeros(0, dtype=bool))
+
+
+def _skeleton_branches(skel: BitVolume, args, slice_depths):
+    """-> (SkeletonBranches, the ComponentRuns of R or None, the ComponentRuns of N or None)."""
+    steps, zc, mm_y, mm_x, min_voxels = args
+    L, dev = _lib.lib(), skel.device
+    bits = skel.bits.contiguous()
+    whole = BitVolume(bits, skel.shape)
+    regular, node_voxels = BitVolume(torch.empty_like(bits), skel.shape), BitVolume(torch.empty_like(bits), skel.shape)
+    counters = torch.zeros(4, dtype=torch.int64, device=dev)
+    COUNTERS["skeleton_branches"] += 1
+    COUNTERS["branch_split"] += 1
+    _lib.check(L.tomo_branch_split(_p(bits), *skel.shape, _p(regular.bits), _p(node_voxels.bits), _p(counters), _stream()),
+               "tomo_branch_split")
+    voxels, regular_voxels, node_count, isolated = (int(v) for v in _download(counters))
+    branches, nodes, runs_r, runs_n, rows = _empty_branch_rows(), _empty_node_rows(), None, None, None
+    if regular_voxels:                                                  # the branches: a labelling of R, the steps, the attachments
+        runs_r = ComponentRuns(regular, 26)
+        rows = runs_r.branch_rows(steps, whole, min_voxels)
+    if node_count:                                                      # the nodes: a labelling of N, its table, its ends and junctions
+        runs_n = ComponentRuns(node_voxels, 26)
+        p = runs_n.properties(_slice_weights(slice_depths, skel.shape[0], mm_y, mm_x), mm_y, mm_x)
+        picked = runs_n.select()
+        marks = _skeleton_nodes(whole)
+        kinds = torch.zeros((picked.m, 2), dtype=torch.int64, device=dev)
+        for column, other in enumerate((marks.ends, marks.junctions)):
+            _lib.check(L.tomo_thin_count(_p(runs_n.bits), *skel.shape, *runs_n._tables(), _p(runs_n.tot), _p(other.bits), _p(picked.sel),
+                                         _p(picked.slot), _p(kinds), column, 2, picked.table.shape[0], picked.m, _stream()),
+                       "tomo_thin_count")
+        (kinds,) = runs_n._download_checked("skeleton_branches", kinds)
+        ends, junctions = kinds[:, 0].copy(), kinds[:, 1].copy()
+        nodes = SkeletonNodeRows(p.labels, p.voxels, p.voxels - junctions, junctions, np.zeros(len(p), dtype=np.int64), p.index_box,
+                                 p.centroid_index, p.centroid_mm, (p.voxels == 1) & (ends == 1))
+    if rows is not None:                                                # which nodes the attached voxels lie in
+        vox, labels, length, counts, attach, count = rows
+        node_of = np.zeros((len(labels), 2), dtype=np.int64)
+        if len(labels) and runs_n is not None:
+            node_of = runs_n.label_at(torch.from_numpy(attach).to(dev)).cpu().numpy()
+            runs_n._checked()
+        branches = _branch_rows_from(skel.shape, zc, mm_y, mm_x, vox, labels, length, counts, attach, count, node_of, nodes.free_end)
+        nodes.branches = np.bincount(node_of[count > 0].reshape(-1), minlength=len(nodes) + 1)[1:].astype(np.int64)
+    return SkeletonBranches(branches, nodes, regular, node_voxels, voxels, regular_voxels, node_count, isolated), runs_r, runs_n
+
+
+def skeleton_branches(skel: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, min_voxels=0) -> SkeletonBranches:
+    """The branch table of a skeleton (or of any volume: nothing assumes thinness) -> SkeletonBranches: how many branches it has,
+    how long each is in mm under the real slice depths, which nodes it joins and how tortuous it is (AnalyzeSkeleton of BoneJ /
+    MorphoLibJ and skan answer the same question).  One definition (include/tomo_hip.h): under the 26-adjacency a set voxel
+    with exactly two set neighbours is REGULAR, every other one a NODE voxel; a branch is a component of the regular voxels -- a
+    path or a closed cycle --, a node a component of the node voxels (an end next to a junction belongs to the junction's node,
+    two voxels are one node without a branch), a free end a one-voxel node with one neighbour.  A path is attached to node
+    voxels by exactly two edges.  length_mm adds up every edge with an end in the branch, the two attaching steps included:
+    the sequential float64 sum, slice by slice and column by column, of count * branch_steps(...).  kind: 0 a closed cycle, 1
+    both nodes are free ends (a plain fibre), 2 exactly one is (a terminal branch, a spur), 3 neither.  min_voxels: only the
+    branches of at least that many voxels get a row; nodes.branches then counts the attachments of those.
+    On the device: tomo_branch_split, one ComponentRuns for the regular and one for the node voxels, tomo_branch_hist behind the
+    driver of the per-component measurements (88 bytes per slice of the box of every selected branch; beyond
+    COMPONENT_HIST_BUDGET bytes for more than one branch: its TomoError) with tomo_cc_surface adding up, tomo_branch_attach,
+    and tomo_branch_lookup for the nodes of the attached voxels; the nodes' ends and junctions come from tomo_thin_nodes under
+    the node tables (tomo_thin_count).  Memory scales with the runs, the branches and their slices, never with the voxels.
+    An empty volume launches nothing past the split; one without regular voxels labels its nodes and returns zero branch rows.
+    Arguments are checked before the first launch."""
+    args = _branch_args(skel, slice_depths, mm_per_pixel_y, mm_per_pixel_x, min_voxels)
+    return _skeleton_branches(skel, args, slice_depths)[0]
+
+
+PRUNE_ROUND_LIMIT = 1 << 16          # a guard against an endless host loop, no tuning knob; read when called
+
+
+def _check_rounds(rounds):
+    if rounds is None:
+        return None
+    if isinstance(rounds, (bool, np.bool_)) or not isinstance(rounds, (int, np.integer)) or rounds < 0:
+        raise ValueError("rounds must be a non-negative whole number or None")
+    return int(rounds)
+
+
+def prune_skeleton(skel: BitVolume, min_length_mm, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, rounds=1) -> PrunedSkeleton:
+    """Remove the short terminal branches of a skeleton -> PrunedSkeleton with a NEW volume; the input is left untouched.  One
+    round removes every branch of kind 2 of skeleton_branches -- exactly one of its nodes is a free end -- with length_mm <
+    min_length_mm, together with the free-end voxel it hangs from; the node at its other end stays.  A pendant path is a chain
+    of simple-point deletions, so components, cavities and handles are the input's.  rounds=None repeats the round on the
+    table of the pruned volume until one removes nothing (a round only merges branches into longer ones, so this ends;
+    PRUNE_ROUND_LIMIT guards the loop).  Plain fibres (kind 1) and cycles are never touched.  On the device a round is
+    skeleton_branches and two tomo_branch_clear: the tables of the regular voxels with the flags of the branches, then the
+    tables of the node voxels with the flags of their free ends.  Arguments are checked before the first launch."""
+    args = _branch_args(skel, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    min_length_mm = float(min_length_mm)
+    if math.isnan(min_length_mm):
+        raise ValueError("min_length_mm must be a number")
+    rounds = _check_rounds(rounds)
+    dev = skel.device
+    vol = BitVolume(skel.bits.contiguous().clone(), skel.shape)
+    removed_branches = removed_voxels = done = 0
+    while rounds is None or done < rounds:
+        if done >= int(PRUNE_ROUND_LIMIT):
+            raise _lib.TomoError("prune_skeleton: no fixed point after %d rounds (PRUNE_ROUND_LIMIT)" % done)
+        t, runs_r, runs_n = _skeleton_branches(vol, args, slice_depths)
+        b = t.branches
+        gone = (b.kind == 2) & (b.length_mm < min_length_mm)
+        if not gone.any():
+            break
+        COUNTERS["prune_rounds"] += 1
+        flags_r = np.zeros(runs_r.n, dtype=np.uint8)
+        flags_r[b.label[gone] - 1] = 1
+        ends = b.nodes[gone]
+        ends = ends[np.concatenate([[False], t.nodes.free_end])[ends]]   # of the two nodes of a spur the free end
+        flags_n = np.zeros(runs_n.n, dtype=np.uint8)
+        flags_n[ends - 1] = 1
+        vol = runs_n.clear(torch.from_numpy(flags_n).to(dev), runs_r.clear(torch.from_numpy(flags_r).to(dev), vol))
+        removed_branches += int(gone.sum())
+        removed_voxels += int(b.voxels[gone].sum()) + len(ends)
+        done += 1
+    return PrunedSkeleton(vol, removed_branches, removed_voxels, done)
 
 
 def local_thickness(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, radii_mm=None,

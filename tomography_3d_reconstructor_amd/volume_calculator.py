@@ -330,6 +330,53 @@ def skeleton_report(voxel_data, connectivity=26, curve=True):
             'junction_voxels': int(nodes.junction_voxels), 'isolated': int(nodes.isolated), 'iterations': int(iterations)}
 
 
+def skeleton_branch_report(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=26, curve=True, prune_mm=0.0,
+                           prune_rounds=1):
+    """The branch table of the skeleton of a volume (no counterpart in the reference; AnalyzeSkeleton of BoneJ answers the same
+    question): the volume is thinned as skeleton_report thins it, short spurs are pruned when prune_mm > 0
+    (pipeline.prune_skeleton: terminal branches shorter than prune_mm, prune_rounds rounds, None = until nothing goes), then
+    pipeline.skeleton_branches -> {'branches', 'nodes', 'free_ends', 'junctions' (nodes that are no free end and have branches),
+    'cycles', 'total_length_mm', 'mean_branch_length_mm' (0.0 without a branch), 'removed_branches', 'branch_table': one dict
+    per branch {'label', 'voxels', 'length_mm', 'chord_mm', 'tortuosity', 'kind', 'nodes': (a, b), 'attach_index': (lo, hi)},
+    'node_table': one dict per node {'label', 'voxels', 'end_voxels', 'junction_voxels', 'branches', 'free_end',
+    'centroid_mm': (z, y, x)}}.  Lengths are in mm under the slice depths; the thinning itself is in voxel steps.  curve=True
+    with connectivity=6 is a ValueError, before the first launch.  voxel_data: the bool (nz, ny, nx) array the other
+    calculations take; anything else is a TypeError."""
+    if not _on_device(voxel_data):
+        raise TypeError("skeleton_branch_report needs a bool (nz, ny, nx) array")
+    connectivity = pipeline._check_connectivity(connectivity)
+    if curve and connectivity == 6:
+        raise ValueError("curve=True needs connectivity=26: the curve skeleton is not defined under 6")
+    prune_mm = float(prune_mm)
+    if not prune_mm >= 0.0:
+        raise ValueError("prune_mm must be non-negative")
+    prune_rounds = pipeline._check_rounds(prune_rounds)
+    nz = np.asarray(voxel_data).shape[0]
+    pipeline.branch_steps(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x)            # the argument checks
+    vol = to_device_volume(voxel_data)
+    skel, _ = pipeline._skeleton(vol, bool(curve), connectivity, None)
+    removed = 0
+    if prune_mm > 0.0:
+        pruned = pipeline.prune_skeleton(skel, prune_mm, slice_depths, mm_per_pixel_y, mm_per_pixel_x, prune_rounds)
+        skel, removed = pruned.volume, pruned.removed_branches
+    t = pipeline.skeleton_branches(skel, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    b, n = t.branches, t.nodes
+    total = 0.0
+    for v in b.length_mm:                                               # in ascending label
+        total += float(v)
+    branch_table = [{'label': int(b.label[i]), 'voxels': int(b.voxels[i]), 'length_mm': float(b.length_mm[i]),
+                     'chord_mm': float(b.chord_mm[i]), 'tortuosity': float(b.tortuosity[i]), 'kind': int(b.kind[i]),
+                     'nodes': tuple(int(v) for v in b.nodes[i]), 'attach_index': tuple(int(v) for v in b.attach_index[i])}
+                    for i in range(len(b))]
+    node_table = [{'label': int(n.label[i]), 'voxels': int(n.voxels[i]), 'end_voxels': int(n.end_voxels[i]),
+                   'junction_voxels': int(n.junction_voxels[i]), 'branches': int(n.branches[i]), 'free_end': bool(n.free_end[i]),
+                   'centroid_mm': tuple(float(v) for v in n.centroid_mm[i])} for i in range(len(n))]
+    return {'branches': len(b), 'nodes': len(n), 'free_ends': int(n.free_end.sum()),
+            'junctions': int((~n.free_end & (n.branches > 0)).sum()), 'cycles': int((b.kind == 0).sum()), 'total_length_mm': total,
+            'mean_branch_length_mm': total / len(b) if len(b) else 0.0, 'removed_branches': int(removed),
+            'branch_table': branch_table, 'node_table': node_table}
+
+
 def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=6, min_voxels=0, largest=False,
                          shape=False, topology=False, surface=False, surface_directions=13, porosity=False, thickness=False,
                          thickness_radii_mm=None, geodesic=False, geodesic_sweeps=3, separate_mm=None, separate_h_mm=None,
