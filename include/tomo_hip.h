@@ -671,6 +671,38 @@ int tomo_branch_lookup(const uint64_t *bits, int nz, int ny, int nx, const uint3
 int tomo_branch_clear(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
                       const uint32_t *rank, unsigned long long *tot, const uint8_t *flagged, int64_t n_flagged, const uint64_t *in,
                       uint64_t *out, void *stream);
+/* A value along the components of a labelled volume: smallest, largest, where, and an exact mean (csrc/profile.hip; no
+ * counterpart in the reference; Tb.Th along the skeleton in BoneJ, the throat radius of a pore-network model).  One definition.
+ * values: float32 (nz, ny, nx).  A value is ADMITTED when its bit pattern is below 0x49800000: 0.0 <= v < 2^20, finite, not -0.0;
+ * for those the unsigned order of the bit patterns is the float order.  Per component c + 1 of the run tables, over its voxels:
+ *   lo, hi             the smallest and the largest bit pattern
+ *   lo_first, hi_first the smallest flat index (z * ny + y) * nx + x whose value has the bits lo[c] / hi[c]
+ *   sum                the int64 sum of q(v) = (int64) rint((double)v * 65536.0): fixed point at 2^-16.  The product is exact in
+ *                      float64, rint rounds half to even, integer adds commute -- the same bytes on every run and under every
+ *                      order; 2^27 voxels of the largest admitted value fit.  mean = ((double)sum / 65536.0) / voxels on the host.
+ * The value of an unset voxel is never read.  A set voxel with a value that is not admitted raises bit 3 (8) of tot[2] and takes
+ * no part.  On the run tables of the REGULAR voxels of a skeleton (tomo_branch_split) with the distance map of the object, the
+ * rows are the radii along the branches; the nodes take tomo_cc_value_max / tomo_cc_value_first under their own tables.
+ *   tomo_profile_stats  arguments and guards as tomo_cc_value_max.  lo uint32[cap] (set to all ones here), hi uint32[cap] and sum
+ *                       int64[cap] (zeroed here).  One wave per word, one lane per bit; a word without a set bit leaves before
+ *                       the map is touched.  Per run of a word one wave reduction each for min, max and the sum and at most three
+ *                       atomics from one lane; a minimum or maximum is sent only where it beats what a plain load shows.
+ *   tomo_profile_where  after it, on the same arrays: lo_first, hi_first uint64[cap], set to all ones here; per run at most two
+ *                       64-bit atomicMin, again only below what a plain load shows.
+ *   tomo_profile_rows   out int64[cap_sel][7] row slot[c] = (c + 1, voxels, lo[c], hi[c], sum[c], lo_first[c], hi_first[c]) for
+ *                       the components tomo_cc_select selected; tot[5] > cap_sel: bit 1 of tot[2], nothing is written.
+ * TOMO_E_ARG for a null pointer, a non-positive size, two of the arrays of a call being one, or one of them over the bits or the
+ * map (tomo_profile_rows: over the table); TOMO_E_SIZE from 2^31 words, runs, components or selected components on.  All of it is
+ * decided before any device use.  Integer atomics only, nobody waits on anybody. */
+int tomo_profile_stats(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
+                       const uint32_t *rank, unsigned long long *tot, const float *values, uint32_t *lo, uint32_t *hi, int64_t *sum,
+                       int64_t cap, void *stream);
+int tomo_profile_where(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
+                       const uint32_t *rank, unsigned long long *tot, const float *values, const uint32_t *lo, const uint32_t *hi,
+                       uint64_t *lo_first, uint64_t *hi_first, int64_t cap, void *stream);
+int tomo_profile_rows(const int64_t *table, const uint32_t *lo, const uint32_t *hi, const int64_t *sum, const uint64_t *lo_first,
+                      const uint64_t *hi_first, int64_t cap, unsigned long long *tot, const uint8_t *sel, const uint32_t *slot,
+                      int64_t *out, int64_t cap_sel, void *stream);
 /* The contact table between zones (csrc/contacts.hip; no counterpart in the reference): which zones touch, over how large an
  * interface, how wide the throat between them is and how long the way across.  One definition.
  * zones: int32 (nz, ny, nx), tomo_zone_sweep's map or any map.  A voxel TAKES PART when it is set and its entry is positive.

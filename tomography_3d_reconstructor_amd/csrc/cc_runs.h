@@ -5,8 +5,9 @@
 // voxel's neighbours decide, which component_measures.hip and branches.hip share.
 //
 // tot (device uint64[8]): [0] runs  [1] components  [2] flags (1: 2^31 runs or more, 2: more runs than the caller's buffers
-// hold, 4: a run id outside the tables -- the bits changed between the calls)  [3] label tomo_cc_filter(largest) kept (0: none)
-// [4] counters of the slice histogram  [5] components tomo_cc_select (tomo_cc_zhist_offsets) selected.
+// hold, 4: a run id outside the tables -- the bits changed between the calls, 8: tomo_profile_stats met a value it does not
+// admit)  [3] label tomo_cc_filter(largest) kept (0: none)  [4] counters of the slice histogram  [5] components tomo_cc_select
+// (tomo_cc_zhist_offsets) selected.
 #pragma once
 #include "tomo_common.h"
 
@@ -262,6 +263,35 @@ __device__ static inline bool cc_word_runs_next(CcWordRuns &it)
     it.m &= ~it.mask;
     return true;
 }
+
+// ---------------------------------------------------------------------------------------------- the word pass
+// One wave per 64-bit word of a row, one lane per bit, for what a per-voxel array gives per component (component_measures.hip:
+// the value passes; profile.hip): the array is read in whole rows, the runs that touch the word are walked by all lanes together.
+struct CcWordAt {
+    int64_t row;                                            // z * ny + y
+    int wj, bit;                                            // the word of the row, the lane's bit: x = 64 * wj + bit
+    u64 cur;                                                // the word, tail bits clear
+    CcWordRuns it;                                          // its runs
+};
+
+// -> false: the wave has no word, or a word without a set bit (wave-uniform)
+__device__ static inline bool cc_word_at(const u64 *__restrict__ bits, int64_t nwords, int nx, int wx, const u32 *__restrict__ row_off,
+                                         CcWordAt &a)
+{
+    const int64_t t = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    const int64_t word = t >> 6;                            // the same for the 64 lanes of a wave
+    if (word >= nwords) return false;
+    a.row = word / wx;
+    a.wj = (int)(word - a.row * wx);
+    a.bit = (int)(t & 63);
+    const u64 *r = bits + a.row * wx;
+    a.cur = cc_word(r, nx, wx, a.wj);
+    if (!a.cur) return false;
+    a.it = {a.cur, cc_before(r, nx, wx, a.wj, row_off[a.row]), a.wj > 0 && (r[a.wj - 1] >> 63) != 0, 0, 0};
+    return true;
+}
+
+__device__ static inline u64 cc_load64(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // ---------------------------------------------------------------------------------------------- the row pass
 // One thread per row adds up what the row gives per component: neighbouring runs of one component first, flushed to the

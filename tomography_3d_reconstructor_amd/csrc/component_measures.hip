@@ -1184,34 +1184,9 @@ TOMO_API int tomo_cc_surface(const int64_t *table, int64_t cap, unsigned long lo
 // inscribed sphere), and the voxels per slice and thickness level.  Distance and local thickness are local to a component --
 // the nearest site of a voxel of A is never a voxel of another component, and a ball that fits lies in the component of its
 // centre -- so ONE transform of the whole volume serves every component, and what is left is a reduction over the run tables.
-// The WORD PASS: one wave per 64-bit word of a row, one lane per bit (edt_at_least_kernel's shape), so that the per-voxel array
-// is read in whole 256- or 512-byte rows.  The runs that touch the word are walked by all lanes together (CcWordRuns: the word,
-// hence every run and its component, is wave-uniform); a lane takes part under the run's mask.
-struct CcWordAt {
-    int64_t row;                                            // z * ny + y
-    int wj, bit;                                            // the word of the row, the lane's bit: x = 64 * wj + bit
-    u64 cur;                                                // the word, tail bits clear
-    CcWordRuns it;                                          // its runs
-};
-
-// -> false: the wave has no word, or a word without a set bit (wave-uniform)
-__device__ static inline bool cc_word_at(const u64 *__restrict__ bits, int64_t nwords, int nx, int wx, const u32 *__restrict__ row_off,
-                                         CcWordAt &a)
-{
-    const int64_t t = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
-    const int64_t word = t >> 6;                            // the same for the 64 lanes of a wave
-    if (word >= nwords) return false;
-    a.row = word / wx;
-    a.wj = (int)(word - a.row * wx);
-    a.bit = (int)(t & 63);
-    const u64 *r = bits + a.row * wx;
-    a.cur = cc_word(r, nx, wx, a.wj);
-    if (!a.cur) return false;
-    a.it = {a.cur, cc_before(r, nx, wx, a.wj, row_off[a.row]), a.wj > 0 && (r[a.wj - 1] >> 63) != 0, 0, 0};
-    return true;
-}
-
-__device__ static inline u64 cc_load64(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// The WORD PASS (cc_runs.h): one wave per 64-bit word of a row, one lane per bit (edt_at_least_kernel's shape), so that the
+// per-voxel array is read in whole 256- or 512-byte rows.  The runs that touch the word are walked by all lanes together
+// (CcWordRuns: the word, hence every run and its component, is wave-uniform); a lane takes part under the run's mask.
 
 // the float32 bits of the value of a SET voxel: the distance map itself, or (float)sqrt(d2) -- what EDT_TAIL_FLOAT stores
 __device__ static inline u32 cc_value_bits(const float *__restrict__ dist, const double *__restrict__ d2, int64_t at)

@@ -30,7 +30,7 @@ COUNTERS = dict.fromkeys(("na_hint_hit", "na_hint_miss", "mc3_hint_hit", "mc3_hi
                           "separate_components", "zone_contacts", "contact_launches", "recon_calls", "recon_sweeps",
                           "thin_calls", "thin_iterations", "thin_passes", "thin_nodes", "component_skeleton",
                           "skeleton_branches", "branch_split", "skeleton_branches_hist", "branch_attach", "branch_lookup", "branch_clear",
-                          "prune_rounds"), 0)
+                          "prune_rounds", "components_profile", "branch_profile", "prune_relative"), 0)
 NA_HINTS = os.environ.get("TOMO_NA_HINTS", "1") not in ("", "0")   # marching_cubes: launch ahead of the first count download
 _NA_HINT = {}
 LIST_LIMIT = 2 ** 31        # active-voxel list entries / vertices / triangles one pass can index (int32 offsets in mc.hip, mesh.hip);
@@ -254,6 +254,10 @@ MOMENT_COLUMNS = 22          # float64 per row of tomo_cc_moments: W, centre (3)
 TOPOLOGY_COLUMNS = 3         # euler, cavities, handles (tomo_cc_cavities)
 SURFACE_COUNTERS = 11        # uint64 per component and slice: x, y, xy, then z, xz, yz, xyz upwards and downwards (tomo_cc_surface_hist)
 SURFACE_CLASSES = 7          # direction classes: x, y, xy, z, xz, yz, xyz
+PROFILE_COLUMNS = 7          # label, voxels, min bits, max bits, sum_q, min index, max index (tomo_profile_rows)
+PROFILE_ADMITTED = 0x49800000    # float32 bit patterns below it are admitted by tomo_profile_stats: 0.0 <= v < 2^20
+PROFILE_F_VALUE = 8          # bit of the flag word: tomo_profile_stats met a set voxel whose value is not admitted
+_PROFILE_VALUE_ERROR = "values: a set voxel holds an entry outside 0.0 <= v < 2^20 (NaN, negative, -0.0 or infinite)"
 
 
 def _check_connectivity(connectivity) -> int:
@@ -525,6 +529,65 @@ class ComponentRuns:
         _lib.check(_lib.lib().tomo_cc_topology_rows(_p(picked.table), _p(topo), topo.shape[0], _p(self.tot), _p(picked.sel), _p(picked.slot),
                                                     _p(rows), picked.m, _stream()), "tomo_cc_topology_rows")
         return _component_topology_from(*self._download_checked(_TOPOLOGY.name, rows))
+
+    def value_max(self, values: torch.Tensor, min_voxels=0) -> np.ndarray:
+        """The largest entry of a float32 map per component of at least min_voxels voxels and the first voxel that attains it ->
+        host int64 (m, 4): label, voxels, the float32 bit pattern, the flat index: the value passes of thickness() on a map of
+        the caller's (thickness() keeps its own lines: its transform sits between the selection and the passes).  The entries
+        are value_profile's: one that is not admitted on a set voxel is a ValueError."""
+        values = _profile_values(self.vol, values)
+        picked = self.select(min_voxels)
+        if picked is None:
+            return np.zeros((0, 4), dtype=np.int64)
+        L, dev, st = _lib.lib(), self.vol.device, _stream()
+        n = picked.table.shape[0]
+        best = torch.empty(n, dtype=torch.int32, device=dev)
+        first = torch.empty(n, dtype=torch.int64, device=dev)
+        rows = torch.empty((picked.m, 4), dtype=torch.int64, device=dev)
+        head = (_p(self.bits), *self.vol.shape, *self._tables(), _p(self.tot), _p(values.contiguous()), None)
+        COUNTERS["components_value"] += 1
+        _lib.check(L.tomo_cc_value_max(*head, _p(best), n, st), "tomo_cc_value_max")
+        _lib.check(L.tomo_cc_value_first(*head, _p(best), _p(first), n, st), "tomo_cc_value_first")
+        _lib.check(L.tomo_cc_value_rows(_p(picked.table), _p(best), _p(first), n, _p(self.tot), _p(picked.sel), _p(picked.slot),
+                                        _p(rows), picked.m, st), "tomo_cc_value_rows")
+        (rows,) = self._download_checked("value_max", rows)
+        if (rows[:, 2] >= PROFILE_ADMITTED).any():          # every pattern that is not admitted lies above the admitted ones
+            raise ValueError(_PROFILE_VALUE_ERROR)
+        return rows
+
+    def value_profile(self, values: torch.Tensor, min_voxels=0) -> np.ndarray:
+        """What a float32 map of the volume's shape gives per component of at least min_voxels voxels, in ascending label -> host
+        int64 (m, 7): label, voxels, the float32 bit patterns of the smallest and the largest entry, sum_q, and the lowest flat
+        index (z * ny + y) * nx + x that attains the smallest and the largest (include/tomo_hip.h, tomo_profile_*; _profile_rows_from
+        turns the rows into floats).  sum_q is the int64 sum of rint(float64(v) * 65536): the same bytes on every run.  Entries
+        of unset voxels are never read; a set voxel with an entry outside 0.0 <= v < 2^20 (NaN, negative, -0.0, infinite) is a
+        ValueError.  Rows are under the object's ONE selection, so they line up with every other measurement of the same rule."""
+        values = _profile_values(self.vol, values)
+        picked = self.select(min_voxels)
+        if picked is None:
+            return np.zeros((0, PROFILE_COLUMNS), dtype=np.int64)
+        L, dev, st = _lib.lib(), self.vol.device, _stream()
+        n = picked.table.shape[0]
+        values = values.contiguous()
+        lo, hi = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+        total = torch.empty(n, dtype=torch.int64, device=dev)
+        lo_first, hi_first = torch.empty(n, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.int64, device=dev)
+        rows = torch.empty((picked.m, PROFILE_COLUMNS), dtype=torch.int64, device=dev)
+        head = (_p(self.bits), *self.vol.shape, *self._tables(), _p(self.tot), _p(values))
+        COUNTERS["components_profile"] += 1
+        _lib.check(L.tomo_profile_stats(*head, _p(lo), _p(hi), _p(total), n, st), "tomo_profile_stats")
+        _lib.check(L.tomo_profile_where(*head, _p(lo), _p(hi), _p(lo_first), _p(hi_first), n, st), "tomo_profile_where")
+        _lib.check(L.tomo_profile_rows(_p(picked.table), _p(lo), _p(hi), _p(total), _p(lo_first), _p(hi_first), n, _p(self.tot),
+                                       _p(picked.sel), _p(picked.slot), _p(rows), picked.m, st), "tomo_profile_rows")
+        host, flags = rows.cpu().numpy(), int(self.tot[2:3].cpu().numpy()[0])
+        if flags & PROFILE_F_VALUE:                         # the one flag that speaks of the caller's map, not of the tables
+            self.tot[2:3].bitwise_and_(~PROFILE_F_VALUE)    # the object stays usable
+            flags &= ~PROFILE_F_VALUE
+            if not flags:
+                raise ValueError(_PROFILE_VALUE_ERROR)
+        if flags:
+            raise _lib.TomoError("value_profile: the tables do not fit the volume (flags %d)" % flags)
+        return host
 
     def thickness(self, slice_depths, mm_y, mm_x, radii_mm=None, min_voxels=0, largest=False, *, max_voxels=None,
                   enclosed=False) -> "ComponentThickness":
@@ -2922,29 +2985,18 @@ def _check_rounds(rounds):
     return int(rounds)
 
 
-def prune_skeleton(skel: BitVolume, min_length_mm, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, rounds=1) -> PrunedSkeleton:
-    """Remove the short terminal branches of a skeleton -> PrunedSkeleton with a NEW volume; the input is left untouched.  One
-    round removes every branch of kind 2 of skeleton_branches -- exactly one of its nodes is a free end -- with length_mm <
-    min_length_mm, together with the free-end voxel it hangs from; the node at its other end stays.  A pendant path is a chain
-    of simple-point deletions, so components, cavities and handles are the input's.  rounds=None repeats the round on the
-    table of the pruned volume until one removes nothing (a round only merges branches into longer ones, so this ends;
-    PRUNE_ROUND_LIMIT guards the loop).  Plain fibres (kind 1) and cycles are never touched.  On the device a round is
-    skeleton_branches and two tomo_branch_clear: the tables of the regular voxels with the flags of the branches, then the
-    tables of the node voxels with the flags of their free ends.  Arguments are checked before the first launch."""
-    args = _branch_args(skel, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
-    min_length_mm = float(min_length_mm)
-    if math.isnan(min_length_mm):
-        raise ValueError("min_length_mm must be a number")
-    rounds = _check_rounds(rounds)
+def _prune(skel: BitVolume, args, slice_depths, rounds, rule, what) -> PrunedSkeleton:
+    """The rounds of pruning.  rule(t) -> bool (m,) over the rows of t.branches, the table of the volume as it stands: the
+    branches that go (only kind 2 may be named); each goes with the free-end voxel it hangs from."""
     dev = skel.device
     vol = BitVolume(skel.bits.contiguous().clone(), skel.shape)
     removed_branches = removed_voxels = done = 0
     while rounds is None or done < rounds:
         if done >= int(PRUNE_ROUND_LIMIT):
-            raise _lib.TomoError("prune_skeleton: no fixed point after %d rounds (PRUNE_ROUND_LIMIT)" % done)
+            raise _lib.TomoError("%s: no fixed point after %d rounds (PRUNE_ROUND_LIMIT)" % (what, done))
         t, runs_r, runs_n = _skeleton_branches(vol, args, slice_depths)
         b = t.branches
-        gone = (b.kind == 2) & (b.length_mm < min_length_mm)
+        gone = rule(t)
         if not gone.any():
             break
         COUNTERS["prune_rounds"] += 1
@@ -2959,6 +3011,169 @@ def prune_skeleton(skel: BitVolume, min_length_mm, slice_depths=None, mm_per_pix
         removed_voxels += int(b.voxels[gone].sum()) + len(ends)
         done += 1
     return PrunedSkeleton(vol, removed_branches, removed_voxels, done)
+
+
+def prune_skeleton(skel: BitVolume, min_length_mm, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, rounds=1) -> PrunedSkeleton:
+    """Remove the short terminal branches of a skeleton -> PrunedSkeleton with a NEW volume; the input is left untouched.  One
+    round removes every branch of kind 2 of skeleton_branches -- exactly one of its nodes is a free end -- with length_mm <
+    min_length_mm, together with the free-end voxel it hangs from; the node at its other end stays.  A pendant path is a chain
+    of simple-point deletions, so components, cavities and handles are the input's.  rounds=None repeats the round on the
+    table of the pruned volume until one removes nothing (a round only merges branches into longer ones, so this ends;
+    PRUNE_ROUND_LIMIT guards the loop with a TomoError).  Plain fibres (kind 1) and cycles are never touched.  On the device a round is
+    skeleton_branches and two tomo_branch_clear: the tables of the regular voxels with the flags of the branches, then the
+    tables of the node voxels with the flags of their free ends.  Arguments are checked before the first launch."""
+    args = _branch_args(skel, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    min_length_mm = float(min_length_mm)
+    if math.isnan(min_length_mm):
+        raise ValueError("min_length_mm must be a number")
+    rounds = _check_rounds(rounds)
+    return _prune(skel, args, slice_depths, rounds, lambda t: (t.branches.kind == 2) & (t.branches.length_mm < min_length_mm),
+                  "prune_skeleton")
+
+
+# ----------------------------------------------------------------------------- a value along the branches: radii, throats
+def _profile_values(vol: BitVolume, values) -> torch.Tensor:
+    """The checks of a value map, all on the host: a float32 tensor of the volume's shape on its device."""
+    if values is None:
+        raise TypeError("values must be a float32 tensor (nz, ny, nx)")
+    return _contact_values(vol, values, "values")
+
+
+def _bits_as_float32(column) -> np.ndarray:
+    return np.ascontiguousarray(column, dtype=np.int64).astype(np.uint32).view(np.float32)
+
+
+@dataclass
+class BranchValueRows:
+    """The branches of skeleton_branch_profile: host arrays, row for row those of SkeletonBranchRows."""
+    label: np.ndarray            # int64 (m,)
+    voxels: np.ndarray           # int64 (m,)
+    min: np.ndarray              # float32 (m,): the smallest value over the regular voxels of the branch -- its throat
+    min_index: np.ndarray        # int64 (m,): the lowest flat index that attains it
+    max: np.ndarray              # float32 (m,)
+    max_index: np.ndarray        # int64 (m,)
+    sum_q: np.ndarray            # int64 (m,): the sum of rint(float64(v) * 65536)
+    mean: np.ndarray             # float64 (m,): (sum_q / 65536) / voxels
+    attach_value: np.ndarray     # float32 (m, 2): the values at attach_index; nan for a cycle
+
+    def __len__(self):
+        return len(self.label)
+
+
+@dataclass
+class NodeValueRows:
+    """The nodes of skeleton_branch_profile: host arrays, row for row those of SkeletonNodeRows."""
+    label: np.ndarray            # int64 (n,)
+    max: np.ndarray              # float32 (n,): the largest value over the voxels of the node
+    max_index: np.ndarray        # int64 (n,): the lowest flat index that attains it
+
+    def __len__(self):
+        return len(self.label)
+
+
+@dataclass
+class SkeletonProfile:
+    """skeleton_branch_profile's answer."""
+    table: SkeletonBranches      # what skeleton_branches returns for the same arguments, from the same call
+    branches: BranchValueRows
+    nodes: NodeValueRows
+
+
+def _profile_rows_from(rows, attach_value=None) -> BranchValueRows:
+    """Host arithmetic on the rows of ComponentRuns.value_profile.  mean = (float64(sum_q) / 65536.0) / voxels."""
+    rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1, PROFILE_COLUMNS)
+    m = len(rows)
+    if attach_value is None:
+        attach_value = np.full((m, 2), np.nan, dtype=np.float32)
+    mean = (rows[:, 4].astype(np.float64) / 65536.0) / rows[:, 1].astype(np.float64)
+    return BranchValueRows(rows[:, 0].copy(), rows[:, 1].copy(), _bits_as_float32(rows[:, 2]), rows[:, 5].copy(),
+                           _bits_as_float32(rows[:, 3]), rows[:, 6].copy(), rows[:, 4].copy(), mean,
+                           np.ascontiguousarray(attach_value, dtype=np.float32).reshape(m, 2))
+
+
+def _node_value_rows_from(rows) -> NodeValueRows:
+    rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1, 4)
+    return NodeValueRows(rows[:, 0].copy(), _bits_as_float32(rows[:, 2]), rows[:, 3].copy())
+
+
+def _values_at(values: torch.Tensor, index: np.ndarray) -> np.ndarray:
+    """The entries of the map at host flat indices -> float32 host array of their shape, nan where the index is negative."""
+    index = np.ascontiguousarray(index, dtype=np.int64)
+    out = np.full(index.shape, np.nan, dtype=np.float32)
+    there = index >= 0
+    if there.any():
+        at = torch.from_numpy(index[there]).to(values.device)
+        out[there] = values.contiguous().reshape(-1).index_select(0, at).cpu().numpy()
+    return out
+
+
+def skeleton_branch_profile(skel: BitVolume, values: torch.Tensor, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0,
+                            min_voxels=0) -> SkeletonProfile:
+    """A per-voxel value along the branches of a skeleton -> SkeletonProfile: with values = distance_transform of the OBJECT, the
+    radius of the object along its centre-line -- how wide each channel is and where it is narrowest (Tb.Th along the skeleton
+    in BoneJ, the throat radius of a pore-network model).  values: a float32 device tensor of the volume's shape.  One
+    definition (include/tomo_hip.h): per branch of skeleton_branches, over its REGULAR voxels only, min and max compare the
+    float32 bit patterns, min_index / max_index are the lowest flat index (z * ny + y) * nx + x that attains each, sum_q is the
+    int64 sum of rint(float64(v) * 65536) -- fixed point at 2^-16, the same bytes on every run and under every order -- and
+    mean = (sum_q / 65536) / voxels.  attach_value holds the values at attach_index (nan for a cycle).  Per node: the largest
+    value over its voxels and the lowest index that attains it.  An entry on a set voxel must be admitted: 0.0 <= v < 2^20,
+    not -0.0 (ValueError otherwise); the entries of unset voxels are never read and may be anything.
+    table is skeleton_branches' answer from the same call, and the rows line up with table.branches / table.nodes by
+    construction: the value passes run under the run tables and the one selection of that call, there is no second labelling.
+    On the device: tomo_profile_stats, tomo_profile_where, tomo_profile_rows under the tables of the regular voxels,
+    tomo_cc_value_max / _first / _rows under those of the node voxels, one gather of 2 m entries.  Memory: 28 bytes per branch,
+    12 per node, nothing per voxel.  An empty skeleton launches nothing past the split; one without regular voxels gives zero
+    branch rows.  Arguments are checked before the first launch."""
+    args = _branch_args(skel, slice_depths, mm_per_pixel_y, mm_per_pixel_x, min_voxels)
+    values = _profile_values(skel, values)
+    COUNTERS["branch_profile"] += 1
+    t, runs_r, runs_n = _skeleton_branches(skel, args, slice_depths)
+    branches, nodes = _profile_rows_from(np.zeros((0, PROFILE_COLUMNS))), _node_value_rows_from(np.zeros((0, 4)))
+    if runs_n is not None:
+        nodes = _node_value_rows_from(runs_n.value_max(values))
+    if runs_r is not None:
+        rows = runs_r.value_profile(values, args[4])
+        branches = _profile_rows_from(rows, _values_at(values, t.branches.attach_index))
+    return SkeletonProfile(t, branches, nodes)
+
+
+def _check_factor(factor) -> float:
+    if isinstance(factor, (bool, np.bool_)) or not isinstance(factor, (int, float, np.integer, np.floating)) or not factor >= 0:
+        raise ValueError("factor must be a non-negative number")
+    return float(factor)
+
+
+def prune_skeleton_relative(skel: BitVolume, values: torch.Tensor, factor=1.0, min_length_mm=0.0, slice_depths=None, mm_per_pixel_y=1.0,
+                            mm_per_pixel_x=1.0, rounds=None) -> PrunedSkeleton:
+    """prune_skeleton with a threshold that follows the object: one round removes every branch of kind 2 with
+    length_mm < max(min_length_mm, factor * r), r = the float64 of the entry of `values` at the attached voxel of the node that
+    is NOT the free end -- with values = distance_transform of the object, the radius of the object where the spur leaves it.
+    Curve thinning makes a thick part sprout spurs about as long as the part is thick, so one absolute length is wrong for any
+    object with two scales; factor 1.0 removes a spur that does not reach out of the ball it hangs from.  The clears, the
+    free-end voxel that goes along, the topology and the meaning of rounds (default: to the fixed point) are prune_skeleton's;
+    factor=0 IS prune_skeleton(min_length_mm).  An r that is nan compares false: the branch stays.  factor negative or nan:
+    ValueError; values: a float32 device tensor of the volume's shape (TypeError / ValueError).  Per round one gather of the
+    spurs' entries on top of prune_skeleton's work.  Arguments are checked before the first launch."""
+    args = _branch_args(skel, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    values = _profile_values(skel, values)
+    factor = _check_factor(factor)
+    min_length_mm = float(min_length_mm)
+    if math.isnan(min_length_mm):
+        raise ValueError("min_length_mm must be a number")
+    rounds = _check_rounds(rounds)
+    COUNTERS["prune_relative"] += 1
+
+    def rule(t):
+        b = t.branches
+        spur = b.kind == 2
+        stays = np.concatenate([[False], t.nodes.free_end])[b.nodes[spur]]            # (k, 2): exactly one True a row
+        held = np.where(stays[:, 0], b.attach_index[spur, 1], b.attach_index[spur, 0])
+        gone = np.zeros(len(b), dtype=bool)
+        with np.errstate(invalid="ignore"):
+            gone[spur] = b.length_mm[spur] < np.maximum(min_length_mm, factor * _values_at(values, held).astype(np.float64))
+        return gone
+
+    return _prune(skel, args, slice_depths, rounds, rule, "prune_skeleton_relative")
 
 
 def local_thickness(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, radii_mm=None,

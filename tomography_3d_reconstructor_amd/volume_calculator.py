@@ -330,20 +330,10 @@ def skeleton_report(voxel_data, connectivity=26, curve=True):
             'junction_voxels': int(nodes.junction_voxels), 'isolated': int(nodes.isolated), 'iterations': int(iterations)}
 
 
-def skeleton_branch_report(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=26, curve=True, prune_mm=0.0,
-                           prune_rounds=1):
-    """The branch table of the skeleton of a volume (no counterpart in the reference; AnalyzeSkeleton of BoneJ answers the same
-    question): the volume is thinned as skeleton_report thins it, short spurs are pruned when prune_mm > 0
-    (pipeline.prune_skeleton: terminal branches shorter than prune_mm, prune_rounds rounds, None = until nothing goes), then
-    pipeline.skeleton_branches -> {'branches', 'nodes', 'free_ends', 'junctions' (nodes that are no free end and have branches),
-    'cycles', 'total_length_mm', 'mean_branch_length_mm' (0.0 without a branch), 'removed_branches', 'branch_table': one dict
-    per branch {'label', 'voxels', 'length_mm', 'chord_mm', 'tortuosity', 'kind', 'nodes': (a, b), 'attach_index': (lo, hi)},
-    'node_table': one dict per node {'label', 'voxels', 'end_voxels', 'junction_voxels', 'branches', 'free_end',
-    'centroid_mm': (z, y, x)}}.  Lengths are in mm under the slice depths; the thinning itself is in voxel steps.  curve=True
-    with connectivity=6 is a ValueError, before the first launch.  voxel_data: the bool (nz, ny, nx) array the other
-    calculations take; anything else is a TypeError."""
+def _branch_report_args(what, voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity, curve, prune_mm, prune_rounds):
+    """The argument checks the branch reports share, all on the host -> (connectivity, prune_mm, prune_rounds)."""
     if not _on_device(voxel_data):
-        raise TypeError("skeleton_branch_report needs a bool (nz, ny, nx) array")
+        raise TypeError("%s needs a bool (nz, ny, nx) array" % what)
     connectivity = pipeline._check_connectivity(connectivity)
     if curve and connectivity == 6:
         raise ValueError("curve=True needs connectivity=26: the curve skeleton is not defined under 6")
@@ -353,13 +343,11 @@ def skeleton_branch_report(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_dep
     prune_rounds = pipeline._check_rounds(prune_rounds)
     nz = np.asarray(voxel_data).shape[0]
     pipeline.branch_steps(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x)            # the argument checks
-    vol = to_device_volume(voxel_data)
-    skel, _ = pipeline._skeleton(vol, bool(curve), connectivity, None)
-    removed = 0
-    if prune_mm > 0.0:
-        pruned = pipeline.prune_skeleton(skel, prune_mm, slice_depths, mm_per_pixel_y, mm_per_pixel_x, prune_rounds)
-        skel, removed = pruned.volume, pruned.removed_branches
-    t = pipeline.skeleton_branches(skel, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    return connectivity, prune_mm, prune_rounds
+
+
+def _branch_report(t, removed):
+    """skeleton_branch_report's dict from a SkeletonBranches and the number of pruned branches."""
     b, n = t.branches, t.nodes
     total = 0.0
     for v in b.length_mm:                                               # in ascending label
@@ -375,6 +363,75 @@ def skeleton_branch_report(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_dep
             'junctions': int((~n.free_end & (n.branches > 0)).sum()), 'cycles': int((b.kind == 0).sum()), 'total_length_mm': total,
             'mean_branch_length_mm': total / len(b) if len(b) else 0.0, 'removed_branches': int(removed),
             'branch_table': branch_table, 'node_table': node_table}
+
+
+def skeleton_branch_report(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=26, curve=True, prune_mm=0.0,
+                           prune_rounds=1):
+    """The branch table of the skeleton of a volume (no counterpart in the reference; AnalyzeSkeleton of BoneJ answers the same
+    question): the volume is thinned as skeleton_report thins it, short spurs are pruned when prune_mm > 0
+    (pipeline.prune_skeleton: terminal branches shorter than prune_mm, prune_rounds rounds, None = until nothing goes), then
+    pipeline.skeleton_branches -> {'branches', 'nodes', 'free_ends', 'junctions' (nodes that are no free end and have branches),
+    'cycles', 'total_length_mm', 'mean_branch_length_mm' (0.0 without a branch), 'removed_branches', 'branch_table': one dict
+    per branch {'label', 'voxels', 'length_mm', 'chord_mm', 'tortuosity', 'kind', 'nodes': (a, b), 'attach_index': (lo, hi)},
+    'node_table': one dict per node {'label', 'voxels', 'end_voxels', 'junction_voxels', 'branches', 'free_end',
+    'centroid_mm': (z, y, x)}}.  Lengths are in mm under the slice depths; the thinning itself is in voxel steps.  curve=True
+    with connectivity=6 is a ValueError, before the first launch.  voxel_data: the bool (nz, ny, nx) array the other
+    calculations take; anything else is a TypeError."""
+    connectivity, prune_mm, prune_rounds = _branch_report_args("skeleton_branch_report", voxel_data, mm_per_pixel_x, mm_per_pixel_y,
+                                                               slice_depths, connectivity, curve, prune_mm, prune_rounds)
+    vol = to_device_volume(voxel_data)
+    skel, _ = pipeline._skeleton(vol, bool(curve), connectivity, None)
+    removed = 0
+    if prune_mm > 0.0:
+        pruned = pipeline.prune_skeleton(skel, prune_mm, slice_depths, mm_per_pixel_y, mm_per_pixel_x, prune_rounds)
+        skel, removed = pruned.volume, pruned.removed_branches
+    return _branch_report(pipeline.skeleton_branches(skel, slice_depths, mm_per_pixel_y, mm_per_pixel_x), removed)
+
+
+def skeleton_thickness_report(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=26, curve=True, prune_factor=1.0,
+                              prune_mm=0.0, prune_rounds=None):
+    """How wide the object is along its skeleton (no counterpart in the reference; Tb.Th along the skeleton in BoneJ, channel and
+    throat radii of a pore-network model): the volume is thinned as skeleton_report thins it, pipeline.distance_transform of the
+    OBJECT gives the radius at every voxel, spurs are pruned relative to it when prune_factor > 0 or prune_mm > 0
+    (pipeline.prune_skeleton_relative: a terminal branch goes when it is shorter than max(prune_mm, prune_factor * the radius
+    where it leaves its junction); prune_rounds rounds, None = until nothing goes), then pipeline.skeleton_branch_profile ->
+    skeleton_branch_report's dict with, per branch, 'min_radius_mm', 'throat_index' (the flat index of the first voxel that
+    attains it), 'max_radius_mm', 'mean_radius_mm' and 'component' -- the label under label_components(connectivity) of the
+    object's component that holds the throat voxel --, per node 'radius_mm' (the largest over its voxels) and 'component', and
+    overall 'mean_thickness_mm' = 2 (sum of sum_q / 65536) / (sum of voxels) over all branches (0.0 without one) and 'narrowest':
+    {'label', 'radius_mm', 'index'} of the branch with the smallest throat, the lowest label among equals (None without a
+    branch).  Argument errors are skeleton_branch_report's, and prune_factor negative or nan is a ValueError; all of them come
+    before the first launch."""
+    connectivity, prune_mm, prune_rounds = _branch_report_args("skeleton_thickness_report", voxel_data, mm_per_pixel_x, mm_per_pixel_y,
+                                                               slice_depths, connectivity, curve, prune_mm, prune_rounds)
+    prune_factor = pipeline._check_factor(prune_factor)
+    vol = to_device_volume(voxel_data)
+    skel, _ = pipeline._skeleton(vol, bool(curve), connectivity, None)
+    radius = pipeline.distance_transform(vol, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    removed = 0
+    if prune_factor > 0.0 or prune_mm > 0.0:
+        pruned = pipeline.prune_skeleton_relative(skel, radius, prune_factor, prune_mm, slice_depths, mm_per_pixel_y, mm_per_pixel_x,
+                                                  prune_rounds)
+        skel, removed = pruned.volume, pruned.removed_branches
+    profile = pipeline.skeleton_branch_profile(skel, radius, slice_depths, mm_per_pixel_y, mm_per_pixel_x)
+    b, n = profile.branches, profile.nodes
+    report = _branch_report(profile.table, removed)
+    runs = pipeline.ComponentRuns(vol, connectivity)
+    owner = runs.label_at(np.concatenate([b.min_index, n.max_index])).cpu().numpy()
+    if runs.runs:
+        runs._checked()                                                 # the guards of the lookup
+    for i, row in enumerate(report['branch_table']):
+        row.update({'min_radius_mm': float(b.min[i]), 'throat_index': int(b.min_index[i]), 'max_radius_mm': float(b.max[i]),
+                    'mean_radius_mm': float(b.mean[i]), 'component': int(owner[i])})
+    for i, row in enumerate(report['node_table']):
+        row.update({'radius_mm': float(n.max[i]), 'component': int(owner[len(b) + i])})
+    voxels = int(b.voxels.sum())
+    report['mean_thickness_mm'] = 2.0 * (float(int(b.sum_q.sum())) / 65536.0) / voxels if voxels else 0.0
+    report['narrowest'] = None
+    if len(b):
+        i = int(np.argmin(b.min))                                       # the first of equals: the lowest label
+        report['narrowest'] = {'label': int(b.label[i]), 'radius_mm': float(b.min[i]), 'index': int(b.min_index[i])}
+    return report
 
 
 def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=6, min_voxels=0, largest=False,
