@@ -340,6 +340,55 @@ int tomo_cc_surface_hist(const uint64_t *bits, int nz, int ny, int nx, const uin
 int tomo_cc_surface(const int64_t *table, int64_t cap, unsigned long long *tot, const uint8_t *sel, const uint64_t *off,
                     const uint32_t *slot, const uint64_t *surf, int64_t hist_cap, const double *F, int nz, int directions,
                     double *out, int64_t *counts, int64_t *labels, int64_t cap_sel, void *stream);
+/* Mean breadth per component by the discretised Crofton formula (Ohser & Muecklich; no counterpart in the reference): the
+ * fourth Minkowski functional, M = 2 pi * mean breadth being the integral of mean curvature.  Lattice and background are the
+ * distance transform's: voxel (k, j, i) sits at (zc[k], j mm_y, i mm_x), everything outside the stack is clear.
+ *     b = sum over m of c_m * delta_m * chi_m
+ * over the 13 families of lattice planes with Miller index m = (a_z, a_y, a_x) in {-1, 0, 1}^3, first non-zero entry positive,
+ * in ascending tuple order:
+ *     (0,0,1) (0,1,-1) (0,1,0) (0,1,1) (1,-1,-1) (1,-1,0) (1,-1,1) (1,0,-1) (1,0,0) (1,0,1) (1,1,-1) (1,1,0) (1,1,1)
+ * For a lattice of height h the normal is n = (a_z / h, a_y / mm_y, a_x / mm_x) (the reciprocal-lattice vector, not the lattice
+ * diagonal), the plane spacing delta_m = 1 / |n|, and c_m twice the share of the unit sphere in the Voronoi cell of +-n / |n|
+ * among the 26 such normals (the weights of tomo_cc_surface on the reciprocal box (1 / h, 1 / mm_y, 1 / mm_x); over the 13
+ * families they sum to 1).  directions = 3: the three axis normals with c = 1 / 3 each.
+ * chi_m is the sum over all planes a . p = const of the 2-D Euler number V - E + F of the section, on the lattice of the plane:
+ *   one non-zero entry (3 families)    edges: the two other axis steps; faces: the unit squares they span
+ *   two (6 families)                   edges: the axis step u of the zero entry and the one face diagonal e perpendicular to m;
+ *                                      faces: the rectangles (p, p + u, p + e, p + u + e)
+ *   three (4 families)                 edges: the three face diagonals perpendicular to m (a triangular lattice, e2 = e1 + e3);
+ *                                      faces: the triangles (p, p + e1, p + e2) and (p, p + e3, p + e2)
+ * An edge counts when both its ends are set, a face when all its corners are.  Every step is a 26-neighbour offset.
+ * Every cell is anchored at its raster-first corner p: filed in the slice of p and credited to the component of p.  Under
+ * connectivity 26 all corners of a cell lie in one component and a row is exactly the value of the mask `labels == c`; a cell
+ * across a diagonal contact under connectivity 6 goes to the component of its first corner: under both connectivities the
+ * counts of all components add up exactly to the counts of the unlabelled volume.  All cells of p lie in its forward
+ * neighbourhood: its own row at x + 1, row (z, y + 1) at x - 1 .. x + 1, rows (z + 1, y - 1 .. y + 1) at x - 1 .. x + 1.
+ * Depths: a cell whose corners all lie in slice k (every vertex is one) is IN the slice and uses h = d[k]; a CROSS cell has
+ * corners in slices k and k + 1 and uses h = (d[k] + d[k + 1]) / 2.  No cell leaves the stack.  B = float64[nz][26]
+ * (pipeline.breadth_factors): columns 0 .. 12 c_m delta_m at d[k], 13 .. 25 at the mean depth; the cross columns are 0.0 in the
+ * last slice, and that of (1, 0, 0), which has no cross cell, everywhere.
+ * Sum: b = sum over k ascending over the slices of the component's box, over the columns 0 .. 25, of
+ * (double)(int64)chi[k][column] * B[k][column], chi^in in the columns 0 .. 12 and chi^cross in 13 .. 25: sequential float64,
+ * never contracted (tomo_cc_zsums' discipline).  directions = 3: only the columns of (0,0,1), (0,1,0) and (1,0,0) enter.
+ *   tomo_cc_breadth_hist  hist uint64[18 * hist_cap], zeroed here; arguments, selection and guard bits are
+ *                         tomo_cc_surface_hist's.  Entry off[c] + z - zmin[c] holds, for the cells anchored in slice z of
+ *                         component c + 1: words 0 .. 5 the raw counts inside the slice -- voxels, edges along x, along y, along
+ *                         (0, 1, 1), along (0, 1, -1), squares x y -- and words 6 .. 17 the signed chi^cross (faces - edges, two's
+ *                         complement) of the families in the order above without (1, 0, 0).  One thread per row slides the row
+ *                         and four forward rows along x; word-wide ANDs, popcounts under the masks of the runs, wrapping integer
+ *                         atomics only: the same bytes on every run.  parent == NULL: the volume is one component, entry z.
+ *   tomo_cc_breadth       one thread per selected component: chi^in = voxels - edges (+ squares for (1, 0, 0)) from the raw
+ *                         counts; out float64[cap_sel] entry slot[c] = b; section_euler int64[cap_sel][13] row slot[c] = chi^in +
+ *                         chi^cross summed over the slices; labels int64[cap_sel] entry slot[c] = c + 1.  Guards and the
+ *                         unlabelled form (table == NULL: row 0 from the entries 0 .. nz - 1) are tomo_cc_surface's.
+ * TOMO_E_ARG for a null pointer, a non-positive size or directions other than 3 / 13; TOMO_E_SIZE from 2^31 words, runs,
+ * components or selected components on (2^60 / 18 histogram entries). */
+int tomo_cc_breadth_hist(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                         const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const int64_t *table, int64_t cap,
+                         const uint8_t *sel, const uint64_t *off, uint64_t *hist, int64_t hist_cap, void *stream);
+int tomo_cc_breadth(const int64_t *table, int64_t cap, unsigned long long *tot, const uint8_t *sel, const uint64_t *off,
+                    const uint32_t *slot, const uint64_t *hist, int64_t hist_cap, const double *B, int nz, int directions,
+                    double *out, int64_t *section_euler, int64_t *labels, int64_t cap_sel, void *stream);
 /* Inscribed sphere and local thickness per component (no counterpart in the reference).  Distance and local thickness are local
  * to a component: the nearest site of a voxel of component A is never a voxel of another component (stepping from such a site
  * towards the voxel ends at an unset voxel that is no farther), and the open digital ball round a centre where it fits is

@@ -75,6 +75,10 @@ SIGNATURES = {
                                     _c_p]),
     "tomo_cc_surface": (_c_i, [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_i64,
                                _c_p]),
+    "tomo_cc_breadth_hist": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64,
+                                    _c_p]),
+    "tomo_cc_breadth": (_c_i, [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_i64,
+                               _c_p]),
     "tomo_cc_value_max": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p]),
     "tomo_cc_value_first": (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p]),
     "tomo_cc_value_rows": (_c_i, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p]),

@@ -374,6 +374,9 @@ struct CcSumAcc {
 // ---------------------------------------------------------------------------------------------- the per-slice histograms
 #define CC_SURF 11                   // counters per component and slice of tomo_cc_surface_hist and tomo_branch_hist
 #define CC_SURF_CLASSES 7            // x, y, xy, z, xz, yz, xyz: the counters with up and down folded
+#define CC_BREADTH 18                // words per component and slice of tomo_cc_breadth_hist: CC_BREADTH_IN raw counts of the cells
+#define CC_BREADTH_IN 6              //   inside the slice, then the signed cross parts of the families but (1, 0, 0)
+#define CC_BREADTH_FAMILIES 13       // families of lattice planes: the columns of section_euler
 
 struct CcHist {
     const u64 *table, *off;                                 // both NULL: the whole volume is component 0, one entry per slice

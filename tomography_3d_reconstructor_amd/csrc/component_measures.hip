@@ -1,12 +1,12 @@
 // component_measures.hip -- what is measured per component on the run tables of components.hip: the measurement table
 // (voxels, box, index sums), the selection and its slice histograms (voxels, or six moment sums, per component and slice),
-// volume and centroid in mm, second moments and principal axes, Euler number, cavities and handles, surface area (Crofton),
-// what a per-voxel array gives per component (the inscribed sphere from the distance map, voxels per thickness level), and
-// caliper diameters along shared directions and along a component's own axes.
+// volume and centroid in mm, second moments and principal axes, Euler number, cavities and handles, surface area and
+// mean breadth (Crofton), what a per-voxel array gives per component (the inscribed sphere from the distance map, voxels per
+// thickness level), and caliper diameters along shared directions and along a component's own axes.
 // Every pass over the rows is an accumulator for the row pass of cc_runs.h -- over the runs, or, where a voxel's neighbours
-// decide (Euler number, surface area), over the words of the row with windows of the neighbour rows slid along; the integer
-// tables are integer atomics only, the float results are sequential sums over those integers (nothing is contracted in this
-// file: -ffp-contract=off).
+// decide (Euler number, surface area, mean breadth), over the words of the row with windows of the neighbour rows slid along;
+// the integer tables are integer atomics only, the float results are sequential sums over those integers (nothing is
+// contracted in this file: -ffp-contract=off).
 #include "cc_runs.h"
 
 // ---------------------------------------------------------------------------------------------- measurements per component
@@ -1175,6 +1175,189 @@ TOMO_API int tomo_cc_surface(const int64_t *table, int64_t cap, unsigned long lo
     hipLaunchKernelGGL(cc_surface_kernel, dim3(table ? (unsigned)ceil_div64(cap, CC_THREADS) : 1u), dim3(CC_THREADS), 0,
                        (hipStream_t)stream, (const u64 *)table, (const u64 *)tot, cap, sel, (const u64 *)off, (const u32 *)slot,
                        (const u64 *)surf, hist_cap, F, nz, directions, out, (u64 *)counts, labels, cap_sel,
+                       tot ? (u64 *)tot + 2 : (u64 *)nullptr);
+    return tomo_status();
+}
+
+// ---------------------------------------------------------------------------------------------- mean breadth (Crofton)
+// The fourth Minkowski functional: b = sum over the 13 families m of lattice planes of c_m * delta_m * chi_m, chi_m the sum over
+// the planes of the family of the 2-D Euler number V - E + F of the section (include/tomo_hip.h has the cells per family).  Every
+// cell is anchored at its raster-first corner p: filed in the slice of p, for the component of p, its other corners being any
+// set bits of the forward neighbourhood -- the row at x + 1, row (z, y + 1) and the rows (z + 1, y - 1 .. y + 1) at x - 1 ..
+// x + 1: five windows.  Per word the cells are ANDs of the run's mask with the shifted forward words, popcounted.
+// An entry of the histogram holds CC_BREADTH words (cc_runs.h):
+//   0 .. 5   the cells inside the slice, raw: voxels, edges along x, along y, along (0, 1, 1), along (0, 1, -1), squares x y
+//   6 .. 17  chi_m^cross = faces - edges of the cells with corners in slice k + 1, signed (two's complement, wrapping adds), for
+//            the families in ascending order without (1, 0, 0), which has no such cell
+// tomo_cc_breadth forms chi_m^in = voxels - edges (+ squares for (1, 0, 0)) from the six raw counts.
+struct CcBreadthAcc {
+    CcHist h;
+    const uint8_t *sel;
+    u32 ncomp, z;
+    u64 n[CC_BREADTH];
+    __device__ u32 filter(u32 c) const { return (c - 1 >= ncomp || !sel[c - 1]) ? 0u : c; }
+    __device__ bool any() const { return n[0] != 0; }
+    __device__ u32 begin(u32 c)
+    {
+#pragma unroll
+        for (int k = 0; k < CC_BREADTH; k++) n[k] = 0;
+        return c;
+    }
+    __device__ void word(const CcWin *) {}
+    // win: 0 the row, 1 row (z, y + 1), 2 .. 4 rows (z + 1, y - 1), (z + 1, y), (z + 1, y + 1)
+    __device__ void add(const CcWin *win, u64 t)
+    {
+        const u64 a = t & cc_xp(win[0]);                                        // p and p + x
+        const u64 Bc = win[1].cur, Bp = cc_xp(win[1]), Bm = cc_xm(win[1]);
+        const u64 Dc = win[2].cur, Dp = cc_xp(win[2]);
+        const u64 Ec = win[3].cur, Ep = cc_xp(win[3]), Em = cc_xm(win[3]);
+        const u64 Gc = win[4].cur, Gp = cc_xp(win[4]), Gm = cc_xm(win[4]);
+        const u64 tz = t & Ec, tEp = t & Ep, tEm = t & Em, tDc = t & Dc, tGc = t & Gc, ty = t & Bc;
+        const u64 ez = (u64)__popcll(tz), eEp = (u64)__popcll(tEp), eEm = (u64)__popcll(tEm), eDc = (u64)__popcll(tDc),
+                  eGc = (u64)__popcll(tGc);
+        n[0] += (u64)__popcll(t);
+        n[1] += (u64)__popcll(a);
+        n[2] += (u64)__popcll(ty);
+        n[3] += (u64)__popcll(t & Bp);
+        n[4] += (u64)__popcll(t & Bm);
+        n[5] += (u64)__popcll(a & Bc & Bp);
+        n[6] += (u64)__popcll(ty & Ec & Gc) - ez;                               // (0, 0, 1): squares y z - edges z
+        n[7] += (u64)__popcll(tz & Bp & Gp) - ez;                               // (0, 1, -1): rectangles z, (0, 1, 1)
+        n[8] += (u64)__popcll(a & Ec & Ep) - ez;                                // (0, 1, 0): squares x z
+        n[9] += (u64)__popcll(tz & Bm & Gm) - ez;                               // (0, 1, 1): rectangles z, (0, 1, -1)
+        n[10] += (u64)__popcll(tGc & Bm) + (u64)__popcll(tGc & Ep) - eGc - eEp; // (1, -1, -1): (0, 1, -1), (1, 1, 0), (1, 0, 1)
+        n[11] += (u64)__popcll(a & Gc & Gp) - eGc;                              // (1, -1, 0): rectangles x, (1, 1, 0)
+        n[12] += (u64)__popcll(tGc & Bp) + (u64)__popcll(tGc & Em) - eGc - eEm; // (1, -1, 1): (0, 1, 1), (1, 1, 0), (1, 0, -1)
+        n[13] += (u64)__popcll(ty & Ep & Gp) - eEp;                             // (1, 0, -1): rectangles y, (1, 0, 1)
+        n[14] += (u64)__popcll(ty & Em & Gm) - eEm;                             // (1, 0, 1): rectangles y, (1, 0, -1)
+        n[15] += (u64)__popcll(tEp & Bp) + (u64)__popcll(tEp & Dc) - eEp - eDc; // (1, 1, -1): (0, 1, 1), (1, 0, 1), (1, -1, 0)
+        n[16] += (u64)__popcll(a & Dc & Dp) - eDc;                              // (1, 1, 0): rectangles x, (1, -1, 0)
+        n[17] += (u64)__popcll(tEm & Bm) + (u64)__popcll(tEm & Dc) - eEm - eDc; // (1, 1, 1): (0, 1, -1), (1, 0, -1), (1, -1, 0)
+    }
+    __device__ CcSliceSum<CC_BREADTH> combine(bool mine, u32 zz) const
+    {
+        CcSliceSum<CC_BREADTH> w = {h, zz};
+#pragma unroll
+        for (int k = 0; k < CC_BREADTH; k++) w.v[k] = wave_sum64(mine ? n[k] : 0);
+        return w;
+    }
+    __device__ void flush(u32 c) const { cc_hist_add<CC_BREADTH>(h, c, z, n); }
+};
+
+template <bool LABELLED>
+__global__ __launch_bounds__(CC_THREADS) void cc_breadth_hist_kernel(const u64 *__restrict__ bits, int64_t nrows, int ny, int nx, int wx,
+                                                                     const u32 *__restrict__ row_off, const u64 *__restrict__ tot,
+                                                                     int64_t cap_runs, const u32 *__restrict__ parent,
+                                                                     const u32 *__restrict__ rank, const u64 *__restrict__ table,
+                                                                     int64_t cap, const uint8_t *__restrict__ sel,
+                                                                     const u64 *__restrict__ off, u64 *__restrict__ hist,
+                                                                     int64_t hist_cap, u64 *flags)
+{
+    const int64_t row = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    const u32 nruns = LABELLED ? (u32)cc_count(tot, cap_runs) : 0u;
+    const u64 total = LABELLED ? tot[4] : (u64)(nrows / ny);    // no labelling: one entry per slice (the host checked hist_cap)
+    const bool fits = total <= (u64)hist_cap;
+    const u32 ncomp = !fits ? 0u : LABELLED ? (u32)cc_ncomp(tot, cap) : 1u;      // a histogram that is too short: nothing is touched
+    if (LABELLED && row == 0 && (!fits || tot[1] > (u64)cap)) cc_flag(flags, CC_F_CAP);
+    const bool live = row < nrows && ncomp != 0;
+    CcBreadthAcc acc = {{table, off, hist, total, flags}, sel, ncomp, live ? (u32)(row / ny) : 0u, {}};
+    u32 comp = 0;                                           // SELECTED component + 1 the thread is left with, 0: none
+    if (live) {
+        const int y = (int)(row % ny);
+        const bool up = y + 1 < ny, down = y > 0, front = row + ny < nrows;
+        const u64 *self = bits + row * wx;
+        const u64 *r[5];
+        r[0] = self;
+        r[1] = up ? self + wx : nullptr;
+        r[2] = front && down ? self + (int64_t)(ny - 1) * wx : nullptr;
+        r[3] = front ? self + (int64_t)ny * wx : nullptr;
+        r[4] = front && up ? self + (int64_t)(ny + 1) * wx : nullptr;
+        comp = cc_window_walk<5, LABELLED, LABELLED>(r, nx, wx, LABELLED ? row_off[row] : 0u, nruns, parent, rank, flags, acc);
+    }
+    cc_wave_tail<true>(comp, acc.z, acc);
+}
+
+TOMO_API int tomo_cc_breadth_hist(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
+                                  const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const int64_t *table,
+                                  int64_t cap, const uint8_t *sel, const uint64_t *off, uint64_t *hist, int64_t hist_cap, void *stream)
+{
+    int64_t nrows;
+    int wx;
+    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
+    if (g != TOMO_OK) return g;
+    if (!hist || hist_cap <= 0) return TOMO_E_ARG;
+    if (parent && (!row_off || !rank || !tot || !table || !sel || !off || cap_runs <= 0 || cap <= 0)) return TOMO_E_ARG;
+    if (!parent && hist_cap < nz) return TOMO_E_ARG;
+    if (hist_cap >= ((int64_t)1 << 60) / CC_BREADTH || (parent && (cap_runs >= ((int64_t)1 << 31) || cap >= ((int64_t)1 << 31))))
+        return TOMO_E_SIZE;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(hist, 0, (size_t)hist_cap * CC_BREADTH * sizeof(u64), st) != hipSuccess) return TOMO_E_LAUNCH;
+    const dim3 grid((unsigned)ceil_div64(nrows, CC_THREADS)), block(CC_THREADS);
+    if (parent)
+        hipLaunchKernelGGL(cc_breadth_hist_kernel<true>, grid, block, 0, st, (const u64 *)bits, nrows, ny, nx, wx, (const u32 *)row_off,
+                           (const u64 *)tot, cap_runs, (const u32 *)parent, (const u32 *)rank, (const u64 *)table, cap, sel,
+                           (const u64 *)off, (u64 *)hist, hist_cap, (u64 *)tot + 2);
+    else
+        hipLaunchKernelGGL(cc_breadth_hist_kernel<false>, grid, block, 0, st, (const u64 *)bits, nrows, ny, nx, wx, (const u32 *)nullptr,
+                           (const u64 *)nullptr, (int64_t)0, (const u32 *)nullptr, (const u32 *)nullptr, (const u64 *)nullptr, (int64_t)1,
+                           (const uint8_t *)nullptr, (const u64 *)nullptr, (u64 *)hist, hist_cap, (u64 *)nullptr);
+    return tomo_status();
+}
+
+// One thread per component, as cc_surface_kernel; a selected one walks its slices in ascending z and per slice the columns
+// 0 .. 25 of B: 0 .. 12 the families' chi^in at the slice's own depth, 13 .. 25 their chi^cross at the mean depth towards slice
+// k + 1: b += (double)(int64)chi * B[z][column], plain sequential float64.  directions == 3: only the columns of (0, 0, 1),
+// (0, 1, 0) and (1, 0, 0) enter.  table == NULL: no labelling, thread 0 sums the slices 0 .. nz - 1 into row 0.
+__global__ __launch_bounds__(CC_THREADS) void cc_breadth_kernel(const u64 *__restrict__ table, const u64 *__restrict__ tot, int64_t cap,
+                                                                const uint8_t *__restrict__ sel, const u64 *__restrict__ off,
+                                                                const u32 *__restrict__ slot, const u64 *__restrict__ hist,
+                                                                int64_t hist_cap, const double *__restrict__ B, int nz, int directions,
+                                                                double *__restrict__ out, u64 *__restrict__ euler,
+                                                                int64_t *__restrict__ labels, int64_t cap_sel, u64 *flags)
+{
+    const int64_t c = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    CcSegment s = {0, (u64)nz - 1, 0, 0};
+    if (table ? !cc_segment(table, tot, cap, sel, off, slot, hist_cap, nz, cap_sel, c, flags, s) : c != 0) return;
+    double b = 0.0;
+    u64 chi[CC_BREADTH_FAMILIES] = {};
+    for (u64 z = s.z0; z <= s.z1; z++) {
+        const u64 *m = hist + CC_BREADTH * (s.o + (z - s.z0));
+        const double *F = B + 2 * CC_BREADTH_FAMILIES * z;
+        const u64 v = m[0], ex = m[1], ey = m[2], ep = m[3], em = m[4];
+        const u64 in[CC_BREADTH_FAMILIES] = {v - ey, v - ep, v - ex, v - em, v - em, v - ex, v - ep, v - ey, v - ex - ey + m[5],
+                                             v - ey, v - ep, v - ex, v - em};
+#pragma unroll
+        for (int f = 0; f < CC_BREADTH_FAMILIES; f++) {
+            if (directions == 13 || f == 0 || f == 2 || f == 8) b += (double)(int64_t)in[f] * F[f];
+            chi[f] += in[f];
+        }
+#pragma unroll
+        for (int f = 0; f < CC_BREADTH_FAMILIES; f++) {
+            const u64 x = f == 8 ? 0ull : m[CC_BREADTH_IN + (f < 8 ? f : f - 1)];
+            if (directions == 13 || f == 0 || f == 2 || f == 8) b += (double)(int64_t)x * F[CC_BREADTH_FAMILIES + f];
+            chi[f] += x;
+        }
+    }
+    out[s.k] = b;
+#pragma unroll
+    for (int f = 0; f < CC_BREADTH_FAMILIES; f++) euler[CC_BREADTH_FAMILIES * (int64_t)s.k + f] = chi[f];
+    labels[s.k] = c + 1;
+}
+
+TOMO_API int tomo_cc_breadth(const int64_t *table, int64_t cap, unsigned long long *tot, const uint8_t *sel, const uint64_t *off,
+                             const uint32_t *slot, const uint64_t *hist, int64_t hist_cap, const double *B, int nz, int directions,
+                             double *out, int64_t *section_euler, int64_t *labels, int64_t cap_sel, void *stream)
+{
+    if (!hist || !B || !out || !section_euler || !labels || hist_cap <= 0 || nz <= 0 || cap_sel <= 0 ||
+        (directions != 3 && directions != 13))
+        return TOMO_E_ARG;
+    if (table && (!tot || !sel || !off || !slot || cap <= 0)) return TOMO_E_ARG;
+    if (!table && hist_cap < nz) return TOMO_E_ARG;
+    if (cap_sel >= ((int64_t)1 << 31) || hist_cap >= ((int64_t)1 << 60) / CC_BREADTH || (table && cap >= ((int64_t)1 << 31)))
+        return TOMO_E_SIZE;
+    hipLaunchKernelGGL(cc_breadth_kernel, dim3(table ? (unsigned)ceil_div64(cap, CC_THREADS) : 1u), dim3(CC_THREADS), 0,
+                       (hipStream_t)stream, (const u64 *)table, (const u64 *)tot, cap, sel, (const u64 *)off, (const u32 *)slot,
+                       (const u64 *)hist, hist_cap, B, nz, directions, out, (u64 *)section_euler, labels, cap_sel,
                        tot ? (u64 *)tot + 2 : (u64 *)nullptr);
     return tomo_status();
 }

@@ -7,6 +7,7 @@ times these functions directly with the inputs already resident.
 
 Reference lines each function replaces are given in its docstring.
 """
+import itertools
 import math
 import os
 import threading
@@ -30,7 +31,7 @@ COUNTERS = dict.fromkeys(("na_hint_hit", "na_hint_miss", "mc3_hint_hit", "mc3_hi
                           "separate_components", "zone_contacts", "contact_launches", "recon_calls", "recon_sweeps",
                           "thin_calls", "thin_iterations", "thin_passes", "thin_nodes", "component_skeleton",
                           "skeleton_branches", "branch_split", "skeleton_branches_hist", "branch_attach", "branch_lookup", "branch_clear",
-                          "prune_rounds", "components_profile", "branch_profile", "prune_relative"), 0)
+                          "prune_rounds", "components_profile", "branch_profile", "prune_relative", "components_breadth"), 0)
 NA_HINTS = os.environ.get("TOMO_NA_HINTS", "1") not in ("", "0")   # marching_cubes: launch ahead of the first count download
 _NA_HINT = {}
 LIST_LIMIT = 2 ** 31        # active-voxel list entries / vertices / triangles one pass can index (int32 offsets in mc.hip, mesh.hip);
@@ -246,7 +247,8 @@ CONNECTIVITIES = (6, 26)     # generate_binary_structure(3, 1) -- the cross of v
 RUN_LIMIT = 2 ** 31          # run ids are 32-bit in csrc/components.hip
 TABLE_COLUMNS = 10           # voxels, zmin, zmax, ymin, ymax, xmin, xmax, sum z, sum y, sum x (tomo_cc_measure)
 # bytes component_properties / component_moments / component_surface may take for the per-slice entries of the selected components
-# (8 bytes an entry for the voxel counts, 48 for the six moment sums, 88 for the surface counters); one component (at most nz
+# (8 bytes an entry for the voxel counts, 48 for the six moment sums, 88 for the surface counters, 144 for the section counters
+# of the mean breadth); one component (at most nz
 # entries) is always granted
 COMPONENT_HIST_BUDGET = 1 << 30
 MOMENT_SUMS = 6              # uint64 per component and slice: N, sum j', sum i', sum j'^2, sum i'^2, sum j' i' (tomo_cc_moment_hist)
@@ -254,6 +256,9 @@ MOMENT_COLUMNS = 22          # float64 per row of tomo_cc_moments: W, centre (3)
 TOPOLOGY_COLUMNS = 3         # euler, cavities, handles (tomo_cc_cavities)
 SURFACE_COUNTERS = 11        # uint64 per component and slice: x, y, xy, then z, xz, yz, xyz upwards and downwards (tomo_cc_surface_hist)
 SURFACE_CLASSES = 7          # direction classes: x, y, xy, z, xz, yz, xyz
+BREADTH_WORDS = 18           # uint64 per component and slice: six raw in-slice counts, twelve signed cross parts (tomo_cc_breadth_hist)
+BREADTH_FAMILIES = 13        # families of lattice planes: the columns of section_euler (breadth_normals)
+BREADTH_COLUMNS = 26         # float64 per slice of breadth_factors: the families in the slice, then towards slice k + 1
 PROFILE_COLUMNS = 7          # label, voxels, min bits, max bits, sum_q, min index, max index (tomo_profile_rows)
 PROFILE_ADMITTED = 0x49800000    # float32 bit patterns below it are admitted by tomo_profile_stats: 0.0 <= v < 2^20
 PROFILE_F_VALUE = 8          # bit of the flag word: tomo_profile_stats met a set voxel whose value is not admitted
@@ -321,6 +326,8 @@ _MOMENTS = _Measurement("component_moments", ((torch.float64, (MOMENT_COLUMNS,))
                         "tomo_cc_moment_hist", "components_moments", "tomo_cc_moments", 2)
 _SURFACE = _Measurement("component_surface", ((torch.float64, ()), (torch.int64, (SURFACE_CLASSES,))), 0, SURFACE_COUNTERS,
                         "surface counters per slice", "tomo_cc_surface_hist", "components_surface", "tomo_cc_surface")
+_BREADTH = _Measurement("component_breadth", ((torch.float64, ()), (torch.int64, (BREADTH_FAMILIES,))), 0, BREADTH_WORDS,
+                        "section counters per slice", "tomo_cc_breadth_hist", "components_breadth", "tomo_cc_breadth")
 _TOPOLOGY = _Measurement("component_topology", ((torch.int64, (2 + TOPOLOGY_COLUMNS,)),))
 _BRANCHES = _Measurement("skeleton_branches", ((torch.float64, ()), (torch.int64, (SURFACE_CLASSES,))), 0, SURFACE_COUNTERS,
                          "step counters per slice", "tomo_branch_hist", "skeleton_branches_hist", "tomo_cc_surface")
@@ -517,6 +524,12 @@ class ComponentRuns:
         rule = _keep_rule(min_voxels, largest, max_voxels, enclosed)
         voxels, labels, area, counts = self._rows(_SURFACE, rule, factors, int(directions))
         return _component_surface_from(voxels, labels, counts, area)
+
+    def breadth(self, factors, directions, min_voxels=0, largest=False, *, max_voxels=None, enclosed=False) -> "ComponentBreadth":
+        """component_breadth of this volume; factors: breadth_factors' (nz, 26) for the same directions.  The rule: select's."""
+        rule = _keep_rule(min_voxels, largest, max_voxels, enclosed)
+        voxels, labels, breadth, euler = self._rows(_BREADTH, rule, factors, int(directions))
+        return _component_breadth_from(voxels, labels, euler, breadth)
 
     def topology_rows(self, min_voxels=0, largest=False, *, max_voxels=None, enclosed=False) -> "ComponentTopology":
         """component_topology of this volume: the rows of topology() the rule (select's) selects."""
@@ -1353,6 +1366,131 @@ def component_surface(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_
     entry; beyond COMPONENT_HIST_BUDGET bytes for more than one component: TomoError) -- never with the voxels."""
     F = surface_factors(slice_depths, vol.shape[0], mm_per_pixel_y, mm_per_pixel_x, directions)
     return ComponentRuns(vol, connectivity).surface(F, directions, min_voxels, largest)
+
+
+# ----------------------------------------------------------------------------- mean breadth (Crofton)
+_BREADTH_NORMALS = tuple(m for m in itertools.product((-1, 0, 1), repeat=3) if m > (0, 0, 0))      # ascending (a_z, a_y, a_x)
+_BREADTH_NO_CROSS = _BREADTH_NORMALS.index((1, 0, 0))               # the family whose cells all lie in one slice
+_BREADTH_AXES = tuple(_BREADTH_NORMALS.index(m) for m in ((0, 0, 1), (0, 1, 0), (1, 0, 0)))
+
+
+def breadth_normals() -> np.ndarray:
+    """The Miller indices (a_z, a_y, a_x) of the 13 families of lattice planes of mean_breadth, first non-zero entry positive,
+    in ascending tuple order -> int64 (13, 3): the columns of section_euler."""
+    return np.array(_BREADTH_NORMALS, dtype=np.int64)
+
+
+def breadth_factors(slice_depths, nz, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, directions=13) -> np.ndarray:
+    """What one unit of a section Euler number of slice k adds to the mean breadth -> float64 (nz, 26): B[k][f] = c_m * delta_m
+    for family f of breadth_normals() on a lattice of height h = depth[k] (columns 0 .. 12: the cells inside the slice) and
+    h = (depth[k] + depth[k + 1]) / 2 (columns 13 .. 25: the cells with corners in slice k + 1).  delta_m = 1 / |n| is the plane
+    spacing, n = (a_z / h, a_y / mm_y, a_x / mm_x) the normal, and c_m = crofton_weights(1 / mm_x, 1 / mm_y, 1 / h, directions) of
+    the class (|a_z|, |a_y|, |a_x|): the Voronoi shares of the normals, which are the lattice directions of the reciprocal box;
+    over the 13 families they sum to 1.  directions=3: 1 / 3 for the three axis normals, 0 otherwise.  The cross columns are 0.0
+    in the last slice, and that of (1, 0, 0) -- no cell of it leaves its slice -- everywhere.  slice_depths=None: 1.0 per slice."""
+    if directions not in (3, 13):
+        raise ValueError("directions must be 3 or 13")
+    zt, _, _ = distance_positions(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x)        # the argument checks
+    nz = len(zt) - 2
+    mm_y, mm_x = float(mm_per_pixel_y), float(mm_per_pixel_x)
+    d = np.ones(nz) if slice_depths is None else np.asarray(slice_depths, dtype=np.float64).reshape(-1)
+    rows = {}
+
+    def row(h):
+        """The 13 factors of a lattice of height h, computed once per distinct height."""
+        h = float(h)
+        if h not in rows:
+            w = crofton_weights(1.0 / mm_x, 1.0 / mm_y, 1.0 / h, directions)
+            rows[h] = [w[_SURFACE_CLASS_STEPS.index((abs(az), abs(ay), abs(ax)))]
+                       * (1.0 / math.sqrt((az / h) ** 2 + (ay / mm_y) ** 2 + (ax / mm_x) ** 2)) for az, ay, ax in _BREADTH_NORMALS]
+        return rows[h]
+
+    B = np.zeros((nz, BREADTH_COLUMNS), dtype=np.float64)
+    for cols, rng, heights in ((slice(0, BREADTH_FAMILIES), slice(0, nz), d), (slice(BREADTH_FAMILIES, BREADTH_COLUMNS), slice(0, nz - 1),
+                                                                            (d[:-1] + d[1:]) / 2.0)):
+        if len(heights):
+            distinct, which = np.unique(heights, return_inverse=True)
+            B[rng, cols] = np.array([row(h) for h in distinct], dtype=np.float64)[which.reshape(-1)]
+    B[:, BREADTH_FAMILIES + _BREADTH_NO_CROSS] = 0.0
+    return B
+
+
+@dataclass
+class MeanBreadth:
+    """mean_breadth's answer."""
+    mean_breadth_mm: float
+    section_euler: np.ndarray    # int64 (13,): the Euler numbers of the plane sections per family of breadth_normals()
+
+
+@dataclass
+class ComponentBreadth:
+    """component_breadth's answer: host arrays, one row per selected component in ascending label."""
+    labels: np.ndarray            # int64 (m,)
+    voxels: np.ndarray            # int64 (m,)
+    section_euler: np.ndarray     # int64 (m, 13): the Euler numbers of the plane sections per family of breadth_normals()
+    mean_breadth_mm: np.ndarray   # float64 (m,)
+
+    def __len__(self):
+        return len(self.labels)
+
+
+def mean_breadth(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, directions=13) -> MeanBreadth:
+    """The mean breadth of a resident volume in mm -- the fourth Minkowski functional: 2 pi times it is the integral of mean
+    curvature, and for a convex body it is the caliper diameter averaged over all directions -- by the discretised Crofton
+    formula (Ohser & Muecklich), without a mesh and without labelling: b = sum over the 13 families of lattice planes of
+    c_m * delta_m * chi_m, chi_m the Euler number V - E + F of the sections of the set by the planes of the family, on the
+    lattice of the plane (include/tomo_hip.h has the cells).  The spacing is distance_transform's (slice_depths=None: 1.0 per
+    slice): the cells inside slice k use its depth, those towards slice k + 1 the mean of the two; the sum is sequential
+    float64 over the slices in ascending z and the columns of breadth_factors(...).  directions=3 uses the three axis normals
+    only: a box of a x b x c mm reads (a + b + c) / 3 there.  A ball of R = 8 voxels reads 1.017 of 2 R, of R = 16 1.004; a box
+    with axis-aligned faces is underestimated (0.873 of (a + b + c) / 2 for a cube): the flat-face bias surface_area has.  An
+    inner surface counts negatively: a hollow ball reads outer minus inner diameter.  Two launches, one host read."""
+    nz, ny, nx = vol.shape
+    B = breadth_factors(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x, directions)
+    L, dev, st = _lib.lib(), vol.device, _stream()
+    hist = torch.empty(BREADTH_WORDS * nz, dtype=torch.int64, device=dev)
+    COUNTERS["components_breadth"] += 1
+    _lib.check(L.tomo_cc_breadth_hist(_p(vol.bits.contiguous()), nz, ny, nx, None, 0, None, None, None, None, 0, None, None, _p(hist),
+                                      nz, st), "tomo_cc_breadth_hist")
+    tab = torch.from_numpy(B).to(dev)
+    out = torch.empty(2 + BREADTH_FAMILIES, dtype=torch.float64, device=dev)      # the breadth, the label, the 13 numbers: one read
+    words = out.view(torch.int64)
+    _lib.check(L.tomo_cc_breadth(None, 0, None, None, None, None, _p(hist), nz, _p(tab), nz, int(directions),
+                                 _p(out), _p(words[2:]), _p(words[1:2]), 1, st), "tomo_cc_breadth")
+    host = out.cpu().numpy()
+    return MeanBreadth(float(host[0]), host[2:].view(np.int64).copy())
+
+
+def _component_breadth_from(voxels, labels, euler, breadth) -> ComponentBreadth:
+    return ComponentBreadth(labels, voxels, np.ascontiguousarray(euler, dtype=np.int64).reshape(-1, BREADTH_FAMILIES), breadth)
+
+
+def component_breadth(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, connectivity=6, min_voxels=0,
+                      largest=False, directions=13) -> ComponentBreadth:
+    """Mean breadth per component of a resident volume by the discretised Crofton formula (mean_breadth) -> ComponentBreadth,
+    one row per component the keep rule of component_properties selects (at least min_voxels voxels; largest: only the largest
+    of those, the lowest label among equals), in ascending label: the rows, in the same order, component_properties returns
+    for the same arguments.  Every cell (vertex, edge, face of a section) is anchored at its raster-first corner and credited
+    to the component of that corner.  Under connectivity 26 all corners of a cell lie in one component, so a row is exactly the
+    value of the mask `labels == c`; a cell across a diagonal contact under connectivity 6 goes to the component of its first
+    corner, so under both connectivities the counts of all components add up to mean_breadth's.  The same four host reads as
+    component_properties; working memory scales with the runs, the components and 18 counters per slice of the box of every
+    SELECTED component (144 bytes an entry; beyond COMPONENT_HIST_BUDGET bytes for more than one component: TomoError) --
+    never with the voxels."""
+    B = breadth_factors(slice_depths, vol.shape[0], mm_per_pixel_y, mm_per_pixel_x, directions)
+    return ComponentRuns(vol, connectivity).breadth(B, directions, min_voxels, largest)
+
+
+def cavity_breadth(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, connectivity=6, min_voxels=0,
+                   max_voxels=None, directions=13) -> ComponentBreadth:
+    """component_breadth of the enclosed voids of a resident volume, one row per cavity of cavity_table under the same size
+    window (min_voxels <= voxels <= max_voxels), in ascending cavity label: the mean caliper diameter of a convex pore.  One
+    labelling of the complement under the complementary connectivity, which is the one the cells of a cavity are credited
+    under; an empty or a full volume has no rows.  Arguments are checked before the first launch."""
+    connectivity = _check_connectivity(connectivity)
+    lo, hi = _check_size_window(min_voxels, max_voxels)
+    B = breadth_factors(slice_depths, vol.shape[0], mm_per_pixel_y, mm_per_pixel_x, directions)
+    return _complement_runs(vol, connectivity).breadth(B, directions, lo, max_voxels=hi, enclosed=True)
 
 
 # ----------------------------------------------------------------------------- Euclidean distance in millimetres

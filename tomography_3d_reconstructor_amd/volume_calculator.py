@@ -9,6 +9,8 @@ float64 operations on the host, done in the order that makes every returned numb
 The host arithmetic is exposed as plain functions of (slice counts, index box) so that a Z-slab job can feed it the
 all-gathered per-rank reductions (slab.SlabJob.voxel_volume / bounding_box) and get the very same numbers.
 """
+import math
+
 import numpy as np
 
 from . import pipeline
@@ -143,6 +145,51 @@ def surface_area(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, direc
     s = pipeline.surface_area(vol, depths, mm_per_pixel_y, mm_per_pixel_x, directions).surface_area_mm2
     v = float(volume_from_slice_counts(pipeline.slice_counts(vol).cpu().numpy(), mm_per_pixel_x, mm_per_pixel_y, depths))
     return {'surface_area_mm2': s, 'voxel_volume_mm3': v, 'sphericity': sphericity(v, s)}
+
+
+def mean_breadth(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, directions=13):
+    """The mean breadth of the whole volume in mm (no counterpart in the reference): the fourth Minkowski functional by the
+    discretised Crofton formula on the voxels (pipeline.mean_breadth: per-slice depths honoured, everything outside the stack
+    is background; directions=13, or 3 for the axis normals alone) -> a Python float; 2 pi times it is the integral of mean
+    curvature.  voxel_data: the bool (nz, ny, nx) array the other calculations take; anything else is a TypeError -- there is
+    no host path for this one."""
+    if not _on_device(voxel_data):
+        raise TypeError("mean_breadth needs a bool (nz, ny, nx) array")
+    depths = np.asarray(slice_depths, dtype=np.float64).reshape(-1)
+    pipeline.breadth_factors(depths, voxel_data.shape[0], mm_per_pixel_y, mm_per_pixel_x, directions)   # the argument checks
+    return pipeline.mean_breadth(to_device_volume(voxel_data), depths, mm_per_pixel_y, mm_per_pixel_x, directions).mean_breadth_mm
+
+
+def minkowski_functionals(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=26, directions=13):
+    """The four Minkowski functionals (intrinsic volumes) of the volume and of its components (no counterpart in the
+    reference) -> {'volume_mm3', 'surface_area_mm2', 'mean_breadth_mm', 'mean_curvature_integral_mm' (2 pi mean_breadth_mm),
+    'euler_number'} of the whole volume -- slice_counts, pipeline.surface_area, pipeline.mean_breadth and pipeline.euler_number
+    under `connectivity`, none of which labels anything -- then the four densities per mm^3 of the stack ('volume_fraction',
+    'surface_density_per_mm', 'mean_curvature_density_per_mm2', 'euler_density_per_mm3'; the stack is nx mm_x by ny mm_y by the
+    sum of the depths) and 'components': the dicts of component_properties(..., connectivity, topology=True, surface=True,
+    breadth=True) with `directions` for both estimators.  Every additive, motion-invariant measure of a grain or a pore is a
+    combination of the four.  Arguments are checked before the first launch; voxel_data: a bool (nz, ny, nx) array, else a
+    TypeError."""
+    if not _on_device(voxel_data):
+        raise TypeError("minkowski_functionals needs a bool (nz, ny, nx) array")
+    depths = np.asarray(slice_depths, dtype=np.float64).reshape(-1)
+    nz, ny, nx = voxel_data.shape
+    pipeline._check_connectivity(connectivity)
+    pipeline.surface_factors(depths, nz, mm_per_pixel_y, mm_per_pixel_x, directions)                    # the argument checks
+    pipeline.breadth_factors(depths, nz, mm_per_pixel_y, mm_per_pixel_x, directions)
+    vol = to_device_volume(voxel_data)
+    v = float(volume_from_slice_counts(pipeline.slice_counts(vol).cpu().numpy(), mm_per_pixel_x, mm_per_pixel_y, depths))
+    s = pipeline.surface_area(vol, depths, mm_per_pixel_y, mm_per_pixel_x, directions).surface_area_mm2
+    b = pipeline.mean_breadth(vol, depths, mm_per_pixel_y, mm_per_pixel_x, directions).mean_breadth_mm
+    e = int(pipeline.euler_number(vol, connectivity))
+    stack = float(nx * float(mm_per_pixel_x) * (ny * float(mm_per_pixel_y)) * float(np.sum(depths)))
+    m = 2.0 * math.pi * b
+    return {'volume_mm3': v, 'surface_area_mm2': s, 'mean_breadth_mm': b, 'mean_curvature_integral_mm': m, 'euler_number': e,
+            'volume_fraction': v / stack, 'surface_density_per_mm': s / stack, 'mean_curvature_density_per_mm2': m / stack,
+            'euler_density_per_mm3': e / stack,
+            'components': component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, depths, connectivity, topology=True,
+                                               surface=True, surface_directions=directions, breadth=True,
+                                               breadth_directions=directions)}
 
 
 def closed_porosity(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=6, min_voxels=0, max_voxels=None,
@@ -436,8 +483,8 @@ def skeleton_thickness_report(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_
 
 def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=6, min_voxels=0, largest=False,
                          shape=False, topology=False, surface=False, surface_directions=13, porosity=False, thickness=False,
-                         thickness_radii_mm=None, geodesic=False, geodesic_sweeps=3, separate_mm=None, separate_h_mm=None,
-                         skeleton=False, caliper=False,
+                         thickness_radii_mm=None, geodesic=False, geodesic_sweeps=3, breadth=False, breadth_directions=13,
+                         separate_mm=None, separate_h_mm=None, skeleton=False, caliper=False,
                          caliper_directions=None, caliper_oriented=False):
     """The calculations of the class per connected component (no counterpart in the reference, which would be handed the mask
     `labels == c` once per component) -> a list of dicts, one per component with at least min_voxels voxels (largest: only the
@@ -479,6 +526,10 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
     skeleton (pipeline.component_skeleton: ONE thinning of the whole volume under `connectivity`, counted under the runs of the
     one labelling; in voxel steps, the spacing plays no part).  The curve skeleton needs connectivity=26: skeleton=True with
     connectivity=6 is a ValueError.
+    breadth=True (a keyword; off: nothing new is launched): every dict also carries 'mean_breadth_mm' -- the fourth Minkowski
+    functional by the discretised Crofton formula on the component's voxels (pipeline.component_breadth; breadth_directions =
+    13 or 3; for a convex grain the caliper diameter averaged over all directions) -- and 'mean_curvature_integral_mm' =
+    2 pi mean_breadth_mm as Python floats.
     Whatever the
     flags, the volume is uploaded and labelled ONCE, and so is its complement: one pipeline.ComponentRuns serves all the
     measurements and owns the one selection their rows come from.  Arguments are checked before the first launch.  voxel_data: a bool (nz, ny, nx) array, else a TypeError."""
@@ -489,6 +540,7 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
     pipeline._check_connectivity(connectivity)
     tables = pipeline._slice_weights(depths, len(voxel_data), mm_per_pixel_y, mm_per_pixel_x)
     factors = pipeline.surface_factors(depths, len(voxel_data), mm_per_pixel_y, mm_per_pixel_x, surface_directions) if surface else None
+    breadth_factors = pipeline.breadth_factors(depths, len(voxel_data), mm_per_pixel_y, mm_per_pixel_x, breadth_directions) if breadth else None
     if thickness:
         pipeline._component_thickness_args(voxel_data.shape, depths, mm_per_pixel_y, mm_per_pixel_x, thickness_radii_mm)
     if caliper:
@@ -525,6 +577,7 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
     f = runs.caliper(depths, mm_per_pixel_y, mm_per_pixel_x, caliper_directions, "voxels", caliper_oriented, *rule) if caliper else None
     g = runs.geodesic(depths, mm_per_pixel_y, mm_per_pixel_x, geodesic_sweeps, *rule) if geodesic else None
     k = runs.skeleton(*rule) if skeleton else None
+    w = runs.breadth(breadth_factors, breadth_directions, *rule) if breadth else None
     pores = {}
     if porosity:                                                 # every cavity of the volume, credited to its owner
         c = pipeline._cavities_from(runs, runs.background().properties(tables, mm_per_pixel_y, mm_per_pixel_x, enclosed=True))
@@ -572,6 +625,9 @@ def component_properties(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depth
         if skeleton:
             d['skeleton_voxels'], d['skeleton_ends'] = int(k.skeleton_voxels[i]), int(k.end_points[i])
             d['skeleton_junctions'] = int(k.junction_voxels[i])
+        if breadth:
+            d['mean_breadth_mm'] = float(w.mean_breadth_mm[i])
+            d['mean_curvature_integral_mm'] = 2.0 * math.pi * d['mean_breadth_mm']
     return out
 
 
