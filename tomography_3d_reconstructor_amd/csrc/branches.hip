@@ -97,43 +97,20 @@ __device__ static inline void branch_node_beside(const CcWin &s, const CcWin &r,
     side += (u64)(__popcll(mask & cc_xp(s) & ~cc_xp(r)) + __popcll(mask & cc_xm(s) & ~cc_xm(r)));
 }
 
-// what the lanes of a wave hold for one slice, added up
-struct BranchSliceSum {
-    const CcHist &h;
-    u32 z;
-    u64 v[CC_SURF];
-    __device__ bool any() const
-    {
-        u64 a = 0;
-#pragma unroll
-        for (int k = 0; k < CC_SURF; k++) a |= v[k];
-        return a != 0;
-    }
-    __device__ void flush(u32 c) const { cc_hist_add<CC_SURF>(h, c, z, v); }
+struct BranchExtra {
+    const u64 *other;                                       // S, the volume the regular voxels were split from
 };
 
-// The accumulator of row (z, y).  A regular voxel whose two neighbours are earlier regular voxels counts nothing: any() asks
-// every counter, not the first one.
-struct BranchAcc {
-    CcHist h;
-    const uint8_t *sel;
-    u32 ncomp, z;
-    u64 n[CC_SURF];
-    __device__ u32 filter(u32 c) const { return (c - 1 >= ncomp || !sel[c - 1]) ? 0u : c; }
-    __device__ bool any() const
-    {
-        u64 a = 0;
-#pragma unroll
-        for (int k = 0; k < CC_SURF; k++) a |= n[k];
-        return a != 0;
-    }
-    __device__ u32 begin(u32 c)
-    {
-#pragma unroll
-        for (int k = 0; k < CC_SURF; k++) n[k] = 0;
-        return c;
-    }
-    __device__ void word(const CcWin *) {}
+// The accumulator of row (z, y) of the histogram pass (cc_runs.h).  ANY_ALL: a regular voxel whose two neighbours are earlier
+// regular voxels counts nothing, so any() asks every counter, not the first one.
+struct BranchAcc : CcCounts<CC_SURF, true> {
+    using CcCounts::CcCounts;
+    using Extra = BranchExtra;
+    static constexpr bool UNLABELLED = false;
+    static constexpr int NR = BRANCH_WINDOWS;
+    static constexpr CcRowAt ROWS[NR] = {{0, 0, 0}, {0, -1, 0}, {-1, -1, 0}, {-1, 0, 0}, {-1, 1, 0},                 // of R
+                                         {0, 0, 1}, {0, -1, 1}, {0, 1, 1}, {1, -1, 1}, {1, 0, 1}, {1, 1, 1},         // of S
+                                         {-1, -1, 1}, {-1, 0, 1}, {-1, 1, 1}};
     __device__ void add(const CcWin *win, u64 mask)
     {
         n[0] += (u64)(__popcll(mask & cc_xp(win[5])) + __popcll(mask & cc_xm(win[5]) & ~cc_xm(win[0])));
@@ -146,77 +123,16 @@ struct BranchAcc {
         branch_node_beside(win[12], win[3], mask, n[7], n[8]);
         branch_node_beside(win[13], win[4], mask, n[9], n[10]);
     }
-    __device__ BranchSliceSum combine(bool mine, u32 zz) const
-    {
-        BranchSliceSum w = {h, zz, {}};
-#pragma unroll
-        for (int k = 0; k < CC_SURF; k++) w.v[k] = wave_sum64(mine ? n[k] : 0);
-        return w;
-    }
-    __device__ void flush(u32 c) const { cc_hist_add<CC_SURF>(h, c, z, n); }
 };
-
-__global__ __launch_bounds__(CC_THREADS) void branch_hist_kernel(const u64 *__restrict__ bits, int64_t nrows, int ny, int nx, int wx,
-                                                                 const u32 *__restrict__ row_off, const u64 *__restrict__ tot,
-                                                                 int64_t cap_runs, const u32 *__restrict__ parent,
-                                                                 const u32 *__restrict__ rank, const u64 *__restrict__ table,
-                                                                 int64_t cap, const uint8_t *__restrict__ sel,
-                                                                 const u64 *__restrict__ off, u64 *__restrict__ hist, int64_t hist_cap,
-                                                                 const u64 *__restrict__ other, u64 *flags)
-{
-    const int64_t row = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
-    const u32 nruns = (u32)cc_count(tot, cap_runs);
-    const u64 total = tot[4];
-    const bool fits = total <= (u64)hist_cap;
-    const u32 ncomp = fits ? (u32)cc_ncomp(tot, cap) : 0u;  // a histogram that is too short: nothing is touched
-    if (row == 0 && (!fits || tot[1] > (u64)cap)) cc_flag(flags, CC_F_CAP);
-    const bool live = row < nrows && ncomp != 0;
-    BranchAcc acc = {{table, off, hist, total, flags}, sel, ncomp, live ? (u32)(row / ny) : 0u, {}};
-    u32 comp = 0;                                           // SELECTED component + 1 the thread is left with, 0: none
-    if (live) {
-        const int y = (int)(row % ny);
-        const bool up = y + 1 < ny, down = y > 0, front = row + ny < nrows, back = row >= ny;
-        const u64 *self = bits + row * wx, *all = other + row * wx;
-        const int64_t slice = (int64_t)ny * wx;
-        const u64 *r[BRANCH_WINDOWS];
-        r[0] = self;
-        r[1] = down ? self - wx : nullptr;
-        r[2] = back && down ? self - slice - wx : nullptr;
-        r[3] = back ? self - slice : nullptr;
-        r[4] = back && up ? self - slice + wx : nullptr;
-        r[5] = all;
-        r[6] = down ? all - wx : nullptr;
-        r[7] = up ? all + wx : nullptr;
-        r[8] = front && down ? all + slice - wx : nullptr;
-        r[9] = front ? all + slice : nullptr;
-        r[10] = front && up ? all + slice + wx : nullptr;
-        r[11] = back && down ? all - slice - wx : nullptr;
-        r[12] = back ? all - slice : nullptr;
-        r[13] = back && up ? all - slice + wx : nullptr;
-        comp = cc_window_walk<BRANCH_WINDOWS, true, true>(r, nx, wx, row_off[row], nruns, parent, rank, flags, acc);
-    }
-    cc_wave_tail<true>(comp, acc.z, acc);
-}
 
 TOMO_API int tomo_branch_hist(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
                               const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const int64_t *table, int64_t cap,
                               const uint8_t *sel, const uint64_t *off, uint64_t *hist, int64_t hist_cap, const uint64_t *other,
                               void *stream)
 {
-    int64_t nrows;
-    int wx;
-    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
-    if (g != TOMO_OK) return g;
-    if (!row_off || !parent || !rank || !tot || !table || !sel || !off || !hist || !other || cap_runs <= 0 || cap <= 0 || hist_cap <= 0 ||
-        (const void *)hist == (const void *)bits || (const void *)hist == (const void *)other)
-        return TOMO_E_ARG;
-    if (hist_cap >= ((int64_t)1 << 60) / CC_SURF || cap_runs >= ((int64_t)1 << 31) || cap >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(hist, 0, (size_t)hist_cap * CC_SURF * sizeof(u64), st) != hipSuccess) return TOMO_E_LAUNCH;
-    hipLaunchKernelGGL(branch_hist_kernel, dim3((unsigned)ceil_div64(nrows, CC_THREADS)), dim3(CC_THREADS), 0, st, (const u64 *)bits, nrows,
-                       ny, nx, wx, (const u32 *)row_off, (const u64 *)tot, cap_runs, (const u32 *)parent, (const u32 *)rank,
-                       (const u64 *)table, cap, sel, (const u64 *)off, (u64 *)hist, hist_cap, (const u64 *)other, (u64 *)tot + 2);
-    return tomo_status();
+    const bool ok = other && (const void *)hist != (const void *)bits && (const void *)hist != (const void *)other;
+    return cc_hist_launch<BranchAcc>(bits, nz, ny, nx, row_off, cap_runs, parent, rank, tot, table, cap, sel, off, hist, hist_cap, ok,
+                                     {(const u64 *)other}, stream);
 }
 
 // ---------------------------------------------------------------------------------------------- the attachments of a branch

@@ -1,14 +1,18 @@
 // cc_runs.h -- the device-side vocabulary of the run tables (components.hip labels them, component_measures.hip measures
 // what they hold, branches.hip measures the branches of a skeleton): rows and their runs, the union-find over run ids, which
 // run a bit lies in, and the ROW PASS -- one thread per row adds up what its runs give per component, a wave combines -- that
-// every per-component quantity goes through; at the end the per-slice histogram and the WINDOW WALK, the row pass for what a
-// voxel's neighbours decide, which component_measures.hip and branches.hip share.
+// every per-component quantity goes through; then the WINDOW WALK, the row pass for what a voxel's neighbours decide, with the
+// table of its neighbour rows; at the end the HISTOGRAM PASS, WORDS uint64 per slice of every selected component's box: one
+// kernel (cc_hist_kernel), one launcher (cc_hist_launch) and one set of counters (CcCounts) for the five such passes of
+// component_measures.hip and branches.hip.  A new measurement per slice writes an accumulator's add(), its row list, its word
+// count and a finishing loop over its entries; the section says what else an accumulator declares.
 //
 // tot (device uint64[8]): [0] runs  [1] components  [2] flags (1: 2^31 runs or more, 2: more runs than the caller's buffers
 // hold, 4: a run id outside the tables -- the bits changed between the calls, 8: tomo_profile_stats met a value it does not
 // admit)  [3] label tomo_cc_filter(largest) kept (0: none)  [4] counters of the slice histogram  [5] components tomo_cc_select
 // (tomo_cc_zhist_offsets) selected.
 #pragma once
+#include <utility>
 #include "tomo_common.h"
 
 #define CC_THREADS 256
@@ -400,6 +404,28 @@ __device__ static inline void cc_hist_add(const CcHist &h, u32 c, u32 z, const u
         if (SUMS == 1 || v[k]) atomicAdd(h.hist + SUMS * pos + k, v[k]);
 }
 
+// has anything been counted?  Word 0 answers where every voxel seen counts there; ANY_ALL asks every word
+template <bool ANY_ALL, int WORDS>
+__device__ static inline bool cc_counted(const u64 (&v)[WORDS])
+{
+    u64 a = v[0];
+    if constexpr (ANY_ALL) {
+#pragma unroll
+        for (int k = 1; k < WORDS; k++) a |= v[k];
+    }
+    return a != 0;
+}
+
+// what the lanes of a wave hold of one component in slice z, added up
+template <int WORDS, bool ANY_ALL = false>
+struct CcSliceSum {
+    const CcHist &h;
+    u32 z;
+    u64 v[WORDS];
+    __device__ bool any() const { return cc_counted<ANY_ALL>(v); }
+    __device__ void flush(u32 c) const { cc_hist_add<WORDS>(h, c, z, v); }
+};
+
 // ---------------------------------------------------------------------------------------------- the window walk
 struct CcWin {                                               // three neighbouring words of one row, slid along x
     u64 prv, cur, nxt;
@@ -462,4 +488,195 @@ __device__ static inline u32 cc_window_walk(const u64 *const *r, int nx, int wx,
         }
     }
     return comp;
+}
+
+// The rows a window walk reads are a constant list next to the accumulator that indexes win[i]: ROWS[i] = row (z + dz, y + dy) of
+// the volume itself (src 0) or of a second volume of the same shape (src 1), NR of them, ROWS[0] the row itself.
+struct CcRowAt {
+    int dz, dy, src;
+};
+
+// self: where row (z, y) starts in the volume named; the step from there to a neighbour row is the same for every thread
+template <int DZ, int DY>
+__device__ static inline const u64 *cc_row_or_null(const u64 *self, int64_t row, int64_t nrows, int ny, int wx, int y)
+{
+    const bool inside = (DY < 0 ? y > 0 : DY > 0 ? y + 1 < ny : true) && (DZ < 0 ? row >= ny : DZ > 0 ? row + ny < nrows : true);
+    return inside ? self + ((int64_t)DZ * ny + DY) * wx : nullptr;
+}
+
+template <class List, int... I>
+__device__ static inline void cc_rows_fill(const u64 **r, const u64 *self, const u64 *all, int64_t row, int64_t nrows, int ny, int wx,
+                                           int y, std::integer_sequence<int, I...>)
+{
+    ((r[I] = cc_row_or_null<List::ROWS[I].dz, List::ROWS[I].dy>(List::ROWS[I].src ? all : self, row, nrows, ny, wx, y)), ...);
+}
+
+template <class List>
+constexpr bool cc_two_volumes()
+{
+    for (const CcRowAt &at : List::ROWS)
+        if (at.src) return true;
+    return false;
+}
+
+// r[i] = where row List::ROWS[i] of row (z, y) starts, NULL for a row outside the stack (the list is resolved when compiled: r[]
+// and the windows stay in registers).  other: the second volume, not read where the list names none.
+template <class List>
+__device__ static inline void cc_rows(const u64 *(&r)[List::NR], const u64 *bits, const u64 *other, int64_t row, int64_t nrows, int ny,
+                                      int wx, int y)
+{
+    const u64 *all = nullptr;
+    if constexpr (cc_two_volumes<List>()) all = other + row * wx;
+    cc_rows_fill<List>(r, bits + row * wx, all, row, nrows, ny, wx, y, std::make_integer_sequence<int, List::NR>{});
+}
+
+// ---------------------------------------------------------------------------------------------- the histogram pass
+// WORDS uint64 per slice of every selected component's box, filed by one thread per row: what tomo_cc_zhist, tomo_cc_moment_hist,
+// tomo_cc_surface_hist, tomo_cc_breadth_hist and tomo_branch_hist are.  One kernel, one launcher; a measurement is its accumulator:
+//   WORDS                uint64 per entry of the histogram
+//   NR, ROWS[NR]         the rows of its window walk (above); NR == 0: it walks the runs (cc_row_walk, add(run))
+//   add(...)             what a run, or the bits of a word under a run's mask, count
+//   Extra                what its kernel takes besides CcHistArgs (CcOneVolume: nothing)
+//   UNLABELLED, WALKS_EMPTY, SQUARES     where the passes differ: the list above cc_hist_launch
+// and a finishing kernel that sums a component's slices (component_measures.hip: cc_slices and its callers).  A window walk gets
+// everything but add and ROWS from CcCounts.
+struct CcHistArgs {
+    const u64 *bits;
+    int64_t nrows;
+    int ny, nx, wx;
+    const u32 *row_off;
+    const u64 *tot;
+    int64_t cap_runs;
+    const u32 *parent, *rank;
+    const u64 *table;
+    int64_t cap;
+    const uint8_t *sel;
+    const u64 *off;
+    u64 *hist;
+    int64_t hist_cap;
+    u64 *flags;
+};
+
+struct CcOneVolume {
+    static constexpr const u64 *other = nullptr;
+};
+
+// The counters of row (z, y) for a window walk: n[WORDS], zero when a component is begun, popcounts added by the add() of the
+// struct that derives from this.  sel == NULL: no labelling, everything counts.  ANY_ALL = false: any() asks n[0], the word that
+// counts every voxel seen (surface: every run ends at a clear bit or at the edge of the stack; breadth: the voxels themselves).
+// ANY_ALL = true: any() ORs every word -- the branch pass must, a regular voxel whose two neighbours are earlier regular voxels
+// counts in none of them.
+template <int N, bool ANY_ALL>
+struct CcCounts {
+    static constexpr int WORDS = N;
+    static constexpr bool WALKS_EMPTY = false, SQUARES = false;
+    CcHist h;
+    const uint8_t *sel;
+    u32 ncomp, z;
+    u64 n[N];
+    __device__ CcCounts(const CcHistArgs &a, u64 total, u32 ncomp, u32 z, u32)
+        : h{a.table, a.off, a.hist, total, a.flags}, sel(a.sel), ncomp(ncomp), z(z), n{}
+    {
+    }
+    __device__ u32 filter(u32 c) const { return (c - 1 >= ncomp || !sel[c - 1]) ? 0u : c; }
+    __device__ bool any() const { return cc_counted<ANY_ALL>(n); }
+    __device__ u32 begin(u32 c)
+    {
+#pragma unroll
+        for (int k = 0; k < N; k++) n[k] = 0;
+        return c;
+    }
+    __device__ void word(const CcWin *) {}
+    __device__ CcSliceSum<N, ANY_ALL> combine(bool mine, u32 zz) const
+    {
+        CcSliceSum<N, ANY_ALL> w = {h, zz, {}};
+#pragma unroll
+        for (int k = 0; k < N; k++) w.v[k] = wave_sum64(mine ? n[k] : 0);
+        return w;
+    }
+    __device__ void flush(u32 c) const { cc_hist_add<N>(h, c, z, n); }
+};
+
+// One thread per row (z, y).  A histogram shorter than the selection's entries, or a table shorter than the components: CC_F_CAP
+// and nothing is touched.  Not LABELLED: no table is read, the whole volume is component 1 with one entry per slice.
+template <class Acc, bool LABELLED>
+__global__ __launch_bounds__(CC_THREADS) void cc_hist_kernel(CcHistArgs a, typename Acc::Extra x)
+{
+    const int64_t row = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    const u32 nruns = LABELLED ? (u32)cc_count(a.tot, a.cap_runs) : 0u;
+    const u64 total = LABELLED ? a.tot[4] : (u64)(a.nrows / a.ny);      // no labelling: the host checked hist_cap
+    const bool fits = total <= (u64)a.hist_cap;
+    const u32 ncomp = !fits ? 0u : LABELLED ? (u32)cc_ncomp(a.tot, a.cap) : 1u;
+    if (LABELLED && row == 0 && (!fits || a.tot[1] > (u64)a.cap)) cc_flag(a.flags, CC_F_CAP);
+    const bool live = row < a.nrows && (Acc::WALKS_EMPTY || ncomp != 0);
+    const u32 z = live ? (u32)(row / a.ny) : 0u, y = live ? (u32)(row % a.ny) : 0u;
+    Acc acc(a, total, ncomp, z, y);
+    u32 comp = 0;                                           // SELECTED component + 1 the thread is left with, 0: none
+    if (live) {
+        if constexpr (Acc::NR == 0) {
+            comp = cc_row_walk<true>(a.bits, row, a.nx, a.wx, a.row_off, nruns, a.parent, a.rank, a.flags, acc);
+        } else {
+            const u64 *r[Acc::NR];
+            cc_rows<Acc>(r, a.bits, x.other, row, a.nrows, a.ny, a.wx, (int)y);
+            comp = cc_window_walk<Acc::NR, LABELLED, LABELLED>(r, a.nx, a.wx, LABELLED ? a.row_off[row] : 0u, nruns, a.parent, a.rank,
+                                                               a.flags, acc);
+        }
+    }
+    cc_wave_tail<true>(comp, acc.z, acc);
+}
+
+// The checks every histogram entry point makes, tomo_cc_level_hist's word pass included: the geometry, then the arguments
+// (TOMO_E_ARG), then the sizes (TOMO_E_SIZE).  ok: what the entry point asks of arguments of its own; words: uint64 per entry, read
+// only once ok holds.  unlabelled: the entry point has the form without tables -- parent == NULL, one entry per slice.
+static int cc_hist_check(bool unlabelled, const void *bits, int nz, int ny, int nx, const void *row_off, int64_t cap_runs,
+                         const void *parent, const void *rank, const void *tot, const void *table, int64_t cap, const void *sel,
+                         const void *off, const void *hist, int64_t hist_cap, int64_t words, bool ok, int64_t *nrows, int *wx)
+{
+    const int g = cc_geometry(bits, nz, ny, nx, nrows, wx);
+    if (g != TOMO_OK) return g;
+    const bool labelled = parent || !unlabelled;
+    if (!ok || !hist || hist_cap <= 0) return TOMO_E_ARG;
+    if (labelled && (!row_off || !parent || !rank || !tot || !table || !sel || !off || cap_runs <= 0 || cap <= 0)) return TOMO_E_ARG;
+    if (!labelled && hist_cap < nz) return TOMO_E_ARG;
+    if (hist_cap >= ((int64_t)1 << 60) / words || (labelled && (cap_runs >= ((int64_t)1 << 31) || cap >= ((int64_t)1 << 31))))
+        return TOMO_E_SIZE;
+    return TOMO_OK;
+}
+
+// Checks, the histogram zeroed, the launch.  Where the five passes differ, and it is behaviour that stays:
+//   Acc::WALKS_EMPTY   the passes over the runs walk a row even with no component to count (a table or a histogram that is too
+//                      short), so they can raise CC_F_RANGE where the window walks, which then stop, raise only CC_F_CAP
+//   Acc::UNLABELLED    surface and breadth have a form without tables: parent == NULL, one entry per slice, hist_cap >= nz, no
+//                      flags; the passes over the runs and the branch pass refuse a null table (TOMO_E_ARG)
+//   Acc::SQUARES       the moment sums alone refuse a stack in which a slice's sum of j'^2, i'^2 or j' i' could leave 63 bits
+//   ok, x              the branch pass alone takes a second volume, and refuses a histogram that is either volume
+//   Acc::WORDS         the bound on hist_cap is 2^60 / WORDS: 2^60 itself for one word
+template <class Acc>
+static int cc_hist_launch(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
+                          const uint32_t *rank, unsigned long long *tot, const int64_t *table, int64_t cap, const uint8_t *sel,
+                          const uint64_t *off, uint64_t *hist, int64_t hist_cap, bool ok, typename Acc::Extra x, void *stream)
+{
+    int64_t nrows;
+    int wx;
+    const int r = cc_hist_check(Acc::UNLABELLED, bits, nz, ny, nx, row_off, cap_runs, parent, rank, tot, table, cap, sel, off, hist,
+                                hist_cap, Acc::WORDS, ok, &nrows, &wx);
+    if (r != TOMO_OK) return r;
+    if constexpr (Acc::SQUARES) {
+        const unsigned __int128 side = (unsigned __int128)(ny > nx ? ny : nx);
+        if ((unsigned __int128)ny * (unsigned __int128)nx * side * side >= ((unsigned __int128)1 << 63)) return TOMO_E_SIZE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(hist, 0, (size_t)hist_cap * Acc::WORDS * sizeof(u64), st) != hipSuccess) return TOMO_E_LAUNCH;
+    const dim3 grid((unsigned)ceil_div64(nrows, CC_THREADS)), block(CC_THREADS);
+    if (parent || !Acc::UNLABELLED) {
+        const CcHistArgs a = {(const u64 *)bits, nrows, ny, nx, wx, (const u32 *)row_off, (const u64 *)tot, cap_runs,
+                              (const u32 *)parent, (const u32 *)rank, (const u64 *)table, cap, sel, (const u64 *)off, (u64 *)hist,
+                              hist_cap, (u64 *)tot + 2};
+        hipLaunchKernelGGL((cc_hist_kernel<Acc, true>), grid, block, 0, st, a, x);
+    } else if constexpr (Acc::UNLABELLED) {
+        const CcHistArgs a = {(const u64 *)bits, nrows, ny, nx, wx, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 1, nullptr, nullptr,
+                              (u64 *)hist, hist_cap, nullptr};
+        hipLaunchKernelGGL((cc_hist_kernel<Acc, false>), grid, block, 0, st, a, x);
+    }
+    return tomo_status();
 }

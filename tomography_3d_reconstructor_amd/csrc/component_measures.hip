@@ -277,25 +277,24 @@ __device__ static inline u64 cc_squares_below(u64 n)
     return (n - 1) * n * (2 * n - 1) / 6;                   // n = 0: the wrapped factor meets a 0
 }
 
-template <int SUMS>
-struct CcSliceSum {
-    const CcHist &h;
-    u32 z;
-    u64 v[SUMS];
-    __device__ bool any() const { return v[0] != 0; }
-    __device__ void flush(u32 c) const { cc_hist_add<SUMS>(h, c, z, v); }
-};
-
-// The accumulator of row (z, y); only the runs of selected components count.  A run [s, e) adds its length and, SUMS > 1, in
-// closed form the sums of i' and i'^2 over it; the row supplies the factors j' when a record is made.  A voxel in front of the
-// box corner (the bits changed since tomo_cc_measure) is CC_F_RANGE and adds nothing; with one sum the corner is never read.
+// The accumulator of row (z, y) of the histogram pass (cc_runs.h), over the runs (NR == 0); only the runs of selected components
+// count.  A run [s, e) adds its length and, SUMS > 1, in closed form the sums of i' and i'^2 over it; the row supplies the factors
+// j' when a record is made.  A voxel in front of the box corner (the bits changed since tomo_cc_measure) is CC_F_RANGE and adds
+// nothing; with one sum the corner is never read.
 template <int SUMS>
 struct CcSliceAcc {
+    using Extra = CcOneVolume;
+    static constexpr int WORDS = SUMS, NR = 0;
+    static constexpr bool UNLABELLED = false, WALKS_EMPTY = true, SQUARES = SUMS > 1;
     CcHist h;
     const uint8_t *sel;
     u32 ncomp, z, y;
     u64 n, si, sii;
     u64 x0, jp;                                             // the component's box corner in x, the row's j' in its box
+    __device__ CcSliceAcc(const CcHistArgs &a, u64 total, u32 ncomp, u32 z, u32 y)
+        : h{a.table, a.off, a.hist, total, a.flags}, sel(a.sel), ncomp(ncomp), z(z), y(y), n(0), si(0), sii(0), x0(0), jp(0)
+    {
+    }
     __device__ u32 filter(u32 c) const { return (c - 1 >= ncomp || !sel[c - 1]) ? 0u : c; }
     __device__ bool any() const { return n != 0; }
     __device__ u32 begin(u32 c, const CcRuns &)
@@ -343,64 +342,20 @@ struct CcSliceAcc {
     }
 };
 
-template <int SUMS>
-__global__ __launch_bounds__(CC_THREADS) void cc_slice_hist_kernel(const u64 *__restrict__ bits, int64_t nrows, int ny, int nx, int wx,
-                                                                   const u32 *__restrict__ row_off, const u64 *__restrict__ tot,
-                                                                   int64_t cap_runs, const u32 *__restrict__ parent,
-                                                                   const u32 *__restrict__ rank, const u64 *__restrict__ table,
-                                                                   int64_t cap, const uint8_t *__restrict__ sel,
-                                                                   const u64 *__restrict__ off, u64 *__restrict__ hist,
-                                                                   int64_t hist_cap, u64 *flags)
-{
-    const int64_t row = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
-    const u32 nruns = (u32)cc_count(tot, cap_runs);
-    const u64 total = tot[4];
-    const bool fits = total <= (u64)hist_cap;
-    const u32 ncomp = fits ? (u32)cc_ncomp(tot, cap) : 0u;  // a histogram that is too short: nothing is touched
-    if (row == 0 && (!fits || tot[1] > (u64)cap)) cc_flag(flags, CC_F_CAP);
-    const bool live = row < nrows;
-    CcSliceAcc<SUMS> acc = {{table, off, hist, total, flags}, sel, ncomp, live ? (u32)(row / ny) : 0u, live ? (u32)(row % ny) : 0u,
-                            0, 0, 0, 0, 0};
-    u32 comp = 0;                                           // SELECTED component + 1 the thread is left with, 0: none
-    if (live) comp = cc_row_walk<true>(bits, row, nx, wx, row_off, nruns, parent, rank, flags, acc);
-    cc_wave_tail<true>(comp, acc.z, acc);
-}
-
-template <int SUMS>
-static int cc_slice_hist(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
-                         const uint32_t *rank, unsigned long long *tot, const int64_t *table, int64_t cap, const uint8_t *sel,
-                         const uint64_t *off, uint64_t *hist, int64_t hist_cap, void *stream)
-{
-    int64_t nrows;
-    int wx;
-    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
-    if (g != TOMO_OK) return g;
-    if (!row_off || !parent || !rank || !tot || !table || !sel || !off || !hist || cap_runs <= 0 || cap <= 0 || hist_cap <= 0)
-        return TOMO_E_ARG;
-    if (cap_runs >= ((int64_t)1 << 31) || cap >= ((int64_t)1 << 31) || hist_cap >= ((int64_t)1 << 60) / SUMS) return TOMO_E_SIZE;
-    const unsigned __int128 side = (unsigned __int128)(ny > nx ? ny : nx);
-    if (SUMS > 1 && (unsigned __int128)ny * (unsigned __int128)nx * side * side >= ((unsigned __int128)1 << 63))
-        return TOMO_E_SIZE;                                 // a slice's sum of j'^2, i'^2 or j' i' could leave 63 bits
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(hist, 0, (size_t)hist_cap * SUMS * sizeof(u64), st) != hipSuccess) return TOMO_E_LAUNCH;
-    hipLaunchKernelGGL(cc_slice_hist_kernel<SUMS>, dim3((unsigned)ceil_div64(nrows, CC_THREADS)), dim3(CC_THREADS), 0, st,
-                       (const u64 *)bits, nrows, ny, nx, wx, (const u32 *)row_off, (const u64 *)tot, cap_runs, (const u32 *)parent,
-                       (const u32 *)rank, (const u64 *)table, cap, sel, (const u64 *)off, (u64 *)hist, hist_cap, (u64 *)tot + 2);
-    return tomo_status();
-}
-
 TOMO_API int tomo_cc_zhist(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
                            const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const int64_t *table, int64_t cap,
                            const uint8_t *sel, const uint64_t *off, uint64_t *hist, int64_t hist_cap, void *stream)
 {
-    return cc_slice_hist<1>(bits, nz, ny, nx, row_off, cap_runs, parent, rank, tot, table, cap, sel, off, hist, hist_cap, stream);
+    return cc_hist_launch<CcSliceAcc<1>>(bits, nz, ny, nx, row_off, cap_runs, parent, rank, tot, table, cap, sel, off, hist, hist_cap, true,
+                                         {}, stream);
 }
 
 TOMO_API int tomo_cc_moment_hist(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
                                  const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const int64_t *table,
                                  int64_t cap, const uint8_t *sel, const uint64_t *off, uint64_t *mom, int64_t hist_cap, void *stream)
 {
-    return cc_slice_hist<CC_MOMS>(bits, nz, ny, nx, row_off, cap_runs, parent, rank, tot, table, cap, sel, off, mom, hist_cap, stream);
+    return cc_hist_launch<CcSliceAcc<CC_MOMS>>(bits, nz, ny, nx, row_off, cap_runs, parent, rank, tot, table, cap, sel, off, mom, hist_cap,
+                                               true, {}, stream);
 }
 
 // ---------------------------------------------------------------------------------------------- per selected component: its segment
@@ -428,6 +383,31 @@ __device__ static inline bool cc_segment(const u64 *__restrict__ table, const u6
         return false;
     }
     return true;
+}
+
+// ... and with table == NULL, the histogram of a call without labelling: thread 0 takes the slices 0 .. nz - 1 into row 0
+__device__ static inline bool cc_slices(const u64 *__restrict__ table, const u64 *__restrict__ tot, int64_t cap,
+                                        const uint8_t *__restrict__ sel, const u64 *__restrict__ off, const u32 *__restrict__ slot,
+                                        int64_t hist_cap, int nz, int64_t cap_sel, int64_t c, u64 *flags, CcSegment &s)
+{
+    if (table) return cc_segment(table, tot, cap, sel, off, slot, hist_cap, nz, cap_sel, c, flags, s);
+    s = {0, (u64)nz - 1, 0, 0};
+    return c == 0;
+}
+
+// The checks every finishing entry point makes of the arguments they share, the arguments first (TOMO_E_ARG), then the sizes
+// (TOMO_E_SIZE).  ok: what the entry point asks of arguments of its own; words: uint64 per entry of the histogram, read only once
+// ok holds.  unlabelled: the entry point has the form without tables -- table == NULL, hist_cap >= nz.
+static int cc_finish_check(bool unlabelled, const void *table, int64_t cap, const void *tot, const void *sel, const void *off,
+                           const void *slot, const void *hist, int64_t hist_cap, int nz, int64_t cap_sel, int64_t words, bool ok)
+{
+    const bool labelled = table || !unlabelled;
+    if (!ok || !hist || hist_cap <= 0 || nz <= 0 || cap_sel <= 0) return TOMO_E_ARG;
+    if (labelled && (!table || !tot || !sel || !off || !slot || cap <= 0)) return TOMO_E_ARG;
+    if (!labelled && hist_cap < nz) return TOMO_E_ARG;
+    if (cap_sel >= ((int64_t)1 << 31) || hist_cap >= ((int64_t)1 << 60) / words || (labelled && cap >= ((int64_t)1 << 31)))
+        return TOMO_E_SIZE;
+    return TOMO_OK;
 }
 
 // what `count` voxels of a slice of weight w, centred at zc, add to a component's volume and z moment -> the slice's volume.
@@ -463,10 +443,8 @@ TOMO_API int tomo_cc_zsums(const int64_t *table, int64_t cap, unsigned long long
                            const uint32_t *slot, const uint64_t *hist, int64_t hist_cap, const double *w, const double *zc, int nz,
                            double *out, int64_t *labels, int64_t cap_sel, void *stream)
 {
-    if (!table || !tot || !sel || !off || !slot || !hist || !w || !zc || !out || !labels || cap <= 0 || hist_cap <= 0 || nz <= 0 ||
-        cap_sel <= 0)
-        return TOMO_E_ARG;
-    if (cap >= ((int64_t)1 << 31) || cap_sel >= ((int64_t)1 << 31) || hist_cap >= ((int64_t)1 << 60)) return TOMO_E_SIZE;
+    const int r = cc_finish_check(false, table, cap, tot, sel, off, slot, hist, hist_cap, nz, cap_sel, 1, w && zc && out && labels);
+    if (r != TOMO_OK) return r;
     hipLaunchKernelGGL(cc_zsums_kernel, dim3((unsigned)ceil_div64(cap, CC_THREADS)), dim3(CC_THREADS), 0, (hipStream_t)stream,
                        (const u64 *)table, (const u64 *)tot, cap, sel, (const u64 *)off, (const u32 *)slot, (const u64 *)hist, hist_cap,
                        w, zc, nz, out, labels, cap_sel, (u64 *)tot + 2);
@@ -616,10 +594,10 @@ TOMO_API int tomo_cc_moments(const int64_t *table, int64_t cap, unsigned long lo
                              const uint32_t *slot, const uint64_t *mom, int64_t hist_cap, const double *w, const double *zc, int nz,
                              double mm_y, double mm_x, double *out, int64_t *labels, int64_t cap_sel, void *stream)
 {
-    if (!table || !tot || !sel || !off || !slot || !mom || !w || !zc || !out || !labels || cap <= 0 || hist_cap <= 0 || nz <= 0 ||
-        cap_sel <= 0 || !(mm_y > 0.0 && mm_y < __builtin_inf()) || !(mm_x > 0.0 && mm_x < __builtin_inf()))
-        return TOMO_E_ARG;                                  // a NaN fails both comparisons
-    if (cap >= ((int64_t)1 << 31) || cap_sel >= ((int64_t)1 << 31) || hist_cap >= ((int64_t)1 << 60) / CC_MOMS) return TOMO_E_SIZE;
+    // (a NaN fails every comparison)
+    const bool ok = w && zc && out && labels && mm_y > 0.0 && mm_y < __builtin_inf() && mm_x > 0.0 && mm_x < __builtin_inf();
+    const int r = cc_finish_check(false, table, cap, tot, sel, off, slot, mom, hist_cap, nz, cap_sel, CC_MOMS, ok);
+    if (r != TOMO_OK) return r;
     hipLaunchKernelGGL(cc_moments_kernel, dim3((unsigned)ceil_div64(cap, CC_THREADS)), dim3(CC_THREADS), 0, (hipStream_t)stream,
                        (const u64 *)table, (const u64 *)tot, cap, sel, (const u64 *)off, (const u32 *)slot, (const u64 *)mom, hist_cap,
                        w, zc, nz, mm_y, mm_x, out, labels, cap_sel, (u64 *)tot + 2);
@@ -697,6 +675,20 @@ __device__ static inline u64 cc_euler_under(const u64 *pos, const u64 *neg, u64 
     return (u64)(int64_t)v;
 }
 
+// the rows cc_euler_terms reads, in the order of its win[]
+template <int K>
+struct CcEulerRows;
+template <>
+struct CcEulerRows<6> {
+    static constexpr int NR = 4;
+    static constexpr CcRowAt ROWS[NR] = {{0, 0, 0}, {0, 1, 0}, {1, 0, 0}, {1, 1, 0}};
+};
+template <>
+struct CcEulerRows<26> {
+    static constexpr int NR = 5;
+    static constexpr CcRowAt ROWS[NR] = {{0, 0, 0}, {0, -1, 0}, {-1, 0, 0}, {-1, -1, 0}, {-1, 1, 0}};
+};
+
 // chi per component: the terms of a word once, their popcounts under every run's mask
 template <int K>
 struct CcEulerAcc : CcSumAcc {
@@ -715,7 +707,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_euler_kernel(const u64 *__restr
                                                               const u32 *__restrict__ rank, unsigned long long *__restrict__ euler,
                                                               int64_t cap, u64 *flags)
 {
-    constexpr int NR = K == 6 ? 4 : 5;
+    constexpr int NR = CcEulerRows<K>::NR;
     const int64_t row = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
     const u32 nruns = LABELLED ? (u32)cc_count(tot, cap_runs) : 0u;
     const u32 ncomp = LABELLED ? (u32)cc_ncomp(tot, cap) : 1u;
@@ -723,21 +715,8 @@ __global__ __launch_bounds__(CC_THREADS) void cc_euler_kernel(const u64 *__restr
     u32 comp = 0;                                           // component + 1 the thread is adding up, 0: none
     CcEulerAcc<K> acc = {{euler, ncomp, 0}, {}, {}};
     if (row < nrows) {
-        const int y = (int)(row % ny);
-        const bool up = y + 1 < ny, down = y > 0, front = row + ny < nrows, back = row >= ny;
-        const u64 *self = bits + row * wx;
         const u64 *r[NR];
-        r[0] = self;
-        if constexpr (K == 6) {
-            r[1] = up ? self + wx : nullptr;
-            r[2] = front ? self + (int64_t)ny * wx : nullptr;
-            r[3] = up && front ? self + (int64_t)(ny + 1) * wx : nullptr;
-        } else {
-            r[1] = down ? self - wx : nullptr;
-            r[2] = back ? self - (int64_t)ny * wx : nullptr;
-            r[3] = back && down ? self - (int64_t)(ny + 1) * wx : nullptr;
-            r[4] = back && up ? self - (int64_t)(ny - 1) * wx : nullptr;
-        }
+        cc_rows<CcEulerRows<K>>(r, bits, nullptr, row, nrows, ny, wx, (int)(row % ny));
         comp = cc_window_walk<NR, LABELLED, false>(r, nx, wx, LABELLED ? row_off[row] : 0u, nruns, parent, rank, flags, acc);
     }
     cc_wave_tail<false>(comp, 0u, acc);
@@ -1028,23 +1007,15 @@ __device__ static inline void cc_clear_beside(const CcWin &r, u64 mask, u64 &cen
     side += (u64)(__popcll(mask & ~cc_xp(r)) + __popcll(mask & ~cc_xm(r)));
 }
 
-// The accumulator of row (z, y) for the window walk over the row, (z, y - 1), (z, y + 1), then (z + 1, y - 1 .. y + 1), then
-// (z - 1, y - 1 .. y + 1).  sel == NULL: no labelling, everything counts.  Every run ends at a clear bit or at the edge of the
-// stack, so n[0] != 0 wherever a voxel was seen.
-struct CcSurfaceAcc {
-    CcHist h;
-    const uint8_t *sel;
-    u32 ncomp, z;
-    u64 n[CC_SURF];
-    __device__ u32 filter(u32 c) const { return (c - 1 >= ncomp || !sel[c - 1]) ? 0u : c; }
-    __device__ bool any() const { return n[0] != 0; }
-    __device__ u32 begin(u32 c)
-    {
-#pragma unroll
-        for (int k = 0; k < CC_SURF; k++) n[k] = 0;
-        return c;
-    }
-    __device__ void word(const CcWin *) {}
+// The accumulator of row (z, y) of the histogram pass (cc_runs.h), for the window walk over the row, (z, y - 1), (z, y + 1), then
+// (z + 1, y - 1 .. y + 1), then (z - 1, y - 1 .. y + 1).  Every run ends at a clear bit or at the edge of the stack, so n[0] != 0
+// wherever a voxel was seen.
+struct CcSurfaceAcc : CcCounts<CC_SURF, false> {
+    using CcCounts::CcCounts;
+    using Extra = CcOneVolume;
+    static constexpr bool UNLABELLED = true;
+    static constexpr int NR = 9;
+    static constexpr CcRowAt ROWS[NR] = {{0, 0, 0}, {0, -1, 0}, {0, 1, 0}, {1, -1, 0}, {1, 0, 0}, {1, 1, 0}, {-1, -1, 0}, {-1, 0, 0}, {-1, 1, 0}};
     __device__ void add(const CcWin *win, u64 mask)
     {
         u64 self = 0;                                       // a bit of the mask is set in the row itself
@@ -1058,78 +1029,14 @@ struct CcSurfaceAcc {
         cc_clear_beside(win[7], mask, n[7], n[8]);
         cc_clear_beside(win[8], mask, n[9], n[10]);
     }
-    __device__ CcSliceSum<CC_SURF> combine(bool mine, u32 zz) const
-    {
-        CcSliceSum<CC_SURF> w = {h, zz};
-#pragma unroll
-        for (int k = 0; k < CC_SURF; k++) w.v[k] = wave_sum64(mine ? n[k] : 0);
-        return w;
-    }
-    __device__ void flush(u32 c) const { cc_hist_add<CC_SURF>(h, c, z, n); }
 };
-
-template <bool LABELLED>
-__global__ __launch_bounds__(CC_THREADS) void cc_surface_hist_kernel(const u64 *__restrict__ bits, int64_t nrows, int ny, int nx, int wx,
-                                                                     const u32 *__restrict__ row_off, const u64 *__restrict__ tot,
-                                                                     int64_t cap_runs, const u32 *__restrict__ parent,
-                                                                     const u32 *__restrict__ rank, const u64 *__restrict__ table,
-                                                                     int64_t cap, const uint8_t *__restrict__ sel,
-                                                                     const u64 *__restrict__ off, u64 *__restrict__ surf,
-                                                                     int64_t hist_cap, u64 *flags)
-{
-    const int64_t row = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
-    const u32 nruns = LABELLED ? (u32)cc_count(tot, cap_runs) : 0u;
-    const u64 total = LABELLED ? tot[4] : (u64)(nrows / ny);    // no labelling: one entry per slice (the host checked hist_cap)
-    const bool fits = total <= (u64)hist_cap;
-    const u32 ncomp = !fits ? 0u : LABELLED ? (u32)cc_ncomp(tot, cap) : 1u;      // a histogram that is too short: nothing is touched
-    if (LABELLED && row == 0 && (!fits || tot[1] > (u64)cap)) cc_flag(flags, CC_F_CAP);
-    const bool live = row < nrows && ncomp != 0;
-    CcSurfaceAcc acc = {{table, off, surf, total, flags}, sel, ncomp, live ? (u32)(row / ny) : 0u, {}};
-    u32 comp = 0;                                           // SELECTED component + 1 the thread is left with, 0: none
-    if (live) {
-        const int y = (int)(row % ny);
-        const bool up = y + 1 < ny, down = y > 0, front = row + ny < nrows, back = row >= ny;
-        const u64 *self = bits + row * wx;
-        const u64 *r[9];
-        r[0] = self;
-        r[1] = down ? self - wx : nullptr;
-        r[2] = up ? self + wx : nullptr;
-        r[3] = front && down ? self + (int64_t)(ny - 1) * wx : nullptr;
-        r[4] = front ? self + (int64_t)ny * wx : nullptr;
-        r[5] = front && up ? self + (int64_t)(ny + 1) * wx : nullptr;
-        r[6] = back && down ? self - (int64_t)(ny + 1) * wx : nullptr;
-        r[7] = back ? self - (int64_t)ny * wx : nullptr;
-        r[8] = back && up ? self - (int64_t)(ny - 1) * wx : nullptr;
-        comp = cc_window_walk<9, LABELLED, LABELLED>(r, nx, wx, LABELLED ? row_off[row] : 0u, nruns, parent, rank, flags, acc);
-    }
-    cc_wave_tail<true>(comp, acc.z, acc);
-}
 
 TOMO_API int tomo_cc_surface_hist(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
                                   const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const int64_t *table,
                                   int64_t cap, const uint8_t *sel, const uint64_t *off, uint64_t *surf, int64_t hist_cap, void *stream)
 {
-    int64_t nrows;
-    int wx;
-    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
-    if (g != TOMO_OK) return g;
-    if (!surf || hist_cap <= 0) return TOMO_E_ARG;
-    if (parent && (!row_off || !rank || !tot || !table || !sel || !off || cap_runs <= 0 || cap <= 0)) return TOMO_E_ARG;
-    if (!parent && hist_cap < nz) return TOMO_E_ARG;
-    if (hist_cap >= ((int64_t)1 << 60) / CC_SURF || (parent && (cap_runs >= ((int64_t)1 << 31) || cap >= ((int64_t)1 << 31))))
-        return TOMO_E_SIZE;
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(surf, 0, (size_t)hist_cap * CC_SURF * sizeof(u64), st) != hipSuccess) return TOMO_E_LAUNCH;
-    const dim3 grid((unsigned)ceil_div64(nrows, CC_THREADS)), block(CC_THREADS);
-    if (parent)
-        hipLaunchKernelGGL(cc_surface_hist_kernel<true>, grid, block, 0, st, (const u64 *)bits, nrows, ny, nx, wx, (const u32 *)row_off,
-                           (const u64 *)tot, cap_runs, (const u32 *)parent, (const u32 *)rank, (const u64 *)table, cap, sel,
-                           (const u64 *)off, (u64 *)surf, hist_cap, (u64 *)tot + 2);
-    else
-        hipLaunchKernelGGL(cc_surface_hist_kernel<false>, grid, block, 0, st, (const u64 *)bits, nrows, ny, nx, wx, (const u32 *)nullptr,
-                           (const u64 *)nullptr, (int64_t)0, (const u32 *)nullptr, (const u32 *)nullptr, (const u64 *)nullptr, (int64_t)1,
-                           (const uint8_t *)nullptr, (const u64 *)nullptr, (u64 *)surf, hist_cap, (u64 *)nullptr);
-    return tomo_status();
+    return cc_hist_launch<CcSurfaceAcc>(bits, nz, ny, nx, row_off, cap_runs, parent, rank, tot, table, cap, sel, off, surf, hist_cap, true,
+                                        {}, stream);
 }
 
 // One thread per component, as cc_zsums_kernel; a selected one walks its slices in ascending z and the columns 0 .. 10 of
@@ -1143,8 +1050,8 @@ __global__ __launch_bounds__(CC_THREADS) void cc_surface_kernel(const u64 *__res
                                                                 int64_t *__restrict__ labels, int64_t cap_sel, u64 *flags)
 {
     const int64_t c = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
-    CcSegment s = {0, (u64)nz - 1, 0, 0};
-    if (table ? !cc_segment(table, tot, cap, sel, off, slot, hist_cap, nz, cap_sel, c, flags, s) : c != 0) return;
+    CcSegment s;
+    if (!cc_slices(table, tot, cap, sel, off, slot, hist_cap, nz, cap_sel, c, flags, s)) return;
     const u64 *m = surf + CC_SURF * s.o;
     double area = 0.0;
     u64 n[CC_SURF_CLASSES] = {};
@@ -1166,12 +1073,9 @@ TOMO_API int tomo_cc_surface(const int64_t *table, int64_t cap, unsigned long lo
                              const uint32_t *slot, const uint64_t *surf, int64_t hist_cap, const double *F, int nz, int directions,
                              double *out, int64_t *counts, int64_t *labels, int64_t cap_sel, void *stream)
 {
-    if (!surf || !F || !out || !counts || !labels || hist_cap <= 0 || nz <= 0 || cap_sel <= 0 || (directions != 3 && directions != 13))
-        return TOMO_E_ARG;
-    if (table && (!tot || !sel || !off || !slot || cap <= 0)) return TOMO_E_ARG;
-    if (!table && hist_cap < nz) return TOMO_E_ARG;
-    if (cap_sel >= ((int64_t)1 << 31) || hist_cap >= ((int64_t)1 << 60) / CC_SURF || (table && cap >= ((int64_t)1 << 31)))
-        return TOMO_E_SIZE;
+    const bool ok = F && out && counts && labels && (directions == 3 || directions == 13);
+    const int r = cc_finish_check(true, table, cap, tot, sel, off, slot, surf, hist_cap, nz, cap_sel, CC_SURF, ok);
+    if (r != TOMO_OK) return r;
     hipLaunchKernelGGL(cc_surface_kernel, dim3(table ? (unsigned)ceil_div64(cap, CC_THREADS) : 1u), dim3(CC_THREADS), 0,
                        (hipStream_t)stream, (const u64 *)table, (const u64 *)tot, cap, sel, (const u64 *)off, (const u32 *)slot,
                        (const u64 *)surf, hist_cap, F, nz, directions, out, (u64 *)counts, labels, cap_sel,
@@ -1190,21 +1094,14 @@ TOMO_API int tomo_cc_surface(const int64_t *table, int64_t cap, unsigned long lo
 //   6 .. 17  chi_m^cross = faces - edges of the cells with corners in slice k + 1, signed (two's complement, wrapping adds), for
 //            the families in ascending order without (1, 0, 0), which has no such cell
 // tomo_cc_breadth forms chi_m^in = voxels - edges (+ squares for (1, 0, 0)) from the six raw counts.
-struct CcBreadthAcc {
-    CcHist h;
-    const uint8_t *sel;
-    u32 ncomp, z;
-    u64 n[CC_BREADTH];
-    __device__ u32 filter(u32 c) const { return (c - 1 >= ncomp || !sel[c - 1]) ? 0u : c; }
-    __device__ bool any() const { return n[0] != 0; }
-    __device__ u32 begin(u32 c)
-    {
-#pragma unroll
-        for (int k = 0; k < CC_BREADTH; k++) n[k] = 0;
-        return c;
-    }
-    __device__ void word(const CcWin *) {}
+// The accumulator of row (z, y) of the histogram pass (cc_runs.h); n[0] counts the voxels themselves.
+struct CcBreadthAcc : CcCounts<CC_BREADTH, false> {
+    using CcCounts::CcCounts;
+    using Extra = CcOneVolume;
+    static constexpr bool UNLABELLED = true;
+    static constexpr int NR = 5;
     // win: 0 the row, 1 row (z, y + 1), 2 .. 4 rows (z + 1, y - 1), (z + 1, y), (z + 1, y + 1)
+    static constexpr CcRowAt ROWS[NR] = {{0, 0, 0}, {0, 1, 0}, {1, -1, 0}, {1, 0, 0}, {1, 1, 0}};
     __device__ void add(const CcWin *win, u64 t)
     {
         const u64 a = t & cc_xp(win[0]);                                        // p and p + x
@@ -1234,74 +1131,14 @@ struct CcBreadthAcc {
         n[16] += (u64)__popcll(a & Dc & Dp) - eDc;                              // (1, 1, 0): rectangles x, (1, -1, 0)
         n[17] += (u64)__popcll(tEm & Bm) + (u64)__popcll(tEm & Dc) - eEm - eDc; // (1, 1, 1): (0, 1, -1), (1, 0, -1), (1, -1, 0)
     }
-    __device__ CcSliceSum<CC_BREADTH> combine(bool mine, u32 zz) const
-    {
-        CcSliceSum<CC_BREADTH> w = {h, zz};
-#pragma unroll
-        for (int k = 0; k < CC_BREADTH; k++) w.v[k] = wave_sum64(mine ? n[k] : 0);
-        return w;
-    }
-    __device__ void flush(u32 c) const { cc_hist_add<CC_BREADTH>(h, c, z, n); }
 };
-
-template <bool LABELLED>
-__global__ __launch_bounds__(CC_THREADS) void cc_breadth_hist_kernel(const u64 *__restrict__ bits, int64_t nrows, int ny, int nx, int wx,
-                                                                     const u32 *__restrict__ row_off, const u64 *__restrict__ tot,
-                                                                     int64_t cap_runs, const u32 *__restrict__ parent,
-                                                                     const u32 *__restrict__ rank, const u64 *__restrict__ table,
-                                                                     int64_t cap, const uint8_t *__restrict__ sel,
-                                                                     const u64 *__restrict__ off, u64 *__restrict__ hist,
-                                                                     int64_t hist_cap, u64 *flags)
-{
-    const int64_t row = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
-    const u32 nruns = LABELLED ? (u32)cc_count(tot, cap_runs) : 0u;
-    const u64 total = LABELLED ? tot[4] : (u64)(nrows / ny);    // no labelling: one entry per slice (the host checked hist_cap)
-    const bool fits = total <= (u64)hist_cap;
-    const u32 ncomp = !fits ? 0u : LABELLED ? (u32)cc_ncomp(tot, cap) : 1u;      // a histogram that is too short: nothing is touched
-    if (LABELLED && row == 0 && (!fits || tot[1] > (u64)cap)) cc_flag(flags, CC_F_CAP);
-    const bool live = row < nrows && ncomp != 0;
-    CcBreadthAcc acc = {{table, off, hist, total, flags}, sel, ncomp, live ? (u32)(row / ny) : 0u, {}};
-    u32 comp = 0;                                           // SELECTED component + 1 the thread is left with, 0: none
-    if (live) {
-        const int y = (int)(row % ny);
-        const bool up = y + 1 < ny, down = y > 0, front = row + ny < nrows;
-        const u64 *self = bits + row * wx;
-        const u64 *r[5];
-        r[0] = self;
-        r[1] = up ? self + wx : nullptr;
-        r[2] = front && down ? self + (int64_t)(ny - 1) * wx : nullptr;
-        r[3] = front ? self + (int64_t)ny * wx : nullptr;
-        r[4] = front && up ? self + (int64_t)(ny + 1) * wx : nullptr;
-        comp = cc_window_walk<5, LABELLED, LABELLED>(r, nx, wx, LABELLED ? row_off[row] : 0u, nruns, parent, rank, flags, acc);
-    }
-    cc_wave_tail<true>(comp, acc.z, acc);
-}
 
 TOMO_API int tomo_cc_breadth_hist(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
                                   const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const int64_t *table,
                                   int64_t cap, const uint8_t *sel, const uint64_t *off, uint64_t *hist, int64_t hist_cap, void *stream)
 {
-    int64_t nrows;
-    int wx;
-    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
-    if (g != TOMO_OK) return g;
-    if (!hist || hist_cap <= 0) return TOMO_E_ARG;
-    if (parent && (!row_off || !rank || !tot || !table || !sel || !off || cap_runs <= 0 || cap <= 0)) return TOMO_E_ARG;
-    if (!parent && hist_cap < nz) return TOMO_E_ARG;
-    if (hist_cap >= ((int64_t)1 << 60) / CC_BREADTH || (parent && (cap_runs >= ((int64_t)1 << 31) || cap >= ((int64_t)1 << 31))))
-        return TOMO_E_SIZE;
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(hist, 0, (size_t)hist_cap * CC_BREADTH * sizeof(u64), st) != hipSuccess) return TOMO_E_LAUNCH;
-    const dim3 grid((unsigned)ceil_div64(nrows, CC_THREADS)), block(CC_THREADS);
-    if (parent)
-        hipLaunchKernelGGL(cc_breadth_hist_kernel<true>, grid, block, 0, st, (const u64 *)bits, nrows, ny, nx, wx, (const u32 *)row_off,
-                           (const u64 *)tot, cap_runs, (const u32 *)parent, (const u32 *)rank, (const u64 *)table, cap, sel,
-                           (const u64 *)off, (u64 *)hist, hist_cap, (u64 *)tot + 2);
-    else
-        hipLaunchKernelGGL(cc_breadth_hist_kernel<false>, grid, block, 0, st, (const u64 *)bits, nrows, ny, nx, wx, (const u32 *)nullptr,
-                           (const u64 *)nullptr, (int64_t)0, (const u32 *)nullptr, (const u32 *)nullptr, (const u64 *)nullptr, (int64_t)1,
-                           (const uint8_t *)nullptr, (const u64 *)nullptr, (u64 *)hist, hist_cap, (u64 *)nullptr);
-    return tomo_status();
+    return cc_hist_launch<CcBreadthAcc>(bits, nz, ny, nx, row_off, cap_runs, parent, rank, tot, table, cap, sel, off, hist, hist_cap, true,
+                                        {}, stream);
 }
 
 // One thread per component, as cc_surface_kernel; a selected one walks its slices in ascending z and per slice the columns
@@ -1316,8 +1153,8 @@ __global__ __launch_bounds__(CC_THREADS) void cc_breadth_kernel(const u64 *__res
                                                                 int64_t *__restrict__ labels, int64_t cap_sel, u64 *flags)
 {
     const int64_t c = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
-    CcSegment s = {0, (u64)nz - 1, 0, 0};
-    if (table ? !cc_segment(table, tot, cap, sel, off, slot, hist_cap, nz, cap_sel, c, flags, s) : c != 0) return;
+    CcSegment s;
+    if (!cc_slices(table, tot, cap, sel, off, slot, hist_cap, nz, cap_sel, c, flags, s)) return;
     double b = 0.0;
     u64 chi[CC_BREADTH_FAMILIES] = {};
     for (u64 z = s.z0; z <= s.z1; z++) {
@@ -1348,13 +1185,9 @@ TOMO_API int tomo_cc_breadth(const int64_t *table, int64_t cap, unsigned long lo
                              const uint32_t *slot, const uint64_t *hist, int64_t hist_cap, const double *B, int nz, int directions,
                              double *out, int64_t *section_euler, int64_t *labels, int64_t cap_sel, void *stream)
 {
-    if (!hist || !B || !out || !section_euler || !labels || hist_cap <= 0 || nz <= 0 || cap_sel <= 0 ||
-        (directions != 3 && directions != 13))
-        return TOMO_E_ARG;
-    if (table && (!tot || !sel || !off || !slot || cap <= 0)) return TOMO_E_ARG;
-    if (!table && hist_cap < nz) return TOMO_E_ARG;
-    if (cap_sel >= ((int64_t)1 << 31) || hist_cap >= ((int64_t)1 << 60) / CC_BREADTH || (table && cap >= ((int64_t)1 << 31)))
-        return TOMO_E_SIZE;
+    const bool ok = B && out && section_euler && labels && (directions == 3 || directions == 13);
+    const int r = cc_finish_check(true, table, cap, tot, sel, off, slot, hist, hist_cap, nz, cap_sel, CC_BREADTH, ok);
+    if (r != TOMO_OK) return r;
     hipLaunchKernelGGL(cc_breadth_kernel, dim3(table ? (unsigned)ceil_div64(cap, CC_THREADS) : 1u), dim3(CC_THREADS), 0,
                        (hipStream_t)stream, (const u64 *)table, (const u64 *)tot, cap, sel, (const u64 *)off, (const u32 *)slot,
                        (const u64 *)hist, hist_cap, B, nz, directions, out, (u64 *)section_euler, labels, cap_sel,
@@ -1550,13 +1383,10 @@ TOMO_API int tomo_cc_level_hist(const uint64_t *bits, int nz, int ny, int nx, co
 {
     int64_t nrows;
     int wx;
-    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
-    if (g != TOMO_OK) return g;
-    if (!row_off || !parent || !rank || !tot || !table || !sel || !off || !hist || !level || cap_runs <= 0 || cap <= 0 ||
-        hist_cap <= 0 || levels < 0 || (const void *)hist == (const void *)level)
-        return TOMO_E_ARG;
-    if (cap_runs >= ((int64_t)1 << 31) || cap >= ((int64_t)1 << 31) || hist_cap >= ((int64_t)1 << 60) / ((int64_t)levels + 1))
-        return TOMO_E_SIZE;
+    const bool ok = level && levels >= 0 && (const void *)hist != (const void *)level;
+    const int r = cc_hist_check(false, bits, nz, ny, nx, row_off, cap_runs, parent, rank, tot, table, cap, sel, off, hist, hist_cap,
+                                (int64_t)levels + 1, ok, &nrows, &wx);
+    if (r != TOMO_OK) return r;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(hist, 0, (size_t)hist_cap * ((size_t)levels + 1) * sizeof(u64), st) != hipSuccess) return TOMO_E_LAUNCH;
     const int64_t nwords = nrows * wx;
@@ -1601,13 +1431,11 @@ TOMO_API int tomo_cc_level_sums(const int64_t *table, int64_t cap, unsigned long
                                 const uint32_t *slot, const uint64_t *hist, int64_t hist_cap, const double *w, int nz, int levels,
                                 int64_t *voxels, double *volume, int64_t *labels, int64_t cap_sel, void *stream)
 {
-    if (!table || !tot || !sel || !off || !slot || !hist || !w || !voxels || !labels || cap <= 0 || hist_cap <= 0 || nz <= 0 ||
-        cap_sel <= 0 || levels < 0 || (levels > 0 && !volume))
-        return TOMO_E_ARG;
     const int64_t per = (int64_t)levels + 1;
-    if (cap >= ((int64_t)1 << 31) || cap_sel >= ((int64_t)1 << 31) || hist_cap >= ((int64_t)1 << 60) / per ||
-        ceil_div64(cap * per, CC_THREADS) >= ((int64_t)1 << 31))
-        return TOMO_E_SIZE;
+    const bool ok = w && voxels && labels && levels >= 0 && (levels == 0 || volume);
+    const int r = cc_finish_check(false, table, cap, tot, sel, off, slot, hist, hist_cap, nz, cap_sel, per, ok);
+    if (r != TOMO_OK) return r;
+    if (ceil_div64(cap * per, CC_THREADS) >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
     hipLaunchKernelGGL(cc_level_sums_kernel, dim3((unsigned)ceil_div64(cap * per, CC_THREADS)), dim3(CC_THREADS), 0,
                        (hipStream_t)stream, (const u64 *)table, (const u64 *)tot, cap, sel, (const u64 *)off, (const u32 *)slot,
                        (const u64 *)hist, hist_cap, w, nz, levels, (u64 *)voxels, volume, labels, cap_sel, (u64 *)tot + 2);
