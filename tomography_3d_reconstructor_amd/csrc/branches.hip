@@ -156,9 +156,7 @@ __global__ __launch_bounds__(GEO_THREADS) void branch_attach_kernel(const u64 *_
                                                                     const u32 *__restrict__ slot, unsigned long long *attach,
                                                                     unsigned long long *count, int64_t cap, int64_t cap_sel, u64 *flags)
 {
-    const bool fits = tot[5] <= (u64)cap_sel && tot[1] <= (u64)cap;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && !fits) cc_flag(flags, CC_F_CAP);
-    if (!fits) return;
+    if (!cc_sel_fits(tot, cap, cap_sel, blockIdx.x == 0 && threadIdx.x == 0, flags)) return;
     const u32 nruns = (u32)cc_count(tot, cap_runs), ncomp = (u32)cc_ncomp(tot, cap);
     const int lane = threadIdx.x & 63;
     const int64_t first = ((int64_t)blockIdx.x * (GEO_THREADS / 64) + (threadIdx.x >> 6)) * BRANCH_WAVE_WORDS;  // wave-uniform
@@ -181,7 +179,7 @@ __global__ __launch_bounds__(GEO_THREADS) void branch_attach_kernel(const u64 *_
             hi = (u64)(((int64_t)(z + b / 9 - 1) * ny + (y + (b / 3) % 3 - 1)) * nx + (x + b % 3 - 1));
         }
         const u64 *r = bits + row * wx;
-        CcWordRuns it = {w, cc_before(r, nx, wx, bx, row_off[row]), bx > 0 && (r[bx - 1] >> 63) != 0, 0, 0};
+        CcWordRuns it = cc_word_runs(r, nx, wx, bx, w, row_off[row]);
         while (cc_word_runs_next(it)) {                      // wave-uniform
             const bool has = ((it.mask >> lane) & 1) && cells != 0u;
             if (!__ballot(has)) continue;
@@ -190,12 +188,8 @@ __global__ __launch_bounds__(GEO_THREADS) void branch_attach_kernel(const u64 *_
                 continue;
             }
             const u32 c = cc_component(parent, rank, it.run);
-            if (c >= ncomp || !sel[c]) continue;
-            const u32 s = slot[c];
-            if ((int64_t)s >= cap_sel) {
-                if (lane == 0) cc_flag(flags, CC_F_RANGE);
-                continue;
-            }
+            u32 s;
+            if (c >= ncomp || !cc_sel_row(sel, slot, cap_sel, c, lane == 0, flags, s)) continue;
             const u64 least = wave_min64(has ? lo : ~0ull), most = wave_max64(has ? hi : 0ull);
             const u32 k = wave_sum(has ? (u32)__popc(cells) : 0u);
             if (lane == 0) {
@@ -297,7 +291,7 @@ __global__ __launch_bounds__(CC_THREADS) void branch_clear_kernel(const u64 *__r
     const u64 m = cc_word(r, nx, wx, wj);
     u64 res = in[i] & cc_tail_mask(nx, wx, wj);
     if (m) {
-        CcWordRuns it = {m, cc_before(r, nx, wx, wj, row_off[row]), wj > 0 && (r[wj - 1] >> 63) != 0, 0, 0};
+        CcWordRuns it = cc_word_runs(r, nx, wx, wj, m, row_off[row]);
         while (cc_word_runs_next(it)) {
             if (it.run < nruns) {
                 const u32 c = cc_component(parent, rank, it.run);

@@ -5,13 +5,18 @@
 // table of its neighbour rows; at the end the HISTOGRAM PASS, WORDS uint64 per slice of every selected component's box: one
 // kernel (cc_hist_kernel), one launcher (cc_hist_launch) and one set of counters (CcCounts) for the five such passes of
 // component_measures.hip and branches.hip.  A new measurement per slice writes an accumulator's add(), its row list, its word
-// count and a finishing loop over its entries; the section says what else an accumulator declares.
+// count and a finishing loop over its entries; the section says what else an accumulator declares.  In between, the WORD PASS --
+// one wave per word, one lane per bit, for what a per-voxel map gives per component: one kernel (cc_word_kernel), one launcher
+// (cc_word_launch), a reduction is a pass struct -- and the SELECTED ROW: cc_selected answers whether the selection fits, whether
+// a component is selected and which row of a compacted result is its own, for every kernel that writes one; the results that
+// only copy columns are writers of cc_rows_kernel.
 //
 // tot (device uint64[8]): [0] runs  [1] components  [2] flags (1: 2^31 runs or more, 2: more runs than the caller's buffers
 // hold, 4: a run id outside the tables -- the bits changed between the calls, 8: tomo_profile_stats met a value it does not
 // admit)  [3] label tomo_cc_filter(largest) kept (0: none)  [4] counters of the slice histogram  [5] components tomo_cc_select
 // (tomo_cc_zhist_offsets) selected.
 #pragma once
+#include <array>
 #include <utility>
 #include "tomo_common.h"
 
@@ -268,9 +273,84 @@ __device__ static inline bool cc_word_runs_next(CcWordRuns &it)
     return true;
 }
 
+// the runs of word wj of the row r whose first run has the id `first`; m: the word, tail bits clear
+__device__ static inline CcWordRuns cc_word_runs(const u64 *__restrict__ r, int nx, int wx, int wj, u64 m, u32 first)
+{
+    return {m, cc_before(r, nx, wx, wj, first), wj > 0 && (r[wj - 1] >> 63) != 0, 0, 0};
+}
+
+// ---------------------------------------------------------------------------------------------- the selected row
+// A selected component c writes row slot[c] of a compacted result of cap_sel rows (sel, slot, tot[5]: tomo_cc_select).  Does the
+// selection fit -- tot[5] rows in cap_sel, tot[1] components in cap, and `room` for what else the kernel needs (a histogram)?  If
+// not, nothing is written at all and the ONE thread of the grid that `speaks` raises CC_F_CAP.
+__device__ static inline bool cc_sel_fits(const u64 *__restrict__ tot, int64_t cap, int64_t cap_sel, bool speaks, u64 *flags,
+                                          bool room = true)
+{
+    const bool fits = room && tot[5] <= (u64)cap_sel && tot[1] <= (u64)cap;
+    if (speaks && !fits) cc_flag(flags, CC_F_CAP);
+    return fits;
+}
+
+// Is component c (below the count of components) selected, and which row k is its own?  A row outside the result is CC_F_RANGE
+// (speaks: every thread that finds one, or one lane for a wave that asks together).
+__device__ static inline bool cc_sel_row(const uint8_t *__restrict__ sel, const u32 *__restrict__ slot, int64_t cap_sel, int64_t c,
+                                         bool speaks, u64 *flags, u32 &k)
+{
+    if (!sel[c]) return false;
+    k = slot[c];
+    if ((int64_t)k < cap_sel) return true;
+    if (speaks) cc_flag(flags, CC_F_RANGE);
+    return false;
+}
+
+// One thread per component c: both questions, thread 0 speaks for the grid.  The per-word kernels ask cc_sel_fits once per thread
+// and cc_sel_row per run.
+__device__ static inline bool cc_selected(const u64 *__restrict__ tot, int64_t cap, const uint8_t *__restrict__ sel,
+                                          const u32 *__restrict__ slot, int64_t cap_sel, int64_t c, u64 *flags, u32 &k,
+                                          bool room = true)
+{
+    if (!cc_sel_fits(tot, cap, cap_sel, c == 0, flags, room) || c >= cc_ncomp(tot, cap)) return false;
+    return cc_sel_row(sel, slot, cap_sel, c, true, flags, k);
+}
+
+// The ROW WRITER: one thread per component, a selected one writes the Writer::COLS columns of its row -- tomo_cc_value_rows,
+// tomo_cc_topology_rows, tomo_profile_rows.  A new compacted result is a writer: COLS, the arrays it reads, and
+//   void write(u64 *o, int64_t c) const     the columns of component c (0-based) into its row o
+struct CcRowsArgs {
+    const u64 *tot;
+    int64_t cap;
+    const uint8_t *sel;
+    const u32 *slot;
+    u64 *out;
+    int64_t cap_sel;
+    u64 *flags;
+};
+
+template <class Writer>
+__global__ __launch_bounds__(CC_THREADS) void cc_rows_kernel(Writer w, CcRowsArgs a)
+{
+    const int64_t c = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    u32 k;
+    if (!cc_selected(a.tot, a.cap, a.sel, a.slot, a.cap_sel, c, a.flags, k)) return;
+    w.write(a.out + Writer::COLS * (int64_t)k, c);
+}
+
+// ok: what the entry point asks of the writer's arrays (TOMO_E_ARG); the sizes come after every argument
+template <class Writer>
+static int cc_rows_launch(const Writer &w, bool ok, int64_t cap, unsigned long long *tot, const uint8_t *sel, const uint32_t *slot,
+                          int64_t *out, int64_t cap_sel, void *stream)
+{
+    if (!ok || !tot || !sel || !slot || !out || cap <= 0 || cap_sel <= 0) return TOMO_E_ARG;
+    if (cap >= ((int64_t)1 << 31) || cap_sel >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
+    const CcRowsArgs a = {(const u64 *)tot, cap, sel, (const u32 *)slot, (u64 *)out, cap_sel, (u64 *)tot + 2};
+    hipLaunchKernelGGL(cc_rows_kernel<Writer>, dim3((unsigned)ceil_div64(cap, CC_THREADS)), dim3(CC_THREADS), 0, (hipStream_t)stream, w, a);
+    return tomo_status();
+}
+
 // ---------------------------------------------------------------------------------------------- the word pass
 // One wave per 64-bit word of a row, one lane per bit, for what a per-voxel array gives per component (component_measures.hip:
-// the value passes; profile.hip): the array is read in whole rows, the runs that touch the word are walked by all lanes together.
+// the value passes and the level histogram; profile.hip): the array is read in whole rows, the runs that touch the word are
+// walked by all lanes together.  One kernel (cc_word_kernel), one launcher (cc_word_launch); a reduction is its PASS, below.
 struct CcWordAt {
     int64_t row;                                            // z * ny + y
     int wj, bit;                                            // the word of the row, the lane's bit: x = 64 * wj + bit
@@ -278,24 +358,112 @@ struct CcWordAt {
     CcWordRuns it;                                          // its runs
 };
 
+__device__ static inline u64 cc_load64(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+struct CcWordArgs {                                         // (the counter block is an argument of its own: see cc_word_kernel)
+    const u64 *bits;
+    int64_t nwords;
+    int ny, nx, wx;
+    const u32 *row_off;
+    int64_t cap_runs;
+    const u32 *parent, *rank;
+    int64_t cap;
+    u64 *flags;
+};
+
 // -> false: the wave has no word, or a word without a set bit (wave-uniform)
-__device__ static inline bool cc_word_at(const u64 *__restrict__ bits, int64_t nwords, int nx, int wx, const u32 *__restrict__ row_off,
-                                         CcWordAt &a)
+__device__ static inline bool cc_word_at(const CcWordArgs &a, CcWordAt &w)
 {
     const int64_t t = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
     const int64_t word = t >> 6;                            // the same for the 64 lanes of a wave
-    if (word >= nwords) return false;
-    a.row = word / wx;
-    a.wj = (int)(word - a.row * wx);
-    a.bit = (int)(t & 63);
-    const u64 *r = bits + a.row * wx;
-    a.cur = cc_word(r, nx, wx, a.wj);
-    if (!a.cur) return false;
-    a.it = {a.cur, cc_before(r, nx, wx, a.wj, row_off[a.row]), a.wj > 0 && (r[a.wj - 1] >> 63) != 0, 0, 0};
+    if (word >= a.nwords) return false;
+    w.row = word / a.wx;
+    w.wj = (int)(word - w.row * a.wx);
+    w.bit = (int)(t & 63);
+    const u64 *r = a.bits + w.row * a.wx;
+    w.cur = cc_word(r, a.nx, a.wx, w.wj);
+    if (!w.cur) return false;
+    w.it = cc_word_runs(r, a.nx, a.wx, w.wj, w.cur, a.row_off[w.row]);
     return true;
 }
 
-__device__ static inline u64 cc_load64(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+struct CcClear {                                            // `bytes` bytes at `array` are set to `byte` before the launch
+    void *array;
+    int byte;
+    size_t bytes;
+};
+
+// The kernel owns the front: CC_F_CAP from thread 0 of workgroup 0 (raised even where the first wave has no word), the word and
+// its runs (a wave without a word, or with an empty one, leaves before the map is read), the counts, CC_F_RANGE for a run id
+// outside the tables, the component of a run, the components beyond the tables skipped.  A PASS says the rest:
+//   Lane                     what a lane holds while the runs are walked
+//   SELECTED, sel            only the components with sel[c] count
+//   bool fits(tot) const     room the pass needs besides the tables: false -> CC_F_CAP and nothing is touched
+//   Lane load(a, tot, w, set, at) const     before the run loop, every lane of the wave: the voxel `at` of the map, read if `set`
+//   void run(a, w, c, mine, lane, at) const   one run of the word, wave-uniform component c (0-based); mine: the lane's bit is the run's
+//   bool ok(bits) const      host: what the entry point asks of the pass's own arguments, aliasing included
+//   std::array<CcClear, N> clears(cap) const   host: the arrays cleared before the launch, and to what
+// A pass sends at most one atomic per run and array, and only what beats a plain load of the cell (cc_load, cc_load64).
+// tot is a const __restrict__ ARGUMENT, not a member of the struct: only so does the compiler take the counts for invariant
+// behind the atomicOr of cc_flag and read them with scalar loads BEHIND the word, next to the loads of the map.  As a member they
+// are vector loads (counts in VGPRs, vector compares per run); read in front of the word every wave waits for them first.  Both
+// cost the value passes 8 to 13 % where nearly every word is set (profiles/r42_word_front.md).
+template <class Pass>
+__global__ __launch_bounds__(CC_THREADS) void cc_word_kernel(CcWordArgs a, const u64 *__restrict__ tot, Pass p)
+{
+    const bool fits = p.fits(tot);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && (!fits || tot[1] > (u64)a.cap)) cc_flag(a.flags, CC_F_CAP);
+    if (!fits) return;
+    CcWordAt w;
+    if (!cc_word_at(a, w)) return;
+    const u32 nruns = (u32)cc_count(tot, a.cap_runs), ncomp = (u32)cc_ncomp(tot, a.cap);
+    const bool set = (w.cur >> w.bit) & 1;
+    const int64_t at = w.row * a.nx + 64 * w.wj + w.bit;    // a set bit lies below nx: inside the map
+    const typename Pass::Lane lane = p.load(a, tot, w, set, at);
+    while (cc_word_runs_next(w.it)) {                       // wave-uniform
+        if (w.it.run >= nruns) {
+            if (w.bit == 0) cc_flag(a.flags, CC_F_RANGE);
+            continue;
+        }
+        const u32 c = cc_component(a.parent, a.rank, w.it.run);
+        if (c >= ncomp) continue;                           // more components than the tables hold: CC_F_CAP, above
+        if constexpr (Pass::SELECTED) {
+            if (!p.sel[c]) continue;
+        }
+        p.run(a, w, c, (w.it.mask >> w.bit) & 1, lane, at);
+    }
+}
+
+// the clears, the grid of one wave per word, the launch: for an entry point that has made its checks (nwords < 2^31: cc_geometry)
+template <class Pass>
+static int cc_word_go(const uint64_t *bits, int64_t nrows, int ny, int nx, int wx, const uint32_t *row_off, int64_t cap_runs,
+                      const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, int64_t cap, const Pass &p, void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    for (const CcClear &c : p.clears(cap))
+        if (hipMemsetAsync(c.array, c.byte, c.bytes, st) != hipSuccess) return TOMO_E_LAUNCH;
+    const int64_t nwords = nrows * wx;                      // the grid has fewer than 2^29 workgroups
+    const CcWordArgs a = {(const u64 *)bits, nwords, ny, nx, wx, (const u32 *)row_off, cap_runs, (const u32 *)parent, (const u32 *)rank,
+                          cap, (u64 *)tot + 2};
+    hipLaunchKernelGGL(cc_word_kernel<Pass>, dim3((unsigned)ceil_div64(nwords * 64, CC_THREADS)), dim3(CC_THREADS), 0, st, a,
+                       (const u64 *)tot, p);
+    return tomo_status();
+}
+
+// The checks of a word pass over the run tables: the geometry, then the arguments (TOMO_E_ARG; p.ok: what the pass asks of its
+// own), then the sizes (TOMO_E_SIZE).  tomo_cc_level_hist makes cc_hist_check's instead and calls cc_word_go.
+template <class Pass>
+static int cc_word_launch(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs, const uint32_t *parent,
+                          const uint32_t *rank, unsigned long long *tot, int64_t cap, const Pass &p, void *stream)
+{
+    int64_t nrows;
+    int wx;
+    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
+    if (g != TOMO_OK) return g;
+    if (!p.ok(bits) || !row_off || !parent || !rank || !tot || cap_runs <= 0 || cap <= 0) return TOMO_E_ARG;
+    if (cap_runs >= ((int64_t)1 << 31) || cap >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
+    return cc_word_go(bits, nrows, ny, nx, wx, row_off, cap_runs, parent, rank, tot, cap, p, stream);
+}
 
 // ---------------------------------------------------------------------------------------------- the row pass
 // One thread per row adds up what the row gives per component: neighbouring runs of one component first, flushed to the

@@ -371,14 +371,11 @@ __device__ static inline bool cc_segment(const u64 *__restrict__ table, const u6
                                          int64_t hist_cap, int nz, int64_t cap_sel, int64_t c, u64 *flags, CcSegment &s)
 {
     const u64 total = tot[4];
-    const bool fits = total <= (u64)hist_cap && tot[5] <= (u64)cap_sel && tot[1] <= (u64)cap;
-    if (c == 0 && !fits) cc_flag(flags, CC_F_CAP);
-    if (!fits || c >= cc_ncomp(tot, cap) || !sel[c]) return false;
+    if (!cc_selected(tot, cap, sel, slot, cap_sel, c, flags, s.k, total <= (u64)hist_cap)) return false;
     s.z0 = table[c * CC_COLS + 1];
     s.z1 = table[c * CC_COLS + 2];
     s.o = off[c];
-    s.k = slot[c];
-    if (s.z1 < s.z0 || s.z1 >= (u64)nz || s.o + (s.z1 - s.z0) >= total || (int64_t)s.k >= cap_sel) {
+    if (s.z1 < s.z0 || s.z1 >= (u64)nz || s.o + (s.z1 - s.z0) >= total) {
         cc_flag(flags, CC_F_RANGE);
         return false;
     }
@@ -959,37 +956,23 @@ TOMO_API int tomo_cc_cavity_owners(const uint64_t *bits, int nz, int ny, int nx,
 }
 
 // out[slot[c]] = (c + 1, voxels, euler, cavities, handles) for every selected component c (sel, slot, tot[5]: tomo_cc_zhist_offsets)
-__global__ __launch_bounds__(CC_THREADS) void cc_topology_rows_kernel(const u64 *__restrict__ table, const u64 *__restrict__ topo,
-                                                                      const u64 *__restrict__ tot, int64_t cap,
-                                                                      const uint8_t *__restrict__ sel, const u32 *__restrict__ slot,
-                                                                      u64 *__restrict__ out, int64_t cap_sel, u64 *flags)
-{
-    const int64_t c = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
-    const bool fits = tot[5] <= (u64)cap_sel && tot[1] <= (u64)cap;
-    if (c == 0 && !fits) cc_flag(flags, CC_F_CAP);
-    if (!fits || c >= cc_ncomp(tot, cap) || !sel[c]) return;
-    const u32 k = slot[c];
-    if ((int64_t)k >= cap_sel) {
-        cc_flag(flags, CC_F_RANGE);
-        return;
+struct CcTopologyRow {
+    static constexpr int COLS = 5;
+    const u64 *__restrict__ table, *__restrict__ topo;
+    __device__ void write(u64 *__restrict__ o, int64_t c) const
+    {
+        o[0] = (u64)c + 1;
+        o[1] = table[c * CC_COLS];
+        o[2] = topo[3 * c];
+        o[3] = topo[3 * c + 1];
+        o[4] = topo[3 * c + 2];
     }
-    u64 *o = out + 5 * (int64_t)k;
-    o[0] = (u64)c + 1;
-    o[1] = table[c * CC_COLS];
-    o[2] = topo[3 * c];
-    o[3] = topo[3 * c + 1];
-    o[4] = topo[3 * c + 2];
-}
+};
 
 TOMO_API int tomo_cc_topology_rows(const int64_t *table, const int64_t *topo, int64_t cap, unsigned long long *tot, const uint8_t *sel,
                                    const uint32_t *slot, int64_t *out, int64_t cap_sel, void *stream)
 {
-    if (!table || !topo || !tot || !sel || !slot || !out || cap <= 0 || cap_sel <= 0) return TOMO_E_ARG;
-    if (cap >= ((int64_t)1 << 31) || cap_sel >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
-    hipLaunchKernelGGL(cc_topology_rows_kernel, dim3((unsigned)ceil_div64(cap, CC_THREADS)), dim3(CC_THREADS), 0, (hipStream_t)stream,
-                       (const u64 *)table, (const u64 *)topo, (const u64 *)tot, cap, sel, (const u32 *)slot, (u64 *)out, cap_sel,
-                       (u64 *)tot + 2);
-    return tomo_status();
+    return cc_rows_launch(CcTopologyRow{(const u64 *)table, (const u64 *)topo}, table && topo, cap, tot, sel, slot, out, cap_sel, stream);
 }
 
 // ---------------------------------------------------------------------------------------------- surface area (Crofton)
@@ -1216,165 +1199,118 @@ __device__ static inline u32 cc_value_bits(const float *__restrict__ dist, const
 // volume on one address), and only the runs that attain the maximum send an index -- and of those only the ones whose index is
 // below what first[c] already shows (a map that is constant over a body, all 0.0 or all +inf, would queue every word again).
 template <bool FIRST>
-__global__ __launch_bounds__(CC_THREADS) void cc_value_kernel(const u64 *__restrict__ bits, int64_t nwords, int nx, int wx,
-                                                              const u32 *__restrict__ row_off, const u64 *__restrict__ tot,
-                                                              int64_t cap_runs, const u32 *__restrict__ parent,
-                                                              const u32 *__restrict__ rank, const float *__restrict__ dist,
-                                                              const double *__restrict__ d2, u32 *best,
-                                                              unsigned long long *__restrict__ first, int64_t cap, u64 *flags)
-{
-    if (blockIdx.x == 0 && threadIdx.x == 0 && tot[1] > (u64)cap) cc_flag(flags, CC_F_CAP);
-    CcWordAt a;
-    if (!cc_word_at(bits, nwords, nx, wx, row_off, a)) return;
-    const u32 nruns = (u32)cc_count(tot, cap_runs), ncomp = (u32)cc_ncomp(tot, cap);
-    const bool set = (a.cur >> a.bit) & 1;
-    const int64_t at = a.row * nx + 64 * a.wj + a.bit;      // a set bit lies below nx: inside the array
-    const u32 v = set ? cc_value_bits(dist, d2, at) : 0u;
-    while (cc_word_runs_next(a.it)) {                       // wave-uniform
-        if (a.it.run >= nruns) {
-            if (a.bit == 0) cc_flag(flags, CC_F_RANGE);
-            continue;
-        }
-        const u32 c = cc_component(parent, rank, a.it.run);
-        if (c >= ncomp) continue;                           // more components than the tables hold: CC_F_CAP, above
-        const bool mine = (a.it.mask >> a.bit) & 1;
+struct CcValuePass {
+    using Lane = u32;
+    static constexpr bool SELECTED = false;
+    const float *__restrict__ dist;
+    const double *__restrict__ d2;
+    u32 *best;
+    unsigned long long *__restrict__ first;
+    __device__ bool fits(const u64 *) const { return true; }
+    __device__ u32 load(const CcWordArgs &, const u64 *, const CcWordAt &, bool set, int64_t at) const { return set ? cc_value_bits(dist, d2, at) : 0u; }
+    __device__ void run(const CcWordArgs &, const CcWordAt &w, u32 c, bool mine, u32 v, int64_t at) const
+    {
         if constexpr (!FIRST) {
             const u32 top = wave_max32(mine ? v : 0u);          // best[c] only rises: a stale read costs an atomic, never the answer
-            if (a.bit == 0 && top > cc_load(best + c)) atomicMax(best + c, top);
+            if (w.bit == 0 && top > cc_load(best + c)) atomicMax(best + c, top);
         } else {
             const u64 hit = __ballot(mine && v == best[c]);
-            if (hit && a.bit == 0) {                            // first[c] only falls: a stale read costs an atomic, never the answer
-                const u64 cand = (u64)(at + (__ffsll((long long)hit) - 1));
+            if (hit && w.bit == 0) {                            // first[c] only falls: a stale read costs an atomic, never the answer
+                const u64 cand = (u64)(at + (__ffsll((long long)hit) - 1));     // at is the flat index of the word's bit 0 here
                 if (cand < cc_load64((const u64 *)first + c)) atomicMin(first + c, (unsigned long long)cand);
             }
         }
     }
-}
-
-static int cc_value_launch(bool first_pass, const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
-                           const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const float *dist, const double *d2,
-                           uint32_t *best, uint64_t *first, int64_t cap, void *stream)
-{
-    int64_t nrows;
-    int wx;
-    const int g = cc_geometry(bits, nz, ny, nx, &nrows, &wx);
-    if (g != TOMO_OK) return g;
-    if (!row_off || !parent || !rank || !tot || !best || (first_pass && !first) || cap_runs <= 0 || cap <= 0 || (dist != nullptr) == (d2 != nullptr))
-        return TOMO_E_ARG;
-    if (cap_runs >= ((int64_t)1 << 31) || cap >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t nwords = nrows * wx;                      // < 2^31 (cc_geometry): the grid has fewer than 2^29 workgroups
-    const dim3 grid((unsigned)ceil_div64(nwords * 64, CC_THREADS)), block(CC_THREADS);
-    if (!first_pass) {
-        if (hipMemsetAsync(best, 0, (size_t)cap * sizeof(u32), st) != hipSuccess) return TOMO_E_LAUNCH;
-        hipLaunchKernelGGL(cc_value_kernel<false>, grid, block, 0, st, (const u64 *)bits, nwords, nx, wx, (const u32 *)row_off,
-                           (const u64 *)tot, cap_runs, (const u32 *)parent, (const u32 *)rank, dist, d2, (u32 *)best,
-                           (unsigned long long *)nullptr, cap, (u64 *)tot + 2);
-    } else {
-        if (hipMemsetAsync(first, 0xff, (size_t)cap * sizeof(u64), st) != hipSuccess) return TOMO_E_LAUNCH;
-        hipLaunchKernelGGL(cc_value_kernel<true>, grid, block, 0, st, (const u64 *)bits, nwords, nx, wx, (const u32 *)row_off,
-                           (const u64 *)tot, cap_runs, (const u32 *)parent, (const u32 *)rank, dist, d2, (u32 *)best,
-                           (unsigned long long *)first, cap, (u64 *)tot + 2);
+    std::array<CcClear, 1> clears(int64_t cap) const
+    {
+        return {FIRST ? CcClear{first, 0xff, (size_t)cap * sizeof(u64)} : CcClear{best, 0, (size_t)cap * sizeof(u32)}};
     }
-    return tomo_status();
-}
+    // host: the arrays are given; dist and d2 both given, or both NULL, is refused
+    bool ok(const void *) const { return best && (!FIRST || first) && (dist != nullptr) != (d2 != nullptr); }
+};
 
 TOMO_API int tomo_cc_value_max(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
                                const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const float *dist,
                                const double *d2, uint32_t *best, int64_t cap, void *stream)
 {
-    return cc_value_launch(false, bits, nz, ny, nx, row_off, cap_runs, parent, rank, tot, dist, d2, best, nullptr, cap, stream);
+    const CcValuePass<false> p = {dist, d2, (u32 *)best, nullptr};
+    return cc_word_launch(bits, nz, ny, nx, row_off, cap_runs, parent, rank, tot, cap, p, stream);
 }
 
 TOMO_API int tomo_cc_value_first(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
                                  const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const float *dist,
                                  const double *d2, const uint32_t *best, uint64_t *first, int64_t cap, void *stream)
 {
-    if ((const void *)best == (const void *)first) return TOMO_E_ARG;
-    return cc_value_launch(true, bits, nz, ny, nx, row_off, cap_runs, parent, rank, tot, dist, d2, (uint32_t *)best, first, cap, stream);
+    if ((const void *)best == (const void *)first) return TOMO_E_ARG;       // before the geometry is judged
+    const CcValuePass<true> p = {dist, d2, (u32 *)best, (unsigned long long *)first};
+    return cc_word_launch(bits, nz, ny, nx, row_off, cap_runs, parent, rank, tot, cap, p, stream);
 }
 
 // out[slot[c]] = (c + 1, voxels, best[c], first[c]) for every selected component c (sel, slot, tot[5]: tomo_cc_select)
-__global__ __launch_bounds__(CC_THREADS) void cc_value_rows_kernel(const u64 *__restrict__ table, const u32 *__restrict__ best,
-                                                                   const u64 *__restrict__ first, const u64 *__restrict__ tot,
-                                                                   int64_t cap, const uint8_t *__restrict__ sel,
-                                                                   const u32 *__restrict__ slot, u64 *__restrict__ out, int64_t cap_sel,
-                                                                   u64 *flags)
-{
-    const int64_t c = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
-    const bool fits = tot[5] <= (u64)cap_sel && tot[1] <= (u64)cap;
-    if (c == 0 && !fits) cc_flag(flags, CC_F_CAP);
-    if (!fits || c >= cc_ncomp(tot, cap) || !sel[c]) return;
-    const u32 k = slot[c];
-    if ((int64_t)k >= cap_sel) {
-        cc_flag(flags, CC_F_RANGE);
-        return;
+struct CcValueRow {
+    static constexpr int COLS = 4;
+    const u64 *__restrict__ table;
+    const u32 *__restrict__ best;
+    const u64 *__restrict__ first;
+    __device__ void write(u64 *__restrict__ o, int64_t c) const
+    {
+        o[0] = (u64)c + 1;
+        o[1] = table[c * CC_COLS];
+        o[2] = best[c];
+        o[3] = first[c];
     }
-    u64 *o = out + 4 * (int64_t)k;
-    o[0] = (u64)c + 1;
-    o[1] = table[c * CC_COLS];
-    o[2] = best[c];
-    o[3] = first[c];
-}
+};
 
 TOMO_API int tomo_cc_value_rows(const int64_t *table, const uint32_t *best, const uint64_t *first, int64_t cap, unsigned long long *tot,
                                 const uint8_t *sel, const uint32_t *slot, int64_t *out, int64_t cap_sel, void *stream)
 {
-    if (!table || !best || !first || !tot || !sel || !slot || !out || cap <= 0 || cap_sel <= 0) return TOMO_E_ARG;
-    if (cap >= ((int64_t)1 << 31) || cap_sel >= ((int64_t)1 << 31)) return TOMO_E_SIZE;
-    hipLaunchKernelGGL(cc_value_rows_kernel, dim3((unsigned)ceil_div64(cap, CC_THREADS)), dim3(CC_THREADS), 0, (hipStream_t)stream,
-                       (const u64 *)table, (const u32 *)best, (const u64 *)first, (const u64 *)tot, cap, sel, (const u32 *)slot,
-                       (u64 *)out, cap_sel, (u64 *)tot + 2);
-    return tomo_status();
+    return cc_rows_launch(CcValueRow{(const u64 *)table, (const u32 *)best, (const u64 *)first}, table && best && first, cap, tot, sel,
+                          slot, out, cap_sel, stream);
 }
 
 // hist[(K + 1) * (off[c] + z - zmin[c]) + level] += 1 for every set voxel of a selected component; level: the int32 level map of
 // the local thickness, outside 0 .. K it counts as 0.  The word pass; inside a run the lanes are aggregated by level: the first
 // lane still to count names its level, the lanes that share it are balloted, the leader adds their number, they retire -- a
 // solid body costs one or two atomics per word, not 64.
-__global__ __launch_bounds__(CC_THREADS) void cc_level_hist_kernel(const u64 *__restrict__ bits, int64_t nwords, int ny, int nx, int wx,
-                                                                   const u32 *__restrict__ row_off, const u64 *__restrict__ tot,
-                                                                   int64_t cap_runs, const u32 *__restrict__ parent,
-                                                                   const u32 *__restrict__ rank, const u64 *__restrict__ table,
-                                                                   int64_t cap, const uint8_t *__restrict__ sel,
-                                                                   const u64 *__restrict__ off, unsigned long long *__restrict__ hist,
-                                                                   int64_t hist_cap, const int32_t *__restrict__ level, int K, u64 *flags)
-{
-    const u64 total = tot[4];
-    const bool fits = total <= (u64)hist_cap;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && (!fits || tot[1] > (u64)cap)) cc_flag(flags, CC_F_CAP);
-    if (!fits) return;                                      // a histogram that is too short: nothing is touched
-    CcWordAt a;
-    if (!cc_word_at(bits, nwords, nx, wx, row_off, a)) return;
-    const u32 nruns = (u32)cc_count(tot, cap_runs), ncomp = (u32)cc_ncomp(tot, cap);
-    const bool set = (a.cur >> a.bit) & 1;
-    int l = set ? level[a.row * nx + 64 * a.wj + a.bit] : 0;
-    if ((unsigned)l > (unsigned)K) l = 0;                   // nothing writes such a level; never index past the entry
-    const u64 z = (u64)(a.row / ny);
-    while (cc_word_runs_next(a.it)) {                       // wave-uniform
-        if (a.it.run >= nruns) {
-            if (a.bit == 0) cc_flag(flags, CC_F_RANGE);
-            continue;
-        }
-        const u32 c = cc_component(parent, rank, a.it.run);
-        if (c >= ncomp || !sel[c]) continue;
+struct CcLevelPass {
+    struct Lane {
+        int l;                                              // the level of the lane's voxel
+        u64 z, total;                                       // wave-uniform, computed once per word: its slice, the histogram's entries
+    };
+    static constexpr bool SELECTED = true;
+    const u64 *__restrict__ table;
+    const uint8_t *__restrict__ sel;
+    const u64 *__restrict__ off;
+    unsigned long long *__restrict__ hist;
+    int64_t hist_cap;
+    const int32_t *__restrict__ level;
+    int K;
+    __device__ bool fits(const u64 *tot) const { return tot[4] <= (u64)hist_cap; }      // a histogram that is too short: nothing is touched
+    __device__ Lane load(const CcWordArgs &a, const u64 *tot, const CcWordAt &w, bool set, int64_t at) const
+    {
+        const int l = set ? level[at] : 0;
+        return {(unsigned)l > (unsigned)K ? 0 : l, (u64)(w.row / a.ny), tot[4]};      // nothing writes such a level; never index past the entry
+    }
+    __device__ void run(const CcWordArgs &a, const CcWordAt &w, u32 c, bool, const Lane &v, int64_t) const
+    {
         const u64 z0 = table[(int64_t)c * CC_COLS + 1], z1 = table[(int64_t)c * CC_COLS + 2];
-        const u64 pos = off[c] + (z - z0);
-        if (z < z0 || z > z1 || pos >= total) {             // a slice outside the component's box: the bits changed
-            if (a.bit == 0) cc_flag(flags, CC_F_RANGE);
-            continue;
+        const u64 pos = off[c] + (v.z - z0);
+        if (v.z < z0 || v.z > z1 || pos >= v.total) {       // a slice outside the component's box: the bits changed
+            if (w.bit == 0) cc_flag(a.flags, CC_F_RANGE);
+            return;
         }
         unsigned long long *entry = hist + (u64)(K + 1) * pos;
-        u64 left = a.it.mask;                               // the lanes still to count, wave-uniform
+        u64 left = w.it.mask;                               // the lanes still to count, wave-uniform
         while (left) {                                      // every turn retires at least the leader: at most 64 turns
             const int leader = __ffsll((long long)left) - 1;
-            const int ll = __shfl(l, leader, 64);
-            const u64 same = __ballot(l == ll) & left;
-            if (a.bit == leader) atomicAdd(entry + ll, (unsigned long long)__popcll(same));
+            const int ll = __shfl(v.l, leader, 64);
+            const u64 same = __ballot(v.l == ll) & left;
+            if (w.bit == leader) atomicAdd(entry + ll, (unsigned long long)__popcll(same));
             left &= ~same;
         }
     }
-}
+    std::array<CcClear, 1> clears(int64_t) const { return {CcClear{hist, 0, (size_t)hist_cap * ((size_t)K + 1) * sizeof(u64)}}; }
+};
 
 TOMO_API int tomo_cc_level_hist(const uint64_t *bits, int nz, int ny, int nx, const uint32_t *row_off, int64_t cap_runs,
                                 const uint32_t *parent, const uint32_t *rank, unsigned long long *tot, const int64_t *table, int64_t cap,
@@ -1387,14 +1323,8 @@ TOMO_API int tomo_cc_level_hist(const uint64_t *bits, int nz, int ny, int nx, co
     const int r = cc_hist_check(false, bits, nz, ny, nx, row_off, cap_runs, parent, rank, tot, table, cap, sel, off, hist, hist_cap,
                                 (int64_t)levels + 1, ok, &nrows, &wx);
     if (r != TOMO_OK) return r;
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(hist, 0, (size_t)hist_cap * ((size_t)levels + 1) * sizeof(u64), st) != hipSuccess) return TOMO_E_LAUNCH;
-    const int64_t nwords = nrows * wx;
-    hipLaunchKernelGGL(cc_level_hist_kernel, dim3((unsigned)ceil_div64(nwords * 64, CC_THREADS)), dim3(CC_THREADS), 0, st,
-                       (const u64 *)bits, nwords, ny, nx, wx, (const u32 *)row_off, (const u64 *)tot, cap_runs, (const u32 *)parent,
-                       (const u32 *)rank, (const u64 *)table, cap, sel, (const u64 *)off, (unsigned long long *)hist, hist_cap, level,
-                       levels, (u64 *)tot + 2);
-    return tomo_status();
+    const CcLevelPass p = {(const u64 *)table, sel, (const u64 *)off, (unsigned long long *)hist, hist_cap, level, levels};
+    return cc_word_go(bits, nrows, ny, nx, wx, row_off, cap_runs, parent, rank, tot, cap, p, stream);
 }
 
 // One thread per (component, level); a selected component walks its slices in ascending z: voxels[slot[c]][level] = the sum of the
@@ -1579,8 +1509,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_caliper_kernel(const u64 *__res
 {
     const int64_t row = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
     const u32 nruns = (u32)cc_count(tot, cap_runs);
-    const bool fits = tot[5] <= (u64)cap_sel && tot[1] <= (u64)cap;
-    if (row == 0 && blockIdx.y == 0 && !fits) cc_flag(flags, CC_F_CAP);
+    const bool fits = cc_sel_fits(tot, cap, cap_sel, row == 0 && blockIdx.y == 0, flags);
     const bool live = row < nrows;
     const int m0 = (int)blockIdx.y * CC_CAL_BATCH, nb = M - m0 < CC_CAL_BATCH ? M - m0 : CC_CAL_BATCH;      // nb >= 1: the grid
     const int64_t z = live ? row / ny : 0, y = live ? row % ny : 0;
@@ -1692,8 +1621,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_caliper_axes_kernel(const u64 *
 {
     const int64_t row = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
     const u32 nruns = (u32)cc_count(tot, cap_runs);
-    const bool fits = tot[5] <= (u64)cap_sel && tot[1] <= (u64)cap;
-    if (row == 0 && !fits) cc_flag(flags, CC_F_CAP);
+    const bool fits = cc_sel_fits(tot, cap, cap_sel, row == 0, flags);
     const bool live = row < nrows;
     const int64_t z = live ? row / ny : 0, y = live ? row % ny : 0;
     CcCaliperAxesAcc acc;
@@ -1744,14 +1672,8 @@ __global__ __launch_bounds__(CC_THREADS) void cc_caliper_rows_kernel(const u64 *
                                                                      double *__restrict__ ext, int64_t cap_sel, u64 *flags)
 {
     const int64_t c = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
-    const bool fits = tot[5] <= (u64)cap_sel && tot[1] <= (u64)cap;
-    if (c == 0 && !fits) cc_flag(flags, CC_F_CAP);
-    if (!fits || c >= cc_ncomp(tot, cap) || !sel[c]) return;
-    const u32 k = slot[c];
-    if ((int64_t)k >= cap_sel) {
-        cc_flag(flags, CC_F_RANGE);
-        return;
-    }
+    u32 k;
+    if (!cc_selected(tot, cap, sel, slot, cap_sel, c, flags, k)) return;
     u64 *h = hi + (int64_t)k * M, *l = lo + (int64_t)k * M;
     double *w = width + (int64_t)k * M;
     double wmax = 0.0, wmin = 0.0;

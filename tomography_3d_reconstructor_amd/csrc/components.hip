@@ -319,7 +319,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_filter_kernel(const u64 *__rest
     const u64 m = cc_word(r, nx, wx, wj);
     u64 res = SOLID ? solid[i] & cc_tail_mask(nx, wx, wj) : 0;
     if (m) {
-        CcWordRuns it = {m, cc_before(r, nx, wx, wj, row_off[row]), wj > 0 && (r[wj - 1] >> 63)};
+        CcWordRuns it = cc_word_runs(r, nx, wx, wj, m, row_off[row]);
         while (cc_word_runs_next(it)) {
             if (it.run < nruns) {
                 const u32 c = cc_component(parent, rank, it.run);

@@ -209,9 +209,7 @@ __global__ __launch_bounds__(CC_THREADS) void thin_count_kernel(const u64 *__res
                                                                 int64_t cap_sel, u64 *flags)
 {
     const int64_t word = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
-    const bool fits = tot[5] <= (u64)cap_sel && tot[1] <= (u64)cap;
-    if (word == 0 && !fits) cc_flag(flags, CC_F_CAP);
-    if (!fits || word >= nwords) return;
+    if (!cc_sel_fits(tot, cap, cap_sel, word == 0, flags) || word >= nwords) return;
     const int64_t row = word / wx;
     const int wj = (int)(word - row * wx);
     const u64 *r = bits + row * wx;
@@ -219,7 +217,7 @@ __global__ __launch_bounds__(CC_THREADS) void thin_count_kernel(const u64 *__res
     const u64 o = other[word] & cur;
     if (!o) return;
     const u32 nruns = (u32)cc_count(tot, cap_runs), ncomp = (u32)cc_ncomp(tot, cap);
-    CcWordRuns it = {cur, cc_before(r, nx, wx, wj, row_off[row]), wj > 0 && (r[wj - 1] >> 63) != 0, 0, 0};
+    CcWordRuns it = cc_word_runs(r, nx, wx, wj, cur, row_off[row]);
     while (cc_word_runs_next(it)) {
         const int k = __popcll(o & it.mask);
         if (!k) continue;
@@ -228,12 +226,8 @@ __global__ __launch_bounds__(CC_THREADS) void thin_count_kernel(const u64 *__res
             continue;
         }
         const u32 c = cc_component(parent, rank, it.run);
-        if (c >= ncomp || !sel[c]) continue;
-        const u32 s = slot[c];
-        if ((int64_t)s >= cap_sel) {
-            cc_flag(flags, CC_F_RANGE);
-            continue;
-        }
+        u32 s;
+        if (c >= ncomp || !cc_sel_row(sel, slot, cap_sel, c, true, flags, s)) continue;
         atomicAdd(out + (int64_t)columns * s + column, (unsigned long long)k);
     }
 }
