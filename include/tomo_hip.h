@@ -752,6 +752,34 @@ int tomo_profile_where(const uint64_t *bits, int nz, int ny, int nx, const uint3
 int tomo_profile_rows(const int64_t *table, const uint32_t *lo, const uint32_t *hi, const int64_t *sum, const uint64_t *lo_first,
                       const uint64_t *hi_first, int64_t cap, unsigned long long *tot, const uint8_t *sel, const uint32_t *slot,
                       int64_t *out, int64_t cap_sel, void *stream);
+/* Chord lengths of the volume as a whole (csrc/chords.hip; no counterpart in the reference): the chord-length distribution per
+ * lattice direction, from which the host derives the lineal-path function, the mean intercept length (MIL) and the MIL fabric
+ * tensor.  No labelling: a network, a foam or a packed bed may be one component.  One definition.
+ * DIRECTIONS: the 13 forward steps s = (dz, dy, dx) in {-1, 0, 1}^3 with the first non-zero entry positive, in ascending tuple
+ * order -- the table of tomo_cc_breadth_hist's families, read as steps:
+ *     (0,0,1) (0,1,-1) (0,1,0) (0,1,1) (1,-1,-1) (1,-1,0) (1,-1,1) (1,0,-1) (1,0,0) (1,0,1) (1,1,-1) (1,1,0) (1,1,1)
+ * CHORD: everything outside the stack is background (the distance transform's convention).  A chord of direction s is a maximal
+ * sequence of set voxels p, p + s, .., p + (n - 1) s: its predecessor p - s and its successor p + n s are each either clear or
+ * outside the stack; n >= 1 is its length in voxels.  Every set voxel lies in exactly one chord per direction.  A chord is a
+ * BORDER chord when its predecessor or its successor is outside the stack.
+ * STEP LENGTH: l_s(k) = sqrt(((dz d[k])^2 + (dy mm_y)^2) + (dx mm_x)^2) in float64, d[k] the depth of slice k: the path through
+ * the voxel's own box (the convention of the caliper's extent = "voxels").  FIXED POINT: q_s(k) = rint(l_s(k) * 65536) as int64,
+ * half to even, made on the host (tomo_profile_stats' rule): steps_q int64[nz][13].
+ * TABLES: int64[13][lmax + 1], lmax >= max(nz, ny, nx), zeroed here; column 0 stays 0.  counts[m][n] = the chords of direction
+ * m and length n; border[m][n] = those of them that are border chords; sum_q[m][n] = the sum of q_s(k) over the voxels (k their
+ * slice) of the chords in that bin: with varying depths the length in mm of a chord with dz != 0 is no function of n, and
+ * sum_q / counts / 65536 is the mean length in mm of the bin from integers alone.  For every m the sum over n of n * counts[m][n]
+ * is the popcount of the volume.
+ *   tomo_chord_hist  the directions led by z: one thread per position (j0, i0) of the slice plane, at step k at voxel
+ *                    (k, (j0 + k dy) mod ny, (i0 + k dx) mod nx); where the index wraps the open chord ends as a border chord
+ *                    and the next one starts as one.  Led by y: the same per slice, one thread per i0.  (0, 0, 1): the runs of the
+ *                    rows.  Chords of fewer than 256 voxels are binned in LDS per workgroup and the non-zero bins added once;
+ *                    a longer one goes to slot n mod 256 of a direct-mapped set of bins in LDS that the first length to come
+ *                    claims, and straight to the tables only where another length holds its slot.  Integer atomics only: the
+ *                    same bytes on every run.
+ * TOMO_E_ARG for a null pointer, a non-positive size or lmax < max(nz, ny, nx); TOMO_E_SIZE from 2^31 words on. */
+int tomo_chord_hist(const uint64_t *bits, int nz, int ny, int nx, const int64_t *steps_q, int64_t lmax, int64_t *counts,
+                    int64_t *border, int64_t *sum_q, void *stream);
 /* The contact table between zones (csrc/contacts.hip; no counterpart in the reference): which zones touch, over how large an
  * interface, how wide the throat between them is and how long the way across.  One definition.
  * zones: int32 (nz, ny, nx), tomo_zone_sweep's map or any map.  A voxel TAKES PART when it is set and its entry is positive.

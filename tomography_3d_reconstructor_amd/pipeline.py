@@ -31,7 +31,8 @@ COUNTERS = dict.fromkeys(("na_hint_hit", "na_hint_miss", "mc3_hint_hit", "mc3_hi
                           "separate_components", "zone_contacts", "contact_launches", "recon_calls", "recon_sweeps",
                           "thin_calls", "thin_iterations", "thin_passes", "thin_nodes", "component_skeleton",
                           "skeleton_branches", "branch_split", "skeleton_branches_hist", "branch_attach", "branch_lookup", "branch_clear",
-                          "prune_rounds", "components_profile", "branch_profile", "prune_relative", "components_breadth"), 0)
+                          "prune_rounds", "components_profile", "branch_profile", "prune_relative", "components_breadth",
+                          "chord_lengths"), 0)
 NA_HINTS = os.environ.get("TOMO_NA_HINTS", "1") not in ("", "0")   # marching_cubes: launch ahead of the first count download
 _NA_HINT = {}
 LIST_LIMIT = 2 ** 31        # active-voxel list entries / vertices / triangles one pass can index (int32 offsets in mc.hip, mesh.hip);
@@ -1491,6 +1492,187 @@ def cavity_breadth(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per
     lo, hi = _check_size_window(min_voxels, max_voxels)
     B = breadth_factors(slice_depths, vol.shape[0], mm_per_pixel_y, mm_per_pixel_x, directions)
     return _complement_runs(vol, connectivity).breadth(B, directions, lo, max_voxels=hi, enclosed=True)
+
+
+# ----------------------------------------------------------------------------- chord lengths along the 13 lattice directions
+CHORD_DIRECTIONS = 13
+CHORD_FRACTION_BITS = 16     # the steps are summed in units of 2^-16 mm (tomo_profile_stats' fixed point)
+CHORD_LDS_BINS = 256         # csrc/chords.hip: chords of fewer voxels have a bin of their own in LDS, longer ones share 256 slots
+CHORD_PHASES = ("object", "background")
+
+
+def chord_directions() -> np.ndarray:
+    """The 13 forward steps (dz, dy, dx) of chord_lengths, first non-zero entry positive, in ascending tuple order -> int64
+    (13, 3): the table of breadth_normals(), read as steps.  The rows of every table of ChordLengths."""
+    return np.array(_BREADTH_NORMALS, dtype=np.int64)
+
+
+def chord_steps(slice_depths, nz, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0) -> np.ndarray:
+    """The length in mm of one step of direction m through a voxel of slice k -> float64 (nz, 13):
+    sqrt(((dz * depth[k])^2 + (dy * mm_y)^2) + (dx * mm_x)^2), the path through the voxel's own box (the convention of
+    component_caliper(extent="voxels")).  slice_depths=None: 1.0 per slice."""
+    zt, _, _ = distance_positions(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x)        # the argument checks
+    nz = len(zt) - 2
+    mm_y, mm_x = float(mm_per_pixel_y), float(mm_per_pixel_x)
+    d = np.ones(nz) if slice_depths is None else np.asarray(slice_depths, dtype=np.float64).reshape(-1)
+    s = chord_directions().astype(np.float64)
+    return np.sqrt(((s[None, :, 0] * d[:, None]) ** 2 + (s[None, :, 1] * mm_y) ** 2) + (s[None, :, 2] * mm_x) ** 2)
+
+
+def chord_steps_q(steps) -> np.ndarray:
+    """chord_steps in the fixed point of the kernel -> int64, rint(steps * 65536), half to even."""
+    return np.rint(np.asarray(steps, dtype=np.float64) * float(1 << CHORD_FRACTION_BITS)).astype(np.int64)
+
+
+@dataclass
+class ChordLengths:
+    """chord_lengths' answer: host arrays, one row per direction of chord_directions(); L = max(nz, ny, nx)."""
+    directions: np.ndarray       # int64 (13, 3): the steps (dz, dy, dx)
+    counts: np.ndarray           # int64 (13, L + 1): chords of length n voxels; column 0 is 0
+    border: np.ndarray           # int64 (13, L + 1): those of them whose predecessor or successor lies outside the stack
+    sum_q: np.ndarray            # int64 (13, L + 1): the steps of their voxels in units of 2^-16 mm
+    steps: np.ndarray            # float64 (nz, 13): chord_steps
+    voxels: int                  # voxels of the phase: sum over n of n * counts[m][n] for every m
+    chords: np.ndarray           # int64 (13,): chords per direction
+    total_length_mm: np.ndarray  # float64 (13,): sum over k ascending of slice_counts[k] * steps[k][m]
+    mean_chord_mm: np.ndarray    # float64 (13,): total_length_mm / chords, the mean intercept length; NaN without a chord
+    shape: tuple                 # (nz, ny, nx)
+    spacing: tuple               # (mean slice depth, mm_y, mm_x)
+
+    def _counts(self, interior):
+        return self.counts - self.border if interior else self.counts
+
+    def mean_length_mm(self) -> np.ndarray:
+        """The mean length in mm of the chords of every bin -> float64 (13, L + 1): sum_q / counts / 65536, NaN in an empty bin.
+        At constant depth it is n times the step; with varying depths a bin of a direction with dz != 0 holds several lengths."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return self.sum_q.astype(np.float64) / self.counts.astype(np.float64) / float(1 << CHORD_FRACTION_BITS)
+
+    def quantiles_mm(self, fractions=(0.1, 0.5, 0.9)) -> np.ndarray:
+        """Quantiles of the chord length by number of chords -> float64 (13, len(fractions)): mean_length_mm() of the first bin n
+        at which the chords of at most n voxels are at least the fraction of all chords of the direction; NaN without a chord."""
+        cum = np.cumsum(self.counts, axis=1)
+        mean = self.mean_length_mm()
+        out = np.full((CHORD_DIRECTIONS, len(fractions)), np.nan)
+        for m in range(CHORD_DIRECTIONS):
+            if self.chords[m] > 0:
+                for c, f in enumerate(fractions):
+                    n = int(np.searchsorted(cum[m], max(1, math.ceil(float(f) * int(self.chords[m]))), side="left"))
+                    out[m, c] = mean[m, n]
+        return out
+
+    def segments(self) -> np.ndarray:
+        """P_m(r), the segments of r voxels of direction m that lie inside the stack -> int64 (13, L + 1) (column 0 is 0):
+        max(0, nz - (r - 1) |dz|) * max(0, ny - (r - 1) |dy|) * max(0, nx - (r - 1) |dx|)."""
+        r = np.arange(self.counts.shape[1], dtype=np.int64)
+        a = np.abs(self.directions)
+        P = np.ones((CHORD_DIRECTIONS, len(r)), dtype=np.int64)
+        for axis, size in enumerate(self.shape):
+            P *= np.maximum(0, size - (r[None, :] - 1) * a[:, axis:axis + 1])
+        P[:, 0] = 0
+        return P
+
+    def lineal_path(self, interior=False) -> np.ndarray:
+        """The lineal-path function -> float64 (13, L + 1): L_m(r) = sum over n >= r of (n - r + 1) * counts[m][n] / P_m(r), the
+        share of the r-voxel segments of direction m inside the stack (segments()) that lie wholly in the phase; 0 where P is
+        0 and in column 0.  L_m(1) is the volume fraction.  interior=True counts the segments of the chords that are not cut
+        by the stack only (counts - border) and leaves the denominators unchanged: a lower bound that does not depend on
+        what lies beyond the faces."""
+        c = self._counts(interior)
+        tail = np.cumsum(c[:, ::-1], axis=1)[:, ::-1]                        # chords of at least r voxels
+        num = np.cumsum(tail[:, ::-1], axis=1)[:, ::-1]                      # sum over n >= r of (n - r + 1) * c[n]
+        P = self.segments()
+        out = np.zeros(c.shape, dtype=np.float64)
+        np.divide(num.astype(np.float64), P.astype(np.float64), out=out, where=P > 0)
+        out[:, 0] = 0.0
+        return out
+
+    def mil_mm(self, interior=False) -> np.ndarray:
+        """The mean intercept length per direction in mm -> float64 (13,), NaN without a chord.  interior=False: mean_chord_mm.
+        interior=True: the mean length in voxels of the chords that are not cut by the stack (counts - border) times the step
+        at the mean slice depth."""
+        if not interior:
+            return self.mean_chord_mm.copy()
+        c = self._counts(True)
+        n = np.arange(c.shape[1], dtype=np.int64)
+        step = np.sqrt(((self.directions * np.array(self.spacing)) ** 2).sum(axis=1))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return (c * n).sum(axis=1).astype(np.float64) / c.sum(axis=1).astype(np.float64) * step
+
+    def fabric(self, interior=False) -> dict:
+        """The MIL fabric tensor -> dict: the symmetric M (3, 3) in (z, y, x) that meets u^T M u = 1 / MIL(u)^2 in the least
+        squares over the unit vectors u = s * (mean slice depth, mm_y, mm_x) / |.| of the directions that have a chord (the
+        ellipsoid fit of Harrigan & Mann, BoneJ's Anisotropy on a fixed set of directions).  principal_mil_mm = 1 /
+        sqrt(eigenvalues) in descending order; axes: the eigenvectors as rows in that order, the largest component positive;
+        degree_of_anisotropy = 1 - lambda_min / lambda_max.  interior=True fits mil_mm(interior=True): the chords cut by the
+        stack are left out, the step lengths are unchanged.  Fewer than six directions with a chord, or a fit that is not
+        positive definite: ValueError."""
+        mil = self.mil_mm(interior)
+        has = np.isfinite(mil) & (mil > 0)
+        if int(has.sum()) < 6:
+            raise ValueError("the fabric tensor needs chords in at least six directions (%d have one)" % int(has.sum()))
+        u = self.directions[has] * np.array(self.spacing)
+        u = u / np.sqrt((u ** 2).sum(axis=1))[:, None]
+        A = np.stack([u[:, 0] ** 2, u[:, 1] ** 2, u[:, 2] ** 2, 2 * u[:, 0] * u[:, 1], 2 * u[:, 0] * u[:, 2], 2 * u[:, 1] * u[:, 2]], axis=1)
+        t = np.linalg.lstsq(A, 1.0 / mil[has] ** 2, rcond=None)[0]
+        M = np.array([[t[0], t[3], t[4]], [t[3], t[1], t[5]], [t[4], t[5], t[2]]])
+        lam, vec = np.linalg.eigh(M)                                         # ascending: the longest intercept first
+        if not lam[0] > 0:
+            raise ValueError("the fitted fabric tensor is not positive definite")
+        axes = vec.T.copy()
+        for row in axes:
+            if row[np.argmax(np.abs(row))] < 0:
+                row *= -1.0
+        return {"tensor": M, "principal_mil_mm": 1.0 / np.sqrt(lam), "axes": axes,
+                "degree_of_anisotropy": float(1.0 - lam[0] / lam[-1]), "directions_used": int(has.sum())}
+
+
+def chord_lengths_from_tables(tables, slices, steps, shape, spacing) -> ChordLengths:
+    """ChordLengths of the integer tables (3, 13, L + 1), the voxels per slice (nz,) and chord_steps: the host half of
+    chord_lengths.  total_length_mm comes from the slice counts, not from sum_q: one checks the other."""
+    counts, border, sum_q = (np.ascontiguousarray(t, dtype=np.int64) for t in tables)
+    slices = np.asarray(slices, dtype=np.int64)
+    chords = counts.sum(axis=1)
+    total = np.zeros(CHORD_DIRECTIONS, dtype=np.float64)
+    for k in range(len(slices)):                                             # sequential float64, ascending k
+        total = total + float(slices[k]) * steps[k]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = np.where(chords > 0, total / chords.astype(np.float64), np.nan)
+    return ChordLengths(chord_directions(), counts, border, sum_q, steps, int(slices.sum()), chords, total, mean,
+                        tuple(int(s) for s in shape), tuple(float(s) for s in spacing))
+
+
+def chord_lengths(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, phase="object") -> ChordLengths:
+    """The chord lengths of a resident volume along the 13 lattice directions (chord_directions()) -> ChordLengths: how far one
+    can go through the structure in a straight line, and which way it runs -- for the volume as a whole, without labelling.
+    A chord is a maximal straight sequence of set voxels; everything outside the stack is background, and a chord that ends
+    at a face of the stack is filed in `border` as well (include/tomo_hip.h has the definitions).  The spacing is
+    distance_transform's (slice_depths=None: 1.0 per slice); the lengths in mm are sums of chord_steps in units of 2^-16 mm,
+    integer atomics only: the same bytes on every run.  phase="background" measures the pore space: the same kernel on the
+    complement inside the stack, where the chords cut by the stack are exactly the border chords.  One call of
+    tomo_chord_hist (plus the complement's launch for the background) and the popcount per slice, one host read."""
+    if phase not in CHORD_PHASES:
+        raise ValueError("phase must be one of %s" % (CHORD_PHASES,))
+    nz, ny, nx = vol.shape
+    steps = chord_steps(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x)
+    d_mean = 1.0 if slice_depths is None else float(np.mean(np.asarray(slice_depths, dtype=np.float64)))
+    L, dev, st = _lib.lib(), vol.device, _stream()
+    bits = vol.bits.contiguous()
+    if phase == "background":
+        outside = torch.empty_like(bits)
+        _lib.check(L.tomo_cc_complement(_p(bits), nz, ny, nx, _p(outside), st), "tomo_cc_complement")
+        bits = outside
+    lmax = max(nz, ny, nx)
+    cells = CHORD_DIRECTIONS * (lmax + 1)
+    out = torch.zeros(3 * cells + nz, dtype=torch.int64, device=dev)         # the three tables and the slice counts: one read
+    tab = torch.from_numpy(chord_steps_q(steps)).to(dev)
+    COUNTERS["chord_lengths"] += 1
+    _lib.check(L.tomo_chord_hist(_p(bits), nz, ny, nx, _p(tab), lmax, _p(out), _p(out[cells:]), _p(out[2 * cells:]), st),
+               "tomo_chord_hist")
+    _lib.check(L.tomo_slice_popcounts(_p(bits), nz, ny, nx, _p(out[3 * cells:]), st), "tomo_slice_popcounts")
+    host = out.cpu().numpy()
+    return chord_lengths_from_tables(host[:3 * cells].reshape(3, CHORD_DIRECTIONS, lmax + 1), host[3 * cells:], steps, vol.shape,
+                               (d_mean, float(mm_per_pixel_y), float(mm_per_pixel_x)))
 
 
 # ----------------------------------------------------------------------------- Euclidean distance in millimetres

@@ -192,6 +192,46 @@ def minkowski_functionals(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_dept
                                                breadth_directions=directions)}
 
 
+CHORD_QUANTILES = (0.1, 0.5, 0.9)
+
+
+def _chord_phase_report(c):
+    """The dict of one phase of chord_report from a pipeline.ChordLengths."""
+    total = int(c.chords.sum())
+    try:
+        f = c.fabric()
+        fabric = {'tensor': f['tensor'].tolist(), 'principal_mil_mm': f['principal_mil_mm'].tolist(), 'axes': f['axes'].tolist(),
+                  'degree_of_anisotropy': f['degree_of_anisotropy']}
+    except ValueError:                                           # chords in fewer than six directions, or no ellipsoid fits
+        fabric = None
+    return {'voxels': c.voxels, 'chords': c.chords.tolist(), 'mil_mm': c.mean_chord_mm.tolist(),
+            'mean_chord_mm': float(np.sum(c.total_length_mm) / total) if total else float('nan'),
+            'fabric': fabric, 'lineal_path': c.lineal_path(),
+            'quantiles_mm': {'fractions': CHORD_QUANTILES, 'values': c.quantiles_mm(CHORD_QUANTILES)}}
+
+
+def chord_report(voxel_data, slice_depths, mm_per_pixel_y, mm_per_pixel_x, background=True):
+    """Which way the structure runs and how far one can go through it in a straight line (no counterpart in the reference):
+    the chord lengths of the volume as a whole along the 13 lattice directions (pipeline.chord_lengths: no labelling, per-slice
+    depths honoured, everything outside the stack is background) -> {'directions': the 13 steps (dz, dy, dx), 'object': {...},
+    'background': {...} or None with background=False}.  A phase holds 'voxels', 'chords' and 'mil_mm' per direction (the mean
+    intercept length: Tb.Th / Tb.Sp by intercepts, the chord-length pore size), 'mean_chord_mm' over all directions, 'fabric'
+    (pipeline.ChordLengths.fabric as lists: 'tensor', 'principal_mil_mm', 'axes', 'degree_of_anisotropy'; None where fewer than
+    six directions have a chord or no ellipsoid fits), 'lineal_path' float64 (13, L + 1) and 'quantiles_mm': the 10 / 50 / 90 %
+    quantiles of the chord length per direction by number of chords, float64 (13, 3).  One upload serves both phases.
+    voxel_data: the bool (nz, ny, nx) array the other calculations take; anything else is a TypeError -- there is no host path
+    for this one."""
+    if not _on_device(voxel_data):
+        raise TypeError("chord_report needs a bool (nz, ny, nx) array")
+    depths = np.asarray(slice_depths, dtype=np.float64).reshape(-1)
+    pipeline.chord_steps(depths, voxel_data.shape[0], mm_per_pixel_y, mm_per_pixel_x)                   # the argument checks
+    vol = to_device_volume(voxel_data)
+    report = {'directions': [tuple(int(v) for v in s) for s in pipeline.chord_directions()], 'background': None}
+    for phase in pipeline.CHORD_PHASES if background else pipeline.CHORD_PHASES[:1]:
+        report[phase] = _chord_phase_report(pipeline.chord_lengths(vol, depths, mm_per_pixel_y, mm_per_pixel_x, phase))
+    return {key: report[key] for key in ('directions', 'object', 'background')}
+
+
 def closed_porosity(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=6, min_voxels=0, max_voxels=None,
                     pore_size=False, pore_geodesic=False, pore_caliper=False):
     """The enclosed voids of the volume, listed and added up (no counterpart in the reference): pipeline.cavity_table -- a
