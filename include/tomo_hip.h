@@ -780,6 +780,31 @@ int tomo_profile_rows(const int64_t *table, const uint32_t *lo, const uint32_t *
  * TOMO_E_ARG for a null pointer, a non-positive size or lmax < max(nz, ny, nx); TOMO_E_SIZE from 2^31 words on. */
 int tomo_chord_hist(const uint64_t *bits, int nz, int ny, int nx, const int64_t *steps_q, int64_t lmax, int64_t *counts,
                     int64_t *border, int64_t *sum_q, void *stream);
+/* The two-point covariance of the volume as a whole (csrc/two_point.hip; no counterpart in the reference): S2(h), the chance
+ * that two points a lag h apart both lie in the phase -- volume fraction, specific surface (the slope at the origin), correlation
+ * length and its anisotropy, periodicity, the input of stochastic reconstruction.  No labelling.  One definition.
+ * LAG: h = (hz, hy, hx), integers, over the box hz in [0, rz], hy in [-ry, ry], hx in [-rx, rx]; the half space suffices because
+ * N(-h) = N(h).
+ * COUNT: pairs[hz][hy + ry][hx + rx] = N(h) = #{p : p set, p + h set, both inside the stack}, int64 (rz + 1, 2 ry + 1, 2 rx + 1),
+ * zeroed here.  No wrap-around and nothing outside the stack takes part: the non-periodic estimator.  N(0) is the popcount.  A
+ * lag whose component reaches the size of its axis (hz >= nz, |hy| >= ny, |hx| >= nx) reads 0.  The plane hz = 0 holds both h and
+ * -h and comes out point-symmetric; the kernel computes the whole box and mirrors nothing.
+ * DENOMINATOR (host, closed form): P(h) = max(0, nz - hz) max(0, ny - |hy|) max(0, nx - |hx|), the pairs of voxels of the stack a
+ * lag h apart; S2(h) = N(h) / P(h), NaN where P = 0; S2(0) is the volume fraction.
+ * LIMITS: every r >= 0; rx <= 63 (a shifted word then comes from a word and one neighbour); rz <= nz - 1, ry <= ny - 1 and
+ * rx <= nx - 1 are NOT required.  The callers keep words * lags within a work budget (pipeline.TWO_POINT_WORK_BUDGET = 2^42).
+ * TAIL BITS of the input are never trusted (cc_word / cc_word_or0 of cc_runs.h).  Integer adds only: the same bytes on every run
+ * and under every grid.  The table is a function of index lags alone: the spacing and the slice depths enter on the host.
+ *   tomo_two_point  grid (planes (hz, hy) that can hold a pair, chunks of the word space), 256 threads: a thread takes word A of
+ *                   row (k, j) and the words Bm, B0, Bp of the partner row (k + hz, j + hy), skipped outside the stack, and adds
+ *                   popcount(A & shift(B, hx)) for every hx of a variant RX in {8, 16, 32, 63}, the smallest >= rx, to 2 RX + 1
+ *                   32-bit accumulators in registers (the loop over hx unrolled when compiled: immediate shifts, static
+ *                   indices); a wave whose A words are all zero skips the word.  At the end one wave sum per accumulator, the wave
+ *                   sums combined in LDS, ONE 64-bit add per workgroup and lag of the box.  A chunk has at most 2^24 words, so a
+ *                   workgroup's sum stays below 2^30 and no 32-bit sum can wrap.
+ * TOMO_E_ARG for a null pointer, a non-positive size, a negative r or rx > 63; TOMO_E_SIZE from 2^31 words on or for a table of
+ * 2^31 entries or more.  A refused call writes nothing. */
+int tomo_two_point(const uint64_t *bits, int nz, int ny, int nx, int rz, int ry, int rx, int64_t *pairs, void *stream);
 /* The contact table between zones (csrc/contacts.hip; no counterpart in the reference): which zones touch, over how large an
  * interface, how wide the throat between them is and how long the way across.  One definition.
  * zones: int32 (nz, ny, nx), tomo_zone_sweep's map or any map.  A voxel TAKES PART when it is set and its entry is positive.

@@ -32,7 +32,7 @@ COUNTERS = dict.fromkeys(("na_hint_hit", "na_hint_miss", "mc3_hint_hit", "mc3_hi
                           "thin_calls", "thin_iterations", "thin_passes", "thin_nodes", "component_skeleton",
                           "skeleton_branches", "branch_split", "skeleton_branches_hist", "branch_attach", "branch_lookup", "branch_clear",
                           "prune_rounds", "components_profile", "branch_profile", "prune_relative", "components_breadth",
-                          "chord_lengths"), 0)
+                          "chord_lengths", "two_point"), 0)
 NA_HINTS = os.environ.get("TOMO_NA_HINTS", "1") not in ("", "0")   # marching_cubes: launch ahead of the first count download
 _NA_HINT = {}
 LIST_LIMIT = 2 ** 31        # active-voxel list entries / vertices / triangles one pass can index (int32 offsets in mc.hip, mesh.hip);
@@ -1673,6 +1673,228 @@ def chord_lengths(vol: BitVolume, slice_depths=None, mm_per_pixel_y=1.0, mm_per_
     host = out.cpu().numpy()
     return chord_lengths_from_tables(host[:3 * cells].reshape(3, CHORD_DIRECTIONS, lmax + 1), host[3 * cells:], steps, vol.shape,
                                (d_mean, float(mm_per_pixel_y), float(mm_per_pixel_x)))
+
+
+# ----------------------------------------------------------------------------- the two-point covariance over a box of lags
+TWO_POINT_WORK_BUDGET = 1 << 42      # words * lags one call may ask for: admits 1024^3 at (32, 32, 32), refuses it at (64, 64, 63)
+TWO_POINT_MAX_RX = 63                # csrc/two_point.hip: a shifted word comes from a word and one neighbour
+TWO_POINT_TABLE_LIMIT = 1 << 31      # entries of the table (tomo_two_point: TOMO_E_SIZE from there on)
+
+
+def two_point_box(max_lag) -> tuple:
+    """max_lag of two_point -> (Rz, Ry, Rx): an int stands for all three.  Integers >= 0, Rx <= 63; anything else is a
+    ValueError naming max_lag (an int above 63 too: the box is never shrunk behind the caller's back)."""
+    box = (max_lag,) * 3 if isinstance(max_lag, (int, np.integer)) and not isinstance(max_lag, (bool, np.bool_)) else max_lag
+    try:
+        box = tuple(box)
+    except TypeError:
+        raise ValueError("max_lag must be an int or (Rz, Ry, Rx), not %r" % (max_lag,)) from None
+    if len(box) != 3 or any(isinstance(r, (bool, np.bool_)) or not isinstance(r, (int, np.integer)) for r in box):
+        raise ValueError("max_lag must be an int or three ints (Rz, Ry, Rx), not %r" % (max_lag,))
+    box = tuple(int(r) for r in box)
+    if min(box) < 0:
+        raise ValueError("max_lag must not be negative: %r" % (box,))
+    if box[2] > TWO_POINT_MAX_RX:
+        raise ValueError("max_lag along x is at most %d (a shifted word comes from a word and one neighbour): %r" % (TWO_POINT_MAX_RX, box))
+    return box
+
+
+@dataclass
+class TwoPoint:
+    """two_point's answer: the integer table of pair counts over the box of lags and what the host needs to read it.  Lag
+    h = (hz, hy, hx) sits at [hz, hy + Ry, hx + Rx]; the half space hz >= 0 suffices because N(-h) = N(h).  Every method is NumPy
+    on the integers with one pinned order of operations."""
+    pairs: np.ndarray            # int64 (Rz + 1, 2 Ry + 1, 2 Rx + 1): N(h), the voxel pairs a lag h apart that both lie in the phase
+    max_lag: tuple               # (Rz, Ry, Rx)
+    shape: tuple                 # (nz, ny, nx)
+    spacing: tuple               # (mean slice depth, mm_y, mm_x)
+    voxels: int                  # voxels of the phase: N(0)
+    phase: str
+    z_lag_mm: np.ndarray         # float64 (Rz + 1,): the mean separation in mm of two slices hz apart; NaN from hz = nz on
+
+    def _lags(self):
+        rz, ry, rx = self.max_lag
+        return (np.arange(rz + 1, dtype=np.int64)[:, None, None], np.arange(-ry, ry + 1, dtype=np.int64)[None, :, None],
+                np.arange(-rx, rx + 1, dtype=np.int64)[None, None, :])
+
+    def inside(self) -> np.ndarray:
+        """P(h), the voxel pairs of the stack a lag h apart -> int64 box: max(0, nz - hz) * max(0, ny - |hy|) * max(0, nx - |hx|)."""
+        hz, hy, hx = self._lags()
+        nz, ny, nx = self.shape
+        return np.maximum(0, nz - hz) * np.maximum(0, ny - np.abs(hy)) * np.maximum(0, nx - np.abs(hx))
+
+    def s2(self) -> np.ndarray:
+        """The two-point probability S2(h) = N(h) / P(h) -> float64 box, NaN where P = 0.  S2(0) is the volume fraction."""
+        P = self.inside()
+        out = np.full(P.shape, np.nan, dtype=np.float64)
+        np.divide(self.pairs.astype(np.float64), P.astype(np.float64), out=out, where=P > 0)
+        return out
+
+    def volume_fraction(self) -> float:
+        """S2(0) = N(0) / (nz ny nx)."""
+        return float(self.voxels) / float(self.shape[0] * self.shape[1] * self.shape[2])
+
+    def covariance(self) -> np.ndarray:
+        """S2(h) - phi * phi, phi = S2(0) -> float64 box."""
+        phi = self.volume_fraction()
+        return self.s2() - phi * phi
+
+    def correlation(self) -> np.ndarray:
+        """covariance() / (phi - phi * phi) -> float64 box: 1 at h = 0, 0 where the two points are independent.  All NaN for an
+        empty or a full phase."""
+        phi = self.volume_fraction()
+        var = phi - phi * phi
+        if not var > 0.0:
+            return np.full(self.pairs.shape, np.nan, dtype=np.float64)
+        return self.covariance() / var
+
+    def lag_mm(self) -> np.ndarray:
+        """The length of every lag in mm -> float64 box: sqrt(((zbar(hz))^2 + (hy mm_y)^2) + (hx mm_x)^2), zbar = z_lag_mm: the
+        mean of zc[k + hz] - zc[k] over the nz - hz slice pairs, summed in ascending k, zc the slice centres of
+        distance_positions.  Exact under uniform depths.  Under varying depths the table is a covariance in INDEX lags and this
+        is the mean separation of the pairs a lag stands for, not a distance every pair has.  NaN from hz = nz on."""
+        hz, hy, hx = self._lags()
+        _, mm_y, mm_x = self.spacing
+        return np.sqrt((self.z_lag_mm[:, None, None] ** 2 + (hy * mm_y) ** 2) + (hx * mm_x) ** 2)
+
+    def _along(self, box):
+        """The values of a box at r * s for the 13 steps s of chord_directions(), r = 0 .. max(max_lag) -> float64 (13, R + 1),
+        NaN where r * s leaves the box."""
+        rz, ry, rx = self.max_lag
+        R = max(self.max_lag)
+        out = np.full((CHORD_DIRECTIONS, R + 1), np.nan, dtype=np.float64)
+        for m, (dz, dy, dx) in enumerate(_BREADTH_NORMALS):
+            for r in range(R + 1):
+                if r * dz <= rz and abs(r * dy) <= ry and abs(r * dx) <= rx:
+                    out[m, r] = box[r * dz, r * dy + ry, r * dx + rx]
+        return out
+
+    def directional(self) -> np.ndarray:
+        """S2 along the 13 steps of chord_directions() -> float64 (13, R + 1), R = max(max_lag): S2 at the lag r * s; NaN where
+        r * s leaves the box or P = 0."""
+        return self._along(self.s2())
+
+    def correlation_length_mm(self) -> np.ndarray:
+        """Where correlation() first falls below 1 / e along each of the 13 directions -> float64 (13,): between the last lag
+        r - 1 at or above and the first lag r below, d[r - 1] + (c[r - 1] - 1 / e) / (c[r - 1] - c[r]) * (d[r] - d[r - 1]) with d
+        = lag_mm() there.  NaN if no crossing lies inside the box (or a NaN comes first)."""
+        c, d = self._along(self.correlation()), self._along(self.lag_mm())
+        level = 1.0 / math.e
+        out = np.full(CHORD_DIRECTIONS, np.nan, dtype=np.float64)
+        for m in range(CHORD_DIRECTIONS):
+            for r in range(1, c.shape[1]):
+                if not (np.isfinite(c[m, r]) and np.isfinite(c[m, r - 1])):
+                    break
+                if c[m, r] < level <= c[m, r - 1]:
+                    out[m] = d[m, r - 1] + (c[m, r - 1] - level) / (c[m, r - 1] - c[m, r]) * (d[m, r] - d[m, r - 1])
+                    break
+        return out
+
+    def radial(self, bin_mm) -> tuple:
+        """The orientation average -> (centres float64 (n,), values float64 (n,), lags int64 (n,)): shell i holds the lags with
+        floor(lag_mm / bin_mm + 0.5) == i and P > 0, its centre is i * bin_mm, its value sum(w N) / sum(w P) with w = 2 for
+        hz > 0 (the lag stands for -h as well) and w = 1 in the plane hz = 0 (which holds both), `lags` the sum of w.  A shell
+        without a lag reads NaN.  Shell 0 holds h = 0 at least: its value is the volume fraction when bin_mm is below the
+        smallest spacing."""
+        bin_mm = _positive(bin_mm, "bin_mm")
+        P = self.inside()
+        d = self.lag_mm()
+        ok = (P > 0) & np.isfinite(d)
+        shell = np.floor(d[ok] / bin_mm + 0.5).astype(np.int64)
+        w = np.where(self._lags()[0] > 0, 2, 1).astype(np.int64) * np.ones(P.shape, dtype=np.int64)
+        n = int(shell.max()) + 1 if shell.size else 0
+        num, den, lags = (np.zeros(n, dtype=np.int64) for _ in range(3))
+        np.add.at(num, shell, (w * self.pairs)[ok])
+        np.add.at(den, shell, (w * P)[ok])
+        np.add.at(lags, shell, w[ok])
+        values = np.full(n, np.nan, dtype=np.float64)
+        np.divide(num.astype(np.float64), den.astype(np.float64), out=values, where=den > 0)
+        return np.arange(n, dtype=np.float64) * bin_mm, values, lags
+
+    def specific_surface_per_mm(self) -> float:
+        """The surface per volume of the stack in 1 / mm: 4 * sum over the 13 steps s_m, in their order, of c_m * (S2(0) -
+        S2(s_m)) / |s_m|, |s_m| = sqrt(((dz h)^2 + (dy mm_y)^2) + (dx mm_x)^2) and c_m the weight of the step's class in
+        crofton_weights(mm_x, mm_y, h), h the mean slice depth.  The slope of S2 at the origin read as Crofton's intersection
+        count: 2 (N(0) - N(s)) is the object / background transitions along +-s that surface_area counts for a body clear of
+        the faces.  The estimator of a structure that fills the stack (a foam, a bed, a rock): S2(s) = N(s) / P(s) corrects for
+        the pairs the faces cut, so for ONE body in an otherwise empty stack it is not that body's surface over the stack's
+        volume -- take 4 sum c_m (N(0) - N(s_m)) / |s_m| from `pairs` there, or surface_area.  Needs every R >= 1 (ValueError);
+        NaN where an axis has one voxel."""
+        if min(self.max_lag) < 1:
+            raise ValueError("specific_surface_per_mm needs max_lag >= 1 along every axis, not %r" % (self.max_lag,))
+        h, mm_y, mm_x = self.spacing
+        c = crofton_weights(mm_x, mm_y, h, 13)
+        s2 = self.directional()
+        total = 0.0
+        for m, (dz, dy, dx) in enumerate(_BREADTH_NORMALS):
+            cls = _SURFACE_CLASS_STEPS.index((abs(dz), abs(dy), abs(dx)))
+            total = total + c[cls] * (s2[m, 0] - s2[m, 1]) / math.sqrt(((dz * h) ** 2 + (dy * mm_y) ** 2) + (dx * mm_x) ** 2)
+        return float(4.0 * total)
+
+
+def two_point_z_lags(slice_depths, nz, rz) -> np.ndarray:
+    """zbar(hz), hz = 0 .. rz -> float64 (rz + 1,): the mean of zc[k + hz] - zc[k] over k = 0 .. nz - hz - 1, summed in
+    ascending k, zc the slice centres of distance_positions (slice_depths=None: 1.0 per slice); NaN from hz = nz on."""
+    zc = distance_positions(slice_depths, nz)[0][1:-1]
+    out = np.full(int(rz) + 1, np.nan, dtype=np.float64)
+    for hz in range(min(int(rz), len(zc) - 1) + 1):
+        total = 0.0
+        for k in range(len(zc) - hz):
+            total = total + (zc[k + hz] - zc[k])
+        out[hz] = total / float(len(zc) - hz)
+    return out
+
+
+def two_point_from_table(pairs, max_lag, shape, spacing, phase, slice_depths=None) -> TwoPoint:
+    """TwoPoint of an integer table: the host half of two_point (pure NumPy; a caller with a table of its own can use it).
+    spacing: (mean slice depth, mm_y, mm_x); slice_depths=None: every slice as deep as the mean."""
+    box = two_point_box(max_lag)
+    shape = tuple(int(s) for s in shape)
+    spacing = tuple(float(s) for s in spacing)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int64)
+    if pairs.shape != (box[0] + 1, 2 * box[1] + 1, 2 * box[2] + 1):
+        raise ValueError("the table of max_lag %r is %r, not %r" % (box, (box[0] + 1, 2 * box[1] + 1, 2 * box[2] + 1), pairs.shape))
+    if phase not in CHORD_PHASES:
+        raise ValueError("phase must be one of %s" % (CHORD_PHASES,))
+    depths = np.full(shape[0], spacing[0]) if slice_depths is None else slice_depths
+    return TwoPoint(pairs, box, shape, spacing, int(pairs[0, box[1], box[2]]), phase, two_point_z_lags(depths, shape[0], box[0]))
+
+
+def two_point(vol: BitVolume, max_lag=16, slice_depths=None, mm_per_pixel_y=1.0, mm_per_pixel_x=1.0, phase="object") -> TwoPoint:
+    """The two-point covariance of a resident volume over the box of integer lags hz in [0, Rz], hy in [-Ry, Ry], hx in
+    [-Rx, Rx] (max_lag: an int or (Rz, Ry, Rx), Rx <= 63) -> TwoPoint: pairs[hz, hy + Ry, hx + Rx] = the voxel pairs a lag h
+    apart that both lie in the phase and inside the stack -- no wrap-around, the non-periodic estimator; a lag that reaches
+    the size of its axis reads 0 (include/tomo_hip.h has the definition).  From the integers, on the host: S2 = N / P, the
+    covariance, the correlation and its length per direction, the radial average, the specific surface.  The table is a
+    function of index lags alone; the spacing (distance_transform's; slice_depths=None: 1.0 per slice) enters on the host.
+    phase="background" measures the pore space: the same kernel on the complement inside the stack.  words * lags beyond
+    TWO_POINT_WORK_BUDGET, or a table of 2^31 entries or more, is a ValueError before anything is allocated.  Integer adds
+    only: the same bytes on every run.  One call of tomo_two_point (plus the complement's launch), one host read."""
+    if phase not in CHORD_PHASES:
+        raise ValueError("phase must be one of %s" % (CHORD_PHASES,))
+    rz, ry, rx = two_point_box(max_lag)
+    nz, ny, nx = vol.shape
+    distance_positions(slice_depths, nz, mm_per_pixel_y, mm_per_pixel_x)                              # the argument checks
+    d_mean = 1.0 if slice_depths is None else float(np.mean(np.asarray(slice_depths, dtype=np.float64)))
+    cells = (rz + 1) * (2 * ry + 1) * (2 * rx + 1)
+    words = nz * ny * ((nx + 63) // 64)
+    if cells >= TWO_POINT_TABLE_LIMIT:
+        raise ValueError("max_lag %r asks for a table of %d entries; fewer than 2^31 can be served" % ((rz, ry, rx), cells))
+    if words * cells > TWO_POINT_WORK_BUDGET:
+        raise ValueError("max_lag %r on %r is %d words * %d lags, beyond TWO_POINT_WORK_BUDGET = %d: take a smaller max_lag"
+                         % ((rz, ry, rx), tuple(vol.shape), words, cells, TWO_POINT_WORK_BUDGET))
+    L, dev, st = _lib.lib(), vol.device, _stream()
+    bits = vol.bits.contiguous()
+    if phase == "background":
+        outside = torch.empty_like(bits)
+        _lib.check(L.tomo_cc_complement(_p(bits), nz, ny, nx, _p(outside), st), "tomo_cc_complement")
+        bits = outside
+    out = torch.empty(cells, dtype=torch.int64, device=dev)                  # zeroed by the call itself
+    COUNTERS["two_point"] += 1
+    _lib.check(L.tomo_two_point(_p(bits), nz, ny, nx, rz, ry, rx, _p(out), st), "tomo_two_point")
+    host = out.cpu().numpy().reshape(rz + 1, 2 * ry + 1, 2 * rx + 1)
+    depths = np.ones(nz) if slice_depths is None else np.asarray(slice_depths, dtype=np.float64).reshape(-1)
+    return two_point_from_table(host, (rz, ry, rx), vol.shape, (d_mean, float(mm_per_pixel_y), float(mm_per_pixel_x)), phase, depths)
 
 
 # ----------------------------------------------------------------------------- Euclidean distance in millimetres

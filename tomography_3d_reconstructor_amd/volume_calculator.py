@@ -232,6 +232,46 @@ def chord_report(voxel_data, slice_depths, mm_per_pixel_y, mm_per_pixel_x, backg
     return {key: report[key] for key in ('directions', 'object', 'background')}
 
 
+def _two_point_phase_report(t):
+    """The dict of one phase of two_point_report from a pipeline.TwoPoint."""
+    centres, values, lags = t.radial(max(t.spacing))
+    return {'volume_fraction': t.volume_fraction(),
+            'specific_surface_per_mm': t.specific_surface_per_mm() if min(t.max_lag) >= 1 else None,
+            'correlation_length_mm': t.correlation_length_mm().tolist(), 'directional': t.directional(),
+            'radial': {'bin_mm': max(t.spacing), 'centres_mm': centres, 'values': values, 'lags': lags}}
+
+
+def two_point_report(voxel_data, slice_depths, mm_per_pixel_y, mm_per_pixel_x, max_lag=16, background=True):
+    """How the structure is correlated with itself (no counterpart in the reference): the two-point probability S2(h) of the
+    volume as a whole over the box of integer lags max_lag (an int or (Rz, Ry, Rx), Rx <= 63; pipeline.two_point: no
+    labelling, no wrap-around, the spacing enters on the host) -> {'max_lag': (Rz, Ry, Rx), 'object': {...}, 'background':
+    {...} or None with background=False, 'cross'}.  A phase holds 'volume_fraction' (S2(0)), 'specific_surface_per_mm' (the
+    slope at the origin by Crofton's weights; None unless every R >= 1), 'correlation_length_mm' per direction of
+    pipeline.chord_directions() (where the correlation first falls below 1 / e; NaN if not inside the box), 'directional'
+    float64 (13, R + 1) (S2 along those directions) and 'radial': the orientation average in shells of 'bin_mm' = the largest
+    spacing, 'centres_mm', 'values', 'lags'.  'cross': the symmetrised chance that of two points a lag apart ONE lies in the object
+    and one in the background, (P - N_object - N_background) / (2 P) as a float64 table over the box, NaN where P = 0; None
+    without the background.  One upload serves both phases.  voxel_data: the bool (nz, ny, nx) array the other calculations
+    take; anything else is a TypeError -- there is no host path for this one."""
+    if not _on_device(voxel_data):
+        raise TypeError("two_point_report needs a bool (nz, ny, nx) array")
+    depths = np.asarray(slice_depths, dtype=np.float64).reshape(-1)
+    pipeline.distance_positions(depths, voxel_data.shape[0], mm_per_pixel_y, mm_per_pixel_x)            # the argument checks
+    box = pipeline.two_point_box(max_lag)
+    vol = to_device_volume(voxel_data)
+    tables = {phase: pipeline.two_point(vol, box, depths, mm_per_pixel_y, mm_per_pixel_x, phase)
+              for phase in (pipeline.CHORD_PHASES if background else pipeline.CHORD_PHASES[:1])}
+    report = {'max_lag': box, 'object': _two_point_phase_report(tables['object']), 'background': None, 'cross': None}
+    if background:
+        report['background'] = _two_point_phase_report(tables['background'])
+        P = tables['object'].inside()
+        cross = np.full(P.shape, np.nan, dtype=np.float64)
+        np.divide((P - tables['object'].pairs - tables['background'].pairs).astype(np.float64), (2 * P).astype(np.float64), out=cross,
+                  where=P > 0)
+        report['cross'] = cross
+    return report
+
+
 def closed_porosity(voxel_data, mm_per_pixel_x, mm_per_pixel_y, slice_depths, connectivity=6, min_voxels=0, max_voxels=None,
                     pore_size=False, pore_geodesic=False, pore_caliper=False):
     """The enclosed voids of the volume, listed and added up (no counterpart in the reference): pipeline.cavity_table -- a
